@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- OFDM frames/s of the AdaFortiTran forward path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3|C2|C5] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3|C2|C5] [--batch B] [--dump-outputs DIR]
 
 ``--gpus N`` with N > 1 and no torchrun environment: this process touches no GPU, starts
 ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`` on
@@ -29,6 +29,10 @@ parity (vs the oracle, bounded sample) . configs (C1, the other default model, C
 training step, ingest, evaluation sweep, LS baseline) . split_precision (the opt-in bf16x3 tier, reported
 separately, never `value`) . cpu_baseline (the reference-equivalent CPU path on this box's host cores).
 
+``--dump-outputs DIR``: after the timed steps, what the last of them returned to the caller (rank 0's estimate) goes to
+``DIR/estimate.npy`` as float32 [B, S, T, 2] (re, im); inputs and weights are seeded, so two builds run with the same arguments
+can be compared output for output.  Above 64 MB a seeded sample of frames is written, their indices in ``DIR/frames.npy``.
+
 ``--stub`` (tests only, tests/test_bench_cli.py): the N-rank control flow with the GPU work replaced by
 CPU sleeps over gloo -- prints ``"data": "stub"`` and measures nothing.
 """
@@ -50,6 +54,7 @@ PEAK_FP32_MFMA_TFLOPS = 157.3   # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 / 
 PEAK_HBM_GBS = 8000.0           # MI355X_MICROARCH.md: HBM3E 8 TB/s (spec)
 SEED = 20251114
 PREWARM_STEPS = 300             # untimed device spin-up before the W warm-up steps (~0.5 s; reported as `prewarm_steps`)
+DUMP_BUDGET_BYTES = 64 << 20    # --dump-outputs: at most this much in all; a larger output is dumped as a seeded sample of frames
 
 C3 = dict(name="C3", model="adafortitran", ofdm=(120, 14), pilot=(12, 2), patch=(3, 2), num_layers=6, model_dim=128,
           num_head=4, hidden=(7, 42, 560), max_seq_len=512, batch=128,
@@ -211,6 +216,7 @@ class Workload:
         with torch.no_grad():
             est = self.model(self.pil_cpu, self.meta_cpu) if self.adaptive else self.model(self.pil_cpu)
         self.acc.update(est, self.tgt)
+        self.last = est                                  # what the caller received (--dump-outputs)
         return est
 
     def forward(self):
@@ -252,6 +258,8 @@ class StubWorkload:
 
     def surface_step(self):
         self.step()
+        self.last = self.out
+        return self.out
 
     def forward(self):
         time.sleep(self.sleep)
@@ -768,6 +776,32 @@ def cpu_baseline(wl):
     return out
 
 
+def dump_outputs(path, arrays, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: each array as PATH/<name>.npy, float32 (float64 stays float64), a complex array as [..., 2] = (re, im).
+    Over `budget` bytes in all, every array keeps the same seeded sample of its leading (frame) axis, in order, and the frame
+    indices go to PATH/frames.npy (float64).  Returns {name: shape written}."""
+    import numpy as np
+    import torch
+    out = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        if t.is_complex():
+            t = torch.view_as_real(t.resolve_conj())
+        a = t.numpy()
+        out[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+    total = sum(a.nbytes for a in out.values())
+    if total > budget:
+        n = min(a.shape[0] for a in out.values())
+        keep = max(1, int(n * (budget - 8 * n) // total))
+        rows = np.sort(np.random.default_rng(SEED).choice(n, size=keep, replace=False))
+        out = {k: a[rows] for k, a in out.items()}
+        out["frames"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+    return {k: list(a.shape) for k, a in out.items()}
+
+
 def load_pmc_traffic():
     """HBM bytes per chain-kernel launch from the committed rocprofv3 --pmc summary (a constant of the committed
     profile -- profiles/pmc_traffic.json: FETCH_SIZE x2 gfx950 correction + WRITE_SIZE -- not something this run observed)."""
@@ -789,12 +823,17 @@ def main() -> int:
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--headline-only", action="store_true", help="skip the N=1 legs (module surface, configs, parity, next rows, CPU)")
     ap.add_argument("--verbose-json", default="", help="also write the annotated record to this path")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed step returned "
+                    "(rank 0's estimate, float32 [B,S,T,2] = re, im) as DIR/estimate.npy, at most 64 MB (a seeded sample of frames beyond)")
     ap.add_argument("--stub", action="store_true", help="tests only: control flow on CPU/gloo, measures nothing")
     ap.add_argument("--share-gpu", action="store_true", help="tests only: every rank on device 0, collectives over gloo (RCCL refuses two "
                     "ranks on one device); runs the N-rank path with the real kernels on a 1-GPU box, the numbers mean nothing")
     args = ap.parse_args()
     if args.gpus < 1:
         print("bench.py: --gpus must be >= 1", file=sys.stderr)
+        return 2
+    if args.steps < 1 or args.warmup < 0:
+        print("bench.py: --steps must be >= 1 and --warmup >= 0", file=sys.stderr)
         return 2
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return self_launch(args, sys.argv[1:])
@@ -853,6 +892,7 @@ def main() -> int:
     wl.acc.sum_sq.zero_()
     wl.acc.n_elements = 0
     elapsed_local, dev_ms, per_step = timed_steps(wl, wl.surface_step, args.steps, 0, fence)
+    dumped = dump_outputs(args.dump_outputs, {"estimate": wl.last}) if args.dump_outputs and rank == 0 else None
     pct = lambda q: per_step[min(len(per_step) - 1, int(q * len(per_step)))]   # noqa: E731
     elapsed, per_rank = elapsed_local, None
     if dist is not None:
@@ -930,6 +970,8 @@ def main() -> int:
         }
         if per_rank is not None:
             result["per_rank"] = per_rank
+        if dumped is not None:
+            result["dumped_outputs"] = dumped
         if not args.stub:
             result["config"]["lanes"] = lanes_of(wl.eng, B)    # launch sequences the timed forward ran as (1 at the stated batches)
             kernels, roof, enc_util, t_flow, fl, ups = kernel_report(wl, 20)

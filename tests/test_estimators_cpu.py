@@ -148,7 +148,8 @@ def test_cpu_standin_is_pinned():
     """bench.py's cpu_baseline times THIS package's CPU composite in place of the reference (which cannot travel to the
     GPU box).  tests/golden/pin_cpu_standin.py measured both side by side in the build container (B = 128, identical
     weights / inputs, interleaved rounds): outputs bit-identical, forward time within +-5 %.
-    The recorded facts are asserted here; the output identity is re-checked live where the reference is importable."""
+    The recorded facts are asserted here; the stand-in's output at the headline config is pinned to the reference's own
+    fixture by test_composite_matches_reference[A_ada]."""
     import json
     import os
     rec = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "cpu_standin.json")))
@@ -162,25 +163,3 @@ def test_cpu_standin_is_pinned():
     enc = blocks.TransformerEncoderForChannels(6, 6, model_dim=32, num_head=1, num_layers=1, max_len=64)
     assert type(enc.transformer) is torch.nn.TransformerEncoder
     assert isinstance(enc.linear_1, torch.nn.Linear) and isinstance(blocks.ConvEnhancer().conv_block[0], torch.nn.Conv2d)
-    if os.path.isdir("/root/reference/src/models"):
-        import subprocess
-        import sys
-        code = ("import sys, typing, typing_extensions; sys.dont_write_bytecode = True\n"
-                "typing.Self = getattr(typing, 'Self', typing_extensions.Self)\n"
-                "sys.path.insert(0, '/root/reference'); sys.path.append(%r)\n"
-                "import torch\n"
-                "from src.config.schemas import ModelConfig as RM, SystemConfig as RS\n"
-                "from src.models import AdaFortiTranEstimator as R\n"
-                "import adafortitran_amd as A\n"
-                "from adafortitran_amd import synth\n"
-                "hid = (7, 42, 560)\n"
-                "sd = synth.make_state_dict(ofdm=(120, 14), pilot=(12, 2), patch=(3, 2), num_layers=6, model_dim=128, num_head=4, adaptive_hidden=hid, seed=5)\n"
-                "def mk(cls, SC, MC):\n"
-                "    m = cls(SC(ofdm=dict(num_scs=120, num_symbols=14), pilot=dict(num_scs=12, num_symbols=2)), MC(model_type='adafortitran', patch_size=(3, 2), num_layers=6, model_dim=128, num_head=4, max_seq_len=512, device='cpu', channel_adaptivity_hidden_sizes=list(hid), adaptive_token_length=6))\n"
-                "    m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}); return m.eval()\n"
-                "inp = synth.make_inputs(4, seed=6); pil = torch.from_numpy(inp['pilots']); meta = synth.meta_tuple(inp)\n"
-                "with torch.no_grad(): d = (mk(R, RS, RM)(pil, meta) - mk(A.AdaFortiTranEstimator, A.SystemConfig, A.ModelConfig)(pil, meta)).abs().max().item()\n"
-                "print('DIFF', d)\n") % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-        out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300,
-                             env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1"))
-        assert "DIFF 0.0" in out.stdout, out.stdout + out.stderr
