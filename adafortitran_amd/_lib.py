@@ -133,15 +133,19 @@ def check(rc: int) -> None:
 
 
 def set_switch(name: str, value) -> None:
-    """A measurement / A-B switch of the library (header: aft_set_switch).  The library reads the AFT_* environment once, when it is
-    loaded; afterwards switches change only through this call (``value`` None = unset) -- never through os.environ."""
+    """A run-time switch (csrc/switches.h declares them; header: aft_set_switch).  The library reads the switches from the environment
+    once, when it is loaded; afterwards they change only through this call (``value`` None = unset) -- never through os.environ.
+    A name that is not a switch raises ValueError."""
     check(load().aft_set_switch(name.encode(), None if value is None else str(value).encode()))
 
 
 def get_switch(name: str):
-    """Current value of a switch (str) or None when it is unset."""
+    """Current value of a switch (str) or None when it is unset; ValueError when ``name`` is not a switch."""
     buf = C.create_string_buffer(256)
-    return buf.value.decode() if load().aft_get_switch(name.encode(), buf, 256) else None
+    rc = load().aft_get_switch(name.encode(), buf, 256)
+    if rc < 0:
+        raise ValueError(f"{name} is not a switch of the library (adafortitran_amd/csrc/switches.h lists them)")
+    return buf.value.decode() if rc else None
 
 
 class switch:

@@ -196,11 +196,12 @@ class TransformerEncoderForChannels(nn.Module):
         p = patch[0] * patch[1]
         l1, l2, d = self.linear_1, self.linear_2, self.linear_1.out_features
         on = lambda lin: HipLinear.default_hip_training if lin.hip_training is None else lin.hip_training
-        return (self.fused_ends and not _lib.get_switch("AFT_TRAIN_NO_FUSED_ENDS") and conv_enhanced.dim() == 3
-                and conv_enhanced.device.type == "cuda" and torch.is_grad_enabled() and conv_enhanced.dtype == torch.float32
+        return (self.fused_ends and conv_enhanced.device.type == "cuda" and torch.is_grad_enabled()
+                and conv_enhanced.dtype == torch.float32 and conv_enhanced.dim() == 3
                 and conv_enhanced.shape[0] % 2 == 0 and self.hip_train_gap() is None and on(l1) and on(l2)
                 and l1.bias is not None and l2.bias is not None and l1.weight.dtype == torch.float32
-                and p <= 32 and d % 4 == 0 and d <= 512 and l2.out_features == p and l1.in_features in (p, p + 6))
+                and p <= 32 and d % 4 == 0 and d <= 512 and l2.out_features == p and l1.in_features in (p, p + 6)
+                and not _lib.get_switch("AFT_TRAIN_NO_FUSED_ENDS"))
 
     def forward_planes(self, conv_enhanced: torch.Tensor, adapter_tokens: Optional[torch.Tensor], patch) -> torch.Tensor:
         """conv_enhanced [P,S,T] (+ adapter tokens [P,tokens,6]) -> conv_enhanced + InversePatchEmbedding(encoder(tokens)): what the

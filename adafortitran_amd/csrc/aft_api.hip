@@ -3,16 +3,14 @@
 // thread-local error string the only things cached are per-device facts (CU count, LDS function
 // attribute) in tables indexed by device ordinal (hipGraph-capturable, re-entrant per stream).
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <map>
 #include <mutex>
 #include <string>
 #include <vector>
-
-extern char **environ;
 
 #include "aft_internal.h"
 
@@ -52,35 +50,44 @@ hipError_t ensure_dynamic_lds(PerDeviceOnce &once, const void *kernel, size_t by
     return e;
 }
 
-// ---- switches: the "AFT_*" environment, read once at load; aft_set_switch afterwards (header) ----
+// ---- switches (switches.h): read from the environment once, at load; aft_set_switch afterwards (header) ----
 namespace {
-struct Switches {
-    std::mutex mu;
-    std::map<std::string, std::string> table;
-    Switches() {      // static initialisation of the shared object: before any call, on the loading thread
-        for (char **e = environ; e != nullptr && *e != nullptr; ++e) {
-            if (strncmp(*e, "AFT_", 4) != 0) continue;
-            const char *eq = strchr(*e, '=');
-            if (eq != nullptr) table[std::string(*e, eq - *e)] = std::string(eq + 1);
-        }
-    }
+constexpr const char *kSwitchNames[kNumSwitches] = {
+#define AFT_SWITCH_NAME(id, name, purpose) name,
+    AFT_SWITCHES(AFT_SWITCH_NAME)
+#undef AFT_SWITCH_NAME
 };
-Switches &switches() {
-    static Switches s;
-    return s;
+// The read path sees g_switch_on / g_switch_value only (constant-initialised, so valid before any static constructor runs); the
+// strings aft_get_switch returns live behind the mutex that aft_set_switch takes.
+std::atomic<bool> g_switch_on[kNumSwitches];
+std::atomic<int> g_switch_value[kNumSwitches];
+std::mutex g_switch_mu;
+std::string g_switch_text[kNumSwitches];
+
+int switch_id(const char *name) {
+    for (int i = 0; i < kNumSwitches; ++i)
+        if (strcmp(name, kSwitchNames[i]) == 0) return i;
+    return -1;
 }
-struct SwitchesAtLoad { SwitchesAtLoad() { switches(); } } g_switches_at_load;
+void store_switch(int i, const char *value) {   // caller holds g_switch_mu (or runs before anything else can)
+    if (value == nullptr) {
+        g_switch_on[i].store(false, std::memory_order_release);
+        g_switch_text[i].clear();
+        return;
+    }
+    g_switch_text[i] = value;
+    g_switch_value[i].store(atoi(value), std::memory_order_relaxed);
+    g_switch_on[i].store(true, std::memory_order_release);
+}
+struct SwitchesAtLoad {   // static initialisation of the shared object: before any call, on the loading thread
+    SwitchesAtLoad() {
+        for (int i = 0; i < kNumSwitches; ++i) store_switch(i, getenv(kSwitchNames[i]));
+    }
+} g_switches_at_load;
 }  // namespace
-bool switch_on(const char *name) {
-    Switches &s = switches();
-    std::lock_guard<std::mutex> lock(s.mu);
-    return s.table.find(name) != s.table.end();
-}
-int switch_int(const char *name, int dflt) {
-    Switches &s = switches();
-    std::lock_guard<std::mutex> lock(s.mu);
-    auto it = s.table.find(name);
-    return it == s.table.end() ? dflt : atoi(it->second.c_str());
+bool switch_on(Switch s) { return g_switch_on[s].load(std::memory_order_relaxed); }
+int switch_int(Switch s, int dflt) {
+    return g_switch_on[s].load(std::memory_order_acquire) ? g_switch_value[s].load(std::memory_order_relaxed) : dflt;
 }
 
 WeightsDev weights_window(const aft_weights &w, int first, int count) {
@@ -279,8 +286,8 @@ static double round_efficiency(long n, long slots) {
 }
 static int lanes_wanted(const aft_config &c, int batch) {
     if (!packed_engine_ok(c)) return 1;         // the general engine's launches are dispatcher-scheduled grids, not persistent rounds
-    if (switch_on("AFT_LANES")) {               // A/B switch: 1 = never split, 2 .. 4 = always that many shares
-        const int v = switch_int("AFT_LANES", 0);
+    if (switch_on(SW_LANES)) {               // A/B switch: 1 = never split, 2 .. 4 = always that many shares
+        const int v = switch_int(SW_LANES, 0);
         if (v >= 1 && v <= kMaxLanes) return std::min(v, batch);
     }
     const long tokens = tokens_of(c), planes = 2L * batch, cus = current_device_cus();
@@ -491,25 +498,23 @@ int aft_engine_of(const aft_config *cfg) {
 }
 
 int aft_set_switch(const char *name, const char *value) {
-    if (name == nullptr || strncmp(name, "AFT_", 4) != 0) {
-        set_error("aft_set_switch: switch names start with AFT_");
+    const int i = name == nullptr ? -1 : switch_id(name);
+    if (i < 0) {
+        set_error("aft_set_switch: %s is not a switch (adafortitran_amd/csrc/switches.h lists them)", name ? name : "(null)");
         return AFT_ERR_ARG;
     }
-    Switches &s = switches();
-    std::lock_guard<std::mutex> lock(s.mu);
-    if (value == nullptr) s.table.erase(name);
-    else s.table[name] = value;
+    std::lock_guard<std::mutex> lock(g_switch_mu);
+    store_switch(i, value);
     return AFT_OK;
 }
 
 int aft_get_switch(const char *name, char *buf, size_t n) {
-    if (name == nullptr) return 0;
-    Switches &s = switches();
-    std::lock_guard<std::mutex> lock(s.mu);
-    auto it = s.table.find(name);
-    if (it == s.table.end()) return 0;
+    const int i = name == nullptr ? -1 : switch_id(name);
+    if (i < 0) return -1;
+    std::lock_guard<std::mutex> lock(g_switch_mu);
+    if (!g_switch_on[i].load(std::memory_order_relaxed)) return 0;
     if (buf != nullptr && n > 0) {
-        strncpy(buf, it->second.c_str(), n - 1);
+        strncpy(buf, g_switch_text[i].c_str(), n - 1);
         buf[n - 1] = 0;
     }
     return 1;
@@ -897,7 +902,7 @@ int aft_profile_kernel_f32(const aft_config *cfg, const aft_weights *w, int whic
                 // AFT_PROLOGUE_NO_UP=1 (measurement only): the launch without the pilot_upsampler product -- bench.py charges the
                 // difference to the upsampler stage (the stage is K0 + K1 + K2)
                 e = launch_prologue(*cfg, wd, cond, cond + batch, cond + 2 * batch, base + ws.tokens6, batch, base + ws.wpack, out,
-                                    lend && prologue_upsample_ok(*cfg, wd) && !switch_on("AFT_PROLOGUE_NO_UP") ? x : nullptr, st,
+                                    lend && prologue_upsample_ok(*cfg, wd) && !switch_on(SW_PROLOGUE_NO_UP) ? x : nullptr, st,
                                     base + ws.convfrag);
                 break;
             }

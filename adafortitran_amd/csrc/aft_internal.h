@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "../../include/adafortitran_amd.h"
+#include "switches.h"   // the run-time switches: switch_on / switch_int
 
 namespace aft {
 
@@ -178,11 +179,6 @@ void set_error(const char *fmt, ...);
 int check_config(const aft_config *c);
 // The launch sequence a configuration runs (aft_engine_of): decided by the configuration alone.
 bool packed_engine_ok(const aft_config &c);
-
-// Measurement / A-B switches (aft_set_switch in the header): a table filled ONCE from the "AFT_*" environment variables when the
-// library is loaded and changed only through the ABI afterwards -- nothing on a call path calls getenv().
-bool switch_on(const char *name);                 // set (to anything)
-int switch_int(const char *name, int dflt);       // atoi of the value, dflt when unset
 
 // The pointer table kernels receive BY VALUE: the public aft_weights with a window of at most kLayerWindow layers inline (the public
 // struct holds a host pointer to any number of layers; kernel arguments cannot follow it).

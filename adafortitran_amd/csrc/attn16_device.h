@@ -4,7 +4,7 @@
 // src/models/blocks/encoders.py:44-55), `num_head: 8` at `model_dim: 128` and the like: heads of 16 features, two per 32-feature block of
 // the q / k / v^T layout the chain kernel writes.
 //
-// Why a second body.  attn_body<HD = 16> runs the head on 32x32x2 MFMAs: S^T is an 8-MFMA chain over the head's 16 features, but the
+// Why a second body.  the removed attn_body<16> ran the head on 32x32x2 MFMAs: S^T is an 8-MFMA chain over the head's 16 features, but the
 // value product O^T = V^T P^T has to take a whole 32-feature block as its A operand (a 32-row MFMA cannot take half its rows): 16 MFMAs
 // of 64 cycles of which half the rows are the OTHER head's -- 1 536 matrix cycles per (head, 32 x 32 key-query tile) for 1 024 useful
 // (other_shapes.d128_h8_hd16: attention at 0.49 of the fp32 roof).  A block-diagonal P does not help there (an MFMA has ONE B operand:

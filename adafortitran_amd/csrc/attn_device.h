@@ -132,12 +132,9 @@ __device__ __forceinline__ float round_to_bf16(float x) { return (float)(__bf16)
 
 // HD = head dimension.  q / k / v^T and the output are laid out per 32-FEATURE BLOCK of the model dimension (`nblk` = model_dim / 32
 // blocks per plane), whatever the head count: for HD = 32 a block is a head.  HD = 64: a head is two adjacent blocks -- S^T sums
-// both blocks' products in one 32-MFMA chain, O^T is one accumulator per block.  HD = 16: a block holds two heads -- a task takes
-// ONE of them (`sub`): S^T is an 8-MFMA chain over this head's two 8-feature slots of Q and K (round 5; round 4 zeroed the other head's
-// query features and ran the whole 16-MFMA chain), O^T is computed for the whole block and only this head's 16 rows are stored (the
-// value product still does twice the work it needs: a 32x32 MFMA cannot take half its rows).  nn.MultiheadAttention as built at reference blocks/encoders.py:44-51 accepts any
-// num_head that divides model_dim (schemas.py:124-127).
-// Every other multiple of 8 (8, 24, 40, 48: what 4 or 8 heads give at model_dim 96 / 160 / 192, or 16 heads at 128; late round 5): a
+// both blocks' products in one 32-MFMA chain, O^T is one accumulator per block.  HD = 16 and 8 run attn16_body (attn16_device.h).
+// nn.MultiheadAttention as built at reference blocks/encoders.py:44-51 accepts any num_head that divides model_dim (schemas.py:124-127).
+// Every other multiple of 8 (24, 40, 48: what 4 or 8 heads give at model_dim 96 / 160 / 192; late round 5): a
 // head is a run of HD / 8 of the plane's 8-FEATURE GROUPS (the slots of the fragment layout) that starts wherever the heads before
 // it end -- anywhere in a block.  S^T contracts exactly the head's features: one Q / K slot per group, fetched from whichever block
 // holds it, 4 MFMAs each.  O^T is computed for the one or two whole blocks the head touches (V^T's rows cannot be picked apart in a
@@ -158,7 +155,8 @@ __device__ __forceinline__ void attn_body(const float *__restrict__ q, const flo
     const Srd qs = make_srd(q), ks = make_srd(k), vs = make_srd(vt), os = make_srd(out);
     static_assert(HD % 8 == 0 && HD >= 8 && HD <= 64 && HD != 56, "head dimension");
     static_assert(!BS || HD == 32, "the split-precision tier is instantiated for head dimension 32");
-    constexpr bool GEN = HD != 16 && HD != 32 && HD != 64;   // a head = HD / 8 feature groups starting anywhere in a block
+    static_assert(HD != 16, "head dimension 16 runs attn16_body (attn16_device.h)");
+    constexpr bool GEN = HD != 32 && HD != 64;   // a head = HD / 8 feature groups starting anywhere in a block
     constexpr int NS = HD / 8;                          // 8-feature groups (fragment slots) per head
     constexpr int NB = GEN ? (32 % HD == 0 ? 1 : 2) : HD == 64 ? 2 : 1;   // 32-feature blocks a head touches (V^T tiles, O^T accumulators)
     constexpr int NQ = GEN ? (NS + 3) / 4 : NB;         // Q / K operand registers, in units of four slots
@@ -182,8 +180,7 @@ __device__ __forceinline__ void attn_body(const float *__restrict__ q, const flo
     auto first_group = [&](int task) { const int ph = task / nkt, plane = ph / heads; return plane * nblk * 4 + (ph - plane * heads) * NS; };
     auto first_block = [&](int task) {
         if constexpr (GEN) return first_group(task) >> 2;
-        const int ph = task / nkt;
-        return HD == 16 ? ph >> 1 : ph * NB;
+        return task / nkt * NB;
     };
     auto head_base = [&](int task) { return ((unsigned)first_block(task) * tokpad * kHeadDim + lane * 4) * 4; };
     const unsigned blk_bytes = (unsigned)tokpad * kHeadDim * 4;     // one (plane, block) of q / k / v^T
@@ -199,10 +196,9 @@ __device__ __forceinline__ void attn_body(const float *__restrict__ q, const flo
 #pragma unroll
             for (int s = 0; s < 4; ++s) dst[b][s] = srd_load(src, base + b * b1_bytes + (unsigned)(kt * 1024 + s * 256) * 4);
     };
-    // HD = 16: only the head's two slots (8-feature groups 2 sub, 2 sub + 1) of a Q / K tile, into slots 0, 1
-    constexpr int NMF = GEN ? 4 * NS : HD == 16 ? 8 : 16 * NB;
-    // sub_: HD = 16: which of the block's two heads.  GEN: the head's first slot within its first block (first_group & 3); `base` is
-    // that block's, and slot i of the head is slot (sub_ + i) & 3 of block (sub_ + i) >> 2 from there
+    constexpr int NMF = GEN ? 4 * NS : 16 * NB;
+    // sub_ (GEN): the head's first slot within its first block (first_group & 3); `base` is that block's, and slot i of the head is
+    // slot (sub_ + i) & 3 of block (sub_ + i) >> 2 from there
     auto load_qk = [&](Srd src, int kt, f32x4 (&dst)[NQ][4], unsigned base, int sub_) {
         if constexpr (GEN) {
 #pragma unroll
@@ -210,26 +206,19 @@ __device__ __forceinline__ void attn_body(const float *__restrict__ q, const flo
                 const int sl = sub_ + i;
                 dst[i >> 2][i & 3] = srd_load(src, base + (unsigned)(sl >> 2) * blk_bytes + (unsigned)(kt * 1024 + (sl & 3) * 256) * 4);
             }
-        } else if constexpr (HD == 16) {
-#pragma unroll
-            for (int s = 0; s < 2; ++s) dst[0][s] = srd_load(src, base + (unsigned)(kt * 1024 + (2 * sub_ + s) * 256) * 4);
         } else {
             load_tile(src, kt, dst, base, blk_bytes);
         }
     };
     auto sub_of = [&](int task) {
         if constexpr (GEN) return first_group(task) & 3;
-        return HD == 16 ? (task / nkt) & 1 : 0;
+        return 0;
     };
     // padded keys of the ragged last tile: logits -> -inf (probability 0), V^T columns -> 0 (the workspace pad is
     // never trusted: 0 x NaN would poison the row)
     // (8 | tokens, the usual case: whole 8-key groups are padding, the same registers in every lane -- a wave-uniform test per
     // group instead of an add, a compare and a select per register and lane: 100 vector instructions per task less)
-#ifdef AFT_ATTN_OLD_MASKS
-    const bool pad8 = false;
-#else
     const bool pad8 = (tokens & 7) == 0;
-#endif
     auto mask_logits = [&](f32x16 &sv, int kt) {
         if (pad8) {
 #pragma unroll
@@ -283,7 +272,7 @@ __device__ __forceinline__ void attn_body(const float *__restrict__ q, const flo
 #endif
     const int qt = task % nkt;
     const int pb = first_block(task);       // plane * nblk + the head's first block
-    const int sub = sub_of(task);           // HD = 16: which of the block's two heads; GEN: the head's first slot in its first block
+    const int sub = sub_of(task);           // GEN: the head's first slot in its first block
     const unsigned hb = head_base(task);   // byte offset of this (plane, block)
     const unsigned vb1 = second_block_bytes(task);
     // the strided tasks of the whole rounds, then (at most) one task of the partial round
@@ -294,13 +283,13 @@ __device__ __forceinline__ void attn_body(const float *__restrict__ q, const flo
     // packed in-projection is added here (k_chain.hip stores q and k without bias: K's bias only adds
     // a row constant to the logits, which softmax cancels), then everything is pre-scaled
     if constexpr (!BS) {   // (split tier: bias and scale were applied before the bf16 split, in the chain kernel's epilogue)
-        // HD = 16: slots 0, 1 hold features 16 sub ..; GEN: slot i holds the features 8 (sub + i) .. of the first block
-        const float *bq = qbias + (pb % nblk) * kHeadDim + 4 * h + (HD == 16 ? 16 * sub : GEN ? 8 * sub : 0);
+        // GEN: slot i holds the features 8 (sub + i) .. of the first block
+        const float *bq = qbias + (pb % nblk) * kHeadDim + 4 * h + (GEN ? 8 * sub : 0);
 #pragma unroll
         for (int b = 0; b < NQ; ++b)
 #pragma unroll
             for (int s = 0; s < 4; ++s)
-                if (4 * b + s < (GEN ? NS : HD == 16 ? 2 : 4 * NB))
+                if (4 * b + s < (GEN ? NS : 4 * NB))
                     qreg[b][s] = (qreg[b][s] + *reinterpret_cast<const f32x4 *>(bq + 32 * b + 8 * s)) * scale_log2e;
     }
     // Padded query lanes of the ragged last query tile read workspace nobody wrote: their results are never stored, but
@@ -312,7 +301,7 @@ __device__ __forceinline__ void attn_body(const float *__restrict__ q, const flo
         for (int b = 0; b < NQ; ++b)
 #pragma unroll
             for (int s = 0; s < 4; ++s)
-                if (4 * b + s < (GEN ? NS : HD == 16 ? 2 : 4 * NB)) qreg[b][s] = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (4 * b + s < (GEN ? NS : 4 * NB)) qreg[b][s] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
 
     // ---- key tile 0: plain logits, reference maximum ----
@@ -442,7 +431,6 @@ __device__ __forceinline__ void attn_body(const float *__restrict__ q, const flo
         for (int b = 0; b < NB; ++b)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                if (HD == 16 && (g >> 1) != sub) continue;   // rows 8g .. 8g+7 of the block belong to the other head
                 if (GEN && (4 * b + g < sub || 4 * b + g >= sub + NS)) continue;   // group 4b + g of the first block onwards: not this head's
                 f32x4 o = {st.oacc[b][4 * g] * inv, st.oacc[b][4 * g + 1] * inv, st.oacc[b][4 * g + 2] * inv, st.oacc[b][4 * g + 3] * inv};
                 srd_store(os, dst + (b * 4 + g) * 1024, o);

@@ -87,7 +87,7 @@ hipError_t launch_attention(const aft_config &c, const float *q, const float *k,
         return hipGetLastError();
     }
 #ifdef AFT_DIAG_STAMPS
-    if (switch_on("AFT_STAMPS")) {   // per-task stamps + in-kernel clock (diagnostic build only)
+    if (switch_on(SW_STAMPS)) {   // per-task stamps + in-kernel clock (diagnostic build only)
         static unsigned long long *dbuf = nullptr;
         if (!dbuf) (void)hipMalloc(&dbuf, sizeof(unsigned long long) * 8 * 16384);
         (void)hipMemset(dbuf, 0, sizeof(unsigned long long) * 8 * 16384);
@@ -138,8 +138,8 @@ hipError_t launch_attention(const aft_config &c, const float *q, const float *k,
                            scale_log2e, ntasks, no_stamps);                                                                           \
         return hipGetLastError();                                                                                                     \
     }
-    if (hd == 8 && !switch_on("AFT_ATTN_HD8_MFMA32")) {       // late round 6: 16x16x4 MFMAs with half of every operand idle (attn16_device.h)
-        if (tokens == 280 && !switch_on("AFT_ATTN_GENERIC"))
+    if (hd == 8) {       // late round 6: 16x16x4 MFMAs with half of every operand idle (attn16_device.h)
+        if (tokens == 280)
             hipLaunchKernelGGL((attn16_kernel<280, 8>), dim3(blocks), dim3(256), 0, st, q, k, vt, qbias, attn, nblk, tokens, tokpad, c.model_dim,
                                scale_log2e, ntasks);
         else
@@ -147,29 +147,26 @@ hipError_t launch_attention(const aft_config &c, const float *q, const float *k,
                                scale_log2e, ntasks);
         return hipGetLastError();
     }
-    AFT_ATTN_HD(8) AFT_ATTN_HD(24) AFT_ATTN_HD(40) AFT_ATTN_HD(48)   // heads that start anywhere in a block (attn_device.h); covered, not tuned
+    AFT_ATTN_HD(24) AFT_ATTN_HD(40) AFT_ATTN_HD(48)   // heads that start anywhere in a block (attn_device.h); covered, not tuned
 #undef AFT_ATTN_HD
     if (hd != 16 && hd != 32 && hd != 64) return hipErrorInvalidValue;   // check_config refuses these
-    if (hd == 16 && !switch_on("AFT_ATTN_HD16_MFMA32")) {     // 16x16x4 MFMAs (attn16_device.h); the switch keeps round 5's 32x32x2 form (A/B)
-        if (tokens == 280 && !switch_on("AFT_ATTN_GENERIC"))
+    if (hd == 16) {     // 16x16x4 MFMAs (attn16_device.h)
+        if (tokens == 280)
             hipLaunchKernelGGL((attn16_kernel<280>), dim3(blocks), dim3(256), 0, st, q, k, vt, qbias, attn, nblk, tokens, tokpad, c.model_dim,
                                scale_log2e, ntasks);
         else
             hipLaunchKernelGGL((attn16_kernel<0>), dim3(blocks), dim3(256), 0, st, q, k, vt, qbias, attn, nblk, tokens, tokpad, c.model_dim,
                                scale_log2e, ntasks);
-    } else if (hd == 16)
-        hipLaunchKernelGGL((attn_kernel<16>), dim3(blocks), dim3(256), 0, st, q, k, vt, qbias, attn, nblk, tokens, tokpad, c.model_dim,
-                           scale_log2e, ntasks, no_stamps);
-    else if (hd == 64)
+    } else if (hd == 64)
         hipLaunchKernelGGL((attn_kernel<64>), dim3(blocks), dim3(256), 0, st, q, k, vt, qbias, attn, nblk, tokens, tokpad, c.model_dim,
                            scale_log2e, ntasks, no_stamps);
     // the two benchmark grids with the token count at compile time (120 x 14 -> 280 tokens, 240 x 28 -> 1120): the tile loop's trip
     // count, the last-tiles logic and the padding masks resolve in the compiler -- 125 VGPRs and no scalar spills instead of 168 and 40,
-    // -2.7 % time at 280 tokens (A/B knob: AFT_ATTN_GENERIC=1 runs the generic instantiation; same bits)
-    else if (tokens == 280 && !switch_on("AFT_ATTN_GENERIC"))
+    // -2.7 % time at 280 tokens
+    else if (tokens == 280)
         hipLaunchKernelGGL((attn_kernel<32, 280>), dim3(blocks), dim3(256), 0, st, q, k, vt, qbias, attn, nblk, tokens, tokpad, c.model_dim,
                            scale_log2e, ntasks, no_stamps);
-    else if (tokens == 1120 && !switch_on("AFT_ATTN_GENERIC"))
+    else if (tokens == 1120)
         hipLaunchKernelGGL((attn_kernel<32, 1120>), dim3(blocks), dim3(256), 0, st, q, k, vt, qbias, attn, nblk, tokens, tokpad, c.model_dim,
                            scale_log2e, ntasks, no_stamps);
     else

@@ -64,7 +64,7 @@ static hipError_t launch_chain_v(const ChainArgs &args, hipStream_t st) {
     const int blocks = std::min((args.rows + 31) / 32, resident);
     const size_t lds = S::LDS_BYTES;
 #ifdef AFT_DIAG_STAMPS
-    if (switch_on("AFT_STAMPS")) {   // phase stamps, printed on the host (never in the product build)
+    if (switch_on(SW_STAMPS)) {   // phase stamps, printed on the host (never in the product build)
         static unsigned long long *dbuf = nullptr;
         if (!dbuf) (void)hipMalloc(&dbuf, sizeof(unsigned long long) * 16 * 4096);
         (void)hipMemset(dbuf, 0, sizeof(unsigned long long) * 16 * 4096);

@@ -768,7 +768,7 @@ static hipError_t launch_chain_fwd_train_t(const ChainTrainArgs &args, hipStream
     if (ea != hipSuccess) return ea;
     const int blocks = std::min((args.rows + 31) / 32, current_device_cus() * 3);
 #ifdef AFT_DIAG_STAMPS
-    if (switch_on("AFT_STAMPS")) {   // diagnostic build only: mean cycles per phase of a tile (wave 0), and when the workgroups started
+    if (switch_on(SW_STAMPS)) {   // diagnostic build only: mean cycles per phase of a tile (wave 0), and when the workgroups started
         const int ntiles = (args.rows + 31) / 32;
         static unsigned long long *dbuf = nullptr;
         if (!dbuf) (void)hipMalloc(&dbuf, sizeof(unsigned long long) * 16 * 8192);
@@ -872,7 +872,7 @@ static hipError_t launch_chain_bwd_t(const ChainBwdArgs &args, hipStream_t st) {
     constexpr int D = 128;
     using B = ChainBwdShape<D>;
     static PerDeviceOnce lds_attr[2];
-    const bool ragged = (args.rows & 31) != 0 || switch_on("AFT_CHAIN_BWD_RAGGED");      // a partial last tile: the instantiation with per-row guards (the variable forces it: A/B)
+    const bool ragged = (args.rows & 31) != 0;      // a partial last tile: the instantiation with per-row guards
     hipError_t ea = ragged ? ensure_dynamic_lds(lds_attr[1], reinterpret_cast<const void *>(chain_bwd_kernel<D, ACT, true>), B::LDS_BYTES)
                            : ensure_dynamic_lds(lds_attr[0], reinterpret_cast<const void *>(chain_bwd_kernel<D, ACT, false>), B::LDS_BYTES);
     if (ea != hipSuccess) return ea;

@@ -754,11 +754,11 @@ static hipError_t launch_conv(ConvArgs &a, int planes, int extra_floats, hipStre
     const bool fixed = a.S == 120 && a.T == 14 && a.SP == 128 && a.band_rows == 120 && a.nbands == 1 && a.ntiles == 4 && a.nseg == 2;
     // default grid, inference, inputs as the whole forward provides them: the column-streaming pipeline (k_conv_stream.hip);
     // AFT_CONV_BANDED=1 keeps the banded kernel (A/B runs)
-    if (fixed && conv_stream_ok(a) && !switch_on("AFT_CONV_BANDED")) return launch_conv_stream(a, planes, st);   // (training: mode 2)
+    if (fixed && conv_stream_ok(a) && !switch_on(SW_CONV_BANDED)) return launch_conv_stream(a, planes, st);   // (training: mode 2)
     if (fixed) return launch_conv_geo<TRAIN, true>(a, planes, lds, st);
     // planes that need several bands here (config 5: five bands of two row tiles): the whole-height column-streaming kernel
     // (k_conv_rows.hip) when its shape conditions hold; AFT_CONV_BANDED=1 keeps the banded kernel (A/B runs)
-    if (!TRAIN && a.nbands > 1 && conv_rows_ok(a, planes) && !switch_on("AFT_CONV_BANDED")) return launch_conv_rows(a, planes, st);
+    if (!TRAIN && a.nbands > 1 && conv_rows_ok(a, planes) && !switch_on(SW_CONV_BANDED)) return launch_conv_rows(a, planes, st);
     return launch_conv_geo<TRAIN, false>(a, planes, lds, st);
 }
 
@@ -768,7 +768,7 @@ static hipError_t launch_conv_geo(ConvArgs &a, int planes, size_t lds, hipStream
     hipError_t ea = ensure_dynamic_lds(lds_attr, reinterpret_cast<const void *>(conv_stack_kernel<TRAIN, FIXED>), 160 * 1024);
     if (ea != hipSuccess) return ea;
 #ifdef AFT_DIAG_STAMPS
-    if (!TRAIN && switch_on("AFT_STAMPS")) {   // diagnostic build only: mean cycles per phase (thread 0 of every workgroup)
+    if (!TRAIN && switch_on(SW_STAMPS)) {   // diagnostic build only: mean cycles per phase (thread 0 of every workgroup)
         static unsigned long long *dbuf = nullptr;
         const int nb = planes * a.nbands;
         if (!dbuf) (void)hipMalloc(&dbuf, sizeof(unsigned long long) * 16 * 4096);

@@ -524,7 +524,7 @@ hipError_t launch_embed_train_bwd(const float *conv, const float *tok6, const fl
     static PerDeviceOnce attr[4];
     const int nout = (g.d * g.din + 255) / 256, npiece = (kEmbTok * (g.d / 4) + 255) / 256;
     hipError_t e;
-    if (g.d == 128 && g.din <= 16 && !switch_on("AFT_EMBED_BWD_GENERIC")) {   // the default model: both products on MFMAs
+    if (g.d == 128 && g.din <= 16 && !switch_on(SW_EMBED_BWD_GENERIC)) {   // the default model: both products on MFMAs
         const size_t lds128 = sizeof(float) * ((16 + kEmbPass * kEmbTok) * (128 + 4) + kEmbPass * kEmbTok * 16);
         if ((e = ensure_dynamic_lds(attr[3], reinterpret_cast<const void *>(embed_rows_bwd128_kernel), 160 * 1024)) != hipSuccess) return e;
         hipLaunchKernelGGL(embed_rows_bwd128_kernel, dim3(tb, chunks), dim3(256), lds128, st, a);

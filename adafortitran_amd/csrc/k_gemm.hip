@@ -848,8 +848,8 @@ hipError_t launch_gemm(int op, const float *A, const float *B, float *C, const f
     // barriers) and wins only where the 64-row form leaves a lone last round -- 71 680 rows x (384 -> 128): 70.5 -> 67.9 us; with
     // several column tiles it measured slower at every row count (tools/debug/gemm_tile_ab.py).
     int rows = 64;
-    if (gemm_fast_ok(op, M, N, K, lda, ldb, ldc) && (N <= GBN || switch_int("AFT_GEMM_BM", 0) == 96)) {
-        const int forced = switch_int("AFT_GEMM_BM", 0);
+    if (gemm_fast_ok(op, M, N, K, lda, ldb, ldc) && (N <= GBN || switch_int(SW_GEMM_BM, 0) == 96)) {
+        const int forced = switch_int(SW_GEMM_BM, 0);
         const long long cus = current_device_cus(), ntn = (N + GBN - 1) / GBN;
         auto cost = [&](int bm, int per_cu) {
             const long long tiles = (M + bm - 1) / bm * ntn, slots = cus * per_cu;

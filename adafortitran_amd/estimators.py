@@ -22,7 +22,7 @@ elements -- the tuned fragment-packed engine where its shape conditions hold (mo
 head dims 8 .. 64 in steps of 8 except 56, patches of up to 16 elements), the row-major general engine elsewhere
 (``hip_engine_name()`` says which).  A configuration the reference accepts beyond that (a larger model_dim or
 head, a grid with no LDS band plan) is refused with a ``ValueError`` when the model is built on a HIP device --
-before any training -- instead of failing in the first ``eval()`` forward.  ``AFT_ALLOW_COMPOSITE=1`` in the environment opts into running such a model entirely on the
+before any training -- instead of failing in the first ``eval()`` forward.  The switch ``AFT_ALLOW_COMPOSITE=1`` opts into running such a model entirely on the
 PyTorch-ROCm composite (logged).  The TRAINING kernels cover what inference covers; where a block of an accepted
 model is nevertheless differentiated by PyTorch-ROCm autograd (switched off by hand, a conv grid without a band plan), the
 constructor logs a warning naming the block and the reason, and ``training_backends()`` returns the same.
@@ -30,7 +30,6 @@ constructor logs a warning naming the block and the reason, and ``training_backe
 from __future__ import annotations
 
 import logging
-import os
 from typing import List, Optional, Tuple
 
 import torch
@@ -138,7 +137,7 @@ class BaseFortiTranEstimator(nn.Module):
         self.device = torch.device(model_config.device)
         self.logger = logging.getLogger(self.__class__.__name__)
         self._engine = None
-        self._hip_precision = os.environ.get("AFT_PRECISION", "f32")   # see the hip_precision property
+        self._hip_precision = None     # see the hip_precision property: None = the AFT_PRECISION switch, read on the HIP device
         self._engine_entries = ()      # (owner dict, key, tensor, data_ptr) per state_dict tensor of the engine
         self._stager = None            # pinned-ring H2D staging of CPU inputs on the HIP inference path
         self._hip_covered = False
@@ -196,6 +195,9 @@ class BaseFortiTranEstimator(nn.Module):
         if self.pilot_upsampler.weight.device.type != "cuda":
             return
         from .hip_ops import config_coverage   # loads the extension: a missing .so raises here, loudly
+        from . import _lib
+        if self._hip_precision is None:
+            self._hip_precision = _lib.get_switch("AFT_PRECISION") or "f32"
         cfg = _abi.config_from_pydantic(self.system_config, self.model_config, self.use_channel_adaptation)
         reason = config_coverage(cfg)
         if reason is None:
@@ -206,13 +208,13 @@ class BaseFortiTranEstimator(nn.Module):
                     self.logger.warning("training: %s is differentiated by PyTorch-ROCm autograd, not by the library's kernels (%s); "
                                         "inference (eval() + no_grad) runs the HIP engine either way", block, gap)
             return
-        from . import _lib
         if _lib.get_switch("AFT_ALLOW_COMPOSITE") == "1":      # the AFT_* environment as the library read it at load, or aft_set_switch
             self.logger.warning("configuration not covered by the gfx950 kernels (%s): AFT_ALLOW_COMPOSITE=1, "
                                 "running the PyTorch-ROCm composite for training AND evaluation", reason)
             return
         raise ValueError(f"configuration not covered by the gfx950 kernels: {reason}. Build the model with "
-                         "device='cpu', or set AFT_ALLOW_COMPOSITE=1 to run the PyTorch-ROCm composite instead.")
+                         "device='cpu', or call _lib.set_switch(\"AFT_ALLOW_COMPOSITE\", 1) (or export AFT_ALLOW_COMPOSITE=1 before "
+                         "the library is loaded) to run the PyTorch-ROCm composite instead.")
 
     def hip_engine_name(self) -> Optional[str]:
         """``"packed"`` / ``"general"``: the launch sequence ``aft_forward_f32`` runs for this configuration (include/adafortitran_amd.h
@@ -249,8 +251,9 @@ class BaseFortiTranEstimator(nn.Module):
         """Arithmetic of the HIP inference path: ``"f32"`` (default: exact-fp32 MFMAs everywhere, the parity contract) or
         ``"bf16x3"`` -- the opt-in split-precision tier of include/adafortitran_amd.h (AFT_PRECISION_BF16X3: the encoder's
         GEMMs and attention products on bf16 hi/lo terms with fp32 accumulation; model_dim 128 or 256; ~1.8-2x the frames/s at
-        max|d| ~ 3e-5 |y|max).  Not part of the reference's YAML surface: set it on the module, or AFT_PRECISION=bf16x3."""
-        return self._hip_precision
+        max|d| ~ 3e-5 |y|max).  Not part of the reference's YAML surface: set it on the module, or the switch AFT_PRECISION=bf16x3
+        (read when the model is first placed on the HIP device)."""
+        return self._hip_precision or "f32"
 
     @hip_precision.setter
     def hip_precision(self, value: str) -> None:

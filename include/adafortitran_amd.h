@@ -123,11 +123,14 @@ int aft_check_config(const aft_config *cfg);
 #define AFT_ENGINE_GENERAL 1
 int aft_engine_of(const aft_config *cfg);
 
-/* Measurement / A-B switches (no reference counterpart).  The library reads every environment variable that starts with "AFT_" ONCE,
- * when it is loaded; afterwards a switch changes only through aft_set_switch (value NULL = unset) -- no getenv() on any call path, so
- * forwards on several host threads never race a setenv() elsewhere in the process.  aft_get_switch copies the current value into
- * buf (at most n bytes including the terminator) and returns 1, or returns 0 when the switch is unset.  The switches in use are
- * listed in DESIGN.md section 5; none of them changes results beyond summation order, and the product never sets one. */
+/* Measurement / A-B switches (no reference counterpart).  Every switch is declared once, with its purpose, in the table of
+ * adafortitran_amd/csrc/switches.h.  The library reads the environment variables of those names ONCE, when it is loaded (other AFT_*
+ * variables are ignored); afterwards a switch changes only through aft_set_switch (value NULL = unset) -- no getenv() on any call
+ * path, so forwards on several host threads never race a setenv() elsewhere in the process.  A switch set to anything is on; its
+ * value is read as atoi() reads it.  aft_set_switch returns AFT_ERR_ARG for a name the table does not declare (aft_last_error names
+ * it).  aft_get_switch copies the current value into buf (at most n bytes including the terminator) and returns 1, returns 0 when
+ * the switch is unset and -1 when the name is not a switch.  None of them changes results beyond summation order, and the product
+ * never sets one. */
 int aft_set_switch(const char *name, const char *value);
 int aft_get_switch(const char *name, char *buf, size_t n);
 

@@ -96,6 +96,38 @@ def test_switches_are_read_once_and_change_through_the_abi_only(switches):
         _lib.set_switch("PATH", "x")              # only AFT_* names
 
 
+def test_unknown_switch_names_are_refused():
+    """A misspelled switch must not pass silently (a test that sets one would compare the product path with itself):
+    aft_set_switch refuses a name csrc/switches.h does not declare, aft_get_switch returns -1 for it."""
+    for name in ("AFT_LANE", "AFT_TRAIN_UNFUSED_FORWARD", "AFT_ATTN_HD16_MFMA32", "AFT_BATCH", "PATH"):
+        with pytest.raises(ValueError, match=name):
+            _lib.set_switch(name, "1")
+        with pytest.raises(ValueError, match=name):
+            _lib.get_switch(name)
+        with pytest.raises(ValueError):
+            with _lib.switch(name, 1):
+                pass
+    bogus = b"AFT_NOT_A_SWITCH"
+    assert _lib.load().aft_get_switch(bogus, None, 0) == -1
+
+
+def test_every_switch_the_repository_names_is_declared(switches):
+    """Every name bench.py, tests/ and tools/ hand to set_switch / get_switch, _lib.switch(...), the `switches` fixture or
+    aft_set_switch is a declared switch (the library accepts it and reads it back)."""
+    call = re.compile(r"(?:set_switch|get_switch|_lib\.switch|switches\.set|switches\.unset)\(\s*b?[\"'](AFT_[A-Z0-9_]+)[\"']")
+    files = [os.path.join(ROOT, "bench.py")]
+    for top in ("tests", "tools"):
+        for base, _, names in os.walk(os.path.join(ROOT, top)):
+            files += [os.path.join(base, n) for n in names if n.endswith((".py", ".sh"))]
+    used = set()
+    for path in files:
+        used.update(call.findall(open(path, errors="replace").read()))
+    assert {"AFT_LANES", "AFT_PROLOGUE_NO_UP", "AFT_CONV_NSPLIT", "AFT_ALLOW_COMPOSITE", "AFT_STAMPS"} <= used, used
+    for name in sorted(used):
+        switches.set(name, "7")
+        assert _lib.get_switch(name) == "7", name
+
+
 def test_lanes_split_the_batch_into_contiguous_shares_inside_the_workspace(switches):
     """aft_workspace_lanes: the shares a forward of `batch` frames runs as (include/adafortitran_amd.h "Lanes"): contiguous,
     non-empty, slices laid end to end and inside aft_workspace_bytes -- which must not depend on AFT_LANES (read per call)."""
@@ -191,7 +223,7 @@ def test_max_batch_is_the_32_bit_offset_limit_of_the_largest_region():
     assert lib.aft_packed_weights_bytes(ctypes.byref(wide)) > 0
 
 
-def test_hot_kernels_compile_without_register_spills():
+def test_hot_kernels_have_no_register_spills():
     """hipcc's own resource report for the two hot kernels that have tripped before (an innocent-looking extra instantiation of the
     attention body's steady-state step spilled 150 VGPRs and cost 33 % of the kernel's speed, round 4): the tuned head-dim-32
     attention kernel, both column-streaming conv kernels and the row-local training kernels must not spill a single vector
@@ -212,11 +244,13 @@ def test_hot_kernels_compile_without_register_spills():
             m = re.search(r"VGPRs Spill: (\d+)", line)
             if m and name:
                 report[name] = int(m.group(1))
-    spills = {k: v for k, v in report.items() if "attn_kernelILi32E" in k or "attn_kernelILi16E" in k or "attn16_kernel" in k or "conv_stream_kernel" in k or "conv_stream16_kernel" in k}
-    # attention HD 32 (generic, 280 tokens, 1120 tokens) / 16, conv stream head / tail (conv_stream16_kernel x 1 / 2 / 4 column ranges and
+    spills = {k: v for k, v in report.items() if "attn_kernelILi32E" in k or "attn16_kernel" in k or "conv_stream_kernel" in k or "conv_stream16_kernel" in k}
+    # attention HD 32 (generic, 280 tokens, 1120 tokens), conv stream head / tail (conv_stream16_kernel x 1 / 2 / 4 column ranges and
     # the 32x32x2 kernel) / training
     # (round 6: + the three training instantiations of conv_stream16_kernel, + attn16_kernel<0 | 280, 16 | 8>: head dims 16 / 8 on 16x16x4 MFMAs)
-    assert len(spills) == 20 and all(v == 0 for v in spills.values()), report
+    assert len(spills) == 19 and all(v == 0 for v in spills.values()), report
+    # the 32x32x2 forms of head dims 16 and 8 are retired: those heads run attn16_kernel only
+    assert not any("attn_kernelILi16E" in k or "attn_kernelILi8E" in k for k in report), report
     assert all(v <= 4 for k, v in report.items() if "attn_kernelILi64E" in k), report
     # the row-local training kernels (forward chain with / without the in-projection tail, backward chain; gelu and relu) sit at the
     # 168 registers three waves per SIMD allow: a scratch reload is a VMEM load whose wait drains vmcnt

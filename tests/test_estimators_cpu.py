@@ -1,6 +1,10 @@
 """Host-side mirror of the reference module surface, exercised on CPU (autograd composite):
 state_dict layout, class identities, error conventions, and the composite's numerics against
 the reference-generated golden vectors."""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 import torch
@@ -117,6 +121,27 @@ def test_training_path_has_gradients():
     loss = torch.view_as_real(out).pow(2).mean()
     loss.backward()
     assert all(p.grad is not None for p in model.parameters())
+
+
+def test_cpu_model_runs_without_the_library():
+    """A model on ``device: cpu`` never loads libaft_hip.so: in a fresh process whose library path points nowhere, a FortiTran
+    estimator still builds and runs a forward and a backward (every predicate checks the device before it reads a switch)."""
+    script = (
+        "import torch\n"
+        "from adafortitran_amd import _lib\n"
+        "from helpers import Golden\n"
+        "from test_estimators_cpu import build_model\n"
+        "g = Golden('T_tiny_forti')\n"
+        "model = build_model(g).train()\n"
+        "out = model(torch.from_numpy(g['pilots']))\n"
+        "torch.view_as_real(out).pow(2).mean().backward()\n"
+        "assert all(p.grad is not None for p in model.parameters())\n"
+        "assert _lib._lib is None\n")
+    tests = os.path.dirname(os.path.abspath(__file__))
+    env = dict(os.environ, AFT_LIB_PATH="/nonexistent/libaft_hip.so",
+               PYTHONPATH=os.pathsep.join([tests, os.path.dirname(tests)]))
+    res = subprocess.run([sys.executable, "-s", "-c", script], cwd=tests, env=env, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-3000:]
 
 
 def test_linear_estimator_cpu():

@@ -146,10 +146,8 @@ def test_one_pass_attention_backward_agrees_with_the_two_pass_form(ofdm, heads, 
     four = run()
     switches.set("AFT_ATTN_BWD_GROUPS", "1")
     three = run()
-    switches.set("AFT_ATTN_BWD_GROUPS", "2")      # round 6: six-wave workgroups, two problems each (64 frames of the default model)
-    six = run()
-    for i, (a, b, c) in enumerate(zip(four, three, six)):
-        assert torch.equal(a, b) and torch.equal(a, c), i
+    for i, (a, b) in enumerate(zip(four, three)):
+        assert torch.equal(a, b), i
 
 
 @pytest.mark.parametrize("d,heads,ofdm", [(128, 4, (120, 14)), (128, 4, (24, 14)), (256, 8, (48, 14))])
