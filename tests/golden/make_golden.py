@@ -216,6 +216,33 @@ def _grad64(spec, batch, perturb=0.0):
     return {n: p.grad.detach().reshape(-1).numpy().copy() for n, p in model.named_parameters()}, float(loss), sd
 
 
+GRAD_SPREAD_BUDGET = 8192
+GOLDEN_FILE_MAX = 1_000_000          # bytes: no fixture file grows past this (the repository takes no larger file)
+SPREAD_SHARD_BYTES = 1_200_000       # uncompressed bytes of gidx + gspread per companion file (~0.75 MB compressed)
+
+
+def spread_index(shape, budget=GRAD_SPREAD_BUDGET):
+    """Flat indices of a ROW-COVERING sample of a tensor of `shape`: a tensor of <= `budget` elements whole; a larger one viewed
+    as [rows, C] (rows = the first dimension, the position table's leading 1 squeezed: 512 position rows; in_proj_weight: 3 d
+    rows, every Q / K / V row of every head), `max(1, budget // rows)` elements per row at columns spread across it,
+    (r P + j ceil(C / k)) mod C with P coprime to C -- so each row is reached, and at a different phase than its neighbour.
+    Sorted, unique, int32."""
+    shape = tuple(int(x) for x in shape)
+    n = int(np.prod(shape))
+    if n <= budget:
+        return np.arange(n, dtype=np.int32)
+    if len(shape) > 2 and shape[0] == 1:
+        shape = shape[1:]
+    rows = shape[0]
+    C = n // rows
+    k = min(C, max(1, budget // rows))
+    P = next(p for p in range(97, 97 + C + 1) if np.gcd(p, C) == 1)
+    r = np.arange(rows, dtype=np.int64)[:, None]
+    j = np.arange(k, dtype=np.int64)[None, :]
+    idx = r * C + (r * P + j * C // k) % C
+    return np.unique(idx.reshape(-1)).astype(np.int32)
+
+
 def run_grad64(name, spec, batch):
     """The same training step as run_grad, computed by the reference in FLOAT64 (model.double(), complex128 inputs): the
     "true" gradient that both fp32 computations -- the reference's own (fixture G_grad_*) and the HIP path's -- are
@@ -224,10 +251,17 @@ def run_grad64(name, spec, batch):
     of the float64 gradient when every parameter is multiplied by (1 + 6e-8 u), u uniform in [-1, 1] (half an fp32 ulp).
     A coherent half-ulp perturbation bounds what ANY fp32 evaluation can promise for that tensor (its intermediate
     roundings are perturbations of that size): 2e-5 for the encoder's weights, 2e-3 for pilot_upsampler.weight at full
-    depth -- the far end of six layers of backward."""
+    depth -- the far end of six layers of backward.
+    The prefix sample reaches only the first rows of a large tensor (no V row of a d = 128 in_proj_weight, no position past
+    token 223), so each tensor also keeps a row-covering sample (spread_index): `gidx` (int32 flat indices) and `gspread` (the
+    float64 gradient there, STORED AS float32: its rounding, 6e-8 of the element, is far below the smallest tolerance it meets,
+    5e-6 of |g|max).  Those go to companion files `{name}.spread{k}.npz` (tests/helpers.py::Golden merges them), as many as
+    keep each file under GOLDEN_FILE_MAX.  An existing `{name}.npz` is not rewritten: its arrays must come out byte-identical."""
+    path = os.path.join(HERE, f"{name}.npz")
     grads, loss, sd = _grad64(spec, batch)
     pert, _, _ = _grad64(spec, batch, perturb=6e-8)
     arrays = {"loss": np.float64(loss)}
+    spread = {}
     names = []
     for n, g in grads.items():
         assert g.dtype == np.float64
@@ -237,15 +271,42 @@ def run_grad64(name, spec, batch):
         arrays[f"gsample__{n}"] = g[::GRAD_SAMPLE_STRIDE][:GRAD_SAMPLE_MAX].copy()
         arrays[f"gcond__{n}"] = np.float64(np.abs(pert[n] - g).max() / np.abs(g).max())
         arrays[f"gcondnorm__{n}"] = np.float64(abs(np.sqrt((pert[n] ** 2).sum()) - arrays[f"gnorm__{n}"]) / arrays[f"gnorm__{n}"])
+        idx = spread_index(sd[n].shape)
+        spread[n] = (idx, g[idx].astype(np.float32))
     arrays["names"] = np.asarray(names)
-    meta_json = dict(spec=spec, batch=batch, torch=torch.__version__, weights_crc=synth.state_dict_checksum(sd), dtype="float64",
-                     cond_perturbation=6e-8)
-    arrays["meta_json"] = np.frombuffer(json.dumps(meta_json).encode(), dtype=np.uint8)
-    path = os.path.join(HERE, f"{name}.npz")
-    np.savez_compressed(path, **arrays)
+    meta = dict(spec=spec, batch=batch, torch=torch.__version__, weights_crc=synth.state_dict_checksum(sd), dtype="float64")
+    if os.path.exists(path):     # regenerating must not move what the fixture already pins
+        with np.load(path) as z:
+            old = {k: z[k] for k in z.files if k != "meta_json"}
+        assert sorted(old) == sorted(arrays), f"{name}: key set changed on regeneration"
+        for k, v in old.items():
+            assert arrays[k].dtype == v.dtype and arrays[k].shape == v.shape and arrays[k].tobytes() == v.tobytes(), \
+                f"{name}: {k} changed on regeneration"
+        print(f"{name}: all {len(old)} arrays of the existing fixture reproduced byte-identically; left as it is")
+    else:
+        arrays["meta_json"] = np.frombuffer(json.dumps(dict(meta, cond_perturbation=6e-8)).encode(), dtype=np.uint8)
+        np.savez_compressed(path, **arrays)
+        assert os.path.getsize(path) <= GOLDEN_FILE_MAX, path
+    for stale in [f for f in os.listdir(HERE) if f.startswith(f"{name}.spread") and f.endswith(".npz")]:
+        os.remove(os.path.join(HERE, stale))
+    shards, cur, nbytes = [], {}, 0
+    for n in names:                 # parameter order; a new shard once ~SPREAD_SHARD_BYTES (uncompressed) are in one
+        if cur and nbytes + spread[n][0].nbytes + spread[n][1].nbytes > SPREAD_SHARD_BYTES:
+            shards.append(cur)
+            cur, nbytes = {}, 0
+        cur[f"gidx__{n}"], cur[f"gspread__{n}"] = spread[n]
+        nbytes += spread[n][0].nbytes + spread[n][1].nbytes
+    shards.append(cur)
+    sizes = []
+    for k, shard in enumerate(shards):
+        shard_meta = dict(meta, spread=dict(budget=GRAD_SPREAD_BUDGET, dtype="float32", shard=k, shards=len(shards)))
+        spath = os.path.join(HERE, f"{name}.spread{k}.npz")
+        np.savez_compressed(spath, meta_json=np.frombuffer(json.dumps(shard_meta).encode(), dtype=np.uint8), **shard)
+        sizes.append(os.path.getsize(spath))
+        assert sizes[-1] <= GOLDEN_FILE_MAX, f"{spath}: {sizes[-1]} bytes"
     worst = max(names, key=lambda n: arrays[f"gcond__{n}"])
     print(f"{name}: B={batch} fp64 loss={loss:.9f} params={len(names)} worst conditioning {arrays['gcond__' + worst]:.1e} ({worst}) "
-          f"-> {os.path.getsize(path) / 1024:.0f} KiB")
+          f"-> {os.path.getsize(path) / 1024:.0f} KiB + spread {' + '.join(f'{b / 1024:.0f}' for b in sizes)} KiB")
 
 
 def run_linear(name, batch, seed):

@@ -19,6 +19,13 @@ class Golden:
     def __init__(self, name):
         z = np.load(os.path.join(GOLDEN, name + ".npz"))
         self.arrays = {k: z[k] for k in z.files if k != "meta_json"}
+        # companion files <name>.<part>.npz carry more arrays of the same set, kept apart so that no file grows too large
+        # (the float64 gradient sets' row-covering samples, tests/golden/make_golden.py::run_grad64)
+        for part in sorted(f for f in os.listdir(GOLDEN) if f.startswith(name + ".") and f.endswith(".npz") and f != name + ".npz"):
+            with np.load(os.path.join(GOLDEN, part)) as zp:
+                extra = {k: zp[k] for k in zp.files if k != "meta_json"}
+            assert not set(extra) & set(self.arrays), (part, sorted(set(extra) & set(self.arrays))[:3])
+            self.arrays.update(extra)
         self.meta = json.loads(bytes(z["meta_json"]).decode())
         self.spec = self.meta.get("spec")
         self.name = name
