@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- OFDM frames/s of the AdaFortiTran forward path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3|C2|C5] [--batch B] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3|C2|C5] [--batch B] [--dump-outputs DIR] [--full]
 
 ``--gpus N`` with N > 1 and no torchrun environment: this process touches no GPU, starts
 ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`` on
@@ -22,12 +22,16 @@ with no data-path collective (weak scaling); ONE RCCL all-gather of the per-rank
 closes the sweep.  Rank 0 prints ONE compact JSON line on stdout (numbers, short keys:
 DESIGN.md section 5 explains every field); ``--verbose-json PATH`` also writes the annotated record.
 
-Fields besides the contract: roofline (dominant kernel, live event timing) . kernels (ms / TFLOP/s per
-class) . upsampler (graded fraction (ii) of SURVEY 8d and the by-construction HBM fraction (i)) .
-encoder_mfma_util . per_rank (N > 1: step ms min/max over ranks, all-gather latency) . and at N = 1:
-parity (vs the oracle, bounded sample) . configs (C1, the other default model, C5) . next_rows (SURVEY 8f:
+A plain run does only what the headline needs: set-up, device spin-up, the W warm-up and K timed steps, the dump if
+asked for, the line.  Its fields besides the contract are read off those steps: device_step_ms percentiles,
+mse_db_vs_random_target, whole_path_tflops, per_rank (N > 1: step ms min/max over ranks, all-gather latency, who took part).
+``--full`` adds everything that needs runs of its own: roofline (dominant kernel, live event timing) . kernels
+(ms / TFLOP/s per class) . upsampler (graded fraction (ii) of SURVEY 8d and the by-construction HBM fraction (i)) .
+encoder_mfma_util . and at N = 1 (unless ``--headline-only``): parity (vs the oracle, bounded sample) . module_surface /
+value_resident . configs (C1, the other default model, C5) . batch_sweep . other_shapes . next_rows (SURVEY 8f:
 training step, ingest, evaluation sweep, LS baseline) . split_precision (the opt-in bf16x3 tier, reported
-separately, never `value`) . cpu_baseline (the reference-equivalent CPU path on this box's host cores).
+separately, never `value`) . cpu_baseline (the reference-equivalent CPU path on the host's cores, unless
+``--no-cpu-baseline``).
 
 ``--dump-outputs DIR``: after the timed steps, what the last of them returned to the caller (rank 0's estimate) goes to
 ``DIR/estimate.npy`` as float32 [B, S, T, 2] (re, im); inputs and weights are seeded, so two builds run with the same arguments
@@ -820,8 +824,12 @@ def main() -> int:
     ap.add_argument("--config", default=None, choices=sorted(CONFIGS), help="per-rank workload (default C3)")
     ap.add_argument("--batch", type=int, default=0, help="frames per GPU per step (default: the config's)")
     ap.add_argument("--model", default=None, choices=["adafortitran", "fortitran"], help="alias: adafortitran = C3, fortitran = C2")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--headline-only", action="store_true", help="skip the N=1 legs (module surface, configs, parity, next rows, CPU)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure and check everything that takes runs of its "
+                    "own: per-kernel times and roofline, and at N=1 parity, module surface, other configs, batch sweep, other shapes, "
+                    "split precision, next rows, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--headline-only", action="store_true", help="with --full: skip the N=1 legs (module surface, configs, parity, "
+                    "next rows, CPU); the per-kernel report still runs")
     ap.add_argument("--verbose-json", default="", help="also write the annotated record to this path")
     ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed step returned "
                     "(rank 0's estimate, float32 [B,S,T,2] = re, im) as DIR/estimate.npy, at most 64 MB (a seeded sample of frames beyond)")
@@ -974,12 +982,14 @@ def main() -> int:
             result["dumped_outputs"] = dumped
         if not args.stub:
             result["config"]["lanes"] = lanes_of(wl.eng, B)    # launch sequences the timed forward ran as (1 at the stated batches)
-            kernels, roof, enc_util, t_flow, fl, ups = kernel_report(wl, 20)
+            fl = algorithmic_flops(head, B)
+            result["whole_path_tflops"] = round(fl["forward_total"] * world * args.steps / elapsed / 1e12, 2)
+        if args.full and not args.stub:
+            kernels, roof, enc_util, t_flow, _, ups = kernel_report(wl, 20)
             roof["traffic"] = load_pmc_traffic()
             result.update({"roofline": roof, "kernels": kernels, "upsampler": ups, "forward_ms_one_event_pair": t_flow,
-                           "encoder_mfma_util": enc_util,
-                           "whole_path_tflops": round(fl["forward_total"] * world * args.steps / elapsed / 1e12, 2)})
-        if world == 1 and not args.headline_only and not args.stub:
+                           "encoder_mfma_util": enc_util})
+        if world == 1 and args.full and not args.headline_only and not args.stub:
             result["parity"] = parity_vs_oracle(wl, 8 if head["name"] != "C5" else 1)
             result["value_h2d_inclusive"] = result["value"]
             ms = module_surface(wl, args.steps, args.warmup, fps)

@@ -12,8 +12,8 @@ REPO=$(pwd)
 OUT=$REPO/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench_trace" -- python3 "$REPO/bench.py" --steps 20 --warmup 5 --headline-only > "$OUT/bench_trace.log" 2>&1
-AFT_ENCODER_PATH=plane rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/plane_trace" -- python3 "$REPO/bench.py" --steps 20 --warmup 5 --headline-only > "$OUT/plane_trace.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench_trace" -- python3 "$REPO/bench.py" --steps 20 --warmup 5 --full --headline-only > "$OUT/bench_trace.log" 2>&1
+AFT_ENCODER_PATH=plane rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/plane_trace" -- python3 "$REPO/bench.py" --steps 20 --warmup 5 --full --headline-only > "$OUT/plane_trace.log" 2>&1
 export AFT_REPS=20 AFT_FWD=1
 AFT_PRECISION=bf16x3 AFT_FWD=20 AFT_ONLY=none rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/split_trace" -- python3 "$REPO/tools/prof_kernels.py" > "$OUT/split_trace.log" 2>&1
 SQ1="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA"
@@ -31,7 +31,7 @@ AFT_FWD=6 pmc none prologue     # the forwards' prologue launches (adapter + wei
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/train_trace" -- python3 "$REPO/tools/train_bench.py" --only hip --steps 10 --warmup 3 > "$OUT/train_trace.log" 2>&1
 python3 "$REPO/tools/train_bench.py" --steps 20 --warmup 5 2>/dev/null | grep "^{" | tail -1 > "$OUT/train_bench_line.json"
 # config 5 (240 x 28, 12 layers, d = 256, 64 frames per GPU) and a general-engine shape (d = 512, 8 heads) as their own kernel traces
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/c5_trace" -- python3 "$REPO/bench.py" --config C5 --steps 5 --warmup 2 --headline-only > "$OUT/c5_trace.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/c5_trace" -- python3 "$REPO/bench.py" --config C5 --steps 5 --warmup 2 --full --headline-only > "$OUT/c5_trace.log" 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/general_trace" -- python3 "$REPO/tools/general_forward.py" > "$OUT/general_trace.log" 2>&1
 cd "$REPO"
 python3 tools/train_step_breakdown.py "$OUT/train_trace" > "$OUT/train_kernel_trace_summary.txt" 2>&1
