@@ -41,7 +41,7 @@ class ConvEnhancer(nn.Module):
 
     #: set to False to differentiate the stack through PyTorch-ROCm (MIOpen) instead (A/B tests)
     hip_training = True
-    _covered = {}   # (S, T) -> the fused kernel has an LDS band plan for that grid
+    _covered = {}   # (S, T) -> the fused kernel has a plan (row bands / column tiles) for that grid
 
     @classmethod
     def _grid_covered(cls, S: int, T: int) -> bool:

@@ -6,6 +6,7 @@
 // parameter tensors.  Everything row-major fp32, rows = 2B * tokens.  The caller (PyTorch autograd,
 // adafortitran_amd/training.py) owns x_in, the tape and the gradient tensors.
 #include <algorithm>
+#include <climits>
 #include <cstdarg>
 #include <cstdlib>
 
@@ -397,14 +398,24 @@ int aft_tail_bwd_f32(const float *x, const float *w2, const float *d_out, float 
     return AFT_OK;
 }
 
+// The training conv kernels address the saved activations and masks ([planes][32][T][S] for conv2) through buffer resources with
+// 32-bit byte offsets (conv_device.h): a launch takes at most this many planes, a call of more runs as consecutive launches
+// (0: not even one plane fits -- refused)
+static int conv_train_chunk(int S, int T) {
+    const size_t per = (size_t)32 * S * T * sizeof(float);
+    return (int)std::min<size_t>((size_t)INT_MAX, (size_t)0x7fffffff / per);
+}
+
 size_t aft_conv_enhancer_scratch_bytes(int planes, int num_scs, int num_symbols) {
     if (planes <= 0 || num_scs <= 0 || num_symbols <= 0 || !conv_plan_ok(num_scs, num_symbols, 0)) return 0;
+    if (conv_train_chunk(num_scs, num_symbols) < 1) return 0;
     return sizeof(float) * (al64((size_t)planes * 48 * num_scs * num_symbols) + al64(conv_wgrad_slice_floats(planes, num_scs, num_symbols)) +
                             al64(kConvFlipFloats) + al64(kConvFragFloats));
 }
 
 size_t aft_conv_enhancer_fwd_scratch_bytes(int planes, int num_scs, int num_symbols) {
     if (planes <= 0 || num_scs <= 0 || num_symbols <= 0 || !conv_plan_ok(num_scs, num_symbols, 0)) return 0;
+    if (conv_train_chunk(num_scs, num_symbols) < 1) return 0;
     return sizeof(float) * al64(kConvFragFloats);
 }
 
@@ -419,9 +430,15 @@ int aft_conv_enhancer_fwd_train_f32(const float *const weights[4], const float *
         set_error("ConvEnhancer forward scratch too small");
         return AFT_ERR_ARG;
     }
-    float *const save[3] = {c1, c2, c3};
-    STEP("conv forward", launch_conv_train(weights, biases, x, y, save, nullptr, planes, num_scs, num_symbols,
-                                           static_cast<hipStream_t>(stream), static_cast<float *>(scratch)));
+    const int chunk = conv_train_chunk(num_scs, num_symbols);
+    if (chunk < 1) { set_error("ConvEnhancer: one %dx%d plane's saved activations exceed 2 GiB", num_scs, num_symbols); return AFT_ERR_SHAPE; }
+    const size_t st1 = (size_t)num_scs * num_symbols;
+    for (int p0 = 0; p0 < planes; p0 += chunk) {
+        const int n = std::min(chunk, planes - p0);
+        float *const save[3] = {c1 + p0 * 8 * st1, c2 + p0 * 32 * st1, c3 + p0 * 8 * st1};
+        STEP("conv forward", launch_conv_train(weights, biases, x + p0 * st1, y + p0 * st1, save, nullptr, n, num_scs, num_symbols,
+                                               static_cast<hipStream_t>(stream), static_cast<float *>(scratch)));
+    }
     return AFT_OK;
 }
 
@@ -438,8 +455,9 @@ int aft_conv_enhancer_bwd_f32(const float *const weights[4], const float *x, con
         return AFT_ERR_ARG;
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t plane8 = (size_t)planes * 8 * num_scs * num_symbols;
-    float *g3 = static_cast<float *>(scratch), *g2 = g3 + plane8, *g1 = g2 + 4 * plane8;
+    const int chunk = conv_train_chunk(num_scs, num_symbols);    // (> 0: the scratch size says so)
+    const size_t st1 = (size_t)num_scs * num_symbols, plane8 = (size_t)planes * 8 * st1, chunk8 = (size_t)std::min(chunk, planes) * 8 * st1;
+    float *g3 = static_cast<float *>(scratch), *g2 = g3 + chunk8, *g1 = g2 + 4 * chunk8;
     float *slices = static_cast<float *>(scratch) + al64(6 * plane8);
     float *flip = slices + al64(conv_wgrad_slice_floats(planes, num_scs, num_symbols));
     float *frag = flip + al64(kConvFlipFloats);      // the flipped weights as 16x16x4 operand fragments (default grid)
@@ -448,10 +466,15 @@ int aft_conv_enhancer_bwd_f32(const float *const weights[4], const float *x, con
     STEP("conv weight transposition", launch_conv_flip_weights(weights, flip, st));
     const float *const flipped_weights[4] = {flip, flip + 72, flip + 72 + 2304, flip + 72 + 4608};
     float *const save[3] = {g3, g2, g1};
-    const float *const mask[3] = {c3, c2, c1};
-    STEP("conv dgrad", launch_conv_train(flipped_weights, nullptr, dy, dx, save, mask, planes, num_scs, num_symbols, st, frag));
-    STEP("conv wgrad", launch_conv_wgrad(x, c1, c2, c3, g1, g2, g3, dy, dweights, dbiases, slices, planes, num_scs, num_symbols,
-                                         accumulate != 0, st));
+    for (int p0 = 0; p0 < planes; p0 += chunk) {   // one pass unless the planes' saved activations pass 2 GiB (conv_train_chunk)
+        const int n = std::min(chunk, planes - p0);
+        const float *cc1 = c1 + p0 * 8 * st1, *cc2 = c2 + p0 * 32 * st1, *cc3 = c3 + p0 * 8 * st1;
+        const float *const mask[3] = {cc3, cc2, cc1};
+        STEP("conv dgrad", launch_conv_train(flipped_weights, nullptr, dy + p0 * st1, dx + p0 * st1, save, mask, n, num_scs, num_symbols,
+                                             st, frag));
+        STEP("conv wgrad", launch_conv_wgrad(x + p0 * st1, cc1, cc2, cc3, g1, g2, g3, dy + p0 * st1, dweights, dbiases, slices, n,
+                                             num_scs, num_symbols, accumulate != 0 || p0 > 0, st));
+    }
     return AFT_OK;
 }
 

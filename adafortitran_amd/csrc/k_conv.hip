@@ -50,13 +50,22 @@ namespace aft {
 template <bool TRAIN, bool FIXED>
 __global__ __launch_bounds__(kConvThreads) void conv_stack_kernel(const ConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int S = FIXED ? 120 : a.S, T = FIXED ? 14 : a.T, SP = FIXED ? 128 : a.SP;
+    const int S = FIXED ? 120 : a.S, TG = FIXED ? 14 : a.T, SP = FIXED ? 128 : a.SP;
     const int BR = FIXED ? 120 : a.band_rows, NB = FIXED ? 1 : a.nbands, NT = FIXED ? 4 : a.ntiles, NSEG = FIXED ? 2 : a.nseg;
+    const int NCT = FIXED ? 1 : max(a.nctiles, 1);
     const int LR = BR + 8;
+    const int n = blockIdx.x / (NB * NCT), band = blockIdx.x % NB, ctile = (blockIdx.x / NB) % NCT;
+    // Column tiles: a workgroup owns the symbol columns [o0, o1) and holds the window [w0, w0 + T) of them in LDS,
+    // 4 halo columns per side (four stacked 3x3 convolutions) clipped to the plane.  Only the plane's own edges are zero padding; a
+    // halo column's outputs are recomputed (wrong near the window edge, never stored), never exchanged.  Untiled: one window = the plane.
+    const int o0 = ctile * (FIXED ? 14 : (NCT > 1 ? a.tcols : TG)), o1 = min(o0 + (NCT > 1 ? a.tcols : TG), TG);
+    const int w0 = max(o0 - 4 * (NCT > 1), 0), T = min(o1 + 4 * (NCT > 1), TG) - w0;   // T = window columns (the plane's, untiled)
+    const int lc0 = o0 - w0, lc1 = o1 - w0;                                                // owned columns, window-local
     const int col_stride = SP, plane = (T + 2) * SP;
     float *in0 = smem;                 // [T+2][SP]      column index = symbol + 1
     float *c1 = in0 + plane;           // [8][T+2][SP]   conv1 output
     float *c3 = c1 + 8 * plane;        // [8][T+2][SP]   conv3 output
+    if (!FIXED) AFT_DEV_ASSERT(17 * plane <= a.arena && 0 <= lc0 && lc0 < lc1 && lc1 <= T && lc0 >= min(o0, 4) && T - lc1 >= min(TG - o1, 4));
 
     const int tid = threadIdx.x;
 #ifdef AFT_DIAG_STAMPS
@@ -65,7 +74,6 @@ __global__ __launch_bounds__(kConvThreads) void conv_stack_kernel(const ConvArgs
 #define CSTAMP(i) do { } while (0)
 #endif
     CSTAMP(0);
-    const int n = blockIdx.x / NB, band = blockIdx.x % NB;
     const int frame = n >> 1, part = n & 1;
     const int gr0 = band * BR - 4;  // global row of local row 0
 
@@ -128,13 +136,13 @@ __global__ __launch_bounds__(kConvThreads) void conv_stack_kernel(const ConvArgs
     if (TRAIN && a.mode == 2) {
         for (int i = tid; i < LR * T; i += kConvThreads) {
             const int lr = i / T, t = i - lr * T, gr = gr0 + lr;
-            if (gr >= 0 && gr < S) in0[(t + 1) * col_stride + lr] = a.in_plane[((size_t)n * S + gr) * T + t];
+            if (gr >= 0 && gr < S) in0[(t + 1) * col_stride + lr] = a.in_plane[((size_t)n * S + gr) * TG + w0 + t];
         }
     } else if (a.mode == 0 && a.in_plane != nullptr) {
         // the upsampled planes were computed by upsample_planes_kernel (one product over all planes): copy the band's rows
         for (int i = tid; i < LR * T; i += kConvThreads) {
             const int lr = i / T, t = i - lr * T, gr = gr0 + lr;
-            if (gr >= 0 && gr < S) in0[(t + 1) * col_stride + lr] = a.in_plane[((size_t)n * S + gr) * T + t];
+            if (gr >= 0 && gr < S) in0[(t + 1) * col_stride + lr] = a.in_plane[((size_t)n * S + gr) * TG + w0 + t];
         }
     } else if (a.mode == 0) {   // pilot_upsampler row (gr*T + t): idx = sc*T + sym (view(B,1,S,T))
         if (FIXED && a.pf == 24) {
@@ -205,7 +213,7 @@ __global__ __launch_bounds__(kConvThreads) void conv_stack_kernel(const ConvArgs
                 for (int u = 0; u < 4; ++u) {
                     const int i = i0 + u * kConvThreads, t = i / LR, lr = i - t * LR, gr = gr0 + lr;
                     const bool ok = i < LR * T && gr >= 0 && gr < S;
-                    const int pix = ok ? gr * T + t : 0;
+                    const int pix = ok ? gr * TG + w0 + t : 0;
                     dsti[u] = ok ? (t + 1) * col_stride + lr : -1;
                     const f32x4 *wr = reinterpret_cast<const f32x4 *>(a.up_w + (size_t)pix * 24);
 #pragma unroll
@@ -283,7 +291,7 @@ __global__ __launch_bounds__(kConvThreads) void conv_stack_kernel(const ConvArgs
             for (int i = tid; i < LR * T; i += kConvThreads) {
                 const int t = i / LR, lr = i - t * LR, gr = gr0 + lr;
                 if (gr < 0 || gr >= S) continue;
-                const int pix = gr * T + t;
+                const int pix = gr * TG + w0 + t;
                 const float *wr = a.up_w + (size_t)pix * a.pf;
                 float v = a.up_b[pix];
                 for (int kk = 0; kk < a.pf; ++kk) v = fmaf(wr[kk], small[kk], v);
@@ -293,23 +301,24 @@ __global__ __launch_bounds__(kConvThreads) void conv_stack_kernel(const ConvArgs
     } else if (!TRAIN && a.lin2_out != nullptr) {
         // inverse patch map + conv_enhanced residual on the linear_2 output of the last chain launch: feature f of
         // token (g, tc) is pixel (g*p0 + f/p1, tc*p1 + f%p1); one thread per pixel of the band
-        const int p0 = a.p0, p1 = a.p1, tpr = T / p1;
+        const int p0 = a.p0, p1 = a.p1, tpr = TG / p1;
         for (int i = tid; i < LR * T; i += kConvThreads) {
-            const int lr = i / T, t = i - lr * T, gr = gr0 + lr;
+            const int lr = i / T, t = i - lr * T, gr = gr0 + lr, tg = w0 + t;
             if (gr < 0 || gr >= S) continue;
-            const int g = gr / p0, tc = t / p1, f = (gr - g * p0) * p1 + (t - tc * p1);
+            const int g = gr / p0, tc = tg / p1, f = (gr - g * p0) * p1 + (tg - tc * p1);
             in0[(t + 1) * col_stride + lr] = a.lin2_out[((size_t)n * a.tokens + g * tpr + tc) * a.lin2_stride + f] +
-                                             a.resid[((size_t)n * S + gr) * T + t];
+                                             a.resid[((size_t)n * S + gr) * TG + tg];
         }
     } else if (!TRAIN) {
         // linear_2 + inverse patch map + conv_enhanced residual.  One thread per token: its x row is read
         // once (d floats) and dotted with the p weight rows (LDS, wave-uniform address -> broadcast), in
         // groups of up to 8 features.  Feature f of token (g, tc) is pixel (g*p0 + f/p1, tc*p1 + f%p1).
-        const int p0 = a.p0, p1 = a.p1, p = p0 * p1, tpr = T / p1;
+        const int p0 = a.p0, p1 = a.p1, p = p0 * p1, tpr = TG / p1;
         const int g_lo = max(gr0, 0) / p0, g_hi = (min(gr0 + LR, S) - 1) / p0;
-        const int items = (g_hi - g_lo + 1) * tpr;
+        const int tc_lo = w0 / p1, ntc = (w0 + T - 1) / p1 - tc_lo + 1;   // token columns that touch the window
+        const int items = (g_hi - g_lo + 1) * ntc;
         for (int i = tid; i < items; i += kConvThreads) {
-            const int g = g_lo + i / tpr, tc = i % tpr;
+            const int g = g_lo + i / ntc, tc = tc_lo + i % ntc;
             const float *xr = a.x + ((size_t)n * a.tokens + g * tpr + tc) * a.d;
             for (int f0 = 0; f0 < p; f0 += 8) {
                 float acc[8];
@@ -337,9 +346,9 @@ __global__ __launch_bounds__(kConvThreads) void conv_stack_kernel(const ConvArgs
                 for (int q = 0; q < 8; ++q) {
                     const int f = f0 + q;
                     if (f >= p) break;
-                    const int gr = g * p0 + f / p1, t = tc * p1 + f % p1, lr = gr - gr0;
-                    if (lr >= 0 && lr < LR && gr < S)
-                        in0[(t + 1) * col_stride + lr] = acc[q] + a.resid[((size_t)n * S + gr) * T + t];
+                    const int gr = g * p0 + f / p1, tg = tc * p1 + f % p1, t = tg - w0, lr = gr - gr0;
+                    if (lr >= 0 && lr < LR && gr < S && t >= 0 && t < T)
+                        in0[(t + 1) * col_stride + lr] = acc[q] + a.resid[((size_t)n * S + gr) * TG + tg];
                 }
             }
         }
@@ -387,9 +396,9 @@ __global__ __launch_bounds__(kConvThreads) void conv_stack_kernel(const ConvArgs
                     v[q] = fmaxf(acc, 0.f);
                     if constexpr (TRAIN) {
                         if (okq[q]) {
-                            const size_t gi = ((size_t)(n * 8 + o) * T + t) * S + gr0 + lr0 + q;
+                            const size_t gi = ((size_t)(n * 8 + o) * TG + w0 + t) * S + gr0 + lr0 + q;
                             if (a.mask[0]) v[q] = a.mask[0][gi] > 0.f ? acc : 0.f;
-                            if (a.save[0] && lr0 + q >= 4 && lr0 + q < 4 + BR) a.save[0][gi] = v[q];
+                            if (a.save[0] && lr0 + q >= 4 && lr0 + q < 4 + BR && t >= lc0 && t < lc1) a.save[0][gi] = v[q];
                         }
                     }
                     v[q] = okq[q] ? v[q] : 0.f;
@@ -462,9 +471,9 @@ __global__ __launch_bounds__(kConvThreads) void conv_stack_kernel(const ConvArgs
                 for (int k = 0; k < 4; ++k) {
                     float y = fmaxf(v[k] + bias3[k], 0.f);
                     if constexpr (TRAIN) {
-                        const unsigned gi = ((unsigned)(n * 8 + 4 * h + k) * T + tout) * S + gr;
+                        const unsigned gi = ((unsigned)(n * 8 + 4 * h + k) * TG + w0 + tout) * S + gr;
                         if (a.mask[2]) y = conv_ld(conv_srd(a.mask[2]), gi) > 0.f ? v[k] : 0.f;
-                        if (a.save[2] && own_row) conv_st(conv_srd(a.save[2]), gi, y);
+                        if (a.save[2] && own_row && tout >= lc0 && tout < lc1) conv_st(conv_srd(a.save[2]), gi, y);
                     }
                     p[k * plane] = y;
                 }
@@ -495,15 +504,15 @@ __global__ __launch_bounds__(kConvThreads) void conv_stack_kernel(const ConvArgs
             for (int e = 0; e < 16; ++e) x2[e] = __builtin_amdgcn_fmed3f(acc2[e], 0.f, relu_hi);   // ReLU, or 0 outside the plane
             if constexpr (TRAIN) {
                 if (a.mask[1] || a.save[1]) {
-                    const unsigned g0 = ((unsigned)(n * 32 + 4 * h) * T + tcol) * S + gr;   // channel (e&3) + 8(e>>2) + 4h
-                    const unsigned cstride = (unsigned)T * S;
+                    const unsigned g0 = ((unsigned)(n * 32 + 4 * h) * TG + w0 + tcol) * S + gr;   // channel (e&3) + 8(e>>2) + 4h
+                    const unsigned cstride = (unsigned)TG * S;
                     if (a.mask[1]) {
                         const ConvSrd m = conv_srd(a.mask[1]);
 #pragma unroll
                         for (int e = 0; e < 16; ++e)
                             x2[e] = (ok2 && conv_ld(m, g0 + ((e & 3) + 8 * (e >> 2)) * cstride) > 0.f) ? acc2[e] : 0.f;
                     }
-                    if (a.save[1] && ok2 && own_row) {
+                    if (a.save[1] && ok2 && own_row && tcol >= lc0 && tcol < lc1) {
                         const ConvSrd sv = conv_srd(a.save[1]);
 #pragma unroll
                         for (int e = 0; e < 16; ++e) conv_st(sv, g0 + ((e & 3) + 8 * (e >> 2)) * cstride, x2[e]);
@@ -608,15 +617,15 @@ __global__ __launch_bounds__(kConvThreads) void conv_stack_kernel(const ConvArgs
                 for (int e = 0; e < 16; ++e) x2[e] = __builtin_amdgcn_fmed3f(acc2[e], 0.f, relu_hi);   // ReLU, or 0 outside the plane
                 if constexpr (TRAIN) {
                     if (a.mask[1] || a.save[1]) {
-                        const unsigned g0 = ((unsigned)(n * 32 + 4 * h) * T + tcol) * S + gr;   // channel (e&3) + 8(e>>2) + 4h
-                        const unsigned cstride = (unsigned)T * S;
+                        const unsigned g0 = ((unsigned)(n * 32 + 4 * h) * TG + w0 + tcol) * S + gr;   // channel (e&3) + 8(e>>2) + 4h
+                        const unsigned cstride = (unsigned)TG * S;
                         if (a.mask[1]) {
                             const ConvSrd m = conv_srd(a.mask[1]);
 #pragma unroll
                             for (int e = 0; e < 16; ++e)
                                 x2[e] = (ok2 && conv_ld(m, g0 + ((e & 3) + 8 * (e >> 2)) * cstride) > 0.f) ? acc2[e] : 0.f;
                         }
-                        if (a.save[1] && ok2 && own_row) {
+                        if (a.save[1] && ok2 && own_row && tcol >= lc0 && tcol < lc1) {
                             const ConvSrd sv = conv_srd(a.save[1]);
 #pragma unroll
                             for (int e = 0; e < 16; ++e) conv_st(sv, g0 + ((e & 3) + 8 * (e >> 2)) * cstride, x2[e]);
@@ -658,9 +667,9 @@ __global__ __launch_bounds__(kConvThreads) void conv_stack_kernel(const ConvArgs
 
     CSTAMP(7);
     // ---- conv4: 8 -> 1, no activation, rows of this band only; one thread = one row x 4 columns ----
-    const int tstrips = (T + 3) >> 2;
+    const int tstrips = (lc1 - lc0 + 3) >> 2;   // the owned columns only
     for (int i = tid; i < BR * tstrips; i += kConvThreads) {
-        const int ts = i / BR, lr = 4 + i - ts * BR, gr = gr0 + lr, t0 = 4 * ts;
+        const int ts = i / BR, lr = 4 + i - ts * BR, gr = gr0 + lr, t0 = lc0 + 4 * ts;
         if (gr >= S) continue;
         float acc[4];
 #pragma unroll
@@ -684,11 +693,11 @@ __global__ __launch_bounds__(kConvThreads) void conv_stack_kernel(const ConvArgs
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int t = t0 + q;
-            if (t >= T) break;
+            if (t >= lc1) break;
             if (TRAIN || a.mode == 0)
-                a.out_plane[((size_t)n * S + gr) * T + t] = acc[q];
+                a.out_plane[((size_t)n * S + gr) * TG + w0 + t] = acc[q];
             else
-                a.out_complex[(((size_t)frame * S + gr) * T + t) * 2 + part] = acc[q];
+                a.out_complex[(((size_t)frame * S + gr) * TG + w0 + t) * 2 + part] = acc[q];
         }
     }
     CSTAMP(8);
@@ -735,19 +744,82 @@ static bool plan_bands(int S, int T, int extra_floats, ConvArgs *a, size_t *lds_
     return false;
 }
 
+// Column tiles, for grids whose bands cannot hold all T columns (plan_bands fails: T > 64 at most) and under
+// AFT_CONV_COLUMN_TILES: row bands as in plan_bands, and each band's columns split into tiles of tcols owned columns that hold a
+// window of tcols + 8 columns (4 halo columns per side) in LDS.  Of the bands that leave room for at least one owned column, the one
+// with the fewest computed pixels per owned pixel; at least min_tiles tiles.  Overlapping column sweeps (no seam exchange): every
+// output element runs the same instructions whatever the band or tile, so its bits do not depend on the split.
+static bool plan_tiles(int S, int T, int extra_floats, int min_tiles, ConvArgs *a, size_t *lds_bytes) {
+    const int extra = (extra_floats + 3) & ~3;
+    double best = 0.0;
+    bool found = false;
+    for (int nb = 1; nb <= S; ++nb) {
+        if (S % nb) continue;
+        const int br = S / nb;
+        const int rows3 = nb == 1 ? br : br + 2;
+        const int ntiles = (rows3 + kTileRows - 1) / kTileRows;
+        if (ntiles > kConvWaves) continue;
+        const int sp = std::max(br + 8, 4 + kTileRows * ntiles + 2);
+        const long room = (long)160 * 1024 / sizeof(float) - extra - 32 - 80 - 4;   // floats for the arena (- its rounding)
+        const int wmax = (int)std::min<long>(room / (17L * sp) - 2, (long)T + 8);   // window columns that fit
+        if (wmax < 9 || room < kWStage) continue;
+        int nct = std::max((T + wmax - 9) / (wmax - 8), std::min(min_tiles, T));
+        const int tcols = (T + nct - 1) / nct;
+        nct = (T + tcols - 1) / tcols;
+        const int win = std::min(tcols + 8, T);
+        const double cost = (double)nb * (br + 8) * nct * win / ((double)S * T);
+        if (found && cost >= best) continue;
+        found = true;
+        best = cost;
+        const int arena = (std::max(17 * (win + 2) * sp, kWStage) + 3) & ~3;
+        a->band_rows = br;
+        a->nbands = nb;
+        a->ntiles = ntiles;
+        a->SP = sp;
+        a->arena = arena;
+        a->extra = extra;
+        a->xoff = -1;                                                            // overlapping sweeps
+        a->nseg = std::max(1, std::min(kConvWaves / ntiles, win / 6));           // every wave a task, segments of >= 6 columns
+        a->nctiles = nct;
+        a->tcols = tcols;
+        *lds_bytes = sizeof(float) * ((size_t)arena + extra + 32 + 80);
+    }
+    return found;
+}
+
 bool conv_plan_ok(int S, int T, int extra_floats) {
     ConvArgs a{};
     size_t lds = 0;
-    return S > 0 && T > 0 && plan_bands(S, T, extra_floats, &a, &lds);
+    return S > 0 && T > 0 && (plan_bands(S, T, extra_floats, &a, &lds) || plan_tiles(S, T, extra_floats, 1, &a, &lds));
 }
 
 template <bool TRAIN, bool FIXED>
 static hipError_t launch_conv_geo(ConvArgs &a, int planes, size_t lds, hipStream_t st);
 
+// Grids without a band plan (or AFT_CONV_COLUMN_TILES): inference with the forward's inputs on planes of four to eight row tiles runs
+// the row-streaming kernel with column ranges sized by the LDS as well (k_conv_rows.hip); everything else -- training, the stage
+// entry points, taller planes, AFT_CONV_BANDED=1 -- the banded kernel with column tiles (row bands x column tiles).
+template <bool TRAIN>
+static hipError_t launch_conv_tiled(ConvArgs &a, int planes, int extra_floats, int min_tiles, hipStream_t st) {
+    // (planes of fewer than four row tiles would leave most of the row-streaming kernel's eight matrix waves idle: 24 x 140 ran its head
+    // at 4.5x the per-pixel time of 120 x 56 there; the banded kernel gives every wave a column segment)
+    if (!TRAIN && !switch_on(SW_CONV_BANDED) && a.S > 3 * kTileRows) {
+        a.rows_min_split = min_tiles;
+        if (conv_rows_ok(a, planes)) return launch_conv_rows(a, planes, st);
+        a.rows_min_split = 0;
+    }
+    size_t lds = 0;
+    if (!plan_tiles(a.S, a.T, extra_floats, min_tiles, &a, &lds)) return hipErrorInvalidValue;
+    a.stream_ok = 0;   // the streamed upsampler walks whole rows of the plane
+    return launch_conv_geo<TRAIN, false>(a, planes, lds, st);
+}
+
 template <bool TRAIN>
 static hipError_t launch_conv(ConvArgs &a, int planes, int extra_floats, hipStream_t st) {
     size_t lds = 0;
-    if (!plan_bands(a.S, a.T, extra_floats, &a, &lds, TRAIN)) return hipErrorInvalidValue;
+    if (switch_on(SW_CONV_COLUMN_TILES))   // A/B, tests: at least two column tiles (ranges) per plane, or the switch's value
+        return launch_conv_tiled<TRAIN>(a, planes, extra_floats, std::max(2, switch_int(SW_CONV_COLUMN_TILES, 2)), st);
+    if (!plan_bands(a.S, a.T, extra_floats, &a, &lds, TRAIN)) return launch_conv_tiled<TRAIN>(a, planes, extra_floats, 1, st);
     if (a.stream_ok < 0)   // streaming upsampler: 8 waves x 32 pixels x (pf / 4 + 1) partial sums inside the 16 conv1 / conv3 planes
         a.stream_ok = (a.pf % 8 == 0 && a.up_w && (reinterpret_cast<uintptr_t>(a.up_w) & 15) == 0 &&
                        (size_t)kConvWaves * 32 * (a.pf / 4 + 1) + a.SP <= (size_t)16 * (a.T + 2) * a.SP) ? 1 : 0;
@@ -791,7 +863,7 @@ static hipError_t launch_conv_geo(ConvArgs &a, int planes, size_t lds, hipStream
         return hipGetLastError();
     }
 #endif
-    hipLaunchKernelGGL((conv_stack_kernel<TRAIN, FIXED>), dim3(planes * a.nbands), dim3(kConvThreads), lds, st, a);
+    hipLaunchKernelGGL((conv_stack_kernel<TRAIN, FIXED>), dim3(planes * a.nbands * std::max(a.nctiles, 1)), dim3(kConvThreads), lds, st, a);
     return hipGetLastError();
 }
 

@@ -683,7 +683,12 @@ static int conv_rows_split(const ConvArgs &a, int planes) {
     while (planes * nsplit < cus && a.T / (nsplit * 2) >= 8) nsplit *= 2;     // column ranges of at least 8 columns
     // ranges are ceil(T / nsplit) columns wide: drop the ranges that would start behind the last column (T = 129, 16 ranges of 9
     // columns: the 16th would start at column 135 -- ADVICE r4), so that every workgroup of the launch owns at least one column
-    const int wcols = (a.T + nsplit - 1) / nsplit;
+    int wcols = (a.T + nsplit - 1) / nsplit;
+    if (a.rows_min_split > 0) {   // grids without a band plan: ranges no wider than the LDS holds, and at least rows_min_split of them
+        nsplit = std::max((a.T + wcols - 1) / wcols, std::min(a.rows_min_split, a.T));
+        while (nsplit < a.T && sizeof(float) * conv_rows_lds_floats(a.S, (a.T + nsplit - 1) / nsplit) > 160 * 1024) ++nsplit;
+        wcols = (a.T + nsplit - 1) / nsplit;
+    }
     return (a.T + wcols - 1) / wcols;
 }
 bool conv_rows_ok(const ConvArgs &a, int planes) {

@@ -21,10 +21,10 @@ any multiple of 8 up to 512, any num_head that divides it with heads of up to 12
 elements -- the tuned fragment-packed engine where its shape conditions hold (model_dim a multiple of 32 up to 256,
 head dims 8 .. 64 in steps of 8 except 56, patches of up to 16 elements), the row-major general engine elsewhere
 (``hip_engine_name()`` says which).  A configuration the reference accepts beyond that (a larger model_dim or
-head, a grid with no LDS band plan) is refused with a ``ValueError`` when the model is built on a HIP device --
+head) is refused with a ``ValueError`` when the model is built on a HIP device --
 before any training -- instead of failing in the first ``eval()`` forward.  The switch ``AFT_ALLOW_COMPOSITE=1`` opts into running such a model entirely on the
 PyTorch-ROCm composite (logged).  The TRAINING kernels cover what inference covers; where a block of an accepted
-model is nevertheless differentiated by PyTorch-ROCm autograd (switched off by hand, a conv grid without a band plan), the
+model is nevertheless differentiated by PyTorch-ROCm autograd (switched off by hand), the
 constructor logs a warning naming the block and the reason, and ``training_backends()`` returns the same.
 """
 from __future__ import annotations
@@ -231,7 +231,7 @@ class BaseFortiTranEstimator(nn.Module):
         device; a string = it is differentiated by PyTorch-ROCm autograd and why (reference trainer.py:195-233 trains
         whatever encoders.py:44-51 builds).  The dense layers, the adapter MLPs and the loss glue are not listed: always HIP / torch."""
         from .hip_ops import conv_enhancer_covered
-        conv_gap = None if conv_enhancer_covered(*self.ofdm_size) else f"no LDS band plan of the fused conv-stack kernel for a {self.ofdm_size} grid"
+        conv_gap = None if conv_enhancer_covered(*self.ofdm_size) else f"the fused conv-stack kernel does not take a {self.ofdm_size} grid"
         return {"transformer_encoder": self.transformer_encoder.hip_train_gap(),
                 "initial_enhancer / final_refiner": conv_gap}
 

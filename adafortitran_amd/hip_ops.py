@@ -30,7 +30,7 @@ def config_coverage(cfg: _abi.AftConfig) -> Optional[str]:
 
 
 def conv_enhancer_covered(num_scs: int, num_symbols: int) -> bool:
-    """True when the fused conv-stack kernel has an LDS band plan for this grid (training path)."""
+    """True when the fused conv-stack kernel has a plan for this grid (row bands and, past what a band holds, column tiles)."""
     return _lib.load().aft_conv_enhancer_scratch_bytes(1, int(num_scs), int(num_symbols)) > 0
 
 

@@ -306,7 +306,8 @@ int aft_conv_enhancer_fwd_train_f32(const float *const weights[4], const float *
  * overwritten, or added to when accumulate != 0).  weights[k] are the module's conv weights as in the forward call:
  * the data gradient of the stack is the stack itself run on dy with weights[3-k].transpose(0,1).flip(2,3), which the
  * call lays out in its scratch (one small kernel).
- * aft_conv_enhancer_scratch_bytes returns 0 for a grid the fused kernel has no LDS band plan for. */
+ * aft_conv_enhancer_scratch_bytes returns 0 for an empty grid and for one whose single plane's conv2 activations pass 2 GiB; every
+ * other grid has a plan (row bands, and column tiles where a band cannot hold all of the grid's symbols). */
 size_t aft_conv_enhancer_scratch_bytes(int planes, int num_scs, int num_symbols);
 int aft_conv_enhancer_bwd_f32(const float *const weights[4], const float *x, const float *c1, const float *c2,
                               const float *c3, const float *dy, float *dx, float *const dweights[4], float *const dbiases[4],
