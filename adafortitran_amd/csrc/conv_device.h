@@ -30,7 +30,6 @@ struct ConvArgs {
     unsigned long long *stamps;   // diagnostic build only (AFT_DIAG_STAMPS): per-workgroup s_memtime at the phase boundaries
     int plane0;                   // conv_stream16_kernel: first plane of this launch (a forward may launch its planes in two parts)
     const float *wfrag;           // conv_stream16_kernel: this stack's conv2 / conv3 weights as 16x16x4 operand fragments (conv_frag16_entry)
-    int ranges;                   // conv_stream_kernel<., true> (training): column ranges a plane is split into (1 | 2 | 4; 0 = 1)
     int nctiles, tcols;           // conv_stack_kernel<., false>: column tiles per plane (0 = 1: the whole plane) of tcols owned columns each
     int rows_min_split;           // conv_rows kernels: 0 = column ranges by the batch only; n > 0 = also by the LDS, at least n ranges
 };
@@ -166,14 +165,14 @@ inline bool upsample_planes_ok(const float *up_w, int pf) {
     return pf % 4 == 0 && upsample_planes_lds(pf) <= 64 * 1024 && (reinterpret_cast<uintptr_t>(up_w) & 15) == 0;   // (config 5: 96 pilots = 50 176 B)
 }
 
-// k_conv_stream.hip: default grid, inference, head with pre-computed upsampled planes (a.in_plane) or tail on linear_2's output
-// (a.lin2_out); returns hipErrorNotSupported when the arguments need the banded kernel
 // the fragment image (kFragFloats floats) of one ConvEnhancer from its four conv weights / biases (cb NULL: no biases), k_conv_stream.hip
 hipError_t launch_conv_frag_pack(const float *const cw[4], const float *const cb[4], float *dst, hipStream_t st);
+// k_conv_stream.hip: default grid with a fragment image (a.wfrag), head with pre-computed upsampled planes (a.in_plane), tail on
+// linear_2's output (a.lin2_out) or training (plain planes); returns hipErrorNotSupported when the arguments need the banded kernel
 bool conv_stream_ok(const ConvArgs &a);
 hipError_t launch_conv_stream(ConvArgs &a, int planes, hipStream_t st);
-// k_conv_rows.hip: inference on grids whose planes need more than one band in k_conv.hip (config 5): whole-height workgroups that
-// stream over the columns through ring buffers; returns hipErrorNotSupported when the arguments need the banded kernel
+// k_conv_rows.hip: inference with a fragment image on grids whose planes need more than one band in k_conv.hip (config 5): whole-height
+// workgroups that stream over the columns through ring buffers; returns hipErrorNotSupported when the arguments need the banded kernel
 bool conv_rows_ok(const ConvArgs &a, int planes);
 hipError_t launch_conv_rows(ConvArgs &a, int planes, hipStream_t st);
 

@@ -13,7 +13,6 @@
     X(CONV_NSPLIT, "AFT_CONV_NSPLIT", "1 | 2 | 4 column ranges per plane in the streaming conv kernels (default: by the batch)") \
     X(CONV_BANDED, "AFT_CONV_BANDED", "the banded conv kernel instead of the column- / row-streaming ones") \
     X(CONV_COLUMN_TILES, "AFT_CONV_COLUMN_TILES", "the column-tiled conv path even where a band plan fits; n > 2 = at least n tiles per plane") \
-    X(CONV_MFMA32, "AFT_CONV_MFMA32", "round 4's 32x32x2 streaming conv kernels instead of the 16x16x4 ones (also in training)") \
     X(GEMM_BM, "AFT_GEMM_BM", "64 | 96: row tile of the training GEMM (default: by the shape)") \
     X(EMBED_ANY_OLD, "AFT_EMBED_ANY_OLD", "the general engine's own embedding kernel instead of the training path's") \
     X(EMBED_BWD_GENERIC, "AFT_EMBED_BWD_GENERIC", "the vector embedding backward instead of the MFMA one (model_dim 128)") \

@@ -296,7 +296,8 @@ int aft_dense_bwd_f32(const float *x, const float *weight, const float *dy, floa
  * are conv_block.{0,2,4,6}.{weight,bias} in PyTorch layout.  c1, c2, c3 receive the activations the
  * backward needs: f32 [planes, C, T, S] with C = 8, 32, 8 (an internal layout; treat as opaque).
  * `scratch`: aft_conv_enhancer_fwd_scratch_bytes() bytes the call may overwrite (the weights re-laid as MFMA operand fragments for the
- * default grid's kernel; ABI 7), or NULL = the kernels that read the weights in place. */
+ * default grid's kernel; ABI 7), or NULL = the kernels that read the weights in place (on the default grid: results that agree with
+ * the scratch call's to rounding, not bit for bit). */
 size_t aft_conv_enhancer_fwd_scratch_bytes(int planes, int num_scs, int num_symbols);
 int aft_conv_enhancer_fwd_train_f32(const float *const weights[4], const float *const biases[4], const float *x, float *y,
                                     float *c1, float *c2, float *c3, void *scratch, size_t scratch_bytes, int planes, int num_scs,

@@ -99,7 +99,7 @@ def test_switches_are_read_once_and_change_through_the_abi_only(switches):
 def test_unknown_switch_names_are_refused():
     """A misspelled switch must not pass silently (a test that sets one would compare the product path with itself):
     aft_set_switch refuses a name csrc/switches.h does not declare, aft_get_switch returns -1 for it."""
-    for name in ("AFT_LANE", "AFT_TRAIN_UNFUSED_FORWARD", "AFT_ATTN_HD16_MFMA32", "AFT_BATCH", "PATH"):
+    for name in ("AFT_LANE", "AFT_TRAIN_UNFUSED_FORWARD", "AFT_ATTN_HD16_MFMA32", "AFT_CONV_MFMA32", "AFT_BATCH", "PATH"):
         with pytest.raises(ValueError, match=name):
             _lib.set_switch(name, "1")
         with pytest.raises(ValueError, match=name):
@@ -244,11 +244,12 @@ def test_hot_kernels_have_no_register_spills():
             m = re.search(r"VGPRs Spill: (\d+)", line)
             if m and name:
                 report[name] = int(m.group(1))
-    spills = {k: v for k, v in report.items() if "attn_kernelILi32E" in k or "attn16_kernel" in k or "conv_stream_kernel" in k or "conv_stream16_kernel" in k}
-    # attention HD 32 (generic, 280 tokens, 1120 tokens), conv stream head / tail (conv_stream16_kernel x 1 / 2 / 4 column ranges and
-    # the 32x32x2 kernel) / training
-    # (round 6: + the three training instantiations of conv_stream16_kernel, + attn16_kernel<0 | 280, 16 | 8>: head dims 16 / 8 on 16x16x4 MFMAs)
-    assert len(spills) == 19 and all(v == 0 for v in spills.values()), report
+    spills = {k: v for k, v in report.items() if "attn_kernelILi32E" in k or "attn16_kernel" in k or "conv_stream16_kernel" in k}
+    # attention HD 32 (generic, 280 tokens, 1120 tokens), conv stream head / tail / training (conv_stream16_kernel x 1 / 2 / 4 column
+    # ranges), attn16_kernel<0 | 280, 16 | 8>: head dims 16 / 8 on 16x16x4 MFMAs
+    assert len(spills) == 16 and all(v == 0 for v in spills.values()), report
+    # the 32x32x2 streaming conv kernels are retired: the default grid and tall planes run the 16x16x4 ones only
+    assert not any("conv_stream_kernelI" in k or "conv_rows_kernelI" in k for k in report), report
     # the 32x32x2 forms of head dims 16 and 8 are retired: those heads run attn16_kernel only
     assert not any("attn_kernelILi16E" in k or "attn_kernelILi8E" in k for k in report), report
     assert all(v <= 4 for k, v in report.items() if "attn_kernelILi64E" in k), report
@@ -256,5 +257,5 @@ def test_hot_kernels_have_no_register_spills():
     # 168 registers three waves per SIMD allow: a scratch reload is a VMEM load whose wait drains vmcnt
     chain = {k: v for k, v in report.items() if "chain_fwd_train_kernel" in k or "chain_bwd_kernel" in k}
     assert len(chain) == 8 and all(v == 0 for v in chain.values()), report      # forward: act x tail; backward: act x partial-last-tile
-    rows = {k: v for k, v in report.items() if "conv_rows_kernel" in k}      # head / tail of the row-streaming conv kernel (226 VGPRs)
+    rows = {k: v for k, v in report.items() if "conv_rows16_kernel" in k}    # head / tail of the row-streaming conv kernel (246 VGPRs)
     assert len(rows) == 2 and all(v == 0 for v in rows.values()), report

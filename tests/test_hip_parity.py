@@ -296,10 +296,6 @@ def test_tall_planes_run_the_row_streaming_conv_kernel(oracle_lib, switches, ofd
     assert np.abs(out.cpu().numpy() - ref).max() <= TOL_HIP_OUT * np.abs(ref).max()
     # the head stage of the kernel the forward launched (conv_rows16_kernel), straight from the workspace
     assert max_rel(eng.forward_region("conv_enhanced", batch).cpu().numpy(), dump["conv_enhanced"]) <= TOL_HIP_OUT
-    switches.set("AFT_CONV_MFMA32", "1")                             # round 4's 32x32x2 row-streaming kernel: rounding-level agreement
-    mfma32 = eng.forward(pil, *meta).clone()
-    switches.unset("AFT_CONV_MFMA32")
-    assert float((mfma32 - out).abs().max()) <= 2e-6 * float(out.abs().max())
     eng.workspace(batch).view(torch.float32).fill_(float("nan"))           # stale workspace: same bits
     assert torch.equal(torch.view_as_real(eng.forward(pil, *meta)), torch.view_as_real(out))
     switches.set("AFT_CONV_BANDED", "1")

@@ -456,7 +456,7 @@ def test_conv_enhancer_forward_backward_matches_autograd(S, T, n):
 
 @pytest.mark.parametrize("n", [3, 10, 130])
 def test_training_conv_column_ranges_reproduce_whole_planes(n, switches):
-    """With fewer planes than CUs the training conv kernel (conv_stream_kernel<0, true>, forward and data gradient) splits every
+    """With fewer planes than CUs the training conv kernel (conv_stream16_kernel<0, NSPLIT, true>, forward and data gradient) splits every
     plane of the default grid into 2 or 4 column ranges that recompute their neighbours' edge columns (64 frames -- the reference's
     default batch -- are 128 planes on 256 CUs): the output, the three saved activations' consumers (the data gradient and every
     weight gradient) carry the same BITS whatever the split."""
@@ -482,6 +482,43 @@ def test_training_conv_column_ranges_reproduce_whole_planes(n, switches):
         got = run(split)
         for i, (a, b) in enumerate(zip(got, ref)):
             assert torch.equal(a, b), (split, i)
+
+
+def test_conv_forward_without_scratch_reads_the_weights_in_place():
+    """aft_conv_enhancer_fwd_train_f32 with scratch == NULL on the default grid runs the banded training kernel (conv_stack_kernel<true,
+    ...>, weights read in place) instead of conv_stream16_kernel on a fragment image: the output and the three saved activations agree
+    with the scratch call's to rounding (conv2 .. conv4 summed in another order), and the output with PyTorch's forward."""
+    import ctypes as C
+    import adafortitran_amd.blocks as blocks
+    from adafortitran_amd import _lib
+    from adafortitran_amd.training import _ptr4
+    S, T, n = 120, 14, 6
+    torch.manual_seed(5)
+    enh = blocks.ConvEnhancer().cuda()
+    x = torch.randn(n, 1, S, T, device="cuda")
+    convs = [enh.conv_block[i] for i in (0, 2, 4, 6)]
+    ws = [c.weight.detach().contiguous() for c in convs]
+    bs = [c.bias.detach().contiguous() for c in convs]
+    lib = _lib.load()
+
+    def run(with_scratch):
+        y = torch.empty_like(x)
+        saved = [torch.empty((n, ch, T, S), device="cuda") for ch in (8, 32, 8)]
+        nbytes = lib.aft_conv_enhancer_fwd_scratch_bytes(n, S, T) if with_scratch else 0
+        scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device="cuda")
+        _lib.check(lib.aft_conv_enhancer_fwd_train_f32(C.byref(_ptr4(ws)), C.byref(_ptr4(bs)), x.data_ptr(), y.data_ptr(),
+                                                       *[t.data_ptr() for t in saved], scratch.data_ptr() if with_scratch else None,
+                                                       nbytes, n, S, T, _lib.current_stream_ptr(x.device)))
+        torch.cuda.synchronize()
+        return [y] + saved
+
+    frag, in_place = run(True), run(False)
+    for name, a, b in zip(("y", "c1", "c2", "c3"), in_place, frag):
+        assert float((a - b).abs().max()) <= 2e-6 * float(b.abs().max()), name
+    enh.hip_training = False
+    with torch.no_grad():
+        ref = enh(x)
+    assert _rel(in_place[0], ref) <= 2e-5
 
 
 @pytest.mark.parametrize("rows,in_f,out_f,bias", [(560, 12, 128, True), (561, 6, 128, True), (1120, 128, 6, True),
