@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes as C
 from typing import Callable, Dict, Optional
 
-AFT_ABI_VERSION = 8
+AFT_ABI_VERSION = 9
 AFT_ENGINE_PACKED, AFT_ENGINE_GENERAL = 0, 1
 AFT_OK, AFT_ERR_ARG, AFT_ERR_SHAPE, AFT_ERR_HIP = 0, 1, 2, 3
 AFT_ACT_RELU, AFT_ACT_GELU = 0, 1
@@ -49,6 +49,13 @@ LAYER_PARAM_NAMES = ("self_attn.in_proj_weight", "self_attn.in_proj_bias", "self
 
 class AftLayerGrads(C.Structure):
     _fields_ = [(n, _fp) for n in LAYER_FIELDS]
+
+
+class AftStepControl(C.Structure):
+    """aft_step_control: 32 bytes of device memory between the preparation launch and the Adam launch (optim.py keeps it as
+    eight int32 words and views the float fields)."""
+    _fields_ = [("skip", C.c_int32), ("step", C.c_int32), ("grad_scale", C.c_float), ("inv_bc1", C.c_float),
+                ("inv_sqrt_bc2", C.c_float), ("grad_norm", C.c_float), ("clip_coef", C.c_float), ("reserved", C.c_int32)]
 
 
 class AftWeights(C.Structure):
@@ -141,6 +148,7 @@ EXPORTED_SYMBOLS = (
     "aft_stage_tail_f32", "aft_profile_kernel_f32", "aft_debug_fill_lds_f32", "aft_debug_peek_lds_f32", "aft_pilot_gather_f32", "aft_ls_mse_db_f32",
     "aft_encoder_tape_bytes", "aft_encoder_train_scratch_bytes",
     "aft_encoder_layer_fwd_train_f32", "aft_encoder_layer_fwd_train_chained_f32", "aft_encoder_layer_bwd_f32", "aft_adam_step_f32",
+    "aft_grad_sumsq_scratch_bytes", "aft_grad_sumsq_f32", "aft_adam_prepare_f32", "aft_adam_step_ctrl_f32", "aft_grad_clip_f32",
     "aft_conv_enhancer_fwd_train_f32", "aft_conv_enhancer_scratch_bytes", "aft_conv_enhancer_fwd_scratch_bytes", "aft_conv_enhancer_bwd_f32",
     "aft_dense_fwd_f32", "aft_dense_bwd_scratch_bytes", "aft_dense_bwd_f32",
     "aft_adapter_fwd_train_f32", "aft_adapter_bwd_f32",
@@ -150,6 +158,6 @@ EXPORTED_SYMBOLS = (
 #: size queries (return size_t, not a status code)
 SIZE_SYMBOLS = ("aft_workspace_bytes", "aft_packed_weights_bytes", "aft_encoder_tape_bytes", "aft_encoder_train_scratch_bytes",
                 "aft_conv_enhancer_scratch_bytes", "aft_conv_enhancer_fwd_scratch_bytes", "aft_dense_bwd_scratch_bytes",
-                "aft_embed_bwd_scratch_bytes", "aft_tail_bwd_scratch_bytes")
+                "aft_embed_bwd_scratch_bytes", "aft_tail_bwd_scratch_bytes", "aft_grad_sumsq_scratch_bytes")
 REGION_IDS = {"conv_enhanced": 0, "tokens6": 1, "enc_out": 2}   # aft_workspace_region
 KERNEL_IDS = {"upsample": 0, "embed": 1, "qkv": 2, "attention": 3, "chain": 4, "tail": 5, "chain_last": 6, "encoder_plane": 7, "prologue": 8}

@@ -113,6 +113,12 @@ def load_path(path: str):
     lib.aft_tail_fwd_train_f32.argtypes = [vp] * 5 + i6 + [vp]
     lib.aft_tail_bwd_f32.argtypes = [vp] * 6 + [C.c_int, vp, C.c_size_t] + i6 + [vp]
     lib.aft_adam_step_f32.argtypes = [vp, vp, vp, vp, C.c_size_t] + [C.c_float] * 6 + [C.c_int, vp]
+    lib.aft_grad_sumsq_scratch_bytes.restype = C.c_size_t
+    lib.aft_grad_sumsq_scratch_bytes.argtypes = [C.c_size_t]
+    lib.aft_grad_sumsq_f32.argtypes = [vp, C.c_size_t, vp, C.c_size_t, vp, vp, vp]
+    lib.aft_adam_prepare_f32.argtypes = [vp, vp, vp, vp, C.c_double, C.c_double, C.c_float, C.c_float, vp]
+    lib.aft_adam_step_ctrl_f32.argtypes = [vp, vp, vp, vp, C.c_size_t] + [C.c_float] * 5 + [vp, vp]
+    lib.aft_grad_clip_f32.argtypes = [vp, C.c_size_t, vp, C.c_double, C.c_double, vp, vp]
     for name in _abi.EXPORTED_SYMBOLS:
         if name not in _abi.SIZE_SYMBOLS + ("aft_version", "aft_last_error", "aft_max_batch"):
             getattr(lib, name).restype = C.c_int

@@ -401,5 +401,16 @@ hipError_t launch_tail_train_bwd(const float *x, const float *w2, const float *d
                                  float *slices, int planes, int S, int T, int p0, int p1, int d, hipStream_t st);
 hipError_t launch_adam(float *p, const float *g, float *m, float *v, size_t n, float lr, float b1, float b2, float eps,
                        float wd, float grad_scale, int step, hipStream_t st);
+// the optimizer step's decisions on the device (k_train.hip): two-stage squared norm, preparation of the control block, Adam reading it
+constexpr size_t kSumsqChunk = 4096;   // floats per workgroup of the squared norm: fixed, so the sum's bits depend on the data and n alone
+size_t grad_sumsq_blocks(size_t n);
+hipError_t launch_grad_sumsq(const float *g, size_t n, double *partial, uint32_t *flag, double *sumsq, float *nonfinite,
+                             hipStream_t st);
+hipError_t launch_adam_prepare(aft_step_control *ctrl, const double *sumsq, const float *found_inf, const float *grad_scale,
+                               double host_scale, double max_norm, float b1, float b2, hipStream_t st);
+hipError_t launch_adam_ctrl(float *p, const float *g, float *m, float *v, size_t n, float lr, float b1, float b2, float eps,
+                            float wd, const aft_step_control *ctrl, hipStream_t st);
+hipError_t launch_grad_clip(float *g, size_t n, const double *sumsq, double pre_scale, double max_norm, float *norm_out,
+                            hipStream_t st);
 
 }  // namespace aft

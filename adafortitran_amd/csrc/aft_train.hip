@@ -521,4 +521,60 @@ int aft_adam_step_f32(float *param, const float *grad, float *exp_avg, float *ex
     return AFT_OK;
 }
 
+// scratch of the squared norm: [blocks] float64 partials, then [blocks] uint32 non-finite flags
+size_t aft_grad_sumsq_scratch_bytes(size_t n) {
+    if (n == 0 || n > ((size_t)1 << 40)) return 0;
+    return (grad_sumsq_blocks(n) * 12 + 15) / 16 * 16;
+}
+
+int aft_grad_sumsq_f32(const float *grad, size_t n, void *scratch, size_t scratch_bytes, double *sumsq, float *nonfinite,
+                       void *stream) {
+    if (!grad || !scratch || !sumsq || !nonfinite || n == 0 || n > ((size_t)1 << 40)) {
+        set_error("bad squared-norm argument (NULL pointer, or n = %zu outside 1 .. 2^40)", n);
+        return AFT_ERR_ARG;
+    }
+    if (((uintptr_t)grad & 15) || ((uintptr_t)scratch & 7) || scratch_bytes < aft_grad_sumsq_scratch_bytes(n)) {
+        set_error("squared norm: grad must be 16-byte aligned and scratch 8-byte aligned with at least %zu bytes (got %zu)",
+                  aft_grad_sumsq_scratch_bytes(n), scratch_bytes);
+        return AFT_ERR_ARG;
+    }
+    double *partial = static_cast<double *>(scratch);
+    STEP("grad sumsq", launch_grad_sumsq(grad, n, partial, reinterpret_cast<uint32_t *>(partial + grad_sumsq_blocks(n)), sumsq,
+                                         nonfinite, static_cast<hipStream_t>(stream)));
+    return AFT_OK;
+}
+
+int aft_adam_prepare_f32(aft_step_control *ctrl, const double *sumsq, const float *found_inf, const float *grad_scale,
+                         double host_scale, double max_norm, float beta1, float beta2, void *stream) {
+    if (!ctrl || (sumsq && !(max_norm >= 0.0))) {
+        set_error("bad Adam preparation argument (NULL control block, or max_norm %g with a squared norm)", max_norm);
+        return AFT_ERR_ARG;
+    }
+    STEP("adam prepare", launch_adam_prepare(ctrl, sumsq, found_inf, grad_scale, host_scale, max_norm, beta1, beta2,
+                                             static_cast<hipStream_t>(stream)));
+    return AFT_OK;
+}
+
+int aft_adam_step_ctrl_f32(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, size_t n, float lr, float beta1,
+                           float beta2, float eps, float weight_decay, const aft_step_control *ctrl, void *stream) {
+    if (!param || !grad || !exp_avg || !exp_avg_sq || !ctrl || n == 0) {
+        set_error("bad Adam argument (NULL pointer or n = 0)");
+        return AFT_ERR_ARG;
+    }
+    STEP("adam", launch_adam_ctrl(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, ctrl,
+                                  static_cast<hipStream_t>(stream)));
+    return AFT_OK;
+}
+
+int aft_grad_clip_f32(float *grad, size_t n, const double *sumsq, double pre_scale, double max_norm, float *norm_out,
+                      void *stream) {
+    if (!grad || !sumsq || !norm_out || n == 0 || (n & 3) || ((uintptr_t)grad & 15) || !(max_norm >= 0.0)) {
+        set_error("bad gradient clipping argument (NULL pointer, n = %zu not a positive multiple of 4, grad not 16-byte aligned, "
+                  "or max_norm %g)", n, max_norm);
+        return AFT_ERR_ARG;
+    }
+    STEP("grad clip", launch_grad_clip(grad, n, sumsq, pre_scale, max_norm, norm_out, static_cast<hipStream_t>(stream)));
+    return AFT_OK;
+}
+
 }  // extern "C"

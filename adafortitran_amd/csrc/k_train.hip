@@ -307,11 +307,9 @@ __global__ __launch_bounds__(256) void add_kernel(const float *__restrict__ a, c
 // torch.optim.Adam (reference src/main/trainer.py:407-413, no amsgrad), one pass over a flat parameter shard:
 //   g = grad * grad_scale + wd * p;  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2
 //   p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
-__global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
-                                                   float *__restrict__ v, size_t n, float lr, float b1, float b2, float eps,
-                                                   float wd, float grad_scale, float inv_bc1, float inv_sqrt_bc2) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
+__device__ __forceinline__ void adam_element(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
+                                             float *__restrict__ v, size_t i, float lr, float b1, float b2, float eps, float wd,
+                                             float grad_scale, float inv_bc1, float inv_sqrt_bc2) {
     const float pw = p[i];
     const float gr = g[i] * grad_scale + wd * pw;
     const float mn = b1 * m[i] + (1.f - b1) * gr;
@@ -321,11 +319,177 @@ __global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, const 
     p[i] = pw - lr * inv_bc1 * mn / (sqrtf(vn) * inv_sqrt_bc2 + eps);
 }
 
+__global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
+                                                   float *__restrict__ v, size_t n, float lr, float b1, float b2, float eps,
+                                                   float wd, float grad_scale, float inv_bc1, float inv_sqrt_bc2) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    adam_element(p, g, m, v, i, lr, b1, b2, eps, wd, grad_scale, inv_bc1, inv_sqrt_bc2);
+}
+
 hipError_t launch_adam(float *p, const float *g, float *m, float *v, size_t n, float lr, float b1, float b2, float eps,
                        float wd, float grad_scale, int step, hipStream_t st) {
     const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
     hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p, g, m, v, n, lr, b1, b2, eps, wd,
                        grad_scale, (float)(1.0 / bc1), (float)(1.0 / sqrt(bc2)));
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// The decisions around optimizer.step() on the device (clip_grad_norm_, GradScaler's skip, the step count):
+//   grad_sumsq_kernel -> sum_partials_kernel -> [all-reduce of the scalar] -> adam_prepare_kernel -> adam_ctrl_kernel
+// Nothing here is read by the host; the control block (aft_step_control) carries the decisions from launch to launch.
+//
+// Squared norm, deterministic and atomics-free.  The bits are a function of the data and of n alone: workgroup b owns elements
+// [b kSumsqChunk, (b + 1) kSumsqChunk) whatever the device; lane t takes the 16-byte piece j * 256 + t of the chunk for
+// j = 0..3 and adds its four squares in element order into ONE float64 (the square of an fp32 value is exact in float64, so only
+// the order of the additions matters); lanes combine by the xor butterfly 32, 16, .., 1, the four waves in wave order.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+// sum over a 256-thread workgroup (every wave's butterfly result, added in wave order); valid in thread 0
+__device__ __forceinline__ double block_sum_f64(double v, double *lds4) {
+    v = wave_sum_f64(v);
+    if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((lds4[0] + lds4[1]) + lds4[2]) + lds4[3];
+}
+
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float *__restrict__ g, size_t n, double *__restrict__ partial,
+                                                         uint32_t *__restrict__ flag) {
+    __shared__ double lds4[4];
+    const size_t base = (size_t)blockIdx.x * kSumsqChunk;
+    double acc = 0.0;
+#pragma unroll
+    for (int j = 0; j < kSumsqChunk / 1024; ++j) {
+        const size_t e = base + (size_t)(j * 256 + threadIdx.x) * 4;
+        if (e + 4 <= n) {
+            const f32x4 x = *reinterpret_cast<const f32x4 *>(g + e);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) acc += (double)x[c] * (double)x[c];
+        } else {
+            for (size_t i = e; i < n; ++i) acc += (double)g[i] * (double)g[i];   // the last piece of a buffer whose n is no multiple of 4
+        }
+    }
+    const double s = block_sum_f64(acc, lds4);
+    if (threadIdx.x == 0) {
+        partial[blockIdx.x] = s;
+        // finite fp32 squares cannot overflow a float64 sum: the partial is non-finite exactly when an element is inf / nan
+        flag[blockIdx.x] = isfinite(s) ? 0u : 1u;
+    }
+}
+
+// Stage 2, one workgroup: thread t adds partials t, t + 256, .. in that order, then the same butterfly and wave order as above --
+// an order that depends on `count` alone.  (A device function so that other two-stage reductions can end in it.)
+__device__ __forceinline__ double sum_partials_f64(const double *__restrict__ partial, size_t count, double *lds4) {
+    double acc = 0.0;
+    for (size_t i = threadIdx.x; i < count; i += 256) acc += partial[i];
+    return block_sum_f64(acc, lds4);
+}
+
+__global__ __launch_bounds__(256) void sum_partials_kernel(const double *__restrict__ partial, const uint32_t *__restrict__ flag,
+                                                           size_t count, double *__restrict__ sumsq, float *__restrict__ nonfinite) {
+    __shared__ double lds4[4];
+    __shared__ uint32_t any[4];
+    uint32_t f = 0;
+    for (size_t i = threadIdx.x; i < count; i += 256) f |= flag[i];
+    const bool wave_any = __any(f != 0);
+    if ((threadIdx.x & 63) == 0) any[threadIdx.x >> 6] = wave_any ? 1u : 0u;
+    const double s = sum_partials_f64(partial, count, lds4);   // (its barrier also publishes any[])
+    if (threadIdx.x == 0) {
+        *sumsq = s;
+        *nonfinite = (any[0] | any[1] | any[2] | any[3]) ? 1.f : 0.f;
+    }
+}
+
+size_t grad_sumsq_blocks(size_t n) { return (n + kSumsqChunk - 1) / kSumsqChunk; }
+
+hipError_t launch_grad_sumsq(const float *g, size_t n, double *partial, uint32_t *flag, double *sumsq, float *nonfinite,
+                             hipStream_t st) {
+    const size_t blocks = grad_sumsq_blocks(n);
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)blocks), dim3(256), 0, st, g, n, partial, flag);
+    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, st, partial, flag, blocks, sumsq, nonfinite);
+    return hipGetLastError();
+}
+
+// The step's decisions, one thread.  Everything in float64, in the order ShardedFlatAdam's CPU path takes them in Python:
+//   skip  = found_inf > 0                                    (GradScaler; a nan flag does not skip, as `float(nan) > 0` does not)
+//   scale = host_scale / grad_scale
+//   norm  = sqrt(sumsq * scale * scale);   scale *= min(1, max_norm / (norm + 1e-6))        (clip_grad_norm_'s coefficient)
+// Non-finite sumsq without a scaler: the rule is Python's `min(1.0, c)`, which returns c only when c < 1.0 -- a nan norm (a nan
+// gradient element) leaves the scale UNCLIPPED, an infinite norm (an inf element) gives c = 0 and with it scale 0.  Either way the
+// non-finite elements then poison their own parameters through the update, exactly as on the CPU path.
+__global__ void adam_prepare_kernel(aft_step_control *__restrict__ ctrl, const double *__restrict__ sumsq,
+                                    const float *__restrict__ found_inf, const float *__restrict__ grad_scale, double host_scale,
+                                    double max_norm, double b1, double b2) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const bool skip = found_inf != nullptr && *found_inf > 0.f;
+    double scale = grad_scale != nullptr ? host_scale * (1.0 / (double)*grad_scale) : host_scale;
+    if (sumsq != nullptr) {
+        const double norm = sqrt(*sumsq * scale * scale);
+        const double c = max_norm / (norm + 1e-6);
+        ctrl->clip_coef = (float)(c < 1.0 ? c : 1.0);
+        scale *= c < 1.0 ? c : 1.0;
+        ctrl->grad_norm = (float)norm;
+    }
+    const int t = ctrl->step + (skip ? 0 : 1);   // the count of APPLIED steps: a skipped step leaves the bias correction where it was
+    const double bc1 = 1.0 - pow(b1, (double)(t > 0 ? t : 1)), bc2 = 1.0 - pow(b2, (double)(t > 0 ? t : 1));
+    ctrl->skip = skip ? 1 : 0;
+    ctrl->step = t;
+    ctrl->grad_scale = (float)scale;
+    ctrl->inv_bc1 = (float)(1.0 / bc1);
+    ctrl->inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+}
+
+hipError_t launch_adam_prepare(aft_step_control *ctrl, const double *sumsq, const float *found_inf, const float *grad_scale,
+                               double host_scale, double max_norm, float b1, float b2, hipStream_t st) {
+    hipLaunchKernelGGL(adam_prepare_kernel, dim3(1), dim3(64), 0, st, ctrl, sumsq, found_inf, grad_scale, host_scale, max_norm,
+                       (double)b1, (double)b2);
+    return hipGetLastError();
+}
+
+// adam_kernel with the gradient scale and the bias corrections read from the control block; a skipped step stores nothing
+__global__ __launch_bounds__(256) void adam_ctrl_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
+                                                        float *__restrict__ v, size_t n, float lr, float b1, float b2, float eps,
+                                                        float wd, const aft_step_control *__restrict__ ctrl) {
+    if (ctrl->skip) return;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    adam_element(p, g, m, v, i, lr, b1, b2, eps, wd, ctrl->grad_scale, ctrl->inv_bc1, ctrl->inv_sqrt_bc2);
+}
+
+hipError_t launch_adam_ctrl(float *p, const float *g, float *m, float *v, size_t n, float lr, float b1, float b2, float eps,
+                            float wd, const aft_step_control *ctrl, hipStream_t st) {
+    hipLaunchKernelGGL(adam_ctrl_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p, g, m, v, n, lr, b1, b2, eps, wd,
+                       ctrl);
+    return hipGetLastError();
+}
+
+// grad *= min(1, max_norm / (norm + 1e-6)),  norm = sqrt(sumsq) * pre_scale: torch.nn.utils.clip_grad_norm_ on the flat buffer for
+// the reference's call order (unscale_ -> clip -> scaler.step).  Every thread derives the coefficient from the device scalar
+// (same rule for a non-finite norm as adam_prepare_kernel); thread 0 of the grid leaves the norm for the caller.
+__global__ __launch_bounds__(256) void grad_clip_kernel(float *__restrict__ g, size_t n4, const double *__restrict__ sumsq,
+                                                        double pre_scale, double max_norm, float *__restrict__ norm_out) {
+    const double norm = sqrt(*sumsq * pre_scale * pre_scale);
+    const double c = max_norm / (norm + 1e-6);
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) *norm_out = (float)norm;
+    if (!(c < 1.0) || i >= n4) return;
+    const float cf = (float)c;
+    f32x4 x = reinterpret_cast<f32x4 *>(g)[i];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) x[k] *= cf;
+    reinterpret_cast<f32x4 *>(g)[i] = x;
+}
+
+hipError_t launch_grad_clip(float *g, size_t n, const double *sumsq, double pre_scale, double max_norm, float *norm_out,
+                            hipStream_t st) {
+    const size_t n4 = n / 4;   // the caller has checked n % 4 == 0
+    hipLaunchKernelGGL(grad_clip_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, g, n4, sumsq, pre_scale, max_norm,
+                       norm_out);
     return hipGetLastError();
 }
 

@@ -24,8 +24,21 @@ Every rank must take the same branch around the collectives.  Two ways to drive 
     ranks; ``step()`` then skips its own reduction.  Driving ``step()`` through a GradScaler with
     unreduced gradients on more than one rank raises instead of risking mismatched collectives.
 
-On the HIP device the update is ``aft_adam_step_f32`` (one kernel over the shard).  On CPU tensors the
-same formula runs through torch ops, which is what the world_size-2 gloo tests exercise.
+On the HIP device ``step()`` never reads the device: the gradient norm, ``clip_grad_norm_``'s coefficient, the GradScaler's
+``found_inf`` / ``grad_scale``, the skip decision and the count of applied steps (the bias-correction exponent) all stay in device
+memory, and the launches around the collectives are
+
+    [aft_grad_sumsq_f32 (two launches; only with clipping) -> all_reduce of the float64 scalar]
+        -> aft_adam_prepare_f32 (one thread: fills the 32-byte control block) -> aft_adam_step_ctrl_f32 (one kernel over the shard)
+
+The squared norm is summed in float64 in an order that depends on the buffer's length alone (no atomics), so a step's bits do not
+depend on the device or on what else runs on it.  A step the scaler skips still runs its launches (and its all-gather, of unchanged
+parameters): the Adam kernel returns before any store and the step count stays.  ``steps`` is read back only where a host value is
+needed (``state_dict()``); ``last_grad_norm`` is the pre-clip norm as a 0-d device tensor for logging.  ``clip_grad_norm_`` serves
+the reference's call order (``unscale_`` -> clip -> ``scaler.step``, trainer.py:207-224) on the flat buffer.
+
+On CPU tensors the same formulas run through torch ops and Python floats, which is what the world_size-2 gloo tests exercise; that
+path is the behavioural specification of the device path (a nan norm leaves the gradient unclipped, as ``min(1.0, nan)`` does).
 """
 from __future__ import annotations
 
@@ -139,8 +152,45 @@ class ShardedFlatAdam(torch.optim.Optimizer):
         self.exp_avg = torch.zeros_like(self.p_shard)
         self.exp_avg_sq = torch.zeros_like(self.p_shard)
         self.max_grad_norm = max_grad_norm
-        self.steps = 0
+        self._hip = on_hip
+        self._steps = 0
+        self._last_grad_norm = None
+        if on_hip:
+            from . import _lib
+            dev = self.flat.data.device
+            # aft_step_control (include/adafortitran_amd.h): skip, step | grad_scale, inv_bc1, inv_sqrt_bc2, grad_norm, clip_coef
+            self._ctrl = torch.zeros(8, dtype=torch.int32, device=dev)
+            self._ctrl_f = self._ctrl.view(torch.float32)
+            self._sumsq = torch.zeros((), dtype=torch.float64, device=dev)
+            self._nonfinite = torch.zeros((), dtype=torch.float32, device=dev)
+            self._clip_norm = torch.zeros((), dtype=torch.float32, device=dev)
+            n_max = max(self.shard, self.flat.padded)
+            self._sumsq_scratch = torch.empty(_lib.load().aft_grad_sumsq_scratch_bytes(n_max), dtype=torch.uint8, device=dev)
         self._grads_reduced = False
+
+    @property
+    def steps(self) -> int:
+        """Applied steps (skipped ones do not count).  On the HIP device the count lives in the control block: reading it here
+        waits for the device, so ``step()`` never does -- ``state_dict()`` is the caller that needs the host value."""
+        return int(self._ctrl[1]) if self._hip else self._steps
+
+    @steps.setter
+    def steps(self, value: int) -> None:
+        if self._hip:
+            self._ctrl[1:2].fill_(int(value))
+        else:
+            self._steps = int(value)
+
+    @property
+    def last_grad_norm(self) -> Optional[torch.Tensor]:
+        """Global gradient norm before clipping, as the last clipped ``step()`` or ``clip_grad_norm_`` left it: a 0-d tensor on
+        the parameters' device (overwritten in place by the next one; ``None`` before the first)."""
+        return self._last_grad_norm
+
+    @property
+    def last_grad_nonfinite(self) -> Optional[torch.Tensor]:
+        """HIP device only: 1.0 when the buffer of the last norm held an inf / nan element, else 0.0 (0-d device tensor)."""
+        return self._nonfinite if self._hip and self._last_grad_norm is not None else None
 
     def zero_grad(self, set_to_none: bool = False) -> None:   # the views must stay attached to the flat buffer
         self.flat.zero_grad()
@@ -176,6 +226,10 @@ class ShardedFlatAdam(torch.optim.Optimizer):
                 raise RuntimeError("ShardedFlatAdam.step() driven through a GradScaler on more than one rank: call "
                                    "optimizer.reduce_gradients() after backward() so that every rank checks the same "
                                    "(averaged) gradients for inf/nan and takes the same branch")
+        if self._hip:
+            self._step_hip(found_inf, grad_scale)
+            return loss
+        if found_inf is not None:
             if float(found_inf) > 0:                     # the scaler skips the step; identical on every rank
                 self._grads_reduced = False
                 return loss
@@ -194,7 +248,12 @@ class ShardedFlatAdam(torch.optim.Optimizer):
                 dist.all_reduce(sq, group=self.group)
             norm = float(sq.sqrt())
             scale *= min(1.0, self.max_grad_norm / (norm + 1e-6))   # clip_grad_norm_'s coefficient
+            self._last_grad_norm = torch.tensor(norm, dtype=torch.float32)
         self._adam(g, scale)
+        self._publish()
+        return loss
+
+    def _publish(self) -> None:
         if self.distributed:
             dist.all_gather_into_tensor(self.flat.data, self.p_shard.clone(), group=self.group)
         # the fused kernel and the all-gather write the flat buffer behind the parameters' backs: move their autograd
@@ -205,18 +264,87 @@ class ShardedFlatAdam(torch.optim.Optimizer):
             for p in self.flat.params:
                 torch._C._increment_version(p)
         self._grads_reduced = False
-        return loss
+
+    # ---- the HIP device: every decision of the step stays in device memory (module docstring) ----
+    def _device_scalar(self, t):
+        """GradScaler's found_inf / grad_scale as a float32 scalar on the parameters' device (no read-back either way)."""
+        if t is None:
+            return None
+        dev = self.p_shard.device
+        if not torch.is_tensor(t):
+            return torch.full((), float(t), dtype=torch.float32, device=dev)
+        return t if t.device == dev and t.dtype == torch.float32 else t.to(device=dev, dtype=torch.float32, non_blocking=True)
+
+    def _sumsq_of(self, g: torch.Tensor, stream: int) -> int:
+        """Squared norm of this rank's gradients into the device scalar, summed over the ranks; its address."""
+        from . import _lib
+        _lib.check(_lib.load().aft_grad_sumsq_f32(g.data_ptr(), g.numel(), self._sumsq_scratch.data_ptr(),
+                                                  self._sumsq_scratch.numel(), self._sumsq.data_ptr(),
+                                                  self._nonfinite.data_ptr(), stream))
+        if self.distributed:
+            dist.all_reduce(self._sumsq, group=self.group)
+        return self._sumsq.data_ptr()
+
+    def _step_hip(self, found_inf, grad_scale) -> None:
+        from . import _lib
+        lib = _lib.load()
+        stream = _lib.current_stream_ptr(self.p_shard.device)
+        host_scale = 1.0
+        if self._grads_reduced:
+            g = self.g_local                             # already the mean over ranks
+        else:
+            if self.distributed:
+                dist.reduce_scatter_tensor(self.g_shard, self.flat.grad, op=dist.ReduceOp.SUM, group=self.group)
+            g = self.g_shard
+            host_scale /= self.world
+        sumsq = None
+        if self.max_grad_norm is not None:
+            sumsq = self._sumsq_of(g, stream)
+            self._last_grad_norm = self._ctrl_f[5]
+        found_inf, grad_scale = self._device_scalar(found_inf), self._device_scalar(grad_scale)
+        g0 = self.param_groups[0]
+        lr, (b1, b2), eps, wd = g0["lr"], g0["betas"], g0["eps"], g0["weight_decay"]
+        _lib.check(lib.aft_adam_prepare_f32(self._ctrl.data_ptr(), sumsq, None if found_inf is None else found_inf.data_ptr(),
+                                            None if grad_scale is None else grad_scale.data_ptr(), host_scale,
+                                            float(self.max_grad_norm or 0.0), b1, b2, stream))
+        _lib.check(lib.aft_adam_step_ctrl_f32(self.p_shard.data_ptr(), g.data_ptr(), self.exp_avg.data_ptr(),
+                                              self.exp_avg_sq.data_ptr(), self.shard, lr, b1, b2, eps, wd, self._ctrl.data_ptr(),
+                                              stream))
+        self._publish()   # also after a skipped step (unchanged parameters): the host does not know, the ranks stay in step
+
+    @torch.no_grad()
+    def clip_grad_norm_(self, max_norm: float) -> torch.Tensor:
+        """``torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm)`` on the flat gradient buffer, for the reference's
+        call order (trainer.py:214,224: ``scaler.unscale_`` -> clip -> ``scaler.step``): scales every ``.grad`` in place by
+        ``min(1, max_norm / (norm + 1e-6))`` and returns the total norm as a 0-d tensor on the parameters' device, without
+        reading it.  The norm is that of the gradient averaged over the ranks, under the rules of ``max_grad_norm``: after
+        ``reduce_gradients()`` each rank contributes its slice of the averaged buffer, otherwise its reduce-scattered shard."""
+        if self._grads_reduced or self.world == 1:
+            g, pre = self.g_local, 1.0
+        else:
+            dist.reduce_scatter_tensor(self.g_shard, self.flat.grad, op=dist.ReduceOp.SUM, group=self.group)
+            g, pre = self.g_shard, 1.0 / self.world
+        if self._hip:
+            from . import _lib
+            stream = _lib.current_stream_ptr(self.p_shard.device)
+            sumsq = self._sumsq_of(g, stream)
+            _lib.check(_lib.load().aft_grad_clip_f32(self.flat.grad.data_ptr(), self.flat.padded, sumsq, pre, float(max_norm),
+                                                     self._clip_norm.data_ptr(), stream))
+            self._last_grad_norm = self._clip_norm
+            return self._clip_norm.clone()
+        sq = (g.double() ** 2).sum() * pre * pre
+        if self.distributed:
+            dist.all_reduce(sq, group=self.group)
+        norm = float(sq.sqrt())
+        coef = min(1.0, float(max_norm) / (norm + 1e-6))
+        if coef < 1.0:
+            self.flat.grad.mul_(coef)
+        self._last_grad_norm = torch.tensor(norm, dtype=torch.float32)
+        return self._last_grad_norm.clone()
 
     def _adam(self, g_shard: torch.Tensor, grad_scale: float) -> None:
         g0 = self.param_groups[0]
         lr, (b1, b2), eps, wd = g0["lr"], g0["betas"], g0["eps"], g0["weight_decay"]
-        if self.p_shard.device.type == "cuda":
-            from . import _lib
-            lib = _lib.load()
-            _lib.check(lib.aft_adam_step_f32(self.p_shard.data_ptr(), g_shard.data_ptr(), self.exp_avg.data_ptr(),
-                                             self.exp_avg_sq.data_ptr(), self.shard, lr, b1, b2, eps, wd, grad_scale,
-                                             self.steps, _lib.current_stream_ptr(self.p_shard.device)))
-            return
         g = g_shard * grad_scale + wd * self.p_shard
         self.exp_avg.mul_(b1).add_(g, alpha=1 - b1)
         self.exp_avg_sq.mul_(b2).addcmul_(g, g, value=1 - b2)

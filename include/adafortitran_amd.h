@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define AFT_ABI_VERSION 8   /* bump whenever an entry point's meaning, a struct or a scratch size changes */
+#define AFT_ABI_VERSION 9   /* bump whenever an entry point's meaning, a struct or a scratch size changes */
 
 #define AFT_OK 0
 #define AFT_ERR_ARG 1   /* NULL pointer, bad batch, workspace too small ...          */
@@ -362,6 +362,46 @@ int aft_tail_bwd_f32(const float *x, const float *w2, const float *d_out, float 
  * sum-reduce-scatter), weight_decay is the L2 form Adam uses; `step` is the 1-based step count. */
 int aft_adam_step_f32(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, size_t n, float lr, float beta1,
                       float beta2, float eps, float weight_decay, float grad_scale, int step, void *stream);
+
+/* ---- the optimizer step without a host read (ABI 9) ----
+ * What torch decides on the host around optimizer.step() -- clip_grad_norm_ (reference src/main/trainer.py:214,222-224),
+ * GradScaler's found_inf / grad_scale (trainer.py:207-217), the step count of the bias correction -- decided on the device:
+ *
+ *     aft_grad_sumsq_f32 -> [all-reduce of *sumsq over the ranks] -> aft_adam_prepare_f32 -> aft_adam_step_ctrl_f32
+ *
+ * The control block is 32 bytes of DEVICE memory owned by the caller, zeroed once (step = 0); the preparation launch rewrites
+ * it every step and the Adam launch reads it.  `step` counts APPLIED steps: a skipped step leaves it, the parameters and both
+ * moments untouched. */
+typedef struct aft_step_control {
+    int32_t skip;        /* 1: found_inf was > 0, the Adam launch stores nothing                                      */
+    int32_t step;        /* applied steps so far, this one included when it is applied                               */
+    float grad_scale;    /* host_scale / grad_scale * min(1, max_norm / (grad_norm + 1e-6))                          */
+    float inv_bc1;       /* 1 / (1 - beta1^step)                                                                     */
+    float inv_sqrt_bc2;  /* 1 / sqrt(1 - beta2^step)                                                                 */
+    float grad_norm;     /* global norm of the unscaled gradient before clipping (written when sumsq is given)       */
+    float clip_coef;     /* min(1, max_norm / (grad_norm + 1e-6))                (written when sumsq is given)       */
+    int32_t reserved;
+} aft_step_control;
+
+/* Sum of squares of a flat float32 buffer (16-byte aligned) in float64: per-workgroup partials over fixed chunks of 4096
+ * elements in `scratch` (aft_grad_sumsq_scratch_bytes(n) bytes; 0 for n = 0 or beyond 2^40), then one workgroup adds them in a
+ * fixed order.  No atomics: the bits depend on the data and on n only, not on the device or on what else runs on it.
+ * *nonfinite = 1 when an element is inf / nan, else 0.  Two launches. */
+size_t aft_grad_sumsq_scratch_bytes(size_t n);
+int aft_grad_sumsq_f32(const float *grad, size_t n, void *scratch, size_t scratch_bytes, double *sumsq, float *nonfinite,
+                       void *stream);
+/* One launch, one thread: fills *ctrl for the Adam launch that follows.  sumsq (NULL: no clipping; max_norm is then ignored) is
+ * the squared norm of the gradient buffer BEFORE host_scale and 1/grad_scale are applied; found_inf / grad_scale are
+ * torch.amp.GradScaler's device scalars (NULL: none).  A nan norm leaves the scale unclipped, an infinite one makes it 0. */
+int aft_adam_prepare_f32(aft_step_control *ctrl, const double *sumsq, const float *found_inf, const float *grad_scale,
+                         double host_scale, double max_norm, float beta1, float beta2, void *stream);
+/* aft_adam_step_f32 with grad_scale and the bias corrections read from *ctrl; nothing is stored when ctrl->skip is set. */
+int aft_adam_step_ctrl_f32(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, size_t n, float lr, float beta1,
+                           float beta2, float eps, float weight_decay, const aft_step_control *ctrl, void *stream);
+/* torch.nn.utils.clip_grad_norm_ on a flat buffer (16-byte aligned, n a multiple of 4) whose squared norm is *sumsq:
+ * norm = sqrt(sumsq) * pre_scale, grad *= min(1, max_norm / (norm + 1e-6)), *norm_out = norm.  One launch. */
+int aft_grad_clip_f32(float *grad, size_t n, const double *sumsq, double pre_scale, double max_norm, float *norm_out,
+                      void *stream);
 
 /* ---- per-stage entry points (known-answer tests) ----
  * Same arithmetic as aft_forward_f32 stage by stage, but NOT always the same kernels: these calls own no scratch, so on the default

@@ -35,16 +35,18 @@ def build(name, dropout, device="cuda"):
 
 
 def measure(batch=128, steps=20, warmup=5, model_name="adafortitran", dropout=0.1, modes=("hip", "torch"), dense="hip",
-            optimizer="flat", dist=None, rank=0, detail=None):
+            optimizer="flat", dist=None, rank=0, detail=None, clip=None, amp=False, loss_item=False):
     """ms per training step for each mode; with a process group the steps are bracketed by barriers and the value is the
-    MAX over ranks.  ``detail`` (dict) receives per-rank device times and the collectives' own cost."""
+    MAX over ranks.  ``detail`` (dict) receives per-rank device times and the collectives' own cost.  ``clip``: gradient clipping
+    at that norm (the flat optimizer's ``max_grad_norm``; ``clip_grad_norm_`` for ``optimizer="torch"``); ``amp``: the reference's
+    GradScaler branch (trainer.py:207-217); ``loss_item``: read ``loss.item()`` after every step as trainer.py:229 does."""
     import torch
     from adafortitran_amd import synth, training
     torch.manual_seed(0)
     model = build(model_name, dropout).train()
     if optimizer == "flat":
         from adafortitran_amd.optim import ShardedFlatAdam
-        opt = ShardedFlatAdam(model.parameters(), lr=1e-3)
+        opt = ShardedFlatAdam(model.parameters(), lr=1e-3, max_grad_norm=clip)
     else:
         opt = torch.optim.Adam(model.parameters(), lr=1e-3)
     inp = synth.make_inputs(batch, seed=1 + 1000 * rank)          # a different shard of frames per rank
@@ -52,12 +54,29 @@ def measure(batch=128, steps=20, warmup=5, model_name="adafortitran", dropout=0.
     pil, tgt = torch.from_numpy(inp["pilots"]).to(dev), torch.from_numpy(inp["target"]).to(dev)
     meta = synth.meta_tuple(inp) if model_name == "adafortitran" else None
 
+    scaler = torch.amp.GradScaler("cuda") if amp else None
+    torch_clip = clip is not None and optimizer != "flat"
+
     def step():
         opt.zero_grad()
         out = model(pil, meta) if meta is not None else model(pil)
-        loss = torch.nn.functional.mse_loss(torch.view_as_real(out), torch.view_as_real(tgt))
-        loss.backward()
-        opt.step()
+        if scaler is None:
+            loss = torch.nn.functional.mse_loss(torch.view_as_real(out), torch.view_as_real(tgt))
+            loss.backward()
+            if torch_clip:
+                torch.nn.utils.clip_grad_norm_(model.parameters(), clip)
+            opt.step()
+        else:
+            with torch.autocast("cuda"):
+                loss = torch.nn.functional.mse_loss(torch.view_as_real(out), torch.view_as_real(tgt))
+            scaler.scale(loss).backward()
+            if torch_clip:
+                scaler.unscale_(opt)
+                torch.nn.utils.clip_grad_norm_(model.parameters(), clip)
+            scaler.step(opt)
+            scaler.update()
+        if loss_item:
+            loss.item()
 
     def fence():
         torch.cuda.synchronize()
@@ -138,6 +157,9 @@ def main():
     ap.add_argument("--only", default="", help="hip | torch")
     ap.add_argument("--dense", default="hip", choices=["blas", "hip"], help="thin dense layers: the library GEMM (default) or hipBLASLt")
     ap.add_argument("--optimizer", default="flat", choices=["flat", "torch"], help="flat = ShardedFlatAdam (fused kernel)")
+    ap.add_argument("--clip", type=float, default=None, help="clip the gradient norm at this value (--gradient_clip_val of the reference)")
+    ap.add_argument("--amp", action="store_true", help="the reference's GradScaler branch (--use_mixed_precision)")
+    ap.add_argument("--loss-item", action="store_true", help="read loss.item() after every step, as the reference's train_epoch does")
     ap.add_argument("--share-gpu", action="store_true", help="tests only: every rank on device 0, collectives over gloo (RCCL refuses "
                     "two ranks on one device); the numbers mean nothing")
     a = ap.parse_args()
@@ -161,10 +183,11 @@ def main():
             dist.init_process_group(backend="nccl", device_id=torch.device("cuda", local))
     modes = (a.only,) if a.only else (("hip", "torch") if world == 1 else ("hip",))
     detail = {}
-    res = measure(a.batch, a.steps, a.warmup, a.model, a.dropout, modes, a.dense, a.optimizer, dist, rank, detail)
+    res = measure(a.batch, a.steps, a.warmup, a.model, a.dropout, modes, a.dense, a.optimizer, dist, rank, detail, a.clip, a.amp,
+                  a.loss_item)
     if rank == 0:
         out = {"metric": "training step (fwd+bwd+Adam) ms", "n_gpus": world, "batch_per_gpu": a.batch, "model": a.model,
-               "dropout": a.dropout, "ms_per_step": {k: round(v, 3) for k, v in res.items()},
+               "dropout": a.dropout, "clip": a.clip, "amp": a.amp, "loss_item": a.loss_item, "ms_per_step": {k: round(v, 3) for k, v in res.items()},
                "frames_per_s": {k: round(a.batch * world / v * 1e3, 1) for k, v in res.items()}}
         if len(res) == 2:
             out["speedup_vs_pytorch_rocm"] = round(res["torch"] / res["hip"], 3)

@@ -5,7 +5,7 @@ with open(p) as f:
     for r in csv.DictReader(f):
         rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), re.sub(r"\(.*", "", r["Kernel_Name"])[:50]))
 rows.sort()
-adam = [i for i, r in enumerate(rows) if "adam_kernel" in r[2]]
+adam = [i for i, r in enumerate(rows) if "adam_kernel" in r[2] or "adam_ctrl_kernel" in r[2]]
 win = rows[adam[-2] + 1: adam[-1] + 1]
 gaps = []
 for a, b in zip(win[:-1], win[1:]):

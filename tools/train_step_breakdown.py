@@ -13,7 +13,7 @@ for p in paths:
         for r in csv.DictReader(f):
             rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]))
 rows.sort()
-adam = [i for i, r in enumerate(rows) if "adam_kernel" in r[2]]
+adam = [i for i, r in enumerate(rows) if "adam_kernel" in r[2] or "adam_ctrl_kernel" in r[2]]
 if len(adam) < 2:
     sys.exit("trace holds fewer than two optimizer steps")
 win = rows[adam[-2] + 1: adam[-1] + 1]
