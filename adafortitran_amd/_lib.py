@@ -77,6 +77,7 @@ def load_path(path: str):
     lib.aft_debug_peek_lds_f32.argtypes = [vp, C.c_int, C.c_int, vp]
     lib.aft_pilot_gather_f32.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
     lib.aft_ls_mse_db_f32.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp]
+    lib.aft_frame_gather_f32.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_longlong, C.c_int, C.c_int, vp]
     lwp, lgp = C.POINTER(_abi.AftLayerWeights), C.POINTER(_abi.AftLayerGrads)
     for name in ("aft_encoder_tape_bytes", "aft_encoder_train_scratch_bytes"):
         getattr(lib, name).restype = C.c_size_t

@@ -742,6 +742,22 @@ int aft_ls_mse_db_f32(const float *ls, const float *ideal, float *db, int batch,
     return e == hipSuccess ? AFT_OK : hip_fail("ls_mse_db", e);
 }
 
+int aft_frame_gather_f32(const float *ideal_all, const float *pilots_all, const long long *index, float *ideal_out,
+                         float *pilots_out, int *flags, int batch, long long frames, int grid_elems, int pilot_elems, void *stream) {
+    AFT_REQUIRE(ideal_all && pilots_all && index && ideal_out && pilots_out && flags, "frame gather: NULL pointer argument");
+    AFT_REQUIRE(batch >= 1 && frames >= 1 && grid_elems >= 1 && pilot_elems >= 1,
+                "frame gather: bad sizes (batch %d, frames %lld, grid_elems %d, pilot_elems %d: all must be at least 1)", batch, frames,
+                grid_elems, pilot_elems);
+    const uintptr_t bases = reinterpret_cast<uintptr_t>(ideal_all) | reinterpret_cast<uintptr_t>(pilots_all) |
+                            reinterpret_cast<uintptr_t>(index) | reinterpret_cast<uintptr_t>(ideal_out) |
+                            reinterpret_cast<uintptr_t>(pilots_out);
+    AFT_REQUIRE(bases % 8 == 0, "frame gather: the frame arrays and the index must be 8-byte aligned");
+    AFT_REQUIRE(reinterpret_cast<uintptr_t>(flags) % 4 == 0, "frame gather: flags must be 4-byte aligned");
+    hipError_t e = launch_frame_gather(ideal_all, pilots_all, index, ideal_out, pilots_out, flags, batch, frames, grid_elems,
+                                       pilot_elems, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? AFT_OK : hip_fail("frame_gather", e);
+}
+
 int aft_debug_fill_lds_f32(float value, void *stream) {
     hipError_t e = launch_fill_lds(value, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? AFT_OK : hip_fail("fill_lds", e);

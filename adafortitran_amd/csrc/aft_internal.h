@@ -276,6 +276,10 @@ hipError_t launch_linear(const float *weight, const float *bias, const float *pi
 hipError_t launch_pilot_gather(const float *hzero_ls, float *pilots, int *counts, int batch, int grid_elems,
                                int expected, hipStream_t st);
 hipError_t launch_ls_mse_db(const float *ls, const float *ideal, float *db, int batch, int grid_elems, hipStream_t st);
+// frames index[0..batch) of both resident arrays (HBM or pinned host memory) -> two batch tensors, in one launch; bases 8-byte aligned
+hipError_t launch_frame_gather(const float *ideal_all, const float *pilots_all, const long long *index, float *ideal_out,
+                               float *pilots_out, int *flags, int batch, long long frames, int grid_elems, int pilot_elems,
+                               hipStream_t st);
 hipError_t launch_mse(const float *est, const float *ref, double *sum_sq, long long n_complex, hipStream_t st);
 hipError_t launch_fill_lds(float value, hipStream_t st);   // test hook: every CU's LDS filled with `value`
 hipError_t launch_peek_lds(float *out, int workgroups, int n, hipStream_t st);   // ... and what a kernel finds in its LDS at start

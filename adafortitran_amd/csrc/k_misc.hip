@@ -456,6 +456,97 @@ hipError_t launch_pilot_gather(const float *hzero_ls, float *pilots, int *counts
 }
 
 // ---------------------------------------------------------------------------------------------
+// Shuffled training batches (ingest.ResidentLoader): output frame b of BOTH resident arrays (targets [frames][grid_elems] and
+// pilots [frames][pilot_elems], complex64, in HBM or in pinned host memory) is a bit copy of frame index[b].  One launch moves both.
+// The unit of work is a PIECE: up to 4 x 64 vectors of one frame of one array, taken by one wave.  The four wave-wide loads of a piece
+// are UNCONDITIONAL (a lane beyond the frame's end re-reads the frame's last vector: the clamp keeps the address inside the frame), so
+// all four are issued before the first wait; only the stores are predicated.  (Predicated loads merged into zero-initialised registers
+// compile to load / wait / load / wait: four serial round trips per piece, which over the link to pinned memory is the whole cost.)
+// The grid is sized by the pieces (the bytes to move), not by the frames: 16 frames of a 240 x 28 grid are 224 + 16 pieces.  A vector
+// is 16 bytes where the array's frame size and both of its bases allow it, 8 bytes (one complex element) otherwise.  An index outside
+// [0, frames) reads nothing: the wave takes the branch that only stores zeros, and flags[b] = 1 (else 0).
+// Everything that selects the piece is wave-uniform 32-bit arithmetic; the frame index is one 8-byte read per wave.
+// ---------------------------------------------------------------------------------------------
+constexpr int kGatherLoads = 4, kGatherPiece = 64 * kGatherLoads;   // vectors per piece
+
+struct FrameGatherArgs {
+    const float *src[2];       // ideal_all, pilots_all
+    float *dst[2];
+    const long long *index;
+    int *flags;
+    long long frames;
+    unsigned waves, per_frame; // waves = batch * per_frame (the launcher refuses 2^31 and more), per_frame = pieces[0] + pieces[1]
+    int elems[2];              // complex elements per frame
+    int nvec[2], pieces[2];    // vectors per frame and pieces per frame, per array
+    int wide[2];               // 1: 16-byte vectors, 0: 8-byte
+};
+
+template <typename V>
+__device__ __forceinline__ void gather_piece(const float *src, float *dst, int nvec, int piece, int lane, bool ok) {
+    V *d = reinterpret_cast<V *>(dst);
+    const int i0 = piece * kGatherPiece + lane;
+    if (ok) {                                     // wave-uniform
+        const V *s = reinterpret_cast<const V *>(src);
+        V v[kGatherLoads];
+#pragma unroll
+        for (int u = 0; u < kGatherLoads; ++u) v[u] = s[min(i0 + 64 * u, nvec - 1)];
+#pragma unroll
+        for (int u = 0; u < kGatherLoads; ++u) {
+            const int i = i0 + 64 * u;
+            if (i < nvec) d[i] = v[u];
+        }
+    } else {
+#pragma unroll
+        for (int u = 0; u < kGatherLoads; ++u) {
+            const int i = i0 + 64 * u;
+            if (i < nvec) d[i] = V{};
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void frame_gather_kernel(const FrameGatherArgs a) {
+    const int lane = threadIdx.x & 63;
+    const unsigned wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) + blockIdx.x * (blockDim.x >> 6);
+    if (wave >= a.waves) return;
+    const unsigned b = wave / a.per_frame;
+    int piece = (int)(wave - b * a.per_frame);
+    const int arr = piece < a.pieces[0] ? 0 : 1;
+    if (arr) piece -= a.pieces[0];
+    const long long idx = a.index[b];
+    const bool ok = (unsigned long long)idx < (unsigned long long)a.frames;   // also false for negative entries
+    if (arr == 0 && piece == 0 && lane == 0) a.flags[b] = ok ? 0 : 1;
+    const size_t fl = 2 * (size_t)a.elems[arr];                               // floats per frame
+    const float *src = a.src[arr] + (ok ? (size_t)idx * fl : 0);              // never formed from a bad index
+    float *dst = a.dst[arr] + (size_t)b * fl;
+    if (a.wide[arr]) gather_piece<f32x4>(src, dst, a.nvec[arr], piece, lane, ok);
+    else gather_piece<f32x2>(src, dst, a.nvec[arr], piece, lane, ok);
+}
+
+hipError_t launch_frame_gather(const float *ideal_all, const float *pilots_all, const long long *index, float *ideal_out,
+                               float *pilots_out, int *flags, int batch, long long frames, int grid_elems, int pilot_elems,
+                               hipStream_t st) {
+    FrameGatherArgs a{};
+    a.src[0] = ideal_all; a.src[1] = pilots_all; a.dst[0] = ideal_out; a.dst[1] = pilots_out;
+    a.index = index; a.flags = flags; a.frames = frames;
+    a.elems[0] = grid_elems; a.elems[1] = pilot_elems;
+    for (int k = 0; k < 2; ++k) {
+        const bool wide = a.elems[k] % 2 == 0 && (reinterpret_cast<uintptr_t>(a.src[k]) | reinterpret_cast<uintptr_t>(a.dst[k])) % 16 == 0;
+        a.wide[k] = wide ? 1 : 0;
+        a.nvec[k] = wide ? a.elems[k] / 2 : a.elems[k];
+        a.pieces[k] = (a.nvec[k] + kGatherPiece - 1) / kGatherPiece;
+    }
+    a.per_frame = (unsigned)(a.pieces[0] + a.pieces[1]);
+    const long long waves = (long long)batch * a.per_frame;
+    if (waves > 0x7fffffffLL) return hipErrorInvalidValue;   // the kernel's piece arithmetic is 32-bit (aft_frame_gather_f32 checks first)
+    a.waves = (unsigned)waves;
+    // small jobs (a training batch) as one-wave workgroups, so that the pieces spread over the CUs; large ones as four waves each
+    const int wpb = waves < 4LL * current_device_cus() ? 1 : 4;
+    const long long blocks = (waves + wpb - 1) / wpb;
+    hipLaunchKernelGGL(frame_gather_kernel, dim3((unsigned)blocks), dim3(64 * wpb), 0, st, a);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
 // The same stage (S3 + S4-concat + linear_1 + positions) for the general engine: ANY model_dim, patches of up to 32 elements.
 // A workgroup takes 8 token rows: their <= 38 input features go to LDS once, thread c' walks the output columns c = c', c' + 256, ..
 // with row c of W1 ([d][din], as PyTorch holds it) in registers across the 8 rows.  x[row][c] = b1[c] + pos[t][c] + sum_f W1[c][f] in[f],

@@ -340,6 +340,54 @@ def check_pilot_counts(counts: torch.Tensor, expected: int, first_frame: int = 0
         raise ValueError(f"Expected {expected} pilot values, got {int(counts[i])} (frame {first_frame + i})")
 
 
+def frame_gather(ideal_all: torch.Tensor, pilots_all: torch.Tensor, index: torch.Tensor, lib=None):
+    """Frames ``index`` (int64 [b], on the HIP device) of two resident complex64 arrays ``ideal_all [n, ...]`` and ``pilots_all [n, ...]``
+    -> ``(ideal [b, ...], pilots [b, ...], flags int32 [b])`` on the index's device, in ONE launch on its current stream
+    (``aft_frame_gather_f32``).  Either array lives on that device or in pinned host memory (read in place over the link); both must be
+    contiguous.  An entry outside ``[0, n)`` gives a zero frame and ``flags == 1`` there; the call itself never synchronises, so a
+    caller that did not make the indices itself checks ``flags`` when it can afford to.  ``lib``: another build of the library
+    (``_lib.load_path``), for the tests that compare builds."""
+    lib = lib or _lib.load()
+    if index.dtype != torch.int64 or index.dim() != 1 or index.device.type != "cuda" or not index.is_contiguous() or index.numel() < 1:
+        raise ValueError("index must be a contiguous, non-empty int64 vector on the HIP device")
+    dev = index.device
+    for name, t in (("ideal_all", ideal_all), ("pilots_all", pilots_all)):
+        if t.dtype != torch.complex64 or t.dim() < 2 or not t.is_contiguous() or t.shape[0] < 1 or t[0].numel() < 1:
+            raise ValueError(f"{name} must be a contiguous complex64 array [n, ...] with n >= 1")
+        if not (t.device == dev or (t.device.type == "cpu" and t.is_pinned())):
+            raise ValueError(f"{name} must live on {dev} or in pinned host memory (it is on {t.device}, not pinned)")
+    if ideal_all.shape[0] != pilots_all.shape[0]:
+        raise ValueError(f"ideal_all holds {ideal_all.shape[0]} frames, pilots_all {pilots_all.shape[0]}")
+    plan = FrameGatherPlan(ideal_all, pilots_all, dev)
+    with torch.cuda.device(dev):
+        return plan(index, lib)
+
+
+class FrameGatherPlan:
+    """Two resident arrays that ``frame_gather`` has accepted, with everything a launch needs taken from them ONCE: a caller that
+    gathers from the same arrays for every batch (ingest.ResidentLoader) pays two ``torch.empty`` (three with the flags), one ``ctypes``
+    call and nothing else per batch.  ``plan(index)`` trusts its caller: ``index`` is a contiguous, non-empty int64 vector on the
+    plan's device and that device is the current one."""
+
+    def __init__(self, ideal_all: torch.Tensor, pilots_all: torch.Tensor, device: torch.device) -> None:
+        self.arrays = (ideal_all, pilots_all)                   # kept alive with the plan
+        self.device = device
+        self.src = (ideal_all.data_ptr(), pilots_all.data_ptr())
+        self.n = ideal_all.shape[0]
+        self.tails = (tuple(ideal_all.shape[1:]), tuple(pilots_all.shape[1:]))
+        self.elems = (ideal_all[0].numel(), pilots_all[0].numel())
+
+    def __call__(self, index: torch.Tensor, lib=None):
+        lib = lib or _lib.load()
+        b, dev = index.shape[0], self.device
+        ideal = torch.empty((b, *self.tails[0]), dtype=torch.complex64, device=dev)      # the kernel writes every element
+        pilots = torch.empty((b, *self.tails[1]), dtype=torch.complex64, device=dev)
+        flags = torch.empty(b, dtype=torch.int32, device=dev)
+        _lib.check(lib.aft_frame_gather_f32(self.src[0], self.src[1], index.data_ptr(), ideal.data_ptr(), pilots.data_ptr(),
+                                            flags.data_ptr(), b, self.n, self.elems[0], self.elems[1], _lib.current_stream_ptr(dev)))
+        return ideal, pilots, flags
+
+
 def ls_mse_db(ls: torch.Tensor, ideal: torch.Tensor) -> torch.Tensor:
     """Per-frame LS-baseline MSE in dB, float32 [B] (reference utils.py:248-261 per file)."""
     lib = _lib.load()

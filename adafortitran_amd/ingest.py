@@ -234,9 +234,13 @@ class PackedLoader:
             settle(prev)
 
     def _meta(self, lo: int, hi: int) -> tuple:
-        m = torch.from_numpy(self.p["meta"][lo:hi])
-        return (m[:, 0:1], m[:, 1:2], m[:, 2:3], m[:, 3:4], m[:, 4:5],
-                [tuple(str(c) for c in self.p["channel_type"][lo:hi])])
+        return _meta_tuple(self.p["meta"][lo:hi], self.p["channel_type"][lo:hi])
+
+
+def _meta_tuple(meta: np.ndarray, channel_type: np.ndarray) -> tuple:
+    """Rows of ``meta [b,5]`` and their channel types in the form the reference's DataLoader collates them to."""
+    m = torch.from_numpy(meta)
+    return (m[:, 0:1], m[:, 1:2], m[:, 2:3], m[:, 3:4], m[:, 4:5], [tuple(str(c) for c in channel_type)])
 
 
 class _Sweep:
@@ -266,6 +270,180 @@ class _Sweep:
         if err is not None:
             logging.getLogger(__name__).error(
                 "PackedLoader: %s -- found while settling an abandoned sweep; loader.raise_pending() (or `with loader:`) raises it", err)
+
+
+def epoch_order(n: int, epoch: int, shuffle: bool = True, seed: int = 0, rank: int = 0, world_size: int = 1,
+                drop_last: bool = False) -> torch.Tensor:
+    """The frames rank ``rank`` visits in epoch ``epoch``, int64 -- by definition what
+    ``torch.utils.data.DistributedSampler(num_replicas=world_size, rank=rank, shuffle=shuffle, seed=seed, drop_last=drop_last)`` yields
+    after ``set_epoch(epoch)``: a permutation seeded with ``seed + epoch`` (file order when ``shuffle`` is off), padded by wrapping to a
+    multiple of ``world_size`` (cut to one when ``drop_last``), of which the rank takes every ``world_size``-th entry."""
+    if shuffle:
+        order = torch.randperm(n, generator=torch.Generator().manual_seed(seed + epoch))
+    else:
+        order = torch.arange(n)
+    if drop_last:
+        order = order[:n // world_size * world_size]
+    else:
+        pad = -n % world_size
+        if pad:
+            order = torch.cat([order, order.repeat(-(-pad // n))[:pad]])
+    return order[rank::world_size].contiguous()
+
+
+class ResidentLoader:
+    """The TRAINING loader: the whole pack stays resident, the order is shuffled per epoch and sharded per rank, and a batch costs
+    one kernel launch (``aft_frame_gather_f32``) with no host synchronisation.  It stands where the reference has
+    ``DataLoader(MatDataset(...), batch_size, shuffle=True)`` (src/main/trainer.py:505-511) and yields that loader's batches:
+    ``(pilots complex64 [b,Ps,Pt], h_ideal complex64 [b,S,T]`` on ``device``, ``(file_no, snr, ds, dop, n: float32 [b,1] host tensors,
+    [tuple of b channel-type strings]))`` -- with the TARGET on the device too, which the reference's ``train_epoch`` (trainer.py:195-233)
+    needs and a stock DataLoader does not give.  (``PackedLoader`` is the streaming evaluation loader: file order, data on the host.)
+
+    Construction.  ``packed`` is what ``pack_mat_folder`` returns, or the path of its ``.npz``.  The pilots of the whole pack are
+    extracted ONCE (``aft_pilot_gather_f32`` over chunks of the sparse grid on a HIP device, ``extract_pilots_host`` on the CPU), the
+    per-frame counts are checked once and the sparse grid is dropped: ``h_ideal [n,S,T]``, ``pilots [n,Ps,Pt]``, ``meta [n,5]`` and
+    ``channel_type [n]`` are what stays.  A frame without exactly ``Ps*Pt`` non-zero entries raises the reference's
+    ``ValueError("Expected 24 pilot values, got 25 (frame k)")``, k the frame's index in the pack, HERE -- earlier than the reference,
+    which raises when the sample is read (dataset.py:128-132).
+
+    Residency (``loader.residency``) follows from the size of the two arrays alone: ``"device"`` (both in HBM) when they fit
+    ``max_device_bytes`` -- 2 GiB by default, the GPUs are shared; the default grid costs 13.6 KB per frame, so that is ~150 000 frames
+    -- else ``"pinned"`` (page-locked host arrays the kernel reads over the link) when they fit ``max_pinned_bytes``, else a
+    ``ValueError``: such a pack is ``PackedLoader``'s streaming job.  ``"host"`` on ``device="cpu"``, where the same class yields the
+    same batches from host arrays.
+
+    Order.  ``epoch_order``: torch's ``DistributedSampler`` is the definition; the loader's own ``drop_last`` then also drops a ragged
+    last batch, as ``DataLoader(drop_last=...)`` does.  Every ``iter(loader)`` runs epoch ``loader.epoch`` and then adds one to it (the
+    reference's trainer calls ``train_epoch(loader)`` once per epoch and knows no ``set_epoch``); ``set_epoch(e)`` sets what the next
+    ``iter`` uses.  The order is a pure function of ``(seed, epoch, rank, world_size)``: resuming at an epoch boundary needs nothing else.
+
+    On a HIP device an epoch's indices are made on the host, placed in a pinned buffer (guarded by an event before it is rewritten) and
+    uploaded with one asynchronous copy on the consumer's current stream; a batch is the output allocations, one launch on the
+    consumer's current stream of the loader's device and a host fancy-index of ``meta``.  No side stream, no host wait, no ``.item()``."""
+
+    DEFAULT_MAX_DEVICE_BYTES = 2 << 30
+
+    def __init__(self, packed: Union[str, Path, Dict[str, np.ndarray]], pilot_size: Tuple[int, int], batch_size: int,
+                 device: Union[str, torch.device] = "cpu", shuffle: bool = True, seed: int = 0, drop_last: bool = False,
+                 rank: int = 0, world_size: int = 1, max_device_bytes: int = DEFAULT_MAX_DEVICE_BYTES,
+                 max_pinned_bytes: int = 8 << 30) -> None:
+        if not isinstance(packed, dict):
+            z = np.load(packed, allow_pickle=False)
+            packed = {k: z[k] for k in ("h_ideal", "h_ls_sparse", "meta", "channel_type")}
+        if batch_size < 1 or world_size < 1 or not 0 <= rank < world_size:
+            raise ValueError(f"bad batch_size / rank / world_size: {batch_size} / {rank} / {world_size}")
+        self.pilot_size = (int(pilot_size[0]), int(pilot_size[1]))
+        self.batch_size, self.device = int(batch_size), torch.device(device)
+        self.shuffle, self.seed, self.drop_last = bool(shuffle), int(seed), bool(drop_last)
+        self.rank, self.world_size = int(rank), int(world_size)
+        self.epoch = 0
+        ideal, sparse = packed["h_ideal"], packed["h_ls_sparse"]
+        self.n = n = ideal.shape[0]
+        if n < 1 or sparse.shape != ideal.shape:
+            raise ValueError(f"h_ideal {ideal.shape} / h_ls_sparse {sparse.shape}: need the same [n, S, T] with n >= 1")
+        self.meta = np.ascontiguousarray(packed["meta"], dtype=np.float32)
+        self.channel_type = np.asarray(packed["channel_type"])
+        ideal_bytes = ideal[0].size * 8 * n
+        need = ideal_bytes + self.pilot_size[0] * self.pilot_size[1] * 8 * n
+        on_gpu = self.device.type == "cuda"
+        if not on_gpu:
+            self.residency = "host"
+        elif need <= max_device_bytes:
+            self.residency = "device"
+        elif need <= max_pinned_bytes:
+            self.residency = "pinned"
+        else:
+            raise ValueError(f"the pack needs {need} bytes resident ({n} frames: targets + pilots), more than max_device_bytes = "
+                             f"{max_device_bytes} and max_pinned_bytes = {max_pinned_bytes}: stream it with PackedLoader")
+        if not on_gpu:
+            self.pilots = torch.from_numpy(extract_pilots_host(sparse, self.pilot_size))
+            self.h_ideal = torch.from_numpy(np.ascontiguousarray(ideal, dtype=np.complex64))
+            return
+        from .hip_ops import check_pilot_counts, pilot_gather
+        if self.device.index is None:                              # "cuda": the device that is current now, for good
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        expected = self.pilot_size[0] * self.pilot_size[1]
+        if self.residency == "device":
+            self.pilots = torch.empty((n, *self.pilot_size), dtype=torch.complex64, device=self.device)
+        else:
+            self.pilots = torch.empty((n, *self.pilot_size), dtype=torch.complex64).pin_memory()
+        chunk = max(1, (64 << 20) // (ideal[0].size * 8))          # 64 MB of sparse grid on the device at a time
+        with torch.cuda.device(self.device):
+            for lo in range(0, n, chunk):
+                part = torch.from_numpy(np.ascontiguousarray(sparse[lo:lo + chunk], dtype=np.complex64)).to(self.device)
+                pil, counts = pilot_gather(part, self.pilot_size, return_counts=True)
+                check_pilot_counts(counts.cpu(), expected, lo)
+                self.pilots[lo:lo + chunk].copy_(pil)
+            host = torch.from_numpy(np.ascontiguousarray(ideal, dtype=np.complex64))
+            self.h_ideal = host.to(self.device) if self.residency == "device" else host.pin_memory()
+            torch.cuda.current_stream(self.device).synchronize()   # resident for whichever stream the consumer iterates on
+        from .hip_ops import FrameGatherPlan
+        self._gather = FrameGatherPlan(self.h_ideal, self.pilots, self.device)     # the arrays are this loader's own: checked here, once
+        self._idx_ring = [None, None]                              # (pinned int64 buffer, event behind its last upload)
+        self._idx_turn = 0
+
+    def set_epoch(self, epoch: int) -> None:
+        """The epoch the next ``iter(loader)`` runs (DistributedSampler's name for it)."""
+        self.epoch = int(epoch)
+
+    def _samples(self) -> int:
+        if self.drop_last:
+            return self.n // self.world_size
+        return -(-self.n // self.world_size)
+
+    def __len__(self) -> int:
+        m = self._samples()
+        return m // self.batch_size if self.drop_last else -(-m // self.batch_size)
+
+    def __iter__(self) -> Iterator[Tuple[torch.Tensor, torch.Tensor, tuple]]:
+        order = epoch_order(self.n, self.epoch, self.shuffle, self.seed, self.rank, self.world_size, self.drop_last)
+        self.epoch += 1
+        order = order[:len(self) * self.batch_size]                # the loader's own drop_last (a no-op otherwise)
+        return self._device_batches(order) if self.device.type == "cuda" else self._host_batches(order)
+
+    def _host_batches(self, order: torch.Tensor):
+        idx = order.numpy()
+        for lo in range(0, len(idx), self.batch_size):
+            sel = idx[lo:lo + self.batch_size]
+            pick = order[lo:lo + self.batch_size]
+            yield self.pilots[pick], self.h_ideal[pick], _meta_tuple(self.meta[sel], self.channel_type[sel])
+
+    def _upload(self, order: torch.Tensor):
+        """One epoch's indices on the device: pinned slot (two, taken in turn) -> one asynchronous copy on the current stream.  A slot is
+        rewritten only when the event behind the copy that last read it (two epochs ago) has completed; if it has not -- the device is
+        two epochs behind the host -- the slot is left to that copy and a fresh buffer takes its place: the host never waits."""
+        turn, self._idx_turn = self._idx_turn, self._idx_turn ^ 1
+        slot = self._idx_ring[turn]
+        if slot is None or not slot[1].query() or slot[0].numel() < order.numel():
+            slot = (torch.empty(max(order.numel(), 1), dtype=torch.int64).pin_memory(), None)
+        host = slot[0][:order.numel()]
+        host.copy_(order)
+        stream = torch.cuda.current_stream(self.device)
+        with torch.cuda.device(self.device):
+            dev = host.to(self.device, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(stream)
+        self._idx_ring[turn] = (slot[0], done)
+        return dev, done, stream
+
+    def _device_batches(self, order: torch.Tensor):
+        if order.numel() == 0:
+            return
+        idx = order.numpy()
+        dev, done, up_stream = self._upload(order)
+        for lo in range(0, len(idx), self.batch_size):
+            sel = idx[lo:lo + self.batch_size]
+            stream = torch.cuda.current_stream(self.device)
+            if stream != up_stream:                                # the consumer changed streams inside the epoch: order it on the device
+                stream.wait_event(done)
+                dev.record_stream(stream)
+            # flags are not read: the loader made the indices itself
+            if torch.cuda.current_device() != self.device.index:   # the launch belongs to the loader's device, whichever is current
+                with torch.cuda.device(self.device):
+                    ideal, pilots, _ = self._gather(dev[lo:lo + self.batch_size])
+            else:
+                ideal, pilots, _ = self._gather(dev[lo:lo + self.batch_size])
+            yield pilots, ideal, _meta_tuple(self.meta[sel], self.channel_type[sel])
 
 
 def ls_mse_db_per_frame(h_ls_full: torch.Tensor, h_ideal: torch.Tensor) -> torch.Tensor:

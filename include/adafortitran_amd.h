@@ -234,6 +234,18 @@ int aft_pilot_gather_f32(const float *hzero_ls, float *pilots, int *counts, int 
  * (:264-303): db[b] = 10 log10( mean_i |ls[b,i] - ideal[b,i]|^2 ), complex64 [B, grid_elems] inputs. */
 int aft_ls_mse_db_f32(const float *ls, const float *ideal, float *db, int batch, int grid_elems, void *stream);
 
+/* Replaces the per-sample collation of DataLoader(MatDataset(...), shuffle=True) (reference src/main/trainer.py:505-511) for a data
+ * set that is resident: ideal_all complex64 [frames, grid_elems] and pilots_all complex64 [frames, pilot_elems] live in device memory
+ * or in pinned (device-addressable) host memory and are read in place.  index int64 [batch], ideal_out complex64 [batch, grid_elems],
+ * pilots_out complex64 [batch, pilot_elems] and flags int32 [batch] are device memory.  Output frame b of either array is a bit copy of
+ * frame index[b]; repeated indices are legal.  Nothing outside the two arrays is read whatever index holds: for an entry outside
+ * [0, frames) output frame b is zero-filled and flags[b] = 1, otherwise flags[b] = 0.  Every output element and every flag is written
+ * (the outputs need no initialisation); no atomics; one launch moves both arrays, nothing is synchronised.
+ * AFT_ERR_ARG (nothing launched): a NULL pointer, batch / frames / grid_elems / pilot_elems below 1, an array or the index not 8-byte
+ * aligned.  16-byte accesses are used for an array whose grid_elems (pilot_elems) is even and whose two bases are 16-byte aligned. */
+int aft_frame_gather_f32(const float *ideal_all, const float *pilots_all, const long long *index, float *ideal_out,
+                         float *pilots_out, int *flags, int batch, long long frames, int grid_elems, int pilot_elems, void *stream);
+
 /* ---- training path of the encoder ---- */
 
 /* Gradients of one nn.TransformerEncoderLayer: same fields and shapes as aft_layer_weights,
