@@ -58,6 +58,24 @@ class AftStepControl(C.Structure):
                 ("inv_sqrt_bc2", C.c_float), ("grad_norm", C.c_float), ("clip_coef", C.c_float), ("reserved", C.c_int32)]
 
 
+AFT_CHANSIM_MAX_TAPS, AFT_CHANSIM_MAX_RAYS, AFT_CHANSIM_MAX_VALUES = 32, 16, 16
+AFT_CHANSIM_MAX_PILOT_SCS, AFT_CHANSIM_MAX_PILOT_SYMBOLS = 64, 16
+
+
+class AftChanSim(C.Structure):
+    """aft_chansim: the channel simulator's configuration, by value (chansim.ChannelSimConfig.tables() fills it)."""
+    _fields_ = [
+        ("num_scs", C.c_int32), ("num_symbols", C.c_int32), ("pilot_scs", C.c_int32), ("pilot_symbols", C.c_int32),
+        ("taps", C.c_int32), ("rays", C.c_int32), ("n_snr", C.c_int32), ("n_ds", C.c_int32), ("n_dop", C.c_int32),
+        ("reserved", C.c_int32),
+        ("subcarrier_spacing_hz", C.c_double), ("symbol_period_s", C.c_double),
+        ("tap_delay", C.c_float * AFT_CHANSIM_MAX_TAPS), ("tap_amp", C.c_float * AFT_CHANSIM_MAX_TAPS),
+        ("snr_db", C.c_float * AFT_CHANSIM_MAX_VALUES), ("noise_sigma", C.c_float * AFT_CHANSIM_MAX_VALUES),
+        ("delay_spread_ns", C.c_float * AFT_CHANSIM_MAX_VALUES), ("doppler_hz", C.c_float * AFT_CHANSIM_MAX_VALUES),
+        ("pilot_sc_index", C.c_int32 * AFT_CHANSIM_MAX_PILOT_SCS), ("pilot_symbol_index", C.c_int32 * AFT_CHANSIM_MAX_PILOT_SYMBOLS),
+    ]
+
+
 class AftWeights(C.Structure):
     _fields_ = [
         ("up_w", _fp), ("up_b", _fp),
@@ -145,7 +163,7 @@ EXPORTED_SYMBOLS = (
     "aft_packed_weights_bytes", "aft_pack_weights_f32", "aft_forward_prepacked_f32",
     "aft_linear_forward_f32", "aft_mse_partial_f32", "aft_stage_upsample_f32",
     "aft_stage_adapter_f32", "aft_stage_embed_f32", "aft_stage_encoder_layer_f32",
-    "aft_stage_tail_f32", "aft_profile_kernel_f32", "aft_debug_fill_lds_f32", "aft_debug_peek_lds_f32", "aft_pilot_gather_f32", "aft_ls_mse_db_f32", "aft_frame_gather_f32",
+    "aft_stage_tail_f32", "aft_profile_kernel_f32", "aft_debug_fill_lds_f32", "aft_debug_peek_lds_f32", "aft_pilot_gather_f32", "aft_ls_mse_db_f32", "aft_frame_gather_f32", "aft_channel_sim_f32",
     "aft_encoder_tape_bytes", "aft_encoder_train_scratch_bytes",
     "aft_encoder_layer_fwd_train_f32", "aft_encoder_layer_fwd_train_chained_f32", "aft_encoder_layer_bwd_f32", "aft_adam_step_f32",
     "aft_grad_sumsq_scratch_bytes", "aft_grad_sumsq_f32", "aft_adam_prepare_f32", "aft_adam_step_ctrl_f32", "aft_grad_clip_f32",

@@ -78,6 +78,7 @@ def load_path(path: str):
     lib.aft_pilot_gather_f32.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
     lib.aft_ls_mse_db_f32.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp]
     lib.aft_frame_gather_f32.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_longlong, C.c_int, C.c_int, vp]
+    lib.aft_channel_sim_f32.argtypes = [C.POINTER(_abi.AftChanSim), C.c_ulonglong] + [C.c_longlong] * 4 + [C.c_int, vp, vp, vp, vp]
     lwp, lgp = C.POINTER(_abi.AftLayerWeights), C.POINTER(_abi.AftLayerGrads)
     for name in ("aft_encoder_tape_bytes", "aft_encoder_train_scratch_bytes"):
         getattr(lib, name).restype = C.c_size_t
@@ -128,12 +129,13 @@ def load_path(path: str):
     return lib
 
 
-def check(rc: int) -> None:
+def check(rc: int, lib=None) -> None:
     """0 -> ok; argument/shape codes -> ValueError (the reference's convention for bad input,
-    fortitran.py:157-158, linear.py:79-83); HIP failures -> RuntimeError."""
+    fortitran.py:157-158, linear.py:79-83); HIP failures -> RuntimeError.  ``lib``: the build the call was made through
+    (``load_path``) when it is not the product's -- the error text is that build's."""
     if rc == _abi.AFT_OK:
         return
-    msg = load().aft_last_error().decode(errors="replace")
+    msg = (lib or load()).aft_last_error().decode(errors="replace")
     if rc in (_abi.AFT_ERR_ARG, _abi.AFT_ERR_SHAPE):
         raise ValueError(msg)
     raise AftError(msg)

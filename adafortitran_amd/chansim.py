@@ -1,0 +1,330 @@
+"""A physical OFDM channel generator: training and evaluation data without a dataset.
+
+The reference ships no data (its ``.mat`` files came from a MATLAB link-level simulation) and
+``synth.make_inputs`` draws pilots and targets independently, which is fine for parity and timing and useless for learning.  This module
+DEFINES a doubly-selective multipath Rayleigh channel over the OFDM grid, the noisy LS estimate at the pilot positions and the three
+conditions the frame was drawn with, as a pure function of ``(seed, g)``, ``g`` the frame's global number:
+
+* ``simulate_frames_host`` evaluates the definition in float64 with NumPy -- the CPU path and the yardstick;
+* ``aft_channel_sim_f32`` (csrc/k_chansim.hip, through ``hip_ops.ChannelSimPlan``) evaluates it in float32 on the device, one launch
+  per batch;
+* ``SynthLoader`` yields ``ingest.ResidentLoader``'s batches from either; ``make_pack`` gives fixed sets in ``pack_mat_folder``'s format.
+
+The model, for frame ``g`` (sum-of-sinusoids taps, ``M = rays``; ``T_sym`` the symbol period, ``df`` the subcarrier spacing)::
+
+    h_p(t)  = amp_p * sum_m exp(j 2 pi (f_D T_sym cos(alpha_pm) t + phi_pm)),   alpha_pm = 2 pi (m + u_pm) / M,  phi_pm = 2 pi u'_pm
+    H[s, t] = sum_p h_p(t) exp(-j 2 pi s df d_p DS)                             d_p the tap's normalised delay, DS the delay spread
+    pilots  = H at the pilot positions + CN(0, 10^(-snr/10))                    Box-Muller on two uniforms (k + 0.5) 2^-23
+
+with ``amp_p = sqrt(pw_p / sum(pw) / M)``, so ``E|H|^2 = 1``, ``E[H[s,t+k] conj H[s,t]] = J0(2 pi f_D k T_sym)`` (the angles of a tap
+cover the circle uniformly) and ``E[H[s+d,t] conj H[s,t]] = sum_p pw_p exp(-j 2 pi d df d_p DS) / sum(pw)``.
+
+Random words are counter-based on ``synth._splitmix64``: ``word(seed, g, stream, index) = sm(sm(sm(seed) ^ g) ^ (stream << 32 | index))``
+with the streams below.  The configuration the definition sees is the one the device sees: the tables are rounded to float32 ONCE
+(``ChannelSimConfig.tables``), the two spacing-times-condition products are formed in float64 and rounded to float32 once.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass, field
+from typing import Dict, Iterator, Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+
+from . import _abi
+from .synth import _DOP_GRID, _DS_GRID, _M64, _SNR_GRID, _splitmix64
+
+STREAM_CONDITION, STREAM_ANGLE, STREAM_PHASE, STREAM_NOISE_RADIUS, STREAM_NOISE_ANGLE = range(5)
+CHANNEL_TYPE = "SYNTH"
+
+
+def _centred(n: int, k: int) -> Tuple[int, ...]:
+    return tuple(i * (n // k) + (n // k) // 2 for i in range(k))
+
+
+def _exponential_profile() -> np.ndarray:
+    delay = 0.5 * np.arange(12)
+    return np.stack([delay, 10.0 * np.log10(np.exp(-delay))], axis=1)
+
+
+@dataclass(frozen=True)
+class ChannelSimConfig:
+    """What a frame is drawn from.  ``profile`` rows are (delay in multiples of the RMS delay spread, power in dB) -- the form of a 3GPP
+    TDL table; the default is a 12-tap exponential profile, a user passes their own table.  ``pilot_scs`` / ``pilot_symbols`` default to
+    evenly centred positions (subcarriers 5, 15, .., 115 and symbols 3, 10 on the default grid)."""
+    ofdm: Tuple[int, int] = (120, 14)
+    pilot: Tuple[int, int] = (12, 2)
+    pilot_scs: Optional[Sequence[int]] = None
+    pilot_symbols: Optional[Sequence[int]] = None
+    subcarrier_spacing_hz: float = 15e3
+    symbol_period_s: float = 1.0 / 14e3
+    profile: Sequence = field(default_factory=_exponential_profile)
+    rays: int = 8
+    snr_db: Sequence[float] = tuple(float(v) for v in _SNR_GRID)
+    delay_spread_ns: Sequence[float] = tuple(float(v) for v in _DS_GRID)
+    doppler_hz: Sequence[float] = tuple(float(v) for v in _DOP_GRID)
+
+    def __post_init__(self) -> None:
+        S, T = (int(v) for v in self.ofdm)
+        Ps, Pt = (int(v) for v in self.pilot)
+        set_ = lambda k, v: object.__setattr__(self, k, v)  # noqa: E731
+        set_("ofdm", (S, T))
+        set_("pilot", (Ps, Pt))
+        if S < 1 or T < 1:
+            raise ValueError(f"ofdm grid {S} x {T}: both sizes must be at least 1")
+        if not (1 <= Ps <= _abi.AFT_CHANSIM_MAX_PILOT_SCS and 1 <= Pt <= _abi.AFT_CHANSIM_MAX_PILOT_SYMBOLS and Ps <= S and Pt <= T):
+            raise ValueError(f"pilot grid {Ps} x {Pt}: at most {_abi.AFT_CHANSIM_MAX_PILOT_SCS} x {_abi.AFT_CHANSIM_MAX_PILOT_SYMBOLS} "
+                             f"and no larger than the ofdm grid {S} x {T}")
+        for name, count, size in (("pilot_scs", Ps, S), ("pilot_symbols", Pt, T)):
+            given = getattr(self, name)
+            idx = _centred(size, count) if given is None else tuple(int(v) for v in given)
+            if len(idx) != count or any(v < 0 or v >= size for v in idx) or any(b <= a for a, b in zip(idx, idx[1:])):
+                raise ValueError(f"{name} = {list(idx)}: need {count} strictly increasing positions in [0, {size})")
+            set_(name, idx)
+        prof = np.array(self.profile, dtype=np.float64)
+        if prof.ndim != 2 or prof.shape[1] != 2 or not 1 <= prof.shape[0] <= _abi.AFT_CHANSIM_MAX_TAPS or not np.isfinite(prof).all():
+            raise ValueError(f"profile must be a finite [P, 2] table (normalised delay, power in dB) with 1 <= P <= "
+                             f"{_abi.AFT_CHANSIM_MAX_TAPS}; got shape {prof.shape}")
+        if (prof[:, 0] < 0).any():
+            raise ValueError("profile delays must not be negative")
+        prof.setflags(write=False)
+        set_("profile", prof)
+        if not 1 <= int(self.rays) <= _abi.AFT_CHANSIM_MAX_RAYS:
+            raise ValueError(f"rays = {self.rays}: 1 to {_abi.AFT_CHANSIM_MAX_RAYS} sinusoids per tap")
+        set_("rays", int(self.rays))
+        for name in ("snr_db", "delay_spread_ns", "doppler_hz"):
+            vals = tuple(float(v) for v in np.atleast_1d(np.asarray(getattr(self, name), dtype=np.float64)))
+            if not 1 <= len(vals) <= _abi.AFT_CHANSIM_MAX_VALUES or not np.isfinite(vals).all():
+                raise ValueError(f"{name} must list 1 to {_abi.AFT_CHANSIM_MAX_VALUES} finite values; got {len(vals)}")
+            set_(name, vals)
+        if min(self.delay_spread_ns) < 0 or min(self.doppler_hz) < 0:
+            raise ValueError("delay_spread_ns and doppler_hz must not be negative")
+        if not (self.subcarrier_spacing_hz > 0 and self.symbol_period_s > 0):
+            raise ValueError("subcarrier_spacing_hz and symbol_period_s must be positive")
+
+    def tables(self) -> Dict[str, np.ndarray]:
+        """The numbers the definition works with, rounded to float32 exactly as ``aft_chansim`` carries them."""
+        power = 10.0 ** (self.profile[:, 1] / 10.0)
+        f32 = lambda v: np.asarray(v, dtype=np.float64).astype(np.float32)  # noqa: E731
+        ds, dop = f32(self.delay_spread_ns), f32(self.doppler_hz)
+        return {
+            "tap_delay": f32(self.profile[:, 0]),
+            "tap_amp": f32(np.sqrt(power / power.sum() / self.rays)),
+            "snr_db": f32(self.snr_db),
+            "noise_sigma": f32(10.0 ** (-np.asarray(self.snr_db) / 20.0)),
+            "delay_spread_ns": ds,
+            "doppler_hz": dop,
+            # the launcher forms these two the same way: double products, one rounding
+            "delay_turns": (np.float64(self.subcarrier_spacing_hz) * ds.astype(np.float64) * 1e-9).astype(np.float32),
+            "doppler_turns": (dop.astype(np.float64) * np.float64(self.symbol_period_s)).astype(np.float32),
+        }
+
+    def to_struct(self) -> "_abi.AftChanSim":
+        t = self.tables()
+        sim = _abi.AftChanSim()
+        sim.num_scs, sim.num_symbols = self.ofdm
+        sim.pilot_scs, sim.pilot_symbols = self.pilot
+        sim.taps, sim.rays = len(t["tap_delay"]), self.rays
+        sim.n_snr, sim.n_ds, sim.n_dop = len(self.snr_db), len(self.delay_spread_ns), len(self.doppler_hz)
+        sim.subcarrier_spacing_hz, sim.symbol_period_s = float(self.subcarrier_spacing_hz), float(self.symbol_period_s)
+        for name in ("tap_delay", "tap_amp", "snr_db", "noise_sigma", "delay_spread_ns", "doppler_hz"):
+            arr = getattr(sim, name)
+            for i, v in enumerate(t[name]):
+                arr[i] = float(v)
+        for i, v in enumerate(self.pilot_scs):
+            sim.pilot_sc_index[i] = v
+        for i, v in enumerate(self.pilot_symbols):
+            sim.pilot_symbol_index[i] = v
+        return sim
+
+
+# ---- the hash: written once, mirrored by csrc/k_chansim.hip ----------------------------------------------------------------
+
+def frame_keys(seed: int, frame_ids) -> np.ndarray:
+    """``sm(sm(seed) ^ g)`` per frame, uint64."""
+    g = np.asarray(frame_ids, dtype=np.int64)
+    if g.ndim != 1 or (g < 0).any():
+        raise ValueError("frame_ids must be a vector of non-negative frame numbers")
+    sk = _splitmix64(np.array([int(seed) & 0xFFFFFFFFFFFFFFFF], dtype=np.uint64))[0]
+    return _splitmix64(sk ^ g.astype(np.uint64))
+
+
+def words(keys: np.ndarray, stream: int, index) -> np.ndarray:
+    """64-bit words of ``stream`` at ``index`` (broadcast against ``keys``)."""
+    tag = (np.uint64(stream) << np.uint64(32)) | np.asarray(index, dtype=np.uint64)
+    return _splitmix64((keys ^ tag) & _M64)
+
+
+def _pick(keys: np.ndarray, which: int, n: int) -> np.ndarray:
+    return (((words(keys, STREAM_CONDITION, which) >> np.uint64(40)) * np.uint64(n)) >> np.uint64(24)).astype(np.int64)
+
+
+def frame_conditions(cfg: ChannelSimConfig, seed: int, frame_ids) -> np.ndarray:
+    """float32 ``[n, 3]``: the (snr_db, delay_spread_ns, doppler_hz) of each frame -- integer arithmetic on the hash, so host and
+    device agree exactly."""
+    return _conditions(cfg.tables(), frame_keys(seed, frame_ids))[0]
+
+
+def _conditions(t: Dict[str, np.ndarray], keys: np.ndarray):
+    idx = [_pick(keys, k, len(t[name])) for k, name in enumerate(("snr_db", "delay_spread_ns", "doppler_hz"))]
+    meta = np.stack([t["snr_db"][idx[0]], t["delay_spread_ns"][idx[1]], t["doppler_hz"][idx[2]]], axis=1).astype(np.float32)
+    return meta, idx
+
+
+def simulate_frames_host(cfg: ChannelSimConfig, seed: int, frame_ids, return_noise: bool = False):
+    """The definition in float64: ``(ideal complex128 [n,S,T], pilots complex128 [n,Ps,Pt], meta float32 [n,3])`` for the given global
+    frame numbers (and the noise that was added, complex128 ``[n,Ps,Pt]``, with ``return_noise``).  Needs no library."""
+    t = cfg.tables()
+    keys = frame_keys(seed, frame_ids)
+    n = len(keys)
+    S, T = cfg.ofdm
+    Ps, Pt = cfg.pilot
+    P, M = len(t["tap_delay"]), cfg.rays
+    meta, (i_snr, i_ds, i_dop) = _conditions(t, keys)
+    kk = keys[:, None, None]
+    ray = (16 * np.arange(P)[:, None] + np.arange(M)[None, :])[None]                                       # [1,P,M]
+    u = (words(kk, STREAM_ANGLE, ray) >> np.uint64(44)).astype(np.float64) * 2.0 ** -20
+    phase = (words(kk, STREAM_PHASE, ray) >> np.uint64(40)).astype(np.float64) * 2.0 ** -24                # turns
+    rate = t["doppler_turns"].astype(np.float64)[i_dop][:, None, None] * np.cos(2.0 * np.pi * (np.arange(M)[None, None, :] + u) / M)
+    turns = rate[..., None] * np.arange(T)[None, None, None, :] + phase[..., None]                         # [n,P,M,T]
+    gain = t["tap_amp"].astype(np.float64)[None, :, None] * np.exp(2j * np.pi * (turns - np.floor(turns))).sum(axis=2)   # [n,P,T]
+    per_sc = t["delay_turns"].astype(np.float64)[i_ds][:, None] * t["tap_delay"].astype(np.float64)[None, :]             # [n,P]
+    x = per_sc[:, :, None] * np.arange(S)[None, None, :]                                                   # [n,P,S]
+    phasor = np.exp(-2j * np.pi * (x - np.floor(x)))
+    ideal = np.einsum("nps,npt->nst", phasor, gain)
+    q = np.arange(Ps * Pt)[None, :]
+    k1 = (words(keys[:, None], STREAM_NOISE_RADIUS, q) >> np.uint64(41)).astype(np.float64)
+    k2 = (words(keys[:, None], STREAM_NOISE_ANGLE, q) >> np.uint64(41)).astype(np.float64)
+    u1, u2 = (k1 + 0.5) * 2.0 ** -23, (k2 + 0.5) * 2.0 ** -23
+    sigma = t["noise_sigma"].astype(np.float64)[i_snr][:, None]
+    noise = (sigma * np.sqrt(-np.log(u1)) * np.exp(2j * np.pi * u2)).reshape(n, Ps, Pt)
+    pilots = ideal[:, np.asarray(cfg.pilot_scs)[:, None], np.asarray(cfg.pilot_symbols)[None, :]] + noise
+    return (ideal, pilots, meta, noise) if return_noise else (ideal, pilots, meta)
+
+
+def _pinned(cfg: ChannelSimConfig, snr_db=None, delay_spread_ns=None, doppler_hz=None) -> ChannelSimConfig:
+    import dataclasses
+    over = {k: (float(v),) for k, v in (("snr_db", snr_db), ("delay_spread_ns", delay_spread_ns), ("doppler_hz", doppler_hz))
+            if v is not None}
+    return dataclasses.replace(cfg, **over) if over else cfg
+
+
+def make_pack(cfg: ChannelSimConfig, n: int, seed: int, snr_db=None, delay_spread_ns=None, doppler_hz=None) -> Dict[str, np.ndarray]:
+    """Frames ``[0, n)`` of ``seed`` as a pack in ``ingest.pack_mat_folder``'s format (``h_ideal``, ``h_ls_sparse``, ``h_ls_full``,
+    ``meta [n,5]`` = (frame number, snr, ds, dop, 0), ``channel_type`` "SYNTH"), any condition pinned to one value: fixed validation
+    and test sets per condition for ``PackedLoader`` / ``ResidentLoader`` / ``get_test_stats`` / the LS-baseline kernel.
+    ``h_ls_full`` is the pilots' LS estimate interpolated linearly over the grid (held constant outside the pilots' span), the baseline
+    an estimator has to beat."""
+    if n < 1:
+        raise ValueError(f"make_pack needs n >= 1 (got {n})")
+    cfg = _pinned(cfg, snr_db, delay_spread_ns, doppler_hz)
+    ideal, pilots, cond = simulate_frames_host(cfg, seed, np.arange(n))
+    ideal, pilots = ideal.astype(np.complex64), pilots.astype(np.complex64)
+    if (pilots == 0).any():                                      # a pilot of exactly zero would vanish from the sparse grid
+        raise ValueError("a simulated pilot is exactly zero: choose another seed")
+    sc, sym = np.asarray(cfg.pilot_scs), np.asarray(cfg.pilot_symbols)
+    sparse = np.zeros_like(ideal)
+    sparse[:, sc[:, None], sym[None, :]] = pilots
+    meta = np.zeros((n, 5), np.float32)
+    meta[:, 0] = np.arange(n)
+    meta[:, 1:4] = cond
+    return {"h_ideal": ideal, "h_ls_sparse": sparse, "h_ls_full": ls_interpolate(cfg, pilots), "meta": meta,
+            "channel_type": np.asarray([CHANNEL_TYPE] * n)}
+
+
+def ls_interpolate(cfg: ChannelSimConfig, pilots: np.ndarray) -> np.ndarray:
+    """Pilots ``[n,Ps,Pt]`` -> complex64 ``[n,S,T]``: linear interpolation along the subcarriers, then along the symbols."""
+    S, T = cfg.ofdm
+    sc, sym = np.asarray(cfg.pilot_scs, dtype=np.float64), np.asarray(cfg.pilot_symbols, dtype=np.float64)
+
+    def weights(at: np.ndarray, size: int) -> np.ndarray:       # [size, len(at)] interpolation matrix, clamped at the ends
+        w = np.zeros((size, len(at)))
+        for i in range(size):
+            if len(at) == 1 or i <= at[0]:
+                w[i, 0] = 1.0
+            elif i >= at[-1]:
+                w[i, -1] = 1.0
+            else:
+                k = int(np.searchsorted(at, i, side="right")) - 1
+                f = (i - at[k]) / (at[k + 1] - at[k])
+                w[i, k], w[i, k + 1] = 1.0 - f, f
+        return w
+
+    return np.einsum("si,nij,tj->nst", weights(sc, S), pilots.astype(np.complex128), weights(sym, T)).astype(np.complex64)
+
+
+class SynthLoader:
+    """Training batches from the simulator, in the format ``ingest.ResidentLoader`` yields: ``(pilots complex64 [b,Ps,Pt], h_ideal
+    complex64 [b,S,T]`` on ``device``, ``(file_no, snr, ds, dop, n: float32 [b,1] host tensors, [tuple of b "SYNTH" strings]))``;
+    ``file_no`` is the frame's global number, ``n`` is 0.  ``file_no`` is informational (the model reads snr, ds and dop only) and, being
+    float32 like the reference's, exact only below 2^24: 256 epochs of 65 536 fresh frames.  ``epoch_frames`` gives the exact numbers.
+
+    An epoch is ``frames_per_epoch`` positions.  Rank ``r`` of ``world_size`` takes positions ``r, r + W, ..`` and wraps round the
+    epoch where ``DistributedSampler`` pads (``drop_last``: the epoch is cut to a multiple of W instead, and a ragged last batch is
+    dropped as well); position q of epoch e is global frame ``e * frames_per_epoch + q`` with ``fresh_each_epoch`` (data never runs
+    out) and frame ``q`` without (every epoch replays ``[0, n)``).  Frames are independent draws, so there is nothing to shuffle.
+    Every ``iter(loader)`` runs epoch ``loader.epoch`` and adds one to it; ``set_epoch`` rewinds, as ``ResidentLoader``'s does.
+
+    On a HIP device a batch is one launch of ``aft_channel_sim_f32`` on the consumer's current stream plus the host's own evaluation
+    of the same hash for the meta tensors: no device read, no ``.item()``, no side stream, no copy in either direction.  On
+    ``device="cpu"`` the float64 definition is evaluated and rounded to complex64."""
+
+    def __init__(self, cfg: ChannelSimConfig, batch_size: int, frames_per_epoch: int, device: Union[str, torch.device] = "cpu",
+                 seed: int = 0, rank: int = 0, world_size: int = 1, drop_last: bool = False, fresh_each_epoch: bool = True) -> None:
+        if batch_size < 1 or world_size < 1 or not 0 <= rank < world_size:
+            raise ValueError(f"bad batch_size / rank / world_size: {batch_size} / {rank} / {world_size}")
+        if frames_per_epoch < 1:
+            raise ValueError(f"frames_per_epoch must be at least 1 (got {frames_per_epoch})")
+        self.cfg, self.batch_size, self.n = cfg, int(batch_size), int(frames_per_epoch)
+        self.device = torch.device(device)
+        self.seed, self.rank, self.world_size = int(seed), int(rank), int(world_size)
+        self.drop_last, self.fresh_each_epoch = bool(drop_last), bool(fresh_each_epoch)
+        self.epoch = 0
+        self._tables = cfg.tables()
+        self._plan = None
+        if self.device.type == "cuda":
+            from .hip_ops import ChannelSimPlan
+            self._plan = ChannelSimPlan(cfg, self.device)
+            self.device = self._plan.device
+
+    def set_epoch(self, epoch: int) -> None:
+        self.epoch = int(epoch)
+
+    def _samples(self) -> int:
+        return self.n // self.world_size if self.drop_last else -(-self.n // self.world_size)
+
+    def __len__(self) -> int:
+        m = self._samples()
+        return m // self.batch_size if self.drop_last else -(-m // self.batch_size)
+
+    def epoch_frames(self, epoch: int) -> np.ndarray:
+        """The global frame numbers this rank visits in ``epoch``, in order (int64)."""
+        count = len(self) * self.batch_size if self.drop_last else self._samples()
+        base = epoch * self.n if self.fresh_each_epoch else 0
+        return base + (self.rank + self.world_size * np.arange(count, dtype=np.int64)) % self.n
+
+    def __iter__(self) -> Iterator[Tuple[torch.Tensor, torch.Tensor, tuple]]:
+        epoch, self.epoch = self.epoch, self.epoch + 1
+        return self._batches(epoch)
+
+    def _meta(self, frames: np.ndarray) -> tuple:
+        cond = _conditions(self._tables, frame_keys(self.seed, frames))[0]
+        m = torch.from_numpy(np.concatenate([frames.astype(np.float32)[:, None], cond, np.zeros((len(frames), 1), np.float32)], axis=1))
+        return (m[:, 0:1], m[:, 1:2], m[:, 2:3], m[:, 3:4], m[:, 4:5], [tuple(CHANNEL_TYPE for _ in frames)])
+
+    def _batches(self, epoch: int):
+        frames = self.epoch_frames(epoch)
+        base = epoch * self.n if self.fresh_each_epoch else 0
+        for lo in range(0, len(frames), self.batch_size):
+            part = frames[lo:lo + self.batch_size]
+            if self._plan is None:
+                ideal, pilots, _ = simulate_frames_host(self.cfg, self.seed, part)
+                yield torch.from_numpy(pilots.astype(np.complex64)), torch.from_numpy(ideal.astype(np.complex64)), self._meta(part)
+                continue
+            args = (self.seed, base, self.rank + self.world_size * lo, self.world_size, self.n, len(part))
+            if torch.cuda.current_device() != self.device.index:    # the launch belongs to the loader's device, whichever is current
+                with torch.cuda.device(self.device):
+                    ideal, pilots, _ = self._plan(*args)
+            else:
+                ideal, pilots, _ = self._plan(*args)
+            yield pilots, ideal, self._meta(part)

@@ -758,6 +758,44 @@ int aft_frame_gather_f32(const float *ideal_all, const float *pilots_all, const 
     return e == hipSuccess ? AFT_OK : hip_fail("frame_gather", e);
 }
 
+int aft_channel_sim_f32(const aft_chansim *sim, unsigned long long seed, long long base, long long start, long long stride,
+                        long long modulo, int batch, float *ideal, float *pilots, float *meta, void *stream) {
+    AFT_REQUIRE(sim && ideal && pilots && meta, "channel sim: NULL pointer argument");
+    AFT_REQUIRE((reinterpret_cast<uintptr_t>(ideal) | reinterpret_cast<uintptr_t>(pilots)) % 8 == 0,
+                "channel sim: ideal and pilots must be 8-byte aligned");
+    AFT_REQUIRE(reinterpret_cast<uintptr_t>(meta) % 4 == 0, "channel sim: meta must be 4-byte aligned");
+    AFT_REQUIRE(batch >= 1, "channel sim: batch must be at least 1 (got %d)", batch);
+    const long long far = 1LL << 62;
+    AFT_REQUIRE(base >= 0 && start >= 0 && stride >= 1 && modulo >= 1 && base < far && modulo < far && start < far &&
+                    stride <= (far - start) / batch,
+                "channel sim: bad frame numbers (base %lld, start %lld, stride %lld, modulo %lld: base, start >= 0, stride, modulo >= 1, "
+                "all frame numbers below 2^62)", base, start, stride, modulo);
+    auto shape = [](bool ok, const char *what, int got, int most) {
+        if (!ok) set_error("channel sim: %s = %d is outside 1..%d", what, got, most);
+        return ok;
+    };
+    auto within = [&](const char *what, int got, int most) { return shape(got >= 1 && got <= most, what, got, most); };
+    if (!within("num_scs", sim->num_scs, 1 << 20) || !within("num_symbols", sim->num_symbols, 1 << 20) ||
+        !within("pilot_scs", sim->pilot_scs, AFT_CHANSIM_MAX_PILOT_SCS) ||
+        !within("pilot_symbols", sim->pilot_symbols, AFT_CHANSIM_MAX_PILOT_SYMBOLS) || !within("taps", sim->taps, AFT_CHANSIM_MAX_TAPS) ||
+        !within("rays", sim->rays, AFT_CHANSIM_MAX_RAYS) || !within("n_snr", sim->n_snr, AFT_CHANSIM_MAX_VALUES) ||
+        !within("n_ds", sim->n_ds, AFT_CHANSIM_MAX_VALUES) || !within("n_dop", sim->n_dop, AFT_CHANSIM_MAX_VALUES))
+        return AFT_ERR_SHAPE;
+    for (int i = 0; i < sim->pilot_scs; ++i)
+        if (sim->pilot_sc_index[i] < 0 || sim->pilot_sc_index[i] >= sim->num_scs) {
+            set_error("channel sim: pilot_sc_index[%d] = %d is outside the grid's %d subcarriers", i, sim->pilot_sc_index[i], sim->num_scs);
+            return AFT_ERR_SHAPE;
+        }
+    for (int j = 0; j < sim->pilot_symbols; ++j)
+        if (sim->pilot_symbol_index[j] < 0 || sim->pilot_symbol_index[j] >= sim->num_symbols) {
+            set_error("channel sim: pilot_symbol_index[%d] = %d is outside the grid's %d symbols", j, sim->pilot_symbol_index[j],
+                      sim->num_symbols);
+            return AFT_ERR_SHAPE;
+        }
+    hipError_t e = launch_channel_sim(*sim, seed, base, start, stride, modulo, batch, ideal, pilots, meta, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? AFT_OK : hip_fail("channel_sim", e);
+}
+
 int aft_debug_fill_lds_f32(float value, void *stream) {
     hipError_t e = launch_fill_lds(value, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? AFT_OK : hip_fail("fill_lds", e);

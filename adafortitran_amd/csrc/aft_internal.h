@@ -280,6 +280,9 @@ hipError_t launch_ls_mse_db(const float *ls, const float *ideal, float *db, int 
 hipError_t launch_frame_gather(const float *ideal_all, const float *pilots_all, const long long *index, float *ideal_out,
                                float *pilots_out, int *flags, int batch, long long frames, int grid_elems, int pilot_elems,
                                hipStream_t st);
+// the channel simulator (k_chansim.hip): `sim` has passed aft_channel_sim_f32's checks
+hipError_t launch_channel_sim(const aft_chansim &sim, unsigned long long seed, long long base, long long start, long long stride,
+                              long long modulo, int batch, float *ideal, float *pilots, float *meta, hipStream_t st);
 hipError_t launch_mse(const float *est, const float *ref, double *sum_sq, long long n_complex, hipStream_t st);
 hipError_t launch_fill_lds(float value, hipStream_t st);   // test hook: every CU's LDS filled with `value`
 hipError_t launch_peek_lds(float *out, int workgroups, int n, hipStream_t st);   // ... and what a kernel finds in its LDS at start

@@ -388,6 +388,33 @@ class FrameGatherPlan:
         return ideal, pilots, flags
 
 
+class ChannelSimPlan:
+    """A channel-simulator configuration (``chansim.ChannelSimConfig``) that has been turned into the ``aft_chansim`` struct ONCE.
+    ``plan(seed, base, start, stride, modulo, batch)`` -> ``(ideal complex64 [batch,S,T], pilots complex64 [batch,Ps,Pt], meta float32
+    [batch,3])`` on the plan's device: three ``torch.empty``, one ``ctypes`` call, one launch (``aft_channel_sim_f32``) on the current
+    stream of that device, no upload and no synchronisation.  Output frame b is global frame ``base + (start + b * stride) % modulo``.
+    The plan trusts its caller in one thing only: its device is the current one."""
+
+    def __init__(self, cfg, device: torch.device) -> None:
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError(f"ChannelSimPlan runs on a HIP device (got {device}); chansim.simulate_frames_host is the CPU path")
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device.index is None else device
+        self.cfg = cfg
+        self.sim = cfg.to_struct()                              # validated by the config itself; the entry point checks again
+        self.grid, self.pilot = tuple(cfg.ofdm), tuple(cfg.pilot)
+
+    def __call__(self, seed: int, base: int, start: int, stride: int, modulo: int, batch: int, lib=None):
+        lib = lib or _lib.load()
+        dev = self.device
+        ideal = torch.empty((batch, *self.grid), dtype=torch.complex64, device=dev)      # the kernel writes every element
+        pilots = torch.empty((batch, *self.pilot), dtype=torch.complex64, device=dev)
+        meta = torch.empty((batch, 3), dtype=torch.float32, device=dev)
+        _lib.check(lib.aft_channel_sim_f32(self.sim, seed & 0xFFFFFFFFFFFFFFFF, base, start, stride, modulo, batch, ideal.data_ptr(),
+                                           pilots.data_ptr(), meta.data_ptr(), _lib.current_stream_ptr(dev)), lib)
+        return ideal, pilots, meta
+
+
 def ls_mse_db(ls: torch.Tensor, ideal: torch.Tensor) -> torch.Tensor:
     """Per-frame LS-baseline MSE in dB, float32 [B] (reference utils.py:248-261 per file)."""
     lib = _lib.load()

@@ -246,6 +246,52 @@ int aft_ls_mse_db_f32(const float *ls, const float *ideal, float *db, int batch,
 int aft_frame_gather_f32(const float *ideal_all, const float *pilots_all, const long long *index, float *ideal_out,
                          float *pilots_out, int *flags, int batch, long long frames, int grid_elems, int pilot_elems, void *stream);
 
+/* ---- training data made on the device: the OFDM channel simulator (adafortitran_amd/chansim.py holds the definition) ----
+ *
+ * A frame is a pure function of (seed, g), g its global frame number: a doubly-selective multipath Rayleigh channel over the S x T
+ * grid, its noisy LS estimate at the pilot positions, and the three conditions it was drawn with.
+ *   word(stream, index) = splitmix64(kf ^ (stream << 32 | index)),   kf = splitmix64(splitmix64(seed) ^ g)
+ *   conditions (stream 0; index 0 snr, 1 delay spread, 2 doppler):  value[((word >> 40) * n_values) >> 24]
+ *   ray (p, m), index 16 p + m:  angle a = (m + (word(1) >> 44) 2^-20) / rays turns,  phase f = (word(2) >> 40) 2^-24 turns
+ *   h_p(t) = tap_amp[p] sum_m exp(j 2 pi (doppler_hz symbol_period_s cos(2 pi a) t + f))
+ *   H[s, t] = sum_p h_p(t) exp(-j 2 pi s subcarrier_spacing_hz tap_delay[p] delay_spread_ns 1e-9)
+ *   pilots[i, j] = H[pilot_sc_index[i], pilot_symbol_index[j]] + noise_sigma sqrt(-ln u1) exp(j 2 pi u2),  index i pilot_symbols + j,
+ *                  u1 = ((word(3) >> 41) + 0.5) 2^-23,  u2 = ((word(4) >> 41) + 0.5) 2^-23
+ * Every phase is formed in turns and reduced to [0, 1) before its sine / cosine.  The two products of a spacing and a condition are
+ * formed in double and rounded to float once, on the host (float(subcarrier_spacing_hz * delay_spread_ns[i] * 1e-9),
+ * float(doppler_hz[i] * symbol_period_s)); everything per frame is float32.  The caller supplies what needs pow():
+ * tap_amp[p] = sqrt(power_p / sum(power) / rays) (unit mean |H|^2) and noise_sigma[i] = 10^(-snr_db[i] / 20). */
+#define AFT_CHANSIM_MAX_TAPS 32
+#define AFT_CHANSIM_MAX_RAYS 16
+#define AFT_CHANSIM_MAX_VALUES 16
+#define AFT_CHANSIM_MAX_PILOT_SCS 64
+#define AFT_CHANSIM_MAX_PILOT_SYMBOLS 16
+typedef struct aft_chansim {
+    int32_t num_scs, num_symbols;      /* OFDM grid S x T, any size (ideal is [batch, S, T])             */
+    int32_t pilot_scs, pilot_symbols;  /* pilot grid, at most 64 x 16                                    */
+    int32_t taps, rays;                /* at most 32 taps of at most 16 sinusoids each                   */
+    int32_t n_snr, n_ds, n_dop;        /* values per condition, 1..16 each                               */
+    int32_t reserved;
+    double subcarrier_spacing_hz, symbol_period_s;
+    float tap_delay[AFT_CHANSIM_MAX_TAPS];   /* in multiples of the RMS delay spread                     */
+    float tap_amp[AFT_CHANSIM_MAX_TAPS];     /* linear, per sinusoid (see above)                         */
+    float snr_db[AFT_CHANSIM_MAX_VALUES], noise_sigma[AFT_CHANSIM_MAX_VALUES];
+    float delay_spread_ns[AFT_CHANSIM_MAX_VALUES], doppler_hz[AFT_CHANSIM_MAX_VALUES];
+    int32_t pilot_sc_index[AFT_CHANSIM_MAX_PILOT_SCS], pilot_symbol_index[AFT_CHANSIM_MAX_PILOT_SYMBOLS];
+} aft_chansim;
+
+/* One launch, one workgroup per frame: output frame b is global frame g = base + ((start + b stride) mod modulo) -- a contiguous
+ * run (stride 1, modulo large) or a rank's share of an epoch that wraps the way DistributedSampler pads.  ideal complex64
+ * [batch, S, T], pilots complex64 [batch, pilot_scs, pilot_symbols] and meta float32 [batch, 3] = (snr_db, delay_spread_ns,
+ * doppler_hz) are device memory.  `sim` is read during the call only and travels to the kernel by value: nothing is uploaded.
+ * Every output element is written (no initialisation needed); no atomics; nothing is synchronised; a frame's bits do not depend on
+ * batch, b or the other arguments.  16-byte stores when T is even and ideal is 16-byte aligned, 8-byte stores otherwise.
+ * Nothing is launched on AFT_ERR_ARG (a NULL pointer; ideal / pilots not 8-byte or meta not 4-byte aligned; batch < 1; base or start
+ * negative, stride or modulo below 1, or a frame number past 2^62) and AFT_ERR_SHAPE (a dimension below 1 or a table beyond its
+ * bound, a pilot index outside the grid). */
+int aft_channel_sim_f32(const aft_chansim *sim, unsigned long long seed, long long base, long long start, long long stride,
+                        long long modulo, int batch, float *ideal, float *pilots, float *meta, void *stream);
+
 /* ---- training path of the encoder ---- */
 
 /* Gradients of one nn.TransformerEncoderLayer: same fields and shapes as aft_layer_weights,
