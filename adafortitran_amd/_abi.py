@@ -76,6 +76,17 @@ class AftChanSim(C.Structure):
     ]
 
 
+class AftLmmse(C.Structure):
+    """aft_lmmse: the LMMSE baseline's plan, by value (lmmse.LmmseTables.to_struct() fills it)."""
+    _fields_ = [
+        ("num_scs", C.c_int32), ("num_symbols", C.c_int32), ("pilot_scs", C.c_int32), ("pilot_symbols", C.c_int32),
+        ("n_snr", C.c_int32), ("n_ds", C.c_int32), ("n_dop", C.c_int32),
+        ("fixed_snr", C.c_int32), ("fixed_ds", C.c_int32), ("fixed_dop", C.c_int32),
+        ("snr_db", C.c_float * AFT_CHANSIM_MAX_VALUES), ("delay_spread_ns", C.c_float * AFT_CHANSIM_MAX_VALUES),
+        ("doppler_hz", C.c_float * AFT_CHANSIM_MAX_VALUES), ("noise_var", C.c_float * AFT_CHANSIM_MAX_VALUES),
+    ]
+
+
 class AftWeights(C.Structure):
     _fields_ = [
         ("up_w", _fp), ("up_b", _fp),
@@ -164,6 +175,7 @@ EXPORTED_SYMBOLS = (
     "aft_linear_forward_f32", "aft_mse_partial_f32", "aft_stage_upsample_f32",
     "aft_stage_adapter_f32", "aft_stage_embed_f32", "aft_stage_encoder_layer_f32",
     "aft_stage_tail_f32", "aft_profile_kernel_f32", "aft_debug_fill_lds_f32", "aft_debug_peek_lds_f32", "aft_pilot_gather_f32", "aft_ls_mse_db_f32", "aft_frame_gather_f32", "aft_channel_sim_f32",
+    "aft_lmmse_table_floats", "aft_lmmse_f32",
     "aft_encoder_tape_bytes", "aft_encoder_train_scratch_bytes",
     "aft_encoder_layer_fwd_train_f32", "aft_encoder_layer_fwd_train_chained_f32", "aft_encoder_layer_bwd_f32", "aft_adam_step_f32",
     "aft_grad_sumsq_scratch_bytes", "aft_grad_sumsq_f32", "aft_adam_prepare_f32", "aft_adam_step_ctrl_f32", "aft_grad_clip_f32",
@@ -176,6 +188,6 @@ EXPORTED_SYMBOLS = (
 #: size queries (return size_t, not a status code)
 SIZE_SYMBOLS = ("aft_workspace_bytes", "aft_packed_weights_bytes", "aft_encoder_tape_bytes", "aft_encoder_train_scratch_bytes",
                 "aft_conv_enhancer_scratch_bytes", "aft_conv_enhancer_fwd_scratch_bytes", "aft_dense_bwd_scratch_bytes",
-                "aft_embed_bwd_scratch_bytes", "aft_tail_bwd_scratch_bytes", "aft_grad_sumsq_scratch_bytes")
+                "aft_embed_bwd_scratch_bytes", "aft_tail_bwd_scratch_bytes", "aft_grad_sumsq_scratch_bytes", "aft_lmmse_table_floats")
 REGION_IDS = {"conv_enhanced": 0, "tokens6": 1, "enc_out": 2}   # aft_workspace_region
 KERNEL_IDS = {"upsample": 0, "embed": 1, "qkv": 2, "attention": 3, "chain": 4, "tail": 5, "chain_last": 6, "encoder_plane": 7, "prologue": 8}

@@ -79,6 +79,9 @@ def load_path(path: str):
     lib.aft_ls_mse_db_f32.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp]
     lib.aft_frame_gather_f32.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_longlong, C.c_int, C.c_int, vp]
     lib.aft_channel_sim_f32.argtypes = [C.POINTER(_abi.AftChanSim), C.c_ulonglong] + [C.c_longlong] * 4 + [C.c_int, vp, vp, vp, vp]
+    lib.aft_lmmse_table_floats.restype = C.c_size_t
+    lib.aft_lmmse_table_floats.argtypes = [C.POINTER(_abi.AftLmmse)]
+    lib.aft_lmmse_f32.argtypes = [C.POINTER(_abi.AftLmmse), vp, vp, vp, vp, vp, vp, C.c_int, vp]
     lwp, lgp = C.POINTER(_abi.AftLayerWeights), C.POINTER(_abi.AftLayerGrads)
     for name in ("aft_encoder_tape_bytes", "aft_encoder_train_scratch_bytes"):
         getattr(lib, name).restype = C.c_size_t

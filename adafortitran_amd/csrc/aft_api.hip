@@ -796,6 +796,49 @@ int aft_channel_sim_f32(const aft_chansim *sim, unsigned long long seed, long lo
     return e == hipSuccess ? AFT_OK : hip_fail("channel_sim", e);
 }
 
+// the plan's own checks, shared by the size query and the launch; 0 = fine
+static int check_lmmse(const aft_lmmse *p) {
+    auto within = [](const char *what, int got, int least, int most) {
+        if (got < least || got > most) set_error("lmmse: %s = %d is outside %d..%d", what, got, least, most);
+        return got >= least && got <= most;
+    };
+    if (!within("num_scs", p->num_scs, 1, 1 << 20) || !within("num_symbols", p->num_symbols, 1, 1 << 20) ||
+        !within("pilot_scs", p->pilot_scs, 1, AFT_CHANSIM_MAX_PILOT_SCS) ||
+        !within("pilot_symbols", p->pilot_symbols, 1, AFT_CHANSIM_MAX_PILOT_SYMBOLS) ||
+        !within("n_snr", p->n_snr, 1, AFT_CHANSIM_MAX_VALUES) || !within("n_ds", p->n_ds, 1, AFT_CHANSIM_MAX_VALUES) ||
+        !within("n_dop", p->n_dop, 1, AFT_CHANSIM_MAX_VALUES) || !within("fixed_snr", p->fixed_snr, -1, p->n_snr - 1) ||
+        !within("fixed_ds", p->fixed_ds, -1, p->n_ds - 1) || !within("fixed_dop", p->fixed_dop, -1, p->n_dop - 1))
+        return AFT_ERR_SHAPE;
+    if (p->pilot_scs > p->num_scs || p->pilot_symbols > p->num_symbols) {
+        set_error("lmmse: the pilot grid %d x %d is larger than the ofdm grid %d x %d", p->pilot_scs, p->pilot_symbols, p->num_scs,
+                  p->num_symbols);
+        return AFT_ERR_SHAPE;
+    }
+    return AFT_OK;
+}
+
+size_t aft_lmmse_table_floats(const aft_lmmse *plan) {
+    if (plan == nullptr || check_lmmse(plan) != AFT_OK) return 0;
+    return (size_t)plan->n_ds * lmmse_fblock_floats(*plan) + (size_t)plan->n_dop * lmmse_tblock_floats(*plan);
+}
+
+int aft_lmmse_f32(const aft_lmmse *plan, const float *tables, const float *pilots, const float *snr, const float *ds,
+                  const float *dop, float *est, int batch, void *stream) {
+    AFT_REQUIRE(plan && tables && pilots && est, "lmmse: NULL pointer argument");
+    AFT_REQUIRE((reinterpret_cast<uintptr_t>(tables) | reinterpret_cast<uintptr_t>(pilots) | reinterpret_cast<uintptr_t>(est)) % 8 == 0,
+                "lmmse: tables, pilots and est must be 8-byte aligned");
+    AFT_REQUIRE((reinterpret_cast<uintptr_t>(snr) | reinterpret_cast<uintptr_t>(ds) | reinterpret_cast<uintptr_t>(dop)) % 4 == 0,
+                "lmmse: the condition arrays must be 4-byte aligned");
+    AFT_REQUIRE(batch >= 1, "lmmse: batch must be at least 1 (got %d)", batch);
+    const int rc = check_lmmse(plan);
+    if (rc != AFT_OK) return rc;
+    AFT_REQUIRE((snr || plan->fixed_snr >= 0) && (ds || plan->fixed_ds >= 0) && (dop || plan->fixed_dop >= 0),
+                "lmmse: NULL condition array whose fixed_* index is -1 (snr %p / %d, ds %p / %d, dop %p / %d)", (const void *)snr,
+                plan->fixed_snr, (const void *)ds, plan->fixed_ds, (const void *)dop, plan->fixed_dop);
+    hipError_t e = launch_lmmse(*plan, tables, pilots, snr, ds, dop, est, batch, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? AFT_OK : hip_fail("lmmse", e);
+}
+
 int aft_debug_fill_lds_f32(float value, void *stream) {
     hipError_t e = launch_fill_lds(value, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? AFT_OK : hip_fail("fill_lds", e);

@@ -283,6 +283,13 @@ hipError_t launch_frame_gather(const float *ideal_all, const float *pilots_all, 
 // the channel simulator (k_chansim.hip): `sim` has passed aft_channel_sim_f32's checks
 hipError_t launch_channel_sim(const aft_chansim &sim, unsigned long long seed, long long base, long long start, long long stride,
                               long long modulo, int batch, float *ideal, float *pilots, float *meta, hipStream_t st);
+
+// the LMMSE baseline estimator (k_lmmse.hip): `plan` has passed aft_lmmse_f32's checks; the two sizes are the per-delay-spread and
+// per-Doppler blocks of the table image (include/adafortitran_amd.h)
+size_t lmmse_fblock_floats(const aft_lmmse &plan);
+size_t lmmse_tblock_floats(const aft_lmmse &plan);
+hipError_t launch_lmmse(const aft_lmmse &plan, const float *tables, const float *pilots, const float *snr, const float *ds,
+                        const float *dop, float *est, int batch, hipStream_t st);
 hipError_t launch_mse(const float *est, const float *ref, double *sum_sq, long long n_complex, hipStream_t st);
 hipError_t launch_fill_lds(float value, hipStream_t st);   // test hook: every CU's LDS filled with `value`
 hipError_t launch_peek_lds(float *out, int workgroups, int n, hipStream_t st);   // ... and what a kernel finds in its LDS at start

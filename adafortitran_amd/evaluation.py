@@ -12,16 +12,21 @@ closed early -- because the counts come back asynchronously; the sweep therefore
 without raising, but the exception's traceback points at the loader, not at the forward of the offending batch."""
 from __future__ import annotations
 
+import itertools
 from typing import Dict, Iterable, List, Optional, Tuple
 
 import torch
 
 from .estimators import AdaFortiTranEstimator
+from .lmmse import LmmseEstimator
 from .metrics import MseAccumulator, to_db
 
 
 def forward_pass(model: torch.nn.Module, pilots: torch.Tensor, meta_data: Optional[tuple]) -> torch.Tensor:
-    """The reference's ``_forward_pass`` (trainer.py:267-288): AdaFortiTran needs ``meta_data``."""
+    """The reference's ``_forward_pass`` (trainer.py:267-288): AdaFortiTran needs ``meta_data``; the LMMSE baseline takes it too (its
+    design point per frame), and may do without when every condition is pinned."""
+    if isinstance(model, LmmseEstimator):
+        return model(pilots, meta_data)
     if isinstance(model, AdaFortiTranEstimator):
         if meta_data is None:
             raise ValueError("AdaFortiTranEstimator requires meta_data but it was not provided")
@@ -32,7 +37,7 @@ def forward_pass(model: torch.nn.Module, pilots: torch.Tensor, meta_data: Option
 def evaluate_dataloader(model: torch.nn.Module, dataloader: Iterable, group=None) -> float:
     """Mean |h_est - h|^2 over every complex element of the loader (one host sync at the end)."""
     model.eval()
-    device = next(model.parameters()).device
+    device = next(itertools.chain(model.parameters(), model.buffers())).device      # the LMMSE baseline has buffers only
     acc = MseAccumulator(device)
     with torch.no_grad():
         for pilots, ideal, meta in dataloader:

@@ -415,6 +415,63 @@ class ChannelSimPlan:
         return ideal, pilots, meta
 
 
+class LmmsePlan:
+    """The LMMSE baseline (``lmmse.LmmseTables``) turned into the ``aft_lmmse`` struct and its float32 table image on the device ONCE.
+    ``plan(pilots, snr, ds, dop)`` -> ``est complex64 [batch,S,T]`` on the plan's device: one ``torch.empty``, one ``ctypes`` call, one
+    launch (``aft_lmmse_f32``) on the current stream of that device, no synchronisation.  ``pilots`` complex64 ``[batch,Ps,Pt]`` and the
+    three float32 conditions (``batch`` values each, any shape) live on the plan's device or in pinned host memory, which the kernel
+    reads in place; a condition that ``assume`` pins may be None.  ``image``: the table image when the caller already holds it on
+    the device (``lmmse.LmmseEstimator``'s buffer).  The plan trusts its caller in one thing only: its device is the current one."""
+
+    def __init__(self, cfg, device: torch.device, assume=None, image: Optional[torch.Tensor] = None) -> None:
+        from .lmmse import LmmseTables
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError(f"LmmsePlan runs on a HIP device (got {device}); lmmse.lmmse_estimate_host is the CPU path")
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device.index is None else device
+        self.tables = cfg if isinstance(cfg, LmmseTables) else LmmseTables(cfg)
+        self.plan = self.tables.to_struct(assume)
+        self.fixed = (self.plan.fixed_snr, self.plan.fixed_ds, self.plan.fixed_dop)
+        self.grid, self.pilot = tuple(self.tables.cfg.ofdm), tuple(self.tables.cfg.pilot)
+        if image is None:
+            image = torch.from_numpy(self.tables.image()).to(self.device)
+        floats = _lib.load().aft_lmmse_table_floats(C.byref(self.plan))
+        if image.dtype != torch.float32 or image.device != self.device or not image.is_contiguous() or image.numel() != floats:
+            raise ValueError(f"the table image must be {floats} contiguous float32 values on {self.device} (got {image.numel()} "
+                             f"{image.dtype} on {image.device})")
+        self.image = image
+
+    def _readable(self, name: str, t: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+        if t.dtype != dtype:
+            raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
+        if not (t.device == self.device or (t.device.type == "cpu" and t.is_pinned())):
+            # a pageable host pointer would be a GPU page fault that aborts the process
+            raise ValueError(f"{name} must live on {self.device} or in pinned host memory (it is on {t.device}, not pinned)")
+        return t.contiguous()
+
+    def __call__(self, pilots: torch.Tensor, snr=None, ds=None, dop=None, lib=None) -> torch.Tensor:
+        lib = lib or _lib.load()
+        if pilots.dim() != 3 or tuple(pilots.shape[1:]) != self.pilot or pilots.shape[0] < 1:
+            raise ValueError(f"Expected pilot shape (B >= 1, {self.pilot[0]}, {self.pilot[1]}), got {tuple(pilots.shape)}")
+        batch = pilots.shape[0]
+        pil = self._readable("pilots", pilots, torch.complex64)
+        conds = []
+        for name, c, fixed in zip(("snr", "ds", "dop"), (snr, ds, dop), self.fixed):
+            if c is None:
+                if fixed < 0:
+                    raise ValueError(f"{name} is required: assume does not pin it")
+                conds.append(None)
+                continue
+            c = self._readable(name, c.reshape(-1), torch.float32)
+            if c.numel() != batch:
+                raise ValueError(f"{name} must hold one value per frame ({batch}), got {c.numel()}")
+            conds.append(c)
+        est = torch.empty((batch, *self.grid), dtype=torch.complex64, device=self.device)   # the kernel writes every element
+        _lib.check(lib.aft_lmmse_f32(C.byref(self.plan), self.image.data_ptr(), pil.data_ptr(), *(_ptr(c) for c in conds),
+                                     est.data_ptr(), batch, _lib.current_stream_ptr(self.device)), lib)
+        return est
+
+
 def ls_mse_db(ls: torch.Tensor, ideal: torch.Tensor) -> torch.Tensor:
     """Per-frame LS-baseline MSE in dB, float32 [B] (reference utils.py:248-261 per file)."""
     lib = _lib.load()

@@ -292,6 +292,50 @@ typedef struct aft_chansim {
 int aft_channel_sim_f32(const aft_chansim *sim, unsigned long long seed, long long base, long long start, long long stride,
                         long long modulo, int batch, float *ideal, float *pilots, float *meta, void *stream);
 
+/* ---- the LMMSE (Wiener) baseline estimator (adafortitran_amd/lmmse.py holds the definition) ----
+ *
+ * The best linear estimator of the simulator's channel from its pilots, for the second-order statistics the simulator is defined
+ * with: E|H|^2 = 1, frequency correlation r_f(d) = sum_p pw_p exp(-j 2 pi d df d_p DS), time correlation r_t(k) = J0(2 pi f_D k T_sym).
+ * The pilot covariance is a Kronecker product, R_pp = R_f (x) R_t, so the estimator runs in its eigenbasis and no inverse is formed:
+ *   R_f = U_f diag(lf) U_f^H  (per delay spread, Ps x Ps Hermitian),   F' = r_f(s - sc_i) U_f   [S, Ps]
+ *   R_t = U_t diag(lt) U_t^T  (per Doppler, Pt x Pt real symmetric),   T' = r_t(t - sym_j) U_t  [T, Pt]
+ *   est = F' [ D o (U_f^H P U_t) ] T'^T,    D[k][l] = 1 / (lf[k] lt[l] + noise_var),    P the frame's [Ps, Pt] pilots.
+ * The caller computes the tables (pow, J0 and the eigen-decompositions are the host's, in double) and passes ONE float32 image:
+ *   per delay spread i (n_ds blocks of fblock = 2 Ps Ps + 2 Ps S + Ps + (Ps & 1) floats, block i at i fblock):
+ *     U_f^H  complex [Ps(k)][Ps(i)]   (re, im pairs; entry (k, i) = conj(U_f[i][k]))
+ *     F'     complex [Ps(k)][S]       (k-major: consecutive subcarriers of one eigen-direction are adjacent)
+ *     lf     real    [Ps]             (eigenvalues, clamped at 0 from below; one float of padding when Ps is odd)
+ *   then per Doppler i (n_dop blocks of tblock = Pt Pt + Pt T + Pt floats, block i at n_ds fblock + i tblock):
+ *     U_t    real    [Pt(j)][Pt(l)]
+ *     T'     real    [Pt(l)][T]       (l-major)
+ *     lt     real    [Pt]
+ * aft_lmmse_table_floats gives the image's length.  Which block a frame uses: per condition, the index of the table value nearest to
+ * the frame's (|v - value[i]| in double, ties to the lower index, a NaN to index 0) -- a total function; fixed_* >= 0 pins a condition
+ * to that index for every frame (the mismatched receiver) and its per-frame array is then not read. */
+typedef struct aft_lmmse {
+    int32_t num_scs, num_symbols;              /* OFDM grid S x T, any size (est is [batch, S, T])           */
+    int32_t pilot_scs, pilot_symbols;          /* pilot grid Ps x Pt, at most 64 x 16 (the simulator's)      */
+    int32_t n_snr, n_ds, n_dop;                /* values per condition, 1..16 each                           */
+    int32_t fixed_snr, fixed_ds, fixed_dop;    /* an index below n_*, or -1: chosen per frame                */
+    float snr_db[AFT_CHANSIM_MAX_VALUES], delay_spread_ns[AFT_CHANSIM_MAX_VALUES], doppler_hz[AFT_CHANSIM_MAX_VALUES];
+    float noise_var[AFT_CHANSIM_MAX_VALUES];   /* 10^(-snr_db[i] / 10)                                       */
+} aft_lmmse;
+
+/* Floats in the table image of `plan` (0 on a plan aft_lmmse_f32 would refuse with AFT_ERR_SHAPE). */
+size_t aft_lmmse_table_floats(const aft_lmmse *plan);
+
+/* One launch, one workgroup per frame: est complex64 [batch, S, T] (device memory) from pilots complex64 [batch, Ps, Pt] and the
+ * float32 [batch] conditions snr / ds / dop.  pilots and the three condition arrays may be any device-addressable memory, pinned host
+ * memory included (as for aft_forward_f32); a condition pointer may be NULL only when its fixed_* is set.  `tables` is the image above
+ * in device memory; `plan` is read during the call only and travels to the kernel by value.  Every output element is written (no
+ * initialisation needed); no atomics; nothing is synchronised; a frame's bits do not depend on batch or on its position in it.
+ * 16-byte stores when T is even and est is 16-byte aligned, 8-byte stores otherwise.
+ * Nothing is launched on AFT_ERR_ARG (a NULL plan / tables / pilots / est, or a NULL condition whose fixed_* is -1; tables, pilots or
+ * est not 8-byte or a condition array not 4-byte aligned; batch < 1) and AFT_ERR_SHAPE (a dimension below 1 or beyond its bound, a
+ * pilot grid larger than the OFDM grid, a fixed_* outside -1 .. n_* - 1). */
+int aft_lmmse_f32(const aft_lmmse *plan, const float *tables, const float *pilots, const float *snr, const float *ds,
+                  const float *dop, float *est, int batch, void *stream);
+
 /* ---- training path of the encoder ---- */
 
 /* Gradients of one nn.TransformerEncoderLayer: same fields and shapes as aft_layer_weights,

@@ -11,8 +11,9 @@ Sections, each run as a child process of its own under a time limit (the parent 
       that existed before the simulator), in alternating rounds in one process: median and spread of both; the verdict holds the
       difference of the medians against the ResidentLoader-fed step's own max - min in this run, no threshold fixed in advance;
   t   a short training at a fixed seed fed by SynthLoader: the loss per window of steps next to the LS baseline (the pilots' linear
-      interpolation, chansim.ls_interpolate's weights applied on the device) of the SAME frames, both as the trainer's MSELoss over
-      the real view.  Reported, not asserted."""
+      interpolation, chansim.ls_interpolate's weights applied on the device) and the LMMSE baseline (lmmse.LmmseEstimator, matched to
+      each frame's condition: the best linear estimator) of the SAME frames, all three as the trainer's MSELoss over the real view.
+      Reported, not asserted."""
 import argparse
 import itertools
 import json
@@ -142,8 +143,10 @@ def section_t(a):
     import torch
     import train_bench
     from adafortitran_amd import chansim
+    from adafortitran_amd.lmmse import LmmseEstimator
     from adafortitran_amd.optim import ShardedFlatAdam
     cfg = chansim.ChannelSimConfig()
+    wiener = LmmseEstimator(cfg).to("cuda")
     torch.manual_seed(0)
     model = train_bench.build("adafortitran", 0.0).train()
     opt = ShardedFlatAdam(model.parameters(), lr=a.lr)
@@ -151,7 +154,7 @@ def section_t(a):
     # the LS baseline's interpolation weights, from ls_interpolate applied to unit pilots
     eye = np.eye(cfg.pilot[0] * cfg.pilot[1]).reshape(-1, *cfg.pilot)
     w = torch.from_numpy(chansim.ls_interpolate(cfg, eye).reshape(len(eye), -1)).cuda()          # [Ps*Pt, S*T]
-    losses, ls = [], []
+    losses, ls, lm = [], [], []
     for pilots, ideal, meta in loader:
         opt.zero_grad()
         loss = torch.nn.functional.mse_loss(torch.view_as_real(model(pilots, meta)), torch.view_as_real(ideal))
@@ -160,13 +163,17 @@ def section_t(a):
         losses.append(loss.detach())
         base = (pilots.reshape(len(pilots), -1) @ w).reshape(ideal.shape)
         ls.append(torch.nn.functional.mse_loss(torch.view_as_real(base), torch.view_as_real(ideal)))
-    losses, ls = torch.stack(losses).cpu().numpy(), torch.stack(ls).cpu().numpy()
+        with torch.no_grad():
+            lm.append(torch.nn.functional.mse_loss(torch.view_as_real(wiener(pilots, meta)), torch.view_as_real(ideal)))
+    losses, ls, lm = (torch.stack(v).cpu().numpy() for v in (losses, ls, lm))
     win = max(1, a.train_steps // 12)
     curve = [{"steps": [lo, min(lo + win, len(losses))], "loss": round(float(losses[lo:lo + win].mean()), 6),
-              "ls_baseline": round(float(ls[lo:lo + win].mean()), 6)} for lo in range(0, len(losses), win)]
+              "ls_baseline": round(float(ls[lo:lo + win].mean()), 6), "lmmse_baseline": round(float(lm[lo:lo + win].mean()), 6)}
+             for lo in range(0, len(losses), win)]
     return {"seed": 7, "batch": 128, "steps": int(len(losses)), "lr": a.lr, "dropout": 0.0, "finite": bool(np.isfinite(losses).all()),
             "curve": curve, "final_loss": curve[-1]["loss"], "final_ls_baseline": curve[-1]["ls_baseline"],
-            "beats_ls": bool(curve[-1]["loss"] < curve[-1]["ls_baseline"])}
+            "final_lmmse_baseline": curve[-1]["lmmse_baseline"], "beats_ls": bool(curve[-1]["loss"] < curve[-1]["ls_baseline"]),
+            "beats_lmmse": bool(curve[-1]["loss"] < curve[-1]["lmmse_baseline"])}
 
 
 SECTIONS = {"k": section_k, "p": section_p, "h": section_h, "d": section_d, "t": section_t}
