@@ -33,18 +33,16 @@ class AftConfig(C.Structure):
         return (self.num_scs // self.patch_scs) * (self.num_symbols // self.patch_symbols)
 
 
-class AftLayerWeights(C.Structure):
-    _fields_ = [(n, _fp) for n in (
-        "in_proj_w", "in_proj_b", "out_proj_w", "out_proj_b", "lin1_w", "lin1_b",
-        "lin2_w", "lin2_b", "norm1_w", "norm1_b", "norm2_w", "norm2_b")]
-
-
 LAYER_FIELDS = ("in_proj_w", "in_proj_b", "out_proj_w", "out_proj_b", "lin1_w", "lin1_b",
                 "lin2_w", "lin2_b", "norm1_w", "norm1_b", "norm2_w", "norm2_b")
 #: nn.TransformerEncoderLayer parameter names in LAYER_FIELDS order
 LAYER_PARAM_NAMES = ("self_attn.in_proj_weight", "self_attn.in_proj_bias", "self_attn.out_proj.weight",
                      "self_attn.out_proj.bias", "linear1.weight", "linear1.bias", "linear2.weight", "linear2.bias",
                      "norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias")
+
+
+class AftLayerWeights(C.Structure):
+    _fields_ = [(n, _fp) for n in LAYER_FIELDS]
 
 
 class AftLayerGrads(C.Structure):
@@ -168,26 +166,78 @@ def pos_key_of(state: Dict[str, object]) -> str:
     return k if k in state else f"{_TE}.positional_encoding.pe"
 
 
+# ---- the entry points: name -> (restype, argtypes), one line each, in the header's order.  _lib.load_path types the library from this
+# table and tests/test_abi.py checks every line of it against the header's prototype (count, kind and order of the arguments, the
+# return type, the struct a pointer names).  A new entry point: the header first, then ONE line here; the test says where they disagree.
+vp = C.c_void_p
+cfgp, wp, lwp, lgp = C.POINTER(AftConfig), C.POINTER(AftWeights), C.POINTER(AftLayerWeights), C.POINTER(AftLayerGrads)
+p3, p4, p9, i3 = C.POINTER(vp * 3), C.POINTER(vp * 4), C.POINTER(vp * 9), C.POINTER(C.c_int32 * 3)
+i6 = [C.c_int] * 6   # planes, num_scs, num_symbols, patch_scs, patch_symbols, model_dim
+SIGNATURES = {
+    "aft_version": (C.c_int, []),
+    "aft_last_error": (C.c_char_p, []),
+    "aft_check_config": (C.c_int, [cfgp]),
+    "aft_engine_of": (C.c_int, [cfgp]),
+    "aft_set_switch": (C.c_int, [C.c_char_p, C.c_char_p]),
+    "aft_get_switch": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t]),
+    "aft_max_batch": (C.c_int, [cfgp]),
+    "aft_workspace_bytes": (C.c_size_t, [cfgp, C.c_int]),
+    "aft_workspace_lanes": (C.c_int, [cfgp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
+    "aft_workspace_region": (C.c_int, [cfgp, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "aft_forward_f32": (C.c_int, [cfgp, wp, vp, vp, vp, vp, vp, vp, C.c_size_t, C.c_int, vp]),
+    "aft_packed_weights_bytes": (C.c_size_t, [cfgp]),
+    "aft_pack_weights_f32": (C.c_int, [cfgp, wp, vp, C.c_size_t, vp]),
+    "aft_forward_prepacked_f32": (C.c_int, [cfgp, wp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, C.c_int, vp]),
+    "aft_linear_forward_f32": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+    "aft_mse_partial_f32": (C.c_int, [vp, vp, vp, C.c_longlong, vp]),
+    # the data formats either side of the path, the channel simulator, the LMMSE baseline
+    "aft_pilot_gather_f32": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+    "aft_ls_mse_db_f32": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
+    "aft_frame_gather_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_longlong, C.c_int, C.c_int, vp]),
+    "aft_channel_sim_f32": (C.c_int, [C.POINTER(AftChanSim), C.c_ulonglong] + [C.c_longlong] * 4 + [C.c_int, vp, vp, vp, vp]),
+    "aft_lmmse_table_floats": (C.c_size_t, [C.POINTER(AftLmmse)]),
+    "aft_lmmse_f32": (C.c_int, [C.POINTER(AftLmmse), vp, vp, vp, vp, vp, vp, C.c_int, vp]),
+    # training path
+    "aft_encoder_tape_bytes": (C.c_size_t, [cfgp, C.c_int]),
+    "aft_encoder_train_scratch_bytes": (C.c_size_t, [cfgp, C.c_int]),
+    "aft_encoder_layer_fwd_train_f32": (C.c_int, [cfgp, lwp, vp, vp, vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_float, C.c_uint64, vp]),
+    "aft_encoder_layer_fwd_train_chained_f32": (C.c_int, [cfgp, lwp, vp, vp, vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_float, C.c_uint64,
+                                                          C.c_int, lwp, vp, C.c_size_t, C.POINTER(C.c_int), vp]),
+    "aft_encoder_layer_bwd_f32": (C.c_int, [cfgp, lwp, vp, vp, C.c_size_t, vp, vp, lgp, C.c_int, vp, C.c_size_t, C.c_int, C.c_float,
+                                            C.c_uint64, vp]),
+    "aft_dense_fwd_f32": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+    "aft_dense_bwd_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "aft_dense_bwd_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, vp]),
+    "aft_conv_enhancer_fwd_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "aft_conv_enhancer_fwd_train_f32": (C.c_int, [p4, p4, vp, vp, vp, vp, vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, vp]),
+    "aft_conv_enhancer_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "aft_conv_enhancer_bwd_f32": (C.c_int, [p4, vp, vp, vp, vp, vp, vp, p4, p4, C.c_int, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, vp]),
+    "aft_adapter_fwd_train_f32": (C.c_int, [p3, p9, p9, i3, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "aft_adapter_bwd_f32": (C.c_int, [p3, p9, p9, i3, C.c_int, C.c_int, vp, vp, vp, vp, vp, p9, p9, C.c_int, vp]),
+    "aft_embed_bwd_scratch_bytes": (C.c_size_t, i6 + [C.c_int]),
+    "aft_embed_fwd_train_f32": (C.c_int, [vp] * 6 + i6 + [vp]),
+    "aft_embed_bwd_f32": (C.c_int, [vp] * 9 + [C.c_int, vp, C.c_size_t] + i6 + [vp]),
+    "aft_tail_bwd_scratch_bytes": (C.c_size_t, i6),
+    "aft_tail_fwd_train_f32": (C.c_int, [vp] * 5 + i6 + [vp]),
+    "aft_tail_bwd_f32": (C.c_int, [vp] * 6 + [C.c_int, vp, C.c_size_t] + i6 + [vp]),
+    # the optimizer step; aft_step_control * stays untyped: optim.py passes the address of a tensor
+    "aft_adam_step_f32": (C.c_int, [vp, vp, vp, vp, C.c_size_t] + [C.c_float] * 6 + [C.c_int, vp]),
+    "aft_grad_sumsq_scratch_bytes": (C.c_size_t, [C.c_size_t]),
+    "aft_grad_sumsq_f32": (C.c_int, [vp, C.c_size_t, vp, C.c_size_t, vp, vp, vp]),
+    "aft_adam_prepare_f32": (C.c_int, [vp, vp, vp, vp, C.c_double, C.c_double, C.c_float, C.c_float, vp]),
+    "aft_adam_step_ctrl_f32": (C.c_int, [vp, vp, vp, vp, C.c_size_t] + [C.c_float] * 5 + [vp, vp]),
+    "aft_grad_clip_f32": (C.c_int, [vp, C.c_size_t, vp, C.c_double, C.c_double, vp, vp]),
+    # per-stage entry points, measurement and test hooks
+    "aft_stage_upsample_f32": (C.c_int, [cfgp, wp, vp, vp, C.c_int, vp]),
+    "aft_stage_adapter_f32": (C.c_int, [cfgp, wp, vp, vp, vp, vp, C.c_int, vp]),
+    "aft_stage_embed_f32": (C.c_int, [cfgp, wp, vp, vp, vp, C.c_int, vp]),
+    "aft_stage_encoder_layer_f32": (C.c_int, [cfgp, wp, C.c_int, vp, vp, C.c_size_t, C.c_int, vp]),
+    "aft_stage_tail_f32": (C.c_int, [cfgp, wp, vp, vp, vp, C.c_int, vp]),
+    "aft_profile_kernel_f32": (C.c_int, [cfgp, wp, C.c_int, vp, vp, C.c_size_t, C.c_int, C.c_int, vp]),
+    "aft_debug_fill_lds_f32": (C.c_int, [C.c_float, vp]),
+    "aft_debug_peek_lds_f32": (C.c_int, [vp, C.c_int, C.c_int, vp]),
+}
 #: every symbol include/adafortitran_amd.h declares (tests check the .so exports them all)
-EXPORTED_SYMBOLS = (
-    "aft_version", "aft_last_error", "aft_check_config", "aft_engine_of", "aft_set_switch", "aft_get_switch", "aft_max_batch", "aft_workspace_bytes", "aft_workspace_region", "aft_workspace_lanes", "aft_forward_f32",
-    "aft_packed_weights_bytes", "aft_pack_weights_f32", "aft_forward_prepacked_f32",
-    "aft_linear_forward_f32", "aft_mse_partial_f32", "aft_stage_upsample_f32",
-    "aft_stage_adapter_f32", "aft_stage_embed_f32", "aft_stage_encoder_layer_f32",
-    "aft_stage_tail_f32", "aft_profile_kernel_f32", "aft_debug_fill_lds_f32", "aft_debug_peek_lds_f32", "aft_pilot_gather_f32", "aft_ls_mse_db_f32", "aft_frame_gather_f32", "aft_channel_sim_f32",
-    "aft_lmmse_table_floats", "aft_lmmse_f32",
-    "aft_encoder_tape_bytes", "aft_encoder_train_scratch_bytes",
-    "aft_encoder_layer_fwd_train_f32", "aft_encoder_layer_fwd_train_chained_f32", "aft_encoder_layer_bwd_f32", "aft_adam_step_f32",
-    "aft_grad_sumsq_scratch_bytes", "aft_grad_sumsq_f32", "aft_adam_prepare_f32", "aft_adam_step_ctrl_f32", "aft_grad_clip_f32",
-    "aft_conv_enhancer_fwd_train_f32", "aft_conv_enhancer_scratch_bytes", "aft_conv_enhancer_fwd_scratch_bytes", "aft_conv_enhancer_bwd_f32",
-    "aft_dense_fwd_f32", "aft_dense_bwd_scratch_bytes", "aft_dense_bwd_f32",
-    "aft_adapter_fwd_train_f32", "aft_adapter_bwd_f32",
-    "aft_embed_bwd_scratch_bytes", "aft_embed_fwd_train_f32", "aft_embed_bwd_f32",
-    "aft_tail_bwd_scratch_bytes", "aft_tail_fwd_train_f32", "aft_tail_bwd_f32",
-)
-#: size queries (return size_t, not a status code)
-SIZE_SYMBOLS = ("aft_workspace_bytes", "aft_packed_weights_bytes", "aft_encoder_tape_bytes", "aft_encoder_train_scratch_bytes",
-                "aft_conv_enhancer_scratch_bytes", "aft_conv_enhancer_fwd_scratch_bytes", "aft_dense_bwd_scratch_bytes",
-                "aft_embed_bwd_scratch_bytes", "aft_tail_bwd_scratch_bytes", "aft_grad_sumsq_scratch_bytes", "aft_lmmse_table_floats")
+EXPORTED_SYMBOLS = tuple(SIGNATURES)
 REGION_IDS = {"conv_enhanced": 0, "tokens6": 1, "enc_out": 2}   # aft_workspace_region
 KERNEL_IDS = {"upsample": 0, "embed": 1, "qkv": 2, "attention": 3, "chain": 4, "tail": 5, "chain_last": 6, "encoder_plane": 7, "prologue": 8}

@@ -21,6 +21,17 @@ def _dev_f32(t: torch.Tensor, device) -> torch.Tensor:
     return t.to(device=device, dtype=torch.float32).contiguous()
 
 
+def resolve_device(device: torch.device) -> torch.device:
+    """``cuda`` without an index means the device that is current now, for good."""
+    return torch.device("cuda", torch.cuda.current_device()) if device.index is None else device
+
+
+def _readable_in_place(t: torch.Tensor, device: torch.device) -> bool:
+    """True when a kernel on ``device`` can read ``t`` where it is: it lives there or in pinned host memory (a pageable host pointer
+    would be a GPU page fault that aborts the process)."""
+    return t.device == device or (t.device.type == "cpu" and t.is_pinned())
+
+
 def config_coverage(cfg: _abi.AftConfig) -> Optional[str]:
     """None when the gfx950 kernels cover ``cfg``, else the library's reason (``aft_check_config``)."""
     lib = _lib.load()
@@ -148,7 +159,7 @@ class HipEngine:
         B = pilots.shape[0]
         if pilots.device.type == "cpu" and not pinned_inputs:
             raise ValueError("pilot_symbols must be on the engine's device (or pinned, with pinned_inputs=True)")
-        if pilots.device.type == "cpu" and not (pilots.is_pinned() and pilots.is_contiguous()):
+        if pilots.device.type == "cpu" and not (_readable_in_place(pilots, self.device) and pilots.is_contiguous()):
             # a pageable (or silently re-copied non-contiguous) host pointer would be a GPU page fault that aborts the process
             raise ValueError("pinned_inputs=True needs contiguous pinned host tensors (pilot_symbols is not)")
         pil = torch.view_as_real(pilots.contiguous())
@@ -158,7 +169,7 @@ class HipEngine:
                 raise ValueError("meta_data is required when channel adaptation is enabled")
             # host conditions are read in place only when they are pinned, contiguous float32; anything else is copied to the device
             metas = [m.reshape(-1) if (pinned_inputs and m.device.type == "cpu" and m.dtype == torch.float32 and m.is_contiguous()
-                                       and m.is_pinned())
+                                       and _readable_in_place(m, self.device))
                      else _dev_f32(m.reshape(-1), self.device) for m in (snr, ds, dop)]
             if any(m.numel() != B for m in metas):
                 raise ValueError("meta_data tensors must have one value per frame")
@@ -354,7 +365,7 @@ def frame_gather(ideal_all: torch.Tensor, pilots_all: torch.Tensor, index: torch
     for name, t in (("ideal_all", ideal_all), ("pilots_all", pilots_all)):
         if t.dtype != torch.complex64 or t.dim() < 2 or not t.is_contiguous() or t.shape[0] < 1 or t[0].numel() < 1:
             raise ValueError(f"{name} must be a contiguous complex64 array [n, ...] with n >= 1")
-        if not (t.device == dev or (t.device.type == "cpu" and t.is_pinned())):
+        if not _readable_in_place(t, dev):
             raise ValueError(f"{name} must live on {dev} or in pinned host memory (it is on {t.device}, not pinned)")
     if ideal_all.shape[0] != pilots_all.shape[0]:
         raise ValueError(f"ideal_all holds {ideal_all.shape[0]} frames, pilots_all {pilots_all.shape[0]}")
@@ -399,7 +410,7 @@ class ChannelSimPlan:
         device = torch.device(device)
         if device.type != "cuda":
             raise ValueError(f"ChannelSimPlan runs on a HIP device (got {device}); chansim.simulate_frames_host is the CPU path")
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device.index is None else device
+        self.device = resolve_device(device)
         self.cfg = cfg
         self.sim = cfg.to_struct()                              # validated by the config itself; the entry point checks again
         self.grid, self.pilot = tuple(cfg.ofdm), tuple(cfg.pilot)
@@ -428,7 +439,7 @@ class LmmsePlan:
         device = torch.device(device)
         if device.type != "cuda":
             raise ValueError(f"LmmsePlan runs on a HIP device (got {device}); lmmse.lmmse_estimate_host is the CPU path")
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device.index is None else device
+        self.device = resolve_device(device)
         self.tables = cfg if isinstance(cfg, LmmseTables) else LmmseTables(cfg)
         self.plan = self.tables.to_struct(assume)
         self.fixed = (self.plan.fixed_snr, self.plan.fixed_ds, self.plan.fixed_dop)
@@ -444,8 +455,7 @@ class LmmsePlan:
     def _readable(self, name: str, t: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
         if t.dtype != dtype:
             raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
-        if not (t.device == self.device or (t.device.type == "cpu" and t.is_pinned())):
-            # a pageable host pointer would be a GPU page fault that aborts the process
+        if not _readable_in_place(t, self.device):
             raise ValueError(f"{name} must live on {self.device} or in pinned host memory (it is on {t.device}, not pinned)")
         return t.contiguous()
 

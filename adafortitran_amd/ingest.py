@@ -359,9 +359,8 @@ class ResidentLoader:
             self.pilots = torch.from_numpy(extract_pilots_host(sparse, self.pilot_size))
             self.h_ideal = torch.from_numpy(np.ascontiguousarray(ideal, dtype=np.complex64))
             return
-        from .hip_ops import check_pilot_counts, pilot_gather
-        if self.device.index is None:                              # "cuda": the device that is current now, for good
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        from .hip_ops import check_pilot_counts, pilot_gather, resolve_device
+        self.device = resolve_device(self.device)
         expected = self.pilot_size[0] * self.pilot_size[1]
         if self.residency == "device":
             self.pilots = torch.empty((n, *self.pilot_size), dtype=torch.complex64, device=self.device)

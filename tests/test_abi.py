@@ -12,14 +12,140 @@ from helpers import DEFAULT_SPEC
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _header_symbols():
+def _header_text():
+    """The header without comments."""
     text = open(os.path.join(ROOT, "include", "adafortitran_amd.h")).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(aft_[a-z0-9_]+)\s*\(", text)))
+    return re.sub(r"//[^\n]*", "", text)
+
+
+def _header_symbols():
+    return sorted(set(re.findall(r"\b(aft_[a-z0-9_]+)\s*\(", _header_text())))
 
 
 def test_binding_lists_every_header_symbol():
     assert _header_symbols() == sorted(_abi.EXPORTED_SYMBOLS)
+
+
+# ---- the binding against the header, declaration by declaration (no library, no GPU) ----
+# What ctypes can get wrong without raising is the KIND of a value: its width, integer or floating point, by value or by address.
+_C_KINDS = {"int": "i32", "int32_t": "i32", "size_t": "u64", "uint64_t": "u64", "unsigned long long": "u64", "long long": "i64",
+            "float": "f32", "double": "f64"}
+_CTYPES_KINDS = {ctypes.c_int: "i32", ctypes.c_size_t: "u64", ctypes.c_uint64: "u64", ctypes.c_ulonglong: "u64",
+                 ctypes.c_longlong: "i64", ctypes.c_float: "f32", ctypes.c_double: "f64"}
+_C_RETURNS = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "const char *": ctypes.c_char_p}
+_MIRRORS = {"aft_config": _abi.AftConfig, "aft_layer_weights": _abi.AftLayerWeights, "aft_weights": _abi.AftWeights,
+            "aft_chansim": _abi.AftChanSim, "aft_lmmse": _abi.AftLmmse, "aft_layer_grads": _abi.AftLayerGrads,
+            "aft_step_control": _abi.AftStepControl}
+_STRUCTS_PASSED_AS_VOID_P = {"aft_step_control"}        # optim.py keeps the control block in a tensor and passes its address
+
+
+def _header_constants():
+    """{name: value} of every ``#define AFT_NAME <integer>`` and every enumerator."""
+    text = _header_text()
+    define = r"^[ \t]*#[ \t]*define[ \t]+(AFT_\w+)[ \t]+(-?(?:0[xX][0-9a-fA-F]+|\d+))[ \t]*$"
+    found = {n: int(v, 0) for n, v in re.findall(define, text, flags=re.M)}
+    for body in re.findall(r"\benum\b[^{;]*\{(.*?)\}", text, flags=re.S):
+        value = -1
+        for item in filter(None, (i.strip() for i in body.split(","))):
+            name, _, given = (part.strip() for part in item.partition("="))
+            value = int(given, 0) if given else value + 1
+            found[name] = value
+    return found
+
+
+def _c_declarations(statement, what):
+    """'const float *enh_w[4], *enh_b[4]' -> [(name, kind, array extents, struct named or None), ...] for one C declaration
+    (a struct's field list or one parameter).  A pointer's extents are those of the array OF pointers; a type passed by value that
+    this test does not know fails it."""
+    defines = _header_constants()
+    first, *more = (d.strip() for d in statement.split(","))
+    m = re.fullmatch(r"(?P<base>[\w ]+?)\s*(?P<decl>(?:\*\s*(?:const\s+)?)?\w+\s*(?:\[\w*\]\s*)*)", first)
+    assert m, f"{what}: cannot read {statement!r}"
+    base = " ".join(w for w in m["base"].split() if w != "const")
+    out = []
+    for decl in (m["decl"], *more):
+        d = re.fullmatch(r"(?P<star>\*?)\s*(?:const\s+)?(?P<name>\w+)\s*(?P<dims>(?:\[\w*\]\s*)*)", decl)
+        assert d, f"{what}: cannot read {decl!r} in {statement!r}"
+        dims = re.findall(r"\[(\w*)\]", d["dims"])
+        struct = base if base in _MIRRORS else None
+        assert d["star"] or struct or base in _C_KINDS, f"{what}: unknown C type {base!r} in {statement!r}"
+        kind = "pointer" if d["star"] else "struct" if struct else _C_KINDS[base]
+        out.append((d["name"], kind, [int(x) if x.isdigit() else defines[x] for x in dims], struct))
+    return out
+
+
+def _ctypes_declaration(t):
+    """(kind, array extents outermost first, struct class a POINTER names or None) of one ctypes type."""
+    extents = []
+    while issubclass(t, ctypes.Array):
+        extents.append(t._length_)
+        t = t._type_
+    if issubclass(t, ctypes._Pointer):
+        return "pointer", extents, t._type_ if issubclass(t._type_, ctypes.Structure) else None
+    if t in (ctypes.c_void_p, ctypes.c_char_p):
+        return "pointer", extents, None
+    assert t in _CTYPES_KINDS, f"{t} is not a type this test knows"
+    return _CTYPES_KINDS[t], extents, None
+
+
+def _header_prototypes():
+    """[(name, return type, [parameter text, ...]), ...] in the header's order."""
+    text = re.sub(r"^[ \t]*#.*$", "", _header_text(), flags=re.M)
+    protos = []
+    for ret, name, params in re.findall(r"([\w\s\*]+?)\b(aft_\w+)\s*\(([^()]*)\)\s*;", text):
+        params = [" ".join(p.split()) for p in params.split(",")]
+        protos.append((name, " ".join(ret.split()), [] if params == ["void"] else params))
+    return protos
+
+
+def test_signatures_match_the_header_prototypes():
+    """Every line of _abi.SIGNATURES against its prototype: the number of arguments, the kind of each (pointer / i32 / u64 / i64 / f32
+    / f64 -- two arguments of one width but different kinds swapped pass ctypes and hand a kernel a wild address), the return type
+    (a size_t query typed c_int is cut to 32 bits), and the mirror class behind every pointer to one of the ABI's structs."""
+    protos = _header_prototypes()
+    assert len(protos) == len(_abi.SIGNATURES) and len(protos) >= 56       # a pattern that stopped matching cannot pass
+    assert [name for name, _, _ in protos] == list(_abi.SIGNATURES)         # exactly once each, in the header's order
+    for name, ret, params in protos:
+        restype, argtypes = _abi.SIGNATURES[name]
+        assert ret in _C_RETURNS, f"{name}: unknown return type {ret!r}"
+        assert restype is _C_RETURNS[ret], f"{name}: returns {ret}, bound as {restype}"
+        assert len(params) == len(argtypes), f"{name}: {len(params)} parameters, {len(argtypes)} argtypes"
+        for i, (param, argtype) in enumerate(zip(params, argtypes)):
+            (_, kind, dims, struct), = _c_declarations(param, name)
+            kind = "pointer" if dims else kind                              # an array parameter is a pointer
+            assert kind != "struct", f"{name}: {param!r} passes a struct by value"
+            bound, extents, target = _ctypes_declaration(argtype)
+            assert not extents and bound == kind, f"{name} argument {i} ({param!r}): {kind} in the header, {argtype} in the binding"
+            want = None if struct in _STRUCTS_PASSED_AS_VOID_P else _MIRRORS.get(struct)
+            assert target is want, f"{name} argument {i} ({param!r}): bound as a pointer to {target}, not {want}"
+
+
+def test_struct_mirrors_match_the_header_field_by_field():
+    """Every typedef'd struct of the header against its ctypes mirror: the same field names in the same order, each of the same kind
+    and array extent (resolved through the header's own #defines), a pointer to another struct typed as that struct's mirror."""
+    structs = re.findall(r"typedef\s+struct\s*\w*\s*\{(.*?)\}\s*(\w+)\s*;", _header_text(), flags=re.S)
+    assert sorted(name for _, name in structs) == sorted(_MIRRORS) and len(structs) == 7
+    for body, name in structs:
+        fields = [f for stmt in body.split(";") if stmt.strip() for f in _c_declarations(" ".join(stmt.split()), name)]
+        mirror = _MIRRORS[name]._fields_
+        assert [f[0] for f in fields] == [m[0] for m in mirror], name
+        for (fname, kind, dims, struct), (_, ctype) in zip(fields, mirror):
+            assert kind != "struct", f"{name}.{fname}: a struct by value"
+            bound, extents, target = _ctypes_declaration(ctype)
+            assert (bound, extents) == (kind, dims), f"{name}.{fname}: {kind}{dims} in the header, {bound}{extents} in the mirror"
+            assert target is _MIRRORS.get(struct), f"{name}.{fname}: mirrored as a pointer to {target}"
+
+
+def test_constants_match_the_header():
+    """Every integer #define / enumerator of the header that _abi mirrors carries the header's value there, and _abi mirrors no
+    AFT_* constant the header does not have."""
+    header = _header_constants()
+    compared = {n: v for n, v in header.items() if hasattr(_abi, n)}
+    assert compared and "AFT_ABI_VERSION" in compared
+    assert {n for n in vars(_abi) if n.startswith("AFT_")} == set(compared)
+    for n, v in compared.items():
+        assert getattr(_abi, n) == v, f"{n}: {v} in the header, {getattr(_abi, n)} in _abi"
 
 
 def test_library_exports_all_symbols():
