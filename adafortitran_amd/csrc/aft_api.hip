@@ -25,6 +25,11 @@ void set_error(const char *fmt, ...) {
     va_end(ap);
 }
 
+int hip_fail(const char *what, hipError_t e) {
+    set_error("%s: %s", what, hipGetErrorString(e));
+    return AFT_ERR_HIP;
+}
+
 int current_device() {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) dev = 0;
@@ -100,8 +105,6 @@ WeightsDev weights_window(const aft_weights &w, int first, int count) {
     for (int i = 0; i < count && i < kLayerWindow && w.layers != nullptr; ++i) d.layers[i] = w.layers[first + i];
     return d;
 }
-
-static int tokens_of(const aft_config &c) { return (c.num_scs / c.patch_scs) * (c.num_symbols / c.patch_symbols); }
 
 bool packed_engine_ok(const aft_config &c) {
     if (c.num_head <= 0 || c.model_dim <= 0 || c.model_dim % c.num_head != 0) return false;
@@ -182,48 +185,49 @@ int check_config(const aft_config *c) {
     return AFT_OK;
 }
 
-static size_t align64(size_t floats) { return (floats + 63) / 64 * 64; }
-
 Workspace plan_workspace(const aft_config &c, int batch) {
     Workspace ws{};
     ws.tokens = tokens_of(c);
     ws.tokpad = round_up(ws.tokens, kTile);
     ws.planes = 2 * batch;
-    const size_t rows = (size_t)ws.planes * ws.tokens;
-    size_t off = 0;
-    ws.conv_enhanced = off; off += align64((size_t)ws.planes * c.num_scs * c.num_symbols);
-    ws.tokens6 = off;       off += align64((size_t)batch * ws.tokens * 6);
+    const size_t rows = (size_t)ws.planes * ws.tokens, plane_floats = (size_t)ws.planes * c.num_scs * c.num_symbols;
+    ws.conv_enhanced = ws.take(plane_floats);
+    ws.tokens6 = ws.take((size_t)batch * ws.tokens * 6, c.adaptive ? (size_t)batch * ws.tokens * 6 : 0);
     if (!packed_engine_ok(c)) {   // general engine: row-major tensors of one layer at a time (run_encoder_general)
         const size_t d = c.model_dim, ff = 2 * d;
-        ws.x = off;        off += align64(std::max(rows * d, (size_t)ws.planes * c.num_scs * c.num_symbols));   // also the upsampler's plane scratch
-        ws.attn = off;     off += align64(rows * d);
-        ws.q = ws.k = ws.vt = ws.wpack = off;
-        ws.out6 = off;     off += align64(rows * out6_stride(c));
-        ws.convfrag = off; off += align64(2 * kConvFragFloats);
-        ws.g_x1 = off;     off += align64(rows * d);
-        ws.g_y = off;      off += align64(rows * d);
-        ws.g_s = off;      off += align64(rows * d);
-        ws.g_stats = off;  off += align64(rows * 2);
-        ws.g_qkv = off;    off += align64(rows * 3 * d);
-        ws.g_lse = off;    off += align64(rows * c.num_head);
-        ws.g_a = off;      off += align64(rows * ff);
-        ws.g_hd = off;     off += align64(rows * ff);
-        ws.g_pad = off;    off += align64(attn_train_pad_floats(c, rows));
-        ws.total_floats = off;
+        ws.x = ws.take(std::max(rows * d, plane_floats));   // also the upsampler's plane scratch
+        ws.attn = ws.take(rows * d);
+        ws.q = ws.k = ws.vt = ws.wpack = ws.total;          // (no such regions: the offset of what follows)
+        ws.out6 = ws.take(rows * out6_stride(c));
+        ws.convfrag = ws.take(2 * kConvFragFloats);
+        ws.g_x1 = ws.take(rows * d);
+        ws.g_y = ws.take(rows * d);
+        ws.g_s = ws.take(rows * d);
+        ws.g_stats = ws.take(rows * 2);
+        ws.g_qkv = ws.take(rows * 3 * d);
+        ws.g_lse = ws.take(rows * c.num_head);
+        ws.g_a = ws.take(rows * ff);
+        ws.g_hd = ws.take(rows * ff);
+        ws.g_pad = ws.take(attn_train_pad_floats(c, rows));
         return ws;
     }
-    ws.x = off;             off += align64((rows + 31) / 32 * 32 * c.model_dim);   // whole 32-row tiles (tile-blocked x)
+    ws.x = ws.take((rows + 31) / 32 * 32 * c.model_dim);   // whole 32-row tiles (tile-blocked x)
     // attention tiles: global 32-row tiles (layer-by-layer path) or ceil(tokens/32) tiles per plane (plane-resident path)
-    ws.attn = off;          off += align64(std::max((size_t)round_up((int)rows, kTile), (size_t)ws.planes * ws.tokpad) * c.model_dim);
+    ws.attn = ws.take(std::max((size_t)round_up((int)rows, kTile), (size_t)ws.planes * ws.tokpad) * c.model_dim);
     const size_t per_head = (size_t)ws.planes * ws.tokpad * c.model_dim;   // planes x (model_dim / 32) blocks x tokpad x 32
-    ws.q = off;             off += align64(per_head);
-    ws.k = off;             off += align64(per_head);
-    ws.vt = off;            off += align64(per_head);
-    ws.wpack = off;         off += align64(packed_layer_floats(c.model_dim) * c.num_layers);
-    ws.out6 = off;          off += align64(rows * out6_stride(c));
-    ws.convfrag = off;      off += align64(2 * kConvFragFloats);
-    ws.total_floats = off;
+    ws.q = ws.take(per_head);
+    ws.k = ws.take(per_head);
+    ws.vt = ws.take(per_head);
+    ws.wpack = ws.take(packed_layer_floats(c.model_dim) * c.num_layers);
+    ws.out6 = ws.take(rows * out6_stride(c));
+    ws.convfrag = ws.take(2 * kConvFragFloats);
     return ws;
+}
+
+// The activation buffer x is idle until the first encoder launch: it lends the upsampler its plane scratch when its rows x model_dim
+// floats (the unpadded count) hold the planes.  The general engine's x is sized for them.
+static bool x_holds_planes(const aft_config &c, const Workspace &ws) {
+    return !packed_engine_ok(c) || (size_t)ws.planes * ws.tokens * c.model_dim >= (size_t)ws.planes * c.num_scs * c.num_symbols;
 }
 
 // The kernels address every workspace region through a buffer resource with 32-bit byte offsets (srd.h: num_records
@@ -247,11 +251,6 @@ static int max_batch_of(const aft_config &c) {
     return (int)std::min<size_t>((((size_t)1 << 31) - 1) / per_frame, (size_t)1 << 24);
 }
 
-static int hip_fail(const char *what, hipError_t e) {
-    set_error("%s: %s", what, hipGetErrorString(e));
-    return AFT_ERR_HIP;
-}
-
 // ---- lanes (late round 5) ----
 // A forward whose launches are fewer than ~2.5 rounds of the persistent grids leaves CUs idle at the end of every launch (whole row
 // tiles / attention tasks over 256 CUs, section 5 of DESIGN.md).  Frames are independent, so such a forward is run as TWO (or more)
@@ -260,11 +259,10 @@ static int hip_fail(const char *what, hipError_t e) {
 // Each share is a complete forward with its own slice of the workspace (laid end to end, share 0 first); per-frame arithmetic does
 // not depend on the batch a frame travels in, so the bits are those of the single forward (tests/test_hip_parity.py).
 constexpr int kMaxLanes = 4;
-struct LanePlan {
+struct LanePlan : Layout {        // one region per share: a whole workspace plan
     int lanes;
     int frames[kMaxLanes], first[kMaxLanes];
     size_t ws_off[kMaxLanes];     // floats
-    size_t total_floats;
 };
 // When it pays (tools/debug/lanes_threshold.py and the tables of DESIGN.md section 5: one lane against two over eight configurations
 // x batches, four boxes):
@@ -304,19 +302,16 @@ static int lanes_wanted(const aft_config &c, int batch) {
 static LanePlan plan_lanes(const aft_config &c, int batch, int lanes) {
     LanePlan p{};
     p.lanes = std::max(1, std::min(lanes, std::min(batch, kMaxLanes)));
-    size_t off = 0;
     for (int i = 0; i < p.lanes; ++i) {
         p.first[i] = (int)((long)batch * i / p.lanes);
         p.frames[i] = (int)((long)batch * (i + 1) / p.lanes) - p.first[i];
-        p.ws_off[i] = off;
-        off += plan_workspace(c, p.frames[i]).total_floats;
+        p.ws_off[i] = p.take(plan_workspace(c, p.frames[i]).total);
     }
-    p.total_floats = off;
     return p;
 }
 static size_t workspace_floats_any_lanes(const aft_config &c, int batch) {   // whatever lanes_wanted() answers at call time fits
     size_t m = 0;
-    for (int l = 1; l <= kMaxLanes; ++l) m = std::max(m, plan_lanes(c, batch, l).total_floats);
+    for (int l = 1; l <= kMaxLanes; ++l) m = std::max(m, plan_lanes(c, batch, l).total);
     return m;
 }
 // Side streams + fork / join events of one caller stream (created on first use, up to the lane count a call asks for; nothing here
@@ -391,53 +386,55 @@ static void release_lane_streams(LaneStreams *ls) {
         if (&en.ls == ls) { --en.in_use; return; }
 }
 
-// `fused` (whole forward only): the first launch computes x0 from conv_enhanced / tokens6 itself (no embed kernel) and
-// the last one leaves linear_2's output in the q buffer instead of storing x (the conv tail reads it from there).
+// What the whole forward fuses into the chain launch at `pos` of the encoder: the first one (QKV only) computes x0 from conv_enhanced /
+// tokens6 itself (no embed kernel), the last one writes linear_2's output to out6 instead of storing x (the conv tail reads it there);
+// nobody but these launches reads x, so it crosses HBM in tile-blocked order (every access 1 KB contiguous).
+enum ChainPos { kChainFirst, kChainMiddle, kChainLast };
+static ChainFusion chain_fusion_for(ChainPos pos, const aft_config &c, const WeightsDev &w, const Workspace &ws, float *base) {
+    ChainFusion f{};
+    f.x_blocked = true;
+    if (pos == kChainFirst) {
+        f.conv_enhanced = base + ws.conv_enhanced;
+        f.tokens6 = c.adaptive ? base + ws.tokens6 : nullptr;
+        f.lin1_w = w.lin1_w; f.lin1_b = w.lin1_b; f.pos = w.pos;
+    } else if (pos == kChainLast) {
+        f.lin2_w = w.lin2_w; f.lin2_b = w.lin2_b; f.out6 = base + ws.out6;
+    }
+    return f;
+}
+
+// The packed engine's launch sequence for layers [first_layer, last_layer] on `x` (the workspace's own, or the caller's row-major
+// tensor: aft_stage_encoder_layer_f32).  `fused` (whole forward only): chain_fusion_for.
 // `prepacked`: the caller's fragment-packed image of ALL layers (aft_pack_weights_f32), or NULL = pack into the workspace now.
 // `w`: the non-layer pointers (+ a window of the first layers for the kernels that take the table by value); `layers`: the HOST array
 // of all num_layers layers.
-static int run_encoder(const aft_config &c, const WeightsDev &w, const aft_layer_weights *layers, const Workspace &ws, float *base,
+static int run_encoder(const aft_config &c, const WeightsDev &w, const aft_layer_weights *layers, const Workspace &ws, float *base, float *x,
                        int first_layer, int last_layer, hipStream_t st, bool fused = false, const float *prepacked = nullptr) {
-    float *x = base + ws.x, *attn = base + ws.attn, *q = base + ws.q, *k = base + ws.k, *vt = base + ws.vt;
+    float *attn = base + ws.attn, *q = base + ws.q, *k = base + ws.k, *vt = base + ws.vt;
     const int rows = ws.planes * ws.tokens;
     const size_t pl = packed_layer_floats(c.model_dim);
     const float *wp = prepacked != nullptr ? prepacked : base + ws.wpack;
-    hipError_t e;
-    if (prepacked == nullptr) {
-        // weights arrive in torch layout on every call (stateless ABI): re-lay them into fragment order
-        e = launch_pack_weights(c, layers + first_layer, base + ws.wpack + first_layer * pl, last_layer - first_layer + 1, st);
-        if (e != hipSuccess) return hip_fail("pack_weights", e);
-    }
+    if (prepacked == nullptr)   // weights arrive in torch layout on every call (stateless ABI): re-lay them into fragment order
+        STEP("pack_weights", launch_pack_weights(c, layers + first_layer, base + ws.wpack + first_layer * pl, last_layer - first_layer + 1, st));
     // whole forward and the caller asks for it: ONE launch for the encoder (k_encoder.hip).  AUTO means the launches:
     // measured on the MI355X at B = 128 (256 planes on 256 CUs, its best case) the plane-resident kernel is 1.5 % slower
     // (profiles/r03_ab_encoder.json), so nothing selects it by itself.
     if (fused && c.encoder_path == AFT_ENCODER_PLANE && c.precision == AFT_PRECISION_F32 && first_layer == 0 &&
         last_layer == c.num_layers - 1 && encoder_plane_ok(c)) {
-        e = launch_encoder_plane(c, w, wp, base + ws.conv_enhanced, c.adaptive ? base + ws.tokens6 : nullptr, x, attn, q, k, vt,
-                                 base + ws.out6, ws.planes, ws.tokens, ws.tokpad, st);
-        return e == hipSuccess ? AFT_OK : hip_fail("encoder(plane-resident)", e);
+        STEP("encoder(plane-resident)", launch_encoder_plane(c, w, wp, base + ws.conv_enhanced, c.adaptive ? base + ws.tokens6 : nullptr, x, attn,
+                                                             q, k, vt, base + ws.out6, ws.planes, ws.tokens, ws.tokpad, st));
+        return AFT_OK;
     }
+    const ChainFusion first = chain_fusion_for(kChainFirst, c, w, ws, base), middle = chain_fusion_for(kChainMiddle, c, w, ws, base),
+                      last = chain_fusion_for(kChainLast, c, w, ws, base);
     // in-projection of the first layer (QKV-only pass of the chain kernel)
-    ChainFusion first{}, last{}, middle{};
-    // whole forward: nobody but these launches reads x, so it crosses HBM in tile-blocked order (every access 1 KB contiguous)
-    first.x_blocked = last.x_blocked = middle.x_blocked = fused;
-    if (fused) {
-        first.conv_enhanced = base + ws.conv_enhanced;
-        first.tokens6 = c.adaptive ? base + ws.tokens6 : nullptr;
-        first.lin1_w = w.lin1_w; first.lin1_b = w.lin1_b; first.pos = w.pos;
-        last.lin2_w = w.lin2_w; last.lin2_b = w.lin2_b; last.out6 = base + ws.out6;
-    }
-    e = launch_chain(c, nullptr, nullptr, &layers[first_layer], wp + first_layer * pl, nullptr, x, q, k, vt, rows,
-                     ws.tokens, ws.tokpad, st, fused ? &first : nullptr);
-    if (e != hipSuccess) return hip_fail("chain(qkv)", e);
+    STEP("chain(qkv)", launch_chain(c, nullptr, nullptr, &layers[first_layer], wp + first_layer * pl, nullptr, x, q, k, vt, rows,
+                                    ws.tokens, ws.tokpad, st, fused ? &first : nullptr));
     for (int l = first_layer; l <= last_layer; ++l) {
-        e = launch_attention(c, q, k, vt, layers[l].in_proj_b, attn, ws.planes, ws.tokens, ws.tokpad, st);
-        if (e != hipSuccess) return hip_fail("attention", e);
+        STEP("attention", launch_attention(c, q, k, vt, layers[l].in_proj_b, attn, ws.planes, ws.tokens, ws.tokpad, st));
         const bool more = l < last_layer;
-        e = launch_chain(c, &layers[l], wp + l * pl, more ? &layers[l + 1] : nullptr,
-                         more ? wp + (l + 1) * pl : nullptr, attn, x, q, k, vt, rows, ws.tokens, ws.tokpad, st,
-                         fused ? (more ? &middle : &last) : nullptr);
-        if (e != hipSuccess) return hip_fail("chain(mlp)", e);
+        STEP("chain(mlp)", launch_chain(c, &layers[l], wp + l * pl, more ? &layers[l + 1] : nullptr, more ? wp + (l + 1) * pl : nullptr, attn,
+                                        x, q, k, vt, rows, ws.tokens, ws.tokpad, st, fused ? (more ? &middle : &last) : nullptr));
     }
     return AFT_OK;
 }
@@ -447,23 +444,18 @@ static int run_encoder(const aft_config &c, const WeightsDev &w, const aft_layer
 // (aft_train.hip) with dropout off -- in-projection GEMM, attention (heads padded to 32-feature blocks where needed), out-projection GEMM,
 // residual + LayerNorm, linear1 GEMM, activation, linear2 GEMM, residual + LayerNorm -- for every shape the packed engine does not
 // take.  The tensors between the launches are one layer's worth of workspace, re-used layer after layer.
-#define GSTEP(name, call)                                   \
-    do {                                                    \
-        hipError_t e_ = (call);                             \
-        if (e_ != hipSuccess) return hip_fail(name, e_);    \
-    } while (0)
 static int general_layer(const aft_config &c, const aft_layer_weights &lw, const Workspace &ws, float *base, float *x, hipStream_t st) {
     const int rows = ws.planes * ws.tokens, d = c.model_dim, ff = 2 * d;
     float *qkv = base + ws.g_qkv, *attn = base + ws.attn, *y = base + ws.g_y, *x1 = base + ws.g_x1, *s = base + ws.g_s,
           *stats = base + ws.g_stats, *a = base + ws.g_a, *hd = base + ws.g_hd;
-    GSTEP("general: in-projection", launch_gemm(0, x, lw.in_proj_w, qkv, lw.in_proj_b, rows, 3 * d, d, d, d, 3 * d, false, st));
-    GSTEP("general: attention", launch_attn_train_fwd(c, qkv, attn, base + ws.g_lse, ws.planes, ws.tokens, 0.f, 0u, st, base + ws.g_pad));
-    GSTEP("general: out-projection", launch_gemm(0, attn, lw.out_proj_w, y, lw.out_proj_b, rows, d, d, d, d, d, false, st));
-    GSTEP("general: norm1", launch_add_ln_fwd(x, y, lw.norm1_w, lw.norm1_b, s, stats, x1, rows, d, 1e-5f, 0.f, 0u, st));
-    GSTEP("general: linear1", launch_gemm(0, x1, lw.lin1_w, a, lw.lin1_b, rows, ff, d, d, d, ff, false, st));
-    GSTEP("general: activation", launch_act_fwd(c.activation, a, hd, rows, ff, 0.f, 0u, st));
-    GSTEP("general: linear2", launch_gemm(0, hd, lw.lin2_w, y, lw.lin2_b, rows, d, ff, ff, ff, d, false, st));
-    GSTEP("general: norm2", launch_add_ln_fwd(x1, y, lw.norm2_w, lw.norm2_b, s, stats, x, rows, d, 1e-5f, 0.f, 0u, st));
+    STEP("general: in-projection", launch_gemm(0, x, lw.in_proj_w, qkv, lw.in_proj_b, rows, 3 * d, d, d, d, 3 * d, false, st));
+    STEP("general: attention", launch_attn_train_fwd(c, qkv, attn, base + ws.g_lse, ws.planes, ws.tokens, 0.f, 0u, st, base + ws.g_pad));
+    STEP("general: out-projection", launch_gemm(0, attn, lw.out_proj_w, y, lw.out_proj_b, rows, d, d, d, d, d, false, st));
+    STEP("general: norm1", launch_add_ln_fwd(x, y, lw.norm1_w, lw.norm1_b, s, stats, x1, rows, d, 1e-5f, 0.f, 0u, st));
+    STEP("general: linear1", launch_gemm(0, x1, lw.lin1_w, a, lw.lin1_b, rows, ff, d, d, d, ff, false, st));
+    STEP("general: activation", launch_act_fwd(c.activation, a, hd, rows, ff, 0.f, 0u, st));
+    STEP("general: linear2", launch_gemm(0, hd, lw.lin2_w, y, lw.lin2_b, rows, d, ff, ff, ff, d, false, st));
+    STEP("general: norm2", launch_add_ln_fwd(x1, y, lw.norm2_w, lw.norm2_b, s, stats, x, rows, d, 1e-5f, 0.f, 0u, st));
     return AFT_OK;
 }
 // embedding -> layers -> linear_2 into out6 [rows][out6_stride] (what the conv tail reads)
@@ -471,12 +463,12 @@ static int run_encoder_general(const aft_config &c, const WeightsDev &w, const a
                                int batch, hipStream_t st) {
     float *x = base + ws.x;
     const int rows = ws.planes * ws.tokens, d = c.model_dim, p = c.patch_scs * c.patch_symbols;
-    GSTEP("general: embedding", launch_embed_any(c, w, base + ws.conv_enhanced, c.adaptive ? base + ws.tokens6 : nullptr, x, batch, st));
+    STEP("general: embedding", launch_embed_any(c, w, base + ws.conv_enhanced, c.adaptive ? base + ws.tokens6 : nullptr, x, batch, st));
     for (int l = 0; l < c.num_layers; ++l) {
         const int rc = general_layer(c, layers[l], ws, base, x, st);
         if (rc != AFT_OK) return rc;
     }
-    GSTEP("general: linear_2", launch_gemm(0, x, w.lin2_w, base + ws.out6, w.lin2_b, rows, p, d, d, d, out6_stride(c), false, st));
+    STEP("general: linear_2", launch_gemm(0, x, w.lin2_w, base + ws.out6, w.lin2_b, rows, p, d, d, d, out6_stride(c), false, st));
     return AFT_OK;
 }
 
@@ -538,15 +530,15 @@ int aft_workspace_region(const aft_config *cfg, int batch, int region, size_t *o
         return AFT_ERR_ARG;
     }
     const Workspace ws = plan_workspace(*cfg, batch);
-    size_t off = 0, n = 0;
+    size_t off = 0;
     switch (region) {
-        case AFT_REGION_CONV_ENHANCED: off = ws.conv_enhanced; n = (size_t)ws.planes * cfg->num_scs * cfg->num_symbols; break;
-        case AFT_REGION_TOKENS6: off = ws.tokens6; n = cfg->adaptive ? (size_t)batch * ws.tokens * 6 : 0; break;
-        case AFT_REGION_ENC_OUT: off = ws.out6; n = (size_t)ws.planes * ws.tokens * out6_stride(*cfg); break;
+        case AFT_REGION_CONV_ENHANCED: off = ws.conv_enhanced; break;
+        case AFT_REGION_TOKENS6: off = ws.tokens6; break;
+        case AFT_REGION_ENC_OUT: off = ws.out6; break;
         default: set_error("aft_workspace_region: unknown region %d", region); return AFT_ERR_ARG;
     }
     *offset_bytes = off * sizeof(float);
-    *size_bytes = n * sizeof(float);
+    *size_bytes = ws.floats_at(off) * sizeof(float);
     return AFT_OK;
 }
 
@@ -575,8 +567,32 @@ int aft_workspace_lanes(const aft_config *cfg, int batch, int *lanes, int *frame
         }                             \
     } while (0)
 
+// one share of the batch: a complete forward on `st` in its own workspace slice
 static int forward_lane(const aft_config *cfg, const aft_weights *w, const float *prepacked, const float *pilots, const float *snr,
-                        const float *ds, const float *dop, float *out, float *base, int batch, hipStream_t st);
+                        const float *ds, const float *dop, float *out, float *base, int batch, hipStream_t st) {
+    const Workspace ws = plan_workspace(*cfg, batch);
+    const bool general = !packed_engine_ok(*cfg);
+    const WeightsDev wd = weights_window(*w, 0, cfg->num_layers);
+    // prologue: the channel adapter, -- unless the caller owns a packed image -- the re-lay of the encoder weights into fragment
+    // order, and the pilot_upsampler product over all planes, in ONE launch (none depends on anything the forward computes).
+    float *wpack = prepacked != nullptr || general ? nullptr : base + ws.wpack;      // (the general engine reads the weights as PyTorch holds them)
+    float *lent = x_holds_planes(*cfg, ws) ? base + ws.x : nullptr;
+    float *up_planes = prologue_upsample_ok(*cfg, wd) ? lent : nullptr;
+    STEP("prologue(adapter + pack_weights + upsampler product)",
+         launch_prologue(*cfg, wd, snr, ds, dop, base + ws.tokens6, batch, wpack, pilots, up_planes, st, base + ws.convfrag));
+    if (wpack != nullptr && cfg->num_layers > kLayerWindow)     // the prologue launch packs the window of layers its argument holds
+        STEP("pack_weights(layers beyond the prologue's window)",
+             launch_pack_weights(*cfg, w->layers + kLayerWindow, wpack + packed_layer_floats(cfg->model_dim) * kLayerWindow,
+                                 cfg->num_layers - kLayerWindow, st));
+    STEP("upsample", launch_upsample(*cfg, wd, pilots, base + ws.conv_enhanced, batch, st, lent, up_planes != nullptr, base + ws.convfrag));
+    // packed engine: patch embedding + linear_1 + positions run inside the first chain launch, linear_2 inside the last one
+    const int rc = general ? run_encoder_general(*cfg, wd, w->layers, ws, base, batch, st)
+                           : run_encoder(*cfg, wd, w->layers, ws, base, base + ws.x, 0, cfg->num_layers - 1, st, true,
+                                         prepacked != nullptr ? prepacked : wpack);
+    if (rc != AFT_OK) return rc;
+    STEP("tail", launch_tail(*cfg, wd, nullptr, base + ws.conv_enhanced, out, batch, st, base + ws.out6, base + ws.convfrag + kConvFragFloats));
+    return AFT_OK;
+}
 
 static int forward_impl(const aft_config *cfg, const aft_weights *w, const float *prepacked, const float *pilots,
                         const float *snr, const float *ds, const float *dop, float *out, void *workspace,
@@ -592,8 +608,8 @@ static int forward_impl(const aft_config *cfg, const aft_weights *w, const float
     hipStream_t user = static_cast<hipStream_t>(stream);
     AFT_REQUIRE(w->layers != nullptr, "aft_weights.layers is NULL (host array of num_layers entries)");
     const LanePlan lp = plan_lanes(*cfg, batch, lanes_wanted(*cfg, batch));
-    AFT_REQUIRE(workspace_bytes >= lp.total_floats * sizeof(float), "workspace too small: %zu < %zu bytes (aft_workspace_bytes)",
-                workspace_bytes, lp.total_floats * sizeof(float));
+    AFT_REQUIRE(workspace_bytes >= lp.total * sizeof(float), "workspace too small: %zu < %zu bytes (aft_workspace_bytes)",
+                workspace_bytes, lp.total * sizeof(float));
     // side streams for the shares beyond the first; none to be had (header, "Lanes") = the shares run one after the other on the
     // caller's stream in the same workspace layout: same bits, and aft_workspace_lanes stays true
     LaneStreams *ls = lp.lanes > 1 ? acquire_lane_streams(user, lp.lanes) : nullptr;
@@ -606,17 +622,15 @@ static int forward_impl(const aft_config *cfg, const aft_weights *w, const float
     const int pil_floats = 2 * cfg->pilot_scs * cfg->pilot_symbols, out_floats = 2 * cfg->num_scs * cfg->num_symbols;   // complex64 per frame
 #ifdef AFT_CHECKED
     {   // workspace-plan invariants: shares cover the batch exactly once, slices are disjoint, in order and inside the caller's buffer,
-        // every region of a slice lies inside it and starts on a 256-byte boundary
+        // every region of a slice lies inside it, behind the one before it, and starts on a 256-byte boundary (check_layout)
         int covered = 0;
         for (int i = 0; i < lp.lanes; ++i) {
             const Workspace wl = plan_workspace(*cfg, lp.frames[i]);
             AFT_HOST_ASSERT(lp.first[i] == covered && lp.frames[i] > 0, "lane shares are not a partition of the batch");
             covered += lp.frames[i];
-            AFT_HOST_ASSERT(lp.ws_off[i] % 64 == 0 && (lp.ws_off[i] + wl.total_floats) * sizeof(float) <= workspace_bytes, "lane slice outside the workspace");
-            AFT_HOST_ASSERT(i + 1 == lp.lanes || lp.ws_off[i] + wl.total_floats <= lp.ws_off[i + 1], "lane slices overlap");
-            const size_t regions[] = {wl.conv_enhanced, wl.tokens6, wl.x, wl.attn, wl.q, wl.k, wl.vt, wl.wpack, wl.out6, wl.convfrag,
-                                      wl.g_x1, wl.g_y, wl.g_s, wl.g_stats, wl.g_qkv, wl.g_lse, wl.g_a, wl.g_hd, wl.g_pad};
-            for (size_t r : regions) AFT_HOST_ASSERT(r % 64 == 0 && r <= wl.total_floats, "workspace region outside its slice");
+            AFT_HOST_ASSERT(lp.ws_off[i] % 64 == 0 && (lp.ws_off[i] + wl.total) * sizeof(float) <= workspace_bytes, "lane slice outside the workspace");
+            AFT_HOST_ASSERT(i + 1 == lp.lanes || lp.ws_off[i] + wl.total <= lp.ws_off[i + 1], "lane slices overlap");
+            AFT_HOST_ASSERT(check_layout(wl, workspace_bytes - lp.ws_off[i] * sizeof(float)), "workspace region outside its slice");
         }
         AFT_HOST_ASSERT(covered == batch, "lane shares do not cover the batch");
     }
@@ -638,42 +652,6 @@ static int forward_impl(const aft_config *cfg, const aft_weights *w, const float
         if (ej != hipSuccess && result == AFT_OK) return hip_fail("lanes(join)", ej);
     }
     return result;
-}
-
-// one share of the batch: a complete forward on `st` in its own workspace slice
-static int forward_lane(const aft_config *cfg, const aft_weights *w, const float *prepacked, const float *pilots, const float *snr,
-                        const float *ds, const float *dop, float *out, float *base, int batch, hipStream_t st) {
-    const Workspace ws = plan_workspace(*cfg, batch);
-    const bool general = !packed_engine_ok(*cfg);
-    const WeightsDev wd = weights_window(*w, 0, cfg->num_layers);
-    int rc = AFT_OK;
-    // prologue: the channel adapter, -- unless the caller owns a packed image -- the re-lay of the encoder weights into fragment
-    // order, and the pilot_upsampler product over all planes, in ONE launch (none depends on anything the forward computes).
-    // The activation buffer x is idle until the first encoder launch: it lends the upsampler its plane scratch when it is large enough
-    float *wpack = prepacked != nullptr || general ? nullptr : base + ws.wpack;      // (the general engine reads the weights as PyTorch holds them)
-    const size_t x_floats = general ? ((size_t)1 << 62) : (size_t)ws.planes * ws.tokens * cfg->model_dim;   // general: x is sized for the planes
-    const size_t up_floats = (size_t)ws.planes * cfg->num_scs * cfg->num_symbols;
-    float *up_planes = x_floats >= up_floats && prologue_upsample_ok(*cfg, wd) ? base + ws.x : nullptr;
-    hipError_t e = launch_prologue(*cfg, wd, snr, ds, dop, base + ws.tokens6, batch, wpack, pilots, up_planes, st, base + ws.convfrag);
-    if (e != hipSuccess) return hip_fail("prologue(adapter + pack_weights + upsampler product)", e);
-    if (wpack != nullptr && cfg->num_layers > kLayerWindow) {     // the prologue launch packs the window of layers its argument holds
-        e = launch_pack_weights(*cfg, w->layers + kLayerWindow, wpack + packed_layer_floats(cfg->model_dim) * kLayerWindow,
-                                cfg->num_layers - kLayerWindow, st);
-        if (e != hipSuccess) return hip_fail("pack_weights(layers beyond the prologue's window)", e);
-    }
-    e = launch_upsample(*cfg, wd, pilots, base + ws.conv_enhanced, batch, st, x_floats >= up_floats ? base + ws.x : nullptr, up_planes != nullptr,
-                        base + ws.convfrag);
-    if (e != hipSuccess) return hip_fail("upsample", e);
-    if (general) {
-        rc = run_encoder_general(*cfg, wd, w->layers, ws, base, batch, st);
-    } else {
-        // patch embedding + linear_1 + positions run inside the first chain launch, linear_2 inside the last one
-        rc = run_encoder(*cfg, wd, w->layers, ws, base, 0, cfg->num_layers - 1, st, true, prepacked != nullptr ? prepacked : wpack);
-    }
-    if (rc != AFT_OK) return rc;
-    e = launch_tail(*cfg, wd, nullptr, base + ws.conv_enhanced, out, batch, st, base + ws.out6, base + ws.convfrag + kConvFragFloats);
-    if (e != hipSuccess) return hip_fail("tail", e);
-    return AFT_OK;
 }
 
 int aft_forward_f32(const aft_config *cfg, const aft_weights *w, const float *pilots, const float *snr,
@@ -887,25 +865,13 @@ int aft_stage_encoder_layer_f32(const aft_config *cfg, const aft_weights *w, int
     AFT_REQUIRE(w && w->layers && x && scratch && batch > 0, "bad argument");
     AFT_REQUIRE(layer >= 0 && layer < cfg->num_layers, "layer %d out of range", layer);
     AFT_REQUIRE(batch <= max_batch_of(*cfg), "batch %d exceeds aft_max_batch = %d", batch, max_batch_of(*cfg));
-    Workspace ws = plan_workspace(*cfg, batch);
-    AFT_REQUIRE(scratch_bytes >= ws.total_floats * sizeof(float), "scratch too small");
-    // run on the caller's x: point the plan's x slot at it (offsets are relative to scratch)
+    const Workspace ws = plan_workspace(*cfg, batch);
+    AFT_REQUIRE(scratch_bytes >= ws.total * sizeof(float), "scratch too small");
+    // the encoder's launch sequence for this one layer on the caller's row-major x (the plan's own x region stays unused)
     float *base = static_cast<float *>(scratch);
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (!packed_engine_ok(*cfg)) return general_layer(*cfg, w->layers[layer], ws, base, x, st);
-    const int rows = ws.planes * ws.tokens;
-    float *wp = base + ws.wpack + layer * packed_layer_floats(cfg->model_dim);
-    hipError_t e = launch_pack_weights(*cfg, w->layers + layer, wp, 1, st);
-    if (e != hipSuccess) return hip_fail("pack_weights", e);
-    e = launch_chain(*cfg, nullptr, nullptr, &w->layers[layer], wp, nullptr, x, base + ws.q, base + ws.k, base + ws.vt,
-                     rows, ws.tokens, ws.tokpad, st);
-    if (e != hipSuccess) return hip_fail("chain(qkv)", e);
-    e = launch_attention(*cfg, base + ws.q, base + ws.k, base + ws.vt, w->layers[layer].in_proj_b, base + ws.attn,
-                         ws.planes, ws.tokens, ws.tokpad, st);
-    if (e != hipSuccess) return hip_fail("attention", e);
-    e = launch_chain(*cfg, &w->layers[layer], wp, nullptr, nullptr, base + ws.attn, x, nullptr, nullptr, nullptr, rows,
-                     ws.tokens, ws.tokpad, st);
-    return e == hipSuccess ? AFT_OK : hip_fail("chain(mlp)", e);
+    return run_encoder(*cfg, weights_window(*w, 0, 0), w->layers, ws, base, x, layer, layer, st);
 }
 
 int aft_stage_tail_f32(const aft_config *cfg, const aft_weights *w, const float *x, const float *conv_enhanced,
@@ -936,56 +902,42 @@ int aft_profile_kernel_f32(const aft_config *cfg, const aft_weights *w, int whic
         return AFT_ERR_SHAPE;
     }
     const Workspace ws = plan_workspace(*cfg, batch);
-    AFT_REQUIRE(workspace_bytes >= ws.total_floats * sizeof(float), "workspace too small");
+    AFT_REQUIRE(workspace_bytes >= ws.total * sizeof(float), "workspace too small");
     const WeightsDev wd = weights_window(*w, 0, cfg->num_layers);
     AFT_REQUIRE(cfg->num_layers >= 2 || which != AFT_KERNEL_CHAIN, "chain profile needs >= 2 layers");
     hipStream_t st = static_cast<hipStream_t>(stream);
     float *base = static_cast<float *>(workspace);
     float *x = base + ws.x, *attn = base + ws.attn, *q = base + ws.q, *k = base + ws.k, *vt = base + ws.vt;
     const int rows = ws.planes * ws.tokens;
+    float *lent = x_holds_planes(*cfg, ws) ? x : nullptr;     // as the forward: the upsampler's planes lie in x when it holds them
+    const float *wp = base + ws.wpack;
+    const ChainFusion first = chain_fusion_for(kChainFirst, *cfg, wd, ws, base), middle = chain_fusion_for(kChainMiddle, *cfg, wd, ws, base),
+                      last = chain_fusion_for(kChainLast, *cfg, wd, ws, base);
     hipError_t e = hipSuccess;
     for (int i = 0; i < reps && e == hipSuccess; ++i) {
         switch (which) {
             case AFT_KERNEL_UPSAMPLE:
                 AFT_REQUIRE(out != nullptr, "upsample profile needs the pilots pointer in `out`");
-                // as the forward: the planes of the pilot_upsampler product lie in x (computed by the prologue launch in the forward;
-                // here whatever x holds -- the conv stack's time does not depend on its data)
-                e = launch_upsample(*cfg, wd, out, base + ws.conv_enhanced, batch, st,
-                                    (size_t)ws.planes * ws.tokens * cfg->model_dim >= (size_t)ws.planes * cfg->num_scs * cfg->num_symbols ? x : nullptr,
-                                    prologue_upsample_ok(*cfg, wd), base + ws.convfrag);
+                // (the prologue launch computes the planes in the forward; here whatever x holds -- the conv stack's time does not
+                // depend on its data)
+                e = launch_upsample(*cfg, wd, out, base + ws.conv_enhanced, batch, st, lent, prologue_upsample_ok(*cfg, wd), base + ws.convfrag);
                 break;
             case AFT_KERNEL_EMBED:
                 e = launch_embed(*cfg, wd, base + ws.conv_enhanced, cfg->adaptive ? base + ws.tokens6 : nullptr, x, batch, st);
                 break;
-            case AFT_KERNEL_QKV: {   // as in the forward: embedding fused in front of the in-projection
-                ChainFusion f{};
-                f.conv_enhanced = base + ws.conv_enhanced;
-                f.tokens6 = cfg->adaptive ? base + ws.tokens6 : nullptr;
-                f.lin1_w = w->lin1_w; f.lin1_b = w->lin1_b; f.pos = w->pos;
-                f.x_blocked = true;
-                e = launch_chain(*cfg, nullptr, nullptr, &w->layers[0], base + ws.wpack, nullptr, x, q, k, vt, rows,
-                                 ws.tokens, ws.tokpad, st, &f);
+            case AFT_KERNEL_QKV:     // as in the forward: embedding fused in front of the in-projection
+                e = launch_chain(*cfg, nullptr, nullptr, &w->layers[0], wp, nullptr, x, q, k, vt, rows, ws.tokens, ws.tokpad, st, &first);
                 break;
-            }
             case AFT_KERNEL_ATTENTION:
                 e = launch_attention(*cfg, q, k, vt, w->layers[0].in_proj_b, attn, ws.planes, ws.tokens, ws.tokpad, st);
                 break;
-            case AFT_KERNEL_CHAIN: {   // as in the forward: x in tile-blocked order
-                ChainFusion f{};
-                f.x_blocked = true;
-                e = launch_chain(*cfg, &w->layers[0], base + ws.wpack, &w->layers[1],
-                                 base + ws.wpack + packed_layer_floats(cfg->model_dim), attn, x, q, k, vt, rows,
-                                 ws.tokens, ws.tokpad, st, &f);
+            case AFT_KERNEL_CHAIN:   // as in the forward: x in tile-blocked order
+                e = launch_chain(*cfg, &w->layers[0], wp, &w->layers[1], wp + packed_layer_floats(cfg->model_dim), attn, x, q, k, vt, rows,
+                                 ws.tokens, ws.tokpad, st, &middle);
                 break;
-            }
-            case AFT_KERNEL_CHAIN_LAST: {   // as in the forward: linear_2 fused behind LN2, x not stored
-                ChainFusion f{};
-                f.lin2_w = w->lin2_w; f.lin2_b = w->lin2_b; f.out6 = base + ws.out6;
-                f.x_blocked = true;
-                e = launch_chain(*cfg, &w->layers[0], base + ws.wpack, nullptr, nullptr, attn, x, q, k, vt, rows,
-                                 ws.tokens, ws.tokpad, st, &f);
+            case AFT_KERNEL_CHAIN_LAST:   // as in the forward: linear_2 fused behind LN2, x not stored
+                e = launch_chain(*cfg, &w->layers[0], wp, nullptr, nullptr, attn, x, q, k, vt, rows, ws.tokens, ws.tokpad, st, &last);
                 break;
-            }
             case AFT_KERNEL_ENCODER_PLANE:
                 AFT_REQUIRE(cfg->model_dim == 128, "the plane-resident encoder is instantiated for model_dim 128");
                 e = launch_encoder_plane(*cfg, wd, base + ws.wpack, base + ws.conv_enhanced,
@@ -994,12 +946,11 @@ int aft_profile_kernel_f32(const aft_config *cfg, const aft_weights *w, int whic
                 break;
             case AFT_KERNEL_PROLOGUE: {
                 AFT_REQUIRE(out != nullptr, "prologue profile needs the pilots pointer in `out`");
-                const bool lend = (size_t)ws.planes * ws.tokens * cfg->model_dim >= (size_t)ws.planes * cfg->num_scs * cfg->num_symbols;
                 const float *cond = out + (size_t)batch * cfg->pilot_scs * cfg->pilot_symbols * 2;   // [snr | ds | dop] behind the pilots
                 // AFT_PROLOGUE_NO_UP=1 (measurement only): the launch without the pilot_upsampler product -- bench.py charges the
                 // difference to the upsampler stage (the stage is K0 + K1 + K2)
                 e = launch_prologue(*cfg, wd, cond, cond + batch, cond + 2 * batch, base + ws.tokens6, batch, base + ws.wpack, out,
-                                    lend && prologue_upsample_ok(*cfg, wd) && !switch_on(SW_PROLOGUE_NO_UP) ? x : nullptr, st,
+                                    prologue_upsample_ok(*cfg, wd) && !switch_on(SW_PROLOGUE_NO_UP) ? lent : nullptr, st,
                                     base + ws.convfrag);
                 break;
             }

@@ -31,7 +31,7 @@ inline __host__ __device__ int round_up(int v, int m) { return (v + m - 1) / m *
 //     wave's LDS requests in issue order); the checked build puts the fence back, so "same bits as the product build" on the soak
 //     test is a test of that assumption.
 //   * AFT_SPIN_GUARD: a poll that does not end within ~2^22 sleeps traps (a lost hand-over becomes a fault, not a hung box).
-//   * AFT_HOST_ASSERT: workspace-plan invariants in aft_api.hip (regions inside the workspace, lanes disjoint).
+//   * AFT_HOST_ASSERT: the lane partition of a forward and check_layout (below) on every caller-owned buffer a call carves up.
 #ifdef AFT_CHECKED
 #define AFT_DEV_ASSERT(cond) do { if (!(cond)) __builtin_trap(); } while (0)
 #define AFT_CHECKED_FENCE() __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup")
@@ -150,6 +150,44 @@ __device__ __forceinline__ bool dropmask_keep(uint32_t row_word, uint32_t col_wo
     return __umul24(row_word, col_word) >= threshold;
 }
 
+// ---- layouts of caller-owned buffers (workspace, tape, scratch) ----
+// Every such buffer is planned ONCE, by a plan_* function that both its size query and its call use.  A plan is a Layout plus named
+// offsets: take(n) reserves n floats at the next 256-byte boundary (the only place that rounds to 64 floats), returns the offset and
+// records (offset, n), so that the checked build walks a plan's regions without naming them (check_layout).  To add a region: one
+// `name = take(floats)` line in the plan function, at the place the buffer shall hold it; nothing else lists regions.
+constexpr int kMaxRegions = 24;
+struct Layout {
+    struct Region { size_t off, floats; };   // floats: the unpadded count (what aft_workspace_region reports)
+    size_t total = 0;                        // floats reserved so far = the buffer's size once the plan is complete
+    int n = 0;
+    Region regions[kMaxRegions];
+    size_t take(size_t reserved, size_t reported) {
+        const size_t off = total;
+        if (n < kMaxRegions) regions[n] = Region{off, reported};
+        ++n;
+        total += (reserved + 63) / 64 * 64;
+        return off;
+    }
+    size_t take(size_t floats) { return take(floats, floats); }
+    size_t floats_at(size_t off) const {     // the recorded count of the region that starts at `off`
+        for (int i = 0; i < n && i < kMaxRegions; ++i)
+            if (regions[i].off == off) return regions[i].floats;
+        return 0;
+    }
+};
+// checked build (AFT_HOST_ASSERT(check_layout(plan, bytes), ...)): every region is recorded, starts on a 256-byte boundary, ends
+// before the next one begins, and the whole plan fits the `bytes` the caller passed
+inline bool check_layout(const Layout &l, size_t bytes) {
+    if (l.n > kMaxRegions || l.total % 64 != 0 || l.total * sizeof(float) > bytes) return false;
+    for (int i = 0; i < l.n; ++i) {
+        const size_t end = i + 1 < l.n ? l.regions[i + 1].off : l.total;
+        if (l.regions[i].off % 64 != 0 || l.regions[i].off + l.regions[i].floats > end) return false;
+    }
+    return true;
+}
+
+inline int tokens_of(const aft_config &c) { return (c.num_scs / c.patch_scs) * (c.num_symbols / c.patch_symbols); }
+
 // Device-resident scratch of one forward call; all offsets in floats, 256-B aligned.
 // Layout in HBM (DESIGN.md "data layout"):
 //   conv_enhanced [2B][S][T]            f32  kept for the S7 residual
@@ -163,8 +201,8 @@ __device__ __forceinline__ bool dropmask_keep(uint32_t row_word, uint32_t col_wo
 //   out6          [2B*tokens][8 | 16]   f32  linear_2 output of the last chain launch (input of the conv tail)
 //   convfrag      [2][22*64*4 + 160]    f32  conv2 / conv3 weights of the initial enhancer | the final refiner as 16x16x4 MFMA
 //                                            operand fragments (conv_device.h: conv_frag16_entry; rebuilt per call by the prologue)
-struct Workspace {
-    size_t conv_enhanced, tokens6, x, attn, q, k, vt, wpack, out6, convfrag, total_floats;
+struct Workspace : Layout {
+    size_t conv_enhanced, tokens6, x, attn, q, k, vt, wpack, out6, convfrag;
     // general engine only (row-major tensors of ONE layer, re-used layer after layer): x1 = LN1 output, y = projection outputs
     // before the residual joins, s / stats = pre-norm sum and (mean, rstd) that launch_add_ln_fwd also writes, qkv [rows][3d],
     // lse, a / hd = FFN pre-activation and activation [rows][2d], pad = padded-head images of qkv and o
@@ -174,8 +212,14 @@ struct Workspace {
 
 Workspace plan_workspace(const aft_config &c, int batch);
 
-// error plumbing (thread-local message, see aft_api.hip)
+// error plumbing (thread-local message, see aft_api.hip); hip_fail: "<what>: <HIP's error string>" -> AFT_ERR_HIP
 void set_error(const char *fmt, ...);
+int hip_fail(const char *what, hipError_t e);
+#define STEP(name, call)                                    \
+    do {                                                    \
+        hipError_t e_ = (call);                             \
+        if (e_ != hipSuccess) return hip_fail(name, e_);    \
+    } while (0)
 int check_config(const aft_config *c);
 // The launch sequence a configuration runs (aft_engine_of): decided by the configuration alone.
 bool packed_engine_ok(const aft_config &c);

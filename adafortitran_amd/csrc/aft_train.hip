@@ -16,56 +16,85 @@ namespace aft {
 
 namespace {
 
-size_t al64(size_t floats) { return (floats + 63) / 64 * 64; }
-
-struct Tape {   // offsets in floats
-    size_t qkv, attn, lse, s1, st1, x1, a, hd, s2, st2, total;
+struct Tape : Layout { size_t qkv, attn, lse, s1, st1, x1, a, hd, s2, st2; };   // offsets in floats
+// sl_*: slice storage per producer of the backward (every gradient kernel of the layer keeps its partial slices until the single
+// reduction launch at the end): LayerNorm-2 / linear2's weight / activation / linear1's weight / LayerNorm-1 / out_proj's weight /
+// in_proj's weight / in_proj's bias
+struct Scratch : Layout {
+    size_t g1, g2, g2b, gff, dqkv, dsum, sl_ln2, sl_w2, sl_act, sl_w1, sl_ln1, sl_wo, sl_wq, sl_bq, packed_t, lnp, attn_pad;
 };
-struct Scratch {
-    size_t g1, g2, g2b, gff, dqkv, dsum, slices, packed_t, lnp, attn_pad, total;
-};
-
-int tokens_of_cfg(const aft_config &c) { return (c.num_scs / c.patch_scs) * (c.num_symbols / c.patch_symbols); }
 
 Tape plan_tape(const aft_config &c, int batch) {
-    const size_t rows = (size_t)2 * batch * tokens_of_cfg(c), d = c.model_dim, ff = 2 * d;
+    const size_t rows = (size_t)2 * batch * tokens_of(c), d = c.model_dim, ff = 2 * d;
     Tape t{};
-    size_t off = 0;
-    t.qkv = off;  off += al64(rows * 3 * d);
-    t.attn = off; off += al64(rows * d);
-    t.lse = off;  off += al64(rows * c.num_head);
-    t.s1 = off;   off += al64(rows * d);
-    t.st1 = off;  off += al64(rows * 2);
-    t.x1 = off;   off += al64(rows * d);
-    t.a = off;    off += al64(rows * ff);
-    t.hd = off;   off += al64(rows * ff);   // drop(act(a)): kept so the backward does not recompute it (24 us per layer)
-    t.s2 = off;   off += al64(rows * d);
-    t.st2 = off;  off += al64(rows * 2);
-    t.total = off;
+    t.qkv = t.take(rows * 3 * d);
+    t.attn = t.take(rows * d);
+    t.lse = t.take(rows * c.num_head);
+    t.s1 = t.take(rows * d);
+    t.st1 = t.take(rows * 2);
+    t.x1 = t.take(rows * d);
+    t.a = t.take(rows * ff);
+    t.hd = t.take(rows * ff);   // drop(act(a)): kept so the backward does not recompute it (24 us per layer)
+    t.s2 = t.take(rows * d);
+    t.st2 = t.take(rows * 2);
     return t;
 }
 
 Scratch plan_scratch(const aft_config &c, int batch) {
-    const size_t rows = (size_t)2 * batch * tokens_of_cfg(c), d = c.model_dim, ff = 2 * d;
-    Scratch s{};
-    size_t off = 0;
-    s.g1 = off;     off += al64(rows * d);
-    s.g2 = off;     off += al64(rows * d);
-    s.g2b = off;    off += al64(rows * d);   // d(out_proj output): g2 stays alive for linear2's weight gradient (batched at the end)
-    s.gff = off;    off += al64(rows * ff);
-    s.dqkv = off;   off += al64(rows * 3 * d);
-    s.dsum = off;   off += al64(rows * c.num_head);
-    // every gradient kernel of the layer keeps its partial slices until the single reduction launch at the end
+    const size_t rows = (size_t)2 * batch * tokens_of(c), d = c.model_dim, ff = 2 * d;
     const int r = (int)rows;
-    s.slices = off;
-    off += al64(gemm_tn_slice_floats(d, ff, r)) + al64(gemm_tn_slice_floats(ff, d, r)) + al64(gemm_tn_slice_floats(d, d, r)) +
-           al64(gemm_tn_slice_floats(3 * d, d, r)) + 2 * al64((size_t)ln_bwd_blocks(r) * 3 * d) +
-           al64((size_t)ln_bwd_blocks(r) * ff) + al64((size_t)colsum_slices(r) * 3 * d);
+    Scratch s{};
+    s.g1 = s.take(rows * d);
+    s.g2 = s.take(rows * d);
+    s.g2b = s.take(rows * d);   // d(out_proj output): g2 stays alive for linear2's weight gradient (batched at the end)
+    s.gff = s.take(rows * ff);
+    s.dqkv = s.take(rows * 3 * d);
+    s.dsum = s.take(rows * c.num_head);
+    s.sl_ln2 = s.take((size_t)ln_bwd_blocks(r) * 3 * d);
+    s.sl_w2 = s.take(gemm_tn_slice_floats(d, ff, r));
+    s.sl_act = s.take((size_t)ln_bwd_blocks(r) * ff);
+    s.sl_w1 = s.take(gemm_tn_slice_floats(ff, d, r));
+    s.sl_ln1 = s.take((size_t)ln_bwd_blocks(r) * 3 * d);
+    s.sl_wo = s.take(gemm_tn_slice_floats(d, d, r));
+    s.sl_wq = s.take(gemm_tn_slice_floats(3 * d, d, r));
+    s.sl_bq = s.take((size_t)colsum_slices(r) * 3 * d);
     // fused row-local backward (k_chain_bwd.hip): transposed fragment-packed weights, per-tile LayerNorm parameter sums
-    s.packed_t = off; off += al64(std::max(chain_bwd_packed_floats((int)d), packed_layer_floats((int)d)));   // also the forward chain's fp32 image
-    s.lnp = off;      off += al64(chain_bwd_lnp_floats(r, (int)d));
-    s.attn_pad = off; off += al64(attn_train_pad_floats(c, rows));    // head dim 16: padded-head images of qkv, o, d_o, dqkv
-    s.total = off;
+    s.packed_t = s.take(std::max(chain_bwd_packed_floats((int)d), packed_layer_floats((int)d)));   // also the forward chain's fp32 image
+    s.lnp = s.take(chain_bwd_lnp_floats(r, (int)d));
+    s.attn_pad = s.take(attn_train_pad_floats(c, rows));    // head dim 16: padded-head images of qkv, o, d_o, dqkv
+    return s;
+}
+
+// dense layer's backward: the weight gradient's split slices, the bias gradient's column-sum slices
+struct DenseScratch : Layout { size_t wgrad, colsum; };
+DenseScratch plan_dense_scratch(int rows, int in_f, int out_f) {
+    const int tiles = ((in_f + 127) / 128) * ((out_f + 127) / 128);
+    DenseScratch s{};
+    s.wgrad = s.take((size_t)gemm_split_slices(rows, tiles) * in_f * out_f);
+    s.colsum = s.take((size_t)colsum_slices(rows) * out_f);
+    return s;
+}
+
+// The training conv kernels address the saved activations and masks ([planes][32][T][S] for conv2) through buffer resources with
+// 32-bit byte offsets (conv_device.h): a launch takes at most this many planes, a call of more runs as consecutive launches
+// (0: not even one plane fits -- refused)
+int conv_train_chunk(int S, int T) {
+    const size_t per = (size_t)32 * S * T * sizeof(float);
+    return (int)std::min<size_t>((size_t)INT_MAX, (size_t)0x7fffffff / per);
+}
+// ConvEnhancer backward: the masked stage outputs g3 [8] | g2 [32] | g1 [8 channels] of one chunk of planes, back to back inside one
+// region sized for all planes' 48 channels, then the weight-gradient slices, the transposed weights and their 16x16x4 operand
+// fragments (default grid).  The forward's scratch is the fragment image alone.
+struct ConvScratch : Layout { size_t g3, g2, g1, slices, flip, frag; };
+ConvScratch plan_conv_scratch(int planes, int S, int T) {
+    const size_t st1 = (size_t)S * T, chunk8 = (size_t)std::min(conv_train_chunk(S, T), planes) * 8 * st1;
+    ConvScratch s{};
+    s.g3 = s.take((size_t)planes * 48 * st1);
+    s.g2 = s.g3 + chunk8;
+    s.g1 = s.g2 + 4 * chunk8;
+    s.slices = s.take(conv_wgrad_slice_floats(planes, S, T));
+    s.flip = s.take(kConvFlipFloats);
+    s.frag = s.take(kConvFragFloats);
     return s;
 }
 
@@ -75,18 +104,6 @@ uint32_t site_seed(uint64_t seed, uint32_t site) {
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return (uint32_t)(z ^ (z >> 31));
 }
-
-thread_local const char *g_step = "";
-int fail(hipError_t e) {
-    set_error("%s: %s", g_step, hipGetErrorString(e));
-    return AFT_ERR_HIP;
-}
-#define STEP(name, call)                     \
-    do {                                     \
-        g_step = name;                       \
-        hipError_t e_ = (call);              \
-        if (e_ != hipSuccess) return fail(e_); \
-    } while (0)
 
 int check_train(const aft_config *cfg, int batch, float dropout_p) {
     int rc = check_config(cfg);
@@ -98,7 +115,7 @@ int check_train(const aft_config *cfg, int batch, float dropout_p) {
     // head dim 32 is the kernels' own shape, 64 runs as two 32-feature blocks under one softmax (forward + the two-pass backward
     // instantiated for two blocks), every other multiple of 8 as zero-padded 32- or 64-feature heads (k_attn_train.hip); check_config
     // above has already refused what the inference engine does not take (head dims off the multiples of 8, 56, > 64)
-    if ((size_t)2 * batch * tokens_of_cfg(*cfg) * 3 * cfg->model_dim >= ((size_t)1 << 32)) {
+    if ((size_t)2 * batch * tokens_of(*cfg) * 3 * cfg->model_dim >= ((size_t)1 << 32)) {
         set_error("batch %d: dropout counters are 32-bit", batch);
         return AFT_ERR_ARG;
     }
@@ -141,9 +158,10 @@ int aft_encoder_layer_fwd_train_chained_f32(const aft_config *cfg, const aft_lay
         set_error("next_tape too small: %zu < %zu bytes (the linked layers share cfg and batch)", next_tape_bytes, t.total * sizeof(float));
         return AFT_ERR_ARG;
     }
+    AFT_HOST_ASSERT(check_layout(t, tape_bytes) && check_layout(s, scratch_bytes), "tape or scratch region outside its buffer");
     hipStream_t st = static_cast<hipStream_t>(stream);
     float *tp = static_cast<float *>(tape), *sc = static_cast<float *>(scratch);
-    const int tokens = tokens_of_cfg(*cfg), planes = 2 * batch, rows = planes * tokens, d = cfg->model_dim, ff = 2 * d;
+    const int tokens = tokens_of(*cfg), planes = 2 * batch, rows = planes * tokens, d = cfg->model_dim, ff = 2 * d;
     float *o = sc + s.g1;   // projection outputs before the residual joins
 
     if (!qkv_ready)   // (else the previous layer's row-local kernel already left this layer's in-projection in the tape)
@@ -212,26 +230,26 @@ int aft_encoder_layer_bwd_f32(const aft_config *cfg, const aft_layer_weights *w,
         set_error("tape or scratch too small");
         return AFT_ERR_ARG;
     }
+    AFT_HOST_ASSERT(check_layout(t, tape_bytes) && check_layout(s, scratch_bytes), "tape or scratch region outside its buffer");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const float *tp = static_cast<const float *>(tape);
     float *sc = static_cast<float *>(scratch);
-    const int tokens = tokens_of_cfg(*cfg), planes = 2 * batch, rows = planes * tokens, d = cfg->model_dim, ff = 2 * d;
+    const int tokens = tokens_of(*cfg), planes = 2 * batch, rows = planes * tokens, d = cfg->model_dim, ff = 2 * d;
     const bool acc = accumulate != 0;
-    float *g1 = sc + s.g1, *g2 = sc + s.g2, *g2b = sc + s.g2b, *gff = sc + s.gff, *dqkv = sc + s.dqkv, *sl = sc + s.slices;
-    const float *hd = tp + t.hd;
-
-    // slice storage per producer (bump-allocated from the scratch's slice region), one reduction launch at the end
-    float *sl_ln2 = sl;
-    float *sl_w2 = sl_ln2 + al64((size_t)ln_bwd_blocks(rows) * 3 * d);
-    float *sl_act = sl_w2 + al64(gemm_tn_slice_floats(d, ff, rows));
-    float *sl_w1 = sl_act + al64((size_t)ln_bwd_blocks(rows) * ff);
-    float *sl_ln1 = sl_w1 + al64(gemm_tn_slice_floats(ff, d, rows));
-    float *sl_wo = sl_ln1 + al64((size_t)ln_bwd_blocks(rows) * 3 * d);
-    float *sl_wq = sl_wo + al64(gemm_tn_slice_floats(d, d, rows));
-    float *sl_bq = sl_wq + al64(gemm_tn_slice_floats(3 * d, d, rows));
+    float *g1 = sc + s.g1, *g2 = sc + s.g2, *g2b = sc + s.g2b, *gff = sc + s.gff, *dqkv = sc + s.dqkv;
     ReduceBatchScope reductions;
     const uint32_t drop_th = dropout_p > 0.f ? (uint32_t)((double)dropout_p * 4294967296.0) : 0u;
     const float drop_ks = dropout_p > 0.f ? 1.f / (1.f - dropout_p) : 1.f;
+    // the layer's four weight gradients in ONE launch (dW2 = g2^T hd, dW1 = gff^T x1, dWo = g2b^T attn, dWqkv = dqkv^T x_in), then the
+    // single reduction launch.  bias_out[j] != NULL: + that bias gradient as the column sums of operand A_j, slices in bias_sl[j]
+    auto weight_grads = [&](float *const bias_out[4], float *const bias_sl[4]) -> int {
+        const float *A[4] = {g2, gff, g2b, dqkv}, *B[4] = {tp + t.hd, tp + t.x1, tp + t.attn, x_in};
+        float *C[4] = {g->lin2_w, g->lin1_w, g->out_proj_w, g->in_proj_w}, *S[4] = {sc + s.sl_w2, sc + s.sl_w1, sc + s.sl_wo, sc + s.sl_wq};
+        const int M[4] = {d, ff, d, 3 * d}, N[4] = {ff, d, d, d}, lda[4] = {d, ff, d, 3 * d}, ldb[4] = {ff, d, d, d};
+        STEP("weight gradients", launch_gemm_tn_batch(A, B, C, S, M, N, lda, ldb, 4, rows, acc, st, bias_out, bias_sl));
+        STEP("gradient reductions", reductions.flush(st));
+        return AFT_OK;
+    };
     if (chain_bwd_ok(*cfg, rows) && !switch_on(SW_TRAIN_UNFUSED_BWD)) {
         // everything row-local in ONE launch: dx_out -> g2, gff, g2b (operands of the weight gradients), g1 = d(attention
         // output), dx_in = the residual branch of dL/dx, per-tile LayerNorm parameter sums
@@ -245,19 +263,13 @@ int aft_encoder_layer_bwd_f32(const aft_config *cfg, const aft_layer_weights *w,
         STEP("attention bwd", launch_attn_train_bwd(*cfg, tp + t.qkv, tp + t.attn, g1, tp + t.lse, sc + s.dsum, dqkv, planes, tokens,
                                                     dropout_p, site_seed(seed, 0), st, sc + s.attn_pad));
         STEP("in_proj dgrad", launch_gemm(1, dqkv, w->in_proj_w, dx_in, nullptr, rows, d, 3 * d, 3 * d, d, d, true, st));
-        {   // the four weight gradients and all four bias gradients (column sums of the A operands) in one launch
-            const float *A[4] = {g2, gff, g2b, dqkv}, *B[4] = {hd, tp + t.x1, tp + t.attn, x_in};
-            float *C[4] = {g->lin2_w, g->lin1_w, g->out_proj_w, g->in_proj_w}, *S[4] = {sl_w2, sl_w1, sl_wo, sl_wq};
-            const int M[4] = {d, ff, d, 3 * d}, N[4] = {ff, d, d, d}, lda[4] = {d, ff, d, 3 * d}, ldb[4] = {ff, d, d, d};
-            float *bias_out[4] = {g->lin2_b, g->lin1_b, g->out_proj_b, g->in_proj_b};
-            float *bias_sl[4] = {sl_ln2, sl_act, sl_ln1, sl_bq};   // the LayerNorm slice regions are free on this path
-            STEP("weight gradients", launch_gemm_tn_batch(A, B, C, S, M, N, lda, ldb, 4, rows, acc, st, bias_out, bias_sl));
-        }
-        STEP("gradient reductions", reductions.flush(st));
-        return AFT_OK;
+        // all four bias gradients ride on the weight-gradient launch; the LayerNorm slice regions are free on this path
+        float *bias_out[4] = {g->lin2_b, g->lin1_b, g->out_proj_b, g->in_proj_b};
+        float *bias_sl[4] = {sc + s.sl_ln2, sc + s.sl_act, sc + s.sl_ln1, sc + s.sl_bq};
+        return weight_grads(bias_out, bias_sl);
     }
     // LN2: g1 = d(x1) through the residual, g2 = d(linear2 output) (dropout 3 applied)
-    STEP("norm2 bwd", launch_ln_bwd(dx_out, tp + t.s2, tp + t.st2, w->norm2_w, g1, g2, g->norm2_w, g->norm2_b, g->lin2_b, sl_ln2,
+    STEP("norm2 bwd", launch_ln_bwd(dx_out, tp + t.s2, tp + t.st2, w->norm2_w, g1, g2, g->norm2_w, g->norm2_b, g->lin2_b, sc + s.sl_ln2,
                                     rows, d, dropout_p, site_seed(seed, 3), acc, st));
     // linear2's data gradient with the activation backward as its epilogue (gff = d(linear1 output)); linear1's bias gradient
     // then rides on the batched weight-gradient launch below (column sums of gff)
@@ -267,37 +279,25 @@ int aft_encoder_layer_bwd_f32(const aft_config *cfg, const aft_layer_weights *w,
                                                                   drop_ks, drop_th, site_seed(seed, 2), st));
     } else {
         STEP("linear2 dgrad", launch_gemm(1, g2, w->lin2_w, gff, nullptr, rows, ff, d, d, ff, ff, false, st));
-        STEP("activation bwd", launch_act_bwd(cfg->activation, tp + t.a, gff, g->lin1_b, sl_act, rows, ff, dropout_p, site_seed(seed, 2),
+        STEP("activation bwd", launch_act_bwd(cfg->activation, tp + t.a, gff, g->lin1_b, sc + s.sl_act, rows, ff, dropout_p, site_seed(seed, 2),
                                               acc, st));
     }
     STEP("linear1 dgrad", launch_gemm(1, gff, w->lin1_w, g1, nullptr, rows, d, ff, ff, d, d, true, st));
     // LN1: dx_in = d(x_in) through the residual, g2b = d(out_proj output) (dropout 1 applied)
-    STEP("norm1 bwd", launch_ln_bwd(g1, tp + t.s1, tp + t.st1, w->norm1_w, dx_in, g2b, g->norm1_w, g->norm1_b, g->out_proj_b, sl_ln1,
+    STEP("norm1 bwd", launch_ln_bwd(g1, tp + t.s1, tp + t.st1, w->norm1_w, dx_in, g2b, g->norm1_w, g->norm1_b, g->out_proj_b, sc + s.sl_ln1,
                                     rows, d, dropout_p, site_seed(seed, 1), acc, st));
     STEP("out_proj dgrad", launch_gemm(1, g2b, w->out_proj_w, g1, nullptr, rows, d, d, d, d, d, false, st));
     STEP("attention bwd", launch_attn_train_bwd(*cfg, tp + t.qkv, tp + t.attn, g1, tp + t.lse, sc + s.dsum, dqkv, planes, tokens,
                                                 dropout_p, site_seed(seed, 0), st, sc + s.attn_pad));
     STEP("in_proj dgrad", launch_gemm(1, dqkv, w->in_proj_w, dx_in, nullptr, rows, d, 3 * d, 3 * d, d, d, true, st));
-    {   // the layer's four weight gradients in one launch: dW2 = g2^T hd, dW1 = gff^T x1, dWo = g2b^T attn, dWqkv = dqkv^T x_in
-        const float *A[4] = {g2, gff, g2b, dqkv}, *B[4] = {hd, tp + t.x1, tp + t.attn, x_in};
-        float *C[4] = {g->lin2_w, g->lin1_w, g->out_proj_w, g->in_proj_w}, *S[4] = {sl_w2, sl_w1, sl_wo, sl_wq};
-        const int M[4] = {d, ff, d, 3 * d}, N[4] = {ff, d, d, d}, lda[4] = {d, ff, d, 3 * d}, ldb[4] = {ff, d, d, d};
-        float *bias_out[4] = {nullptr, fused_act ? g->lin1_b : nullptr, nullptr, g->in_proj_b};   // db1 = gff^T 1, db_qkv = dqkv^T 1
-        float *bias_sl[4] = {nullptr, sl_act, nullptr, sl_bq};
-        STEP("weight gradients", launch_gemm_tn_batch(A, B, C, S, M, N, lda, ldb, 4, rows, acc, st, bias_out, bias_sl));
-    }
-    STEP("gradient reductions", reductions.flush(st));
-    return AFT_OK;
-}
-
-static size_t dense_slice_floats(int rows, int in_f, int out_f) {
-    const int tiles = ((in_f + 127) / 128) * ((out_f + 127) / 128);
-    return al64((size_t)gemm_split_slices(rows, tiles) * in_f * out_f) + al64((size_t)colsum_slices(rows) * out_f);
+    float *bias_out[4] = {nullptr, fused_act ? g->lin1_b : nullptr, nullptr, g->in_proj_b};   // db1 = gff^T 1, db_qkv = dqkv^T 1
+    float *bias_sl[4] = {nullptr, sc + s.sl_act, nullptr, sc + s.sl_bq};
+    return weight_grads(bias_out, bias_sl);
 }
 
 size_t aft_dense_bwd_scratch_bytes(int rows, int in_features, int out_features) {
     if (rows <= 0 || in_features <= 0 || out_features <= 0) return 0;
-    return sizeof(float) * dense_slice_floats(rows, in_features, out_features);
+    return plan_dense_scratch(rows, in_features, out_features).total * sizeof(float);
 }
 
 int aft_dense_fwd_f32(const float *x, const float *weight, const float *bias, float *y, int rows, int in_features,
@@ -315,17 +315,17 @@ int aft_dense_bwd_f32(const float *x, const float *weight, const float *dy, floa
         set_error("bad dense argument");
         return AFT_ERR_ARG;
     }
-    if (scratch_bytes < aft_dense_bwd_scratch_bytes(rows, in_features, out_features)) { set_error("dense scratch too small"); return AFT_ERR_ARG; }
+    const DenseScratch s = plan_dense_scratch(rows, in_features, out_features);
+    if (scratch_bytes < s.total * sizeof(float)) { set_error("dense scratch too small"); return AFT_ERR_ARG; }
+    AFT_HOST_ASSERT(check_layout(s, scratch_bytes), "dense scratch region outside its buffer");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    float *sl = static_cast<float *>(scratch);
-    const int tiles = ((in_features + 127) / 128) * ((out_features + 127) / 128);
-    float *sl2 = sl + al64((size_t)gemm_split_slices(rows, tiles) * in_features * out_features);
+    float *sc = static_cast<float *>(scratch);
     ReduceBatchScope reductions;
     if (dx) STEP("dense dgrad", launch_gemm(1, dy, weight, dx, nullptr, rows, in_features, out_features, out_features, in_features,
                                             in_features, false, st));
-    STEP("dense wgrad", launch_gemm_tn(dy, x, dweight, sl, out_features, in_features, rows, out_features, in_features,
+    STEP("dense wgrad", launch_gemm_tn(dy, x, dweight, sc + s.wgrad, out_features, in_features, rows, out_features, in_features,
                                        accumulate != 0, st));
-    if (dbias) STEP("dense bgrad", launch_colsum(dy, dbias, sl2, rows, out_features, out_features, accumulate != 0, st));
+    if (dbias) STEP("dense bgrad", launch_colsum(dy, dbias, sc + s.colsum, rows, out_features, out_features, accumulate != 0, st));
     STEP("gradient reductions", reductions.flush(st));
     return AFT_OK;
 }
@@ -398,25 +398,18 @@ int aft_tail_bwd_f32(const float *x, const float *w2, const float *d_out, float 
     return AFT_OK;
 }
 
-// The training conv kernels address the saved activations and masks ([planes][32][T][S] for conv2) through buffer resources with
-// 32-bit byte offsets (conv_device.h): a launch takes at most this many planes, a call of more runs as consecutive launches
-// (0: not even one plane fits -- refused)
-static int conv_train_chunk(int S, int T) {
-    const size_t per = (size_t)32 * S * T * sizeof(float);
-    return (int)std::min<size_t>((size_t)INT_MAX, (size_t)0x7fffffff / per);
-}
-
 size_t aft_conv_enhancer_scratch_bytes(int planes, int num_scs, int num_symbols) {
     if (planes <= 0 || num_scs <= 0 || num_symbols <= 0 || !conv_plan_ok(num_scs, num_symbols, 0)) return 0;
     if (conv_train_chunk(num_scs, num_symbols) < 1) return 0;
-    return sizeof(float) * (al64((size_t)planes * 48 * num_scs * num_symbols) + al64(conv_wgrad_slice_floats(planes, num_scs, num_symbols)) +
-                            al64(kConvFlipFloats) + al64(kConvFragFloats));
+    return plan_conv_scratch(planes, num_scs, num_symbols).total * sizeof(float);
 }
 
 size_t aft_conv_enhancer_fwd_scratch_bytes(int planes, int num_scs, int num_symbols) {
     if (planes <= 0 || num_scs <= 0 || num_symbols <= 0 || !conv_plan_ok(num_scs, num_symbols, 0)) return 0;
     if (conv_train_chunk(num_scs, num_symbols) < 1) return 0;
-    return sizeof(float) * al64(kConvFragFloats);
+    Layout s{};
+    s.take(kConvFragFloats);
+    return s.total * sizeof(float);
 }
 
 int aft_conv_enhancer_fwd_train_f32(const float *const weights[4], const float *const biases[4], const float *x, float *y,
@@ -454,13 +447,13 @@ int aft_conv_enhancer_bwd_f32(const float *const weights[4], const float *x, con
         set_error("ConvEnhancer scratch too small");
         return AFT_ERR_ARG;
     }
+    const ConvScratch s = plan_conv_scratch(planes, num_scs, num_symbols);
+    AFT_HOST_ASSERT(check_layout(s, scratch_bytes), "ConvEnhancer scratch region outside its buffer");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int chunk = conv_train_chunk(num_scs, num_symbols);    // (> 0: the scratch size says so)
-    const size_t st1 = (size_t)num_scs * num_symbols, plane8 = (size_t)planes * 8 * st1, chunk8 = (size_t)std::min(chunk, planes) * 8 * st1;
-    float *g3 = static_cast<float *>(scratch), *g2 = g3 + chunk8, *g1 = g2 + 4 * chunk8;
-    float *slices = static_cast<float *>(scratch) + al64(6 * plane8);
-    float *flip = slices + al64(conv_wgrad_slice_floats(planes, num_scs, num_symbols));
-    float *frag = flip + al64(kConvFlipFloats);      // the flipped weights as 16x16x4 operand fragments (default grid)
+    const size_t st1 = (size_t)num_scs * num_symbols;
+    float *sc = static_cast<float *>(scratch);
+    float *flip = sc + s.flip, *frag = sc + s.frag, *slices = sc + s.slices, *g3 = sc + s.g3, *g2 = sc + s.g2, *g1 = sc + s.g1;
     // dgrad: the stack run on dy with conv4^T (1->8), conv3^T (8->32), conv2^T (32->8), conv1^T (8->1);
     // stage outputs masked by the saved activations = g3, g2, g1
     STEP("conv weight transposition", launch_conv_flip_weights(weights, flip, st));

@@ -4,12 +4,13 @@ item 8; GPU AddressSanitizer is not available on the pool).
 ``libaft_hip_check.so`` = the same sources with -DAFT_CHECKED=1 (``python -m adafortitran_amd.build --variant check -DAFT_CHECKED=1``,
 built by ``__graft_entry__.build()``): slot / ring-offset asserts and ring-occupancy tags in the wave-specialised conv pipelines
 (k_conv_stream.hip, k_conv_rows.hip), the LDS-flag hand-overs published BEHIND a release fence (the product publishes without one and
-relies on gfx950 serving a wave's LDS requests in issue order), polls that trap instead of hanging, workspace-plan invariants in
-aft_api.hip.  A violated assert is ``__builtin_trap`` -> the launch faults and the next synchronisation raises.
+relies on gfx950 serving a wave's LDS requests in issue order), polls that trap instead of hanging, and the layout invariants of every
+caller-owned buffer a call carves up (workspace, training tape and scratch: aft_internal.h check_layout).  A violated assert is ``__builtin_trap`` -> the launch faults and the next synchronisation raises.
 
 What is tested: the soak of the conv hand-overs and ten random configurations (both engines) run through the checked build without a
 fault, and every output has the product build's BITS -- so the fences the product leaves out change nothing.
 """
+import ctypes as C
 import os
 
 import numpy as np
@@ -113,3 +114,42 @@ def test_lanes_plan_invariants_on_the_checked_build(checked):
         pil, meta = _t(inp["pilots"]), [_t(inp[k]) for k in ("snr", "ds", "dop")]
         assert torch.equal(torch.view_as_real(chk.forward(pil, *meta)), torch.view_as_real(prod.forward(pil, *meta)))
     torch.cuda.synchronize()
+
+
+def _layer_step(lib, cfg, params, x, gout):
+    """One encoder layer's training forward and backward (dropout 0.1) through ``lib``: x_out, dx_in and the twelve parameter gradients."""
+    from adafortitran_amd.training import _layer_struct
+    batch, st = x.shape[0] // 2, _lib.current_stream_ptr(x.device)
+    tape = torch.empty(lib.aft_encoder_tape_bytes(C.byref(cfg), batch), dtype=torch.uint8, device=DEV)
+    scratch = torch.empty(lib.aft_encoder_train_scratch_bytes(C.byref(cfg), batch), dtype=torch.uint8, device=DEV)
+    out, dx, grads = torch.empty_like(x), torch.empty_like(x), [torch.empty_like(p) for p in params]
+    w, g = _layer_struct(_abi.AftLayerWeights, params), _layer_struct(_abi.AftLayerGrads, grads)
+    rc = lib.aft_encoder_layer_fwd_train_f32(C.byref(cfg), C.byref(w), x.data_ptr(), out.data_ptr(), tape.data_ptr(), tape.numel(),
+                                             scratch.data_ptr(), scratch.numel(), batch, 0.1, 77, st)
+    assert rc == _abi.AFT_OK, lib.aft_last_error()
+    rc = lib.aft_encoder_layer_bwd_f32(C.byref(cfg), C.byref(w), x.data_ptr(), tape.data_ptr(), tape.numel(), gout.data_ptr(), dx.data_ptr(),
+                                       C.byref(g), 0, scratch.data_ptr(), scratch.numel(), batch, 0.1, 77, st)
+    assert rc == _abi.AFT_OK, lib.aft_last_error()
+    return [out, dx] + grads
+
+
+def test_encoder_layer_training_on_the_checked_build(checked):
+    """The tiny configuration (12 x 4 grid, 8 tokens: a 32-row tile spans planes; model_dim 16, 2 heads) through the encoder layer's
+    training forward and backward at batch 1 and 3: the checked build walks the tape's and the scratch's layout on both calls
+    (AFT_OK = every region in order, on a 256-byte boundary, inside the caller's buffer), and the output and every gradient have the
+    product build's bits."""
+    cfg = _abi.make_config(ofdm=(12, 4), pilot=(4, 2), patch=(3, 2), num_layers=2, model_dim=16, num_head=2, adaptive_hidden=(3, 5, 16))
+    d, tokens = 16, 8
+    gen = torch.Generator().manual_seed(11)
+    shapes = [(3 * d, d), (3 * d,), (d, d), (d,), (2 * d, d), (2 * d,), (d, 2 * d), (d,), (d,), (d,), (d,), (d,)]   # _abi.LAYER_FIELDS order
+    params = [(torch.randn(s, generator=gen) * (0.3 if len(s) == 2 else 0.1) + (1.0 if i in (8, 10) else 0.0)).to(DEV)
+              for i, s in enumerate(shapes)]
+    prod = _lib.load()
+    for batch in (1, 3):
+        x = torch.randn(2 * batch, tokens, d, generator=gen).to(DEV)
+        gout = torch.randn(2 * batch, tokens, d, generator=gen).to(DEV)
+        want = _layer_step(prod, cfg, params, x, gout)
+        got = _layer_step(checked, cfg, params, x, gout)
+        torch.cuda.synchronize()
+        for i, (a, b) in enumerate(zip(got, want)):
+            assert torch.isfinite(b).all() and torch.equal(a, b), (batch, i)
