@@ -2,7 +2,8 @@
 drop_keep), restated in numpy: element (q, k) is kept when the low 32 bits of row_word(q) * col_word(k) (two odd
 24-bit words) reach p * 2^32.  The reference draws the mask from torch's Philox stream
 (torch.nn.MultiheadAttention(dropout=p), reference src/models/blocks/encoders.py:44-55); what must carry over is
-the distribution: keep rate 1-p and no correlation along rows, columns or across 2x2 rectangles."""
+the distribution: keep rate 1-p and no correlation along rows, columns or across 2x2 rectangles.
+That the kernels produce exactly this mask: tests/test_train_dropout.py::test_kernel_masks_are_the_restated_masks."""
 import numpy as np
 import pytest
 
