@@ -182,6 +182,8 @@ SIGNATURES = {
     "aft_get_switch": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t]),
     "aft_max_batch": (C.c_int, [cfgp]),
     "aft_workspace_bytes": (C.c_size_t, [cfgp, C.c_int]),
+    "aft_workspace_bytes_layer_fused": (C.c_size_t, [cfgp, C.c_int]),
+    "aft_layer_fused_of": (C.c_int, [cfgp, C.c_int]),
     "aft_workspace_lanes": (C.c_int, [cfgp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
     "aft_workspace_region": (C.c_int, [cfgp, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "aft_forward_f32": (C.c_int, [cfgp, wp, vp, vp, vp, vp, vp, vp, C.c_size_t, C.c_int, vp]),

@@ -282,6 +282,29 @@ static double round_efficiency(long n, long slots) {
     const long rounds = (n + slots - 1) / std::max<long>(slots, 1);
     return rounds > 0 ? (double)n / (double)(rounds * slots) : 1.0;
 }
+// ---- the fused layer sequence (k_layer.hip) ----
+// One launch per layer on plane-aligned row tiles.  It runs for a whole forward of `batch` frames (one lane's share) when the shape is
+// instantiated (layer_fused_ok), the caller left the encoder path to the library, and plane alignment adds no ROUND to the persistent
+// chain grid: planes x ceil(tokens / 32) tiles take no more rounds of 3 x CUs workgroups than the ceil(rows / 32) global tiles (the
+// default model at 128 frames: 2 304 = 3 x 768 tiles against 2 240, three rounds either way; at 129 frames 2 322 tiles would be a fourth).
+// AFT_LAYER_FUSED: 0 = never, anything else = wherever the shape is instantiated (the A/B lever).
+// What the fused sequence needs BEYOND the workspace plan, per lane of `frames` frames: x on plane-aligned tiles (planes x tokpad rows)
+// and the second V^T buffer (K and V^T alternate between two buffers from layer to layer, k_layer.hip; the second K buffer is the
+// plan's `attn`, idle there and never smaller than a q / k / v^T block).  These two blocks are laid BEHIND the planned slices of all
+// lanes, so every planned offset (aft_workspace_lanes, aft_workspace_region) holds whichever sequence runs; a caller opts in by passing
+// a workspace of aft_workspace_bytes_layer_fused, and a smaller one (>= aft_workspace_bytes) runs the launches.
+static size_t layer_ext_floats(const aft_config &c, int frames) {
+    const size_t block = (size_t)2 * frames * round_up(tokens_of(c), kTile) * c.model_dim;
+    return 2 * ((block + 63) / 64 * 64);
+}
+static long round_count(long n, long slots) { return (n + slots - 1) / std::max<long>(slots, 1); }
+static bool layer_fused_selected(const aft_config &c, int batch) {
+    if (!layer_fused_ok(c) || c.encoder_path != AFT_ENCODER_AUTO) return false;
+    if (switch_on(SW_LAYER_FUSED)) return switch_int(SW_LAYER_FUSED, 1) != 0;
+    const long tokens = tokens_of(c), planes = 2L * batch, slots = 3L * current_device_cus();
+    return round_count(planes * ((tokens + kTile - 1) / kTile), slots) <= round_count((planes * tokens + kTile - 1) / kTile, slots);
+}
+
 static int lanes_wanted(const aft_config &c, int batch) {
     if (!packed_engine_ok(c)) return 1;         // the general engine's launches are dispatcher-scheduled grids, not persistent rounds
     if (switch_on(SW_LANES)) {               // A/B switch: 1 = never split, 2 .. 4 = always that many shares
@@ -295,6 +318,8 @@ static int lanes_wanted(const aft_config &c, int batch) {
     const long chain_slots = cus * (c.model_dim <= 128 ? 3 : 1);                                  // k_chain.hip: workgroups per CU
     const long attn_slots = cus * 4 * ((hd == 64 || hd == 24 || hd == 40 || hd == 48) ? 2 : 3);   // k_attn.hip: waves per SIMD
     const long attn_tasks = planes * c.num_head * ((tokens + 31) / 32);
+    if (layer_fused_selected(c, batch))     // one lane would run the fused layers: attention and chain share the plane-aligned tiles' rounds
+        return 0.90 * round_efficiency(planes * ((tokens + 31) / 32), chain_slots) + 0.10 * round_efficiency(planes, cus) >= 0.97 ? 1 : 2;
     const double eff = 0.55 * round_efficiency(tiles, chain_slots) + 0.35 * round_efficiency(attn_tasks, attn_slots) +
                        0.10 * round_efficiency(planes, cus);
     return eff >= 0.97 ? 1 : 2;
@@ -409,7 +434,8 @@ static ChainFusion chain_fusion_for(ChainPos pos, const aft_config &c, const Wei
 // `w`: the non-layer pointers (+ a window of the first layers for the kernels that take the table by value); `layers`: the HOST array
 // of all num_layers layers.
 static int run_encoder(const aft_config &c, const WeightsDev &w, const aft_layer_weights *layers, const Workspace &ws, float *base, float *x,
-                       int first_layer, int last_layer, hipStream_t st, bool fused = false, const float *prepacked = nullptr) {
+                       int first_layer, int last_layer, hipStream_t st, bool fused = false, const float *prepacked = nullptr,
+                       float *layer_ext = nullptr) {
     float *attn = base + ws.attn, *q = base + ws.q, *k = base + ws.k, *vt = base + ws.vt;
     const int rows = ws.planes * ws.tokens;
     const size_t pl = packed_layer_floats(c.model_dim);
@@ -427,6 +453,22 @@ static int run_encoder(const aft_config &c, const WeightsDev &w, const aft_layer
     }
     const ChainFusion first = chain_fusion_for(kChainFirst, c, w, ws, base), middle = chain_fusion_for(kChainMiddle, c, w, ws, base),
                       last = chain_fusion_for(kChainLast, c, w, ws, base);
+    // whole forward on the workspace's own x: one launch per layer on plane-aligned tiles where layer_fused_selected says so.
+    // Layer l reads K / V^T buffer l & 1 and writes the other one ((k, vt) | (attn, vt2)).
+    // `layer_ext`: the lane's two blocks behind the planned slices (layer_ext_floats), NULL when the caller's workspace has no room
+    if (fused && layer_ext != nullptr && x == base + ws.x && first_layer == 0 && last_layer == c.num_layers - 1 &&
+        layer_fused_selected(c, ws.planes / 2)) {
+        x = layer_ext;                                             // plane-aligned tiles: planes x tokpad rows
+        float *kbuf[2] = {k, attn}, *vbuf[2] = {vt, layer_ext + layer_ext_floats(c, ws.planes / 2) / 2};
+        STEP("chain(qkv, plane tiles)", launch_chain_plane_tiles(c, &layers[0], wp, x, q, kbuf[0], vbuf[0], ws.planes, ws.tokens, ws.tokpad, st, &first));
+        for (int l = 0; l <= last_layer; ++l) {
+            const bool more = l < last_layer;
+            STEP("layer", launch_layer(c, &layers[l], wp + l * pl, more ? &layers[l + 1] : nullptr, more ? wp + (l + 1) * pl : nullptr, x, q,
+                                       kbuf[l & 1], vbuf[l & 1], kbuf[(l + 1) & 1], vbuf[(l + 1) & 1], ws.planes, ws.tokens, ws.tokpad, st,
+                                       more ? &middle : &last));
+        }
+        return AFT_OK;
+    }
     // in-projection of the first layer (QKV-only pass of the chain kernel)
     STEP("chain(qkv)", launch_chain(c, nullptr, nullptr, &layers[first_layer], wp + first_layer * pl, nullptr, x, q, k, vt, rows,
                                     ws.tokens, ws.tokpad, st, fused ? &first : nullptr));
@@ -542,6 +584,27 @@ int aft_workspace_region(const aft_config *cfg, int batch, int region, size_t *o
     return AFT_OK;
 }
 
+size_t aft_workspace_bytes_layer_fused(const aft_config *cfg, int batch) {
+    if (check_config(cfg) != AFT_OK || batch <= 0) return 0;
+    size_t floats = workspace_floats_any_lanes(*cfg, batch);
+    if (layer_fused_ok(*cfg)) {    // whatever split lanes_wanted() picks at call time: its blocks are no larger than these
+        size_t ext = 0;
+        for (int l = 1; l <= kMaxLanes; ++l) {
+            const LanePlan lp = plan_lanes(*cfg, batch, l);
+            size_t e = 0;
+            for (int i = 0; i < lp.lanes; ++i) e += layer_ext_floats(*cfg, lp.frames[i]);
+            ext = std::max(ext, e);
+        }
+        floats += ext;
+    }
+    return floats * sizeof(float);
+}
+
+int aft_layer_fused_of(const aft_config *cfg, int batch) {
+    if (check_config(cfg) != AFT_OK || batch <= 0) return -1;
+    return layer_fused_selected(*cfg, batch) ? 1 : 0;
+}
+
 int aft_workspace_lanes(const aft_config *cfg, int batch, int *lanes, int *frames, size_t *offset_bytes) {
     int rc = check_config(cfg);
     if (rc != AFT_OK) return rc;
@@ -569,7 +632,7 @@ int aft_workspace_lanes(const aft_config *cfg, int batch, int *lanes, int *frame
 
 // one share of the batch: a complete forward on `st` in its own workspace slice
 static int forward_lane(const aft_config *cfg, const aft_weights *w, const float *prepacked, const float *pilots, const float *snr,
-                        const float *ds, const float *dop, float *out, float *base, int batch, hipStream_t st) {
+                        const float *ds, const float *dop, float *out, float *base, int batch, hipStream_t st, float *layer_ext) {
     const Workspace ws = plan_workspace(*cfg, batch);
     const bool general = !packed_engine_ok(*cfg);
     const WeightsDev wd = weights_window(*w, 0, cfg->num_layers);
@@ -588,7 +651,7 @@ static int forward_lane(const aft_config *cfg, const aft_weights *w, const float
     // packed engine: patch embedding + linear_1 + positions run inside the first chain launch, linear_2 inside the last one
     const int rc = general ? run_encoder_general(*cfg, wd, w->layers, ws, base, batch, st)
                            : run_encoder(*cfg, wd, w->layers, ws, base, base + ws.x, 0, cfg->num_layers - 1, st, true,
-                                         prepacked != nullptr ? prepacked : wpack);
+                                         prepacked != nullptr ? prepacked : wpack, layer_ext);
     if (rc != AFT_OK) return rc;
     STEP("tail", launch_tail(*cfg, wd, nullptr, base + ws.conv_enhanced, out, batch, st, base + ws.out6, base + ws.convfrag + kConvFragFloats));
     return AFT_OK;
@@ -635,12 +698,20 @@ static int forward_impl(const aft_config *cfg, const aft_weights *w, const float
         AFT_HOST_ASSERT(covered == batch, "lane shares do not cover the batch");
     }
 #endif
+    // the fused layer sequence's blocks, lane after lane behind the planned slices -- when the caller's workspace holds them
+    size_t ext_off[kMaxLanes], ext_end = lp.total;
+    for (int i = 0; i < lp.lanes; ++i) {
+        ext_off[i] = ext_end;
+        ext_end += layer_ext_floats(*cfg, lp.frames[i]);
+    }
+    const bool have_ext = layer_fused_ok(*cfg) && workspace_bytes >= ext_end * sizeof(float);
     int result = AFT_OK;
     for (int i = 0; i < lp.lanes; ++i) {
         const int f0 = lp.first[i];
         const int rc_lane = forward_lane(cfg, w, prepacked, pilots + (size_t)f0 * pil_floats, snr ? snr + f0 : nullptr, ds ? ds + f0 : nullptr,
                                          dop ? dop + f0 : nullptr, out + (size_t)f0 * out_floats, static_cast<float *>(workspace) + lp.ws_off[i],
-                                         lp.frames[i], i == 0 || ls == nullptr ? user : ls->side[i - 1]);
+                                         lp.frames[i], i == 0 || ls == nullptr ? user : ls->side[i - 1],
+                                         have_ext ? static_cast<float *>(workspace) + ext_off[i] : nullptr);
         if (rc_lane != AFT_OK && result == AFT_OK) result = rc_lane;     // keep going: the join below must still happen
     }
     if (ls != nullptr) {

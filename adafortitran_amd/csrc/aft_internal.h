@@ -298,6 +298,18 @@ hipError_t launch_chain(const aft_config &c, const aft_layer_weights *mlp_w, con
                         float *q, float *k, float *vt, int rows, int tokens, int tokpad, hipStream_t st,
                         const ChainFusion *fuse = nullptr);
 size_t packed_layer_floats(int d);
+// The fused layer sequence (k_layer.hip): one launch per encoder layer on PLANE-ALIGNED row tiles (x: planes x
+// ceil(tokens / 32) whole tiles, tile-blocked).  layer_fused_ok: the shape is instantiated (fp32, d = 128, head dimension 32, >= 32 tokens).
+//   launch_chain_plane_tiles: embedding + layer 0's in-projection (launch_chain's first launch on those tiles; `fuse` as there)
+//   launch_layer: attention of layer `mlp_w` on q / k_in / vt_in, its row-local chain, and the in-projection of `qkv_w` (NULL: last
+//     layer, linear_2 into fuse->out6) into q (in place: a tile's queries are read and re-written by the same wave) / k_out / vt_out,
+//     which must not be k_in / vt_in: other workgroups still read those
+bool layer_fused_ok(const aft_config &c);
+hipError_t launch_chain_plane_tiles(const aft_config &c, const aft_layer_weights *qkv_w, const float *qkv_packed, float *x, float *q,
+                                    float *k, float *vt, int planes, int tokens, int tokpad, hipStream_t st, const ChainFusion *fuse);
+hipError_t launch_layer(const aft_config &c, const aft_layer_weights *mlp_w, const float *mlp_packed, const aft_layer_weights *qkv_w,
+                        const float *qkv_packed, float *x, float *q, const float *k_in, const float *vt_in, float *k_out, float *vt_out,
+                        int planes, int tokens, int tokpad, hipStream_t st, const ChainFusion *fuse);
 // Plane-resident encoder (k_encoder.hip): embedding + all layers + linear_2 of every plane in ONE launch, one 12-wave
 // workgroup per plane.  encoder_plane_ok: the shape is instantiated (d = 128).
 bool encoder_plane_ok(const aft_config &c);

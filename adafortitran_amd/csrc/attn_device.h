@@ -143,12 +143,16 @@ __device__ __forceinline__ float round_to_bf16(float x) { return (float)(__bf16)
 // would split a fragment slot: refused by aft_check_config.
 // TOK > 0: the token count as a compile-time constant (the default grid's 280: nine key tiles, the last one ragged) -- the tile loop's
 // trip count, the "last two or three tiles" logic and the padding masks resolve at compile time.  TOK = 0: any count at run time.
-template <bool BS = false, int HD = 32, int TOK = 0>
+// SINK (layer_kernel, k_layer.hip): the normalised O^T fragments of the task go to `sink` [s][lane][4] (the calling wave's block of an
+// LDS exchange buffer) instead of the attention tiles in memory -- ALL 32 rows: a row past the plane's end holds the result of a zero
+// query (finite, a function of the plane's own V), and the consumer drops it.
+template <bool BS = false, int HD = 32, int TOK = 0, bool SINK = false>
 __device__ __forceinline__ void attn_body(const float *__restrict__ q, const float *__restrict__ k,
                                           const float *__restrict__ vt, const float *__restrict__ qbias,
                                           float *__restrict__ out, int nblk, int tokens_rt, int tokpad_rt, int model_dim,
                                           float scale_log2e, const int first_task, const int total_waves, int ntasks,
-                                          unsigned long long *stamps, const int tail_task = -1) {
+                                          unsigned long long *stamps, const int tail_task = -1, float *sink = nullptr) {
+    static_assert(!SINK || (!BS && HD == 32), "the LDS sink is instantiated for the fp32 head-dimension-32 body");
     int lane_l = threadIdx.x & 63;
     asm volatile("" : "+v"(lane_l));   // laundered: lane-dependent offsets are recomputed per call, not hoisted out of the caller's loops
     const int lane = lane_l;
@@ -255,7 +259,7 @@ __device__ __forceinline__ void attn_body(const float *__restrict__ q, const flo
     };
 
   // wave priority by work left (set_progress_priority, aft_internal.h): keeps the waves of a SIMD abreast
-  const int rounds = (ntasks + total_waves - 1) / total_waves + (tail_task >= 0 ? 1 : 0);
+  const int rounds = SINK ? 1 : (ntasks + total_waves - 1) / total_waves + (tail_task >= 0 ? 1 : 0);
   int round = 0;
   int task = first_task < ntasks ? first_task : tail_task;     // -1: nothing to do
   f32x4 qreg[NQ][4], kcur[NQ][4], vcur[NB][4];
@@ -276,7 +280,8 @@ __device__ __forceinline__ void attn_body(const float *__restrict__ q, const flo
     const unsigned hb = head_base(task);   // byte offset of this (plane, block)
     const unsigned vb1 = second_block_bytes(task);
     // the strided tasks of the whole rounds, then (at most) one task of the partial round
-    const int next_task = task >= ntasks ? -1 : (task + total_waves < ntasks ? task + total_waves : tail_task);
+    // (SINK: one task per call and no hand-over -- a chain tile lies between two tasks of a wave, k_layer.hip)
+    const int next_task = SINK || task >= ntasks ? -1 : (task + total_waves < ntasks ? task + total_waves : tail_task);
     const bool has_next = next_task >= 0;
 
     // B operand of S^T = K Q^T : lane (q = r, h) holds Q[q][8s + 4h + j]; the query bias of the
@@ -422,6 +427,13 @@ __device__ __forceinline__ void attn_body(const float *__restrict__ q, const flo
     float l_run = st.lsum2[0] + st.lsum2[1];
     l_run += other_half(l_run);
     const int qrow = qt * kTile + r;
+    if constexpr (SINK) {
+        const float inv = 1.0f / l_run;
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+            *reinterpret_cast<f32x4 *>(sink + g * 256 + lane * 4) =
+                f32x4{st.oacc[0][4 * g] * inv, st.oacc[0][4 * g + 1] * inv, st.oacc[0][4 * g + 2] * inv, st.oacc[0][4 * g + 3] * inv};
+    } else
     if (qrow < tokens) {
         const float inv = 1.0f / l_run;
         const int plane = pb / nblk, blk = pb % nblk;

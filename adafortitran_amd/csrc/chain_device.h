@@ -76,7 +76,16 @@ struct ChainArgs {
     const float *emb_conv, *emb_tok6, *emb_w1, *emb_b1, *emb_pos;   // [planes][S][T], [frames][tokens][6] or NULL, [D][K], [D], [>=tokens][D]
     int emb_S, emb_T, emb_p0, emb_p1, emb_K;                          // K = p0*p1 (+6 with adapter tokens)
     unsigned long long *stamps;  // diagnostic build only (AFT_DIAG_STAMPS), else NULL
+    // plane-tile mode (chain_body<..., PT = true>: the fused layer sequence, k_layer.hip) only: row tiles per plane, ceil(tokens / 32).
+    // Tile t is (plane t / tpp, query tile t % tpp): no tile straddles a plane; the last tile of a plane holds tokens - 32 (tpp - 1)
+    // valid rows.  x holds planes x tpp whole tiles in that numbering; out6 keeps its global rows.
+    int tpp;
 };
+
+// host (k_chain.hip): the arguments of a chain launch from the launcher's parameters (launch_chain's own, aft_internal.h); tpp stays 0
+ChainArgs make_chain_args(const aft_config &c, const aft_layer_weights *mlp_w, const float *mlp_packed, const aft_layer_weights *qkv_w,
+                          const float *qkv_packed, const float *attn, float *x, float *q, float *k, float *vt, int rows, int tokens,
+                          int tokpad, const ChainFusion *fuse);
 
 // Weight-fragment ring of one wave: PF+1 k-blocks (32 deep) x NT tiles x 4 k-steps.
 // Packed layout (pack_weights_kernel): [tile][k-block][s][lane][4] so ONE global_load_dwordx4 of a
@@ -257,6 +266,11 @@ __device__ __forceinline__ f32x16 bias_acc(Srd bias, int f0, int h) {
 #define STAMP(i) do { } while (0)
 #endif
 
+// What a tile does before its chain (chain_body's `pre`): nothing in the launch sequence; the tile's attention in layer_kernel.
+struct ChainNoPre {
+    __device__ __forceinline__ void operator()(int) const {}
+};
+
 // MLP / QKV select the three launch variants at compile time (distinct symbols in a profile):
 //   <true,true>  layer l's out-proj+LN1+FFN+LN2 and layer l+1's in-projection   (5 of 7 launches at L=6)
 //   <false,true> in-projection only (first layer)      <true,false> last layer, no in-projection
@@ -265,11 +279,16 @@ __device__ __forceinline__ f32x16 bias_acc(Srd bias, int f0, int h) {
 // of three groups of a 12-wave workgroup in the plane-resident encoder kernel (k_encoder.hip).  __syncthreads() is the
 // only cross-wave synchronisation, so every group of a workgroup must walk the same NUMBER of tiles (tiles past the
 // last row are computed on clamped rows and never stored).
-template <int D, int ACT, bool MLP, bool QKV, bool BS = false>
+// PT (k_layer.hip): PLANE-ALIGNED tiles (ChainArgs::tpp), tile_end = planes x tpp.  Rows past the plane's end are computed on the clamped
+// last valid row's inputs and never stored.  x is tile-blocked.  With MLP, `pre(tile)` has left the tile's attention output -- all W
+// feature blocks, operand-fragment order -- in the UPPER half of the hidden buffer, behind a workgroup barrier, and the
+// out-projection takes its B operands from there: nothing is read from `a.attn`.
+template <int D, int ACT, bool MLP, bool QKV, bool BS = false, bool PT = false, class Pre = ChainNoPre>
 __device__ __forceinline__ void chain_body(const ChainArgs &a, float *smem, const int tid_in, const int first_tile,
-                                           const int tile_stride, const int tile_end) {
+                                           const int tile_stride, const int tile_end, Pre pre = Pre{}) {
     using S = ChainShape<D>;
     constexpr int W = S::WAVES;
+    static_assert(!PT || !BS, "plane-aligned tiles are instantiated for the fp32 body");
     // laundered: everything derived from the thread index is (re)computed inside this body.  In k_encoder.hip the body
     // sits inside a plane loop and a layer loop; LICM hoisted a dozen lane-dependent offsets to the top of the kernel,
     // where they were spilled at once and reloaded from scratch at every tile start (a scratch reload drains vmcnt).
@@ -280,9 +299,9 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, float *smem, cons
     float *stats = hb + S::HB;     // LayerNorm partials
     float *par = stats + S::ST;    // g1 | be1 | g2 | be2
 
-    const int lane = tid & 63;
+    int lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave = feature block = head
-    const int r = lane & 31, h = lane >> 5;
+    int r = lane & 31, h = lane >> 5;                         // (assigned once, but for PT with MLP: re-derived behind `pre`, below)
     const int fb = 32 * w;                                    // first feature of this wave's block
 
     const Srd srd_wo = make_srd(a.wo), srd_w1 = make_srd(a.w1), srd_w2 = make_srd(a.w2), srd_wq = make_srd(a.wqkv);
@@ -338,6 +357,7 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, float *smem, cons
 #endif
     constexpr int PFK = MLP ? (AFT_CHAIN_PFK < W ? AFT_CHAIN_PFK : W) : 0;
     constexpr bool AHEAD = AFT_CHAIN_PFK > 0;
+    static_assert(!PT || !AHEAD, "plane-aligned tiles request a tile's operands at the tile's start");
     f32x4 of[MLP ? W : 1][4], xres[4];
     auto request_attn = [&](int t, int kb0, int kb1) {
         const unsigned ap = ((unsigned)t * W * 1024 + lane * 4) * 4;
@@ -346,6 +366,12 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, float *smem, cons
 #pragma unroll
             for (int s = 0; s < 4; ++s)
                 if (kb >= kb0 && kb < kb1) of[kb][s] = srd_load_c(srd_attn, ap, (unsigned)(kb * 1024 + s * 256) * 4);
+    };
+    // PT: lanes of rows past the plane's end take the last valid row's lane (pad rows of x are never written, so never read)
+    auto request_x_pt = [&](int t, int valid) {
+        const unsigned xr = ((unsigned)t * 32 * D + w * 1024 + (min(r, valid - 1) + 32 * h) * 4) * 4;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) xres[s] = srd_load(srd_x, xr + 1024 * s);
     };
     auto request_x = [&](int t) {
         if (a.x_blocked) {
@@ -370,8 +396,15 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, float *smem, cons
     f32x16 emb_acc0;
     float emb_bv[kEmbSteps];
     auto emb_request = [&](int t) {
-        const int grow_n = min(t * 32 + r, a.rows - 1);
-        const int plane = grow_n / a.tokens, tok = grow_n - plane * a.tokens;
+        int plane, tok;
+        if constexpr (PT) {
+            plane = t / a.tpp;
+            tok = min((t - plane * a.tpp) * 32 + r, a.tokens - 1);
+        } else {
+            const int grow_n = min(t * 32 + r, a.rows - 1);
+            plane = grow_n / a.tokens;
+            tok = grow_n - plane * a.tokens;
+        }
         const int tpr = a.emb_T / a.emb_p1, g = tok / tpr, tc = tok - g * tpr;
         const float *cplane = a.emb_conv + ((size_t)plane * a.emb_S + g * a.emb_p0) * a.emb_T + tc * a.emb_p1;
         const float *t6 = a.emb_tok6 ? a.emb_tok6 + ((size_t)(plane >> 1) * a.tokens + tok) * 6 : nullptr;
@@ -397,10 +430,10 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, float *smem, cons
     }
     // linear_2 partials of the previous tile (fused variant of <MLP,!QKV>): sum the W per-wave partials in wave order, add
     // the bias, store [row][out6_stride].  Called by ONE wave per tile, after the barrier that ended that tile.
-    int pending_row0 = -1;
+    int pending_row0 = -1, pending_valid = 0;    // (PT: out6 row of the tile's first row, its valid rows)
     auto reduce_out6 = [&]() {
         const int P = a.out6_features;
-        if (pending_row0 + r < a.rows) {
+        if (PT ? r < pending_valid : pending_row0 + r < a.rows) {
 #pragma unroll
             for (int half = 0; half < 2; ++half) {      // features 4h + {0..3} (half 0), 8 + 4h + {0..3} (half 1)
                 const int f0 = 8 * half + 4 * h;
@@ -423,6 +456,16 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, float *smem, cons
     if constexpr (MLP && !QKV) {
         if (pending_row0 >= 0 && w == (round & (W - 1 < 3 ? W - 1 : 3))) reduce_out6();
     }
+    pre(tile);
+    if constexpr (PT && MLP) {
+        // `pre` is a whole attention task at the register bound: nothing lane-dependent of the chain shall live across it.  The lane
+        // index and everything derived from it are derived again, from a freshly laundered thread index, tile by tile.
+        int tid2 = tid_in;
+        asm volatile("" : "+v"(tid2));
+        lane = tid2 & 63;
+        r = lane & 31;
+        h = lane >> 5;
+    }
 #ifndef AFT_NO_PROGRESS_PRIORITY
     {
         const int left = rounds - 1 - round;
@@ -432,9 +475,16 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, float *smem, cons
         else __builtin_amdgcn_s_setprio(0);
     }
 #endif
-    const int row0 = tile * 32;
+    const int row0 = tile * 32;                               // (PT: the tile's first row in the tile-blocked x)
     const int grow = min(row0 + r, a.rows - 1);               // clamped: ragged last tile computes, never stores
-    const bool row_ok = row0 + r < a.rows;
+    int plane_pt = 0, qt_pt = 0, valid_pt = 32;               // PT: the tile's plane, its query tile there, its valid rows
+    if constexpr (PT) {
+        plane_pt = tile / a.tpp;
+        qt_pt = tile - plane_pt * a.tpp;
+        valid_pt = min(32, a.tokens - qt_pt * 32);
+    }
+    const bool row_ok = PT ? r < valid_pt : row0 + r < a.rows;
+    const bool blocked = PT || a.x_blocked;
     const unsigned xrow = ((unsigned)grow * D + fb + 4 * h) * 4;   // byte offset of this lane's 16 features: + 32s + 4j
     // the weight addresses do not depend on the tile: launder the pointers so LICM cannot hoist all
     // 128 KB of this wave's fragment loads out of the tile loop (241 spilled VGPRs when it did)
@@ -442,8 +492,11 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, float *smem, cons
     //  become flat_load, whose out-of-order return forces vmcnt(0)+lgkmcnt(0) waits)
     unsigned lo = 0;
     asm volatile("" : "+v"(lo));
-    const unsigned wo_lane = (wo_off + lo) * 4, w1_lane = (w1_off + lo) * 4, w2_lane = (w2_off + lo) * 4,
-                   wq_lane = (wq_off + lo) * 4;   // byte offsets into the packed weight blocks
+    const unsigned lo_lane = PT && MLP ? lo + lane * 4 : lo;     // (PT with MLP: the lane's part from the re-derived lane index)
+    const unsigned wo_lane = ((PT && MLP ? (unsigned)w * W * 1024 : wo_off) + lo_lane) * 4,
+                   w1_lane = ((PT && MLP ? (unsigned)(2 * w) * W * 1024 : w1_off) + lo_lane) * 4,
+                   w2_lane = ((PT && MLP ? (unsigned)w * (2 * W) * 1024 : w2_off) + lo_lane) * 4,
+                   wq_lane = ((PT && MLP ? (unsigned)w * W * 1024 : wq_off) + lo_lane) * 4;   // byte offsets into the packed weight blocks
     STAMP(0);
 #ifdef AFT_DIAG_STAMPS
     if (a.stamps && tid == 0) {
@@ -464,12 +517,20 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, float *smem, cons
         f32x16 acc_o[1] = {bias_acc(srd_bo, fb, h)};
         gemm_preload<W, 1, PFD, 1>(ring_d, srd_wo, wo_lane);
         // attention output of this row tile, all W feature blocks, straight into operand registers
-        request_attn(tile, AHEAD ? PFK : 0, W);
-        if (!AHEAD) request_x(tile);
+        if constexpr (PT) {
+            request_x_pt(tile, valid_pt);
+        } else {
+            request_attn(tile, AHEAD ? PFK : 0, W);
+            if (!AHEAD) request_x(tile);
+        }
         STAMP(1);
         // ---- out-projection (transposed) + bias + residual ----
         if constexpr (BS)
             gemm_run_bs<W, 1, PFD, 1, 0>(ring_d, srd_wo, wo_lane, acc_o, [&](int kb, int m) { return bs_split(of[kb][2 * m], of[kb][2 * m + 1]); });
+        else if constexpr (PT)     // the attention output `pre` left in the hidden buffer's upper half
+            gemm_run<W, 1, PFD, 1, 0>(ring_d, srd_wo, wo_lane, acc_o, [&](int kb, int s) {
+                return *reinterpret_cast<const f32x4 *>(hb + S::XB + (kb * 4 + s) * 256 + lane * 4);
+            });
         else
             gemm_run<W, 1, PFD, 1, 0>(ring_d, srd_wo, wo_lane, acc_o, [&](int kb, int s) { return of[kb][s]; });
         f32x16 acc_h[2] = {bias_acc(srd_b1, 2 * fb, h), bias_acc(srd_b1, 2 * fb + 32, h)};
@@ -555,11 +616,12 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, float *smem, cons
                 float *part = hb + (w * 64 + lane) * 8;
                 *reinterpret_cast<f32x4 *>(part) = f32x4{acc6[0], acc6[1], acc6[2], acc6[3]};
                 *reinterpret_cast<f32x4 *>(part + 4) = f32x4{acc6[4], acc6[5], acc6[6], acc6[7]};
-                pending_row0 = row0;
+                pending_row0 = PT ? plane_pt * a.tokens + qt_pt * 32 : row0;
+                pending_valid = valid_pt;
             }
         }
         if (store_x && row_ok) {
-            if (a.x_blocked) {
+            if (blocked) {
                 const unsigned xblk = ((unsigned)row0 * D + w * 1024 + lane * 4) * 4;
 #pragma unroll
                 for (int s = 0; s < 4; ++s)
@@ -594,7 +656,7 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, float *smem, cons
                 if (2 * st < a.emb_K) acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[st], emb_bv[st], acc0, 0, 0, 0);
             cur = acc0;
             if (row_ok) {
-                if (a.x_blocked) {
+                if (blocked) {
                     const unsigned xblk = ((unsigned)row0 * D + w * 1024 + lane * 4) * 4;
 #pragma unroll
                     for (int s = 0; s < 4; ++s)
@@ -652,6 +714,34 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, float *smem, cons
         //   vt   : [plane*H + head][key tile][g][lane = d + 32*hh][4]        value (d, key = 32kt + 8g + 4hh + j)
         // q/k tiles (lane = token row, registers = features): registers 4s..4s+3 of half hh are one
         // 16-byte fragment element; the v tile (lane = feature, registers = tokens) likewise.
+        if constexpr (PT) {
+            // plane-aligned tile: token tok0 + r of plane `plane_pt` IS row (r, key tile qt) of the fragment layout and every V^T group of
+            // four tokens one whole element at the lane-linear offset -- the in-plane fast path below, with the rows past the plane's
+            // end left out (lanes of q / k; whole groups of v^T, or single tokens where 4 does not divide the token count)
+            const unsigned ph_base = (unsigned)(plane_pt * a.heads + w) * ((unsigned)a.tokpad * kHeadDim) + (unsigned)qt_pt * 1024;
+            if (row_ok) {
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    srd_store(srd_q, (ph_base + lane * 4 + s * 256) * 4, f32x4{acc[0][4 * s], acc[0][4 * s + 1], acc[0][4 * s + 2], acc[0][4 * s + 3]});
+                    srd_store(srd_k, (ph_base + lane * 4 + s * 256) * 4, f32x4{acc[1][4 * s], acc[1][4 * s + 1], acc[1][4 * s + 2], acc[1][4 * s + 3]});
+                }
+            }
+#pragma unroll
+            for (int gq = 0; gq < 4; ++gq) {   // registers 4gq..4gq+3 = tokens 32 qt + 8gq + 4h + {0..3}
+                const int tok = qt_pt * 32 + 8 * gq + 4 * h;
+                const f32x4 v = {acc[2][4 * gq], acc[2][4 * gq + 1], acc[2][4 * gq + 2], acc[2][4 * gq + 3]};
+                if (tok + 3 < a.tokens) {
+                    srd_store(srd_vt, (ph_base + gq * 256 + lane * 4) * 4, v);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (tok + j < a.tokens) {
+                            const float vj = acc[2][4 * gq + j];    // (a scalar first: bit_cast of a vector ELEMENT read element 0 for every j)
+                            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, vj), srd_vt, (ph_base + gq * 256 + lane * 4 + j) * 4, 0, 0);
+                        }
+                }
+            }
+        } else {
         const int plane0 = row0 / a.tokens, tok0 = row0 - plane0 * a.tokens;
         const unsigned head_stride = (unsigned)a.tokpad * kHeadDim;             // floats per (plane, head)
         // token index past the end of its plane -> the next plane's (plane, head) block.  A 32-row tile crosses at most one
@@ -787,6 +877,7 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, float *smem, cons
             }
         }
         }   // general epilogue
+        }   // !PT
     }
     STAMP(11);
 #ifdef AFT_DIAG_STAMPS
@@ -796,6 +887,10 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, float *smem, cons
     // that follows the last read (xb: LN1 barrier of the next tile; stats: the x2-exchange barrier; hb:
     // two barriers).  <!MLP,QKV> double-buffers its exchange (above).  <MLP,!QKV> has no x2-exchange
     // barrier in front of the next tile's LN1 partials: one more barrier.
+    // PT with MLP: `pre` writes the attention fragments to hb's upper half -- last read by the previous tile's FFN-down product, two
+    // barriers back (LN2 table, x2 exchange / the closing barrier) -- and its own barrier follows; the out-projection's reads of them end
+    // before the LN1 barrier, two barriers in front of the hidden publish that re-writes hb.  The partials of out6 (hb's first
+    // quarter) never meet them.  x1 goes to xb behind `pre`'s barrier and LN1's: every in-projection read of x2 is over.
     if constexpr (MLP && !QKV) __syncthreads();
   }
     if constexpr (MLP && !QKV) {

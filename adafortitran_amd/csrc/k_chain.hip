@@ -177,10 +177,9 @@ static hipError_t launch_chain_t(const ChainArgs &args, bool mlp, bool qkv, hipS
     return launch_chain_v<D, ACT, false, true>(args, st);
 }
 
-hipError_t launch_chain(const aft_config &c, const aft_layer_weights *m, const float *m_packed,
-                        const aft_layer_weights *qw, const float *q_packed,
-                        const float *attn, float *x, float *q, float *k, float *vt, int rows, int tokens,
-                        int tokpad, hipStream_t st, const ChainFusion *fuse) {
+ChainArgs make_chain_args(const aft_config &c, const aft_layer_weights *m, const float *m_packed, const aft_layer_weights *qw,
+                          const float *q_packed, const float *attn, float *x, float *q, float *k, float *vt, int rows, int tokens,
+                          int tokpad, const ChainFusion *fuse) {
     const size_t dd = (size_t)c.model_dim * c.model_dim;
     ChainArgs a{};
     if (fuse != nullptr && fuse->out6 != nullptr && m != nullptr && qw == nullptr) {
@@ -211,6 +210,14 @@ hipError_t launch_chain(const aft_config &c, const aft_layer_weights *m, const f
     a.q = q; a.k = k; a.vt = vt;
     a.rows = rows; a.tokens = tokens; a.tokpad = tokpad;
     a.heads = c.model_dim / kHeadDim;   // q / k / v^T are laid out per 32-feature block, whatever the head count (attn_device.h)
+    return a;
+}
+
+hipError_t launch_chain(const aft_config &c, const aft_layer_weights *m, const float *m_packed,
+                        const aft_layer_weights *qw, const float *q_packed,
+                        const float *attn, float *x, float *q, float *k, float *vt, int rows, int tokens,
+                        int tokpad, hipStream_t st, const ChainFusion *fuse) {
+    const ChainArgs a = make_chain_args(c, m, m_packed, qw, q_packed, attn, x, q, k, vt, rows, tokens, tokpad, fuse);
     const bool gelu = c.activation == AFT_ACT_GELU;
     const bool mlp = m != nullptr, qkv = qw != nullptr;
     if (c.precision == AFT_PRECISION_BF16X3) {

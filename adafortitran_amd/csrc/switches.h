@@ -9,6 +9,7 @@
 
 #define AFT_SWITCHES(X) \
     X(LANES, "AFT_LANES", "1 = never split a forward into lanes; 2 .. 4 = always that many shares (header section \"Lanes\")") \
+    X(LAYER_FUSED, "AFT_LAYER_FUSED", "0 = never the one-launch-per-layer sequence (k_layer.hip), 1 = wherever its shape is covered (default: where plane-aligned tiles add no round)") \
     X(PROLOGUE_NO_UP, "AFT_PROLOGUE_NO_UP", "measurement: the profiled prologue launch without the pilot upsampler product") \
     X(CONV_NSPLIT, "AFT_CONV_NSPLIT", "1 | 2 | 4 column ranges per plane in the streaming conv kernels (default: by the batch)") \
     X(CONV_BANDED, "AFT_CONV_BANDED", "the banded conv kernel instead of the column- / row-streaming ones") \

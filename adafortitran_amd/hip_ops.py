@@ -105,7 +105,8 @@ class HipEngine:
                 if stream in table:
                     table[stream] = table.pop(stream)
         if ws is None or batch > self._ws_batch[stream]:
-            nbytes = self.lib.aft_workspace_bytes(C.byref(self.cfg), batch)
+            # (with room for the fused layer sequence's two blocks behind the planned slices; the same size where it does not apply)
+            nbytes = self.lib.aft_workspace_bytes_layer_fused(C.byref(self.cfg), batch)
             if nbytes == 0:
                 _lib.check(self.lib.aft_forward_f32(C.byref(self.cfg), None, None, None, None, None, None, None, 0, batch, None))
                 raise ValueError("unsupported configuration")

@@ -142,6 +142,18 @@ int aft_max_batch(const aft_config *cfg);
 /* Bytes of scratch aft_forward_f32 needs for `batch` frames (0 on a bad config). */
 size_t aft_workspace_bytes(const aft_config *cfg, int batch);
 
+/* The fused layer sequence (no reference counterpart): one launch per encoder layer on plane-aligned row tiles instead
+ * of the [attention, chain] launches.  Same bits either way.  It needs two more blocks of scratch than aft_workspace_bytes plans
+ * (x on plane-aligned tiles, a second V^T buffer), which the forward lays BEHIND the planned slices of all lanes: a caller opts in
+ * by passing a workspace of aft_workspace_bytes_layer_fused bytes (= aft_workspace_bytes where the sequence is not instantiated);
+ * with less, the launches run.  Every offset aft_workspace_lanes / aft_workspace_region report holds in both cases.
+ * aft_layer_fused_of: which sequence a forward of `batch` frames in ONE lane runs given such a workspace: 1 = fused (fp32, model_dim
+ * 128, head dimension 32, >= 32 tokens, encoder_path AUTO, and a batch at which plane-aligned tiles take no more rounds of the
+ * persistent grid than global ones), 0 = the launches.  The switch AFT_LAYER_FUSED (0 = never, 1 = wherever the shape is covered)
+ * overrides the batch rule.  -1 on a bad config or batch. */
+size_t aft_workspace_bytes_layer_fused(const aft_config *cfg, int batch);
+int aft_layer_fused_of(const aft_config *cfg, int batch);
+
 /* Lanes (no reference counterpart).  A forward whose launches do not fill whole rounds of the kernels' persistent grids -- more than
  * one row tile per CU, fewer than ~15, and not as well aligned as the default model's 127 / 128 frames (DESIGN.md section 5 has the
  * rule and the measurements) -- is run as TWO complete forwards over contiguous shares of the batch: share 0 on the
