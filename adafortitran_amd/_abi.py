@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes as C
 from typing import Callable, Dict, Optional
 
-AFT_ABI_VERSION = 9
+AFT_ABI_VERSION = 10
 AFT_ENGINE_PACKED, AFT_ENGINE_GENERAL = 0, 1
 AFT_OK, AFT_ERR_ARG, AFT_ERR_SHAPE, AFT_ERR_HIP = 0, 1, 2, 3
 AFT_ACT_RELU, AFT_ACT_GELU = 0, 1
@@ -242,4 +242,4 @@ SIGNATURES = {
 #: every symbol include/adafortitran_amd.h declares (tests check the .so exports them all)
 EXPORTED_SYMBOLS = tuple(SIGNATURES)
 REGION_IDS = {"conv_enhanced": 0, "tokens6": 1, "enc_out": 2}   # aft_workspace_region
-KERNEL_IDS = {"upsample": 0, "embed": 1, "qkv": 2, "attention": 3, "chain": 4, "tail": 5, "chain_last": 6, "encoder_plane": 7, "prologue": 8}
+KERNEL_IDS = {"upsample": 0, "embed": 1, "qkv": 2, "attention": 3, "chain": 4, "tail": 5, "chain_last": 6, "prologue": 8}

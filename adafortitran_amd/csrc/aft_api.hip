@@ -212,7 +212,8 @@ Workspace plan_workspace(const aft_config &c, int batch) {
         return ws;
     }
     ws.x = ws.take((rows + 31) / 32 * 32 * c.model_dim);   // whole 32-row tiles (tile-blocked x)
-    // attention tiles: global 32-row tiles (layer-by-layer path) or ceil(tokens/32) tiles per plane (plane-resident path)
+    // attention tiles: global 32-row tiles for the launches; never smaller than a whole q / k / v^T block (planes x tokpad rows),
+    // because the fused layer sequence uses this region as its second K buffer (run_encoder)
     ws.attn = ws.take(std::max((size_t)round_up((int)rows, kTile), (size_t)ws.planes * ws.tokpad) * c.model_dim);
     const size_t per_head = (size_t)ws.planes * ws.tokpad * c.model_dim;   // planes x (model_dim / 32) blocks x tokpad x 32
     ws.q = ws.take(per_head);
@@ -259,10 +260,12 @@ static int max_batch_of(const aft_config &c) {
 // Each share is a complete forward with its own slice of the workspace (laid end to end, share 0 first); per-frame arithmetic does
 // not depend on the batch a frame travels in, so the bits are those of the single forward (tests/test_hip_parity.py).
 constexpr int kMaxLanes = 4;
-struct LanePlan : Layout {        // one region per share: a whole workspace plan
+struct LanePlan : Layout {        // one region per share: a whole workspace plan; then the fused layer sequence's blocks (below)
     int lanes;
     int frames[kMaxLanes], first[kMaxLanes];
     size_t ws_off[kMaxLanes];     // floats
+    size_t planned;               // floats: the end of the shares' slices = what aft_workspace_bytes covers
+    size_t x_pt[kMaxLanes], vt2[kMaxLanes];   // layer_fused_ok only: each share's two blocks behind `planned`
 };
 // When it pays (tools/debug/lanes_threshold.py and the tables of DESIGN.md section 5: one lane against two over eight configurations
 // x batches, four boxes):
@@ -278,8 +281,9 @@ struct LanePlan : Layout {        // one region per share: a whole workspace pla
 //    one launch sequence and its per-kernel accounting) -- else two (16 frames 1.12 x, 32 1.10, 64 1.03-1.06, 96 1.02-1.04,
 //    129 1.04, 132 1.07, 160 1.01, 192 1.03; model_dim 256: 16 frames 1.32 x, 64 1.05-1.08; config 5: 4 / 8 / 16 / 48 frames
 //    1.27 / 1.15 / 1.05 / 1.03; other head counts and model dims at 64 / 128 frames 0.99-1.10).
+static long round_count(long n, long slots) { return (n + slots - 1) / std::max<long>(slots, 1); }
 static double round_efficiency(long n, long slots) {
-    const long rounds = (n + slots - 1) / std::max<long>(slots, 1);
+    const long rounds = round_count(n, slots);
     return rounds > 0 ? (double)n / (double)(rounds * slots) : 1.0;
 }
 // ---- the fused layer sequence (k_layer.hip) ----
@@ -288,16 +292,11 @@ static double round_efficiency(long n, long slots) {
 // chain grid: planes x ceil(tokens / 32) tiles take no more rounds of 3 x CUs workgroups than the ceil(rows / 32) global tiles (the
 // default model at 128 frames: 2 304 = 3 x 768 tiles against 2 240, three rounds either way; at 129 frames 2 322 tiles would be a fourth).
 // AFT_LAYER_FUSED: 0 = never, anything else = wherever the shape is instantiated (the A/B lever).
-// What the fused sequence needs BEYOND the workspace plan, per lane of `frames` frames: x on plane-aligned tiles (planes x tokpad rows)
-// and the second V^T buffer (K and V^T alternate between two buffers from layer to layer, k_layer.hip; the second K buffer is the
-// plan's `attn`, idle there and never smaller than a q / k / v^T block).  These two blocks are laid BEHIND the planned slices of all
+// What the fused sequence needs BEYOND the workspace plan, per lane: x on plane-aligned tiles (LanePlan::x_pt) and the second V^T
+// buffer (LanePlan::vt2; K and V^T alternate between two buffers from layer to layer, k_layer.hip; the second K buffer is the plan's
+// `attn`, idle there and never smaller than a q / k / v^T block).  plan_lanes lays these two blocks BEHIND the planned slices of all
 // lanes, so every planned offset (aft_workspace_lanes, aft_workspace_region) holds whichever sequence runs; a caller opts in by passing
 // a workspace of aft_workspace_bytes_layer_fused, and a smaller one (>= aft_workspace_bytes) runs the launches.
-static size_t layer_ext_floats(const aft_config &c, int frames) {
-    const size_t block = (size_t)2 * frames * round_up(tokens_of(c), kTile) * c.model_dim;
-    return 2 * ((block + 63) / 64 * 64);
-}
-static long round_count(long n, long slots) { return (n + slots - 1) / std::max<long>(slots, 1); }
 static bool layer_fused_selected(const aft_config &c, int batch) {
     if (!layer_fused_ok(c) || c.encoder_path != AFT_ENCODER_AUTO) return false;
     if (switch_on(SW_LAYER_FUSED)) return switch_int(SW_LAYER_FUSED, 1) != 0;
@@ -332,11 +331,21 @@ static LanePlan plan_lanes(const aft_config &c, int batch, int lanes) {
         p.frames[i] = (int)((long)batch * (i + 1) / p.lanes) - p.first[i];
         p.ws_off[i] = p.take(plan_workspace(c, p.frames[i]).total);
     }
+    p.planned = p.total;
+    for (int i = 0; i < p.lanes && layer_fused_ok(c); ++i) {
+        const size_t block = (size_t)2 * p.frames[i] * round_up(tokens_of(c), kTile) * c.model_dim;   // planes x tokpad rows
+        p.x_pt[i] = p.take(block);
+        p.vt2[i] = p.take(block);
+    }
     return p;
 }
-static size_t workspace_floats_any_lanes(const aft_config &c, int batch) {   // whatever lanes_wanted() answers at call time fits
+// whatever lanes_wanted() answers at call time fits; `fused_blocks`: with room for the fused layer sequence's blocks
+static size_t workspace_floats_any_lanes(const aft_config &c, int batch, bool fused_blocks) {
     size_t m = 0;
-    for (int l = 1; l <= kMaxLanes; ++l) m = std::max(m, plan_lanes(c, batch, l).total);
+    for (int l = 1; l <= kMaxLanes; ++l) {
+        const LanePlan lp = plan_lanes(c, batch, l);
+        m = std::max(m, fused_blocks ? lp.total : lp.planned);
+    }
     return m;
 }
 // Side streams + fork / join events of one caller stream (created on first use, up to the lane count a call asks for; nothing here
@@ -435,31 +444,22 @@ static ChainFusion chain_fusion_for(ChainPos pos, const aft_config &c, const Wei
 // of all num_layers layers.
 static int run_encoder(const aft_config &c, const WeightsDev &w, const aft_layer_weights *layers, const Workspace &ws, float *base, float *x,
                        int first_layer, int last_layer, hipStream_t st, bool fused = false, const float *prepacked = nullptr,
-                       float *layer_ext = nullptr) {
+                       float *x_pt = nullptr, float *vt2 = nullptr) {
     float *attn = base + ws.attn, *q = base + ws.q, *k = base + ws.k, *vt = base + ws.vt;
     const int rows = ws.planes * ws.tokens;
     const size_t pl = packed_layer_floats(c.model_dim);
     const float *wp = prepacked != nullptr ? prepacked : base + ws.wpack;
     if (prepacked == nullptr)   // weights arrive in torch layout on every call (stateless ABI): re-lay them into fragment order
         STEP("pack_weights", launch_pack_weights(c, layers + first_layer, base + ws.wpack + first_layer * pl, last_layer - first_layer + 1, st));
-    // whole forward and the caller asks for it: ONE launch for the encoder (k_encoder.hip).  AUTO means the launches:
-    // measured on the MI355X at B = 128 (256 planes on 256 CUs, its best case) the plane-resident kernel is 1.5 % slower
-    // (profiles/r03_ab_encoder.json), so nothing selects it by itself.
-    if (fused && c.encoder_path == AFT_ENCODER_PLANE && c.precision == AFT_PRECISION_F32 && first_layer == 0 &&
-        last_layer == c.num_layers - 1 && encoder_plane_ok(c)) {
-        STEP("encoder(plane-resident)", launch_encoder_plane(c, w, wp, base + ws.conv_enhanced, c.adaptive ? base + ws.tokens6 : nullptr, x, attn,
-                                                             q, k, vt, base + ws.out6, ws.planes, ws.tokens, ws.tokpad, st));
-        return AFT_OK;
-    }
     const ChainFusion first = chain_fusion_for(kChainFirst, c, w, ws, base), middle = chain_fusion_for(kChainMiddle, c, w, ws, base),
                       last = chain_fusion_for(kChainLast, c, w, ws, base);
     // whole forward on the workspace's own x: one launch per layer on plane-aligned tiles where layer_fused_selected says so.
     // Layer l reads K / V^T buffer l & 1 and writes the other one ((k, vt) | (attn, vt2)).
-    // `layer_ext`: the lane's two blocks behind the planned slices (layer_ext_floats), NULL when the caller's workspace has no room
-    if (fused && layer_ext != nullptr && x == base + ws.x && first_layer == 0 && last_layer == c.num_layers - 1 &&
+    // `x_pt`, `vt2`: the lane's two blocks behind the planned slices (LanePlan), NULL when the caller's workspace has no room
+    if (fused && x_pt != nullptr && x == base + ws.x && first_layer == 0 && last_layer == c.num_layers - 1 &&
         layer_fused_selected(c, ws.planes / 2)) {
-        x = layer_ext;                                             // plane-aligned tiles: planes x tokpad rows
-        float *kbuf[2] = {k, attn}, *vbuf[2] = {vt, layer_ext + layer_ext_floats(c, ws.planes / 2) / 2};
+        x = x_pt;                                                  // plane-aligned tiles: planes x tokpad rows
+        float *kbuf[2] = {k, attn}, *vbuf[2] = {vt, vt2};
         STEP("chain(qkv, plane tiles)", launch_chain_plane_tiles(c, &layers[0], wp, x, q, kbuf[0], vbuf[0], ws.planes, ws.tokens, ws.tokpad, st, &first));
         for (int l = 0; l <= last_layer; ++l) {
             const bool more = l < last_layer;
@@ -561,7 +561,7 @@ int aft_max_batch(const aft_config *cfg) {
 
 size_t aft_workspace_bytes(const aft_config *cfg, int batch) {
     if (check_config(cfg) != AFT_OK || batch <= 0) return 0;
-    return workspace_floats_any_lanes(*cfg, batch) * sizeof(float);
+    return workspace_floats_any_lanes(*cfg, batch, false) * sizeof(float);
 }
 
 int aft_workspace_region(const aft_config *cfg, int batch, int region, size_t *offset_bytes, size_t *size_bytes) {
@@ -586,18 +586,7 @@ int aft_workspace_region(const aft_config *cfg, int batch, int region, size_t *o
 
 size_t aft_workspace_bytes_layer_fused(const aft_config *cfg, int batch) {
     if (check_config(cfg) != AFT_OK || batch <= 0) return 0;
-    size_t floats = workspace_floats_any_lanes(*cfg, batch);
-    if (layer_fused_ok(*cfg)) {    // whatever split lanes_wanted() picks at call time: its blocks are no larger than these
-        size_t ext = 0;
-        for (int l = 1; l <= kMaxLanes; ++l) {
-            const LanePlan lp = plan_lanes(*cfg, batch, l);
-            size_t e = 0;
-            for (int i = 0; i < lp.lanes; ++i) e += layer_ext_floats(*cfg, lp.frames[i]);
-            ext = std::max(ext, e);
-        }
-        floats += ext;
-    }
-    return floats * sizeof(float);
+    return workspace_floats_any_lanes(*cfg, batch, true) * sizeof(float);
 }
 
 int aft_layer_fused_of(const aft_config *cfg, int batch) {
@@ -632,7 +621,7 @@ int aft_workspace_lanes(const aft_config *cfg, int batch, int *lanes, int *frame
 
 // one share of the batch: a complete forward on `st` in its own workspace slice
 static int forward_lane(const aft_config *cfg, const aft_weights *w, const float *prepacked, const float *pilots, const float *snr,
-                        const float *ds, const float *dop, float *out, float *base, int batch, hipStream_t st, float *layer_ext) {
+                        const float *ds, const float *dop, float *out, float *base, int batch, hipStream_t st, float *x_pt, float *vt2) {
     const Workspace ws = plan_workspace(*cfg, batch);
     const bool general = !packed_engine_ok(*cfg);
     const WeightsDev wd = weights_window(*w, 0, cfg->num_layers);
@@ -651,7 +640,7 @@ static int forward_lane(const aft_config *cfg, const aft_weights *w, const float
     // packed engine: patch embedding + linear_1 + positions run inside the first chain launch, linear_2 inside the last one
     const int rc = general ? run_encoder_general(*cfg, wd, w->layers, ws, base, batch, st)
                            : run_encoder(*cfg, wd, w->layers, ws, base, base + ws.x, 0, cfg->num_layers - 1, st, true,
-                                         prepacked != nullptr ? prepacked : wpack, layer_ext);
+                                         prepacked != nullptr ? prepacked : wpack, x_pt, vt2);
     if (rc != AFT_OK) return rc;
     STEP("tail", launch_tail(*cfg, wd, nullptr, base + ws.conv_enhanced, out, batch, st, base + ws.out6, base + ws.convfrag + kConvFragFloats));
     return AFT_OK;
@@ -671,8 +660,10 @@ static int forward_impl(const aft_config *cfg, const aft_weights *w, const float
     hipStream_t user = static_cast<hipStream_t>(stream);
     AFT_REQUIRE(w->layers != nullptr, "aft_weights.layers is NULL (host array of num_layers entries)");
     const LanePlan lp = plan_lanes(*cfg, batch, lanes_wanted(*cfg, batch));
-    AFT_REQUIRE(workspace_bytes >= lp.total * sizeof(float), "workspace too small: %zu < %zu bytes (aft_workspace_bytes)",
-                workspace_bytes, lp.total * sizeof(float));
+    AFT_REQUIRE(workspace_bytes >= lp.planned * sizeof(float), "workspace too small: %zu < %zu bytes (aft_workspace_bytes)",
+                workspace_bytes, lp.planned * sizeof(float));
+    // the fused layer sequence's blocks behind the planned slices -- when the plan has them and the caller's workspace holds them
+    const bool fused_blocks = lp.total > lp.planned && workspace_bytes >= lp.total * sizeof(float);
     // side streams for the shares beyond the first; none to be had (header, "Lanes") = the shares run one after the other on the
     // caller's stream in the same workspace layout: same bits, and aft_workspace_lanes stays true
     LaneStreams *ls = lp.lanes > 1 ? acquire_lane_streams(user, lp.lanes) : nullptr;
@@ -696,22 +687,17 @@ static int forward_impl(const aft_config *cfg, const aft_weights *w, const float
             AFT_HOST_ASSERT(check_layout(wl, workspace_bytes - lp.ws_off[i] * sizeof(float)), "workspace region outside its slice");
         }
         AFT_HOST_ASSERT(covered == batch, "lane shares do not cover the batch");
+        AFT_HOST_ASSERT(!fused_blocks || check_layout(lp, workspace_bytes), "fused layer sequence's blocks outside the workspace");
     }
 #endif
-    // the fused layer sequence's blocks, lane after lane behind the planned slices -- when the caller's workspace holds them
-    size_t ext_off[kMaxLanes], ext_end = lp.total;
-    for (int i = 0; i < lp.lanes; ++i) {
-        ext_off[i] = ext_end;
-        ext_end += layer_ext_floats(*cfg, lp.frames[i]);
-    }
-    const bool have_ext = layer_fused_ok(*cfg) && workspace_bytes >= ext_end * sizeof(float);
     int result = AFT_OK;
     for (int i = 0; i < lp.lanes; ++i) {
         const int f0 = lp.first[i];
         const int rc_lane = forward_lane(cfg, w, prepacked, pilots + (size_t)f0 * pil_floats, snr ? snr + f0 : nullptr, ds ? ds + f0 : nullptr,
                                          dop ? dop + f0 : nullptr, out + (size_t)f0 * out_floats, static_cast<float *>(workspace) + lp.ws_off[i],
                                          lp.frames[i], i == 0 || ls == nullptr ? user : ls->side[i - 1],
-                                         have_ext ? static_cast<float *>(workspace) + ext_off[i] : nullptr);
+                                         fused_blocks ? static_cast<float *>(workspace) + lp.x_pt[i] : nullptr,
+                                         fused_blocks ? static_cast<float *>(workspace) + lp.vt2[i] : nullptr);
         if (rc_lane != AFT_OK && result == AFT_OK) result = rc_lane;     // keep going: the join below must still happen
     }
     if (ls != nullptr) {
@@ -1008,12 +994,6 @@ int aft_profile_kernel_f32(const aft_config *cfg, const aft_weights *w, int whic
                 break;
             case AFT_KERNEL_CHAIN_LAST:   // as in the forward: linear_2 fused behind LN2, x not stored
                 e = launch_chain(*cfg, &w->layers[0], wp, nullptr, nullptr, attn, x, q, k, vt, rows, ws.tokens, ws.tokpad, st, &last);
-                break;
-            case AFT_KERNEL_ENCODER_PLANE:
-                AFT_REQUIRE(cfg->model_dim == 128, "the plane-resident encoder is instantiated for model_dim 128");
-                e = launch_encoder_plane(*cfg, wd, base + ws.wpack, base + ws.conv_enhanced,
-                                         cfg->adaptive ? base + ws.tokens6 : nullptr, x, attn, q, k, vt, base + ws.out6,
-                                         ws.planes, ws.tokens, ws.tokpad, st);
                 break;
             case AFT_KERNEL_PROLOGUE: {
                 AFT_REQUIRE(out != nullptr, "prologue profile needs the pilots pointer in `out`");

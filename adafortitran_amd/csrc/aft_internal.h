@@ -192,7 +192,7 @@ inline int tokens_of(const aft_config &c) { return (c.num_scs / c.patch_scs) * (
 // Layout in HBM (DESIGN.md "data layout"):
 //   conv_enhanced [2B][S][T]            f32  kept for the S7 residual
 //   tokens6       [B][tokens][6]        f32  adapter features (adaptive only)
-//   x             [2B*tokens][d]        f32  token activations: row-major (stage entry points, plane-resident path) or, in the
+//   x             [2B*tokens][d]        f32  token activations: row-major (stage entry points) or, in the
 //                                            whole-forward launch sequence, tile-blocked [tile][feature block][s][lane][4] (ChainArgs::x_blocked)
 //   attn          [ceil(2B*tokens/32)][H][4 s][64 lanes][4]  f32  attention output in operand-fragment order
 //   q, k          [2B][H][tokpad/32][4 s][64 lanes][4]  f32  MFMA-fragment order: (key%32 + 32hh, d = 8s+4hh+j)
@@ -310,12 +310,6 @@ hipError_t launch_chain_plane_tiles(const aft_config &c, const aft_layer_weights
 hipError_t launch_layer(const aft_config &c, const aft_layer_weights *mlp_w, const float *mlp_packed, const aft_layer_weights *qkv_w,
                         const float *qkv_packed, float *x, float *q, const float *k_in, const float *vt_in, float *k_out, float *vt_out,
                         int planes, int tokens, int tokpad, hipStream_t st, const ChainFusion *fuse);
-// Plane-resident encoder (k_encoder.hip): embedding + all layers + linear_2 of every plane in ONE launch, one 12-wave
-// workgroup per plane.  encoder_plane_ok: the shape is instantiated (d = 128).
-bool encoder_plane_ok(const aft_config &c);
-hipError_t launch_encoder_plane(const aft_config &c, const WeightsDev &w, const float *wpack, const float *conv_enhanced,
-                                const float *tokens6, float *x, float *attn, float *q, float *k, float *vt, float *out6,
-                                int planes, int tokens, int tokpad, hipStream_t st);
 // Re-lay the encoder GEMM weights of layers [first, first+count) into MFMA-fragment order.
 // `layers`: HOST array of `count` layers; the image starts at layers[0]'s block (any count: windows of kLayerWindow per launch)
 hipError_t launch_pack_weights(const aft_config &c, const aft_layer_weights *layers, float *packed, int count, hipStream_t st);

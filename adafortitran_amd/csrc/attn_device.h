@@ -1,4 +1,4 @@
-// attn_device.h (device code of k_attn.hip, shared with k_encoder.hip) -- multi-head self-attention core on gfx950 fp32 MFMA.
+// attn_device.h (device code of k_attn.hip, shared with k_layer.hip) -- multi-head self-attention core on gfx950 fp32 MFMA.
 //
 // Reference semantics: the scaled-dot-product part of nn.MultiheadAttention inside
 // nn.TransformerEncoderLayer (constructed at reference src/models/blocks/encoders.py:44-55):
@@ -104,8 +104,8 @@ struct AttnRow {          // per-lane softmax state of the lane's query row
 // itself, one per wave at most, so that a partial last round is spread over all XCDs and CUs instead of filling half the chip for a
 // full round (k_attn.hip); -1 = none.  Which wave works a task never changes the task's arithmetic: same bits.
 // One WAVE walks the tasks first_task, first_task + total_waves, ... < ntasks (task = (plane * heads + head) * nkt + query
-// tile): attn_kernel (k_attn.hip) deals them over a persistent grid, the plane-resident encoder kernel (k_encoder.hip)
-// over the 12 waves of the workgroup that owns the plane.  No LDS, no barriers.
+// tile): attn_kernel (k_attn.hip) deals them over a persistent grid; layer_kernel (k_layer.hip) hands each wave the one task of
+// its tile and head.  No LDS, no barriers.
 // S^T tile of the split-precision tier: K and Q^T arrive as bf16 hi / lo fragments (slot 2m + term of a tile = MFMA m's
 // 8 k-values, written by the chain kernel's in-projection epilogue with the query bias and the softmax scale already
 // applied): hi.hi + hi.lo + lo.hi per MFMA m on v_mfma_f32_32x32x16_bf16.  The reference enters as one more MFMA whose
@@ -154,7 +154,9 @@ __device__ __forceinline__ void attn_body(const float *__restrict__ q, const flo
                                           unsigned long long *stamps, const int tail_task = -1, float *sink = nullptr) {
     static_assert(!SINK || (!BS && HD == 32), "the LDS sink is instantiated for the fp32 head-dimension-32 body");
     int lane_l = threadIdx.x & 63;
-    asm volatile("" : "+v"(lane_l));   // laundered: lane-dependent offsets are recomputed per call, not hoisted out of the caller's loops
+    // laundered: lane-dependent offsets are recomputed per call, not hoisted out of the caller's loops (first needed by the retired
+    // plane-resident encoder kernel; layer_kernel calls this body per tile too, and the generated code is pinned as measured)
+    asm volatile("" : "+v"(lane_l));
     const int lane = lane_l;
     const Srd qs = make_srd(q), ks = make_srd(k), vs = make_srd(vt), os = make_srd(out);
     static_assert(HD % 8 == 0 && HD >= 8 && HD <= 64 && HD != 56, "head dimension");

@@ -1,4 +1,4 @@
-// chain_device.h (device code of k_chain.hip, shared with k_encoder.hip) -- the row-local part of an encoder layer as ONE gfx950 kernel.
+// chain_device.h (device code of k_chain.hip, shared with k_layer.hip) -- the row-local part of an encoder layer as ONE gfx950 kernel.
 //
 // Reference semantics (nn.TransformerEncoderLayer, post-LN, eval; constructed at
 // reference src/models/blocks/encoders.py:44-55, dim_feedforward = 2*model_dim :47):
@@ -62,8 +62,8 @@ struct ChainArgs {
     int rows, tokens, tokpad, heads;
     // x (the residual stream between two launches) in TILE-BLOCKED order: tile t's 32 rows as [feature block][fragment s][lane][4],
     // i.e. every 16-byte load / store of a wave is 1 KB contiguous instead of 64 pieces of 32 rows (round 4: -0.7 % on the whole
-    // forward).  Only the whole-forward launch sequence sets it -- nobody else reads x there; the stage entry points, the
-    // plane-resident kernel and the training path keep x row-major.  The x region must hold whole tiles.
+    // forward).  Only the whole-forward launch sequence sets it -- nobody else reads x there; the stage entry points
+    // and the training path keep x row-major.  The x region must hold whole tiles.
     int x_blocked;
     // <MLP,!QKV> only, optional: transformer_encoder.linear_2 (reference blocks/encoders.py:56,70) fused behind LN2.
     // out6 [rows][out6_stride] receives x2 W2^T + b2 and x is NOT stored (the conv tail reads out6); NULL = store x.
@@ -275,10 +275,8 @@ struct ChainNoPre {
 //   <true,true>  layer l's out-proj+LN1+FFN+LN2 and layer l+1's in-projection   (5 of 7 launches at L=6)
 //   <false,true> in-projection only (first layer)      <true,false> last layer, no in-projection
 // The body works on the row tiles first_tile, first_tile + tile_stride, ... < tile_end with the S::THREADS threads
-// `tid` = 0 .. THREADS-1 of one wave GROUP whose LDS block is `smem`: a whole workgroup in chain_kernel (k_chain.hip), one
-// of three groups of a 12-wave workgroup in the plane-resident encoder kernel (k_encoder.hip).  __syncthreads() is the
-// only cross-wave synchronisation, so every group of a workgroup must walk the same NUMBER of tiles (tiles past the
-// last row are computed on clamped rows and never stored).
+// `tid` = 0 .. THREADS-1 of the workgroup, whose LDS block is `smem` (chain_kernel in k_chain.hip, layer_kernel in k_layer.hip).
+// __syncthreads() is the only cross-wave synchronisation (tiles past the last row are computed on clamped rows and never stored).
 // PT (k_layer.hip): PLANE-ALIGNED tiles (ChainArgs::tpp), tile_end = planes x tpp.  Rows past the plane's end are computed on the clamped
 // last valid row's inputs and never stored.  x is tile-blocked.  With MLP, `pre(tile)` has left the tile's attention output -- all W
 // feature blocks, operand-fragment order -- in the UPPER half of the hidden buffer, behind a workgroup barrier, and the
@@ -289,9 +287,9 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, float *smem, cons
     using S = ChainShape<D>;
     constexpr int W = S::WAVES;
     static_assert(!PT || !BS, "plane-aligned tiles are instantiated for the fp32 body");
-    // laundered: everything derived from the thread index is (re)computed inside this body.  In k_encoder.hip the body
-    // sits inside a plane loop and a layer loop; LICM hoisted a dozen lane-dependent offsets to the top of the kernel,
-    // where they were spilled at once and reloaded from scratch at every tile start (a scratch reload drains vmcnt).
+    // laundered: everything derived from the thread index is (re)computed inside this body, so that LICM in a caller's loops cannot
+    // hoist lane-dependent offsets out of it (the retired plane-resident encoder kernel was the original reason: hoisted offsets were
+    // spilled at once and reloaded at every tile start).  Kept because the generated code of every kernel is pinned as measured.
     int tid = tid_in;
     asm volatile("" : "+v"(tid));
     float *xb = smem;              // x1 then x2, fragment order

@@ -26,7 +26,7 @@
     X(TRAIN_NO_FUSED_ENDS, "AFT_TRAIN_NO_FUSED_ENDS", "training: PyTorch's unfold / cat / add around the dense ends, not fused") \
     X(TRAIN_NO_QKV_CHAIN, "AFT_TRAIN_NO_QKV_CHAIN", "training: every layer runs its own in-projection GEMM (no chained tapes)") \
     X(PRECISION, "AFT_PRECISION", "f32 | bf16x3: the estimators' default hip_precision") \
-    X(ENCODER_PATH, "AFT_ENCODER_PATH", "auto | launches | plane: aft_config.encoder_path of every HipEngine")
+    X(ENCODER_PATH, "AFT_ENCODER_PATH", "auto | launches | plane: aft_config.encoder_path of every HipEngine (`plane`: retired, runs the launches)")
 
 namespace aft {
 

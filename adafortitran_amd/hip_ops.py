@@ -66,8 +66,8 @@ class HipEngine:
                 raise ValueError(f"{k}: HIP path needs contiguous float32 (got {v.dtype})")
             self._keep[k] = v
         self.weights = _abi.make_weights(cfg, lambda k: self._keep[k].data_ptr(), pos_key=_abi.pos_key_of(self._keep))
-        # the switch AFT_ENCODER_PATH=launches|plane (A/B runs) overrides the automatic choice between the layer-by-layer launches
-        # and the plane-resident encoder kernel (same output bits either way)
+        # the switch AFT_ENCODER_PATH=launches (A/B runs) overrides the automatic choice between the layer-by-layer launches and
+        # the fused layer sequence (same output bits either way); `plane`: retired, runs the launches
         forced = _lib.get_switch("AFT_ENCODER_PATH")
         if forced:
             cfg.encoder_path = {"auto": _abi.AFT_ENCODER_AUTO, "launches": _abi.AFT_ENCODER_LAUNCHES,

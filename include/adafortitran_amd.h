@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define AFT_ABI_VERSION 9   /* bump whenever an entry point's meaning, a struct or a scratch size changes */
+#define AFT_ABI_VERSION 10   /* bump whenever an entry point's meaning, a struct or a scratch size changes */
 
 #define AFT_OK 0
 #define AFT_ERR_ARG 1   /* NULL pointer, bad batch, workspace too small ...          */
@@ -44,9 +44,9 @@ extern "C" {
 #define AFT_ERR_HIP 3   /* a HIP runtime call or kernel launch failed                */
 
 /* aft_config.encoder_path.  LAUNCHES: embedding+QKV, then [attention, chain] per layer (13 launches at 6 layers).
- * PLANE: the plane-resident kernel -- embedding + all layers + linear_2 in ONE launch, one 12-wave workgroup per plane
- * (model_dim 128 only; other shapes run the launches).  Identical output bits.  AUTO = LAUNCHES: on the MI355X the
- * plane kernel measured 1.5 % slower even at its best case, 256 planes on 256 CUs (profiles/r03_ab_encoder.json). */
+ * AUTO: the library chooses between the launches and the fused layer sequence (aft_layer_fused_of, below).
+ * PLANE: retired, runs the launches (it selected a one-launch plane-resident encoder kernel, measured 1.5 % slower than
+ * the launches and removed; the value stays accepted for existing callers).  Identical output bits whichever is set. */
 #define AFT_ENCODER_AUTO 0
 #define AFT_ENCODER_LAUNCHES 1
 #define AFT_ENCODER_PLANE 2
@@ -559,7 +559,7 @@ int aft_stage_tail_f32(const aft_config *cfg, const aft_weights *w, const float 
 #define AFT_KERNEL_CHAIN 4      /* chain kernel: out-proj+LN1+FFN+LN2 (layer 0) + QKV (layer 1) */
 #define AFT_KERNEL_TAIL 5       /* fold + residual + final ConvEnhancer (linear_2 done by AFT_KERNEL_CHAIN_LAST) */
 #define AFT_KERNEL_CHAIN_LAST 6 /* chain kernel of the last layer: out-proj+LN1+FFN+LN2 + linear_2             */
-#define AFT_KERNEL_ENCODER_PLANE 7 /* plane-resident encoder: embedding + all layers + linear_2 in one launch (k_encoder.hip) */
+/* (7 was the retired plane-resident encoder kernel: now an unknown kernel id) */
 #define AFT_KERNEL_PROLOGUE 8   /* the forward's first launch: channel adapter + weight re-lay + pilot_upsampler product; `out` = one
                                    buffer [pilots: batch x Ps x Pt x 2 floats | snr: batch | ds: batch | dop: batch]        */
 int aft_profile_kernel_f32(const aft_config *cfg, const aft_weights *w, int which, float *out,

@@ -165,7 +165,8 @@ def test_loader_checks_version_and_host_only_calls():
     planes, tokens, tokpad, d = 256, 280, 288, 128
     # conv_enhanced + tokens6 + x + attn + q + k + vt + fragment-packed encoder weights (6 layers x 8 d^2)
     # + linear_2 output of the last chain launch (rows x 8)
-    # (the attention tiles are sized for per-plane row tiles, planes x tokpad rows: the plane-resident encoder's layout)
+    # (the attention tiles are sized like a whole q / k / v^T block, planes x tokpad rows: the fused layer sequence uses the
+    # region as its second K buffer)
     expect = 4 * (planes * 1680 + 128 * tokens * 6 + planes * tokens * d + planes * tokpad * d + 3 * planes * 4 * tokpad * 32
                   + 6 * 8 * d * d + planes * tokens * 8 + 2 * (22 * 64 * 4 + 160))   # + both conv stacks' 16x16x4 operand fragments and helper tables
     # ABI 6: the forward may run as up to AFT_MAX_LANES = 4 shares of the batch, each with its own packed weights and fragment tables

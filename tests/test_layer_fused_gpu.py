@@ -147,13 +147,14 @@ def test_a_workspace_without_room_runs_the_launches(switches):
 # ---- host only ----
 def test_fused_workspace_size_is_the_plan_plus_two_blocks():
     """aft_workspace_bytes stays what it was; the opt-in size adds x on plane-aligned tiles and the second V^T buffer (each planes x
-    tokpad x model_dim floats, per lane rounded to 256 bytes), and nothing where the sequence is not instantiated."""
+    tokpad x model_dim floats: a whole number of 256-byte units, so exactly that much), and nothing where the sequence is not
+    instantiated."""
     lib = _lib.load()
     cfg = _abi.make_config(**DEFAULT_SPEC, adaptive_hidden=HID)
-    for b in (1, 5, 128):
+    for b in (1, 5, 37, 128):
         base, big = lib.aft_workspace_bytes(ctypes.byref(cfg), b), lib.aft_workspace_bytes_layer_fused(ctypes.byref(cfg), b)
         block = 4 * 2 * b * 288 * 128
-        assert base + 2 * block <= big <= base + 2 * block + 4 * 2 * 256
+        assert big == base + 2 * block
     other = _abi.make_config(**dict(DEFAULT_SPEC, num_head=8), adaptive_hidden=None)
     assert lib.aft_workspace_bytes_layer_fused(ctypes.byref(other), 8) == lib.aft_workspace_bytes(ctypes.byref(other), 8) > 0
 

@@ -65,7 +65,7 @@ def test_checked_build_exports_the_new_entry_points():
         from adafortitran_amd import build
         build.build_checked()
     lib = _lib.load_path(path)
-    assert lib.aft_version() == _abi.AFT_ABI_VERSION == 9
+    assert lib.aft_version() == _abi.AFT_ABI_VERSION == 10
     assert lib.aft_grad_sumsq_scratch_bytes(1 << 20) == 256 * 12
 
 

@@ -170,4 +170,4 @@ def test_frame_gather_refuses_bad_arguments_without_a_device():
     args = list(good)
     args[5] = p + 2
     refused(lib.aft_frame_gather_f32(*args, None), "4-byte")
-    assert "aft_frame_gather_f32" in _abi.EXPORTED_SYMBOLS and _abi.AFT_ABI_VERSION == 9
+    assert "aft_frame_gather_f32" in _abi.EXPORTED_SYMBOLS and _abi.AFT_ABI_VERSION == 10

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A/B of the two encoder launch sequences of ONE library build, interleaved rounds in one process (tools/ab_encoder.py's pattern):
+"""A/B of the two encoder launch sequences of ONE library build, interleaved rounds in one process:
 
     python tools/ab_layer_fused.py [--config C3|C2] [--batch B] [--rounds R] [--reps N] [--json OUT]
 

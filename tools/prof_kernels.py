@@ -30,9 +30,7 @@ for _ in range(int(os.environ.get("AFT_FWD", "3"))):
 torch.cuda.synchronize()
 only = os.environ.get("AFT_ONLY")
 for name, io in (("upsample", pil), ("embed", None), ("qkv", None), ("attention", None), ("chain", None), ("chain_last", None),
-                 ("tail", out), ("encoder_plane", None)):
-    if name == "encoder_plane" and not only:
-        continue
+                 ("tail", out)):
     if only and name not in only.split(","):
         continue
     profile_kernel(eng, name, B, REPS, io)

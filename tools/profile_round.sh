@@ -1,7 +1,6 @@
 #!/bin/bash
 # Round profile (run on the GPU box through gpurun):  bash tools/profile_round.sh r03
-#  1. rocprofv3 --kernel-trace --stats of the SAME command the bench line comes from (+ the plane-resident encoder
-#     path and the split-precision tier, each as its own trace)
+#  1. rocprofv3 --kernel-trace --stats of the SAME command the bench line comes from (+ the split-precision tier as its own trace)
 #  2. separate --pmc passes (never combined with tracing): FETCH_SIZE / WRITE_SIZE / SQ+GRBM for the dominant kernel
 #     (chain), for attention, and for the conv HEAD and the conv TAIL in separate runs (same kernel symbol, two rows)
 #  3. kernel trace of one training step
@@ -13,7 +12,6 @@ OUT=$REPO/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench_trace" -- python3 "$REPO/bench.py" --steps 20 --warmup 5 --full --headline-only > "$OUT/bench_trace.log" 2>&1
-AFT_ENCODER_PATH=plane rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/plane_trace" -- python3 "$REPO/bench.py" --steps 20 --warmup 5 --full --headline-only > "$OUT/plane_trace.log" 2>&1
 export AFT_REPS=20 AFT_FWD=1
 AFT_PRECISION=bf16x3 AFT_FWD=20 AFT_ONLY=none rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/split_trace" -- python3 "$REPO/tools/prof_kernels.py" > "$OUT/split_trace.log" 2>&1
 SQ1="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA"
@@ -36,7 +34,6 @@ rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/general_trace" -- 
 cd "$REPO"
 python3 tools/train_step_breakdown.py "$OUT/train_trace" > "$OUT/train_kernel_trace_summary.txt" 2>&1
 python3 tools/summarize_prof.py "$OUT/bench_trace" > "$OUT/kernel_trace_summary.txt" 2>&1
-python3 tools/summarize_prof.py "$OUT/plane_trace" > "$OUT/plane_kernel_trace_summary.txt" 2>&1
 python3 tools/summarize_prof.py "$OUT/c5_trace" > "$OUT/c5_kernel_trace_summary.txt" 2>&1
 python3 tools/summarize_prof.py "$OUT/general_trace" > "$OUT/general_kernel_trace_summary.txt" 2>&1
 python3 tools/summarize_prof.py "$OUT/split_trace" > "$OUT/split_kernel_trace_summary.txt" 2>&1
@@ -44,4 +41,4 @@ python3 tools/summarize_prof.py "$OUT"/pmc_chain_* "$OUT"/pmc_attn_* "$OUT"/pmc_
 cp "$OUT"/bench_trace/*/*kernel_stats.csv "$OUT/kernel_stats.csv" 2>/dev/null
 find "$OUT" -name "*.csv" -size +1M -delete
 grep -h "^{\"metric\"" "$OUT/bench_trace.log" | tail -1 > "$OUT/bench_under_rocprof.json"
-cat "$OUT/kernel_trace_summary.txt"; head -12 "$OUT/plane_kernel_trace_summary.txt"; head -14 "$OUT/split_kernel_trace_summary.txt"
+cat "$OUT/kernel_trace_summary.txt"; head -14 "$OUT/split_kernel_trace_summary.txt"

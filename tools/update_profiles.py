@@ -18,7 +18,7 @@ from collections import defaultdict
 tag = sys.argv[1] if len(sys.argv) > 1 else "r03"
 src = os.path.join("gpurun_out", tag)
 os.makedirs("profiles", exist_ok=True)
-for name in ("kernel_stats.csv", "kernel_trace_summary.txt", "plane_kernel_trace_summary.txt", "split_kernel_trace_summary.txt",
+for name in ("kernel_stats.csv", "kernel_trace_summary.txt", "split_kernel_trace_summary.txt",
              "pmc_summary.txt", "bench_under_rocprof.json", "train_kernel_trace_summary.txt", "train_bench_line.json",
              "c5_kernel_trace_summary.txt", "general_kernel_trace_summary.txt"):
     p = os.path.join(src, name)
@@ -78,10 +78,6 @@ attn = block("attn", "attn_kernel", 6, 3 * planes * heads * tokpad * 32 * 4 + ro
              "attn_kernel, B=128 frames (1024 (plane, head) problems, 9 query tiles each); algorithmic = q + k + v^T read once, attention tiles written once")
 if attn:
     out["attention"] = attn
-plane = block("plane", "encoder_plane_kernel", 0, 128 * 13644 + 3_950_000,
-              "encoder_plane_kernel<128,GELU>: the whole encoder of B=128 as one launch (algorithmic = the forward's compulsory bytes)")
-if plane:
-    out["encoder_plane"] = plane
 # conv stacks: compulsory bytes per frame: head 192 B pilots in + 13,440 B conv_enhanced out (+ 187 KB of weights once per
 # launch); tail reads conv_enhanced (13,440) + the linear_2 output (280 tokens x 8 floats x 2 planes = 17,920) and writes 13,440
 # round 4: the default grid runs the column-streaming kernels (k_conv_stream.hip) -- <0> = head, <1> = tail, distinct symbols -- and
