@@ -85,6 +85,15 @@ class AftLmmse(C.Structure):
     ]
 
 
+class AftLink(C.Structure):
+    """aft_link: the link-level error count's configuration, by value (linksim.LinkConfig.to_struct() fills it)."""
+    _fields_ = [
+        ("num_scs", C.c_int32), ("num_symbols", C.c_int32), ("pilot_scs", C.c_int32), ("pilot_symbols", C.c_int32),
+        ("bits_per_symbol", C.c_int32), ("reserved", C.c_int32),
+        ("pilot_sc_index", C.c_int32 * AFT_CHANSIM_MAX_PILOT_SCS), ("pilot_symbol_index", C.c_int32 * AFT_CHANSIM_MAX_PILOT_SYMBOLS),
+    ]
+
+
 class AftWeights(C.Structure):
     _fields_ = [
         ("up_w", _fp), ("up_b", _fp),
@@ -199,6 +208,8 @@ SIGNATURES = {
     "aft_channel_sim_f32": (C.c_int, [C.POINTER(AftChanSim), C.c_ulonglong] + [C.c_longlong] * 4 + [C.c_int, vp, vp, vp, vp]),
     "aft_lmmse_table_floats": (C.c_size_t, [C.POINTER(AftLmmse)]),
     "aft_lmmse_f32": (C.c_int, [C.POINTER(AftLmmse), vp, vp, vp, vp, vp, vp, C.c_int, vp]),
+    # aft_link * stays untyped: hip_ops.LinkPlan passes the address of the AftLink it keeps
+    "aft_link_errors_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, vp]),
     # training path
     "aft_encoder_tape_bytes": (C.c_size_t, [cfgp, C.c_int]),
     "aft_encoder_train_scratch_bytes": (C.c_size_t, [cfgp, C.c_int]),

@@ -874,6 +874,51 @@ int aft_lmmse_f32(const aft_lmmse *plan, const float *tables, const float *pilot
     return e == hipSuccess ? AFT_OK : hip_fail("lmmse", e);
 }
 
+int aft_link_errors_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys,
+                        const float *sigma, int32_t *counts, int batch, void *stream) {
+    AFT_REQUIRE(link && ideal && est && keys && sigma && counts, "link errors: NULL pointer argument");
+    AFT_REQUIRE((reinterpret_cast<uintptr_t>(ideal) | reinterpret_cast<uintptr_t>(est) | reinterpret_cast<uintptr_t>(keys)) % 8 == 0,
+                "link errors: ideal, est and keys must be 8-byte aligned");
+    AFT_REQUIRE((reinterpret_cast<uintptr_t>(sigma) | reinterpret_cast<uintptr_t>(counts)) % 4 == 0,
+                "link errors: sigma and counts must be 4-byte aligned");
+    AFT_REQUIRE(batch >= 1, "link errors: batch must be at least 1 (got %d)", batch);
+    auto within = [](const char *what, int got, int most) {
+        if (got < 1 || got > most) set_error("link errors: %s = %d is outside 1..%d", what, got, most);
+        return got >= 1 && got <= most;
+    };
+    if (!within("num_scs", link->num_scs, INT32_MAX) || !within("num_symbols", link->num_symbols, INT32_MAX) ||
+        !within("pilot_scs", link->pilot_scs, AFT_CHANSIM_MAX_PILOT_SCS) ||
+        !within("pilot_symbols", link->pilot_symbols, AFT_CHANSIM_MAX_PILOT_SYMBOLS))
+        return AFT_ERR_SHAPE;
+    if ((unsigned long long)link->num_scs * (unsigned long long)link->num_symbols > (1ull << 31)) {
+        set_error("link errors: the grid %d x %d has more than 2^31 elements", link->num_scs, link->num_symbols);
+        return AFT_ERR_SHAPE;
+    }
+    if (link->pilot_scs > link->num_scs || link->pilot_symbols > link->num_symbols) {
+        set_error("link errors: the pilot grid %d x %d is larger than the ofdm grid %d x %d", link->pilot_scs, link->pilot_symbols,
+                  link->num_scs, link->num_symbols);
+        return AFT_ERR_SHAPE;
+    }
+    auto listed = [](const char *what, const int32_t *index, int n, int size) {
+        for (int i = 0; i < n; ++i)
+            if (index[i] < 0 || index[i] >= size || (i > 0 && index[i] <= index[i - 1])) {
+                set_error("link errors: %s[%d] = %d: the positions must be strictly increasing inside [0, %d)", what, i, index[i], size);
+                return false;
+            }
+        return true;
+    };
+    if (!listed("pilot_sc_index", link->pilot_sc_index, link->pilot_scs, link->num_scs) ||
+        !listed("pilot_symbol_index", link->pilot_symbol_index, link->pilot_symbols, link->num_symbols))
+        return AFT_ERR_SHAPE;
+    const int m = link->bits_per_symbol;
+    if (m != 2 && m != 4 && m != 6 && m != 8) {
+        set_error("link errors: bits_per_symbol = %d is not one of 2, 4, 6, 8", m);
+        return AFT_ERR_SHAPE;
+    }
+    hipError_t e = launch_link_errors(*link, ideal, est, keys, sigma, counts, batch, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? AFT_OK : hip_fail("link_errors", e);
+}
+
 int aft_debug_fill_lds_f32(float value, void *stream) {
     hipError_t e = launch_fill_lds(value, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? AFT_OK : hip_fail("fill_lds", e);

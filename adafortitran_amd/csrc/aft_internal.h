@@ -340,6 +340,9 @@ size_t lmmse_fblock_floats(const aft_lmmse &plan);
 size_t lmmse_tblock_floats(const aft_lmmse &plan);
 hipError_t launch_lmmse(const aft_lmmse &plan, const float *tables, const float *pilots, const float *snr, const float *ds,
                         const float *dop, float *est, int batch, hipStream_t st);
+// the link-level error count (k_link.hip): `link` has passed aft_link_errors_f32's checks
+hipError_t launch_link_errors(const aft_link &link, const float *ideal, const float *est, const unsigned long long *keys,
+                              const float *sigma, int32_t *counts, int batch, hipStream_t st);
 hipError_t launch_mse(const float *est, const float *ref, double *sum_sq, long long n_complex, hipStream_t st);
 hipError_t launch_fill_lds(float value, hipStream_t st);   // test hook: every CU's LDS filled with `value`
 hipError_t launch_peek_lds(float *out, int workgroups, int n, hipStream_t st);   // ... and what a kernel finds in its LDS at start

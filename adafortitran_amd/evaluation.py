@@ -50,3 +50,28 @@ def get_test_stats(model: torch.nn.Module, test_dataloaders: List[Tuple[str, Ite
     for name, loader in sorted(test_dataloaders, key=lambda x: int(x[0].split("_")[1])):
         stats[int(name.split("_")[1])] = to_db(evaluate_dataloader(model, loader, group))
     return stats
+
+
+def get_link_stats(model: Optional[torch.nn.Module], test_dataloaders: List[Tuple[str, Iterable]], link_cfg, seed: int = 0,
+                   group=None) -> Dict[int, float]:
+    """Bit-error rate per loader on the link ``link_cfg`` (``linksim.LinkConfig``) defines: data symbols through each frame's true channel
+    plus noise at the frame's SNR, equalised with the model's estimate; ``model=None`` is perfect channel knowledge.  Same sorting and
+    keys as ``get_test_stats``; the estimate comes from ``forward_pass``, so every estimator here works; the counts accumulate on the
+    device (``linksim.LinkAccumulator``) and are read once per loader.  A frame's data bits and noise are a function of
+    ``(seed, file_no)``, whichever estimator is measured: two estimators see the same link."""
+    from .linksim import LinkAccumulator
+    if model is not None:
+        model.eval()
+    stats: Dict[int, float] = {}
+    for name, loader in sorted(test_dataloaders, key=lambda x: int(x[0].split("_")[1])):
+        acc = None
+        with torch.no_grad():
+            for pilots, ideal, meta in loader:
+                est = None if model is None else forward_pass(model, pilots, meta)
+                if acc is None:
+                    acc = LinkAccumulator(link_cfg, ideal.device if est is None else est.device, seed)
+                acc.update(est, ideal, meta)
+        if acc is None:
+            raise ValueError(f"loader {name} yielded no batch")
+        stats[int(name.split("_")[1])] = acc.result(group)
+    return stats

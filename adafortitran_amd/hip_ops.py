@@ -483,6 +483,54 @@ class LmmsePlan:
         return est
 
 
+class LinkPlan:
+    """A link configuration (``linksim.LinkConfig``) turned into the ``aft_link`` struct ONCE.  ``plan(ideal, est, keys, sigma)`` ->
+    ``counts int32 [batch, 2]`` = (bit errors, symbol errors) per frame on the plan's device: one ``torch.empty``, one ``ctypes`` call,
+    one launch (``aft_link_errors_f32``) on the current stream of that device, no synchronisation.  ``ideal`` / ``est`` complex64
+    ``[batch,S,T]`` live on the plan's device; ``keys`` (int64, the 64-bit keys' bits) and ``sigma`` (float32), ``batch`` values each,
+    live there or in pinned host memory, which the kernel reads in place.  The plan trusts its caller in one thing only: its device
+    is the current one."""
+
+    def __init__(self, cfg, device: torch.device) -> None:
+        from .linksim import LinkConfig
+        if not isinstance(cfg, LinkConfig):
+            raise ValueError(f"LinkPlan needs a linksim.LinkConfig (got {type(cfg).__name__})")
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError(f"LinkPlan runs on a HIP device (got {device}); linksim.link_errors_host is the CPU path")
+        self.device = resolve_device(device)
+        self.cfg = cfg
+        self.link = cfg.to_struct()                             # validated by the config itself; the entry point checks again
+        self.grid = tuple(cfg.sim.ofdm)
+
+    def __call__(self, ideal: torch.Tensor, est: torch.Tensor, keys: torch.Tensor, sigma: torch.Tensor, lib=None) -> torch.Tensor:
+        lib = lib or _lib.load()
+        if ideal.dim() != 3 or tuple(ideal.shape[1:]) != self.grid or ideal.shape[0] < 1:
+            raise ValueError(f"Expected ideal shape (B >= 1, {self.grid[0]}, {self.grid[1]}), got {tuple(ideal.shape)}")
+        batch = ideal.shape[0]
+        if est.shape != ideal.shape:
+            raise ValueError(f"est must have ideal's shape {tuple(ideal.shape)}, got {tuple(est.shape)}")
+        for name, t in (("ideal", ideal), ("est", est)):
+            if t.dtype != torch.complex64:
+                raise ValueError(f"{name} must be complex64, got {t.dtype}")
+            if t.device != self.device:
+                raise ValueError(f"{name} must live on {self.device} (it is on {t.device})")
+        ideal, est = ideal.contiguous(), est.contiguous()      # held until after the launch is enqueued
+        small = []
+        for name, t, dtype in (("keys", keys, torch.int64), ("sigma", sigma, torch.float32)):
+            if t.dtype != dtype:
+                raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
+            if t.numel() != batch:
+                raise ValueError(f"{name} must hold one value per frame ({batch}), got {t.numel()}")
+            if not _readable_in_place(t, self.device):
+                raise ValueError(f"{name} must live on {self.device} or in pinned host memory (it is on {t.device}, not pinned)")
+            small.append(t.reshape(-1).contiguous())
+        counts = torch.empty((batch, 2), dtype=torch.int32, device=self.device)             # the kernel writes every element
+        _lib.check(lib.aft_link_errors_f32(C.addressof(self.link), ideal.data_ptr(), est.data_ptr(), small[0].data_ptr(),
+                                           small[1].data_ptr(), counts.data_ptr(), batch, _lib.current_stream_ptr(self.device)), lib)
+        return counts
+
+
 def ls_mse_db(ls: torch.Tensor, ideal: torch.Tensor) -> torch.Tensor:
     """Per-frame LS-baseline MSE in dB, float32 [B] (reference utils.py:248-261 per file)."""
     lib = _lib.load()

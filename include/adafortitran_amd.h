@@ -348,6 +348,45 @@ size_t aft_lmmse_table_floats(const aft_lmmse *plan);
 int aft_lmmse_f32(const aft_lmmse *plan, const float *tables, const float *pilots, const float *snr, const float *ds,
                   const float *dop, float *est, int batch, void *stream);
 
+/* ---- link-level bit errors (adafortitran_amd/linksim.py holds the definition) ----
+ *
+ * What a channel estimate is for: data symbols go through the TRUE channel H plus noise, a one-tap equaliser uses the ESTIMATE E, a hard
+ * demapper decides, and the wrong bits are counted.  Per frame, with key kf (for simulated frames the simulator's,
+ * splitmix64(splitmix64(seed) ^ g)), noise scale sigma and m = bits_per_symbol in {2, 4, 6, 8} (square QAM, L = 2^(m/2) levels per
+ * axis, d = sqrt(3 / (2 (L^2 - 1))): unit mean symbol energy), over every grid element (s, t) that is not a pilot position
+ * (pilot_sc_index x pilot_symbol_index), q = s T + t:
+ *   word(stream, q) = splitmix64(kf ^ (stream << 32 | q)); streams 5 data bits, 6 data-noise radius, 7 data-noise angle (0..4 are the
+ *                     simulator's)
+ *   sent bits   w = word(5, q) >> (64 - m);  Gray codes gi = w >> (m/2), gq = w & (L - 1);  level k of a Gray code g: k ^ (k >> 1) = g
+ *   sent symbol x = d ((2 ki - (L-1)) + j (2 kq - (L-1)))
+ *   received    y = H[s,t] x + sigma sqrt(-ln u1) exp(j 2 pi u2),  u1 = ((word(6,q) >> 41) + 0.5) 2^-23,  u2 likewise from word(7,q)
+ *               (the simulator's Box-Muller; the angle is formed in turns and reduced before its sine and cosine)
+ *   decision    c = y conj(E[s,t]),  p = |E[s,t]|^2;  per axis (Re c for I, Im c for Q) the level is
+ *               k^ = #{b in 1..L-1 : component >= beta_b p},  beta_b = 2 d (b - L/2);  its Gray code is k^ ^ (k^ >> 1)
+ *   counts      bit errors = sum popcount(gi ^ g^i) + popcount(gq ^ g^q);  symbol errors = elements with any bit wrong
+ * Zero-forcing with a hard decision and without a division: a total function, no special case for p = 0.  Everything per element is
+ * float32, products are fused multiply-add chains; d is formed in double and rounded to float once.  The struct is declared and then
+ * named, in two statements; it is the C type `typedef struct aft_link { ... } aft_link;` would give. */
+struct aft_link {
+    int32_t num_scs, num_symbols;              /* OFDM grid S x T, any size with S T <= 2^31                 */
+    int32_t pilot_scs, pilot_symbols;          /* pilot grid Ps x Pt, at most 64 x 16 (the simulator's)      */
+    int32_t bits_per_symbol, reserved;         /* 2, 4, 6 or 8                                               */
+    int32_t pilot_sc_index[AFT_CHANSIM_MAX_PILOT_SCS], pilot_symbol_index[AFT_CHANSIM_MAX_PILOT_SYMBOLS];   /* strictly increasing */
+};
+typedef struct aft_link aft_link;
+
+/* One launch, one workgroup per frame: counts int32 [batch][2] = (bit errors, symbol errors) of each frame (device memory) from ideal
+ * and est complex64 [batch, S, T] (device memory), keys uint64 [batch] and sigma float32 [batch]; keys and sigma may be any
+ * device-addressable memory, pinned host memory included.  `link` is read during the call only and travels to the kernel by value.
+ * Every element of counts is written (no initialisation needed; a grid whose every element is a pilot gives (0, 0)); no atomics; nothing
+ * is synchronised; a frame's counts depend neither on batch, nor on its position in it, nor on the run.  16-byte loads when T is even
+ * and ideal and est are 16-byte aligned, 8-byte loads otherwise.
+ * Nothing is launched on AFT_ERR_ARG (a NULL pointer; ideal / est / keys not 8-byte or sigma / counts not 4-byte aligned; batch < 1) and
+ * AFT_ERR_SHAPE (a dimension below 1; S T above 2^31; a pilot grid beyond its bounds or larger than the grid; pilot indices not strictly
+ * increasing or outside the grid; bits_per_symbol not one of 2, 4, 6, 8). */
+int aft_link_errors_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys,
+                        const float *sigma, int32_t *counts, int batch, void *stream);
+
 /* ---- training path of the encoder ---- */
 
 /* Gradients of one nn.TransformerEncoderLayer: same fields and shapes as aft_layer_weights,
