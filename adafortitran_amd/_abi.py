@@ -201,15 +201,14 @@ SIGNATURES = {
     "aft_forward_prepacked_f32": (C.c_int, [cfgp, wp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, C.c_int, vp]),
     "aft_linear_forward_f32": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     "aft_mse_partial_f32": (C.c_int, [vp, vp, vp, C.c_longlong, vp]),
-    # the data formats either side of the path, the channel simulator, the LMMSE baseline
+    # the data formats either side of the path, the channel simulator, the LMMSE baseline, the link-level error count
     "aft_pilot_gather_f32": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     "aft_ls_mse_db_f32": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
     "aft_frame_gather_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_longlong, C.c_int, C.c_int, vp]),
     "aft_channel_sim_f32": (C.c_int, [C.POINTER(AftChanSim), C.c_ulonglong] + [C.c_longlong] * 4 + [C.c_int, vp, vp, vp, vp]),
     "aft_lmmse_table_floats": (C.c_size_t, [C.POINTER(AftLmmse)]),
     "aft_lmmse_f32": (C.c_int, [C.POINTER(AftLmmse), vp, vp, vp, vp, vp, vp, C.c_int, vp]),
-    # aft_link * stays untyped: hip_ops.LinkPlan passes the address of the AftLink it keeps
-    "aft_link_errors_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, vp]),
+    "aft_link_errors_f32": (C.c_int, [C.POINTER(AftLink), vp, vp, vp, vp, vp, C.c_int, vp]),
     # training path
     "aft_encoder_tape_bytes": (C.c_size_t, [cfgp, C.c_int]),
     "aft_encoder_train_scratch_bytes": (C.c_size_t, [cfgp, C.c_int]),

@@ -34,7 +34,9 @@ import torch
 from . import _abi
 from .synth import _DOP_GRID, _DS_GRID, _M64, _SNR_GRID, _splitmix64
 
+# the streams of the counter-based hash (csrc/frame_device.h FrameStream): 0..4 the simulator's, 5..7 the link's (linksim.py)
 STREAM_CONDITION, STREAM_ANGLE, STREAM_PHASE, STREAM_NOISE_RADIUS, STREAM_NOISE_ANGLE = range(5)
+STREAM_DATA_BITS, STREAM_DATA_NOISE_RADIUS, STREAM_DATA_NOISE_ANGLE = range(5, 8)
 CHANNEL_TYPE = "SYNTH"
 
 
@@ -119,11 +121,17 @@ class ChannelSimConfig:
             "doppler_turns": (dop.astype(np.float64) * np.float64(self.symbol_period_s)).astype(np.float32),
         }
 
+    def fill_grid(self, struct):
+        """The OFDM grid, the pilot grid and the pilot positions into a struct that carries them (``aft_chansim``, ``aft_link``)."""
+        struct.num_scs, struct.num_symbols = self.ofdm
+        struct.pilot_scs, struct.pilot_symbols = self.pilot
+        struct.pilot_sc_index[:len(self.pilot_scs)] = self.pilot_scs
+        struct.pilot_symbol_index[:len(self.pilot_symbols)] = self.pilot_symbols
+        return struct
+
     def to_struct(self) -> "_abi.AftChanSim":
         t = self.tables()
-        sim = _abi.AftChanSim()
-        sim.num_scs, sim.num_symbols = self.ofdm
-        sim.pilot_scs, sim.pilot_symbols = self.pilot
+        sim = self.fill_grid(_abi.AftChanSim())
         sim.taps, sim.rays = len(t["tap_delay"]), self.rays
         sim.n_snr, sim.n_ds, sim.n_dop = len(self.snr_db), len(self.delay_spread_ns), len(self.doppler_hz)
         sim.subcarrier_spacing_hz, sim.symbol_period_s = float(self.subcarrier_spacing_hz), float(self.symbol_period_s)
@@ -131,14 +139,10 @@ class ChannelSimConfig:
             arr = getattr(sim, name)
             for i, v in enumerate(t[name]):
                 arr[i] = float(v)
-        for i, v in enumerate(self.pilot_scs):
-            sim.pilot_sc_index[i] = v
-        for i, v in enumerate(self.pilot_symbols):
-            sim.pilot_symbol_index[i] = v
         return sim
 
 
-# ---- the hash: written once, mirrored by csrc/k_chansim.hip ----------------------------------------------------------------
+# ---- the hash: written once, mirrored by csrc/frame_device.h ----------------------------------------------------------------
 
 def frame_keys(seed: int, frame_ids) -> np.ndarray:
     """``sm(sm(seed) ^ g)`` per frame, uint64."""

@@ -611,14 +611,6 @@ int aft_workspace_lanes(const aft_config *cfg, int batch, int *lanes, int *frame
     return AFT_OK;
 }
 
-#define AFT_REQUIRE(cond, ...)        \
-    do {                              \
-        if (!(cond)) {                \
-            set_error(__VA_ARGS__);   \
-            return AFT_ERR_ARG;       \
-        }                             \
-    } while (0)
-
 // one share of the batch: a complete forward on `st` in its own workspace slice
 static int forward_lane(const aft_config *cfg, const aft_weights *w, const float *prepacked, const float *pilots, const float *snr,
                         const float *ds, const float *dop, float *out, float *base, int batch, hipStream_t st, float *x_pt, float *vt2) {
@@ -791,132 +783,6 @@ int aft_frame_gather_f32(const float *ideal_all, const float *pilots_all, const 
     hipError_t e = launch_frame_gather(ideal_all, pilots_all, index, ideal_out, pilots_out, flags, batch, frames, grid_elems,
                                        pilot_elems, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? AFT_OK : hip_fail("frame_gather", e);
-}
-
-int aft_channel_sim_f32(const aft_chansim *sim, unsigned long long seed, long long base, long long start, long long stride,
-                        long long modulo, int batch, float *ideal, float *pilots, float *meta, void *stream) {
-    AFT_REQUIRE(sim && ideal && pilots && meta, "channel sim: NULL pointer argument");
-    AFT_REQUIRE((reinterpret_cast<uintptr_t>(ideal) | reinterpret_cast<uintptr_t>(pilots)) % 8 == 0,
-                "channel sim: ideal and pilots must be 8-byte aligned");
-    AFT_REQUIRE(reinterpret_cast<uintptr_t>(meta) % 4 == 0, "channel sim: meta must be 4-byte aligned");
-    AFT_REQUIRE(batch >= 1, "channel sim: batch must be at least 1 (got %d)", batch);
-    const long long far = 1LL << 62;
-    AFT_REQUIRE(base >= 0 && start >= 0 && stride >= 1 && modulo >= 1 && base < far && modulo < far && start < far &&
-                    stride <= (far - start) / batch,
-                "channel sim: bad frame numbers (base %lld, start %lld, stride %lld, modulo %lld: base, start >= 0, stride, modulo >= 1, "
-                "all frame numbers below 2^62)", base, start, stride, modulo);
-    auto shape = [](bool ok, const char *what, int got, int most) {
-        if (!ok) set_error("channel sim: %s = %d is outside 1..%d", what, got, most);
-        return ok;
-    };
-    auto within = [&](const char *what, int got, int most) { return shape(got >= 1 && got <= most, what, got, most); };
-    if (!within("num_scs", sim->num_scs, 1 << 20) || !within("num_symbols", sim->num_symbols, 1 << 20) ||
-        !within("pilot_scs", sim->pilot_scs, AFT_CHANSIM_MAX_PILOT_SCS) ||
-        !within("pilot_symbols", sim->pilot_symbols, AFT_CHANSIM_MAX_PILOT_SYMBOLS) || !within("taps", sim->taps, AFT_CHANSIM_MAX_TAPS) ||
-        !within("rays", sim->rays, AFT_CHANSIM_MAX_RAYS) || !within("n_snr", sim->n_snr, AFT_CHANSIM_MAX_VALUES) ||
-        !within("n_ds", sim->n_ds, AFT_CHANSIM_MAX_VALUES) || !within("n_dop", sim->n_dop, AFT_CHANSIM_MAX_VALUES))
-        return AFT_ERR_SHAPE;
-    for (int i = 0; i < sim->pilot_scs; ++i)
-        if (sim->pilot_sc_index[i] < 0 || sim->pilot_sc_index[i] >= sim->num_scs) {
-            set_error("channel sim: pilot_sc_index[%d] = %d is outside the grid's %d subcarriers", i, sim->pilot_sc_index[i], sim->num_scs);
-            return AFT_ERR_SHAPE;
-        }
-    for (int j = 0; j < sim->pilot_symbols; ++j)
-        if (sim->pilot_symbol_index[j] < 0 || sim->pilot_symbol_index[j] >= sim->num_symbols) {
-            set_error("channel sim: pilot_symbol_index[%d] = %d is outside the grid's %d symbols", j, sim->pilot_symbol_index[j],
-                      sim->num_symbols);
-            return AFT_ERR_SHAPE;
-        }
-    hipError_t e = launch_channel_sim(*sim, seed, base, start, stride, modulo, batch, ideal, pilots, meta, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? AFT_OK : hip_fail("channel_sim", e);
-}
-
-// the plan's own checks, shared by the size query and the launch; 0 = fine
-static int check_lmmse(const aft_lmmse *p) {
-    auto within = [](const char *what, int got, int least, int most) {
-        if (got < least || got > most) set_error("lmmse: %s = %d is outside %d..%d", what, got, least, most);
-        return got >= least && got <= most;
-    };
-    if (!within("num_scs", p->num_scs, 1, 1 << 20) || !within("num_symbols", p->num_symbols, 1, 1 << 20) ||
-        !within("pilot_scs", p->pilot_scs, 1, AFT_CHANSIM_MAX_PILOT_SCS) ||
-        !within("pilot_symbols", p->pilot_symbols, 1, AFT_CHANSIM_MAX_PILOT_SYMBOLS) ||
-        !within("n_snr", p->n_snr, 1, AFT_CHANSIM_MAX_VALUES) || !within("n_ds", p->n_ds, 1, AFT_CHANSIM_MAX_VALUES) ||
-        !within("n_dop", p->n_dop, 1, AFT_CHANSIM_MAX_VALUES) || !within("fixed_snr", p->fixed_snr, -1, p->n_snr - 1) ||
-        !within("fixed_ds", p->fixed_ds, -1, p->n_ds - 1) || !within("fixed_dop", p->fixed_dop, -1, p->n_dop - 1))
-        return AFT_ERR_SHAPE;
-    if (p->pilot_scs > p->num_scs || p->pilot_symbols > p->num_symbols) {
-        set_error("lmmse: the pilot grid %d x %d is larger than the ofdm grid %d x %d", p->pilot_scs, p->pilot_symbols, p->num_scs,
-                  p->num_symbols);
-        return AFT_ERR_SHAPE;
-    }
-    return AFT_OK;
-}
-
-size_t aft_lmmse_table_floats(const aft_lmmse *plan) {
-    if (plan == nullptr || check_lmmse(plan) != AFT_OK) return 0;
-    return (size_t)plan->n_ds * lmmse_fblock_floats(*plan) + (size_t)plan->n_dop * lmmse_tblock_floats(*plan);
-}
-
-int aft_lmmse_f32(const aft_lmmse *plan, const float *tables, const float *pilots, const float *snr, const float *ds,
-                  const float *dop, float *est, int batch, void *stream) {
-    AFT_REQUIRE(plan && tables && pilots && est, "lmmse: NULL pointer argument");
-    AFT_REQUIRE((reinterpret_cast<uintptr_t>(tables) | reinterpret_cast<uintptr_t>(pilots) | reinterpret_cast<uintptr_t>(est)) % 8 == 0,
-                "lmmse: tables, pilots and est must be 8-byte aligned");
-    AFT_REQUIRE((reinterpret_cast<uintptr_t>(snr) | reinterpret_cast<uintptr_t>(ds) | reinterpret_cast<uintptr_t>(dop)) % 4 == 0,
-                "lmmse: the condition arrays must be 4-byte aligned");
-    AFT_REQUIRE(batch >= 1, "lmmse: batch must be at least 1 (got %d)", batch);
-    const int rc = check_lmmse(plan);
-    if (rc != AFT_OK) return rc;
-    AFT_REQUIRE((snr || plan->fixed_snr >= 0) && (ds || plan->fixed_ds >= 0) && (dop || plan->fixed_dop >= 0),
-                "lmmse: NULL condition array whose fixed_* index is -1 (snr %p / %d, ds %p / %d, dop %p / %d)", (const void *)snr,
-                plan->fixed_snr, (const void *)ds, plan->fixed_ds, (const void *)dop, plan->fixed_dop);
-    hipError_t e = launch_lmmse(*plan, tables, pilots, snr, ds, dop, est, batch, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? AFT_OK : hip_fail("lmmse", e);
-}
-
-int aft_link_errors_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys,
-                        const float *sigma, int32_t *counts, int batch, void *stream) {
-    AFT_REQUIRE(link && ideal && est && keys && sigma && counts, "link errors: NULL pointer argument");
-    AFT_REQUIRE((reinterpret_cast<uintptr_t>(ideal) | reinterpret_cast<uintptr_t>(est) | reinterpret_cast<uintptr_t>(keys)) % 8 == 0,
-                "link errors: ideal, est and keys must be 8-byte aligned");
-    AFT_REQUIRE((reinterpret_cast<uintptr_t>(sigma) | reinterpret_cast<uintptr_t>(counts)) % 4 == 0,
-                "link errors: sigma and counts must be 4-byte aligned");
-    AFT_REQUIRE(batch >= 1, "link errors: batch must be at least 1 (got %d)", batch);
-    auto within = [](const char *what, int got, int most) {
-        if (got < 1 || got > most) set_error("link errors: %s = %d is outside 1..%d", what, got, most);
-        return got >= 1 && got <= most;
-    };
-    if (!within("num_scs", link->num_scs, INT32_MAX) || !within("num_symbols", link->num_symbols, INT32_MAX) ||
-        !within("pilot_scs", link->pilot_scs, AFT_CHANSIM_MAX_PILOT_SCS) ||
-        !within("pilot_symbols", link->pilot_symbols, AFT_CHANSIM_MAX_PILOT_SYMBOLS))
-        return AFT_ERR_SHAPE;
-    if ((unsigned long long)link->num_scs * (unsigned long long)link->num_symbols > (1ull << 31)) {
-        set_error("link errors: the grid %d x %d has more than 2^31 elements", link->num_scs, link->num_symbols);
-        return AFT_ERR_SHAPE;
-    }
-    if (link->pilot_scs > link->num_scs || link->pilot_symbols > link->num_symbols) {
-        set_error("link errors: the pilot grid %d x %d is larger than the ofdm grid %d x %d", link->pilot_scs, link->pilot_symbols,
-                  link->num_scs, link->num_symbols);
-        return AFT_ERR_SHAPE;
-    }
-    auto listed = [](const char *what, const int32_t *index, int n, int size) {
-        for (int i = 0; i < n; ++i)
-            if (index[i] < 0 || index[i] >= size || (i > 0 && index[i] <= index[i - 1])) {
-                set_error("link errors: %s[%d] = %d: the positions must be strictly increasing inside [0, %d)", what, i, index[i], size);
-                return false;
-            }
-        return true;
-    };
-    if (!listed("pilot_sc_index", link->pilot_sc_index, link->pilot_scs, link->num_scs) ||
-        !listed("pilot_symbol_index", link->pilot_symbol_index, link->pilot_symbols, link->num_symbols))
-        return AFT_ERR_SHAPE;
-    const int m = link->bits_per_symbol;
-    if (m != 2 && m != 4 && m != 6 && m != 8) {
-        set_error("link errors: bits_per_symbol = %d is not one of 2, 4, 6, 8", m);
-        return AFT_ERR_SHAPE;
-    }
-    hipError_t e = launch_link_errors(*link, ideal, est, keys, sigma, counts, batch, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? AFT_OK : hip_fail("link_errors", e);
 }
 
 int aft_debug_fill_lds_f32(float value, void *stream) {

@@ -1,0 +1,129 @@
+// aft_frames.hip -- the C ABI of the one-workgroup-per-frame kernels: the channel simulator, the LMMSE baseline and the link-level error
+// count.  Their structs start with the same four fields and two carry the pilot positions, so those checks are written once.
+#include "aft_internal.h"
+
+using namespace aft;
+
+namespace {
+
+bool within(const char *who, const char *what, int got, int least, int most) {
+    if (got < least || got > most) set_error("%s: %s = %d is outside %d..%d", who, what, got, least, most);
+    return got >= least && got <= most;
+}
+
+// num_scs, num_symbols in 1 .. most (the caller's bound), the pilot grid inside the bounds the kernels' LDS is sized for
+template <class Frame>
+bool grid_ok(const char *who, const Frame &f, int most) {
+    return within(who, "num_scs", f.num_scs, 1, most) && within(who, "num_symbols", f.num_symbols, 1, most) &&
+           within(who, "pilot_scs", f.pilot_scs, 1, AFT_CHANSIM_MAX_PILOT_SCS) &&
+           within(who, "pilot_symbols", f.pilot_symbols, 1, AFT_CHANSIM_MAX_PILOT_SYMBOLS);
+}
+
+template <class Frame>
+bool pilots_fit(const char *who, const Frame &f) {
+    if (f.pilot_scs <= f.num_scs && f.pilot_symbols <= f.num_symbols) return true;
+    set_error("%s: the pilot grid %d x %d is larger than the ofdm grid %d x %d", who, f.pilot_scs, f.pilot_symbols, f.num_scs, f.num_symbols);
+    return false;
+}
+
+// index[0 .. n) inside [0, size), `unit` of them; increasing: and each above the one before it
+bool index_ok(const char *who, const char *what, const int32_t *index, int n, int size, const char *unit, bool increasing) {
+    for (int i = 0; i < n; ++i) {
+        if (index[i] >= 0 && index[i] < size && !(increasing && i > 0 && index[i] <= index[i - 1])) continue;
+        if (increasing) set_error("%s: %s[%d] = %d: the positions must be strictly increasing inside [0, %d)", who, what, i, index[i], size);
+        else set_error("%s: %s[%d] = %d is outside the grid's %d %s", who, what, i, index[i], size, unit);
+        return false;
+    }
+    return true;
+}
+
+template <class Frame>
+bool pilot_index_ok(const char *who, const Frame &f, bool increasing) {
+    return index_ok(who, "pilot_sc_index", f.pilot_sc_index, f.pilot_scs, f.num_scs, "subcarriers", increasing) &&
+           index_ok(who, "pilot_symbol_index", f.pilot_symbol_index, f.pilot_symbols, f.num_symbols, "symbols", increasing);
+}
+
+// the plan's own checks, shared by the size query and the launch; 0 = fine
+int check_lmmse(const aft_lmmse *p) {
+    const char *who = "lmmse";
+    if (!grid_ok(who, *p, 1 << 20) || !within(who, "n_snr", p->n_snr, 1, AFT_CHANSIM_MAX_VALUES) ||
+        !within(who, "n_ds", p->n_ds, 1, AFT_CHANSIM_MAX_VALUES) || !within(who, "n_dop", p->n_dop, 1, AFT_CHANSIM_MAX_VALUES) ||
+        !within(who, "fixed_snr", p->fixed_snr, -1, p->n_snr - 1) || !within(who, "fixed_ds", p->fixed_ds, -1, p->n_ds - 1) ||
+        !within(who, "fixed_dop", p->fixed_dop, -1, p->n_dop - 1) || !pilots_fit(who, *p))
+        return AFT_ERR_SHAPE;
+    return AFT_OK;
+}
+
+template <class... P>
+bool aligned(size_t bytes, const P *...p) {
+    return (... | reinterpret_cast<uintptr_t>(p)) % bytes == 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int aft_channel_sim_f32(const aft_chansim *sim, unsigned long long seed, long long base, long long start, long long stride,
+                        long long modulo, int batch, float *ideal, float *pilots, float *meta, void *stream) {
+    const char *who = "channel sim";
+    AFT_REQUIRE(sim && ideal && pilots && meta, "channel sim: NULL pointer argument");
+    AFT_REQUIRE(aligned(8, ideal, pilots), "channel sim: ideal and pilots must be 8-byte aligned");
+    AFT_REQUIRE(aligned(4, meta), "channel sim: meta must be 4-byte aligned");
+    AFT_REQUIRE(batch >= 1, "channel sim: batch must be at least 1 (got %d)", batch);
+    const long long far = 1LL << 62;
+    AFT_REQUIRE(base >= 0 && start >= 0 && stride >= 1 && modulo >= 1 && base < far && modulo < far && start < far &&
+                    stride <= (far - start) / batch,
+                "channel sim: bad frame numbers (base %lld, start %lld, stride %lld, modulo %lld: base, start >= 0, stride, modulo >= 1, "
+                "all frame numbers below 2^62)", base, start, stride, modulo);
+    if (!grid_ok(who, *sim, 1 << 20) || !within(who, "taps", sim->taps, 1, AFT_CHANSIM_MAX_TAPS) ||
+        !within(who, "rays", sim->rays, 1, AFT_CHANSIM_MAX_RAYS) || !within(who, "n_snr", sim->n_snr, 1, AFT_CHANSIM_MAX_VALUES) ||
+        !within(who, "n_ds", sim->n_ds, 1, AFT_CHANSIM_MAX_VALUES) || !within(who, "n_dop", sim->n_dop, 1, AFT_CHANSIM_MAX_VALUES) ||
+        !pilot_index_ok(who, *sim, false))
+        return AFT_ERR_SHAPE;
+    hipError_t e = launch_channel_sim(*sim, seed, base, start, stride, modulo, batch, ideal, pilots, meta, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? AFT_OK : hip_fail("channel_sim", e);
+}
+
+size_t aft_lmmse_table_floats(const aft_lmmse *plan) {
+    if (plan == nullptr || check_lmmse(plan) != AFT_OK) return 0;
+    return (size_t)plan->n_ds * lmmse_fblock_floats(*plan) + (size_t)plan->n_dop * lmmse_tblock_floats(*plan);
+}
+
+int aft_lmmse_f32(const aft_lmmse *plan, const float *tables, const float *pilots, const float *snr, const float *ds,
+                  const float *dop, float *est, int batch, void *stream) {
+    AFT_REQUIRE(plan && tables && pilots && est, "lmmse: NULL pointer argument");
+    AFT_REQUIRE(aligned(8, tables, pilots, est), "lmmse: tables, pilots and est must be 8-byte aligned");
+    AFT_REQUIRE(aligned(4, snr, ds, dop), "lmmse: the condition arrays must be 4-byte aligned");
+    AFT_REQUIRE(batch >= 1, "lmmse: batch must be at least 1 (got %d)", batch);
+    const int rc = check_lmmse(plan);
+    if (rc != AFT_OK) return rc;
+    AFT_REQUIRE((snr || plan->fixed_snr >= 0) && (ds || plan->fixed_ds >= 0) && (dop || plan->fixed_dop >= 0),
+                "lmmse: NULL condition array whose fixed_* index is -1 (snr %p / %d, ds %p / %d, dop %p / %d)", (const void *)snr,
+                plan->fixed_snr, (const void *)ds, plan->fixed_ds, (const void *)dop, plan->fixed_dop);
+    hipError_t e = launch_lmmse(*plan, tables, pilots, snr, ds, dop, est, batch, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? AFT_OK : hip_fail("lmmse", e);
+}
+
+int aft_link_errors_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys,
+                        const float *sigma, int32_t *counts, int batch, void *stream) {
+    const char *who = "link errors";
+    AFT_REQUIRE(link && ideal && est && keys && sigma && counts, "link errors: NULL pointer argument");
+    AFT_REQUIRE(aligned(8, ideal, est, keys), "link errors: ideal, est and keys must be 8-byte aligned");
+    AFT_REQUIRE(aligned(4, sigma, counts), "link errors: sigma and counts must be 4-byte aligned");
+    AFT_REQUIRE(batch >= 1, "link errors: batch must be at least 1 (got %d)", batch);
+    if (!grid_ok(who, *link, INT32_MAX)) return AFT_ERR_SHAPE;
+    if ((unsigned long long)link->num_scs * (unsigned long long)link->num_symbols > (1ull << 31)) {
+        set_error("link errors: the grid %d x %d has more than 2^31 elements", link->num_scs, link->num_symbols);
+        return AFT_ERR_SHAPE;
+    }
+    if (!pilots_fit(who, *link) || !pilot_index_ok(who, *link, true)) return AFT_ERR_SHAPE;
+    const int m = link->bits_per_symbol;
+    if (m != 2 && m != 4 && m != 6 && m != 8) {
+        set_error("link errors: bits_per_symbol = %d is not one of 2, 4, 6, 8", m);
+        return AFT_ERR_SHAPE;
+    }
+    hipError_t e = launch_link_errors(*link, ideal, est, keys, sigma, counts, batch, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? AFT_OK : hip_fail("link_errors", e);
+}
+
+}  // extern "C"

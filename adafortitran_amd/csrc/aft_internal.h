@@ -220,6 +220,7 @@ int hip_fail(const char *what, hipError_t e);
         hipError_t e_ = (call);                             \
         if (e_ != hipSuccess) return hip_fail(name, e_);    \
     } while (0)
+#define AFT_REQUIRE(cond, ...) do { if (!(cond)) { set_error(__VA_ARGS__); return AFT_ERR_ARG; } } while (0)
 int check_config(const aft_config *c);
 // The launch sequence a configuration runs (aft_engine_of): decided by the configuration alone.
 bool packed_engine_ok(const aft_config &c);

@@ -16,14 +16,10 @@
 // Phases are formed in TURNS and reduced with x - floor(x) (exact in floating point) before sincospi, so the evaluation error of the
 // sine does not grow with the argument; what does grow is the rounding of the turn count itself (2^-24 relative), which is what the
 // bound of tests/test_chansim_gpu.py is made of.  No atomics, no reads of device buffers (lane-indexed table entries are read from the kernel-argument segment), every output element written exactly once.
-#include "aft_internal.h"
+#include "frame_device.h"
 
 namespace aft {
 namespace {
-
-constexpr int kSimThreads = 256;
-constexpr int kSimTile = 16;    // symbols per time tile
-constexpr int kSimCols = 8;     // columns one thread accumulates: 64 bytes of a row
 
 struct ChanSimArgs {
     aft_chansim c;
@@ -36,26 +32,8 @@ struct ChanSimArgs {
     int wide;                                      // 1: 16-byte stores into ideal
 };
 
-__host__ __device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
-__device__ __forceinline__ unsigned long long sim_word(unsigned long long kf, unsigned stream, unsigned index) {
-    return splitmix64(kf ^ ((unsigned long long)stream << 32 | index));
-}
-
 __device__ __forceinline__ int sim_pick(unsigned long long kf, unsigned which, int n) {
-    return (int)(((unsigned)(sim_word(kf, 0, which) >> 40) * (unsigned)n) >> 24);    // 24-bit word x n <= 16: fits 32 bits
-}
-
-// exp(j 2 pi x) for x in turns, any size: reduced to [0, 1] first
-__device__ __forceinline__ float2 cis_turns(float x) {
-    float s, c;
-    sincospif(2.f * (x - floorf(x)), &s, &c);
-    return make_float2(c, s);
+    return (int)(((unsigned)(frame_word(kf, kStreamCondition, which) >> 40) * (unsigned)n) >> 24);    // 24-bit word x n <= 16: fits 32 bits
 }
 
 __device__ __forceinline__ float2 tap_gain(const aft_chansim &c, const float2 *ray, int p, int t) {
@@ -77,9 +55,9 @@ __device__ __forceinline__ float2 delay_phasor(const aft_chansim &c, float tau, 
     return make_float2(z.x, -z.y);
 }
 
-__global__ __launch_bounds__(kSimThreads) void channel_sim_kernel(const ChanSimArgs a) {
+__global__ __launch_bounds__(kFrameThreads) void channel_sim_kernel(const ChanSimArgs a) {
     __shared__ float2 ray[AFT_CHANSIM_MAX_TAPS * AFT_CHANSIM_MAX_RAYS];
-    __shared__ float2 gain[AFT_CHANSIM_MAX_TAPS][kSimTile];
+    __shared__ float2 gain[AFT_CHANSIM_MAX_TAPS][kFrameTile];
     __shared__ float2 pgain[AFT_CHANSIM_MAX_TAPS][AFT_CHANSIM_MAX_PILOT_SYMBOLS];
     const aft_chansim &c = a.c;
     const int tid = threadIdx.x;
@@ -92,59 +70,46 @@ __global__ __launch_bounds__(kSimThreads) void channel_sim_kernel(const ChanSimA
     if (tid < 3) a.meta[3 * b + tid] = tid == 0 ? c.snr_db[i_snr] : tid == 1 ? c.delay_spread_ns[i_ds] : c.doppler_hz[i_dop];
     const float dop = a.doppler_turns[i_dop], tau = a.delay_turns[i_ds], sigma = c.noise_sigma[i_snr];
 
-    for (int i = tid; i < P * M; i += kSimThreads) {
+    for (int i = tid; i < P * M; i += kFrameThreads) {
         const int p = i / M, m = i - p * M;
         const unsigned idx = 16u * p + m;
-        const float u = (float)(unsigned)(sim_word(kf, 1, idx) >> 44) * 0x1p-20f;        // m + u is exact: 4 + 20 bits
+        const float u = (float)(unsigned)(frame_word(kf, kStreamRayAngle, idx) >> 44) * 0x1p-20f;        // m + u is exact: 4 + 20 bits
         const float turn = ((float)m + u) / (float)M;
-        const float phase = (float)(unsigned)(sim_word(kf, 2, idx) >> 40) * 0x1p-24f;
+        const float phase = (float)(unsigned)(frame_word(kf, kStreamRayPhase, idx) >> 40) * 0x1p-24f;
         ray[i] = make_float2(dop * cospif(2.f * turn), phase);
     }
     __syncthreads();
 
-    for (int t0 = 0; t0 < T; t0 += kSimTile) {
+    for (int t0 = 0; t0 < T; t0 += kFrameTile) {
         const bool first = t0 == 0;
         if (!first) __syncthreads();                                    // the previous tile's readers are done with `gain`
-        for (int i = tid; i < P * kSimTile + (first ? P * Pt : 0); i += kSimThreads) {
-            if (i < P * kSimTile) {
-                const int p = i / kSimTile, tt = i - p * kSimTile;
+        for (int i = tid; i < P * kFrameTile + (first ? P * Pt : 0); i += kFrameThreads) {
+            if (i < P * kFrameTile) {
+                const int p = i / kFrameTile, tt = i - p * kFrameTile;
                 gain[p][tt] = t0 + tt < T ? tap_gain(c, ray, p, t0 + tt) : make_float2(0.f, 0.f);
             } else {
-                const int q = i - P * kSimTile, p = q / Pt, j = q - p * Pt;
+                const int q = i - P * kFrameTile, p = q / Pt, j = q - p * Pt;
                 AFT_DEV_ASSERT(p < P && c.pilot_symbol_index[j] >= 0 && c.pilot_symbol_index[j] < T);
                 pgain[p][j] = tap_gain(c, ray, p, c.pilot_symbol_index[j]);
             }
         }
         __syncthreads();
 
-        const int groups = (min(T - t0, kSimTile) + kSimCols - 1) / kSimCols;
-        for (int i = tid; i < S * groups + (first ? Ps * Pt : 0); i += kSimThreads) {
+        const int groups = (min(T - t0, kFrameTile) + kFrameCols - 1) / kFrameCols;
+        for (int i = tid; i < S * groups + (first ? Ps * Pt : 0); i += kFrameThreads) {
             if (i < S * groups) {
-                const int hg = i / S, s = i - hg * S, col = kSimCols * hg;
-                float2 acc[kSimCols];
+                const int hg = i / S, s = i - hg * S, col = kFrameCols * hg;
+                float2 acc[kFrameCols];
 #pragma unroll
-                for (int j = 0; j < kSimCols; ++j) acc[j] = make_float2(0.f, 0.f);
+                for (int j = 0; j < kFrameCols; ++j) acc[j] = make_float2(0.f, 0.f);
                 for (int p = 0; p < P; ++p) {
                     const float2 e = delay_phasor(c, tau, p, s);
 #pragma unroll
-                    for (int j = 0; j < kSimCols; ++j) {
-                        const float2 h = gain[p][col + j];
-                        acc[j].x = fmaf(h.x, e.x, fmaf(-h.y, e.y, acc[j].x));
-                        acc[j].y = fmaf(h.x, e.y, fmaf(h.y, e.x, acc[j].y));
-                    }
+                    for (int j = 0; j < kFrameCols; ++j) cfma(acc[j], gain[p][col + j], e);
                 }
-                const int n = min(kSimCols, T - t0 - col);              // valid columns; even when T is
-                AFT_DEV_ASSERT(n >= 1 && s < S && t0 + col + n <= T);
-                float2 *row = a.ideal + (b * S + s) * (size_t)T + t0 + col;
-                if (a.wide) {
-#pragma unroll
-                    for (int j = 0; j < kSimCols; j += 2)
-                        if (j < n) *reinterpret_cast<f32x4 *>(row + j) = f32x4{acc[j].x, acc[j].y, acc[j + 1].x, acc[j + 1].y};
-                } else {
-#pragma unroll
-                    for (int j = 0; j < kSimCols; ++j)
-                        if (j < n) row[j] = acc[j];
-                }
+                const int n = min(kFrameCols, T - t0 - col);           // valid columns; even when T is
+                AFT_DEV_ASSERT(s < S && t0 + col + n <= T);
+                store_row_piece(a.ideal + (b * S + s) * (size_t)T + t0 + col, acc, n, a.wide);
             } else {
                 const int q = i - S * groups, pi = q / Pt, pj = q - pi * Pt, s = c.pilot_sc_index[pi];
                 AFT_DEV_ASSERT(pi < Ps && s >= 0 && s < S);
@@ -154,12 +119,8 @@ __global__ __launch_bounds__(kSimThreads) void channel_sim_kernel(const ChanSimA
                     re = fmaf(h.x, e.x, fmaf(-h.y, e.y, re));
                     im = fmaf(h.x, e.y, fmaf(h.y, e.x, im));
                 }
-                // Box-Muller on two uniforms (k + 0.5) 2^-23: exact in fp32, never 0, never 1
-                const float u1 = ((float)(unsigned)(sim_word(kf, 3, (unsigned)q) >> 41) + 0.5f) * 0x1p-23f;
-                const float u2 = ((float)(unsigned)(sim_word(kf, 4, (unsigned)q) >> 41) + 0.5f) * 0x1p-23f;
-                const float r = sigma * sqrtf(-logf(u1));
-                const float2 z = cis_turns(u2);
-                a.pilots[b * (size_t)(Ps * Pt) + q] = make_float2(fmaf(r, z.x, re), fmaf(r, z.y, im));
+                const FrameNoise nz = frame_noise(kf, kStreamPilotNoiseRadius, kStreamPilotNoiseAngle, (unsigned)q, sigma);
+                a.pilots[b * (size_t)(Ps * Pt) + q] = make_float2(fmaf(nz.r, nz.c, re), fmaf(nz.r, nz.s, im));
             }
         }
     }
@@ -179,8 +140,8 @@ hipError_t launch_channel_sim(const aft_chansim &sim, unsigned long long seed, l
     a.base = (unsigned long long)base; a.start = (unsigned long long)start;
     a.stride = (unsigned long long)stride; a.modulo = (unsigned long long)modulo;
     a.ideal = reinterpret_cast<float2 *>(ideal); a.pilots = reinterpret_cast<float2 *>(pilots); a.meta = meta;
-    a.wide = sim.num_symbols % 2 == 0 && reinterpret_cast<uintptr_t>(ideal) % 16 == 0 ? 1 : 0;
-    hipLaunchKernelGGL(channel_sim_kernel, dim3((unsigned)batch), dim3(kSimThreads), 0, st, a);
+    a.wide = wide_ok(sim.num_symbols, ideal);
+    hipLaunchKernelGGL(channel_sim_kernel, dim3((unsigned)batch), dim3(kFrameThreads), 0, st, a);
     return hipGetLastError();
 }
 

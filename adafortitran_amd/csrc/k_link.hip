@@ -7,20 +7,20 @@
 //      (T even -- a pair never straddles a row -- and both bases 16-byte aligned), one per 8-byte load otherwise.  An element whose
 //      column and row are both in the lists is a pilot and is skipped (two binary searches; the row's only when the column hit);
 //   3. per data element: three words of the counter-based hash (sent bits, noise radius, noise angle), the Gray-coded square-QAM
-//      symbol, y = H x + noise (the simulator's Box-Muller), c = y conj(E), p = |E|^2 and, per axis, the count of inner boundaries
-//      beta_b p at or below the component of c -- zero-forcing with a hard decision and without a division, total at p = 0;
+//      symbol, y = H x + noise (frame_device.h: the simulator's hash and Box-Muller), c = y conj(E), p = |E|^2 and, per axis, the
+//      count of inner boundaries beta_b p at or below the component of c -- zero-forcing with a hard decision and without a division,
+//      total at p = 0;
 //   4. the two integer counts stay in registers, are summed in the wave with shuffles and across the four waves through LDS, and two
 //      threads store the frame's pair, one count each.
 //
 // No atomics: integer sums do not depend on their order, so a frame's counts depend neither on the batch nor on the run.  The rounding
 // behind tests/test_linksim_gpu.py's margin: every product is a fused multiply-add chain, the angle is formed in turns, no fast-math.
-#include "aft_internal.h"
+#include "frame_device.h"
 
 namespace aft {
 namespace {
 
-constexpr int kLinkThreads = 256;
-constexpr int kLinkWaves = kLinkThreads / kWave;
+constexpr int kLinkWaves = kFrameThreads / kWave;
 
 struct LinkArgs {
     aft_link c;
@@ -32,18 +32,6 @@ struct LinkArgs {
     float d, d2;                // float(sqrt(3 / (2 (L^2 - 1)))) and twice that
     int wide;                   // 1: 16-byte loads of ideal and est
 };
-
-// the simulator's hash (k_chansim.hip splitmix64 / sim_word), written once for this file
-__device__ __forceinline__ unsigned long long link_splitmix64(unsigned long long x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
-__device__ __forceinline__ unsigned long long link_word(unsigned long long kf, unsigned stream, unsigned index) {
-    return link_splitmix64(kf ^ ((unsigned long long)stream << 32 | index));
-}
 
 // v in sorted[0 .. n): n <= 64
 __device__ __forceinline__ bool link_listed(const int *sorted, int n, int v) {
@@ -80,17 +68,12 @@ template <int M>
 __device__ __forceinline__ void link_element(const LinkArgs &a, unsigned long long kf, float sigma, unsigned q, float2 h, float2 e,
                                              LinkCounts &n) {
     constexpr int half = M / 2, L = 1 << half;
-    const unsigned w = (unsigned)(link_word(kf, 5, q) >> (64 - M));
+    const unsigned w = (unsigned)(frame_word(kf, kStreamDataBits, q) >> (64 - M));
     const unsigned gi = w >> half, gq = w & (unsigned)(L - 1);
     const float xr = a.d * (float)(2 * (int)gray_level(gi) - (L - 1)), xi = a.d * (float)(2 * (int)gray_level(gq) - (L - 1));
-    // Box-Muller on two uniforms (k + 0.5) 2^-23: exact in fp32, never 0, never 1 (k_chansim.hip's)
-    const float u1 = ((float)(unsigned)(link_word(kf, 6, q) >> 41) + 0.5f) * 0x1p-23f;
-    const float u2 = ((float)(unsigned)(link_word(kf, 7, q) >> 41) + 0.5f) * 0x1p-23f;
-    const float r = sigma * sqrtf(-logf(u1));
-    float sn, cs;
-    sincospif(2.f * (u2 - floorf(u2)), &sn, &cs);
-    const float yr = fmaf(r, cs, fmaf(h.x, xr, -(h.y * xi)));
-    const float yi = fmaf(r, sn, fmaf(h.x, xi, h.y * xr));
+    const FrameNoise nz = frame_noise(kf, kStreamDataNoiseRadius, kStreamDataNoiseAngle, q, sigma);
+    const float yr = fmaf(nz.r, nz.c, fmaf(h.x, xr, -(h.y * xi)));
+    const float yi = fmaf(nz.r, nz.s, fmaf(h.x, xi, h.y * xr));
     const float cr = fmaf(yr, e.x, yi * e.y);                   // y conj(E)
     const float ci = fmaf(yi, e.x, -(yr * e.y));
     const float step = a.d2 * fmaf(e.x, e.x, e.y * e.y);
@@ -101,7 +84,7 @@ __device__ __forceinline__ void link_element(const LinkArgs &a, unsigned long lo
 }
 
 template <int M>
-__global__ __launch_bounds__(kLinkThreads) void link_errors_kernel(const LinkArgs a) {
+__global__ __launch_bounds__(kFrameThreads) void link_errors_kernel(const LinkArgs a) {
     __shared__ int psc[AFT_CHANSIM_MAX_PILOT_SCS], psym[AFT_CHANSIM_MAX_PILOT_SYMBOLS];
     __shared__ int part[kLinkWaves][2];
     const aft_link &c = a.c;
@@ -124,7 +107,7 @@ __global__ __launch_bounds__(kLinkThreads) void link_errors_kernel(const LinkArg
     };
     if (a.wide) {
         const unsigned pairs = (last >> 1) + 1;                 // S T is even here
-        for (unsigned i = tid; i < pairs; i += kLinkThreads) {
+        for (unsigned i = tid; i < pairs; i += kFrameThreads) {
             const unsigned q = 2 * i;
             AFT_DEV_ASSERT(q + 1 <= last);
             const f32x4 h = *reinterpret_cast<const f32x4 *>(hp + q), e = *reinterpret_cast<const f32x4 *>(ep + q);
@@ -132,7 +115,7 @@ __global__ __launch_bounds__(kLinkThreads) void link_errors_kernel(const LinkArg
             if (data(q + 1)) link_element<M>(a, kf, sigma, q + 1, make_float2(h[2], h[3]), make_float2(e[2], e[3]), n);
         }
     } else {
-        for (unsigned i = tid; i <= last; i += kLinkThreads)     // last < 2^31: the index cannot wrap
+        for (unsigned i = tid; i <= last; i += kFrameThreads)    // last < 2^31: the index cannot wrap
             if (data(i)) link_element<M>(a, kf, sigma, i, hp[i], ep[i], n);
     }
 #pragma unroll
@@ -167,8 +150,8 @@ hipError_t launch_link_errors(const aft_link &link, const float *ideal, const fl
     const int L = 1 << (link.bits_per_symbol / 2);
     a.d = (float)sqrt(3.0 / (2.0 * ((double)L * L - 1.0)));
     a.d2 = 2.f * a.d;
-    a.wide = link.num_symbols % 2 == 0 && (reinterpret_cast<uintptr_t>(ideal) | reinterpret_cast<uintptr_t>(est)) % 16 == 0 ? 1 : 0;
-    const dim3 grid((unsigned)batch), block(kLinkThreads);
+    a.wide = wide_ok(link.num_symbols, ideal, est);
+    const dim3 grid((unsigned)batch), block(kFrameThreads);
     switch (link.bits_per_symbol) {
         case 2: hipLaunchKernelGGL(link_errors_kernel<2>, grid, block, 0, st, a); break;
         case 4: hipLaunchKernelGGL(link_errors_kernel<4>, grid, block, 0, st, a); break;

@@ -11,19 +11,16 @@
 //      tile's columns and accumulates F'[s][k] V[k][col ..] over k.  F' is stored k-major, so consecutive lanes read consecutive
 //      subcarriers (one coalesced 8-byte load per lane and k); V[k][col] is read by every lane of the wave from the same LDS address (a
 //      broadcast: no bank conflicts).  A thread's 8 results are 64 contiguous bytes of the row-major [S, T] plane and leave as four
-//      16-byte stores (T even, base 16-byte aligned; 8-byte stores otherwise) -- the simulator's store pattern and tile loop
-//      (k_chansim.hip), which is what lets T be anything: LDS holds one tile whatever the grid's length.
+//      16-byte stores (T even, base 16-byte aligned; 8-byte stores otherwise) -- the row-tile pass of frame_device.h, shared with
+//      the simulator, which is what lets T be anything: LDS holds one tile whatever the grid's length.
 //
 // No atomics, every output element written exactly once.  The rounding behind tests/test_lmmse_gpu.py's bound: every product stage is a
 // chain of fused multiply-adds in sequence, the table entries are float32 roundings of the host's double tables.
-#include "aft_internal.h"
+#include "frame_device.h"
 
 namespace aft {
 namespace {
 
-constexpr int kLmThreads = 256;
-constexpr int kLmTile = 16;     // symbols per time tile
-constexpr int kLmCols = 8;      // columns one thread accumulates: 64 bytes of a row
 constexpr int kLmMaxPs = AFT_CHANSIM_MAX_PILOT_SCS, kLmMaxPt = AFT_CHANSIM_MAX_PILOT_SYMBOLS;
 
 struct LmmseArgs {
@@ -47,10 +44,10 @@ __device__ __forceinline__ int nearest(const float *value, int n, float v) {
     return best;
 }
 
-__global__ __launch_bounds__(kLmThreads) void lmmse_kernel(const LmmseArgs a) {
+__global__ __launch_bounds__(kFrameThreads) void lmmse_kernel(const LmmseArgs a) {
     __shared__ float2 pc[kLmMaxPs * kLmMaxPt];       // the pilots, then C = D o Y
     __shared__ float2 y1[kLmMaxPs * kLmMaxPt];       // U_f^H P
-    __shared__ float2 v[kLmMaxPs][kLmTile];          // C T'^T, one time tile
+    __shared__ float2 v[kLmMaxPs][kFrameTile];       // C T'^T, one time tile
     const aft_lmmse &c = a.c;
     const int tid = threadIdx.x;
     const size_t b = blockIdx.x;
@@ -67,9 +64,9 @@ __global__ __launch_bounds__(kLmThreads) void lmmse_kernel(const LmmseArgs a) {
     const float *lf = fb + 2 * ((size_t)Ps * Ps + (size_t)Ps * S);                   // [Ps]
     const float *ut = tb, *tp = tb + Pt * Pt, *lt = tp + (size_t)Pt * T;             // [Pt(j)][Pt(l)], [Pt(l)][T], [Pt]
 
-    for (int i = tid; i < Ps * Pt; i += kLmThreads) pc[i] = a.pilots[b * (size_t)(Ps * Pt) + i];
+    for (int i = tid; i < Ps * Pt; i += kFrameThreads) pc[i] = a.pilots[b * (size_t)(Ps * Pt) + i];
     __syncthreads();
-    for (int i = tid; i < Ps * Pt; i += kLmThreads) {                               // y1[k][j] = sum_i conj(U_f[i][k]) P[i][j]
+    for (int i = tid; i < Ps * Pt; i += kFrameThreads) {                            // y1[k][j] = sum_i conj(U_f[i][k]) P[i][j]
         const int k = i / Pt, j = i - k * Pt;
         float re = 0.f, im = 0.f;
         for (int q = 0; q < Ps; ++q) {
@@ -81,7 +78,7 @@ __global__ __launch_bounds__(kLmThreads) void lmmse_kernel(const LmmseArgs a) {
         y1[i] = make_float2(re, im);
     }
     __syncthreads();                                                                // the pilots have been read: pc is free for C
-    for (int i = tid; i < Ps * Pt; i += kLmThreads) {                               // C[k][l] = D[k][l] sum_j y1[k][j] U_t[j][l]
+    for (int i = tid; i < Ps * Pt; i += kFrameThreads) {                            // C[k][l] = D[k][l] sum_j y1[k][j] U_t[j][l]
         const int k = i / Pt, l = i - k * Pt;
         float re = 0.f, im = 0.f;
         for (int j = 0; j < Pt; ++j) {
@@ -96,10 +93,10 @@ __global__ __launch_bounds__(kLmThreads) void lmmse_kernel(const LmmseArgs a) {
     }
     __syncthreads();
 
-    for (int t0 = 0; t0 < T; t0 += kLmTile) {
+    for (int t0 = 0; t0 < T; t0 += kFrameTile) {
         if (t0 != 0) __syncthreads();                                   // the previous tile's readers are done with `v`
-        for (int i = tid; i < Ps * kLmTile; i += kLmThreads) {          // v[k][tt] = sum_l C[k][l] T'[t0 + tt][l]
-            const int k = i / kLmTile, tt = i - k * kLmTile, t = t0 + tt;
+        for (int i = tid; i < Ps * kFrameTile; i += kFrameThreads) {    // v[k][tt] = sum_l C[k][l] T'[t0 + tt][l]
+            const int k = i / kFrameTile, tt = i - k * kFrameTile, t = t0 + tt;
             float re = 0.f, im = 0.f;
             if (t < T)
                 for (int l = 0; l < Pt; ++l) {
@@ -113,34 +110,21 @@ __global__ __launch_bounds__(kLmThreads) void lmmse_kernel(const LmmseArgs a) {
         }
         __syncthreads();
 
-        const int groups = (min(T - t0, kLmTile) + kLmCols - 1) / kLmCols;
-        for (int i = tid; i < S * groups; i += kLmThreads) {
-            const int hg = i / S, s = i - hg * S, col = kLmCols * hg;
-            float2 acc[kLmCols];
+        const int groups = (min(T - t0, kFrameTile) + kFrameCols - 1) / kFrameCols;
+        for (int i = tid; i < S * groups; i += kFrameThreads) {
+            const int hg = i / S, s = i - hg * S, col = kFrameCols * hg;
+            float2 acc[kFrameCols];
 #pragma unroll
-            for (int j = 0; j < kLmCols; ++j) acc[j] = make_float2(0.f, 0.f);
+            for (int j = 0; j < kFrameCols; ++j) acc[j] = make_float2(0.f, 0.f);
             for (int k = 0; k < Ps; ++k) {
-                AFT_DEV_ASSERT(s < S && col + kLmCols <= kLmTile);
+                AFT_DEV_ASSERT(s < S && col + kFrameCols <= kFrameTile);
                 const float2 f = fp[(size_t)k * S + s];
 #pragma unroll
-                for (int j = 0; j < kLmCols; ++j) {
-                    const float2 h = v[k][col + j];
-                    acc[j].x = fmaf(f.x, h.x, fmaf(-f.y, h.y, acc[j].x));
-                    acc[j].y = fmaf(f.x, h.y, fmaf(f.y, h.x, acc[j].y));
-                }
+                for (int j = 0; j < kFrameCols; ++j) cfma(acc[j], f, v[k][col + j]);
             }
-            const int n = min(kLmCols, T - t0 - col);                   // valid columns; even when T is
-            AFT_DEV_ASSERT(n >= 1 && s < S && t0 + col + n <= T);
-            float2 *row = a.est + (b * S + s) * (size_t)T + t0 + col;
-            if (a.wide) {
-#pragma unroll
-                for (int j = 0; j < kLmCols; j += 2)
-                    if (j < n) *reinterpret_cast<f32x4 *>(row + j) = f32x4{acc[j].x, acc[j].y, acc[j + 1].x, acc[j + 1].y};
-            } else {
-#pragma unroll
-                for (int j = 0; j < kLmCols; ++j)
-                    if (j < n) row[j] = acc[j];
-            }
+            const int n = min(kFrameCols, T - t0 - col);                // valid columns; even when T is
+            AFT_DEV_ASSERT(s < S && t0 + col + n <= T);
+            store_row_piece(a.est + (b * S + s) * (size_t)T + t0 + col, acc, n, a.wide);
         }
     }
 }
@@ -167,8 +151,8 @@ hipError_t launch_lmmse(const aft_lmmse &plan, const float *tables, const float 
     a.est = reinterpret_cast<float2 *>(est);
     a.fblock = lmmse_fblock_floats(plan);
     a.tblock = lmmse_tblock_floats(plan);
-    a.wide = plan.num_symbols % 2 == 0 && reinterpret_cast<uintptr_t>(est) % 16 == 0 ? 1 : 0;
-    hipLaunchKernelGGL(lmmse_kernel, dim3((unsigned)batch), dim3(kLmThreads), 0, st, a);
+    a.wide = wide_ok(plan.num_symbols, est);
+    hipLaunchKernelGGL(lmmse_kernel, dim3((unsigned)batch), dim3(kFrameThreads), 0, st, a);
     return hipGetLastError();
 }
 

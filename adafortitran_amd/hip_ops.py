@@ -32,6 +32,27 @@ def _readable_in_place(t: torch.Tensor, device: torch.device) -> bool:
     return t.device == device or (t.device.type == "cpu" and t.is_pinned())
 
 
+def _hip_device(device, who: str, cpu_path: str) -> torch.device:
+    """The device a plan of the frame kernels runs on; ``cpu_path`` is what the error points a CPU caller to."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise ValueError(f"{who} runs on a HIP device (got {device}); {cpu_path} is the CPU path")
+    return resolve_device(device)
+
+
+def _in_place(name: str, t: torch.Tensor, dtype: torch.dtype, device: torch.device, count: Optional[int] = None) -> torch.Tensor:
+    """``t`` as the contiguous flat tensor a kernel on ``device`` reads where it is: of ``dtype``, ``count`` values when given, on the
+    device or in pinned host memory -- checked on the flat tensor, since the copy that flattening a strided host tensor makes is pageable."""
+    if t.dtype != dtype:
+        raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
+    if count is not None and t.numel() != count:
+        raise ValueError(f"{name} must hold one value per frame ({count}), got {t.numel()}")
+    flat = t.reshape(-1).contiguous()
+    if not _readable_in_place(flat, device):
+        raise ValueError(f"{name} must live on {device} or in pinned host memory (it is on {flat.device}, not pinned)")
+    return flat
+
+
 def config_coverage(cfg: _abi.AftConfig) -> Optional[str]:
     """None when the gfx950 kernels cover ``cfg``, else the library's reason (``aft_check_config``)."""
     lib = _lib.load()
@@ -366,8 +387,7 @@ def frame_gather(ideal_all: torch.Tensor, pilots_all: torch.Tensor, index: torch
     for name, t in (("ideal_all", ideal_all), ("pilots_all", pilots_all)):
         if t.dtype != torch.complex64 or t.dim() < 2 or not t.is_contiguous() or t.shape[0] < 1 or t[0].numel() < 1:
             raise ValueError(f"{name} must be a contiguous complex64 array [n, ...] with n >= 1")
-        if not _readable_in_place(t, dev):
-            raise ValueError(f"{name} must live on {dev} or in pinned host memory (it is on {t.device}, not pinned)")
+        _in_place(name, t, torch.complex64, dev)
     if ideal_all.shape[0] != pilots_all.shape[0]:
         raise ValueError(f"ideal_all holds {ideal_all.shape[0]} frames, pilots_all {pilots_all.shape[0]}")
     plan = FrameGatherPlan(ideal_all, pilots_all, dev)
@@ -408,10 +428,7 @@ class ChannelSimPlan:
     The plan trusts its caller in one thing only: its device is the current one."""
 
     def __init__(self, cfg, device: torch.device) -> None:
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise ValueError(f"ChannelSimPlan runs on a HIP device (got {device}); chansim.simulate_frames_host is the CPU path")
-        self.device = resolve_device(device)
+        self.device = _hip_device(device, "ChannelSimPlan", "chansim.simulate_frames_host")
         self.cfg = cfg
         self.sim = cfg.to_struct()                              # validated by the config itself; the entry point checks again
         self.grid, self.pilot = tuple(cfg.ofdm), tuple(cfg.pilot)
@@ -437,10 +454,7 @@ class LmmsePlan:
 
     def __init__(self, cfg, device: torch.device, assume=None, image: Optional[torch.Tensor] = None) -> None:
         from .lmmse import LmmseTables
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise ValueError(f"LmmsePlan runs on a HIP device (got {device}); lmmse.lmmse_estimate_host is the CPU path")
-        self.device = resolve_device(device)
+        self.device = _hip_device(device, "LmmsePlan", "lmmse.lmmse_estimate_host")
         self.tables = cfg if isinstance(cfg, LmmseTables) else LmmseTables(cfg)
         self.plan = self.tables.to_struct(assume)
         self.fixed = (self.plan.fixed_snr, self.plan.fixed_ds, self.plan.fixed_dop)
@@ -453,19 +467,12 @@ class LmmsePlan:
                              f"{image.dtype} on {image.device})")
         self.image = image
 
-    def _readable(self, name: str, t: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
-        if t.dtype != dtype:
-            raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
-        if not _readable_in_place(t, self.device):
-            raise ValueError(f"{name} must live on {self.device} or in pinned host memory (it is on {t.device}, not pinned)")
-        return t.contiguous()
-
     def __call__(self, pilots: torch.Tensor, snr=None, ds=None, dop=None, lib=None) -> torch.Tensor:
         lib = lib or _lib.load()
         if pilots.dim() != 3 or tuple(pilots.shape[1:]) != self.pilot or pilots.shape[0] < 1:
             raise ValueError(f"Expected pilot shape (B >= 1, {self.pilot[0]}, {self.pilot[1]}), got {tuple(pilots.shape)}")
         batch = pilots.shape[0]
-        pil = self._readable("pilots", pilots, torch.complex64)
+        pil = _in_place("pilots", pilots, torch.complex64, self.device)
         conds = []
         for name, c, fixed in zip(("snr", "ds", "dop"), (snr, ds, dop), self.fixed):
             if c is None:
@@ -473,10 +480,7 @@ class LmmsePlan:
                     raise ValueError(f"{name} is required: assume does not pin it")
                 conds.append(None)
                 continue
-            c = self._readable(name, c.reshape(-1), torch.float32)
-            if c.numel() != batch:
-                raise ValueError(f"{name} must hold one value per frame ({batch}), got {c.numel()}")
-            conds.append(c)
+            conds.append(_in_place(name, c, torch.float32, self.device, batch))
         est = torch.empty((batch, *self.grid), dtype=torch.complex64, device=self.device)   # the kernel writes every element
         _lib.check(lib.aft_lmmse_f32(C.byref(self.plan), self.image.data_ptr(), pil.data_ptr(), *(_ptr(c) for c in conds),
                                      est.data_ptr(), batch, _lib.current_stream_ptr(self.device)), lib)
@@ -495,10 +499,7 @@ class LinkPlan:
         from .linksim import LinkConfig
         if not isinstance(cfg, LinkConfig):
             raise ValueError(f"LinkPlan needs a linksim.LinkConfig (got {type(cfg).__name__})")
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise ValueError(f"LinkPlan runs on a HIP device (got {device}); linksim.link_errors_host is the CPU path")
-        self.device = resolve_device(device)
+        self.device = _hip_device(device, "LinkPlan", "linksim.link_errors_host")
         self.cfg = cfg
         self.link = cfg.to_struct()                             # validated by the config itself; the entry point checks again
         self.grid = tuple(cfg.sim.ofdm)
@@ -516,18 +517,11 @@ class LinkPlan:
             if t.device != self.device:
                 raise ValueError(f"{name} must live on {self.device} (it is on {t.device})")
         ideal, est = ideal.contiguous(), est.contiguous()      # held until after the launch is enqueued
-        small = []
-        for name, t, dtype in (("keys", keys, torch.int64), ("sigma", sigma, torch.float32)):
-            if t.dtype != dtype:
-                raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
-            if t.numel() != batch:
-                raise ValueError(f"{name} must hold one value per frame ({batch}), got {t.numel()}")
-            if not _readable_in_place(t, self.device):
-                raise ValueError(f"{name} must live on {self.device} or in pinned host memory (it is on {t.device}, not pinned)")
-            small.append(t.reshape(-1).contiguous())
+        keys = _in_place("keys", keys, torch.int64, self.device, batch)
+        sigma = _in_place("sigma", sigma, torch.float32, self.device, batch)
         counts = torch.empty((batch, 2), dtype=torch.int32, device=self.device)             # the kernel writes every element
-        _lib.check(lib.aft_link_errors_f32(C.addressof(self.link), ideal.data_ptr(), est.data_ptr(), small[0].data_ptr(),
-                                           small[1].data_ptr(), counts.data_ptr(), batch, _lib.current_stream_ptr(self.device)), lib)
+        _lib.check(lib.aft_link_errors_f32(C.byref(self.link), ideal.data_ptr(), est.data_ptr(), keys.data_ptr(), sigma.data_ptr(),
+                                           counts.data_ptr(), batch, _lib.current_stream_ptr(self.device)), lib)
         return counts
 
 

@@ -45,10 +45,9 @@ import numpy as np
 import torch
 
 from . import _abi
-from .chansim import ChannelSimConfig, frame_keys, words
+from .chansim import STREAM_DATA_BITS, STREAM_DATA_NOISE_ANGLE, STREAM_DATA_NOISE_RADIUS, ChannelSimConfig, frame_keys, words
 from .synth import _splitmix64
 
-STREAM_DATA_BITS, STREAM_DATA_NOISE_RADIUS, STREAM_DATA_NOISE_ANGLE = 5, 6, 7
 BITS_PER_SYMBOL = (2, 4, 6, 8)
 _POPCOUNT = np.array([bin(i).count("1") for i in range(16)], dtype=np.int64)
 
@@ -95,14 +94,8 @@ class LinkConfig:
         return self.bits_per_symbol * self.data_elements
 
     def to_struct(self) -> "_abi.AftLink":
-        p = _abi.AftLink()
-        p.num_scs, p.num_symbols = self.sim.ofdm
-        p.pilot_scs, p.pilot_symbols = self.sim.pilot
+        p = self.sim.fill_grid(_abi.AftLink())
         p.bits_per_symbol = self.bits_per_symbol
-        for i, v in enumerate(self.sim.pilot_scs):
-            p.pilot_sc_index[i] = v
-        for i, v in enumerate(self.sim.pilot_symbols):
-            p.pilot_symbol_index[i] = v
         return p
 
 

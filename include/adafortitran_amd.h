@@ -365,15 +365,13 @@ int aft_lmmse_f32(const aft_lmmse *plan, const float *tables, const float *pilot
  *               k^ = #{b in 1..L-1 : component >= beta_b p},  beta_b = 2 d (b - L/2);  its Gray code is k^ ^ (k^ >> 1)
  *   counts      bit errors = sum popcount(gi ^ g^i) + popcount(gq ^ g^q);  symbol errors = elements with any bit wrong
  * Zero-forcing with a hard decision and without a division: a total function, no special case for p = 0.  Everything per element is
- * float32, products are fused multiply-add chains; d is formed in double and rounded to float once.  The struct is declared and then
- * named, in two statements; it is the C type `typedef struct aft_link { ... } aft_link;` would give. */
-struct aft_link {
+ * float32, products are fused multiply-add chains; d is formed in double and rounded to float once. */
+typedef struct aft_link {
     int32_t num_scs, num_symbols;              /* OFDM grid S x T, any size with S T <= 2^31                 */
     int32_t pilot_scs, pilot_symbols;          /* pilot grid Ps x Pt, at most 64 x 16 (the simulator's)      */
     int32_t bits_per_symbol, reserved;         /* 2, 4, 6 or 8                                               */
     int32_t pilot_sc_index[AFT_CHANSIM_MAX_PILOT_SCS], pilot_symbol_index[AFT_CHANSIM_MAX_PILOT_SYMBOLS];   /* strictly increasing */
-};
-typedef struct aft_link aft_link;
+} aft_link;
 
 /* One launch, one workgroup per frame: counts int32 [batch][2] = (bit errors, symbol errors) of each frame (device memory) from ideal
  * and est complex64 [batch, S, T] (device memory), keys uint64 [batch] and sigma float32 [batch]; keys and sigma may be any

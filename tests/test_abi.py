@@ -35,7 +35,7 @@ _CTYPES_KINDS = {ctypes.c_int: "i32", ctypes.c_size_t: "u64", ctypes.c_uint64: "
                  ctypes.c_longlong: "i64", ctypes.c_float: "f32", ctypes.c_double: "f64"}
 _C_RETURNS = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "const char *": ctypes.c_char_p}
 _MIRRORS = {"aft_config": _abi.AftConfig, "aft_layer_weights": _abi.AftLayerWeights, "aft_weights": _abi.AftWeights,
-            "aft_chansim": _abi.AftChanSim, "aft_lmmse": _abi.AftLmmse, "aft_layer_grads": _abi.AftLayerGrads,
+            "aft_chansim": _abi.AftChanSim, "aft_lmmse": _abi.AftLmmse, "aft_link": _abi.AftLink, "aft_layer_grads": _abi.AftLayerGrads,
             "aft_step_control": _abi.AftStepControl}
 _STRUCTS_PASSED_AS_VOID_P = {"aft_step_control"}        # optim.py keeps the control block in a tensor and passes its address
 
@@ -125,7 +125,7 @@ def test_struct_mirrors_match_the_header_field_by_field():
     """Every typedef'd struct of the header against its ctypes mirror: the same field names in the same order, each of the same kind
     and array extent (resolved through the header's own #defines), a pointer to another struct typed as that struct's mirror."""
     structs = re.findall(r"typedef\s+struct\s*\w*\s*\{(.*?)\}\s*(\w+)\s*;", _header_text(), flags=re.S)
-    assert sorted(name for _, name in structs) == sorted(_MIRRORS) and len(structs) == 7
+    assert sorted(name for _, name in structs) == sorted(_MIRRORS) and len(structs) == 8
     for body, name in structs:
         fields = [f for stmt in body.split(";") if stmt.strip() for f in _c_declarations(" ".join(stmt.split()), name)]
         mirror = _MIRRORS[name]._fields_

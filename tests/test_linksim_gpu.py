@@ -237,12 +237,12 @@ def test_the_8_byte_load_form_on_bases_off_16_bytes(m):
     fh[1:], fe[1:] = h.reshape(-1), e.reshape(-1)
     assert (fh.data_ptr() + 8) % 16 == 8 and (fe.data_ptr() + 8) % 16 == 8
     counts = torch.full((37, 2), POISON, dtype=torch.int32, device=DEV)
-    _lib.check(_lib.load().aft_link_errors_f32(ctypes.addressof(plan.link), fh.data_ptr() + 8, fe.data_ptr() + 8, k.data_ptr(),
+    _lib.check(_lib.load().aft_link_errors_f32(ctypes.byref(plan.link), fh.data_ptr() + 8, fe.data_ptr() + 8, k.data_ptr(),
                                                s.data_ptr(), counts.data_ptr(), 37, _lib.current_stream_ptr(counts.device)))
     _same_bits([counts], [want])
     # ... and with one base only off: still the 8-byte form
     counts.fill_(POISON)
-    _lib.check(_lib.load().aft_link_errors_f32(ctypes.addressof(plan.link), h.data_ptr(), fe.data_ptr() + 8, k.data_ptr(),
+    _lib.check(_lib.load().aft_link_errors_f32(ctypes.byref(plan.link), h.data_ptr(), fe.data_ptr() + 8, k.data_ptr(),
                                                s.data_ptr(), counts.data_ptr(), 37, _lib.current_stream_ptr(counts.device)))
     _same_bits([counts], [want])
 
@@ -334,7 +334,7 @@ def test_every_refusal_of_the_entry_point_launches_nothing():
     def call(p=None, **kw):
         a = dict(good, **kw)
         p = cfg.to_struct() if p is None else p
-        return lib.aft_link_errors_f32(ctypes.addressof(p), a["ideal"], a["est"], a["keys"], a["sigma"], a["counts"], a["batch"], None)
+        return lib.aft_link_errors_f32(ctypes.byref(p), a["ideal"], a["est"], a["keys"], a["sigma"], a["counts"], a["batch"], None)
 
     def refused(code, word, p=None, **kw):
         rc = call(p, **kw)
