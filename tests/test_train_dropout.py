@@ -9,7 +9,6 @@ per kernel family; (c) the A/B variants; (d) two backward passes accumulated int
 Bounds of (b) .. (e), per tensor, relative to the float64 tensor's max: max(project bound, 2 * e_torch32 + 1e-6), project bound =
 5e-5 forward, 2e-4 gradients (3e-4 through a stack), e_torch32 = the error of the same composite in float32 on the GPU.  The HIP
 result never enters a bound.  tools/debug/dropout_vs_fp64.py prints every figure; profiles/dropout_vs_fp64.json holds them."""
-import ctypes as C
 import functools
 
 import numpy as np
@@ -18,6 +17,7 @@ import torch
 
 import dropout_reference as R
 from adafortitran_amd import _abi
+from train_tape import forward_tape
 
 gpu = pytest.mark.gpu
 
@@ -100,32 +100,6 @@ def test_relu_cases_have_a_margin_cpu(case):
 
 # ---------------------------------------------------------------- GPU
 
-def _forward_tape(cfg, ps, x, p, seed):
-    """aft_encoder_layer_fwd_train_f32 called directly: the layer output and the tape's regions (plan_tape's order, each rounded
-    up to 64 floats)."""
-    from adafortitran_amd import _lib
-    from adafortitran_amd.training import _layer_struct
-    lib = _lib.load()
-    planes, tokens, d = x.shape
-    heads, rows, batch = cfg.num_head, planes * tokens, planes // 2
-    params = [q.cuda().contiguous() for q in ps]
-    x = x.cuda().contiguous()
-    out = torch.empty_like(x)
-    tape = torch.zeros(lib.aft_encoder_tape_bytes(C.byref(cfg), batch), dtype=torch.uint8, device="cuda")
-    scratch = torch.empty(lib.aft_encoder_train_scratch_bytes(C.byref(cfg), batch), dtype=torch.uint8, device="cuda")
-    w = _layer_struct(_abi.AftLayerWeights, params)
-    _lib.check(lib.aft_encoder_layer_fwd_train_f32(C.byref(cfg), C.byref(w), x.data_ptr(), out.data_ptr(), tape.data_ptr(), tape.numel(),
-                                                   scratch.data_ptr(), scratch.numel(), batch, p, seed, _lib.current_stream_ptr(x.device)))
-    torch.cuda.synchronize()
-    layout = (("qkv", 3 * d), ("attn", d), ("lse", heads), ("s1", d), ("st1", 2), ("x1", d), ("a", 2 * d), ("hd", 2 * d), ("s2", d),
-              ("st2", 2))
-    f, off, seg = tape.view(torch.float32), 0, {"out": out.cpu().numpy(), "x": x.cpu().numpy().reshape(rows, d)}
-    for name, cols in layout:
-        seg[name] = f[off:off + rows * cols].reshape(rows, cols).cpu().numpy()
-        off += (rows * cols + 63) // 64 * 64
-    return seg
-
-
 def _bits(a):
     return np.ascontiguousarray(a).view(np.uint32)
 
@@ -151,7 +125,7 @@ def test_kernel_masks_are_the_restated_masks(d, heads, ofdm, p):
     ks = R.keep_scale(p)
     x, _, ps = R.make_case(d, heads, tokens, planes, seed=17)
     m0, m1, m2, m3 = R.layer_masks(seed, p, planes, heads, tokens, d)
-    t = _forward_tape(cfg, ps, x, p, seed)
+    t = forward_tape(cfg, ps, x, p, seed)
 
     a64 = torch.from_numpy(t["a"]).double()
     g64 = torch.nn.functional.gelu(a64).numpy()
@@ -179,7 +153,7 @@ def test_kernel_masks_are_the_restated_masks(d, heads, ofdm, p):
         for h in range(heads):
             for f in range(tokens):
                 crafted[0][2 * d + h * 32 + f, f] = 1.0
-        attn = _forward_tape(cfg, crafted, xs, p, seed)["attn"].reshape(planes, tokens, heads, 32)
+        attn = forward_tape(cfg, crafted, xs, p, seed)["attn"].reshape(planes, tokens, heads, 32)
         got = attn[..., :tokens].transpose(0, 2, 1, 3)                       # [plane, head, q, k]
         assert np.array_equal(got != 0, m0), f"site 0: {int(((got != 0) != m0).sum())} elements differ"
         assert not attn[..., tokens:].any()
