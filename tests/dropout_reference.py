@@ -106,8 +106,11 @@ def attention(q, k, v, m0, ks0, defect=None):
     kernel can get wrong at the last key or query of a plane (the tests of the token-edge bounds): ``last_key_left_out`` -- the
     softmax runs over every key but the last; ``phantom_key`` -- one more key with score 0 and value 0, what a range mask one key
     too long produces; ``last_query_detached_kv`` -- the last query row reads detached k and v (its q stays live), so it
-    contributes nothing to dK and dV."""
+    contributes nothing to dK and dV; ``last_value_zeroed`` (the inference matrix, tests/infer_edges.py; not in DEFECTS) -- the last key
+    keeps its softmax weight but contributes a zero value, what a V^T padding mask one column too long produces."""
     scale = 1.0 / math.sqrt(q.shape[-1])
+    if defect == "last_value_zeroed":
+        v = torch.cat([v[..., :-1, :], torch.zeros_like(v[..., -1:, :])], dim=-2)
     s = q @ k.transpose(-1, -2) * scale if defect != "last_query_detached_kv" else torch.cat(
         [q[..., :-1, :] @ k.transpose(-1, -2), q[..., -1:, :] @ k.detach().transpose(-1, -2)], dim=-2) * scale
     if defect == "last_key_left_out":

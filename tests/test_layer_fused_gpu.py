@@ -144,6 +144,119 @@ def test_a_workspace_without_room_runs_the_launches(switches):
     assert torch.isnan(buf[small // 4:]).all()
 
 
+# ---- every layer_kernel instantiation, walks of more than one tile per workgroup, lanes, stale workspaces ----
+# d = 128, 4 heads.  Token count -> (grid, patch): N tokens are the grid (3 N, 2) at patch 3 x 2 except where noted.
+GRIDS = {280: ((120, 14), (3, 2)), 210: ((120, 14), (4, 2)), 512: ((192, 16), (3, 2))}
+INSTANTIATION_TOKENS = [32, 33, 40, 41, 64, 65, 210, 280]
+
+
+def _spec(tokens, layers):
+    ofdm, patch = GRIDS.get(tokens, ((3 * tokens, 2), (3, 2)))
+    return dict(DEFAULT_SPEC, ofdm=ofdm, patch=patch, num_layers=layers)
+
+
+def _setup_act(tokens, layers, act, adaptive, batch, seed):
+    """_setup on the token count's grid; the activation is the configuration's alone (the synthetic weights do not know it)."""
+    eng, pil, meta, rest = _setup(_spec(tokens, layers), (7, 42, 2 * tokens) if adaptive else None, batch, seed)
+    eng.cfg.activation = _abi.AFT_ACT_GELU if act == "gelu" else _abi.AFT_ACT_RELU
+    assert eng.tokens == tokens
+    return eng, pil, meta, rest
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tokens", INSTANTIATION_TOKENS)
+@pytest.mark.parametrize("layers", [1, 2, 3])
+@pytest.mark.parametrize("act", ["gelu", "relu"])
+def test_every_instantiation_matches_launch_path(switches, act, layers, tokens):
+    """layer_kernel<activation, last layer or not, 280 tokens or any count> at batch 2: 32 tokens are one tile and one key tile per
+    plane; a single layer runs only the first launch and the last-layer kernel; three layers end on the other K / V^T buffer than two.
+    Adaptive on for half of the cases."""
+    adaptive = (INSTANTIATION_TOKENS.index(tokens) + layers + (act == "relu")) % 2 == 0
+    eng, pil, meta, _ = _setup_act(tokens, layers, act, adaptive, 2, seed=800 + 10 * tokens + layers)
+    a, b = _both(switches, eng, pil, meta, 2)
+    assert torch.equal(a, b)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("act", ["gelu", "relu"])
+def test_xcd_remap_below_the_resident_count_matches_launch_path(switches, act):
+    """Batch 4 at 280 tokens: 8 planes x 9 tiles = 72 workgroups, a multiple of 8 -- the XCD remap is active on a grid smaller than the
+    co-resident workgroup count."""
+    eng, pil, meta, _ = _setup_act(280, 2, act, act == "relu", 4, seed=850)
+    a, b = _both(switches, eng, pil, meta, 4)
+    assert torch.equal(a, b)
+
+
+def _slots():
+    return 3 * torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def _ceil_div(a, b):
+    return -(-a // b)
+
+
+# (tokens, act, layers, frames as a function of slots = 3 x CUs).  At 256 CUs: 43 frames = 774 tiles, a few workgroups take a second tile
+# and the remap is active; 64 frames = 1.5 rounds; 193 frames of 33 tokens = 772 tiles, a second-round tile may hold a single valid row;
+# 25 frames of 512 tokens = 800 tiles of 16 per plane on the run-time count.
+WALKS = {"280tok_a_few_second_tiles": (280, "gelu", 2, lambda s: _ceil_div(s + 1, 18)),
+         "280tok_one_and_a_half_rounds": (280, "gelu", 2, lambda s: _ceil_div(3 * s, 2 * 18)),
+         "33tok_relu_three_layers": (33, "relu", 3, lambda s: _ceil_div(s + 1, 4)),
+         "512tok_relu_one_layer": (512, "relu", 1, lambda s: _ceil_div(s + 1, 32))}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("walk", list(WALKS))
+def test_partial_second_round_matches_launch_path(switches, walk):
+    """One lane, more plane-aligned tiles than the 3 x CUs workgroups of the persistent grid, a partial last round: the workgroups that
+    take a second tile, and the ones that do not, carry the bits of the launches; the last three frames -- second-round tiles -- equal a
+    3-frame call on those frames."""
+    tokens, act, layers, frames_of = WALKS[walk]
+    slots = _slots()
+    batch = frames_of(slots)
+    tiles = 2 * batch * _ceil_div(tokens, 32)
+    assert slots < tiles < 2 * slots, (slots, tiles)
+    switches.set("AFT_LANES", "1")
+    eng, pil, meta, _ = _setup_act(tokens, layers, act, walk.startswith("280"), batch, seed=900 + tokens)
+    launches, big = _both(switches, eng, pil, meta, batch)
+    assert torch.equal(big, launches)
+    k = batch - 3      # (a workgroup's second tile is its first + the grid size: the second round is the last tiles, so the last frames)
+    small = torch.view_as_real(eng.forward(pil[k:k + 3], *[m[k:k + 3] for m in meta]).clone())      # the switch is still at 1
+    assert torch.equal(big[k:k + 3], small)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("batch", [64, 100])
+def test_default_lanes_match_launch_path(switches, batch):
+    """AFT_LANES unset, 280 tokens: whatever split aft_workspace_lanes reports gives the bits of the launches."""
+    switches.unset("AFT_LANES")
+    eng, pil, meta, _ = _setup_act(280, 2, "gelu", True, batch, seed=950 + batch)
+    lanes, frames, offs = ctypes.c_int(), (ctypes.c_int * 4)(), (ctypes.c_size_t * 4)()
+    for v in ("0", "1"):
+        switches.set("AFT_LAYER_FUSED", v)
+        assert _lib.load().aft_workspace_lanes(ctypes.byref(eng.cfg), batch, ctypes.byref(lanes), frames, offs) == _abi.AFT_OK
+        assert 1 <= lanes.value <= 4 and sum(frames[:lanes.value]) == batch
+        print(f"batch {batch} AFT_LAYER_FUSED={v}: {lanes.value} lane(s) of {list(frames[:lanes.value])} frames")
+    a, b = _both(switches, eng, pil, meta, batch)
+    assert torch.equal(a, b)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tokens", [33, 210])
+def test_stale_workspace_on_ragged_run_time_counts(switches, tokens):
+    """33 and 210 tokens (a last tile of 1 and of 18 valid rows, the run-time token count), relu, three layers, batch 3: a NaN- and a
+    1e30-filled workspace give the bits of a zero-filled one -- and of the launch path."""
+    eng, pil, meta, _ = _setup_act(tokens, 3, "relu", tokens == 210, 3, seed=1000 + tokens)
+    ref, _ = _both(switches, eng, pil, meta, 3)
+    outs = []
+    for fill in (0.0, float("nan"), 1e30):
+        eng.workspace(3).view(torch.float32).fill_(fill)
+        outs.append(torch.view_as_real(eng.forward(pil, *meta).clone()))     # the switch is still at 1
+    assert torch.isfinite(outs[0]).all()
+    for fill, o in zip(("nan", "1e30"), outs[1:]):
+        assert torch.equal(o, outs[0]), fill
+    assert torch.equal(outs[0], ref)
+
+
 # ---- host only ----
 def test_fused_workspace_size_is_the_plan_plus_two_blocks():
     """aft_workspace_bytes stays what it was; the opt-in size adds x on plane-aligned tiles and the second V^T buffer (each planes x
