@@ -209,6 +209,7 @@ SIGNATURES = {
     "aft_lmmse_table_floats": (C.c_size_t, [C.POINTER(AftLmmse)]),
     "aft_lmmse_f32": (C.c_int, [C.POINTER(AftLmmse), vp, vp, vp, vp, vp, vp, C.c_int, vp]),
     "aft_link_errors_f32": (C.c_int, [C.POINTER(AftLink), vp, vp, vp, vp, vp, C.c_int, vp]),
+    "aft_link_soft_f32": (C.c_int, [C.POINTER(AftLink), vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp]),
     # training path
     "aft_encoder_tape_bytes": (C.c_size_t, [cfgp, C.c_int]),
     "aft_encoder_train_scratch_bytes": (C.c_size_t, [cfgp, C.c_int]),

@@ -59,6 +59,22 @@ bool aligned(size_t bytes, const P *...p) {
     return (... | reinterpret_cast<uintptr_t>(p)) % bytes == 0;
 }
 
+// what both link entry points ask of the struct; 0 = fine
+int check_link(const char *who, const aft_link &l) {
+    if (!grid_ok(who, l, INT32_MAX)) return AFT_ERR_SHAPE;
+    if ((unsigned long long)l.num_scs * (unsigned long long)l.num_symbols > (1ull << 31)) {
+        set_error("%s: the grid %d x %d has more than 2^31 elements", who, l.num_scs, l.num_symbols);
+        return AFT_ERR_SHAPE;
+    }
+    if (!pilots_fit(who, l) || !pilot_index_ok(who, l, true)) return AFT_ERR_SHAPE;
+    const int m = l.bits_per_symbol;
+    if (m != 2 && m != 4 && m != 6 && m != 8) {
+        set_error("%s: bits_per_symbol = %d is not one of 2, 4, 6, 8", who, m);
+        return AFT_ERR_SHAPE;
+    }
+    return AFT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -106,24 +122,29 @@ int aft_lmmse_f32(const aft_lmmse *plan, const float *tables, const float *pilot
 
 int aft_link_errors_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys,
                         const float *sigma, int32_t *counts, int batch, void *stream) {
-    const char *who = "link errors";
     AFT_REQUIRE(link && ideal && est && keys && sigma && counts, "link errors: NULL pointer argument");
     AFT_REQUIRE(aligned(8, ideal, est, keys), "link errors: ideal, est and keys must be 8-byte aligned");
     AFT_REQUIRE(aligned(4, sigma, counts), "link errors: sigma and counts must be 4-byte aligned");
     AFT_REQUIRE(batch >= 1, "link errors: batch must be at least 1 (got %d)", batch);
-    if (!grid_ok(who, *link, INT32_MAX)) return AFT_ERR_SHAPE;
-    if ((unsigned long long)link->num_scs * (unsigned long long)link->num_symbols > (1ull << 31)) {
-        set_error("link errors: the grid %d x %d has more than 2^31 elements", link->num_scs, link->num_symbols);
-        return AFT_ERR_SHAPE;
-    }
-    if (!pilots_fit(who, *link) || !pilot_index_ok(who, *link, true)) return AFT_ERR_SHAPE;
-    const int m = link->bits_per_symbol;
-    if (m != 2 && m != 4 && m != 6 && m != 8) {
-        set_error("link errors: bits_per_symbol = %d is not one of 2, 4, 6, 8", m);
-        return AFT_ERR_SHAPE;
-    }
+    const int rc = check_link("link errors", *link);
+    if (rc != AFT_OK) return rc;
     hipError_t e = launch_link_errors(*link, ideal, est, keys, sigma, counts, batch, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? AFT_OK : hip_fail("link_errors", e);
+}
+
+int aft_link_soft_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys,
+                      const float *sigma, const float *scale, const float *factors, int n_factors, float *loss, float *llr,
+                      int batch, void *stream) {
+    AFT_REQUIRE(link && ideal && est && keys && sigma && scale && factors && loss, "link soft: NULL pointer argument");
+    AFT_REQUIRE(aligned(8, ideal, est, keys), "link soft: ideal, est and keys must be 8-byte aligned");
+    AFT_REQUIRE(aligned(4, sigma, scale, factors, loss, llr), "link soft: sigma, scale, factors, loss and llr must be 4-byte aligned");
+    AFT_REQUIRE(batch >= 1, "link soft: batch must be at least 1 (got %d)", batch);
+    AFT_REQUIRE(n_factors >= 1 && n_factors <= 8, "link soft: n_factors = %d is outside 1..8", n_factors);
+    const int rc = check_link("link soft", *link);
+    if (rc != AFT_OK) return rc;
+    hipError_t e = launch_link_soft(*link, ideal, est, keys, sigma, scale, factors, n_factors, loss, llr, batch,
+                                    static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? AFT_OK : hip_fail("link_soft", e);
 }
 
 }  // extern "C"

@@ -344,6 +344,10 @@ hipError_t launch_lmmse(const aft_lmmse &plan, const float *tables, const float 
 // the link-level error count (k_link.hip): `link` has passed aft_link_errors_f32's checks
 hipError_t launch_link_errors(const aft_link &link, const float *ideal, const float *est, const unsigned long long *keys,
                               const float *sigma, int32_t *counts, int batch, hipStream_t st);
+// ... and its soft half (k_link.hip): `link`, n_factors and the pointers have passed aft_link_soft_f32's checks; llr may be NULL
+hipError_t launch_link_soft(const aft_link &link, const float *ideal, const float *est, const unsigned long long *keys,
+                            const float *sigma, const float *scale, const float *factors, int n_factors, float *loss, float *llr,
+                            int batch, hipStream_t st);
 hipError_t launch_mse(const float *est, const float *ref, double *sum_sq, long long n_complex, hipStream_t st);
 hipError_t launch_fill_lds(float value, hipStream_t st);   // test hook: every CU's LDS filled with `value`
 hipError_t launch_peek_lds(float *out, int workgroups, int n, hipStream_t st);   // ... and what a kernel finds in its LDS at start

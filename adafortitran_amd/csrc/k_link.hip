@@ -1,5 +1,5 @@
-// The link-level error count (include/adafortitran_amd.h "link-level bit errors"; adafortitran_amd/linksim.py is the definition and
-// the float64 twin).  One workgroup per frame, one launch per batch; a frame's two counts are a function of its own key, noise scale,
+// The link-level error count and its soft half (include/adafortitran_amd.h "link-level bit errors"; adafortitran_amd/linksim.py is the
+// definition and the float64 twin).  One workgroup per frame, one launch per batch; a frame's two counts are a function of its own key, noise scale,
 // true channel and estimate only.
 //
 //   1. the pilot positions go to LDS (two sorted lists of at most 64 and 16 entries);
@@ -15,6 +15,12 @@
 //
 // No atomics: integer sums do not depend on their order, so a frame's counts depend neither on the batch nor on the run.  The rounding
 // behind tests/test_linksim_gpu.py's margin: every product is a fused multiply-add chain, the angle is formed in turns, no fast-math.
+//
+// The soft half (aft_link_soft_f32; the second kernel below) shares step 1 and the front of step 3 -- link_front, so both kernels see the
+// same bits of c and p -- and goes on per axis with the L metrics a_k (a_k p - 2 comp) in registers, the m/2 pairs of minima, the LLRs
+// scale (min1 - min0) and, per factor, softplus of the LLR against its sent bit.  The K float sums stay in registers and are reduced in
+// a fixed order (shuffles, then the four waves through LDS); a thread takes the same element pairs whichever load form runs, so a
+// frame's loss depends neither on the batch, nor on the run, nor on the alignment of the bases, nor on whether the LLRs are stored.
 #include "frame_device.h"
 
 namespace aft {
@@ -63,22 +69,36 @@ struct LinkCounts {
     int bits, symbols;
 };
 
-// M = bits per symbol: one instantiation per modulation order, so the boundary loops unroll
+// What both kernels do first with a data element: the three words of the hash, the sent Gray codes, y = H x + noise, c = y conj(E) and
+// p = |E|^2.  Written once, so the hard and the soft kernel see the same bits of c and p.  M = bits per symbol.
+struct LinkFront {
+    unsigned gi, gq;            // the sent Gray codes of the I and the Q axis
+    float cr, ci, p;
+};
+
 template <int M>
-__device__ __forceinline__ void link_element(const LinkArgs &a, unsigned long long kf, float sigma, unsigned q, float2 h, float2 e,
-                                             LinkCounts &n) {
+__device__ __forceinline__ LinkFront link_front(float d, unsigned long long kf, float sigma, unsigned q, float2 h, float2 e) {
     constexpr int half = M / 2, L = 1 << half;
     const unsigned w = (unsigned)(frame_word(kf, kStreamDataBits, q) >> (64 - M));
     const unsigned gi = w >> half, gq = w & (unsigned)(L - 1);
-    const float xr = a.d * (float)(2 * (int)gray_level(gi) - (L - 1)), xi = a.d * (float)(2 * (int)gray_level(gq) - (L - 1));
+    const float xr = d * (float)(2 * (int)gray_level(gi) - (L - 1)), xi = d * (float)(2 * (int)gray_level(gq) - (L - 1));
     const FrameNoise nz = frame_noise(kf, kStreamDataNoiseRadius, kStreamDataNoiseAngle, q, sigma);
     const float yr = fmaf(nz.r, nz.c, fmaf(h.x, xr, -(h.y * xi)));
     const float yi = fmaf(nz.r, nz.s, fmaf(h.x, xi, h.y * xr));
     const float cr = fmaf(yr, e.x, yi * e.y);                   // y conj(E)
     const float ci = fmaf(yi, e.x, -(yr * e.y));
-    const float step = a.d2 * fmaf(e.x, e.x, e.y * e.y);
-    const unsigned ki = decide<L>(cr, step), kq = decide<L>(ci, step);
-    const int wrong = __popc(gi ^ ki ^ (ki >> 1)) + __popc(gq ^ kq ^ (kq >> 1));
+    return LinkFront{gi, gq, cr, ci, fmaf(e.x, e.x, e.y * e.y)};
+}
+
+// one instantiation per modulation order, so the boundary loops unroll
+template <int M>
+__device__ __forceinline__ void link_element(const LinkArgs &a, unsigned long long kf, float sigma, unsigned q, float2 h, float2 e,
+                                             LinkCounts &n) {
+    constexpr int L = 1 << (M / 2);
+    const LinkFront f = link_front<M>(a.d, kf, sigma, q, h, e);
+    const float step = a.d2 * f.p;
+    const unsigned ki = decide<L>(f.cr, step), kq = decide<L>(f.ci, step);
+    const int wrong = __popc(f.gi ^ ki ^ (ki >> 1)) + __popc(f.gq ^ kq ^ (kq >> 1));
     n.bits += wrong;
     n.symbols += wrong != 0 ? 1 : 0;
 }
@@ -136,6 +156,176 @@ __global__ __launch_bounds__(kFrameThreads) void link_errors_kernel(const LinkAr
     }
 }
 
+
+// ---- the soft half: max-log LLRs and the loss the achievable rate is read from (linksim.py "the soft link") ----
+
+constexpr int kMaxFactors = 8;
+constexpr float kInvLn2 = 1.44269504088896341f;
+
+struct LinkSoftArgs {
+    aft_link c;
+    const float2 *ideal, *est;
+    const unsigned long long *keys;
+    const float *sigma, *scale, *factors;
+    float *loss, *llr;          // llr may be NULL
+    unsigned elems;             // S T - 1, as in LinkArgs
+    float d;
+    int n_factors;              // 1 .. kMaxFactors
+    int wide;                   // 1: 16-byte loads of ideal and est
+    int store;                  // bytes per store of llr: 16, 8 or 4
+};
+
+// One axis: the L metrics mu_k = a_k (a_k p - 2 comp) in registers, and per bit of the Gray code (MSB first) the scaled difference of
+// the two minima.  Two roundings per metric (the fused multiply-add and the product) and nothing contracted behind the source's back.
+template <int L>
+__device__ __forceinline__ void link_axis_llrs(float d, float comp, float p, float scale, float *out) {
+#pragma clang fp contract(off)
+    constexpr int half = L == 2 ? 1 : L == 4 ? 2 : L == 8 ? 3 : 4;
+    const float m2c = -2.f * comp;
+    float mu[L];
+#pragma unroll
+    for (int k = 0; k < L; ++k) {
+        const float ak = d * (float)(2 * k - (L - 1));
+        mu[k] = ak * fmaf(ak, p, m2c);
+    }
+#pragma unroll
+    for (int j = 0; j < half; ++j) {
+        float m0 = 0.f, m1 = 0.f;
+        bool have0 = false, have1 = false;                      // constants once the loop over k is unrolled
+#pragma unroll
+        for (int k = 0; k < L; ++k) {
+            if (((k ^ (k >> 1)) >> (half - 1 - j)) & 1) {
+                m1 = have1 ? fminf(m1, mu[k]) : mu[k];
+                have1 = true;
+            } else {
+                m0 = have0 ? fminf(m0, mu[k]) : mu[k];
+                have0 = true;
+            }
+        }
+        out[j] = scale * (m1 - m0);
+    }
+}
+
+// A data element: its M LLRs into v (I-axis bits first, MSB first: the order of the sent word) and, for each factor, the sum over its
+// bits of softplus(z) = max(z, 0) + log1p(exp(-|z|)) in nats, z = -(1 - 2 b) factor Lambda with b the sent bit.
+template <int M>
+__device__ __forceinline__ void link_soft_element(const LinkSoftArgs &a, unsigned long long kf, float sigma, float scale,
+                                                  const float (&fac)[kMaxFactors], unsigned q, float2 h, float2 e, float *v,
+                                                  float (&acc)[kMaxFactors]) {
+#pragma clang fp contract(off)
+    constexpr int half = M / 2, L = 1 << half;
+    const LinkFront f = link_front<M>(a.d, kf, sigma, q, h, e);
+    link_axis_llrs<L>(a.d, f.cr, f.p, scale, v);
+    link_axis_llrs<L>(a.d, f.ci, f.p, scale, v + half);
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+        const unsigned sent = ((j < half ? f.gi : f.gq) >> (half - 1 - j % half)) & 1u;
+        const float against = sent ? v[j] : -v[j];              // -(1 - 2 b) Lambda
+#pragma unroll
+        for (int k = 0; k < kMaxFactors; ++k)
+            if (k < a.n_factors) {
+                const float z = fac[k] * against;
+                acc[k] += fmaxf(z, 0.f) + log1pf(expf(-fabsf(z)));
+            }
+    }
+}
+
+// the n leading floats of v (n = M or 2 M, a multiple of the store's width) to dst
+template <int M>
+__device__ __forceinline__ void link_store_llrs(float *dst, const float *v, int n, int bytes) {
+    if (bytes == 16) {
+#pragma unroll
+        for (int j = 0; j < 2 * M; j += 4)
+            if (j < n) *reinterpret_cast<f32x4 *>(dst + j) = f32x4{v[j], v[j + 1], v[j + 2], v[j + 3]};
+    } else if (bytes == 8) {
+#pragma unroll
+        for (int j = 0; j < 2 * M; j += 2)
+            if (j < n) *reinterpret_cast<float2 *>(dst + j) = make_float2(v[j], v[j + 1]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 2 * M; ++j)
+            if (j < n) dst[j] = v[j];
+    }
+}
+
+// A thread takes the element pairs (2 i, 2 i + 1), i = tid, tid + 256, ..., whichever load form runs: the order of a frame's float
+// sums, and so its loss, depends neither on the alignment of the bases nor on anything outside the frame.
+template <int M>
+__global__ __launch_bounds__(kFrameThreads) void link_soft_kernel(const LinkSoftArgs a) {
+    __shared__ int psc[AFT_CHANSIM_MAX_PILOT_SCS], psym[AFT_CHANSIM_MAX_PILOT_SYMBOLS];
+    __shared__ float part[kLinkWaves][kMaxFactors];
+    const aft_link &c = a.c;
+    const int tid = threadIdx.x;
+    const size_t b = blockIdx.x;
+    const int Ps = c.pilot_scs, Pt = c.pilot_symbols, nf = a.n_factors;
+    const unsigned T = (unsigned)c.num_symbols, last = a.elems;
+    AFT_DEV_ASSERT(Ps >= 1 && Ps <= AFT_CHANSIM_MAX_PILOT_SCS && Pt >= 1 && Pt <= AFT_CHANSIM_MAX_PILOT_SYMBOLS);
+    AFT_DEV_ASSERT(nf >= 1 && nf <= kMaxFactors);
+    if (tid < Ps) psc[tid] = c.pilot_sc_index[tid];
+    if (tid >= kWave && tid - kWave < Pt) psym[tid - kWave] = c.pilot_symbol_index[tid - kWave];
+    __syncthreads();
+    const unsigned long long kf = a.keys[b];
+    const float sigma = a.sigma[b], scale = a.scale[b];
+    float fac[kMaxFactors], acc[kMaxFactors];
+#pragma unroll
+    for (int k = 0; k < kMaxFactors; ++k) {
+        fac[k] = k < nf ? a.factors[k] : 0.f;
+        acc[k] = 0.f;
+    }
+    const size_t base = b * ((size_t)last + 1);                 // the frame's first element
+    const float2 *hp = a.ideal + base, *ep = a.est + base;
+    float *lp = a.llr != nullptr ? a.llr + base * M : nullptr;
+    auto data = [&](unsigned q) {                               // not a pilot position
+        const unsigned s = q / T, t = q - s * T;
+        return !(link_listed(psym, Pt, (int)t) && link_listed(psc, Ps, (int)s));
+    };
+    const unsigned pairs = (last >> 1) + 1;                     // the last pair of an odd grid holds one element
+    for (unsigned i = tid; i < pairs; i += kFrameThreads) {      // pairs <= 2^30: the index cannot wrap
+        const unsigned q = 2 * i;
+        const bool two = q < last;
+        AFT_DEV_ASSERT(q <= last && (two || !a.wide));
+        float2 h0, e0, h1 = make_float2(0.f, 0.f), e1 = h1;
+        if (a.wide) {
+            const f32x4 h = *reinterpret_cast<const f32x4 *>(hp + q), e = *reinterpret_cast<const f32x4 *>(ep + q);
+            h0 = make_float2(h[0], h[1]); e0 = make_float2(e[0], e[1]);
+            h1 = make_float2(h[2], h[3]); e1 = make_float2(e[2], e[3]);
+        } else {
+            h0 = hp[q]; e0 = ep[q];
+            if (two) { h1 = hp[q + 1]; e1 = ep[q + 1]; }
+        }
+        float v[2 * M];
+#pragma unroll
+        for (int j = 0; j < 2 * M; ++j) v[j] = 0.f;             // what a pilot position carries
+#pragma unroll 1
+        for (int s = 0; s < 2; ++s) {                           // one copy of the element's code: 52 KB at m = 8, two are 100 KB
+            if ((s == 0 || two) && data(q + s)) {
+                float w[M];
+                link_soft_element<M>(a, kf, sigma, scale, fac, q + s, s ? h1 : h0, s ? e1 : e0, w, acc);
+#pragma unroll
+                for (int j = 0; j < M; ++j) {
+                    if (s) v[M + j] = w[j];
+                    else v[j] = w[j];
+                }
+            }
+        }
+        if (lp != nullptr) link_store_llrs<M>(lp + (size_t)q * M, v, two ? 2 * M : M, a.store);
+    }
+#pragma unroll
+    for (int k = 0; k < kMaxFactors; ++k)
+        if (k < nf) {
+#pragma unroll
+            for (int o = kWave / 2; o >= 1; o >>= 1) acc[k] += __shfl_xor(acc[k], o);
+            if ((tid & (kWave - 1)) == 0) part[tid / kWave][k] = acc[k];
+        }
+    __syncthreads();
+    if (tid < nf) {                                             // thread k the loss at factor k: the four waves in a fixed order
+        float total = part[0][tid];
+#pragma unroll
+        for (int w = 1; w < kLinkWaves; ++w) total += part[w][tid];
+        a.loss[b * (size_t)nf + tid] = total * kInvLn2;
+    }
+}
+
 }  // namespace
 
 hipError_t launch_link_errors(const aft_link &link, const float *ideal, const float *est, const unsigned long long *keys,
@@ -158,6 +348,35 @@ hipError_t launch_link_errors(const aft_link &link, const float *ideal, const fl
         case 6: hipLaunchKernelGGL(link_errors_kernel<6>, grid, block, 0, st, a); break;
         case 8: hipLaunchKernelGGL(link_errors_kernel<8>, grid, block, 0, st, a); break;
         default: return hipErrorInvalidValue;           // aft_link_errors_f32 has refused it
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_link_soft(const aft_link &link, const float *ideal, const float *est, const unsigned long long *keys,
+                            const float *sigma, const float *scale, const float *factors, int n_factors, float *loss, float *llr,
+                            int batch, hipStream_t st) {
+    LinkSoftArgs a{};
+    a.c = link;
+    a.ideal = reinterpret_cast<const float2 *>(ideal);
+    a.est = reinterpret_cast<const float2 *>(est);
+    a.keys = keys; a.sigma = sigma; a.scale = scale; a.factors = factors; a.loss = loss; a.llr = llr;
+    a.n_factors = n_factors;
+    const unsigned long long elems = (unsigned long long)link.num_scs * (unsigned long long)link.num_symbols;
+    a.elems = (unsigned)(elems - 1);
+    const int m = link.bits_per_symbol, L = 1 << (m / 2);
+    a.d = (float)sqrt(3.0 / (2.0 * ((double)L * L - 1.0)));
+    a.wide = wide_ok(link.num_symbols, ideal, est);
+    // an element's m floats start at a multiple of 4 m bytes: every pair of elements starts on 16 bytes when m is 4 or 8, or when the
+    // frames hold an even number of elements (then every pair is whole, too)
+    const uintptr_t at = reinterpret_cast<uintptr_t>(llr);
+    a.store = at % 16 == 0 && (m % 4 == 0 || elems % 2 == 0) ? 16 : at % 8 == 0 ? 8 : 4;
+    const dim3 grid((unsigned)batch), block(kFrameThreads);
+    switch (m) {
+        case 2: hipLaunchKernelGGL(link_soft_kernel<2>, grid, block, 0, st, a); break;
+        case 4: hipLaunchKernelGGL(link_soft_kernel<4>, grid, block, 0, st, a); break;
+        case 6: hipLaunchKernelGGL(link_soft_kernel<6>, grid, block, 0, st, a); break;
+        case 8: hipLaunchKernelGGL(link_soft_kernel<8>, grid, block, 0, st, a); break;
+        default: return hipErrorInvalidValue;           // aft_link_soft_f32 has refused it
     }
     return hipGetLastError();
 }

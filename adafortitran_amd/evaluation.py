@@ -18,6 +18,7 @@ from typing import Dict, Iterable, List, Optional, Tuple
 import torch
 
 from .estimators import AdaFortiTranEstimator
+from .linksim import DEFAULT_FACTORS, LinkAccumulator, RateAccumulator
 from .lmmse import LmmseEstimator
 from .metrics import MseAccumulator, to_db
 
@@ -52,14 +53,8 @@ def get_test_stats(model: torch.nn.Module, test_dataloaders: List[Tuple[str, Ite
     return stats
 
 
-def get_link_stats(model: Optional[torch.nn.Module], test_dataloaders: List[Tuple[str, Iterable]], link_cfg, seed: int = 0,
-                   group=None) -> Dict[int, float]:
-    """Bit-error rate per loader on the link ``link_cfg`` (``linksim.LinkConfig``) defines: data symbols through each frame's true channel
-    plus noise at the frame's SNR, equalised with the model's estimate; ``model=None`` is perfect channel knowledge.  Same sorting and
-    keys as ``get_test_stats``; the estimate comes from ``forward_pass``, so every estimator here works; the counts accumulate on the
-    device (``linksim.LinkAccumulator``) and are read once per loader.  A frame's data bits and noise are a function of
-    ``(seed, file_no)``, whichever estimator is measured: two estimators see the same link."""
-    from .linksim import LinkAccumulator
+def _link_sweep(model, test_dataloaders, make_acc, read) -> Dict[int, float]:
+    """One accumulator per loader, sorted and keyed as ``get_test_stats``: ``make_acc(device)`` opens it, ``read(acc)`` closes it."""
     if model is not None:
         model.eval()
     stats: Dict[int, float] = {}
@@ -69,9 +64,29 @@ def get_link_stats(model: Optional[torch.nn.Module], test_dataloaders: List[Tupl
             for pilots, ideal, meta in loader:
                 est = None if model is None else forward_pass(model, pilots, meta)
                 if acc is None:
-                    acc = LinkAccumulator(link_cfg, ideal.device if est is None else est.device, seed)
+                    acc = make_acc(ideal.device if est is None else est.device)
                 acc.update(est, ideal, meta)
         if acc is None:
             raise ValueError(f"loader {name} yielded no batch")
-        stats[int(name.split("_")[1])] = acc.result(group)
+        stats[int(name.split("_")[1])] = read(acc)
     return stats
+
+
+def get_link_stats(model: Optional[torch.nn.Module], test_dataloaders: List[Tuple[str, Iterable]], link_cfg, seed: int = 0,
+                   group=None) -> Dict[int, float]:
+    """Bit-error rate per loader on the link ``link_cfg`` (``linksim.LinkConfig``) defines: data symbols through each frame's true channel
+    plus noise at the frame's SNR, equalised with the model's estimate; ``model=None`` is perfect channel knowledge.  Same sorting and
+    keys as ``get_test_stats``; the estimate comes from ``forward_pass``, so every estimator here works; the counts accumulate on the
+    device (``linksim.LinkAccumulator``) and are read once per loader.  A frame's data bits and noise are a function of
+    ``(seed, file_no)``, whichever estimator is measured: two estimators see the same link."""
+    return _link_sweep(model, test_dataloaders, lambda device: LinkAccumulator(link_cfg, device, seed), lambda acc: acc.result(group))
+
+
+def get_link_rates(model: Optional[torch.nn.Module], test_dataloaders: List[Tuple[str, Iterable]], link_cfg, seed: int = 0,
+                   factors=DEFAULT_FACTORS, group=None) -> Dict[int, float]:
+    """Achievable rate per loader in bit/symbol on the same link: the bit-interleaved coded-modulation rate (GMI) of the max-log LLRs a
+    demapper forms with the model's estimate at the frame's SNR, the best of the LLR scale factors ``factors``; ``model=None`` is perfect
+    channel knowledge.  Sorting, keys and the frames' bits and noise as ``get_link_stats``; the losses accumulate on the device
+    (``linksim.RateAccumulator``) and are read once per loader."""
+    return _link_sweep(model, test_dataloaders, lambda device: RateAccumulator(link_cfg, device, seed, factors),
+                       lambda acc: acc.result_gmi(group))

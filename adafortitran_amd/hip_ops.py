@@ -494,18 +494,19 @@ class LinkPlan:
     ``[batch,S,T]`` live on the plan's device; ``keys`` (int64, the 64-bit keys' bits) and ``sigma`` (float32), ``batch`` values each,
     live there or in pinned host memory, which the kernel reads in place.  The plan trusts its caller in one thing only: its device
     is the current one."""
+    cpu_path = "linksim.link_errors_host"
 
     def __init__(self, cfg, device: torch.device) -> None:
         from .linksim import LinkConfig
         if not isinstance(cfg, LinkConfig):
-            raise ValueError(f"LinkPlan needs a linksim.LinkConfig (got {type(cfg).__name__})")
-        self.device = _hip_device(device, "LinkPlan", "linksim.link_errors_host")
+            raise ValueError(f"{type(self).__name__} needs a linksim.LinkConfig (got {type(cfg).__name__})")
+        self.device = _hip_device(device, type(self).__name__, self.cpu_path)
         self.cfg = cfg
         self.link = cfg.to_struct()                             # validated by the config itself; the entry point checks again
         self.grid = tuple(cfg.sim.ofdm)
 
-    def __call__(self, ideal: torch.Tensor, est: torch.Tensor, keys: torch.Tensor, sigma: torch.Tensor, lib=None) -> torch.Tensor:
-        lib = lib or _lib.load()
+    def _checked(self, ideal: torch.Tensor, est: torch.Tensor, keys: torch.Tensor, sigma: torch.Tensor):
+        """The four operands every launch on this link takes, checked: ``(batch, ideal, est, keys, sigma)``."""
         if ideal.dim() != 3 or tuple(ideal.shape[1:]) != self.grid or ideal.shape[0] < 1:
             raise ValueError(f"Expected ideal shape (B >= 1, {self.grid[0]}, {self.grid[1]}), got {tuple(ideal.shape)}")
         batch = ideal.shape[0]
@@ -516,13 +517,40 @@ class LinkPlan:
                 raise ValueError(f"{name} must be complex64, got {t.dtype}")
             if t.device != self.device:
                 raise ValueError(f"{name} must live on {self.device} (it is on {t.device})")
-        ideal, est = ideal.contiguous(), est.contiguous()      # held until after the launch is enqueued
-        keys = _in_place("keys", keys, torch.int64, self.device, batch)
-        sigma = _in_place("sigma", sigma, torch.float32, self.device, batch)
+        return (batch, ideal.contiguous(), est.contiguous(),   # held by the caller until after the launch is enqueued
+                _in_place("keys", keys, torch.int64, self.device, batch), _in_place("sigma", sigma, torch.float32, self.device, batch))
+
+    def __call__(self, ideal: torch.Tensor, est: torch.Tensor, keys: torch.Tensor, sigma: torch.Tensor, lib=None) -> torch.Tensor:
+        lib = lib or _lib.load()
+        batch, ideal, est, keys, sigma = self._checked(ideal, est, keys, sigma)
         counts = torch.empty((batch, 2), dtype=torch.int32, device=self.device)             # the kernel writes every element
         _lib.check(lib.aft_link_errors_f32(C.byref(self.link), ideal.data_ptr(), est.data_ptr(), keys.data_ptr(), sigma.data_ptr(),
                                            counts.data_ptr(), batch, _lib.current_stream_ptr(self.device)), lib)
         return counts
+
+
+class LinkSoftPlan(LinkPlan):
+    """The soft half of ``LinkPlan``'s link.  ``plan(ideal, est, keys, sigma, scale, factors, want_llr=False)`` -> ``(loss float32
+    [batch, K], llr float32 [batch, S, T, m] or None)`` on the plan's device: the loss of each frame at each of the K factors and, when
+    asked for, the max-log LLR of every sent bit (0 at the pilots); one ``ctypes`` call, one launch (``aft_link_soft_f32``) on the
+    current stream, no synchronisation.  ``scale`` (float32, ``batch`` values) and ``factors`` (float32, 1 .. 8 values) live where
+    ``keys`` and ``sigma`` may: on the plan's device or in pinned host memory.  Everything else as ``LinkPlan``."""
+    cpu_path = "linksim.link_llrs_host"
+
+    def __call__(self, ideal: torch.Tensor, est: torch.Tensor, keys: torch.Tensor, sigma: torch.Tensor, scale: torch.Tensor,
+                 factors: torch.Tensor, want_llr: bool = False, lib=None):
+        lib = lib or _lib.load()
+        batch, ideal, est, keys, sigma = self._checked(ideal, est, keys, sigma)
+        scale = _in_place("scale", scale, torch.float32, self.device, batch)
+        if not torch.is_tensor(factors) or not 1 <= factors.numel() <= 8:
+            raise ValueError(f"factors must hold between 1 and 8 values, got {factors.numel() if torch.is_tensor(factors) else factors!r}")
+        factors = _in_place("factors", factors, torch.float32, self.device, factors.numel())
+        loss = torch.empty((batch, factors.numel()), dtype=torch.float32, device=self.device)   # the kernel writes every element
+        llr = torch.empty((batch, *self.grid, self.cfg.bits_per_symbol), dtype=torch.float32, device=self.device) if want_llr else None
+        _lib.check(lib.aft_link_soft_f32(C.byref(self.link), ideal.data_ptr(), est.data_ptr(), keys.data_ptr(), sigma.data_ptr(),
+                                         scale.data_ptr(), factors.data_ptr(), factors.numel(), loss.data_ptr(), _ptr(llr), batch,
+                                         _lib.current_stream_ptr(self.device)), lib)
+        return loss, llr
 
 
 def ls_mse_db(ls: torch.Tensor, ideal: torch.Tensor) -> torch.Tensor:

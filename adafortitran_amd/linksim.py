@@ -35,6 +35,30 @@ The margin, which is what a float32 evaluation is compared through: for each (el
 when any of its boundaries has margin <= ``tau``: there a relative error of ``tau`` in the two sides may move the decision across that
 boundary.  Because of the Gray map a flagged (element, axis) changes a frame's bit-error count by at most 1, and a
 flagged element its symbol-error count by at most 1.
+
+The soft link.  No OFDM system runs uncoded 64- or 256-QAM: what decides whether an MSE gain matters is how much soft information the
+demapper hands the decoder.  The decoder-free measure of that is the bit-interleaved coded-modulation rate, the generalised mutual
+information (GMI) of the LLRs.  ``link_llrs_host`` (float64), ``aft_link_soft_f32`` (csrc/k_link.hip, through ``hip_ops.LinkSoftPlan``),
+``RateAccumulator`` and ``evaluation.get_link_rates`` are to it what the four names above are to the bit errors.  Per frame and data
+element, with ``w, gi, gq, x, y, c, p`` exactly as above::
+
+    levels   a_k = d (2k - (L-1)),  label g_k = k ^ (k >> 1),  k = 0 .. L-1
+    metric   mu_k(comp) = a_k (a_k p - 2 comp)        |y - E x|^2 up to a constant, separable per axis, no division
+    bit j of an axis's Gray code, MSB first:  bit_j(g) = (g >> (m/2 - 1 - j)) & 1
+    Delta_j  = min{mu_k : bit_j(g_k) = 1} - min{mu_k : bit_j(g_k) = 0}
+    LLR      Lambda_j = scale Delta_j                 positive favours bit 0; I-axis bits 0 .. m/2-1, Q-axis bits m/2 .. m-1 (the order of w)
+    loss_f  += log2(1 + exp(-(1 - 2 b_j) factor_f Lambda_j))       b_j the sent bit, for each of the K factors
+
+``scale`` is a float32 per frame (``llr_scale``: one over the noise variance plus the estimate's error variance), ``factors`` float32
+``[K]``, 1 <= K <= 8.  The LLR at a pilot position is 0.  A frame's rate at factor f is ``m - loss_f / data_elements`` bit/symbol; it
+may be negative (over-confident LLRs under a mismatched channel, which is why the loss is evaluated on a grid of factors in one pass),
+and the best of the grid is the GMI's supremum over the LLR scale taken on that grid.
+
+What a float32 evaluation of the LLRs is compared through: ``q = scale A (A p + 2 R)`` with ``A = (L-1) d`` the outermost level and
+``R = (|H||x| + |noise|) |E|`` the reach of ``comp`` -- every ``|mu_k| <= A (A p + 2 R)``, so an evaluation whose metrics err by a
+relative ``e`` of that errs in ``Lambda_j`` by about ``2 e q``.  The loss is monotone in every ``Lambda_j``, so the losses at
+``Lambda -+ e_lambda q`` (each bit moved towards, or away from, the sent bit) are an exact interval for every evaluation whose LLRs
+are within ``e_lambda q``.
 """
 from __future__ import annotations
 
@@ -124,11 +148,9 @@ def _uniform(keys: np.ndarray, stream: int, q: np.ndarray) -> np.ndarray:
     return ((words(keys, stream, q) >> np.uint64(41)).astype(np.float64) + 0.5) * 2.0 ** -23
 
 
-def link_errors_host(cfg: LinkConfig, keys, ideal, est, sigma, tau: Optional[float] = None):
-    """The definition in float64 on the given arrays: ``keys`` uint64 ``[n]`` (an int64 array is taken bit for bit), ``ideal`` / ``est``
-    complex ``[n, S, T]``, ``sigma`` ``[n]`` -> ``counts`` int64 ``[n, 2]`` = (bit errors, symbol errors) per frame.  With ``tau``:
-    ``(counts, errors, flags)``, ``errors`` int64 ``[n, S, T]`` the wrong bits of each element (0 at the pilots) and ``flags`` bool
-    ``[n, S, T, 2]`` the flagged (element, axis) pairs at ``tau`` (module docstring; False at the pilots).  Needs no library."""
+def _front(cfg: LinkConfig, keys, ideal, est, sigma):
+    """What the hard and the soft definition share, in float64: the checked operands and, per element, the sent Gray codes ``gi`` / ``gq``,
+    ``c = y conj(E)``, ``p = |E|^2`` and the reach ``(|H||x| + |noise|) |E|`` of a component of ``c``."""
     keys = np.ascontiguousarray(keys)
     if keys.dtype == np.int64:
         keys = keys.view(np.uint64)
@@ -142,19 +164,28 @@ def link_errors_host(cfg: LinkConfig, keys, ideal, est, sigma, tau: Optional[flo
     if sigma.shape != (n,):
         raise ValueError(f"sigma must hold one value per frame ({n}), got {sigma.size}")
     m, L, d = cfg.bits_per_symbol, cfg.levels, cfg.d
-    half = m // 2
     q = np.arange(S * T, dtype=np.uint64).reshape(1, S, T)
     kk = keys[:, None, None]
     w = (words(kk, STREAM_DATA_BITS, q) >> np.uint64(64 - m)).astype(np.int64)
-    gi, gq = w >> half, w & (L - 1)
+    gi, gq = w >> (m // 2), w & (L - 1)
     x = d * ((2 * gray_level(gi) - (L - 1)) + 1j * (2 * gray_level(gq) - (L - 1)))
     u1, u2 = _uniform(kk, STREAM_DATA_NOISE_RADIUS, q), _uniform(kk, STREAM_DATA_NOISE_ANGLE, q)
     noise = sigma[:, None, None] * np.sqrt(-np.log(u1)) * np.exp(2j * np.pi * u2)
     c = (H * x + noise) * E.conj()
     p = E.real ** 2 + E.imag ** 2
+    reach = (np.abs(H) * np.abs(x) + np.abs(noise)) * np.abs(E)
+    return gi, gq, c, p, reach
+
+
+def link_errors_host(cfg: LinkConfig, keys, ideal, est, sigma, tau: Optional[float] = None):
+    """The definition in float64 on the given arrays: ``keys`` uint64 ``[n]`` (an int64 array is taken bit for bit), ``ideal`` / ``est``
+    complex ``[n, S, T]``, ``sigma`` ``[n]`` -> ``counts`` int64 ``[n, 2]`` = (bit errors, symbol errors) per frame.  With ``tau``:
+    ``(counts, errors, flags)``, ``errors`` int64 ``[n, S, T]`` the wrong bits of each element (0 at the pilots) and ``flags`` bool
+    ``[n, S, T, 2]`` the flagged (element, axis) pairs at ``tau`` (module docstring; False at the pilots).  Needs no library."""
+    gi, gq, c, p, reach = _front(cfg, keys, ideal, est, sigma)
+    (n, S, T), L, d = c.shape, cfg.levels, cfg.d
     mask = cfg.data_mask[None]
     if tau is not None:
-        reach = (np.abs(H) * np.abs(x) + np.abs(noise)) * np.abs(E)
         flags = np.zeros((n, S, T, 2), dtype=bool)
     wrong = np.zeros((n, S, T), dtype=np.int64)
     for axis, (comp, sent) in enumerate(((c.real, gi), (c.imag, gq))):
@@ -173,6 +204,60 @@ def link_errors_host(cfg: LinkConfig, keys, ideal, est, sigma, tau: Optional[flo
         return counts
     flags &= mask[..., None]
     return counts, wrong, flags
+
+
+DEFAULT_FACTORS = tuple(2.0 ** -k for k in range(8))        # 1, 1/2, ..., 1/128: the grid the GMI's supremum over the LLR scale is taken on
+MAX_FACTORS = 8
+
+
+def llr_scale(snr_db, err_var=0.0) -> np.ndarray:
+    """``float32(1 / (10^(-snr_db / 10) + err_var))``: one over the noise variance plus the estimate's error variance, formed in double
+    and rounded once."""
+    return (1.0 / (10.0 ** (-np.asarray(snr_db, dtype=np.float64) / 10.0) + float(err_var))).astype(np.float32)
+
+
+def _factors(factors) -> np.ndarray:
+    f = np.asarray(factors, dtype=np.float32).reshape(-1)
+    if not 1 <= f.size <= MAX_FACTORS:
+        raise ValueError(f"between 1 and {MAX_FACTORS} factors, got {f.size}")
+    return f
+
+
+def link_llrs_host(cfg: LinkConfig, keys, ideal, est, sigma, scale, factors=(1.0,), e_lambda: Optional[float] = None):
+    """The soft definition (module docstring) in float64: operands as ``link_errors_host``'s, ``scale`` ``[n]`` and ``factors`` ``[K]``
+    taken as the float32 numbers they are -> ``(loss float64 [n, K], llr float64 [n, S, T, m])``, the LLRs 0 at the pilots.  With
+    ``e_lambda``: ``(loss, llr, loss_lo, loss_hi, q)``, ``q [n, S, T, m] = scale A (A p + 2 R)`` (0 at the pilots) and ``loss_lo`` /
+    ``loss_hi`` the losses at ``Lambda -+ e_lambda q``, every bit moved towards / away from the sent bit.  Needs no library."""
+    gi, gq, c, p, reach = _front(cfg, keys, ideal, est, sigma)
+    (n, S, T), m, L, d = c.shape, cfg.bits_per_symbol, cfg.levels, cfg.d
+    half = m // 2
+    scale = np.asarray(scale, dtype=np.float32).astype(np.float64).reshape(-1)
+    if scale.shape != (n,):
+        raise ValueError(f"scale must hold one value per frame ({n}), got {scale.size}")
+    factors = _factors(factors).astype(np.float64)
+    k = np.arange(L)
+    a, label = d * (2 * k - (L - 1)), k ^ (k >> 1)
+    mask = cfg.data_mask[None, :, :, None]
+    llr = np.empty((n, S, T, m))
+    sign = np.empty((n, S, T, m))                              # 1 - 2 b_j
+    for axis, (comp, sent) in enumerate(((c.real, gi), (c.imag, gq))):
+        mu = a * (a * p[..., None] - 2.0 * comp[..., None])                      # [n, S, T, L]
+        for j in range(half):
+            one = ((label >> (half - 1 - j)) & 1).astype(bool)
+            llr[..., axis * half + j] = mu[..., one].min(axis=-1) - mu[..., ~one].min(axis=-1)
+            sign[..., axis * half + j] = 1 - 2 * ((sent >> (half - 1 - j)) & 1)
+    llr *= scale[:, None, None, None] * mask
+
+    def losses(lam):
+        z = -(sign * lam)
+        return np.stack([(np.logaddexp(0.0, f * z) * mask).sum(axis=(1, 2, 3)) for f in factors], axis=1) / np.log(2.0)
+
+    loss = losses(llr)
+    if e_lambda is None:
+        return loss, llr
+    A = (L - 1) * d
+    q = np.broadcast_to((scale[:, None, None] * A * (A * p + 2.0 * reach))[..., None] * mask, llr.shape).copy()
+    return loss, llr, losses(llr + sign * (e_lambda * q)), losses(llr - sign * (e_lambda * q)), q
 
 
 # ---- the frame keys with torch ops, for frame numbers that live on the device (no synchronisation) ----
@@ -200,35 +285,29 @@ def frame_keys_torch(seed: int, frame_ids: torch.Tensor) -> torch.Tensor:
     return _splitmix64_torch(frame_ids.reshape(-1).to(torch.int64) ^ _s64(sk))
 
 
-class LinkAccumulator:
-    """Bit and symbol errors of a sweep, with the surface of ``metrics.MseAccumulator``: ``update`` per batch, ``result`` once.
+class _FrameSweep:
+    """What the accumulators of a sweep share: a batch's checked operands where the accumulator computes.  ``_operands`` returns None
+    for an empty batch, else ``(b, H, E, keys, per_frame)``: on a CPU device NumPy arrays for the float64 definition, on a HIP device
+    tensors for the plan -- frame numbers and SNRs that are host tensors are hashed and converted on the host and copied from pinned
+    memory, device tensors with torch ops, so nothing synchronises.  ``per_frame`` holds one float32 ``[b]`` operand per entry of
+    ``of_snr``, pairs ``(numpy function, torch function on a float64 tensor)`` of the SNR in dB."""
 
-    ``update(est, ideal, meta)`` takes the frames' numbers from ``meta[0]`` (the loaders' ``file_no``: float32 as the reference's, so
-    exact below 2^24; ``frame_ids=`` gives exact ones) and their SNR from ``meta[1]`` (``snr_db=`` overrides; one value or one per
-    frame); the frame's key is ``chansim.frame_keys(seed, g)``.  ``est=None`` is perfect channel knowledge (``est = ideal``).  On a HIP
-    device a batch is one launch of ``aft_link_errors_f32`` plus one small integer add into an int64 ``[2]`` device tensor: frame
-    numbers and SNRs that are host tensors are hashed on the host and copied from pinned memory, device tensors are hashed with
-    torch ops -- nothing synchronises.  On a CPU device the float64 definition runs.  ``result`` / ``result_ser`` close the sweep with
-    one read and, with several ranks, the same 16-byte all-gather as the MSE accumulator."""
-
-    def __init__(self, cfg: LinkConfig, device, seed: int = 0) -> None:
+    def _open(self, cfg: LinkConfig, device, seed: int, plan_name: str) -> None:
         if not isinstance(cfg, LinkConfig):
-            raise ValueError(f"LinkAccumulator needs a LinkConfig (got {type(cfg).__name__})")
+            raise ValueError(f"{type(self).__name__} needs a LinkConfig (got {type(cfg).__name__})")
         self.cfg, self.seed = cfg, int(seed)
         self.device = torch.device(device)
         self._plan = None
         if self.device.type == "cuda":
-            from .hip_ops import LinkPlan          # loads the extension: a missing .so raises here, loudly
-            self._plan = LinkPlan(cfg, self.device)
+            from . import hip_ops                  # loads the extension: a missing .so raises here, loudly
+            self._plan = getattr(hip_ops, plan_name)(cfg, self.device)
             self.device = self._plan.device
-        self.errors = torch.zeros(2, dtype=torch.int64, device=self.device)     # bit errors, symbol errors
         self.frames = 0
 
     def _stage(self, a: np.ndarray) -> torch.Tensor:
         return torch.from_numpy(a).pin_memory().to(self.device, non_blocking=True)
 
-    def update(self, est: Optional[torch.Tensor], ideal: torch.Tensor, meta: Optional[tuple] = None, *, frame_ids=None,
-               snr_db=None) -> None:
+    def _operands(self, est, ideal, meta, frame_ids, snr_db, of_snr):
         S, T = self.cfg.sim.ofdm
         if ideal.dim() != 3 or tuple(ideal.shape[1:]) != (S, T) or ideal.dtype != torch.complex64:
             raise ValueError(f"ideal must be complex64 [B, {S}, {T}], got {ideal.dtype} {tuple(ideal.shape)}")
@@ -244,7 +323,7 @@ class LinkAccumulator:
                 raise ValueError("the SNR is needed: meta (snr second) or snr_db=")
             snr_db = meta[1]
         if b == 0:
-            return
+            return None
         on_device = lambda v: torch.is_tensor(v) and v.device.type == "cuda"  # noqa: E731
         host = lambda v: v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)  # noqa: E731
         if self._plan is None or not on_device(frame_ids):
@@ -256,13 +335,10 @@ class LinkAccumulator:
             snr = host(snr_db).reshape(-1)
             if snr.size not in (1, b):
                 raise ValueError(f"one SNR, or one per frame ({b}), got {snr.size}")
-            sigma = noise_sigma(np.broadcast_to(snr, (b,)))
+            per_frame = [on_host(np.broadcast_to(snr, (b,))) for on_host, _ in of_snr]
         if self._plan is None:
             H = ideal.detach().cpu().numpy()
-            E = H if est is None else est.detach().cpu().numpy()
-            self.errors += torch.from_numpy(link_errors_host(self.cfg, keys, H, E, sigma).sum(axis=0))
-            self.frames += b
-            return
+            return b, H, (H if est is None else est.detach().cpu().numpy()), keys, per_frame
         dev = self.device
         if on_device(frame_ids):
             if frame_ids.numel() != b:
@@ -274,17 +350,59 @@ class LinkAccumulator:
         if on_device(snr_db):
             if snr_db.numel() not in (1, b):
                 raise ValueError(f"one SNR, or one per frame ({b}), got {snr_db.numel()}")
-            sigma_t = torch.pow(10.0, -snr_db.reshape(-1).to(device=dev, dtype=torch.float64) / 20.0).to(torch.float32).expand(b).contiguous()
+            snr_t = snr_db.reshape(-1).to(device=dev, dtype=torch.float64)
+            per_frame_t = [on_dev(snr_t).to(torch.float32).expand(b).contiguous() for _, on_dev in of_snr]
         else:
-            sigma_t = self._stage(sigma)
+            per_frame_t = [self._stage(a) for a in per_frame]
         H = ideal.to(dev).contiguous()
-        E = H if est is None else est.to(dev).contiguous()
-        if torch.cuda.current_device() != dev.index:                # the launch belongs to the accumulator's device
-            with torch.cuda.device(dev):
-                counts = self._plan(H, E, keys_t, sigma_t)
+        return b, H, (H if est is None else est.to(dev).contiguous()), keys_t, per_frame_t
+
+    def _launch(self, *args, **kw):
+        """The plan on the accumulator's device: the launch belongs to it, whichever device is current."""
+        if torch.cuda.current_device() != self.device.index:
+            with torch.cuda.device(self.device):
+                return self._plan(*args, **kw)
+        return self._plan(*args, **kw)
+
+    @staticmethod
+    def _all_ranks(local: torch.Tensor, group) -> list:
+        """The sweep's one read: ``local`` (float64, on the device) summed over all ranks -- with several, one all-gather."""
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized():   # world_size 1 included: same code path on every launch
+            gathered = [torch.empty_like(local) for _ in range(dist.get_world_size(group))]
+            dist.all_gather(gathered, local, group=group)
+            local = torch.stack(gathered).sum(dim=0)
+        return local.tolist()
+
+
+_SIGMA_OF_SNR = (noise_sigma, lambda snr: torch.pow(10.0, -snr / 20.0))
+
+
+class LinkAccumulator(_FrameSweep):
+    """Bit and symbol errors of a sweep, with the surface of ``metrics.MseAccumulator``: ``update`` per batch, ``result`` once.
+
+    ``update(est, ideal, meta)`` takes the frames' numbers from ``meta[0]`` (the loaders' ``file_no``: float32 as the reference's, so
+    exact below 2^24; ``frame_ids=`` gives exact ones) and their SNR from ``meta[1]`` (``snr_db=`` overrides; one value or one per
+    frame); the frame's key is ``chansim.frame_keys(seed, g)``.  ``est=None`` is perfect channel knowledge (``est = ideal``).  On a HIP
+    device a batch is one launch of ``aft_link_errors_f32`` plus one small integer add into an int64 ``[2]`` device tensor: frame
+    numbers and SNRs that are host tensors are hashed on the host and copied from pinned memory, device tensors are hashed with
+    torch ops -- nothing synchronises.  On a CPU device the float64 definition runs.  ``result`` / ``result_ser`` close the sweep with
+    one read and, with several ranks, the same 16-byte all-gather as the MSE accumulator."""
+
+    def __init__(self, cfg: LinkConfig, device, seed: int = 0) -> None:
+        self._open(cfg, device, seed, "LinkPlan")
+        self.errors = torch.zeros(2, dtype=torch.int64, device=self.device)     # bit errors, symbol errors
+
+    def update(self, est: Optional[torch.Tensor], ideal: torch.Tensor, meta: Optional[tuple] = None, *, frame_ids=None,
+               snr_db=None) -> None:
+        ops = self._operands(est, ideal, meta, frame_ids, snr_db, (_SIGMA_OF_SNR,))
+        if ops is None:
+            return
+        b, H, E, keys, (sigma,) = ops
+        if self._plan is None:
+            self.errors += torch.from_numpy(link_errors_host(self.cfg, keys, H, E, sigma).sum(axis=0))
         else:
-            counts = self._plan(H, E, keys_t, sigma_t)
-        self.errors += counts.sum(dim=0, dtype=torch.int64)
+            self.errors += self._launch(H, E, keys, sigma).sum(dim=0, dtype=torch.int64)
         self.frames += b
 
     def local_pair(self, which: int = 0) -> torch.Tensor:
@@ -293,13 +411,7 @@ class LinkAccumulator:
         return torch.stack([self.errors[which].to(torch.float64), torch.tensor(float(sent), dtype=torch.float64, device=self.device)])
 
     def _rate(self, which: int, group) -> float:
-        pair = self.local_pair(which)
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized():   # world_size 1 included: same code path on every launch
-            gathered = [torch.empty_like(pair) for _ in range(dist.get_world_size(group))]
-            dist.all_gather(gathered, pair, group=group)
-            pair = torch.stack(gathered).sum(dim=0)
-        errors, sent = pair.tolist()                         # the sweep's one read
+        errors, sent = self._all_ranks(self.local_pair(which), group)
         return errors / sent if sent > 0 else 0.0
 
     def result(self, group: Optional["torch.distributed.ProcessGroup"] = None) -> float:
@@ -309,3 +421,48 @@ class LinkAccumulator:
     def result_ser(self, group=None) -> float:
         """Global symbol-error rate."""
         return self._rate(1, group)
+
+
+class RateAccumulator(_FrameSweep):
+    """The achievable rate of a sweep from its max-log LLRs (module docstring, "the soft link"), with ``LinkAccumulator``'s ``update``
+    surface.  A frame's LLR scale is ``llr_scale(snr_db, err_var)``: ``err_var`` is what the caller knows of the estimate's error
+    variance (0: the LLRs trust the estimate as if it were the channel), and ``factors`` the grid of further scale factors the loss is
+    evaluated on in the same pass.  On a HIP device a batch is one launch of ``aft_link_soft_f32`` plus one float64 add into a device
+    tensor ``[K]``; nothing synchronises.  On a CPU device the float64 definition runs.  ``result`` returns the K rates in bit/symbol
+    (``m - loss / data elements``; a rate may be negative), ``result_gmi`` their maximum; either is one read and, with several ranks,
+    one all-gather of ``K + 1`` float64 (the K losses and the frames).  The losses are float sums: ranks that split a sweep differently
+    agree to rounding, not bit for bit -- every rank of one sweep reports the same number."""
+
+    def __init__(self, cfg: LinkConfig, device, seed: int = 0, factors=(1.0,), err_var: float = 0.0) -> None:
+        self._open(cfg, device, seed, "LinkSoftPlan")
+        self.err_var = float(err_var)
+        if not self.err_var >= 0.0:
+            raise ValueError(f"err_var = {err_var!r}: a variance, at least 0")
+        self.factors = _factors(factors)
+        self.loss = torch.zeros(len(self.factors), dtype=torch.float64, device=self.device)
+        self._factors_t = None if self._plan is None else torch.from_numpy(self.factors).to(self.device)
+        self._of_snr = (_SIGMA_OF_SNR, (lambda snr: llr_scale(snr, self.err_var),
+                                        lambda snr: 1.0 / (torch.pow(10.0, -snr / 10.0) + self.err_var)))
+
+    def update(self, est: Optional[torch.Tensor], ideal: torch.Tensor, meta: Optional[tuple] = None, *, frame_ids=None,
+               snr_db=None) -> None:
+        ops = self._operands(est, ideal, meta, frame_ids, snr_db, self._of_snr)
+        if ops is None:
+            return
+        b, H, E, keys, (sigma, scale) = ops
+        if self._plan is None:
+            self.loss += torch.from_numpy(link_llrs_host(self.cfg, keys, H, E, sigma, scale, self.factors)[0].sum(axis=0))
+        else:
+            self.loss += self._launch(H, E, keys, sigma, scale, self._factors_t)[0].sum(dim=0, dtype=torch.float64)
+        self.frames += b
+
+    def result(self, group: Optional["torch.distributed.ProcessGroup"] = None) -> list:
+        """The K rates in bit/symbol over all ranks, one per factor (0.0 each for an empty sweep)."""
+        frames = torch.tensor([float(self.frames)], dtype=torch.float64, device=self.device)
+        *loss, frames = self._all_ranks(torch.cat([self.loss, frames]), group)
+        m, elements = self.cfg.bits_per_symbol, frames * self.cfg.data_elements
+        return [m - v / elements if elements > 0 else 0.0 for v in loss]
+
+    def result_gmi(self, group=None) -> float:
+        """The best rate of the factor grid: the GMI's supremum over the LLR scale, taken on the grid."""
+        return max(self.result(group))

@@ -385,6 +385,29 @@ typedef struct aft_link {
 int aft_link_errors_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys,
                         const float *sigma, int32_t *counts, int batch, void *stream);
 
+/* The soft half of the same link: max-log LLRs of the sent bits and the loss the achievable rate (the bit-interleaved coded-modulation
+ * rate, the GMI of the LLRs) is read from.  With w, gi, gq, x, y, c, p as above, per data element and axis (comp = Re c for I, Im c for Q):
+ *   levels   a_k = d (2k - (L-1)) with Gray label g_k = k ^ (k >> 1), k = 0 .. L-1
+ *   metric   mu_k = a_k (a_k p - 2 comp)              |y - E x|^2 up to a constant: separable per axis, no division
+ *   Delta_j  = min{mu_k : bit_j(g_k) = 1} - min{mu_k : bit_j(g_k) = 0},  bit_j(g) = (g >> (m/2 - 1 - j)) & 1  (MSB first)
+ *   LLR      Lambda_j = scale Delta_j                 positive favours bit 0; I-axis bits 0 .. m/2-1, Q-axis bits m/2 .. m-1 (the order of w)
+ *   loss[f] += log2(1 + exp(-(1 - 2 b_j) factors[f] Lambda_j))      b_j the sent bit, for each of the n_factors factors
+ * A frame's rate at factor f is m - loss[f] / data elements (it may be negative: over-confident LLRs under a mismatched channel), and
+ * the best of a factor grid is the GMI's supremum taken on that grid.  scale float32 [batch] is the LLR scale of each frame
+ * (1 / (noise variance + the estimate's error variance)); factors float32 [n_factors], 1 <= n_factors <= 8.
+ * One launch, one workgroup per frame: loss float32 [batch][n_factors] and, when llr is not NULL, llr float32 [batch, S, T, m], an
+ * element's m values contiguous and zeros at the pilot positions (both device memory).  keys, sigma, scale and factors may be any
+ * device-addressable memory, pinned host memory included.  Every element of loss and llr is written (no initialisation needed); no
+ * atomics; nothing is synchronised; the K sums are float32, added in a fixed order, so a frame's outputs depend neither on batch, nor on
+ * its position in it, nor on the run, nor on whether llr is written.  Loads as aft_link_errors_f32; 16-byte stores of llr when it is
+ * 16-byte aligned and m is 4 or 8 or S T is even, 8-byte stores when it is 8-byte aligned, 4-byte stores otherwise.  exp and log1p are
+ * the device library's, no fast-math; every metric is one fused multiply-add and one product.
+ * Nothing is launched on AFT_ERR_ARG (what aft_link_errors_f32 refuses; a NULL scale / factors / loss; n_factors outside 1..8; scale /
+ * factors / loss / llr not 4-byte aligned) and AFT_ERR_SHAPE (as aft_link_errors_f32). */
+int aft_link_soft_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys,
+                      const float *sigma, const float *scale, const float *factors, int n_factors,
+                      float *loss /* [batch][n_factors] */, float *llr /* [batch,S,T,m] or NULL */, int batch, void *stream);
+
 /* ---- training path of the encoder ---- */
 
 /* Gradients of one nn.TransformerEncoderLayer: same fields and shapes as aft_layer_weights,
