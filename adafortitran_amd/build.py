@@ -14,7 +14,7 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-SOURCES = ("aft_api.hip", "aft_frames.hip", "aft_train.hip", "k_chain.hip", "k_attn.hip", "k_layer.hip", "k_conv.hip", "k_conv_stream.hip", "k_conv_rows.hip", "k_misc.hip", "k_gemm.hip",
+SOURCES = ("aft_api.hip", "aft_frames.hip", "aft_train.hip", "aft_stamps.hip", "k_chain.hip", "k_attn.hip", "k_layer.hip", "k_conv.hip", "k_conv_stream.hip", "k_conv_rows.hip", "k_misc.hip", "k_gemm.hip",
            "k_attn_train.hip", "k_train.hip", "k_conv_train.hip", "k_chain_bwd.hip", "k_ends_train.hip", "k_chansim.hip", "k_lmmse.hip", "k_link.hip")
 LIB = os.path.join(CSRC, "libaft_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -26,15 +26,11 @@ def _deps(src: str):
     return [os.path.join(CSRC, src), *headers, os.path.join(CSRC, "..", "..", "include", "adafortitran_amd.h")]
 
 
-DIAG = False  # --diag: -DAFT_DIAG_STAMPS (in-kernel phase stamps; never for the product build)
-
-
 def _compile(src: str, force: bool, objdir: str, extra) -> str:
     obj = os.path.join(objdir, src.replace(".hip", ".o"))
     if not force and os.path.exists(obj) and all(os.path.getmtime(d) <= os.path.getmtime(obj) for d in _deps(src)):
         return obj
-    flags = FLAGS + (["-DAFT_DIAG_STAMPS"] if DIAG else []) + list(extra)
-    subprocess.run([HIPCC, *flags, "-c", os.path.join(CSRC, src), "-o", obj], check=True)
+    subprocess.run([HIPCC, *FLAGS, *extra, "-c", os.path.join(CSRC, src), "-o", obj], check=True)
     return obj
 
 
@@ -44,6 +40,15 @@ CHECK_FLAGS = ("-DAFT_CHECKED=1",)   # the checked build (aft_internal.h: assert
 def build_checked(force: bool = False, verbose: bool = False) -> str:
     """`libaft_hip_check.so`: the same sources with -DAFT_CHECKED=1, run against the product build by tests/test_checked_build.py."""
     return build(force=force, verbose=verbose, variant="check", extra_flags=CHECK_FLAGS)
+
+
+DIAG_FLAGS = ("-DAFT_DIAG_STAMPS",)   # the diagnostic build (csrc/stamps.h: in-kernel phase stamps, reported under AFT_STAMPS=1); never the product
+
+
+def build_diag(force: bool = False, verbose: bool = False) -> str:
+    """`libaft_hip_diag.so`: the same sources with -DAFT_DIAG_STAMPS, run against the product build by tests/test_diag_build_gpu.py.
+    Load it with AFT_LIB_PATH (or _lib.load_path) and set AFT_STAMPS=1: DESIGN.md section 5, "the diagnostic build"."""
+    return build(force=force, verbose=verbose, variant="diag", extra_flags=DIAG_FLAGS)
 
 
 def build(force: bool = False, verbose: bool = False, variant: str = "", extra_flags=()) -> str:
@@ -56,7 +61,7 @@ def build(force: bool = False, verbose: bool = False, variant: str = "", extra_f
         os.makedirs(objdir, exist_ok=True)
         lib = os.path.join(CSRC, f"libaft_hip_{variant}.so")
         stamp = os.path.join(objdir, "flags.txt")
-        flags_now = " ".join(list(extra_flags) + (["-DAFT_DIAG_STAMPS"] if DIAG else []))
+        flags_now = " ".join(extra_flags)
         if not os.path.exists(stamp) or open(stamp).read() != flags_now:
             force = True
             with open(stamp, "w") as fh:
@@ -72,7 +77,10 @@ def build(force: bool = False, verbose: bool = False, variant: str = "", extra_f
 
 
 if __name__ == "__main__":
-    # python -m adafortitran_amd.build [--force] [--diag] [--variant NAME -DX=1 -DY=2 ...]      (--variant check -DAFT_CHECKED=1 = build_checked)
-    DIAG = "--diag" in sys.argv
-    var = sys.argv[sys.argv.index("--variant") + 1] if "--variant" in sys.argv else ""
-    build(force="--force" in sys.argv or DIAG, verbose=True, variant=var, extra_flags=[a for a in sys.argv[1:] if a.startswith("-D")])
+    # python -m adafortitran_amd.build [--force] [--diag | --variant NAME -DX=1 -DY=2 ...]
+    # (--variant check -DAFT_CHECKED=1 = build_checked; --diag = --variant diag -DAFT_DIAG_STAMPS = build_diag)
+    if "--diag" in sys.argv:
+        build_diag(force="--force" in sys.argv, verbose=True)
+    else:
+        var = sys.argv[sys.argv.index("--variant") + 1] if "--variant" in sys.argv else ""
+        build(force="--force" in sys.argv, verbose=True, variant=var, extra_flags=[a for a in sys.argv[1:] if a.startswith("-D")])

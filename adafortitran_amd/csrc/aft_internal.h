@@ -8,6 +8,9 @@
 
 #include "../../include/adafortitran_amd.h"
 #include "switches.h"   // the run-time switches: switch_on / switch_int
+#ifdef AFT_DIAG_STAMPS
+#include "stamp_report.h"   // the diagnostic build's reports, for the launchers that take a StampRun (below)
+#endif
 
 namespace aft {
 
@@ -18,8 +21,7 @@ using f32x16 = __attribute__((ext_vector_type(16))) float;
 constexpr int kWave = 64;       // CDNA4 wavefront
 constexpr int kHeadDim = 32;    // model_dim / num_head for every config the kernels cover
 constexpr int kTile = 32;       // v_mfma_f32_32x32x2_f32 tile edge
-constexpr int kMaxPatchFeatures = 16;
-constexpr int kSchedSlots = 2048;       // (xcc id, se id, sh id, cu id) -> one ticket counter per CU   // patch_scs * patch_symbols the embedding kernel unrolls
+constexpr int kMaxPatchFeatures = 16;   // patch_scs * patch_symbols the embedding kernel unrolls
 
 inline __host__ __device__ int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
@@ -256,6 +258,27 @@ struct PerDeviceOnce {       // one flag per device; `static PerDeviceOnce x;` i
 };
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device)
 hipError_t ensure_dynamic_lds(PerDeviceOnce &once, const void *kernel, size_t bytes);
+
+#ifdef AFT_DIAG_STAMPS
+// The diagnostic build's stamp table for ONE launch (aft_stamps.hip; device side: stamps.h, reports: stamp_report.h).  A launcher
+// takes a StampRun, hands buffer() to the launch it makes anyway and gives collect() to the report of its kind.  buffer() is the
+// current device's table with `rows` rows zeroed on `st`, or NULL -- the launch runs as in the product -- when the switch is off,
+// the rows do not fit (stamp_rows_fit; says so in one line), the allocation failed or `st` is capturing.
+enum StampKind { kStampChainQkv, kStampChainMlpQkv, kStampChainMlp, kStampAttn, kStampConv, kStampConvStream, kStampChainTrain, kStampKinds };
+class StampRun {
+public:
+    StampRun(Switch sw, StampKind kind, long long rows, hipStream_t st);
+    unsigned long long *buffer() const { return dev_; }
+    // waits for `st`: the table on the host (valid while the StampRun lives); NULL when not stamped or the kind has had its reports
+    const unsigned long long *collect();
+private:
+    unsigned long long *dev_ = nullptr;
+    std::vector<unsigned long long> host_;
+    StampKind kind_;
+    long long rows_;
+    hipStream_t st_;
+};
+#endif
 
 // ---- kernel launchers (each enqueues on `st`, returns hipError_t of the launch) ----
 // scratch_planes (optional, 2 B * S * T floats, free to overwrite): grids other than the default one compute the upsampler as one

@@ -29,6 +29,7 @@
 
 #include "aft_internal.h"
 #include "srd.h"
+#include "stamps.h"
 
 namespace aft {
 
@@ -173,11 +174,6 @@ __device__ __forceinline__ void attn_body(const float *__restrict__ q, const flo
     const int r = lane & 31, h = lane >> 5;
     const bool ragged = (tokens & (kTile - 1)) != 0;   // last key tile holds padded keys
     const float a_one = h == 0 ? 1.0f : 0.0f;           // A operand of the reference MFMA: 1 on the k = 0 half
-#ifdef AFT_DIAG_STAMPS
-#define ASTAMP(i) do { if (stamps && lane == 0) stamps[(size_t)task * 8 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define ASTAMP(i) do { } while (0)
-#endif
     // q, k, vt arrive in MFMA-fragment order from k_chain.hip: [ph][tile][s or g][lane][4] -> every
     // operand load below is one fully coalesced 1-KB buffer_load_dwordx4 per wave
     // (plane, block) index of a task's first block: task / nkt is (plane, head)
@@ -272,10 +268,8 @@ __device__ __forceinline__ void attn_body(const float *__restrict__ q, const flo
       load_tile(vs, 0, vcur, hb0, second_block_bytes(task));
   }
   for (; task >= 0; ++round) {
-    ASTAMP(0);
-#ifdef AFT_DIAG_STAMPS
-    if (stamps && lane == 0) stamps[(size_t)task * 8 + 6] = __builtin_amdgcn_s_memrealtime();
-#endif
+    AFT_STAMP(lane == 0, stamps, task, 0);   // diagnostic build only (stamps.h): lane 0's clock per task, slots 0 .. 4
+    AFT_STAMP_WALL(lane == 0, stamps, task, 6);
     const int qt = task % nkt;
     const int pb = first_block(task);       // plane * nblk + the head's first block
     const int sub = sub_of(task);           // GEN: the head's first slot in its first block
@@ -332,7 +326,7 @@ __device__ __forceinline__ void attn_body(const float *__restrict__ q, const flo
 #pragma unroll
     for (int b = 0; b < NB; ++b) st.oacc[b] = f32x16{0};
     st.lsum2 = f32x2{0.f, 0.f};
-    ASTAMP(1);
+    AFT_STAMP(lane == 0, stamps, task, 1);
 
     // one key tile: `cur` holds S_kt - m_ref (its chain finished an iteration ago), `nxt` receives S_{kt+1} - m_ref.
     // FAST (compile time) = the steady state: tiles kt+1 and kt+2 exist and are full, so there is no mask, no bounds
@@ -419,8 +413,8 @@ __device__ __forceinline__ void attn_body(const float *__restrict__ q, const flo
     step(General{}, sA, sB, kt);           // the last two or three tiles (nkt - kt is 2 or 3; 1 when nkt == 1)
     if (kt + 1 < nkt) step(General{}, sB, sA, kt + 1);
     if (kt + 2 < nkt) step(General{}, sA, sB, kt + 2);
-    ASTAMP(2);
-    ASTAMP(3);
+    AFT_STAMP(lane == 0, stamps, task, 2);
+    AFT_STAMP(lane == 0, stamps, task, 3);
 
     // O^T accumulator: lane = query r, register e = feature d = (e&3) + 8*(e>>2) + 4h -- i.e. registers
     // 4s..4s+3 are the operand-fragment element (s, h) of this head's feature block.  Stored in the
@@ -450,10 +444,8 @@ __device__ __forceinline__ void attn_body(const float *__restrict__ q, const flo
                 srd_store(os, dst + (b * 4 + g) * 1024, o);
             }
     }
-    ASTAMP(4);
-#ifdef AFT_DIAG_STAMPS
-    if (stamps && lane == 0) stamps[(size_t)task * 8 + 5] = __builtin_amdgcn_s_memrealtime();
-#endif
+    AFT_STAMP(lane == 0, stamps, task, 4);
+    AFT_STAMP_WALL(lane == 0, stamps, task, 5);
     task = next_task;
   }
 }

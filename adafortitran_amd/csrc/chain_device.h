@@ -38,6 +38,7 @@
 #pragma once
 #include "aft_internal.h"
 #include "srd.h"
+#include "stamps.h"
 
 namespace aft {
 
@@ -256,15 +257,6 @@ __device__ __forceinline__ f32x16 bias_acc(Srd bias, int f0, int h) {
     }
     return acc;
 }
-
-#ifdef AFT_DIAG_STAMPS  // diagnostic build only: per-phase s_memtime stamps of wave 0
-#define STAMP(i)                                                                                               \
-    do {                                                                                                       \
-        if (a.stamps && tid == 0) a.stamps[(size_t)tile * 16 + (i)] = __builtin_amdgcn_s_memtime();    \
-    } while (0)
-#else
-#define STAMP(i) do { } while (0)
-#endif
 
 // What a tile does before its chain (chain_body's `pre`): nothing in the launch sequence; the tile's attention in layer_kernel.
 struct ChainNoPre {
@@ -495,14 +487,10 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, float *smem, cons
                    w1_lane = ((PT && MLP ? (unsigned)(2 * w) * W * 1024 : w1_off) + lo_lane) * 4,
                    w2_lane = ((PT && MLP ? (unsigned)w * (2 * W) * 1024 : w2_off) + lo_lane) * 4,
                    wq_lane = ((PT && MLP ? (unsigned)w * W * 1024 : wq_off) + lo_lane) * 4;   // byte offsets into the packed weight blocks
-    STAMP(0);
-#ifdef AFT_DIAG_STAMPS
-    if (a.stamps && tid == 0) {
-        a.stamps[(size_t)tile * 16 + 12] = __builtin_amdgcn_s_memrealtime();
-        a.stamps[(size_t)tile * 16 + 14] = ((unsigned long long)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)) << 32) |
-                                           __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11));   // HW_ID, XCC_ID
-    }
-#endif
+    AFT_STAMP(tid == 0, a.stamps, tile, 0);   // diagnostic build only (stamps.h): thread 0's clock at the phase boundaries of a tile, slots 0 .. 11
+    AFT_STAMP_WALL(tid == 0, a.stamps, tile, 12);
+    AFT_STAMP_VALUE(tid == 0, a.stamps, tile, 14, ((unsigned long long)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)) << 32) |
+                                                      __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)));   // HW_ID, XCC_ID
 #ifndef AFT_CHAIN_PFS
 #define AFT_CHAIN_PFS 4   // lead of the weight stream in units of 4 MFMAs (256 cycles); 3..8 measured within 1.5 %
 #endif
@@ -521,7 +509,7 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, float *smem, cons
             request_attn(tile, AHEAD ? PFK : 0, W);
             if (!AHEAD) request_x(tile);
         }
-        STAMP(1);
+        AFT_STAMP(tid == 0, a.stamps, tile, 1);
         // ---- out-projection (transposed) + bias + residual ----
         if constexpr (BS)
             gemm_run_bs<W, 1, PFD, 1, 0>(ring_d, srd_wo, wo_lane, acc_o, [&](int kb, int m) { return bs_split(of[kb][2 * m], of[kb][2 * m + 1]); });
@@ -537,9 +525,9 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, float *smem, cons
         for (int s = 0; s < 4; ++s)
 #pragma unroll
             for (int j = 0; j < 4; ++j) cur[4 * s + j] = acc_o[0][4 * s + j] + xres[s][j];
-        STAMP(2);
+        AFT_STAMP(tid == 0, a.stamps, tile, 2);
         layernorm_rows<D>(cur, stats, par + fb, par + D + fb, w, r, h);   // -> x1 (kept: FFN residual)
-        STAMP(3);
+        AFT_STAMP(tid == 0, a.stamps, tile, 3);
         if constexpr (BS) {
             bs_publish(xb, w, lane, cur);
         } else {
@@ -548,7 +536,7 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, float *smem, cons
                 *reinterpret_cast<f32x4 *>(xb + (w * 4 + s) * 256 + lane * 4) = f32x4{cur[4 * s], cur[4 * s + 1], cur[4 * s + 2], cur[4 * s + 3]};
         }
         __syncthreads();
-        STAMP(4);
+        AFT_STAMP(tid == 0, a.stamps, tile, 4);
         // ---- FFN up-projection + activation -> hidden blocks 2w, 2w+1 ----
         if constexpr (BS)
             gemm_run_bs<W, 2, PFF, 1, 0>(ring_ff, srd_w1, w1_lane, acc_h, [&](int kb, int m) { return bs_fetch(xb, kb, m, lane); });
@@ -558,7 +546,7 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, float *smem, cons
             });
         f32x16 acc_d[1] = {bias_acc(srd_b2, fb, h)};
         gemm_preload<2 * W, 1, PFD, 1>(ring_d, srd_w2, w2_lane);
-        STAMP(5);
+        AFT_STAMP(tid == 0, a.stamps, tile, 5);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             f32x16 hid;
@@ -575,7 +563,7 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, float *smem, cons
             if constexpr (BS) bs_publish(hb, 2 * w + t, lane, hid);
         }
         __syncthreads();
-        STAMP(6);
+        AFT_STAMP(tid == 0, a.stamps, tile, 6);
         // ---- FFN down-projection (transposed) + bias + residual(x1, registers) ----
         if constexpr (BS)
             gemm_run_bs<2 * W, 1, PFD, 1, 0>(ring_d, srd_w2, w2_lane, acc_d, [&](int kb, int m) { return bs_fetch(hb, kb, m, lane); });
@@ -586,9 +574,9 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, float *smem, cons
         if constexpr (QKV) gemm_preload<W, 3, PFQ, W>(ring_qkv, srd_wq, wq_lane);
 #pragma unroll
         for (int e = 0; e < 16; ++e) cur[e] += acc_d[0][e];
-        STAMP(7);
+        AFT_STAMP(tid == 0, a.stamps, tile, 7);
         layernorm_rows<D>(cur, stats, par + 2 * D + fb, par + 3 * D + fb, w, r, h);   // -> x2
-        STAMP(8);
+        AFT_STAMP(tid == 0, a.stamps, tile, 8);
         if constexpr (!QKV) {
             if (AHEAD && tile + tile_stride < ntiles) request_tile(tile + tile_stride);
         }
@@ -685,7 +673,7 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, float *smem, cons
                 *reinterpret_cast<f32x4 *>(xq + (w * 4 + s) * 256 + lane * 4) = f32x4{cur[4 * s], cur[4 * s + 1], cur[4 * s + 2], cur[4 * s + 3]};
         }
         __syncthreads();
-        STAMP(9);
+        AFT_STAMP(tid == 0, a.stamps, tile, 9);
         f32x16 vinit;
 #pragma unroll
         for (int e = 0; e < 16; ++e) vinit[e] = bias_v;
@@ -701,7 +689,7 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, float *smem, cons
             auto xq_frag = [&](int kb, int s) { return *reinterpret_cast<const f32x4 *>(xq + (kb * 4 + s) * 256 + lane * 4); };
             gemm_run<W, 3, PFQ, W, 0x4, decltype(xq_frag), 0x3>(ring_qkv, srd_wq, wq_lane, acc, xq_frag);   // q, k start from 0
         }
-        STAMP(10);
+        AFT_STAMP(tid == 0, a.stamps, tile, 10);
         if (AHEAD && tile + tile_stride < ntiles) request_tile(tile + tile_stride);   // before this tile's stores
         if constexpr (!MLP) {
             if (a.emb_conv != nullptr && tile + tile_stride < tile_end) emb_request(tile + tile_stride);
@@ -877,10 +865,8 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, float *smem, cons
         }   // general epilogue
         }   // !PT
     }
-    STAMP(11);
-#ifdef AFT_DIAG_STAMPS
-    if (a.stamps && tid == 0) a.stamps[(size_t)tile * 16 + 13] = __builtin_amdgcn_s_memrealtime();
-#endif
+    AFT_STAMP(tid == 0, a.stamps, tile, 11);
+    AFT_STAMP_WALL(tid == 0, a.stamps, tile, 13);
     // cross-tile LDS hazards of the persistent loop.  <MLP,QKV>: every re-write sits behind a barrier
     // that follows the last read (xb: LN1 barrier of the next tile; stats: the x2-exchange barrier; hb:
     // two barriers).  <!MLP,QKV> double-buffers its exchange (above).  <MLP,!QKV> has no x2-exchange

@@ -4,6 +4,7 @@
 #include <cstdint>
 
 #include "aft_internal.h"
+#include "stamps.h"
 
 namespace aft {
 

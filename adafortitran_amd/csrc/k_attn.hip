@@ -1,8 +1,6 @@
 // k_attn.hip -- launcher of the attention kernel (device code: attn_device.h).
 #include <algorithm>
-#include <cstdio>
 #include <cstdlib>
-#include <vector>
 
 #include "attn_device.h"
 #include "attn16_device.h"
@@ -86,93 +84,36 @@ hipError_t launch_attention(const aft_config &c, const float *q, const float *k,
                            ntasks);
         return hipGetLastError();
     }
-#ifdef AFT_DIAG_STAMPS
-    if (switch_on(SW_STAMPS)) {   // per-task stamps + in-kernel clock (diagnostic build only)
-        static unsigned long long *dbuf = nullptr;
-        if (!dbuf) (void)hipMalloc(&dbuf, sizeof(unsigned long long) * 8 * 16384);
-        (void)hipMemset(dbuf, 0, sizeof(unsigned long long) * 8 * 16384);
-        hipLaunchKernelGGL((attn_kernel<32>), dim3(blocks), dim3(256), 0, st, q, k, vt, qbias, attn, nblk, tokens,
-                           tokpad, c.model_dim, scale_log2e, ntasks, dbuf);
-        (void)hipDeviceSynchronize();
-        static int printed = 0;
-        if (printed++ < 2) {
-            std::vector<unsigned long long> hbuf(8 * 16384);
-            (void)hipMemcpy(hbuf.data(), dbuf, hbuf.size() * 8, hipMemcpyDeviceToHost);
-            double sum[5] = {0};
-            int n = ntasks < 16384 ? ntasks : 16384;
-            for (int t = 0; t < n; ++t)
-                for (int i = 1; i < 5; ++i) sum[i] += (double)(hbuf[t * 8 + i] - hbuf[t * 8 + i - 1]);
-            double clk = 0;
-            for (int t = 0; t < n; ++t)
-                clk += (double)(hbuf[t * 8 + 4] - hbuf[t * 8 + 0]) / (double)(hbuf[t * 8 + 5] - hbuf[t * 8 + 6]) * 100e6;
-            printf("in-kernel shader clock: %.3f GHz\n", clk / n / 1e9);
-            printf("attn stamps: mean per task: prologue=%.0f loop=%.0f store=%.0f (cycles); MFMA ideal %d\n",
-                   sum[1] / n, sum[2] / n, sum[4] / n, 32 * (tokpad / kTile) * 64);
-            // schedule: when do the tasks of each persistent round start / end (memrealtime = 100 MHz ticks)
-            unsigned long long t0 = ~0ull, t1 = 0;
-            for (int t = 0; t < n; ++t) { t0 = std::min(t0, hbuf[t * 8 + 6]); t1 = std::max(t1, hbuf[t * 8 + 5]); }
-            const int per_round = blocks * 4;
-            double busy = 0;
-            for (int t = 0; t < n; ++t) busy += (double)(hbuf[t * 8 + 5] - hbuf[t * 8 + 6]);
-            printf("  span %.1f us, %d tasks in rounds of %d; mean concurrent waves per SIMD %.2f\n", (t1 - t0) / 100.0, n, per_round,
-                   busy / (double)(t1 - t0) / 1024.0);
-            for (int r0 = 0; r0 < n; r0 += per_round) {
-                double smin = 1e30, smax = 0, ssum = 0, emin = 1e30, emax = 0, esum = 0;
-                const int r1 = std::min(n, r0 + per_round);
-                for (int t = r0; t < r1; ++t) {
-                    const double st = (hbuf[t * 8 + 6] - t0) / 100.0, en = (hbuf[t * 8 + 5] - t0) / 100.0;
-                    smin = std::min(smin, st); smax = std::max(smax, st); ssum += st;
-                    emin = std::min(emin, en); emax = std::max(emax, en); esum += en;
-                }
-                printf("  round %d: start %.1f / %.1f / %.1f us (min/mean/max), end %.1f / %.1f / %.1f us\n", r0 / per_round, smin,
-                       ssum / (r1 - r0), smax, emin, esum / (r1 - r0), emax);
-            }
-        }
-        return hipGetLastError();
-    }
+    // one launch of whichever instantiation the shape selects; `extra`: the stamps pointer of attn_kernel
+    auto launch = [&](auto kernel, auto... extra) {
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, st, q, k, vt, qbias, attn, nblk, tokens, tokpad, c.model_dim, scale_log2e,
+                           ntasks, extra...);
+    };
+    unsigned long long *stamps = nullptr;
+#ifdef AFT_DIAG_STAMPS   // per-task stamps + in-kernel clock of this launch (never in the product build); attn16_kernel carries none
+    StampRun run(SW_STAMPS, kStampAttn, hd == 8 || hd == 16 ? 0 : ntasks, st);
+    stamps = run.buffer();
 #endif
-    unsigned long long *no_stamps = nullptr;
-#define AFT_ATTN_HD(HD_)                                                                                                              \
-    if (hd == HD_) {                                                                                                                  \
-        hipLaunchKernelGGL((attn_kernel<HD_>), dim3(blocks), dim3(256), 0, st, q, k, vt, qbias, attn, nblk, tokens, tokpad, c.model_dim, \
-                           scale_log2e, ntasks, no_stamps);                                                                           \
-        return hipGetLastError();                                                                                                     \
-    }
-    if (hd == 8) {       // late round 6: 16x16x4 MFMAs with half of every operand idle (attn16_device.h)
-        if (tokens == 280)
-            hipLaunchKernelGGL((attn16_kernel<280, 8>), dim3(blocks), dim3(256), 0, st, q, k, vt, qbias, attn, nblk, tokens, tokpad, c.model_dim,
-                               scale_log2e, ntasks);
-        else
-            hipLaunchKernelGGL((attn16_kernel<0, 8>), dim3(blocks), dim3(256), 0, st, q, k, vt, qbias, attn, nblk, tokens, tokpad, c.model_dim,
-                               scale_log2e, ntasks);
-        return hipGetLastError();
-    }
-    AFT_ATTN_HD(24) AFT_ATTN_HD(40) AFT_ATTN_HD(48)   // heads that start anywhere in a block (attn_device.h); covered, not tuned
-#undef AFT_ATTN_HD
-    if (hd != 16 && hd != 32 && hd != 64) return hipErrorInvalidValue;   // check_config refuses these
-    if (hd == 16) {     // 16x16x4 MFMAs (attn16_device.h)
-        if (tokens == 280)
-            hipLaunchKernelGGL((attn16_kernel<280>), dim3(blocks), dim3(256), 0, st, q, k, vt, qbias, attn, nblk, tokens, tokpad, c.model_dim,
-                               scale_log2e, ntasks);
-        else
-            hipLaunchKernelGGL((attn16_kernel<0>), dim3(blocks), dim3(256), 0, st, q, k, vt, qbias, attn, nblk, tokens, tokpad, c.model_dim,
-                               scale_log2e, ntasks);
-    } else if (hd == 64)
-        hipLaunchKernelGGL((attn_kernel<64>), dim3(blocks), dim3(256), 0, st, q, k, vt, qbias, attn, nblk, tokens, tokpad, c.model_dim,
-                           scale_log2e, ntasks, no_stamps);
+    if (hd == 8)         // late round 6: 16x16x4 MFMAs with half of every operand idle (attn16_device.h)
+        tokens == 280 ? launch(attn16_kernel<280, 8>) : launch(attn16_kernel<0, 8>);
+    else if (hd == 24) launch(attn_kernel<24>, stamps);   // 24, 40, 48: heads that start anywhere in a block (attn_device.h); covered, not tuned
+    else if (hd == 40) launch(attn_kernel<40>, stamps);
+    else if (hd == 48) launch(attn_kernel<48>, stamps);
+    else if (hd == 16)   // 16x16x4 MFMAs (attn16_device.h)
+        tokens == 280 ? launch(attn16_kernel<280>) : launch(attn16_kernel<0>);
+    else if (hd == 64) launch(attn_kernel<64>, stamps);
+    else if (hd != 32) return hipErrorInvalidValue;   // check_config refuses these
     // the two benchmark grids with the token count at compile time (120 x 14 -> 280 tokens, 240 x 28 -> 1120): the tile loop's trip
     // count, the last-tiles logic and the padding masks resolve in the compiler -- 125 VGPRs and no scalar spills instead of 168 and 40,
     // -2.7 % time at 280 tokens
-    else if (tokens == 280)
-        hipLaunchKernelGGL((attn_kernel<32, 280>), dim3(blocks), dim3(256), 0, st, q, k, vt, qbias, attn, nblk, tokens, tokpad, c.model_dim,
-                           scale_log2e, ntasks, no_stamps);
-    else if (tokens == 1120)
-        hipLaunchKernelGGL((attn_kernel<32, 1120>), dim3(blocks), dim3(256), 0, st, q, k, vt, qbias, attn, nblk, tokens, tokpad, c.model_dim,
-                           scale_log2e, ntasks, no_stamps);
-    else
-        hipLaunchKernelGGL((attn_kernel<32>), dim3(blocks), dim3(256), 0, st, q, k, vt, qbias, attn, nblk, tokens, tokpad, c.model_dim,
-                           scale_log2e, ntasks, no_stamps);
-    return hipGetLastError();
+    else if (tokens == 280) launch(attn_kernel<32, 280>, stamps);
+    else if (tokens == 1120) launch(attn_kernel<32, 1120>, stamps);
+    else launch(attn_kernel<32>, stamps);
+    const hipError_t e = hipGetLastError();
+#ifdef AFT_DIAG_STAMPS
+    if (const unsigned long long *h = run.collect()) report_attn(stdout, h, ntasks, blocks, tokpad);
+#endif
+    return e;
 }
 
 }  // namespace aft

@@ -1,8 +1,6 @@
 // k_chain.hip -- launchers of the row-local chain kernel (device code: chain_device.h) and the weight re-packing kernel.
 #include <algorithm>
-#include <cstdio>
 #include <cstdlib>
-#include <vector>
 
 #include "chain_device.h"
 #include "pack_device.h"
@@ -63,89 +61,24 @@ static hipError_t launch_chain_v(const ChainArgs &args, hipStream_t st) {
     const int resident = current_device_cus() * kPerCu;
     const int blocks = std::min((args.rows + 31) / 32, resident);
     const size_t lds = S::LDS_BYTES;
+#ifdef AFT_DIAG_STAMPS   // phase stamps of this launch, printed on the host (never in the product build)
+    StampRun run(SW_STAMPS, MLP && QKV ? kStampChainMlpQkv : MLP ? kStampChainMlp : kStampChainQkv, (args.rows + 31) / 32, st);
+    ChainArgs stamped = args;
+    stamped.stamps = run.buffer();
+    const ChainArgs &a = stamped;
+#else
+    const ChainArgs &a = args;
+#endif
+    hipLaunchKernelGGL((chain_kernel<D, ACT, MLP, QKV>), dim3(blocks), dim3(S::THREADS), lds, st, a);
+    const hipError_t e = hipGetLastError();
 #ifdef AFT_DIAG_STAMPS
-    if (switch_on(SW_STAMPS)) {   // phase stamps, printed on the host (never in the product build)
-        static unsigned long long *dbuf = nullptr;
-        if (!dbuf) (void)hipMalloc(&dbuf, sizeof(unsigned long long) * 16 * 4096);
-        (void)hipMemset(dbuf, 0, sizeof(unsigned long long) * 16 * 4096);
-        ChainArgs a2 = args;
-        a2.stamps = dbuf;
-        hipLaunchKernelGGL((chain_kernel<D, ACT, MLP, QKV>), dim3(blocks), dim3(S::THREADS), lds, st, a2);
-        (void)hipDeviceSynchronize();
-        static int printed = 0;
-        if (printed++ < 2) {
-            int nb = 0;
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, chain_kernel<D, ACT, MLP, QKV>, S::THREADS, lds);
-            std::vector<unsigned long long> h(16 * 4096);
-            (void)hipMemcpy(h.data(), dbuf, h.size() * 8, hipMemcpyDeviceToHost);
-            double sum[12] = {0};
-            const int nblk = std::min((args.rows + 31) / 32, 4096);
-            for (int b = 0; b < nblk; ++b)
-                for (int i = 1; i < 12; ++i) {
-                    int k = i - 1;
-                    while (k > 0 && h[b * 16 + k] == 0) --k;
-                    if (h[b * 16 + i]) sum[i] += (double)(h[b * 16 + i] - h[b * 16 + k]);
-                }
-            printf("chain<%d,mlp=%d,qkv=%d> %d blocks/CU at %zu B LDS; mean cycles per phase:", D, (int)MLP, (int)QKV, nb, lds);
-            for (int i = 1; i < 12; ++i) printf(" [%d]=%.0f", i, sum[i] / nblk);
-            printf("\n");
-            // residency: busy tile-time per (xcc, hw cu id) / kernel span (memrealtime = 100 MHz)
-            unsigned long long t0 = ~0ull, t1 = 0;
-            std::vector<double> busy(8 * 4096, 0.0);
-            std::vector<int> cnt(8 * 4096, 0);
-            for (int b = 0; b < nblk; ++b) {
-                const unsigned long long s0 = h[b * 16 + 12], s1 = h[b * 16 + 13], id = h[b * 16 + 14];
-                t0 = std::min(t0, s0); t1 = std::max(t1, s1);
-                const unsigned hw = (unsigned)(id >> 32), xcc = (unsigned)id & 7;
-                const unsigned cu = ((hw >> 8) & 0xf) | (((hw >> 13) & 0x7) << 4) | (((hw >> 12) & 1) << 7);   // cu_id, se_id, sh_id
-                busy[xcc * 4096 + cu] += (double)(s1 - s0);
-                cnt[xcc * 4096 + cu]++;
-            }
-            int ncu = 0, mn = 1 << 30, mx = 0; double tot = 0;
-            for (size_t i = 0; i < busy.size(); ++i) if (cnt[i]) { ++ncu; tot += busy[i]; mn = std::min(mn, cnt[i]); mx = std::max(mx, cnt[i]); }
-            printf("  span %.1f us; %d distinct CUs; tiles/CU min %d max %d; mean concurrent workgroups per CU %.2f; mean tile time %.1f us\n",
-                   (t1 - t0) / 100.0, ncu, mn, mx, tot / ncu / (double)(t1 - t0), tot / nblk / 100.0);
-            {   // is the spread of finish times WITHIN a CU (arbitration between its workgroups) or ACROSS CUs / XCDs?
-                std::vector<double> first(8 * 4096, 1e30), last(8 * 4096, 0.0);
-                double xlast[8] = {0}; int xn[8] = {0};
-                for (int b = 0; b < nblk; ++b) {
-                    const unsigned long long id = h[b * 16 + 14];
-                    const unsigned hw = (unsigned)(id >> 32), xcc = (unsigned)id & 7;
-                    const unsigned cu = ((hw >> 8) & 0xf) | (((hw >> 13) & 0x7) << 4) | (((hw >> 12) & 1) << 7);
-                    const double en = (h[b * 16 + 13] - t0) / 100.0;
-                    if (b + blocks >= nblk || b + 2 * blocks >= nblk) {   // a workgroup's last tile
-                        if (b + blocks >= nblk) { first[xcc * 4096 + cu] = std::min(first[xcc * 4096 + cu], en); last[xcc * 4096 + cu] = std::max(last[xcc * 4096 + cu], en); }
-                    }
-                }
-                double fmin = 1e30, fmax = 0, fsum = 0, lmin = 1e30, lmax = 0, lsum = 0; int n = 0;
-                for (size_t i = 0; i < last.size(); ++i) if (last[i] > 0) {
-                    ++n; fmin = std::min(fmin, first[i]); fmax = std::max(fmax, first[i]); fsum += first[i];
-                    lmin = std::min(lmin, last[i]); lmax = std::max(lmax, last[i]); lsum += last[i];
-                    xlast[i / 4096] += last[i]; xn[i / 4096]++;
-                }
-                printf("  per CU, last-round tiles: first workgroup done %.1f / %.1f / %.1f us, last workgroup done %.1f / %.1f / %.1f us (min/mean/max over %d CUs)\n",
-                       fmin, fsum / n, fmax, lmin, lsum / n, lmax, n);
-                printf("  mean finish per XCD:");
-                for (int x = 0; x < 8; ++x) printf(" %.1f", xn[x] ? xlast[x] / xn[x] : 0.0);
-                printf("\n");
-            }
-            for (int r0 = 0; r0 < nblk; r0 += blocks) {   // persistent rounds: when do their tiles start / end
-                double smin = 1e30, smax = 0, ssum = 0, emin = 1e30, emax = 0, esum = 0;
-                const int r1 = std::min(nblk, r0 + blocks);
-                for (int b = r0; b < r1; ++b) {
-                    const double st = (h[b * 16 + 12] - t0) / 100.0, en = (h[b * 16 + 13] - t0) / 100.0;
-                    smin = std::min(smin, st); smax = std::max(smax, st); ssum += st;
-                    emin = std::min(emin, en); emax = std::max(emax, en); esum += en;
-                }
-                printf("  round %d (%d tiles): start %.1f / %.1f / %.1f us (min/mean/max), end %.1f / %.1f / %.1f us\n", r0 / blocks, r1 - r0,
-                       smin, ssum / (r1 - r0), smax, emin, esum / (r1 - r0), emax);
-            }
-        }
-        return hipGetLastError();
+    if (const unsigned long long *h = run.collect()) {
+        int per_cu = 0;
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, chain_kernel<D, ACT, MLP, QKV>, S::THREADS, lds);
+        report_chain(stdout, h, (args.rows + 31) / 32, blocks, D, (int)MLP, (int)QKV, per_cu, lds);
     }
 #endif
-    hipLaunchKernelGGL((chain_kernel<D, ACT, MLP, QKV>), dim3(blocks), dim3(S::THREADS), lds, st, args);
-    return hipGetLastError();
+    return e;
 }
 
 // Packed-weight block of one layer inside the workspace (floats): [in_proj 3D*D][out_proj D*D][lin1 2D*D][lin2 D*2D]

@@ -24,9 +24,7 @@
 // (g (.) xhat, g) for the LayerNorm parameter gradients (cross-lane DPP reduction, fixed-order slice reduction later).
 #include <algorithm>
 
-#include <cstdio>
 #include <cstdlib>
-#include <vector>
 
 #include "chain_device.h"
 
@@ -536,11 +534,6 @@ __global__ __launch_bounds__(D * 2, D <= 128 ? 3 : 2) void chain_fwd_train_kerne
     // (timing experiment, round 3: without the five tape stores below the launch takes 106 us instead of 145 -- the inference chain's
     //  time for the same products; the 39 us are store waits)
     constexpr bool TAPE = true;
-#ifdef AFT_DIAG_STAMPS
-#define TSTAMP(i) do { if (a.stamps && tid == 0) a.stamps[(size_t)tile * 16 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define TSTAMP(i) do { } while (0)
-#endif
 
     const Srd srd_wo = make_srd(a.wo), srd_w1 = make_srd(a.w1), srd_w2 = make_srd(a.w2);
     const Srd srd_attn = make_srd(a.attn), srd_x = make_srd(a.x);
@@ -624,10 +617,8 @@ __global__ __launch_bounds__(D * 2, D <= 128 ? 3 : 2) void chain_fwd_train_kerne
         WRing<1, PFD> ring_d;
         WRing<2, PFF> ring_ff;
 
-        TSTAMP(0);
-#ifdef AFT_DIAG_STAMPS
-        if (a.stamps && tid == 0) a.stamps[(size_t)tile * 16 + 9] = __builtin_amdgcn_s_memrealtime();   // 100 MHz, one clock for the chip
-#endif
+        AFT_STAMP(tid == 0, a.stamps, tile, 0);   // diagnostic build only (stamps.h)
+        AFT_STAMP_WALL(tid == 0, a.stamps, tile, 9);
         // ---- out-projection + bias, dropout 1, residual ----
         f32x16 acc_o[1] = {bias_acc(srd_bo, fb, h)};
         gemm_preload<W, 1, PFD, 1>(ring_d, srd_wo, wo_lane);
@@ -638,7 +629,7 @@ __global__ __launch_bounds__(D * 2, D <= 128 ? 3 : 2) void chain_fwd_train_kerne
         gemm_run<W, 1, PFD, 1, 0>(ring_d, srd_wo, wo_lane, acc_o, [&](int kb, int s) {
             return *reinterpret_cast<const f32x4 *>(hb + (2 * kb * 4 + s) * 256 + io.pw[s]);   // attention tile: the waves' even hidden blocks
         });
-        TSTAMP(1);
+        AFT_STAMP(tid == 0, a.stamps, tile, 1);
         f32x16 acc_h[2] = {bias_acc(srd_b1, 2 * fb, h), bias_acc(srd_b1, 2 * fb + 32, h)};
         gemm_preload<W, 2, PFF, 1>(ring_ff, srd_w1, w1_lane);
         uint32_t rw1 = 0, rw2 = 0, rw3 = 0;
@@ -666,12 +657,12 @@ __global__ __launch_bounds__(D * 2, D <= 128 ? 3 : 2) void chain_fwd_train_kerne
             line_put(xw, io, s, f32x4{cur[4 * s], cur[4 * s + 1], cur[4 * s + 2], cur[4 * s + 3]});   // published, and stored from there
         if (TAPE) line_store<D>(srd_x1, xw, row0, fb, a.rows);
         __syncthreads();
-        TSTAMP(2);
+        AFT_STAMP(tid == 0, a.stamps, tile, 2);
         // ---- linear1 + bias -> a (kept), activation, dropout 2 -> hd (kept, published) ----
         gemm_run<W, 2, PFF, 1, 0>(ring_ff, srd_w1, w1_lane, acc_h, [&](int kb, int s) {
             return *reinterpret_cast<const f32x4 *>(xb + (kb * 4 + s) * 256 + io.pw[s]);
         });
-        TSTAMP(3);
+        AFT_STAMP(tid == 0, a.stamps, tile, 3);
         f32x16 acc_d[1] = {bias_acc(srd_b2, fb, h)};
         gemm_preload<2 * W, 1, PFD, 1>(ring_d, srd_w2, w2_lane);
         // a (block t) takes its turn through the wave's OTHER hidden block, hd is stored from where it is published; the LDS serves
@@ -695,7 +686,7 @@ __global__ __launch_bounds__(D * 2, D <= 128 ? 3 : 2) void chain_fwd_train_kerne
             if (TAPE) line_store<2 * D>(srd_hd, hw + 1024 * t, row0, 2 * fb + 32 * t, a.rows);
         }
         __syncthreads();
-        TSTAMP(4);
+        AFT_STAMP(tid == 0, a.stamps, tile, 4);
         {   // the next tile's attention / residual blocks: requested here, staged at the end of this tile
             const int ntile = tile + gridDim.x;
             fetch_tile(ntile < ntiles ? ntile * 32 : a.rows);
@@ -704,7 +695,7 @@ __global__ __launch_bounds__(D * 2, D <= 128 ? 3 : 2) void chain_fwd_train_kerne
         gemm_run<2 * W, 1, PFD, 1, 0>(ring_d, srd_w2, w2_lane, acc_d, [&](int kb, int s) {
             return *reinterpret_cast<const f32x4 *>(hb + (kb * 4 + s) * 256 + io.pw[s]);
         });
-        TSTAMP(5);
+        AFT_STAMP(tid == 0, a.stamps, tile, 5);
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             f32x4 y = {acc_d[0][4 * s], acc_d[0][4 * s + 1], acc_d[0][4 * s + 2], acc_d[0][4 * s + 3]};
@@ -723,7 +714,7 @@ __global__ __launch_bounds__(D * 2, D <= 128 ? 3 : 2) void chain_fwd_train_kerne
 #pragma unroll
         for (int s = 0; s < 4; ++s) line_put(xw, io, s, f32x4{cur[4 * s], cur[4 * s + 1], cur[4 * s + 2], cur[4 * s + 3]});
         line_store<D>(srd_out, xw, row0, fb, a.rows);
-        TSTAMP(6);
+        AFT_STAMP(tid == 0, a.stamps, tile, 6);
         if constexpr (QKV) {
             // ---- the next layer's in-projection on x2 (the tile is still in registers): q | k | v of feature block w, bias as the
             //      accumulators' initial value, row-major into the next layer's tape.  x1's readers are past the hidden barrier. ----
@@ -749,9 +740,9 @@ __global__ __launch_bounds__(D * 2, D <= 128 ? 3 : 2) void chain_fwd_train_kerne
             stage_lines(hw, na);      // (the hidden blocks' readers are past the LayerNorm-2 barrier)
         }
         stage_lines(hw + 1024, nx);
-        TSTAMP(7);
+        AFT_STAMP(tid == 0, a.stamps, tile, 7);
         __syncthreads();    // the next tile's LayerNorm-1 partials must not overtake this tile's LayerNorm-2 readers
-        TSTAMP(8);
+        AFT_STAMP(tid == 0, a.stamps, tile, 8);
     }
 }
 
@@ -767,45 +758,20 @@ static hipError_t launch_chain_fwd_train_t(const ChainTrainArgs &args, hipStream
     hipError_t ea = ensure_dynamic_lds(lds_attr, reinterpret_cast<const void *>(chain_fwd_train_kernel<D, ACT, QKV>), T::LDS_BYTES);
     if (ea != hipSuccess) return ea;
     const int blocks = std::min((args.rows + 31) / 32, current_device_cus() * 3);
-#ifdef AFT_DIAG_STAMPS
-    if (switch_on(SW_STAMPS)) {   // diagnostic build only: mean cycles per phase of a tile (wave 0), and when the workgroups started
-        const int ntiles = (args.rows + 31) / 32;
-        static unsigned long long *dbuf = nullptr;
-        if (!dbuf) (void)hipMalloc(&dbuf, sizeof(unsigned long long) * 16 * 8192);
-        (void)hipMemsetAsync(dbuf, 0, sizeof(unsigned long long) * 16 * 8192, st);
-        ChainTrainArgs a2 = args;
-        a2.stamps = ntiles <= 8192 ? dbuf : nullptr;
-        hipLaunchKernelGGL((chain_fwd_train_kernel<D, ACT, QKV>), dim3(blocks), dim3(ChainShape<D>::THREADS), T::LDS_BYTES, st, a2);
-        (void)hipStreamSynchronize(st);
-        static int printed = 0;
-        if (a2.stamps && printed++ < 3) {
-            std::vector<unsigned long long> hb(16 * (size_t)ntiles);
-            (void)hipMemcpy(hb.data(), dbuf, hb.size() * 8, hipMemcpyDeviceToHost);
-            const int nb = std::min(blocks, ntiles);
-            unsigned long long t0 = ~0ull, tend = 0;
-            for (int t = 0; t < nb; ++t) t0 = std::min(t0, hb[(size_t)t * 16 + 9]);
-            for (int t = 0; t < ntiles; ++t) tend = std::max(tend, hb[(size_t)t * 16 + 9]);
-            int late = 0;
-            double mean = 0, mx = 0;
-            for (int t = 0; t < nb; ++t) {
-                const double us = (double)(hb[(size_t)t * 16 + 9] - t0) * 0.01;
-                mean += us; mx = std::max(mx, us); late += us > 20.0;
-            }
-            printf("chain_fwd_train<QKV=%d>: %d workgroups, first tile starts %.1f us (mean) / %.1f us (max) after the earliest, %d later than 20 us; "
-                   "the launch's last tile starts at %.1f us\n", (int)QKV, nb, mean / nb, mx, late, (double)(tend - t0) * 0.01);
-            double sum[9] = {0};
-            for (int t = 0; t < ntiles; ++t)
-                for (int i = 1; i < 9; ++i) sum[i] += (double)(hb[(size_t)t * 16 + i] - hb[(size_t)t * 16 + i - 1]);
-            printf("  mean cycles per tile: outproj=%.0f s1+LN1+x1+barrier=%.0f ffn_up=%.0f act+a+hd+barrier=%.0f ffn_down=%.0f s2+LN2+out=%.0f "
-                   "qkv=%.0f end_barrier=%.0f total=%.0f\n", sum[1] / ntiles, sum[2] / ntiles, sum[3] / ntiles, sum[4] / ntiles, sum[5] / ntiles,
-                   sum[6] / ntiles, sum[7] / ntiles, sum[8] / ntiles,
-                   (sum[1] + sum[2] + sum[3] + sum[4] + sum[5] + sum[6] + sum[7] + sum[8]) / ntiles);
-        }
-        return hipGetLastError();
-    }
+#ifdef AFT_DIAG_STAMPS   // wave 0's cycles per phase of a tile and when the workgroups started (never in the product build)
+    StampRun run(SW_STAMPS, kStampChainTrain, (args.rows + 31) / 32, st);
+    ChainTrainArgs stamped = args;
+    stamped.stamps = run.buffer();
+    const ChainTrainArgs &a = stamped;
+#else
+    const ChainTrainArgs &a = args;
 #endif
-    hipLaunchKernelGGL((chain_fwd_train_kernel<D, ACT, QKV>), dim3(blocks), dim3(ChainShape<D>::THREADS), T::LDS_BYTES, st, args);
-    return hipGetLastError();
+    hipLaunchKernelGGL((chain_fwd_train_kernel<D, ACT, QKV>), dim3(blocks), dim3(ChainShape<D>::THREADS), T::LDS_BYTES, st, a);
+    const hipError_t e = hipGetLastError();
+#ifdef AFT_DIAG_STAMPS
+    if (const unsigned long long *h = run.collect()) report_chain_train(stdout, h, (args.rows + 31) / 32, blocks, (int)QKV);
+#endif
+    return e;
 }
 
 // packed: one layer's fp32 fragment image (packed_layer_floats(d) floats of scratch, filled here)

@@ -28,9 +28,7 @@
 // the whole kernel.  HBM traffic per plane = compulsory only (pilots / x rows in, one plane out).
 // Bands carry a 4-row halo (4 stacked 3x3 convs); the default 120x14 grid is one band, 4 tiles.
 #include <cstdint>
-#include <cstdio>
 #include <cstdlib>
-#include <vector>
 
 #include "conv_device.h"
 
@@ -68,12 +66,7 @@ __global__ __launch_bounds__(kConvThreads) void conv_stack_kernel(const ConvArgs
     if (!FIXED) AFT_DEV_ASSERT(17 * plane <= a.arena && 0 <= lc0 && lc0 < lc1 && lc1 <= T && lc0 >= min(o0, 4) && T - lc1 >= min(TG - o1, 4));
 
     const int tid = threadIdx.x;
-#ifdef AFT_DIAG_STAMPS
-#define CSTAMP(i) do { if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 16 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define CSTAMP(i) do { } while (0)
-#endif
-    CSTAMP(0);
+    AFT_STAMP(tid == 0, a.stamps, blockIdx.x, 0);
     const int frame = n >> 1, part = n & 1;
     const int gr0 = band * BR - 4;  // global row of local row 0
 
@@ -117,7 +110,7 @@ __global__ __launch_bounds__(kConvThreads) void conv_stack_kernel(const ConvArgs
         }
     }
     __syncthreads();
-    CSTAMP(1);
+    AFT_STAMP(tid == 0, a.stamps, blockIdx.x, 1);
     // ---- zero LDS (border columns, rows outside the plane, halo rows nobody writes); the conv2
     //      bias in accumulator-register order sits behind `small` ----
     {
@@ -130,7 +123,7 @@ __global__ __launch_bounds__(kConvThreads) void conv_stack_kernel(const ConvArgs
     if (tid >= 64 && tid < 144) w1s[tid - 64] = tid < 136 ? a.cw[0][tid - 64] : ((TRAIN && !a.cb[0]) ? 0.f : a.cb[0][tid - 136]);
     if (tid < 32) bias2[tid] = (TRAIN && !a.cb[1]) ? 0.f : a.cb[1][(tid & 3) + 8 * ((tid & 15) >> 2) + 4 * (tid >> 4)];
     __syncthreads();
-    CSTAMP(2);
+    AFT_STAMP(tid == 0, a.stamps, blockIdx.x, 2);
 
     // ---- input plane ----
     if (TRAIN && a.mode == 2) {
@@ -354,7 +347,7 @@ __global__ __launch_bounds__(kConvThreads) void conv_stack_kernel(const ConvArgs
         }
     }
     __syncthreads();
-    CSTAMP(3);
+    AFT_STAMP(tid == 0, a.stamps, blockIdx.x, 3);
 
     // ---- conv1: 1 -> 8, ReLU, rows [1, LR-1); one thread = 4 consecutive rows of one column (a 6 x 3 window read once).
     //      The 80 weights / biases come from LDS into VECTOR registers: as scalar operands they overflowed the SGPR file
@@ -416,7 +409,7 @@ __global__ __launch_bounds__(kConvThreads) void conv_stack_kernel(const ConvArgs
         }
     }
     __syncthreads();
-    CSTAMP(4);
+    AFT_STAMP(tid == 0, a.stamps, blockIdx.x, 4);
 
     // ---- conv2 + conv3 on the matrix cores ----
     const int r3lo = band == 0 ? 4 : 3;   // first local row whose conv3 output is needed and inside the plane
@@ -646,9 +639,9 @@ __global__ __launch_bounds__(kConvThreads) void conv_stack_kernel(const ConvArgs
         store_col(thi, acc3[4], acc3[5], acc3[6], acc3[7]);   // overlapping sweep: only stored when thi == T-1 (column T is zero padding)
         if (EXACT) store_col(thi + 1, acc3[0], acc3[1], acc3[2], acc3[3]);   // the kx = 0 tap of column thi for the right neighbour
     }
-    CSTAMP(5);
+    AFT_STAMP(tid == 0, a.stamps, blockIdx.x, 5);
     __syncthreads();
-    CSTAMP(6);
+    AFT_STAMP(tid == 0, a.stamps, blockIdx.x, 6);
     if constexpr (!TRAIN) {
         // seam fix-up: c3[ch][t][row] = ReLU(own partial + neighbour's tap + bias) for the two columns at each seam
         const int nseam = (NSEG >= 2 && (FIXED || a.xoff >= 0)) ? NSEG - 1 : 0;
@@ -665,7 +658,7 @@ __global__ __launch_bounds__(kConvThreads) void conv_stack_kernel(const ConvArgs
         }
     }
 
-    CSTAMP(7);
+    AFT_STAMP(tid == 0, a.stamps, blockIdx.x, 7);
     // ---- conv4: 8 -> 1, no activation, rows of this band only; one thread = one row x 4 columns ----
     const int tstrips = (lc1 - lc0 + 3) >> 2;   // the owned columns only
     for (int i = tid; i < BR * tstrips; i += kConvThreads) {
@@ -700,8 +693,7 @@ __global__ __launch_bounds__(kConvThreads) void conv_stack_kernel(const ConvArgs
                 a.out_complex[(((size_t)frame * S + gr) * TG + w0 + t) * 2 + part] = acc[q];
         }
     }
-    CSTAMP(8);
-#undef CSTAMP
+    AFT_STAMP(tid == 0, a.stamps, blockIdx.x, 8);
 }
 
 // Largest row band (divides S) whose 17 channel planes fit 160 KB of LDS.  A band needs conv3 rows
@@ -839,32 +831,18 @@ static hipError_t launch_conv_geo(ConvArgs &a, int planes, size_t lds, hipStream
     static PerDeviceOnce lds_attr;   // per instantiation x device
     hipError_t ea = ensure_dynamic_lds(lds_attr, reinterpret_cast<const void *>(conv_stack_kernel<TRAIN, FIXED>), 160 * 1024);
     if (ea != hipSuccess) return ea;
-#ifdef AFT_DIAG_STAMPS
-    if (!TRAIN && switch_on(SW_STAMPS)) {   // diagnostic build only: mean cycles per phase (thread 0 of every workgroup)
-        static unsigned long long *dbuf = nullptr;
-        const int nb = planes * a.nbands;
-        if (!dbuf) (void)hipMalloc(&dbuf, sizeof(unsigned long long) * 16 * 4096);
-        (void)hipMemset(dbuf, 0, sizeof(unsigned long long) * 16 * 4096);
-        a.stamps = dbuf;
-        hipLaunchKernelGGL((conv_stack_kernel<TRAIN, FIXED>), dim3(nb), dim3(kConvThreads), lds, st, a);
-        (void)hipDeviceSynchronize();
-        static int printed = 0;
-        if (printed++ < 4 && nb <= 4096) {
-            std::vector<unsigned long long> hb(16 * (size_t)nb);
-            (void)hipMemcpy(hb.data(), dbuf, hb.size() * 8, hipMemcpyDeviceToHost);
-            double sum[9] = {0};
-            for (int b = 0; b < nb; ++b)
-                for (int i = 1; i < 9; ++i) sum[i] += (double)(hb[(size_t)b * 16 + i] - hb[(size_t)b * 16 + i - 1]);
-            printf("conv mode %d stamps (mean cycles, thread 0): weights=%.0f zero=%.0f input=%.0f conv1=%.0f mfma(wave0)=%.0f "
-                   "wait=%.0f fixup=%.0f conv4=%.0f total=%.0f\n", a.mode, sum[1] / nb, sum[2] / nb, sum[3] / nb, sum[4] / nb, sum[5] / nb,
-                   sum[6] / nb, sum[7] / nb, sum[8] / nb, (sum[1] + sum[2] + sum[3] + sum[4] + sum[5] + sum[6] + sum[7] + sum[8]) / nb);
-        }
-        a.stamps = nullptr;
-        return hipGetLastError();
-    }
+    const int nb = planes * a.nbands * std::max(a.nctiles, 1);
+#ifdef AFT_DIAG_STAMPS   // inference only: thread 0's cycles per phase of every workgroup of this launch (never in the product build)
+    StampRun run(SW_STAMPS, kStampConv, TRAIN ? 0 : nb, st);
+    a.stamps = run.buffer();
 #endif
-    hipLaunchKernelGGL((conv_stack_kernel<TRAIN, FIXED>), dim3(planes * a.nbands * std::max(a.nctiles, 1)), dim3(kConvThreads), lds, st, a);
-    return hipGetLastError();
+    hipLaunchKernelGGL((conv_stack_kernel<TRAIN, FIXED>), dim3(nb), dim3(kConvThreads), lds, st, a);
+    const hipError_t e = hipGetLastError();
+#ifdef AFT_DIAG_STAMPS
+    if (const unsigned long long *h = run.collect()) report_conv(stdout, h, nb, a.mode);
+    a.stamps = nullptr;
+#endif
+    return e;
 }
 
 // Training path: ConvEnhancer on plain planes.  Forward: w/b = the module's tensors, save = {c1, c2, c3},

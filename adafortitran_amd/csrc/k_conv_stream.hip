@@ -20,9 +20,7 @@
 // The head takes the upsampled planes from the forward's prologue launch (one product over all planes, up_w read once per launch
 // instead of 161 KB streamed through every CU's L1); callers without that scratch (the per-stage entry points) run the banded kernel.
 #include <cstdint>
-#include <cstdio>
 #include <cstdlib>
-#include <vector>
 
 #include "conv_device.h"
 
@@ -137,12 +135,9 @@ __global__ __launch_bounds__(kConvThreads) void conv_stream16_kernel(const ConvA
     const int inlo = max(ta - 4, 0), inhi = min(tb + 4, T);      // input columns fetched
     const int c3first = c2lo == 0 ? 0 : c2lo + 1;                // first conv3 column with all three kx taps inside the sweep (= ta - 1)
     const bool matrix = wave < 4;
-#ifdef AFT_DIAG_STAMPS
-#define SSTAMP(i) do { if (a.stamps && (tid == 0 || tid == 256)) a.stamps[(size_t)blockIdx.x * 16 + (tid ? 8 : 0) + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define SSTAMP(i) do { } while (0)
-#endif
-    SSTAMP(0);
+    // diagnostic build only (stamps.h): the first matrix wave's thread 0 in slots 0 .. 6, the first helper wave's (tid 256) in 8 .. 15
+    // diagnostic build only (stamps.h): the first matrix wave's thread 0 in slots 0 .. 6, the first helper wave's (tid 256) in 8 .. 15
+    AFT_STAMP(tid == 0 || tid == 256, a.stamps, blockIdx.x, (tid ? 8 : 0) + 0);
     // the kernel's first instructions are its global requests: the matrix waves' operand fragments, the helpers' input plane (one pixel
     // per thread and pass, coalesced; all 7 requests of a thread in flight together) -- the input's trip from the previous launch's
     // output (another XCD's L2 or the memory side) is the one latency nothing in this kernel can hide
@@ -185,7 +180,7 @@ __global__ __launch_bounds__(kConvThreads) void conv_stream16_kernel(const ConvA
     // a bare barrier behind the LDS stores: __syncthreads() would also wait for the global requests just issued (vmcnt(0)), i.e. every
     // wave would sit here until the slowest wave's data had arrived (2 000 cycles, stamps)
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    SSTAMP(1);
+    AFT_STAMP(tid == 0 || tid == 256, a.stamps, blockIdx.x, (tid ? 8 : 0) + 1);
     if (matrix) {   // behind the helpers' requests: 88 KB of fragments per workgroup would otherwise queue in front of the input plane
         __builtin_amdgcn_s_sleep(3);
         const f32x4 *fp = reinterpret_cast<const f32x4 *>(a.wfrag) + lane;
@@ -412,13 +407,13 @@ __global__ __launch_bounds__(kConvThreads) void conv_stream16_kernel(const ConvA
                 Y[pt][4] = acc[pt][4][2]; Y[pt][5] = acc[pt][4][3];
             }
         };
-        SSTAMP(2);
+        AFT_STAMP(tid == 0 || tid == 256, a.stamps, blockIdx.x, (tid ? 8 : 0) + 2);
         request_mask2(c2lo);
         request_mask3(c3first);
         need_c1(min(c2lo + 2, T));
 #pragma unroll
         for (int gi = 0; gi < 6; ++gi) load_b(gi >> 1, gi & 1, c2lo);
-        SSTAMP(3);
+        AFT_STAMP(tid == 0 || tid == 256, a.stamps, blockIdx.x, (tid ? 8 : 0) + 3);
         // prologue: conv2 of the first column (conv1's third column is only needed behind the first group: the sweeps start a column earlier)
 #pragma unroll
         for (int gi = 0; gi < 6; ++gi) {
@@ -527,10 +522,10 @@ __global__ __launch_bounds__(kConvThreads) void conv_stream16_kernel(const ConvA
             const int i = ht + 256 * u, gr = i / T, t = i - gr * T;
             if (i < S * T) in0[(t + 1) * SP + gr + 4] = vin[u];
         }
-        SSTAMP(7);    // (helper slot 7: the input plane has arrived and is in LDS)
+        AFT_STAMP(tid == 0 || tid == 256, a.stamps, blockIdx.x, (tid ? 8 : 0) + 7);    // (helper slot 7: the input plane has arrived and is in LDS)
         signal_count(4);
         wait_count(4, 4);
-        SSTAMP(2);
+        AFT_STAMP(tid == 0 || tid == 256, a.stamps, blockIdx.x, (tid ? 8 : 0) + 2);
         {   // conv1: 1 -> 8, ReLU, all T columns; the window slides by renaming (fully unrolled)
             const int lr = 32 * hw + j, gr = lr - 4;
             const bool ok = lr >= 1 && lr < LR - 1 && gr >= 0 && gr < S;
@@ -580,7 +575,7 @@ __global__ __launch_bounds__(kConvThreads) void conv_stream16_kernel(const ConvA
                 asm volatile("" ::: "memory");
             }
         }
-        SSTAMP(3);
+        AFT_STAMP(tid == 0 || tid == 256, a.stamps, blockIdx.x, (tid ? 8 : 0) + 3);
         // conv3's zero borders, then conv4 (8 -> 1) column by column behind the matrix waves
         for (int i = ht; i < 8 * 2 * SP; i += 256) {
             const int pl = i / (2 * SP), rem = i - pl * 2 * SP, col = rem < SP ? 0 : T + 1, row = rem & (SP - 1);
@@ -674,9 +669,9 @@ __global__ __launch_bounds__(kConvThreads) void conv_stream16_kernel(const ConvA
             if (h == 0 && okrow) obuf[(lr - 4) * T + t] = acc + b4;
         }
     }
-    SSTAMP(4);
+    AFT_STAMP(tid == 0 || tid == 256, a.stamps, blockIdx.x, (tid ? 8 : 0) + 4);
     __syncthreads();
-    SSTAMP(5);
+    AFT_STAMP(tid == 0 || tid == 256, a.stamps, blockIdx.x, (tid ? 8 : 0) + 5);
     // ---- the output plane leaves in one coalesced pass ----
     {
         const float *obuf = in0;
@@ -696,8 +691,7 @@ __global__ __launch_bounds__(kConvThreads) void conv_stream16_kernel(const ConvA
             for (int i = tid; i < S * T; i += kConvThreads) dstp[2 * i] = obuf[i];
         }
     }
-    SSTAMP(6);
-#undef SSTAMP
+    AFT_STAMP(tid == 0 || tid == 256, a.stamps, blockIdx.x, (tid ? 8 : 0) + 6);
 }
 
 // The fragment image of ONE ConvEnhancer for the training instantiation (the forward's prologue launch packs the inference images):
@@ -775,51 +769,28 @@ hipError_t launch_conv_stream(ConvArgs &a, int planes, hipStream_t st) {
     if (forced) { const int f = switch_int(SW_CONV_NSPLIT, 1); nsplit = f == 4 ? 4 : (f == 2 ? 2 : 1); }
     a.plane0 = 0;
     if (a.mode == 2) return launch_stream16(a, nsplit, planes, st);   // training: plain plane in / out, stage tensors saved, masked activation
-#ifdef AFT_DIAG_STAMPS
-    static unsigned long long *dbuf = nullptr;
-    const bool stamp = switch_on(SW_STAMPS) && planes <= 4096;
-    if (stamp) {
-        if (!dbuf) (void)hipMalloc(&dbuf, sizeof(unsigned long long) * 16 * 4096);
-        (void)hipMemset(dbuf, 0, sizeof(unsigned long long) * 16 * 4096);
-        a.stamps = dbuf;
-    }
-#endif
     // One plane per CU (the LDS): planes beyond a whole number of rounds would cost a full round for a few workgroups (258 planes
     // on 256 CUs: the 128 -> 129 frames step).  When that remainder fits the chip as column ranges it is a second launch of
     // ranges -- 0.42 (four ranges) or 0.62 (two) of a round instead of 1.0.  Same bits (ranges reproduce whole planes).
     const int rem = planes % cus, whole = planes - rem;
-    hipError_t e;
-    if (!forced && nsplit == 1 && whole > 0 && rem > 0 && 2 * rem <= cus) {
-        e = launch_stream16(a, 1, whole, st);
+    const bool two = !forced && nsplit == 1 && whole > 0 && rem > 0 && 2 * rem <= cus;
+    const int first = two ? whole : planes;
+#ifdef AFT_DIAG_STAMPS   // the first launch's workgroups (blockIdx.x restarts in the second); never in the product build
+    StampRun run(SW_STAMPS, kStampConvStream, (long long)first * nsplit, st);
+    ConvArgs stamped = a;
+    stamped.stamps = run.buffer();
+    const ConvArgs &a1 = stamped;
+#else
+    const ConvArgs &a1 = a;
+#endif
+    hipError_t e = launch_stream16(a1, nsplit, first, st);
+    if (two) {
         a.plane0 = whole;
         if (e == hipSuccess) e = launch_stream16(a, 4 * rem <= cus ? 4 : 2, rem, st);
         a.plane0 = 0;
-    } else {
-        e = launch_stream16(a, nsplit, planes, st);
     }
 #ifdef AFT_DIAG_STAMPS
-    if (stamp) {
-        (void)hipDeviceSynchronize();
-        static int printed = 0;
-        if (printed++ < 4) {
-            std::vector<unsigned long long> hb(16 * (size_t)planes);
-            (void)hipMemcpy(hb.data(), dbuf, hb.size() * 8, hipMemcpyDeviceToHost);
-            double m[7] = {0}, hsum[7] = {0};
-            for (int b = 0; b < planes; ++b)
-                for (int i = 1; i < 7; ++i) {
-                    m[i] += (double)(hb[(size_t)b * 16 + i] - hb[(size_t)b * 16 + i - 1]);
-                    hsum[i] += (double)(hb[(size_t)b * 16 + 8 + i] - hb[(size_t)b * 16 + 8 + i - 1]);
-                }
-            double in_lds = 0;
-            for (int b = 0; b < planes; ++b) in_lds += (double)(hb[(size_t)b * 16 + 15] - hb[(size_t)b * 16 + 8]);
-            printf("conv stream16: input plane in LDS %.0f cycles after the kernel's start (helper wave)\n", in_lds / planes);
-            printf("conv stream mode %d (mean cycles): matrix wave: stage=%.0f gather=%.0f wait=%.0f sweeps=%.0f wait=%.0f store=%.0f | "
-                   "helper wave: stage=%.0f zero+input+conv1=%.0f wait=%.0f conv4=%.0f wait=%.0f store=%.0f\n", a.mode, m[1] / planes,
-                   m[2] / planes, m[3] / planes, m[4] / planes, m[5] / planes, m[6] / planes, hsum[1] / planes, hsum[2] / planes,
-                   hsum[3] / planes, hsum[4] / planes, hsum[5] / planes, hsum[6] / planes);
-        }
-        a.stamps = nullptr;
-    }
+    if (const unsigned long long *h = run.collect()) report_conv_stream(stdout, h, first * nsplit, a.mode, nsplit, two ? 2 : 1);
 #endif
     return e;
 }

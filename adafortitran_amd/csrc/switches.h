@@ -21,7 +21,7 @@
     X(TRAIN_UNFUSED_BWD, "AFT_TRAIN_UNFUSED_BWD", "the launch sequence the fused backward chain of a training layer replaced") \
     X(TRAIN_ATTN_BWD_SPLIT, "AFT_TRAIN_ATTN_BWD_SPLIT", "the two-pass attention backward instead of the one-pass kernel") \
     X(ATTN_BWD_GROUPS, "AFT_ATTN_BWD_GROUPS", "1 | 4 problems per workgroup of the one-pass attention backward (default: by shape)") \
-    X(STAMPS, "AFT_STAMPS", "phase stamps printed on the host (diagnostic build, -DAFT_DIAG_STAMPS, only)") \
+    X(STAMPS, "AFT_STAMPS", "phase stamps printed on the host: the diag variant only (libaft_hip_diag.so, build.build_diag(): -DAFT_DIAG_STAMPS)") \
     X(ALLOW_COMPOSITE, "AFT_ALLOW_COMPOSITE", "1 = run a configuration the kernels do not cover on the PyTorch-ROCm composite") \
     X(TRAIN_NO_FUSED_ENDS, "AFT_TRAIN_NO_FUSED_ENDS", "training: PyTorch's unfold / cat / add around the dense ends, not fused") \
     X(TRAIN_NO_QKV_CHAIN, "AFT_TRAIN_NO_QKV_CHAIN", "training: every layer runs its own in-projection GEMM (no chained tapes)") \

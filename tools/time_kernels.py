@@ -1,5 +1,8 @@
 #!/usr/bin/env python3
-"""Quick per-kernel timing on the GPU box (events on the launch stream)."""
+"""Quick per-kernel timing on the GPU box (events on the launch stream).
+
+In-kernel phase stamps: python -m adafortitran_amd.build --diag, then
+AFT_LIB_PATH=adafortitran_amd/csrc/libaft_hip_diag.so AFT_STAMPS=1 tools/time_kernels.py chain"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -22,7 +25,7 @@ dev = lambda a: torch.from_numpy(a).to("cuda:0")
 pil, meta = dev(inp["pilots"]), [dev(inp[k]) for k in ("snr", "ds", "dop")]
 out = torch.empty((B, *SPEC["ofdm"]), dtype=torch.complex64, device="cuda:0")
 from adafortitran_amd import _lib
-stamps = _lib.get_switch("AFT_STAMPS")   # only meaningful with a --diag build; off for the first forward
+stamps = _lib.get_switch("AFT_STAMPS")   # only meaningful with the diag variant (above); off for the first forward
 _lib.set_switch("AFT_STAMPS", None)
 eng.forward(pil, *meta, out=out); torch.cuda.synchronize()
 if stamps: _lib.set_switch("AFT_STAMPS", stamps)
