@@ -147,4 +147,59 @@ int aft_link_soft_f32(const aft_link *link, const float *ideal, const float *est
     return e == hipSuccess ? AFT_OK : hip_fail("link_soft", e);
 }
 
+int aft_link_decode_f32(const aft_link *link, const float *llr, const unsigned long long *keys, int info_bits, int rate,
+                        unsigned long long stride, unsigned long long stride_inverse, float qgain, int32_t *counts,
+                        unsigned char *bits, int batch, void *stream) {
+    const char *who = "link decode";
+    AFT_REQUIRE(link && llr && keys && counts, "link decode: NULL pointer argument");
+    AFT_REQUIRE(aligned(8, keys), "link decode: keys must be 8-byte aligned");
+    AFT_REQUIRE(aligned(4, llr, counts), "link decode: llr and counts must be 4-byte aligned");
+    AFT_REQUIRE(batch >= 1, "link decode: batch must be at least 1 (got %d)", batch);
+    AFT_REQUIRE(std::isfinite(qgain) && qgain > 0.f, "link decode: qgain = %g must be finite and positive", (double)qgain);
+    const int rc = check_link(who, *link);
+    if (rc != AFT_OK) return rc;
+    if (!within(who, "info_bits", info_bits, 1, AFT_LINK_CODE_MAX_INFO_BITS)) return AFT_ERR_SHAPE;
+    if (rate != AFT_LINK_RATE_1_2 && rate != AFT_LINK_RATE_2_3 && rate != AFT_LINK_RATE_3_4) {
+        set_error("%s: rate = %d is not one of AFT_LINK_RATE_1_2, _2_3, _3_4", who, rate);
+        return AFT_ERR_SHAPE;
+    }
+    // kept outputs of the K + 6 steps: A0 B0 | A0 B0 A1 | A0 B0 A1 B2 per period of 1, 2, 3 steps
+    const unsigned long long steps = (unsigned long long)info_bits + 6;
+    const unsigned long long coded = rate == AFT_LINK_RATE_1_2   ? 2 * steps
+                                     : rate == AFT_LINK_RATE_2_3 ? 3 * (steps / 2) + 2 * (steps % 2)
+                                                                 : 4 * (steps / 3) + (steps % 3 == 0 ? 0 : steps % 3 + 1);
+    const unsigned long long carried = (unsigned long long)link->bits_per_symbol *
+        ((unsigned long long)link->num_scs * link->num_symbols - (unsigned long long)link->pilot_scs * link->pilot_symbols);
+    const unsigned long long blocks = carried / coded, used = blocks * coded;
+    if (blocks == 0) {
+        set_error("%s: a frame carries %llu bits, fewer than the %llu coded bits of one block", who, carried, coded);
+        return AFT_ERR_SHAPE;
+    }
+    if (blocks * (unsigned long long)info_bits > (1ull << 31)) {
+        set_error("%s: %llu blocks of %d information bits: more than 2^31, where the hash's index and the int32 counts end", who, blocks,
+                  info_bits);
+        return AFT_ERR_SHAPE;
+    }
+    if (stride < 1 || stride >= used) {                         // used >= 10: no block has fewer coded bits
+        set_error("%s: stride = %llu is outside [1, %llu)", who, stride, used);
+        return AFT_ERR_SHAPE;
+    }
+    unsigned long long g = stride, r = used;
+    while (r != 0) {
+        const unsigned long long next = g % r;
+        g = r; r = next;
+    }
+    if (g != 1) {
+        set_error("%s: stride = %llu is not coprime to the %llu used bits", who, stride, used);
+        return AFT_ERR_SHAPE;
+    }
+    if (stride_inverse < 1 || stride_inverse >= used || (unsigned long long)((unsigned __int128)stride * stride_inverse % used) != 1) {
+        set_error("%s: stride_inverse = %llu is not the inverse of stride = %llu modulo %llu", who, stride_inverse, stride, used);
+        return AFT_ERR_SHAPE;
+    }
+    hipError_t e = launch_link_decode(*link, llr, keys, info_bits, rate, (unsigned)coded, (unsigned)blocks, stride, qgain,
+                                      counts, bits, batch, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? AFT_OK : hip_fail("link_decode", e);
+}
+
 }  // extern "C"

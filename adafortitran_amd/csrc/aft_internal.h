@@ -371,6 +371,12 @@ hipError_t launch_link_errors(const aft_link &link, const float *ideal, const fl
 hipError_t launch_link_soft(const aft_link &link, const float *ideal, const float *est, const unsigned long long *keys,
                             const float *sigma, const float *scale, const float *factors, int n_factors, float *loss, float *llr,
                             int batch, hipStream_t st);
+// the coded link's Viterbi decoder (k_linkcode.hip): everything has passed aft_link_decode_f32's checks; coded_bits = n and blocks = B
+// of the definition; bits may be NULL.  link_code_waves: the code blocks a workgroup decodes at once (its survivor words fill LDS)
+int link_code_waves(unsigned steps, unsigned blocks);
+hipError_t launch_link_decode(const aft_link &link, const float *llr, const unsigned long long *keys, int info_bits, int rate,
+                              unsigned coded_bits, unsigned blocks, unsigned long long stride, float qgain, int32_t *counts,
+                              unsigned char *bits, int batch, hipStream_t st);
 hipError_t launch_mse(const float *est, const float *ref, double *sum_sq, long long n_complex, hipStream_t st);
 hipError_t launch_fill_lds(float value, hipStream_t st);   // test hook: every CU's LDS filled with `value`
 hipError_t launch_peek_lds(float *out, int workgroups, int n, hipStream_t st);   // ... and what a kernel finds in its LDS at start

@@ -59,9 +59,44 @@ What a float32 evaluation of the LLRs is compared through: ``q = scale A (A p + 
 relative ``e`` of that errs in ``Lambda_j`` by about ``2 e q``.  The loss is monotone in every ``Lambda_j``, so the losses at
 ``Lambda -+ e_lambda q`` (each bit moved towards, or away from, the sent bit) are an exact interval for every evaluation whose LLRs
 are within ``e_lambda q``.
+
+The coded link.  The rate says how much information the LLRs carry; a link-level user wants the same with a decoder in the loop: the
+block-error rate of coded blocks and the throughput that follows from it.  ``CodeConfig``, ``link_encode_host`` / ``link_decode_host``
+(integer NumPy), ``aft_link_decode_f32`` (csrc/k_linkcode.hip, through ``hip_ops.LinkDecodePlan``), ``BlockErrorAccumulator`` and
+``evaluation.get_link_bler`` are to it what the names above are to the bit errors.  The link is unchanged -- a frame still sends the
+words ``w`` of stream 5 -- and the code rides on it through a scrambler both ends know::
+
+    code         rate 1/2, constraint length 7, zero-terminated.  Inputs u_0 .. u_{K-1}; u_t = 0 for t < 0 and K <= t < K + 6.
+                 For t = 0 .. K + 5:   A_t = u_t ^ u_{t-2} ^ u_{t-3} ^ u_{t-5} ^ u_{t-6}       (133 octal)
+                                       B_t = u_t ^ u_{t-1} ^ u_{t-2} ^ u_{t-3} ^ u_{t-6}       (171 octal)
+                 u = 1,0,0,0,0,0,0 gives A = 1,0,1,1,0,1,1 and B = 1,1,1,1,0,0,1: weight 10
+    puncturing   by t mod P, the 802.11 patterns: rate 1/2 (P = 1) keeps A B; 2/3 (P = 2) keeps A0 B0 A1; 3/4 (P = 3) keeps A0 B0 A1 B2.
+                 The kept bits in step-major order, A before B, are the n coded bits of a block
+                 (K = 512: n = 1036 at rate 1/2 and 691 at 3/4; K = 1024: n = 1374 at 3/4)
+    blocks       N = m data_elements bits per frame, B = N // n blocks (B = 0 is refused), U = B n used bits.  Data-bit index j is
+                 bit k = j % m -- the last axis of the LLR tensor, bit (w >> (m-1-k)) & 1 of the sent word -- of the (j // m)-th grid
+                 element that is no pilot, in row-major order.  Bits j >= U are filler: sent as the link sends them, ignored by the
+                 decoder.  LLRs at pilot positions are never read
+    interleaver  coded bit i of block b, p = b n + i, sits at j = (p A) mod U with gcd(A, U) = 1.  The default stride A is the smallest
+                 integer >= max(1, floor(0.3819660112501051 U)) coprime to U (a golden-section stride); U >= 10, so 1 <= A < U
+    information  u[b][t] = word(kf, stream 8, b K + t) >> 63            (B K <= 2^31: the hash's index is 32 bits, the counts are int32)
+    input        scrambler s_p = w_j ^ c_p with c_p the coded bit;  lambda_p = (1 - 2 s_p) llr_j;
+                 z_p = clamp(rint(float32(lambda_p qgain)), -127, 127): ONE float32 product, to nearest with ties to even, NaN gives 0
+                 (qgain = 8: steps of 1/8, clipped at +-15.875)
+    Viterbi      state sigma = sum_{i=1..6} u_{t-i} 2^(6-i), successor (sigma >> 1) | (u_t << 5).  int32 metrics, M[0] = 0 and
+                 -2^30 elsewhere.  A branch gains the sum over its kept outputs of (1 - 2 out) z; a punctured output gives nothing.
+                 State n has predecessors r0 = (n & 31) << 1 and r1 = r0 | 1 with input n >> 5; the survivor is the larger sum and A
+                 TIE TAKES r0: the decision bit is 1 only when r1 is strictly larger.  Traceback from state 0 after K + 6 steps:
+                 u^_t = n >> 5, previous state ((n & 31) << 1) | decision.  K <= 4090: 4096 steps of at most 254 each overflow nothing
+    result       (information-bit errors over the B K bits, blocks with any error) per frame
+
+Everything after the quantiser is integer, so the host and the device agree bit for bit on the same float32 LLRs: no tolerance.  The
+path a tie-breaking Viterbi returns is, of all paths of the largest metric, the one whose inputs read from the last to the first are
+smallest (each merge prefers the older input 0), which is what tests/test_linkcode.py's brute force over all 2^K inputs compares.
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass, field
 from typing import Optional, Tuple, Union
 
@@ -69,7 +104,8 @@ import numpy as np
 import torch
 
 from . import _abi
-from .chansim import STREAM_DATA_BITS, STREAM_DATA_NOISE_ANGLE, STREAM_DATA_NOISE_RADIUS, ChannelSimConfig, frame_keys, words
+from .chansim import (STREAM_CODE_BITS, STREAM_DATA_BITS, STREAM_DATA_NOISE_ANGLE, STREAM_DATA_NOISE_RADIUS, ChannelSimConfig, frame_keys,
+                      words)
 from .synth import _splitmix64
 
 BITS_PER_SYMBOL = (2, 4, 6, 8)
@@ -357,12 +393,14 @@ class _FrameSweep:
         H = ideal.to(dev).contiguous()
         return b, H, (H if est is None else est.to(dev).contiguous()), keys_t, per_frame_t
 
-    def _launch(self, *args, **kw):
-        """The plan on the accumulator's device: the launch belongs to it, whichever device is current."""
+    def _launch(self, *args, plan=None, **kw):
+        """The plan (``self._plan`` unless another is given) on the accumulator's device: the launch belongs to it, whichever device
+        is current."""
+        plan = self._plan if plan is None else plan
         if torch.cuda.current_device() != self.device.index:
             with torch.cuda.device(self.device):
-                return self._plan(*args, **kw)
-        return self._plan(*args, **kw)
+                return plan(*args, **kw)
+        return plan(*args, **kw)
 
     @staticmethod
     def _all_ranks(local: torch.Tensor, group) -> list:
@@ -466,3 +504,267 @@ class RateAccumulator(_FrameSweep):
     def result_gmi(self, group=None) -> float:
         """The best rate of the factor grid: the GMI's supremum over the LLR scale, taken on the grid."""
         return max(self.result(group))
+
+
+# ---- the coded link (module docstring, "the coded link"): integer NumPy, mirrored by csrc/k_linkcode.hip ----
+
+CODE_TAIL = 6                                               # constraint length 7
+MAX_INFO_BITS = _abi.AFT_LINK_CODE_MAX_INFO_BITS
+GOLDEN_STRIDE = 0.3819660112501051                          # 2 - the golden ratio
+#: rate -> (the library's constant, which of (A, B) each step of the period keeps)
+RATES = {"1/2": (_abi.AFT_LINK_RATE_1_2, ((1, 1),)),
+         "2/3": (_abi.AFT_LINK_RATE_2_3, ((1, 1), (1, 0))),
+         "3/4": (_abi.AFT_LINK_RATE_3_4, ((1, 1), (1, 0), (0, 1)))}
+_GEN_A, _GEN_B = 0o133, 0o171                                # on the window u_t .. u_{t-6}, u_t the top bit
+_PARITY = np.array([bin(i).count("1") & 1 for i in range(128)], dtype=np.int32)
+
+
+def keep_mask(info_bits: int, rate: str) -> np.ndarray:
+    """bool ``[K + 6, 2]``: which of (A_t, B_t) the puncturing keeps."""
+    pattern = np.array(RATES[rate][1], dtype=bool)
+    return pattern[np.arange(int(info_bits) + CODE_TAIL) % len(pattern)]
+
+
+def coded_bits(info_bits: int, rate: str) -> int:
+    """``n``: the kept outputs of the ``K + 6`` steps of a block."""
+    return int(keep_mask(info_bits, rate).sum())
+
+
+def default_stride(used_bits: int) -> int:
+    """The smallest integer at least ``max(1, floor(0.3819660112501051 U))`` that is coprime to ``U``."""
+    a = max(1, int(math.floor(GOLDEN_STRIDE * used_bits)))
+    while math.gcd(a, used_bits) != 1:
+        a += 1
+    return a
+
+
+def conv_encode(u, rate: str = "1/2") -> np.ndarray:
+    """The zero-terminated, punctured codewords uint8 ``[..., n]`` of the inputs ``u`` ``[..., K]`` (0 / 1)."""
+    u = np.asarray(u).astype(np.uint8)
+    K = u.shape[-1]
+    pad = np.zeros((*u.shape[:-1], CODE_TAIL), dtype=np.uint8)
+    x = np.concatenate([pad, u, pad], axis=-1)               # x[t + 6 - i] = u_{t-i}
+    d = lambda i: x[..., CODE_TAIL - i:CODE_TAIL - i + K + CODE_TAIL]  # noqa: E731
+    a = d(0) ^ d(2) ^ d(3) ^ d(5) ^ d(6)
+    b = d(0) ^ d(1) ^ d(2) ^ d(3) ^ d(6)
+    return np.stack([a, b], axis=-1)[..., keep_mask(K, rate)]
+
+
+@dataclass(frozen=True)
+class CodeConfig:
+    """A convolutional code on a link: ``info_bits`` = K per block, ``rate`` one of ``RATES``, the interleaver's ``stride`` (None: the
+    golden-section default) and the quantiser's gain.  Derives ``coded_bits`` n, ``blocks`` B, ``used_bits`` U, ``stride_inverse`` and
+    ``info_bits_per_frame``; refuses what ``aft_link_decode_f32`` refuses."""
+    link: LinkConfig = field(default_factory=LinkConfig)
+    info_bits: int = 1024
+    rate: str = "1/2"
+    stride: Optional[int] = None
+    qgain: float = 8.0
+
+    def __post_init__(self) -> None:
+        if not isinstance(self.link, LinkConfig):
+            raise ValueError(f"CodeConfig needs a LinkConfig (got {type(self.link).__name__})")
+        K = self.info_bits
+        if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= int(K) <= MAX_INFO_BITS:
+            raise ValueError(f"info_bits = {K!r}: an integer in 1 .. {MAX_INFO_BITS}")
+        object.__setattr__(self, "info_bits", int(K))
+        if self.rate not in RATES:
+            raise ValueError(f"rate = {self.rate!r}: one of {tuple(RATES)}")
+        if self.blocks == 0:
+            raise ValueError(f"a frame carries {self.link.bits_per_frame} bits, fewer than the {self.coded_bits} coded bits of one block")
+        if self.info_bits_per_frame > 1 << 31:
+            raise ValueError(f"{self.blocks} blocks of {self.info_bits} information bits: more than 2^31, where the hash's index and the "
+                             f"int32 counts end")
+        U = self.used_bits
+        a = default_stride(U) if self.stride is None else self.stride
+        if isinstance(a, bool) or not isinstance(a, (int, np.integer)) or not 1 <= int(a) < U:
+            raise ValueError(f"stride = {a!r}: an integer in [1, {U})")
+        if math.gcd(int(a), U) != 1:
+            raise ValueError(f"stride = {a} is not coprime to the {U} used bits")
+        object.__setattr__(self, "stride", int(a))
+        with np.errstate(over="ignore", under="ignore"):
+            g = np.float32(self.qgain)
+        if not (np.isfinite(g) and g > 0):
+            raise ValueError(f"qgain = {self.qgain!r}: a finite positive float32")
+        object.__setattr__(self, "qgain", float(g))
+
+    @property
+    def rate_code(self) -> int:
+        return RATES[self.rate][0]
+
+    @property
+    def steps(self) -> int:
+        return self.info_bits + CODE_TAIL
+
+    @property
+    def coded_bits(self) -> int:
+        return coded_bits(self.info_bits, self.rate)
+
+    @property
+    def blocks(self) -> int:
+        return self.link.bits_per_frame // self.coded_bits
+
+    @property
+    def used_bits(self) -> int:
+        return self.blocks * self.coded_bits
+
+    @property
+    def stride_inverse(self) -> int:
+        return pow(self.stride, -1, self.used_bits)
+
+    @property
+    def info_bits_per_frame(self) -> int:
+        return self.blocks * self.info_bits
+
+    def positions(self) -> np.ndarray:
+        """int64 ``[B, n]``: the data-bit index ``j = (p stride) mod U`` of coded bit ``i`` of block ``b``, ``p = b n + i``."""
+        U, p = self.used_bits, np.arange(self.used_bits, dtype=np.int64)
+        if U <= 1 << 31:
+            j = (p * np.int64(self.stride)) % np.int64(U)
+        else:
+            j = np.array([(int(v) * self.stride) % U for v in p], dtype=np.int64)
+        return j.reshape(self.blocks, self.coded_bits)
+
+
+def _keys64(keys) -> np.ndarray:
+    keys = np.ascontiguousarray(keys)
+    if keys.dtype == np.int64:
+        keys = keys.view(np.uint64)
+    if keys.dtype != np.uint64 or keys.ndim != 1:
+        raise ValueError("keys must be a vector of 64-bit words (uint64, or int64 taken bit for bit)")
+    return keys
+
+
+def link_encode_host(code: CodeConfig, keys) -> Tuple[np.ndarray, np.ndarray]:
+    """The information bits uint8 ``[n, B, K]`` and the codewords uint8 ``[n, B, coded_bits]`` of the frames with ``keys``."""
+    keys = _keys64(keys)
+    B, K = code.blocks, code.info_bits
+    index = np.arange(B * K, dtype=np.uint64).reshape(1, B, K)
+    info = (words(keys[:, None, None], STREAM_CODE_BITS, index) >> np.uint64(63)).astype(np.uint8)
+    return info, conv_encode(info, code.rate)
+
+
+def quantise(lam, qgain: float) -> np.ndarray:
+    """``clamp(rint(float32(lam qgain)), -127, 127)`` as int32: one float32 product, ties to even, NaN gives 0."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        v = np.asarray(lam, dtype=np.float32) * np.float32(qgain)
+        z = np.clip(np.rint(v), -127.0, 127.0)
+    return np.where(np.isnan(v), np.float32(0), z).astype(np.int32)
+
+
+def viterbi_host(z: np.ndarray) -> np.ndarray:
+    """The decoder of the definition on depunctured int32 inputs ``z [..., steps, 2]`` (0 where punctured): the inputs uint8
+    ``[..., steps]`` on the surviving path to state 0 (the last six are the tail's zeros)."""
+    z = np.asarray(z, dtype=np.int32)
+    lead, steps = z.shape[:-2], z.shape[-2]
+    z = z.reshape(-1, steps, 2)
+    R = z.shape[0]
+    n = np.arange(64)
+    pred = np.stack([(n & 31) << 1, ((n & 31) << 1) | 1])                       # [2, 64]
+    window = ((n >> 5) << 6) | pred                                            # u_t on top of the predecessor's six bits
+    sa, sb = 1 - 2 * _PARITY[window & _GEN_A], 1 - 2 * _PARITY[window & _GEN_B]   # [2, 64] of +-1
+    metric = np.full((R, 64), -(1 << 30), dtype=np.int32)
+    metric[:, 0] = 0
+    decision = np.zeros((R, steps, 64), dtype=bool)
+    for t in range(steps):
+        za, zb = z[:, t, 0, None], z[:, t, 1, None]
+        m0 = metric[:, pred[0]] + sa[0] * za + sb[0] * zb
+        m1 = metric[:, pred[1]] + sa[1] * za + sb[1] * zb
+        decision[:, t] = m1 > m0                                               # a tie takes r0
+        metric = np.where(decision[:, t], m1, m0).astype(np.int32)
+    state = np.zeros(R, dtype=np.int64)
+    out = np.zeros((R, steps), dtype=np.uint8)
+    rows = np.arange(R)
+    for t in range(steps - 1, -1, -1):
+        out[:, t] = state >> 5
+        state = ((state & 31) << 1) | decision[rows, t, state]
+    return out.reshape(*lead, steps)
+
+
+def link_decode_host(code: CodeConfig, keys, llr) -> Tuple[np.ndarray, np.ndarray]:
+    """The coded link's definition on ``llr`` ``[n, S, T, m]``, taken as the float32 numbers it rounds to: ``(counts int64 [n, 2] =
+    (information-bit errors, blocks with any error) per frame, bits uint8 [n, B, K] the decoded information bits)``.  Needs no library."""
+    keys = _keys64(keys)
+    cfg = code.link
+    (S, T), m, nf = cfg.sim.ofdm, cfg.bits_per_symbol, len(keys)
+    llr = np.asarray(llr)
+    if llr.shape != (nf, S, T, m):
+        raise ValueError(f"Expected llr of shape ({nf}, {S}, {T}, {m}), got {llr.shape}")
+    llr = llr.astype(np.float32).reshape(nf, S * T, m)
+    info, sent = link_encode_host(code, keys)
+    j = code.positions()                                                       # [B, n]
+    q, k = np.flatnonzero(cfg.data_mask)[j // m], j % m                        # the grid element and the bit of its word
+    w = (words(keys[:, None, None], STREAM_DATA_BITS, q[None].astype(np.uint64)) >> (np.uint64(63) - k[None].astype(np.uint64))) & np.uint64(1)
+    scrambler = w.astype(np.uint8) ^ sent
+    at = llr[:, q, k]                                                          # [n, B, coded_bits]
+    z = quantise(np.where(scrambler == 1, -at, at), code.qgain)
+    full = np.zeros((nf, code.blocks, code.steps, 2), dtype=np.int32)
+    full[..., keep_mask(code.info_bits, code.rate)] = z
+    bits = viterbi_host(full)[..., :code.info_bits]
+    wrong = bits != info
+    counts = np.stack([wrong.sum(axis=(1, 2)), wrong.any(axis=2).sum(axis=1)], axis=1).astype(np.int64)
+    return counts, bits
+
+
+_SCALE_OF_SNR = lambda err_var: (lambda snr: llr_scale(snr, err_var), lambda snr: 1.0 / (torch.pow(10.0, -snr / 10.0) + err_var))  # noqa: E731
+
+
+class BlockErrorAccumulator(_FrameSweep):
+    """Block errors of a sweep with a decoder in the loop (module docstring, "the coded link"), with ``LinkAccumulator``'s ``update``
+    surface.  The LLRs are the soft link's at factor 1 with the scale ``llr_scale(snr_db, err_var)``.  On a HIP device a batch is the
+    launch of ``aft_link_soft_f32`` with its LLR output, the launch of ``aft_link_decode_f32`` on that tensor, and one integer add into
+    an int64 ``[2]`` device tensor; nothing synchronises.  On a CPU device the host definitions run (float64 LLRs rounded to float32).
+    ``result`` is the block-error rate, ``result_ber`` the information-bit error rate, ``result_throughput`` the delivered information
+    bits per data element; each is one read and, with several ranks, one all-gather of three float64."""
+
+    def __init__(self, code: CodeConfig, device, seed: int = 0, err_var: float = 0.0) -> None:
+        if not isinstance(code, CodeConfig):
+            raise ValueError(f"BlockErrorAccumulator needs a CodeConfig (got {type(code).__name__})")
+        self._open(code.link, device, seed, "LinkSoftPlan")
+        self.code = code
+        self.err_var = float(err_var)
+        if not self.err_var >= 0.0:
+            raise ValueError(f"err_var = {err_var!r}: a variance, at least 0")
+        self.errors = torch.zeros(2, dtype=torch.int64, device=self.device)     # information-bit errors, block errors
+        self._decode = self._one = None
+        if self._plan is not None:
+            from . import hip_ops
+            self._decode = hip_ops.LinkDecodePlan(code, self.device)
+            self._one = torch.ones(1, dtype=torch.float32, device=self.device)
+        self._of_snr = (_SIGMA_OF_SNR, _SCALE_OF_SNR(self.err_var))
+
+    def update(self, est: Optional[torch.Tensor], ideal: torch.Tensor, meta: Optional[tuple] = None, *, frame_ids=None,
+               snr_db=None) -> None:
+        ops = self._operands(est, ideal, meta, frame_ids, snr_db, self._of_snr)
+        if ops is None:
+            return
+        b, H, E, keys, (sigma, scale) = ops
+        if self._plan is None:
+            llr = link_llrs_host(self.cfg, keys, H, E, sigma, scale)[1]
+            self.errors += torch.from_numpy(link_decode_host(self.code, keys, llr)[0].sum(axis=0))
+        else:
+            llr = self._launch(H, E, keys, sigma, scale, self._one, want_llr=True)[1]
+            self.errors += self._launch(llr, keys, plan=self._decode)[0].sum(dim=0, dtype=torch.int64)
+        self.frames += b
+
+    def _read(self, group) -> Tuple[float, float, float]:
+        frames = torch.tensor([float(self.frames)], dtype=torch.float64, device=self.device)
+        bit_errors, block_errors, frames = self._all_ranks(torch.cat([self.errors.to(torch.float64), frames]), group)
+        return bit_errors, block_errors, frames
+
+    def result(self, group: Optional["torch.distributed.ProcessGroup"] = None) -> float:
+        """Global block-error rate over all ranks (integers summed: identical on every rank); 0.0 for an empty sweep."""
+        _, block_errors, frames = self._read(group)
+        return block_errors / (frames * self.code.blocks) if frames > 0 else 0.0
+
+    def result_ber(self, group=None) -> float:
+        """Global information-bit error rate after decoding."""
+        bit_errors, _, frames = self._read(group)
+        return bit_errors / (frames * self.code.info_bits_per_frame) if frames > 0 else 0.0
+
+    def result_throughput(self, group=None) -> float:
+        """Information bits of the blocks decoded without error, per data element sent."""
+        _, block_errors, frames = self._read(group)
+        if frames <= 0:
+            return 0.0
+        return (frames * self.code.blocks - block_errors) * self.code.info_bits / (frames * self.cfg.data_elements)

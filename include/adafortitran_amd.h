@@ -408,6 +408,47 @@ int aft_link_soft_f32(const aft_link *link, const float *ideal, const float *est
                       const float *sigma, const float *scale, const float *factors, int n_factors,
                       float *loss /* [batch][n_factors] */, float *llr /* [batch,S,T,m] or NULL */, int batch, void *stream);
 
+/* ---- coded link: a convolutional code and a Viterbi decoder on those LLRs (adafortitran_amd/linksim.py holds the definition) ----
+ *
+ * The link is unchanged: a frame still sends the words w of stream 5.  The code rides on it through a scrambler both ends know.
+ *   code        rate 1/2, constraint length 7, zero-terminated: for inputs u_0 .. u_{K-1} (u_t = 0 for t < 0 and K <= t < K + 6) and
+ *               t = 0 .. K + 5:  A_t = u_t ^ u_{t-2} ^ u_{t-3} ^ u_{t-5} ^ u_{t-6} (133 octal),
+ *               B_t = u_t ^ u_{t-1} ^ u_{t-2} ^ u_{t-3} ^ u_{t-6} (171 octal)
+ *   puncturing  by t mod P, the 802.11 patterns: rate 1/2 (P = 1) keeps A B, 2/3 (P = 2) keeps A0 B0 A1, 3/4 (P = 3) keeps A0 B0 A1 B2;
+ *               the kept bits step-major, A before B, are the n coded bits of a block
+ *   blocks      N = m (S T - Ps Pt) bits per frame, B = N / n blocks (integer division), U = B n used bits.  Data-bit index j is bit
+ *               k = j % m (the last axis of llr; bit (w >> (m-1-k)) & 1 of the sent word) of the (j / m)-th grid element that is no
+ *               pilot, in row-major order.  Bits j >= U are filler the decoder ignores; LLRs at pilot positions are never read
+ *   interleaver coded bit i of block b, p = b n + i, sits at j = p stride mod U, gcd(stride, U) = 1
+ *   information u[b][t] = word(8, b K + t) >> 63: stream 8 of the frame's hash
+ *   input       scrambler s_p = w_j ^ c_p (c_p the coded bit); lambda_p = (1 - 2 s_p) llr_j;
+ *               z_p = clamp(rint(float32(lambda_p qgain)), -127, 127): one float32 product, to nearest with ties to even, NaN gives 0
+ *   Viterbi     state sigma = sum_{i=1..6} u_{t-i} 2^(6-i), successor (sigma >> 1) | (u_t << 5); int32 metrics, M[0] = 0 and -2^30
+ *               elsewhere; a branch gains the sum over its kept outputs of (1 - 2 out) z.  State n has predecessors
+ *               r0 = (n & 31) << 1 and r1 = r0 | 1 with input n >> 5; the survivor is the larger sum and A TIE TAKES r0 (the decision
+ *               bit is 1 only when r1 is strictly larger).  Traceback from state 0 after K + 6 steps: u^_t = n >> 5, previous state
+ *               ((n & 31) << 1) | decision
+ *   counts      (information-bit errors over the B K bits, blocks with any error) per frame
+ * Everything after the quantiser is integer: a host evaluation of this definition agrees bit for bit. */
+#define AFT_LINK_RATE_1_2 0
+#define AFT_LINK_RATE_2_3 1
+#define AFT_LINK_RATE_3_4 2
+#define AFT_LINK_CODE_MAX_INFO_BITS 4090   /* 4096 trellis steps: a block's survivor words are 32 KiB, no metric can overflow */
+
+/* One launch, one workgroup per frame, one wave per code block and one lane per trellis state: counts int32 [batch][2] = (bit errors,
+ * block errors) of each frame and, when bits is not NULL, the decoded information bits uint8 [batch, B, K] (both device memory) from
+ * llr float32 [batch, S, T, m] (device memory; what aft_link_soft_f32 writes) and keys uint64 [batch] (any device-addressable memory,
+ * pinned host memory included).  `link` is read during the call only and travels to the kernel by value.  Every element of counts and
+ * bits is written (no initialisation needed); no atomics; no workspace; nothing is synchronised; a frame's outputs depend neither on
+ * batch, nor on its position in it, nor on the run, nor on whether bits is written.
+ * Nothing is launched on AFT_ERR_ARG (a NULL link / llr / keys / counts; keys not 8-byte or llr / counts not 4-byte aligned; batch < 1;
+ * qgain not finite and positive) and AFT_ERR_SHAPE (what aft_link_errors_f32 refuses; info_bits outside 1 ..
+ * AFT_LINK_CODE_MAX_INFO_BITS; a rate that is none of the three; B = 0; B K above 2^31, where the hash's index and the int32 counts end; a stride outside
+ * [1, U) -- U is at least 10 -- or not coprime to U; a stride_inverse outside [1, U) or with stride stride_inverse mod U != 1). */
+int aft_link_decode_f32(const aft_link *link, const float *llr /* [batch,S,T,m] */, const unsigned long long *keys, int info_bits,
+                        int rate /* AFT_LINK_RATE_* */, unsigned long long stride, unsigned long long stride_inverse, float qgain,
+                        int32_t *counts /* [batch][2] */, unsigned char *bits /* [batch,B,K] or NULL */, int batch, void *stream);
+
 /* ---- training path of the encoder ---- */
 
 /* Gradients of one nn.TransformerEncoderLayer: same fields and shapes as aft_layer_weights,
