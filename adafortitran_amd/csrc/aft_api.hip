@@ -420,6 +420,22 @@ static void release_lane_streams(LaneStreams *ls) {
         if (&en.ls == ls) { --en.in_use; return; }
 }
 
+// ---- the fold (chain_device.h, k_misc.hip) ----
+// In a whole forward the first encoder launch forms layer 0's K and V from the row's K input features instead of a model_dim-deep
+// product over x0.  Selected by the configuration alone -- the packed engine in fp32 (the split tier keeps the deep product: its K / V
+// leave as bf16 pairs of an x0 that was split first) -- never by batch, lanes or workspace; AFT_L0_FOLD=0 is the A/B lever.
+// Its operands live in regions of the lane's planned slice that are idle from the prologue until the first encoder launch ends:
+// the tables in `attn` (>= 2 x tokpad x model_dim floats at every batch; first written by attention 0, or as the second K buffer by
+// layer 0's launch), the folded matrices in the packed image's slot of layer 0's K / V fragments (the prologue does not pack those
+// then; with a caller-owned image the lane's own wpack is idle altogether).
+static bool l0_fold_selected(const aft_config &c) {
+    return packed_engine_ok(c) && c.precision == AFT_PRECISION_F32 && switch_int(SW_L0_FOLD, 1) != 0;
+}
+static L0Fold l0_fold_at(const aft_config &c, const Workspace &ws, float *base) {
+    float *tables = base + ws.attn;
+    return L0Fold{tables, tables + (size_t)ws.tokpad * c.model_dim, base + ws.wpack + (size_t)c.model_dim * c.model_dim};
+}
+
 // What the whole forward fuses into the chain launch at `pos` of the encoder: the first one (QKV only) computes x0 from conv_enhanced /
 // tokens6 itself (no embed kernel), the last one writes linear_2's output to out6 instead of storing x (the conv tail reads it there);
 // nobody but these launches reads x, so it crosses HBM in tile-blocked order (every access 1 KB contiguous).
@@ -444,15 +460,18 @@ static ChainFusion chain_fusion_for(ChainPos pos, const aft_config &c, const Wei
 // of all num_layers layers.
 static int run_encoder(const aft_config &c, const WeightsDev &w, const aft_layer_weights *layers, const Workspace &ws, float *base, float *x,
                        int first_layer, int last_layer, hipStream_t st, bool fused = false, const float *prepacked = nullptr,
-                       float *x_pt = nullptr, float *vt2 = nullptr) {
+                       float *x_pt = nullptr, float *vt2 = nullptr, const L0Fold *fold = nullptr) {
     float *attn = base + ws.attn, *q = base + ws.q, *k = base + ws.k, *vt = base + ws.vt;
     const int rows = ws.planes * ws.tokens;
     const size_t pl = packed_layer_floats(c.model_dim);
     const float *wp = prepacked != nullptr ? prepacked : base + ws.wpack;
     if (prepacked == nullptr)   // weights arrive in torch layout on every call (stateless ABI): re-lay them into fragment order
         STEP("pack_weights", launch_pack_weights(c, layers + first_layer, base + ws.wpack + first_layer * pl, last_layer - first_layer + 1, st));
-    const ChainFusion first = chain_fusion_for(kChainFirst, c, w, ws, base), middle = chain_fusion_for(kChainMiddle, c, w, ws, base),
-                      last = chain_fusion_for(kChainLast, c, w, ws, base);
+    ChainFusion first = chain_fusion_for(kChainFirst, c, w, ws, base);
+    const ChainFusion middle = chain_fusion_for(kChainMiddle, c, w, ws, base), last = chain_fusion_for(kChainLast, c, w, ws, base);
+    if (fused && fold != nullptr && first_layer == 0) {   // the prologue has left the fold's operands (forward_lane)
+        first.fold_tk = fold->tk; first.fold_tvt = fold->tvt; first.fold_w = fold->wf;
+    }
     // whole forward on the workspace's own x: one launch per layer on plane-aligned tiles where layer_fused_selected says so.
     // Layer l reads K / V^T buffer l & 1 and writes the other one ((k, vt) | (attn, vt2)).
     // `x_pt`, `vt2`: the lane's two blocks behind the planned slices (LanePlan), NULL when the caller's workspace has no room
@@ -622,8 +641,11 @@ static int forward_lane(const aft_config *cfg, const aft_weights *w, const float
     float *wpack = prepacked != nullptr || general ? nullptr : base + ws.wpack;      // (the general engine reads the weights as PyTorch holds them)
     float *lent = x_holds_planes(*cfg, ws) ? base + ws.x : nullptr;
     float *up_planes = prologue_upsample_ok(*cfg, wd) ? lent : nullptr;
+    const bool fold_on = l0_fold_selected(*cfg);       // read once per call: the prologue and the first encoder launch agree
+    const L0Fold fold = fold_on ? l0_fold_at(*cfg, ws, base) : L0Fold{};
     STEP("prologue(adapter + pack_weights + upsampler product)",
-         launch_prologue(*cfg, wd, snr, ds, dop, base + ws.tokens6, batch, wpack, pilots, up_planes, st, base + ws.convfrag));
+         launch_prologue(*cfg, wd, snr, ds, dop, base + ws.tokens6, batch, wpack, pilots, up_planes, st, base + ws.convfrag,
+                         fold_on ? &fold : nullptr));
     if (wpack != nullptr && cfg->num_layers > kLayerWindow)     // the prologue launch packs the window of layers its argument holds
         STEP("pack_weights(layers beyond the prologue's window)",
              launch_pack_weights(*cfg, w->layers + kLayerWindow, wpack + packed_layer_floats(cfg->model_dim) * kLayerWindow,
@@ -632,7 +654,7 @@ static int forward_lane(const aft_config *cfg, const aft_weights *w, const float
     // packed engine: patch embedding + linear_1 + positions run inside the first chain launch, linear_2 inside the last one
     const int rc = general ? run_encoder_general(*cfg, wd, w->layers, ws, base, batch, st)
                            : run_encoder(*cfg, wd, w->layers, ws, base, base + ws.x, 0, cfg->num_layers - 1, st, true,
-                                         prepacked != nullptr ? prepacked : wpack, x_pt, vt2);
+                                         prepacked != nullptr ? prepacked : wpack, x_pt, vt2, fold_on ? &fold : nullptr);
     if (rc != AFT_OK) return rc;
     STEP("tail", launch_tail(*cfg, wd, nullptr, base + ws.conv_enhanced, out, batch, st, base + ws.out6, base + ws.convfrag + kConvFragFloats));
     return AFT_OK;
@@ -879,8 +901,13 @@ int aft_profile_kernel_f32(const aft_config *cfg, const aft_weights *w, int whic
     const int rows = ws.planes * ws.tokens;
     float *lent = x_holds_planes(*cfg, ws) ? x : nullptr;     // as the forward: the upsampler's planes lie in x when it holds them
     const float *wp = base + ws.wpack;
-    const ChainFusion first = chain_fusion_for(kChainFirst, *cfg, wd, ws, base), middle = chain_fusion_for(kChainMiddle, *cfg, wd, ws, base),
-                      last = chain_fusion_for(kChainLast, *cfg, wd, ws, base);
+    ChainFusion first = chain_fusion_for(kChainFirst, *cfg, wd, ws, base);
+    const ChainFusion middle = chain_fusion_for(kChainMiddle, *cfg, wd, ws, base), last = chain_fusion_for(kChainLast, *cfg, wd, ws, base);
+    // the fold, as the forward selects it: the prologue class writes its operands, the qkv class reads whatever `attn` and layer 0's
+    // K / V slot of the packed image hold by then (header: meaningful K / V only right behind the prologue class)
+    const bool fold_on = l0_fold_selected(*cfg);
+    const L0Fold fold = fold_on ? l0_fold_at(*cfg, ws, base) : L0Fold{};
+    if (fold_on) { first.fold_tk = fold.tk; first.fold_tvt = fold.tvt; first.fold_w = fold.wf; }
     hipError_t e = hipSuccess;
     for (int i = 0; i < reps && e == hipSuccess; ++i) {
         switch (which) {
@@ -913,7 +940,7 @@ int aft_profile_kernel_f32(const aft_config *cfg, const aft_weights *w, int whic
                 // difference to the upsampler stage (the stage is K0 + K1 + K2)
                 e = launch_prologue(*cfg, wd, cond, cond + batch, cond + 2 * batch, base + ws.tokens6, batch, base + ws.wpack, out,
                                     prologue_upsample_ok(*cfg, wd) && !switch_on(SW_PROLOGUE_NO_UP) ? lent : nullptr, st,
-                                    base + ws.convfrag);
+                                    base + ws.convfrag, fold_on ? &fold : nullptr);
                 break;
             }
             case AFT_KERNEL_TAIL:

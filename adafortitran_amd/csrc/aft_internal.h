@@ -295,9 +295,15 @@ hipError_t launch_adapter(const aft_config &c, const WeightsDev &w, const float 
 // planes (if up_planes != NULL and prologue_upsample_ok: [2 batch][S*T] floats) as ONE launch (k_misc.hip)
 bool prologue_upsample_ok(const aft_config &c, const WeightsDev &w);
 // conv_frag != NULL: + both ConvEnhancers' conv2 / conv3 weights as 16x16x4 operand fragments (2 x kConvFragFloats floats)
+// fold != NULL (l0_fold_selected): + the operands of the first encoder launch's fold (chain_device.h) -- the two tables and the folded
+// matrices' fragments -- and layer 0's K / V fragments of `packed` are left unwritten (the matrices may live there)
+constexpr int kFoldSteps = (kMaxPatchFeatures + 6 + 1) / 2;   // k-steps (two input features each) of the embedding's MFMA products
+struct L0Fold {
+    float *tk, *tvt, *wf;   // [tokens][d] | [d][tokpad] | [2][d / 32][kFoldSteps][64]
+};
 hipError_t launch_prologue(const aft_config &c, const WeightsDev &w, const float *snr, const float *ds, const float *dop,
                            float *tokens6, int batch, float *packed, const float *pilots, float *up_planes, hipStream_t st,
-                           float *conv_frag = nullptr);
+                           float *conv_frag = nullptr, const L0Fold *fold = nullptr);
 hipError_t launch_embed(const aft_config &c, const WeightsDev &w, const float *conv_enhanced,
                         const float *tokens6, float *x, int batch, hipStream_t st);
 // the same stage for ANY model_dim and patches of up to kMaxPatchGeneral elements (general engine, k_misc.hip)
@@ -314,6 +320,8 @@ struct ChainFusion {
     const float *conv_enhanced = nullptr, *tokens6 = nullptr, *lin1_w = nullptr, *lin1_b = nullptr, *pos = nullptr;
     const float *lin2_w = nullptr, *lin2_b = nullptr;
     float *out6 = nullptr;
+    // first launch, optional (l0_fold_selected): layer 0's K / V from the input features on the prologue's tables (ChainArgs::fold_tk ...)
+    const float *fold_tk = nullptr, *fold_tvt = nullptr, *fold_w = nullptr;
     bool x_blocked = false;   // x between the launches in tile-blocked order (ChainArgs::x_blocked): the whole-forward sequence only
 };
 inline int out6_stride(const aft_config &c) { return round_up(c.patch_scs * c.patch_symbols, 8); }   // 8 | 16 (packed engine); 24 | 32 too (general)

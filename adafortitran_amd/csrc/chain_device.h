@@ -76,6 +76,12 @@ struct ChainArgs {
     // x0 is computed from conv_enhanced / tokens6 instead of being read, and written to x.  NULL conv = read x.
     const float *emb_conv, *emb_tok6, *emb_w1, *emb_b1, *emb_pos;   // [planes][S][T], [frames][tokens][6] or NULL, [D][K], [D], [>=tokens][D]
     int emb_S, emb_T, emb_p0, emb_p1, emb_K;                          // K = p0*p1 (+6 with adapter tokens)
+    // fused embedding only, optional (fp32 body): layer 0's K and V straight from the K input features ("the fold").
+    // With x0 = W1 in + b1 + pos[t]:  K[t] = (Wk W1) in + Wk (b1 + pos[t]),  V[t] = (Wv W1) in + Wv (b1 + pos[t]) + bv.  The prologue
+    // launch (k_misc.hip) leaves the two tables and the folded matrices in the workspace; NULL fold_tk = the 128-deep product.
+    const float *fold_tk;    // [tokens][D]: Wk (b1 + pos[t])                  -- the K accumulator's initial value (lane = token row)
+    const float *fold_tvt;   // [D][tokpad]: Wv (b1 + pos[t]) + bv, transposed -- the V accumulator's (lane = feature, registers = tokens)
+    const float *fold_w;     // [K | V][feature block][step][lane]: (Wk W1 | Wv W1)[32 block + lane % 32][2 step + lane / 32], 0 beyond emb_K
     unsigned long long *stamps;  // diagnostic build only (AFT_DIAG_STAMPS), else NULL
     // plane-tile mode (chain_body<..., PT = true>: the fused layer sequence, k_layer.hip) only: row tiles per plane, ceil(tokens / 32).
     // Tile t is (plane t / tpp, query tile t % tpp): no tile straddles a plane; the last tile of a plane holds tokens - 32 (tpp - 1)
@@ -315,7 +321,8 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, float *smem, cons
     // fused embedding (<!MLP,QKV> with emb_conv set): linear_1's weights [D][K] and the K input-feature offsets are
     // staged once per workgroup in the upper half of the hidden buffer (idle in this variant: `xq` below alternates
     // between xb and hb's lower half), so nothing tile-invariant is held in registers across the in-projection GEMM.
-    constexpr int kEmbSteps = (kMaxPatchFeatures + 6 + 1) / 2;
+    constexpr int kEmbSteps = kFoldSteps;   // (kMaxPatchFeatures + 6 + 1) / 2
+    constexpr int kFoldSteps0 = 6;   // the fold's first group of k-steps: K <= 12
     float *emb_w = hb + S::XB;                                   // [D][K]
     int *emb_offs = reinterpret_cast<int *>(emb_w + D * (kMaxPatchFeatures + 6));   // [K]: offset into the row's patch block, or ~index into tokens6
     if constexpr (!MLP) {
@@ -418,6 +425,14 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, float *smem, cons
     if constexpr (!MLP) {
         if (a.emb_conv != nullptr && first_tile < tile_end) emb_request(first_tile);
     }
+    // The fold (ChainArgs::fold_tk set; fp32 body): K and V of the tile are ceil(K/2) MFMAs each on the row's input features -- emb_bv is
+    // the B operand of K's transposed product exactly as it is of x0's, and the A operand of V's normally oriented one (lane = token,
+    // half h supplies k = 2 st + h) -- on accumulators that start from the two tables; only Q's tile runs the 128-deep product over x0.
+    // The 32 table values and the tile-invariant fragments of the folded matrices are requested inside the tile, behind Q's first
+    // weight fragments and x0's MFMAs (nothing more is carried a tile ahead), through SRDs.
+    bool fold = false;
+    if constexpr (!MLP && !BS) fold = a.emb_conv != nullptr && a.fold_tk != nullptr;
+    const Srd srd_tk = make_srd(a.fold_tk), srd_tvt = make_srd(a.fold_tvt), srd_fw = make_srd(a.fold_w);
     // linear_2 partials of the previous tile (fused variant of <MLP,!QKV>): sum the W per-wave partials in wave order, add
     // the bias, store [row][out6_stride].  Called by ONE wave per tile, after the barrier that ended that tile.
     int pending_row0 = -1, pending_valid = 0;    // (PT: out6 row of the tile's first row, its valid rows)
@@ -499,6 +514,41 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, float *smem, cons
     WRing<2, PFF> ring_ff;   // FFN-up fragments
     WRing<3, PFQ> ring_qkv;  // in-projection fragments (q, k, v tiles of head w)
     f32x16 cur;   // this lane's 16 features of the current activation (operand layout)
+    f32x16 acc[3];   // QKV: the q, k and v tiles of head w
+    // the in-projection of the tile's 32 rows of `cur` (x2; x0 or the caller's x in <!MLP,QKV>) -> acc: q, k, v of head w
+    auto in_projection = [&]() {
+        // V tile: lane = feature (fetched before the barrier wait; through an SRD: a 64-bit per-lane pointer here was one
+        // of the values the register allocator spilled, and a scratch reload drains vmcnt -- i.e. waited for the x stores)
+        const float bias_v = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(srd_bv, (unsigned)(fb + r) * 4, 0, 0));
+        // publish x2 (or x0) for the in-projection.  x1 readers are all past the hidden-exchange barrier.
+        // The QKV-only variant has one barrier per tile, so it alternates between two exchange buffers
+        // (xb / the idle hidden buffer): a re-write then sits two barriers behind the last read.
+        float *xq = xb;
+        if constexpr (!MLP) xq = (round & 1) ? hb : xb;
+        if constexpr (BS) {
+            bs_publish(xq, w, lane, cur);
+        } else {
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+                *reinterpret_cast<f32x4 *>(xq + (w * 4 + s) * 256 + lane * 4) = f32x4{cur[4 * s], cur[4 * s + 1], cur[4 * s + 2], cur[4 * s + 3]};
+        }
+        __syncthreads();
+        AFT_STAMP(tid == 0, a.stamps, tile, 9);
+        f32x16 vinit;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) vinit[e] = bias_v;
+        acc[2] = vinit;
+        if constexpr (BS) {
+            // split tier: the attention kernel receives q as bf16 pairs, so the query bias (the accumulator's initial value)
+            // and the softmax scale are applied here, before the split
+            acc[0] = bias_acc(make_srd(a.bv - 2 * D), fb, h);
+            auto xq_bs = [&](int kb, int m) { return bs_fetch(xq, kb, m, lane); };
+            gemm_run_bs<W, 3, PFQ, W, 0x4, decltype(xq_bs), 0x2>(ring_qkv, srd_wq, wq_lane, acc, xq_bs);
+        } else {
+            auto xq_frag = [&](int kb, int s) { return *reinterpret_cast<const f32x4 *>(xq + (kb * 4 + s) * 256 + lane * 4); };
+            gemm_run<W, 3, PFQ, W, 0x4, decltype(xq_frag), 0x3>(ring_qkv, srd_wq, wq_lane, acc, xq_frag);   // q, k start from 0
+        }
+    };
     if constexpr (MLP) {
         f32x16 acc_o[1] = {bias_acc(srd_bo, fb, h)};
         gemm_preload<W, 1, PFD, 1>(ring_d, srd_wo, wo_lane);
@@ -619,17 +669,10 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, float *smem, cons
             }
         }
     } else {
-        gemm_preload<W, 3, PFQ, W>(ring_qkv, srd_wq, wq_lane);
-        if (a.emb_conv == nullptr) {
-            if (!AHEAD) request_x(tile);
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) cur[4 * s + j] = xres[s][j];
-        } else {
-            // x0 = [patch features | adapter features] W1^T + b1 + pos[token]: ceil(K/2) MFMAs of the same transposed
-            // form (A = W1 rows of this wave's feature block, B = the row's input features), the accumulator starting
-            // from b1 + pos -- it comes out in operand layout like any other `cur`.
+        // x0 = [patch features | adapter features] W1^T + b1 + pos[token]: ceil(K/2) MFMAs of the same transposed
+        // form (A = W1 rows of this wave's feature block, B = the row's input features), the accumulator starting
+        // from b1 + pos -- it comes out in operand layout like any other `cur`.
+        auto embed_x0 = [&]() {
             f32x16 acc0 = emb_acc0;
             float av[kEmbSteps];
 #pragma unroll
@@ -640,55 +683,115 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, float *smem, cons
 #pragma unroll
             for (int st = 0; st < kEmbSteps; ++st)
                 if (2 * st < a.emb_K) acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[st], emb_bv[st], acc0, 0, 0, 0);
-            cur = acc0;
+            return acc0;
+        };
+        auto store_x0 = [&](const f32x16 &v) {
             if (row_ok) {
                 if (blocked) {
                     const unsigned xblk = ((unsigned)row0 * D + w * 1024 + lane * 4) * 4;
 #pragma unroll
                     for (int s = 0; s < 4; ++s)
-                        srd_store(srd_x, xblk + 1024 * s, f32x4{cur[4 * s], cur[4 * s + 1], cur[4 * s + 2], cur[4 * s + 3]});
+                        srd_store(srd_x, xblk + 1024 * s, f32x4{v[4 * s], v[4 * s + 1], v[4 * s + 2], v[4 * s + 3]});
                 } else {
 #pragma unroll
                     for (int s = 0; s < 4; ++s)
-                        srd_store(srd_x, xrow + 32 * s, f32x4{cur[4 * s], cur[4 * s + 1], cur[4 * s + 2], cur[4 * s + 3]});
+                        srd_store(srd_x, xrow + 32 * s, f32x4{v[4 * s], v[4 * s + 1], v[4 * s + 2], v[4 * s + 3]});
                 }
             }
+        };
+        if (fold) {
+          if constexpr (!BS) {
+            // ---- the fold: the whole tile in this one block (a value that crossed a join with the other path would be carried
+            // around the tile loop: 32 + 22 registers the kernel does not have) ----
+            gemm_preload<W, 1, PFD, 1>(ring_d, srd_wq, wq_lane);   // Q's tile (tile w of the packed in-projection) alone
+            const f32x16 x0 = embed_x0();
+            // The requests: behind x0's MFMAs and in front of x0's stores (a wait for them is no wait for the stores).
+            // K's initial value: lane = token row, registers = features, as bias_acc
+            const unsigned tok_k = PT ? (unsigned)min(qt_pt * 32 + r, a.tokens - 1) : (unsigned)grow % (unsigned)a.tokens;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const f32x4 t = srd_load(srd_tk, (tok_k * D + fb + 8 * s + 4 * h) * 4);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[1][4 * s + j] = t[j];
+            }
+            // V's: lane = feature, registers 4g .. 4g+3 = tokens 8g + 4h + {0..3} of the tile.  A plane-aligned tile's four tokens are
+            // 16 aligned bytes of the transposed table (its rows are tokpad long: the plane's pad tokens read the zeros written there);
+            // a global tile's may start anywhere and wrap into the next plane
+            const unsigned vrow = (unsigned)(fb + r) * (unsigned)a.tokpad;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                if constexpr (PT) {
+                    const f32x4 t = srd_load(srd_tvt, (vrow + qt_pt * 32 + 8 * g + 4 * h) * 4);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[2][4 * g + j] = t[j];
+                } else {
+                    unsigned t = (unsigned)(row0 + 8 * g + 4 * h) % (unsigned)a.tokens;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        acc[2][4 * g + j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(srd_tvt, (vrow + t) * 4, 0, 0));
+                        if (++t >= (unsigned)a.tokens) t = 0;
+                    }
+                }
+            }
+            // the folded matrices' fragments of this wave's feature block (tile-invariant; the offset is laundered like the weights').
+            // Steps in two groups, each all or nothing -- the default 3 x 2 patch + 6 adapter features is the first group exactly; a
+            // step beyond emb_K multiplies the zeros the prologue wrote there with the zeros emb_request put into emb_bv
+            float fold_wk[kEmbSteps], fold_wv[kEmbSteps];
+            auto frag = [&](int st) {
+                const unsigned fo = ((unsigned)(w * kEmbSteps + st) * 64 + lane + lo) * 4;
+                fold_wk[st] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(srd_fw, fo, 0, 0));
+                fold_wv[st] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(srd_fw, fo + W * kEmbSteps * 64 * 4, 0, 0));
+            };
+            const bool more_steps = a.emb_K > 2 * kFoldSteps0;
+#pragma unroll
+            for (int st = 0; st < kEmbSteps; ++st) fold_wk[st] = fold_wv[st] = 0.f;
+#pragma unroll
+            for (int st = 0; st < kFoldSteps0; ++st) frag(st);
+            if (more_steps) {
+#pragma unroll
+                for (int st = kFoldSteps0; st < kEmbSteps; ++st) frag(st);
+            }
+            store_x0(x0);
+            // publish x0 for Q's product; K and V (off the row's input features, on the tables) fill the wait for the barrier
+            float *xq = (round & 1) ? hb : xb;
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+                *reinterpret_cast<f32x4 *>(xq + (w * 4 + s) * 256 + lane * 4) = f32x4{x0[4 * s], x0[4 * s + 1], x0[4 * s + 2], x0[4 * s + 3]};
+            auto kv_step = [&](int st) {     // ascending k, as every product here
+                acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fold_wk[st], emb_bv[st], acc[1], 0, 0, 0);
+                acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(emb_bv[st], fold_wv[st], acc[2], 0, 0, 0);
+            };
+#pragma unroll
+            for (int st = 0; st < kFoldSteps0; ++st) kv_step(st);
+            if (more_steps) {
+#pragma unroll
+                for (int st = kFoldSteps0; st < kEmbSteps; ++st) kv_step(st);
+            }
+            __syncthreads();
+            AFT_STAMP(tid == 0, a.stamps, tile, 9);
+            f32x16 acc_q[1];
+            auto xq_frag = [&](int kb, int s) { return *reinterpret_cast<const f32x4 *>(xq + (kb * 4 + s) * 256 + lane * 4); };
+            gemm_run<W, 1, PFD, 1, 0, decltype(xq_frag), 0x1>(ring_d, srd_wq, wq_lane, acc_q, xq_frag);   // q starts from 0: the 3-tile product's bits
+            acc[0] = acc_q[0];
+          }
+        } else {
+            gemm_preload<W, 3, PFQ, W>(ring_qkv, srd_wq, wq_lane);
+            if (a.emb_conv == nullptr) {
+                if (!AHEAD) request_x(tile);
+#pragma unroll
+                for (int s = 0; s < 4; ++s)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) cur[4 * s + j] = xres[s][j];
+            } else {
+                cur = embed_x0();
+                store_x0(cur);
+            }
+            if constexpr (QKV) in_projection();
         }
     }
 
     if constexpr (QKV) {
-        // V tile: lane = feature (fetched before the barrier wait; through an SRD: a 64-bit per-lane pointer here was one
-        // of the values the register allocator spilled, and a scratch reload drains vmcnt -- i.e. waited for the x stores)
-        const float bias_v = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(srd_bv, (unsigned)(fb + r) * 4, 0, 0));
-        // publish x2 (or x0) for the in-projection.  x1 readers are all past the hidden-exchange barrier.
-        // The QKV-only variant has one barrier per tile, so it alternates between two exchange buffers
-        // (xb / the idle hidden buffer): a re-write then sits two barriers behind the last read.
-        float *xq = xb;
-        if constexpr (!MLP) xq = (round & 1) ? hb : xb;
-        if constexpr (BS) {
-            bs_publish(xq, w, lane, cur);
-        } else {
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-                *reinterpret_cast<f32x4 *>(xq + (w * 4 + s) * 256 + lane * 4) = f32x4{cur[4 * s], cur[4 * s + 1], cur[4 * s + 2], cur[4 * s + 3]};
-        }
-        __syncthreads();
-        AFT_STAMP(tid == 0, a.stamps, tile, 9);
-        f32x16 vinit;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) vinit[e] = bias_v;
-        f32x16 acc[3];
-        acc[2] = vinit;
-        if constexpr (BS) {
-            // split tier: the attention kernel receives q as bf16 pairs, so the query bias (the accumulator's initial value)
-            // and the softmax scale are applied here, before the split
-            acc[0] = bias_acc(make_srd(a.bv - 2 * D), fb, h);
-            auto xq_bs = [&](int kb, int m) { return bs_fetch(xq, kb, m, lane); };
-            gemm_run_bs<W, 3, PFQ, W, 0x4, decltype(xq_bs), 0x2>(ring_qkv, srd_wq, wq_lane, acc, xq_bs);
-        } else {
-            auto xq_frag = [&](int kb, int s) { return *reinterpret_cast<const f32x4 *>(xq + (kb * 4 + s) * 256 + lane * 4); };
-            gemm_run<W, 3, PFQ, W, 0x4, decltype(xq_frag), 0x3>(ring_qkv, srd_wq, wq_lane, acc, xq_frag);   // q, k start from 0
-        }
+      if constexpr (MLP) in_projection();   // (<!MLP,QKV>: done above, inside the branch that formed its x)
         AFT_STAMP(tid == 0, a.stamps, tile, 10);
         if (AHEAD && tile + tile_stride < ntiles) request_tile(tile + tile_stride);   // before this tile's stores
         if constexpr (!MLP) {

@@ -125,6 +125,9 @@ ChainArgs make_chain_args(const aft_config &c, const aft_layer_weights *m, const
         a.emb_pos = fuse->pos;
         a.emb_S = c.num_scs; a.emb_T = c.num_symbols; a.emb_p0 = c.patch_scs; a.emb_p1 = c.patch_symbols;
         a.emb_K = c.patch_scs * c.patch_symbols + (fuse->tokens6 ? 6 : 0);
+        if (fuse->fold_tk != nullptr && c.precision == AFT_PRECISION_F32) {   // (the split tier keeps the 128-deep product: l0_fold_selected)
+            a.fold_tk = fuse->fold_tk; a.fold_tvt = fuse->fold_tvt; a.fold_w = fuse->fold_w;
+        }
     }
     a.attn = attn;
     a.x = x;

@@ -119,7 +119,98 @@ hipError_t launch_adapter(const aft_config &c, const WeightsDev &w, const float 
 // launch.  As two launches they cost 7.6 + 5.1 us of a 1.57-ms forward; together they take as long as the longer one,
 // which makes the stateless entry point (weights re-packed on every call: the image can never be stale) as fast as a
 // cached image.  Either part may be absent (FortiTran has no adapter; a caller-owned image needs no pack).
+// Further parts, each a range of workgroups of the same launch: the pilot_upsampler product, the conv stacks' operand fragments, and
+// the operands of the first encoder launch's fold (below).
 // ---------------------------------------------------------------------------------------------
+
+// ---- the fold's operands (ChainArgs::fold_tk ...): what layer 0's K and V need beside a row's input features ----
+// They depend on the weights only, but the forward is stateless: every call rebuilds them, as further workgroups of the prologue launch.
+//   tables:  T_k[t][f] = sum_k Wk[f][k] c[t][k],  T_v^T[f][t] = bv[f] + sum_k Wv[f][k] c[t][k],  c[t] = b1 + pos[t]
+//     A workgroup takes kFoldTok tokens and 256 of the 2 d rows of [Wk; Wv], one row per thread.  The rows pass through LDS in
+//     chunks of 16 columns (coalesced 16-byte reads, a padded row per thread), c[t] is read as a broadcast.  Each sum runs in
+//     ascending k with one fp32 FMA per term, so a table entry is the same bits whatever the batch, the lane or the grid.
+//     2 x tokens x d x d MACs: 9.2 M over 144 workgroups at the default.  The pad tokens of T_v^T's rows are written as zeros.
+//   matrices: (Wk W1 | Wv W1)[row][k] = sum_j W[row][j] W1[j][k] in ascending j, one thread per entry, stored as the MFMA operand
+//     fragments of the first launch: [K | V][feature block][step][lane] = entry (32 block + lane % 32, 2 step + lane / 32), zeros beyond K.
+constexpr int kFoldTok = 2, kFoldChunk = 16;
+struct FoldArgs {
+    const float *wkv, *bv;          // layer 0: in_proj_weight + d d ([2 d][d]: Wk then Wv), in_proj_bias + 2 d
+    const float *w1, *b1, *pos;     // linear_1 [d][K], [d]; positions [>= tokens][d]
+    float *tk, *tvt, *wf;
+    int d, K, tokens, tokpad;
+};
+inline size_t fold_tables_lds(int d) { return sizeof(float) * ((size_t)256 * (kFoldChunk + 1) + (size_t)kFoldTok * d); }
+
+__device__ __forceinline__ void fold_tables_body(const FoldArgs &f, int blk, float *sm) {
+    float *sw = sm, *sc = sm + 256 * (kFoldChunk + 1);     // [256 rows][chunk + 1] | [kFoldTok][d]
+    const int tid = threadIdx.x, chunks = (2 * f.d + 255) / 256;
+    const int t0 = (blk / chunks) * kFoldTok, row0 = (blk % chunks) * 256, row = row0 + tid;
+    for (int i = tid; i < kFoldTok * f.d; i += 256) {
+        const int tt = i / f.d, k = i - tt * f.d, t = t0 + tt;
+        sc[i] = t < f.tokens ? f.b1[k] + f.pos[(size_t)t * f.d + k] : 0.f;     // (b1 + pos: x0's own initial value, chain_device.h)
+    }
+    float acc[kFoldTok];
+#pragma unroll
+    for (int tt = 0; tt < kFoldTok; ++tt) acc[tt] = row >= f.d && row < 2 * f.d ? f.bv[row - f.d] : 0.f;
+    // a chunk is kFoldChunk / 4 pieces of 16 bytes per thread; the next chunk's pieces are requested before this one's FMAs, so the
+    // d / kFoldChunk round trips to memory overlap the arithmetic instead of standing in a row
+    constexpr int kPieces = kFoldChunk / 4;
+    f32x4 piece[kPieces];
+    auto request = [&](int kc) {
+#pragma unroll
+        for (int m = 0; m < kPieces; ++m) {
+            const int i = tid + 256 * m, rr = i / kPieces, c4 = (i % kPieces) * 4;
+            piece[m] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (row0 + rr < 2 * f.d) piece[m] = *reinterpret_cast<const f32x4 *>(f.wkv + (size_t)(row0 + rr) * f.d + kc + c4);
+        }
+    };
+    request(0);
+    for (int kc = 0; kc < f.d; kc += kFoldChunk) {
+        __syncthreads();     // the previous chunk has been read (first pass: sc is written)
+#pragma unroll
+        for (int m = 0; m < kPieces; ++m) {
+            const int i = tid + 256 * m, rr = i / kPieces, c4 = (i % kPieces) * 4;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) sw[rr * (kFoldChunk + 1) + c4 + j] = piece[m][j];
+        }
+        if (kc + kFoldChunk < f.d) request(kc + kFoldChunk);
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < kFoldChunk; ++kk) {
+            const float wv = sw[tid * (kFoldChunk + 1) + kk];
+#pragma unroll
+            for (int tt = 0; tt < kFoldTok; ++tt) acc[tt] = fmaf(wv, sc[tt * f.d + kc + kk], acc[tt]);
+        }
+    }
+#pragma unroll
+    for (int tt = 0; tt < kFoldTok; ++tt) {
+        const int t = t0 + tt;
+        if (row < f.d) {
+            if (t < f.tokens) f.tk[(size_t)t * f.d + row] = acc[tt];
+        } else if (row < 2 * f.d && t < f.tokpad) {
+            f.tvt[(size_t)(row - f.d) * f.tokpad + t] = t < f.tokens ? acc[tt] : 0.f;
+        }
+    }
+}
+
+__device__ __forceinline__ void fold_matrices_body(const FoldArgs &f, int blk) {
+    const int o = blk * 256 + threadIdx.x, per_part = (f.d / 32) * kFoldSteps * 64;
+    if (o >= 2 * per_part) return;
+    const int part = o / per_part, rem = o - part * per_part;
+    const int wblock = rem / (kFoldSteps * 64), st = rem / 64 % kFoldSteps, lane = rem & 63;
+    const int row = part * f.d + 32 * wblock + (lane & 31), k = 2 * st + (lane >> 5);
+    float acc = 0.f;
+    if (k < f.K) {
+        const float *wr = f.wkv + (size_t)row * f.d;
+        for (int j = 0; j < f.d; j += 4) {
+            const f32x4 wv = *reinterpret_cast<const f32x4 *>(wr + j);
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) acc = fmaf(wv[jj], f.w1[(size_t)(j + jj) * f.K + k], acc);
+        }
+    }
+    f.wf[o] = acc;
+}
+
 struct PrologueArgs {
     AdapterArgs ad;
     float *packed;
@@ -129,6 +220,8 @@ struct PrologueArgs {
     int up_bx, npix, pf, nplanes;
     float *conv_frag;          // [2 stacks][22 quads][64 lanes][4]: conv2 / conv3 weights as 16x16x4 operand fragments (conv_device.h)
     int frag_blocks;
+    FoldArgs fold;             // the fold's operands; fold_table_blocks = 0: not computed
+    int fold_table_blocks, fold_matrix_blocks;
 };
 
 __global__ __launch_bounds__(256) void prologue_kernel(const WeightsDev w, const PrologueArgs a) {
@@ -139,8 +232,22 @@ __global__ __launch_bounds__(256) void prologue_kernel(const WeightsDev w, const
         return;
     }
     blk -= a.adapter_blocks;
+    if (blk < a.fold_table_blocks) {         // (workgroup-uniform as well)
+        fold_tables_body(a.fold, blk, sm);
+        return;
+    }
+    blk -= a.fold_table_blocks;
+    if (blk < a.fold_matrix_blocks) {
+        fold_matrices_body(a.fold, blk);
+        return;
+    }
+    blk -= a.fold_matrix_blocks;
     if (blk < a.pack_blocks) {
-        pack_weights_vec(w, a.packed, a.d, 0, a.num_layers, a.split, (size_t)blk * 256 + threadIdx.x);
+        // with the fold, layer 0's K and V fragments (floats [d d, 3 d d) of the image) are not packed: the first launch does not read
+        // them and the folded matrices live there
+        const size_t v = (size_t)blk * 256 + threadIdx.x, dd4 = (size_t)a.d * a.d / 4;
+        if (a.fold_table_blocks > 0 && v >= dd4 && v < 3 * dd4) return;
+        pack_weights_vec(w, a.packed, a.d, 0, a.num_layers, a.split, v);
         return;
     }
     blk -= a.pack_blocks;
@@ -175,7 +282,7 @@ bool prologue_upsample_ok(const aft_config &c, const WeightsDev &w) {
 
 hipError_t launch_prologue(const aft_config &c, const WeightsDev &w, const float *snr, const float *ds, const float *dop,
                            float *tokens6, int batch, float *packed, const float *pilots, float *up_planes, hipStream_t st,
-                           float *conv_frag) {
+                           float *conv_frag, const L0Fold *fold) {
     PrologueArgs a{};
     if (conv_frag != nullptr) {
         a.conv_frag = conv_frag;
@@ -200,7 +307,19 @@ hipError_t launch_prologue(const aft_config &c, const WeightsDev &w, const float
         up_blocks = a.up_bx * ((a.nplanes + kUpPlanes - 1) / kUpPlanes);
         lds = std::max(lds, upsample_planes_lds(a.pf));
     }
-    const int blocks = a.adapter_blocks + a.pack_blocks + a.frag_blocks + up_blocks;
+    if (fold != nullptr && fold->tk != nullptr) {
+        FoldArgs &f = a.fold;
+        f.d = c.model_dim; f.K = c.patch_scs * c.patch_symbols + (c.adaptive ? 6 : 0);
+        f.tokens = tokens_of(c); f.tokpad = round_up(f.tokens, kTile);
+        f.wkv = w.layers[0].in_proj_w + (size_t)f.d * f.d; f.bv = w.layers[0].in_proj_b + 2 * f.d;
+        f.w1 = w.lin1_w; f.b1 = w.lin1_b; f.pos = w.pos;
+        f.tk = fold->tk; f.tvt = fold->tvt; f.wf = fold->wf;
+        a.d = c.model_dim;
+        a.fold_table_blocks = (f.tokpad + kFoldTok - 1) / kFoldTok * ((2 * f.d + 255) / 256);
+        a.fold_matrix_blocks = (2 * (f.d / 32) * kFoldSteps * 64 + 255) / 256;
+        lds = std::max(lds, fold_tables_lds(f.d));
+    }
+    const int blocks = a.adapter_blocks + a.fold_table_blocks + a.fold_matrix_blocks + a.pack_blocks + a.frag_blocks + up_blocks;
     if (blocks == 0) return hipSuccess;
     hipLaunchKernelGGL(prologue_kernel, dim3(blocks), dim3(256), lds, st, w, a);
     return hipGetLastError();

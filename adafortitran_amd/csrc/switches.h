@@ -1,6 +1,6 @@
 // switches.h -- every run-time switch of the library, declared once.  A switch is an "AFT_*" name that selects a kernel variant, a
-// split or a fallback path for measurements and A/B comparisons; none changes results beyond summation order and the product never
-// sets one.  The library fills the table from the environment ONCE, when it is loaded (names not listed here are ignored: the tools'
+// split or a fallback path for measurements and A/B comparisons; none changes results beyond summation order -- but AFT_L0_FOLD, which
+// also changes rounding: it selects between two algebraically equal forms of layer 0's keys and values -- and the product never sets one.  The library fills the table from the environment ONCE, when it is loaded (names not listed here are ignored: the tools'
 // own AFT_BATCH, AFT_REPS, AFT_LIB_PATH ... are not switches); afterwards a switch changes only through aft_set_switch, and an unknown
 // name is refused there.  Set to anything = on; switch_int reads the value as atoi() does.
 //
@@ -9,6 +9,7 @@
 
 #define AFT_SWITCHES(X) \
     X(LANES, "AFT_LANES", "1 = never split a forward into lanes; 2 .. 4 = always that many shares (header section \"Lanes\")") \
+    X(L0_FOLD, "AFT_L0_FOLD", "0 = layer 0's keys and values by the model_dim-deep product over x0, not from the input features on the prologue's tables (DESIGN.md 4.1)") \
     X(LAYER_FUSED, "AFT_LAYER_FUSED", "0 = never the one-launch-per-layer sequence (k_layer.hip), 1 = wherever its shape is covered (default: where plane-aligned tiles add no round)") \
     X(PROLOGUE_NO_UP, "AFT_PROLOGUE_NO_UP", "measurement: the profiled prologue launch without the pilot upsampler product") \
     X(CONV_NSPLIT, "AFT_CONV_NSPLIT", "1 | 2 | 4 column ranges per plane in the streaming conv kernels (default: by the batch)") \

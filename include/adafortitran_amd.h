@@ -655,13 +655,17 @@ int aft_stage_tail_f32(const aft_config *cfg, const aft_weights *w, const float 
                                    pilot_upsampler product where the forward does that; else product + ConvEnhancer fused) */
 #define AFT_KERNEL_EMBED 1      /* patch gather + adapter concat + linear_1 + pos as its own kernel (the stage entry
                                    point's; aft_forward_f32 runs it inside AFT_KERNEL_QKV)                     */
-#define AFT_KERNEL_QKV 2        /* chain kernel: embedding + in-projection of layer 0        */
+#define AFT_KERNEL_QKV 2        /* chain kernel: embedding + in-projection of layer 0.  Where the forward folds layer 0's K / V
+                                   (fp32 packed engine, switch AFT_L0_FOLD) so does this class: it reads the two tables the
+                                   prologue leaves in the workspace, which a forward overwrites later on -- its K / V are
+                                   meaningful only right behind AFT_KERNEL_PROLOGUE; its timing is the forward's launch's either way */
 #define AFT_KERNEL_ATTENTION 3  /* MFMA attention                                            */
 #define AFT_KERNEL_CHAIN 4      /* chain kernel: out-proj+LN1+FFN+LN2 (layer 0) + QKV (layer 1) */
 #define AFT_KERNEL_TAIL 5       /* fold + residual + final ConvEnhancer (linear_2 done by AFT_KERNEL_CHAIN_LAST) */
 #define AFT_KERNEL_CHAIN_LAST 6 /* chain kernel of the last layer: out-proj+LN1+FFN+LN2 + linear_2             */
 /* (7 was the retired plane-resident encoder kernel: now an unknown kernel id) */
-#define AFT_KERNEL_PROLOGUE 8   /* the forward's first launch: channel adapter + weight re-lay + pilot_upsampler product; `out` = one
+#define AFT_KERNEL_PROLOGUE 8   /* the forward's first launch: channel adapter + weight re-lay + pilot_upsampler product (+ the
+                                   tables and folded matrices of layer 0's K / V where the forward folds them); `out` = one
                                    buffer [pilots: batch x Ps x Pt x 2 floats | snr: batch | ds: batch | dop: batch]        */
 int aft_profile_kernel_f32(const aft_config *cfg, const aft_weights *w, int which, float *out,
                            void *workspace, size_t workspace_bytes, int batch, int reps, void *stream);
