@@ -34,11 +34,12 @@ import torch
 from . import _abi
 from .synth import _DOP_GRID, _DS_GRID, _M64, _SNR_GRID, _splitmix64
 
-# the streams of the counter-based hash (csrc/frame_device.h FrameStream): 0..4 the simulator's, 5..7 the link's, 8 the coded link's
-# information bits (linksim.py)
+# the streams of the counter-based hash (csrc/frame_device.h FrameStream): 0..4 the simulator's, 5..7 the link's, 8 the coded links'
+# information bits, 9 the shifts of the default LDPC base matrix, keyed by its seed and used on the host only (linksim.py)
 STREAM_CONDITION, STREAM_ANGLE, STREAM_PHASE, STREAM_NOISE_RADIUS, STREAM_NOISE_ANGLE = range(5)
 STREAM_DATA_BITS, STREAM_DATA_NOISE_RADIUS, STREAM_DATA_NOISE_ANGLE = range(5, 8)
 STREAM_CODE_BITS = 8
+STREAM_LDPC_SHIFTS = 9
 CHANNEL_TYPE = "SYNTH"
 
 

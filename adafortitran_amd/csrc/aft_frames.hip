@@ -75,6 +75,28 @@ int check_link(const char *who, const aft_link &l) {
     return AFT_OK;
 }
 
+// the interleaver of the coded links: a stride in [1, used) coprime to the used bits, and its inverse
+bool stride_ok(const char *who, unsigned long long stride, unsigned long long stride_inverse, unsigned long long used) {
+    if (stride < 1 || stride >= used) {
+        set_error("%s: stride = %llu is outside [1, %llu)", who, stride, used);
+        return false;
+    }
+    unsigned long long g = stride, r = used;
+    while (r != 0) {
+        const unsigned long long next = g % r;
+        g = r; r = next;
+    }
+    if (g != 1) {
+        set_error("%s: stride = %llu is not coprime to the %llu used bits", who, stride, used);
+        return false;
+    }
+    if (stride_inverse < 1 || stride_inverse >= used || (unsigned long long)((unsigned __int128)stride * stride_inverse % used) != 1) {
+        set_error("%s: stride_inverse = %llu is not the inverse of stride = %llu modulo %llu", who, stride_inverse, stride, used);
+        return false;
+    }
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -180,26 +202,65 @@ int aft_link_decode_f32(const aft_link *link, const float *llr, const unsigned l
                   info_bits);
         return AFT_ERR_SHAPE;
     }
-    if (stride < 1 || stride >= used) {                         // used >= 10: no block has fewer coded bits
-        set_error("%s: stride = %llu is outside [1, %llu)", who, stride, used);
-        return AFT_ERR_SHAPE;
-    }
-    unsigned long long g = stride, r = used;
-    while (r != 0) {
-        const unsigned long long next = g % r;
-        g = r; r = next;
-    }
-    if (g != 1) {
-        set_error("%s: stride = %llu is not coprime to the %llu used bits", who, stride, used);
-        return AFT_ERR_SHAPE;
-    }
-    if (stride_inverse < 1 || stride_inverse >= used || (unsigned long long)((unsigned __int128)stride * stride_inverse % used) != 1) {
-        set_error("%s: stride_inverse = %llu is not the inverse of stride = %llu modulo %llu", who, stride_inverse, stride, used);
-        return AFT_ERR_SHAPE;
-    }
+    if (!stride_ok(who, stride, stride_inverse, used)) return AFT_ERR_SHAPE;   // used >= 10: no block has fewer coded bits
     hipError_t e = launch_link_decode(*link, llr, keys, info_bits, rate, (unsigned)coded, (unsigned)blocks, stride, qgain,
                                       counts, bits, batch, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? AFT_OK : hip_fail("link_decode", e);
+}
+
+int aft_link_ldpc_f32(const aft_link *link, const float *llr, const unsigned long long *keys, int base_rows, int base_cols,
+                      const int32_t *shifts, unsigned long long stride, unsigned long long stride_inverse, float qgain, int offset,
+                      int max_iters, int32_t *counts, unsigned char *bits, int batch, void *stream) {
+    const char *who = "link ldpc";
+    AFT_REQUIRE(link && llr && keys && shifts && counts, "link ldpc: NULL pointer argument");
+    AFT_REQUIRE(aligned(8, keys), "link ldpc: keys must be 8-byte aligned");
+    AFT_REQUIRE(aligned(4, llr, shifts, counts), "link ldpc: llr, shifts and counts must be 4-byte aligned");
+    AFT_REQUIRE(batch >= 1, "link ldpc: batch must be at least 1 (got %d)", batch);
+    AFT_REQUIRE(std::isfinite(qgain) && qgain > 0.f, "link ldpc: qgain = %g must be finite and positive", (double)qgain);
+    const int rc = check_link(who, *link);
+    if (rc != AFT_OK) return rc;
+    if (!within(who, "base_rows", base_rows, 3, 16) || !within(who, "base_cols", base_cols, base_rows + 1, 32) ||
+        !within(who, "offset", offset, 0, 127) || !within(who, "max_iters", max_iters, 1, 255))
+        return AFT_ERR_SHAPE;
+    const int kb = base_cols - base_rows;
+    int edges = 3 + 2 * (base_rows - 1);                        // the parity part
+    for (int j = 0; j < kb; ++j) {
+        int weight = 0;
+        for (int i = 0; i < base_rows; ++i) {
+            const int s = shifts[i * kb + j];
+            if (s < -1 || s >= AFT_LINK_LDPC_Z) {
+                set_error("%s: shifts[%d][%d] = %d is neither -1 nor a shift in 0..%d", who, i, j, s, AFT_LINK_LDPC_Z - 1);
+                return AFT_ERR_SHAPE;
+            }
+            weight += s >= 0 ? 1 : 0;
+        }
+        if (weight == 0) {
+            set_error("%s: base column %d has no entry", who, j);
+            return AFT_ERR_SHAPE;
+        }
+        edges += weight;
+    }
+    if (edges > AFT_LINK_LDPC_MAX_EDGES) {
+        set_error("%s: %d entries in the base matrix, parity part included; at most %d", who, edges, AFT_LINK_LDPC_MAX_EDGES);
+        return AFT_ERR_SHAPE;
+    }
+    const unsigned long long coded = (unsigned long long)base_cols * AFT_LINK_LDPC_Z, info = (unsigned long long)kb * AFT_LINK_LDPC_Z;
+    const unsigned long long carried = (unsigned long long)link->bits_per_symbol *
+        ((unsigned long long)link->num_scs * link->num_symbols - (unsigned long long)link->pilot_scs * link->pilot_symbols);
+    const unsigned long long blocks = carried / coded, used = blocks * coded;
+    if (blocks == 0) {
+        set_error("%s: a frame carries %llu bits, fewer than the %llu coded bits of one block", who, carried, coded);
+        return AFT_ERR_SHAPE;
+    }
+    if (blocks * info > (1ull << 31)) {
+        set_error("%s: %llu blocks of %llu information bits: more than 2^31, where the hash's index and the int32 counts end", who, blocks,
+                  info);
+        return AFT_ERR_SHAPE;
+    }
+    if (!stride_ok(who, stride, stride_inverse, used)) return AFT_ERR_SHAPE;
+    hipError_t e = launch_link_ldpc(*link, llr, keys, base_rows, base_cols, shifts, (unsigned)blocks, stride, qgain, offset, max_iters,
+                                    counts, bits, batch, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? AFT_OK : hip_fail("link_ldpc", e);
 }
 
 }  // extern "C"

@@ -385,6 +385,13 @@ int link_code_waves(unsigned steps, unsigned blocks);
 hipError_t launch_link_decode(const aft_link &link, const float *llr, const unsigned long long *keys, int info_bits, int rate,
                               unsigned coded_bits, unsigned blocks, unsigned long long stride, float qgain, int32_t *counts,
                               unsigned char *bits, int batch, hipStream_t st);
+// the LDPC-coded link's layered min-sum decoder (k_linkldpc.hip): everything has passed aft_link_ldpc_f32's checks; shifts is the host
+// table [base_rows][base_cols - base_rows], read during the call; bits may be NULL.  link_ldpc_waves: the code blocks a workgroup
+// decodes at once (their posteriors and messages fill LDS)
+int link_ldpc_waves(int base_cols, int edges, unsigned blocks);
+hipError_t launch_link_ldpc(const aft_link &link, const float *llr, const unsigned long long *keys, int base_rows, int base_cols,
+                            const int32_t *shifts, unsigned blocks, unsigned long long stride, float qgain, int offset, int max_iters,
+                            int32_t *counts, unsigned char *bits, int batch, hipStream_t st);
 hipError_t launch_mse(const float *est, const float *ref, double *sum_sq, long long n_complex, hipStream_t st);
 hipError_t launch_fill_lds(float value, hipStream_t st);   // test hook: every CU's LDS filled with `value`
 hipError_t launch_peek_lds(float *out, int workgroups, int n, hipStream_t st);   // ... and what a kernel finds in its LDS at start

@@ -14,7 +14,7 @@ enum FrameStream : unsigned {
     kStreamPilotNoiseRadius = 3, kStreamPilotNoiseAngle = 4,    // noise on the pilots (index i pilot_symbols + j)
     kStreamDataBits = 5,                                        // the link's sent bits (index q = s T + t)
     kStreamDataNoiseRadius = 6, kStreamDataNoiseAngle = 7,      // ... and the noise on its data symbols
-    kStreamCodeBits = 8,                                        // the coded link's information bits (index b K + t, the top bit)
+    kStreamCodeBits = 8,                                        // the coded links' information bits (index b K + t, the top bit)
 };
 
 __host__ __device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {

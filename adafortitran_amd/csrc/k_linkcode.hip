@@ -22,7 +22,7 @@
 //
 // No atomics, no workspace: everything is integer after the quantiser, whose one float32 product and round-to-nearest-even are the
 // definition's.
-#include "frame_device.h"
+#include "linkcode_device.h"
 
 namespace aft {
 namespace {
@@ -61,43 +61,6 @@ __device__ __forceinline__ unsigned code_offset(int rate, unsigned t, bool &keep
     return 4 * period + (ph == 0 ? 0 : ph + 1);
 }
 
-// x mod u without a division: inv = floor(2^64 / u), so mulhi(x, inv) is the quotient or up to two below it
-__device__ __forceinline__ unsigned long long code_mod(unsigned long long x, unsigned long long u, unsigned long long inv) {
-    unsigned long long r = x - __umul64hi(x, inv) * u;
-    r -= r >= u ? u : 0;
-    r -= r >= u ? u : 0;
-    AFT_DEV_ASSERT(r < u);
-    return r;
-}
-
-// p a mod u for p, a < u < 2^35: the product fits 64 bits below 2^32, else in three pieces of 17 bits
-__device__ __forceinline__ unsigned long long code_mulmod(unsigned long long p, unsigned long long a, unsigned long long u,
-                                                          unsigned long long inv) {
-    if (u <= (1ull << 32)) return code_mod(p * a, u, inv);
-    const unsigned long long hi = code_mod((p >> 17) * a, u, inv);
-    return code_mod(code_mod(hi << 17, u, inv) + code_mod((p & 0x1FFFF) * a, u, inv), u, inv);
-}
-
-// grid index of the e-th data element: before[i] data elements lie before pilot row psc[i]
-__device__ __forceinline__ unsigned code_grid_index(const int *psc, const unsigned *before, const int *psym, int Ps, int Pt, unsigned T,
-                                                    unsigned e) {
-    int lo = 0, hi = Ps;
-    while (lo < hi) {                                           // lo = #{i : before[i] <= e}
-        const int mid = (lo + hi) >> 1;
-        if (before[mid] <= e) lo = mid + 1;
-        else hi = mid;
-    }
-    if (lo > 0) {
-        const unsigned l = e - before[lo - 1];
-        if (l < T - (unsigned)Pt) {                             // inside pilot row lo - 1: the l-th column that is no pilot
-            unsigned t = l;
-            for (int i = 0; i < Pt; ++i) t += (unsigned)psym[i] <= t ? 1u : 0u;
-            return (unsigned)psc[lo - 1] * T + t;
-        }
-    }
-    return e + (unsigned)lo * (unsigned)Pt;                     // as if the lo pilot rows before it were whole
-}
-
 __global__ __launch_bounds__(kCodeMaxWaves *kWave) void link_decode_kernel(const LinkCodeArgs a) {
     extern __shared__ unsigned long long surv_all[];            // [waves][steps]: a step's 64 decisions
     __shared__ int psc[AFT_CHANSIM_MAX_PILOT_SCS], psym[AFT_CHANSIM_MAX_PILOT_SYMBOLS];
@@ -110,11 +73,7 @@ __global__ __launch_bounds__(kCodeMaxWaves *kWave) void link_decode_kernel(const
     const unsigned T = (unsigned)c.num_symbols, K = a.info, steps = a.steps;
     AFT_DEV_ASSERT(Ps >= 1 && Ps <= AFT_CHANSIM_MAX_PILOT_SCS && Pt >= 1 && Pt <= AFT_CHANSIM_MAX_PILOT_SYMBOLS && (unsigned)Pt <= T);
     AFT_DEV_ASSERT(waves >= 1 && waves <= kCodeMaxWaves && steps == K + kCodeTail && steps <= AFT_LINK_CODE_MAX_INFO_BITS + kCodeTail);
-    if (tid < Ps) {
-        psc[tid] = c.pilot_sc_index[tid];
-        before[tid] = (unsigned)c.pilot_sc_index[tid] * T - (unsigned)tid * (unsigned)Pt;
-    }
-    if (tid < Pt) psym[tid] = c.pilot_symbol_index[tid];
+    code_pilot_tables(c, tid, psc, before, psym);
     __syncthreads();
     const unsigned long long kf = a.keys[f];
     const float *llr = a.llr + f * ((size_t)a.elems + 1) * (size_t)m;
@@ -133,23 +92,14 @@ __global__ __launch_bounds__(kCodeMaxWaves *kWave) void link_decode_kernel(const
     auto locate = [&](unsigned long long j, unsigned cbit) {
         AFT_DEV_ASSERT(j < a.used);
         unsigned e, k;
-        switch (m) {
-            case 2: e = (unsigned)(j >> 1); k = (unsigned)j & 1u; break;
-            case 4: e = (unsigned)(j >> 2); k = (unsigned)j & 3u; break;
-            case 8: e = (unsigned)(j >> 3); k = (unsigned)j & 7u; break;
-            default: e = (unsigned)((j >> 1) / 3); k = (unsigned)(j - 6ull * e); break;
-        }
+        code_split(j, m, e, k);
         const unsigned q = code_grid_index(psc, before, psym, Ps, Pt, T, e);
         AFT_DEV_ASSERT(q <= a.elems && k < (unsigned)m);
         const unsigned sent = (unsigned)(frame_word(kf, kStreamDataBits, q) >> (63 - k)) & 1u;
         return Input{llr + ((size_t)q * m + k), (sent ^ cbit) != 0};
     };
     // the descrambled LLR, quantised: one float32 product, to nearest with ties to even, NaN gives 0
-    auto quantise = [&](float l, bool turn) {
-        const float v = (turn ? -l : l) * a.qgain;
-        if (v != v) return 0;
-        return (int)fminf(fmaxf(rintf(v), -127.f), 127.f);
-    };
+    auto quantise = [&](float l, bool turn) { return code_quantise(l, turn, a.qgain); };
     // What lane l prepares of step t0 + l: the two LLRs are LOADED here and quantised by `pack` after the serial chain of the 64
     // steps before them has run, so their latency is the chain's to hide.
     struct Fetched {

@@ -18,7 +18,7 @@ from typing import Dict, Iterable, List, Optional, Tuple
 import torch
 
 from .estimators import AdaFortiTranEstimator
-from .linksim import DEFAULT_FACTORS, BlockErrorAccumulator, LinkAccumulator, RateAccumulator
+from .linksim import DEFAULT_FACTORS, BlockErrorAccumulator, LdpcBlockErrorAccumulator, LdpcConfig, LinkAccumulator, RateAccumulator
 from .lmmse import LmmseEstimator
 from .metrics import MseAccumulator, to_db
 
@@ -94,9 +94,11 @@ def get_link_rates(model: Optional[torch.nn.Module], test_dataloaders: List[Tupl
 
 def get_link_bler(model: Optional[torch.nn.Module], test_dataloaders: List[Tuple[str, Iterable]], code_cfg, seed: int = 0,
                   err_var: float = 0.0, group=None) -> Dict[int, float]:
-    """Block-error rate per loader with a decoder in the loop: the convolutional code ``code_cfg`` (``linksim.CodeConfig``) rides on the
-    same link, a Viterbi decoder reads the max-log LLRs the demapper forms with the model's estimate; ``model=None`` is perfect channel
-    knowledge.  Sorting, keys and the frames' bits and noise as ``get_link_stats``; the counts accumulate on the device
-    (``linksim.BlockErrorAccumulator``) and are read once per loader."""
-    return _link_sweep(model, test_dataloaders, lambda device: BlockErrorAccumulator(code_cfg, device, seed, err_var),
+    """Block-error rate per loader with a decoder in the loop: the code ``code_cfg`` rides on the same link and its decoder reads the
+    max-log LLRs the demapper forms with the model's estimate -- a ``linksim.CodeConfig`` is the convolutional code with a Viterbi
+    decoder (``linksim.BlockErrorAccumulator``), a ``linksim.LdpcConfig`` the quasi-cyclic LDPC code with a layered min-sum decoder
+    (``linksim.LdpcBlockErrorAccumulator``); ``model=None`` is perfect channel knowledge.  Sorting, keys and the frames' bits and noise
+    as ``get_link_stats``; the counts accumulate on the device and are read once per loader."""
+    accumulator = LdpcBlockErrorAccumulator if isinstance(code_cfg, LdpcConfig) else BlockErrorAccumulator
+    return _link_sweep(model, test_dataloaders, lambda device: accumulator(code_cfg, device, seed, err_var),
                        lambda acc: acc.result(group))

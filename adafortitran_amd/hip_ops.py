@@ -588,6 +588,43 @@ class LinkDecodePlan:
         return counts, bits
 
 
+class LinkLdpcPlan:
+    """An LDPC-coded link (``linksim.LdpcConfig``) turned into ``aft_link_ldpc_f32``'s arguments ONCE.  ``plan(llr, keys,
+    want_bits=False)`` -> ``(counts int32 [batch, 3] = (information-bit errors, block errors, iterations summed over the blocks) per
+    frame, bits uint8 [batch, B, K] or None)`` on the plan's device: one ``ctypes`` call, one launch on the current stream, no
+    synchronisation.  Operands as ``LinkDecodePlan``'s.  The plan trusts its caller in one thing only: its device is the current one."""
+
+    def __init__(self, code, device: torch.device) -> None:
+        from .linksim import LdpcConfig
+        if not isinstance(code, LdpcConfig):
+            raise ValueError(f"LinkLdpcPlan needs a linksim.LdpcConfig (got {type(code).__name__})")
+        self.device = _hip_device(device, "LinkLdpcPlan", "linksim.link_ldpc_host")
+        self.code = code
+        self.link = code.link.to_struct()                       # validated by the config itself; the entry point checks again
+        self.shape = (*code.link.sim.ofdm, code.link.bits_per_symbol)
+        kb = code.base_cols - code.base_rows
+        self.shifts = (C.c_int32 * (code.base_rows * kb))(*(v for row in code.shifts for v in row))      # host memory, read per call
+        self.args = (code.base_rows, code.base_cols, C.addressof(self.shifts), code.stride, code.stride_inverse, code.qgain, code.offset,
+                     code.max_iters)
+
+    def __call__(self, llr: torch.Tensor, keys: torch.Tensor, want_bits: bool = False, lib=None):
+        lib = lib or _lib.load()
+        if llr.dim() != 4 or tuple(llr.shape[1:]) != self.shape or llr.shape[0] < 1:
+            raise ValueError(f"Expected llr shape (B >= 1, {self.shape[0]}, {self.shape[1]}, {self.shape[2]}), got {tuple(llr.shape)}")
+        if llr.dtype != torch.float32:
+            raise ValueError(f"llr must be float32, got {llr.dtype}")
+        if llr.device != self.device:
+            raise ValueError(f"llr must live on {self.device} (it is on {llr.device})")
+        batch = llr.shape[0]
+        llr = llr.contiguous()                                  # held by the caller until after the launch is enqueued
+        keys = _in_place("keys", keys, torch.int64, self.device, batch)
+        counts = torch.empty((batch, 3), dtype=torch.int32, device=self.device)             # the kernel writes every element
+        bits = torch.empty((batch, self.code.blocks, self.code.info_bits), dtype=torch.uint8, device=self.device) if want_bits else None
+        _lib.check(lib.aft_link_ldpc_f32(C.byref(self.link), llr.data_ptr(), keys.data_ptr(), *self.args, counts.data_ptr(), _ptr(bits),
+                                         batch, _lib.current_stream_ptr(self.device)), lib)
+        return counts, bits
+
+
 def ls_mse_db(ls: torch.Tensor, ideal: torch.Tensor) -> torch.Tensor:
     """Per-frame LS-baseline MSE in dB, float32 [B] (reference utils.py:248-261 per file)."""
     lib = _lib.load()

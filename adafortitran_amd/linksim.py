@@ -93,6 +93,47 @@ words ``w`` of stream 5 -- and the code rides on it through a scrambler both end
 Everything after the quantiser is integer, so the host and the device agree bit for bit on the same float32 LLRs: no tolerance.  The
 path a tie-breaking Viterbi returns is, of all paths of the largest metric, the one whose inputs read from the last to the first are
 smallest (each merge prefers the older input 0), which is what tests/test_linkcode.py's brute force over all 2^K inputs compares.
+The LDPC-coded link.  Data channels of current OFDM systems run LDPC codes, and an iterative decoder reacts to LLR quality (a cliff,
+and a sensitivity to mis-scaled LLRs) unlike a Viterbi decoder.  ``LdpcConfig``, ``ldpc_base``, ``ldpc_encode``,
+``link_ldpc_encode_host`` / ``ldpc_decode_host`` / ``link_ldpc_host`` (integer NumPy), ``aft_link_ldpc_f32`` (csrc/k_linkldpc.hip,
+through ``hip_ops.LinkLdpcPlan``), ``LdpcBlockErrorAccumulator`` and ``evaluation.get_link_bler`` are the same surface for a
+quasi-cyclic LDPC code with a layered offset min-sum decoder.  Position on the link, hash streams, scrambler and quantiser are the
+convolutional code's::
+
+    code         quasi-cyclic, lifting Z = 64.  Base matrix of mb rows and nb columns, 3 <= mb <= 16, mb < nb <= 32, kb = nb - mb;
+                 n = 64 nb coded and K = 64 kb information bits.  An entry is -1 (no block) or a shift s in 0 .. 63: block (i, j)
+                 with shift s has, in its row r, its one at column (r + s) mod 64 -- check 64 i + r contains variable
+                 64 j + ((r + s) mod 64)
+    parity part  columns kb .. nb-1, fixed by structure, mid = mb // 2: column kb has shift 1 in rows 0 and mb-1 and shift 0 in row
+                 mid; column kb + 1 + i (i = 0 .. mb-2) has shift 0 in rows i and i + 1
+    information  an int32 table [mb][kb]: every entry in -1 .. 63, every column with at least one entry, at most 160 entries
+    part         (AFT_LINK_LDPC_MAX_EDGES) over the whole base matrix, parity part included.  The default is ldpc_base(mb, nb, seed):
+                 offsets o = (0, 1, mb//2 - 1) if mb >= 8 else (0, 1, 2); for j = 0 .. kb-1 and t = 0, 1, 2 in that order the row is
+                 r = (j + o[t]) mod mb, h = splitmix64(seed ^ (9 << 32 | 4 j + t)) >> 58 (stream 9), and the shift is (h + c) mod 64
+                 for the smallest c in 0 .. 63 that closes no 4-cycle with what is already placed (the parity columns, information
+                 columns < j, column j's earlier t): v is refused when for an already-placed row r2 of column j and another column
+                 b with entries in both r and r2, (v - S[r2][j]) mod 64 == (S[r][b] - S[r2][b]) mod 64.  No c: ValueError
+    rates        "1/2" = (12, 24), "2/3" = (8, 24), "3/4" = (6, 24): n = 1536; or any (mb, nb)
+    encoding     u_j the 64 bits of block column j, rot(x, s)[r] = x[(r + s) mod 64]:  lam_i = XOR_j rot(u_j, S[i][j]) over the row's
+                 information blocks;  p_0 = XOR_i lam_i;  p_1 = lam_0 ^ rot(p_0, 1);  p_{i+1} = lam_i ^ p_i ^ (p_0 if i == mid else 0)
+                 for i = 1 .. mb-2;  the codeword is u | p_0 | .. | p_{mb-1}
+    position     B = N // n blocks (B = 0 is refused), U = B n, interleaver j = (b n + i) stride mod U with the same default stride,
+                 u[b][t] = word(kf, stream 8, b K + t) >> 63, scrambler s_p = w_j ^ c_p,
+                 z_p = clamp(rint(float32((1 - 2 s_p) llr_j qgain)), -127, 127), NaN gives 0
+    decoder      layered offset min-sum, integer.  Posterior L_v = z_v, messages R = 0; offset beta in 0 .. 127 (default 4),
+                 max_iters I in 1 .. 255 (default 20).  For iteration 1 .. I and layer i = 0 .. mb-1 -- its edges e the nonzero base
+                 columns in increasing order, parity included -- each of the layer's 64 rows on its own:
+                   Q_e = L_v(e) - R_e (all Q of a layer before any update);  neg_e = Q_e < 0;  tot = XOR_e neg_e;
+                   m1 = min_e |Q_e| at the lowest e that attains it, a;  m2 = min_{e != a} |Q_e|;
+                   mag_e = min(max((m2 if e == a else m1) - beta, 0), 127);  R_e = -mag_e if tot ^ neg_e else +mag_e;
+                   L_v(e) = clamp(Q_e + R_e, -8191, 8191)
+                 After each whole iteration x_v = [L_v < 0]; the decoder stops when all 64 mb checks hold, or after I iterations.
+                 The decoded bits are x_0 .. x_{K-1}
+    result       (information-bit errors, blocks with any error, iterations run summed over the B blocks) per frame
+
+Messages fit int8 and posteriors int16.  Rows of one layer share no variable (a block column holds at most one block per layer, and
+a circulant is a permutation), so the order of a layer's rows does not matter: tests/test_linkldpc.py decodes row by row over the
+expanded matrix and compares for equality.
 """
 from __future__ import annotations
 
@@ -104,8 +145,8 @@ import numpy as np
 import torch
 
 from . import _abi
-from .chansim import (STREAM_CODE_BITS, STREAM_DATA_BITS, STREAM_DATA_NOISE_ANGLE, STREAM_DATA_NOISE_RADIUS, ChannelSimConfig, frame_keys,
-                      words)
+from .chansim import (STREAM_CODE_BITS, STREAM_DATA_BITS, STREAM_DATA_NOISE_ANGLE, STREAM_DATA_NOISE_RADIUS, STREAM_LDPC_SHIFTS,
+                      ChannelSimConfig, frame_keys, words)
 from .synth import _splitmix64
 
 BITS_PER_SYMBOL = (2, 4, 6, 8)
@@ -681,6 +722,19 @@ def viterbi_host(z: np.ndarray) -> np.ndarray:
     return out.reshape(*lead, steps)
 
 
+def _decoder_input(code, keys: np.ndarray, llr: np.ndarray, sent: np.ndarray) -> np.ndarray:
+    """int32 ``[n, B, coded_bits]``: the LLRs ``[n, S T, m]`` at the interleaver's positions, descrambled with the codewords ``sent``
+    and quantised (a ``CodeConfig`` or an ``LdpcConfig``: the position on the link is the same)."""
+    cfg = code.link
+    m = cfg.bits_per_symbol
+    j = code.positions()                                                       # [B, n]
+    q, k = np.flatnonzero(cfg.data_mask)[j // m], j % m                        # the grid element and the bit of its word
+    w = (words(keys[:, None, None], STREAM_DATA_BITS, q[None].astype(np.uint64)) >> (np.uint64(63) - k[None].astype(np.uint64))) & np.uint64(1)
+    scrambler = w.astype(np.uint8) ^ sent
+    at = llr[:, q, k]                                                          # [n, B, coded_bits]
+    return quantise(np.where(scrambler == 1, -at, at), code.qgain)
+
+
 def link_decode_host(code: CodeConfig, keys, llr) -> Tuple[np.ndarray, np.ndarray]:
     """The coded link's definition on ``llr`` ``[n, S, T, m]``, taken as the float32 numbers it rounds to: ``(counts int64 [n, 2] =
     (information-bit errors, blocks with any error) per frame, bits uint8 [n, B, K] the decoded information bits)``.  Needs no library."""
@@ -692,12 +746,7 @@ def link_decode_host(code: CodeConfig, keys, llr) -> Tuple[np.ndarray, np.ndarra
         raise ValueError(f"Expected llr of shape ({nf}, {S}, {T}, {m}), got {llr.shape}")
     llr = llr.astype(np.float32).reshape(nf, S * T, m)
     info, sent = link_encode_host(code, keys)
-    j = code.positions()                                                       # [B, n]
-    q, k = np.flatnonzero(cfg.data_mask)[j // m], j % m                        # the grid element and the bit of its word
-    w = (words(keys[:, None, None], STREAM_DATA_BITS, q[None].astype(np.uint64)) >> (np.uint64(63) - k[None].astype(np.uint64))) & np.uint64(1)
-    scrambler = w.astype(np.uint8) ^ sent
-    at = llr[:, q, k]                                                          # [n, B, coded_bits]
-    z = quantise(np.where(scrambler == 1, -at, at), code.qgain)
+    z = _decoder_input(code, keys, llr, sent)
     full = np.zeros((nf, code.blocks, code.steps, 2), dtype=np.int32)
     full[..., keep_mask(code.info_bits, code.rate)] = z
     bits = viterbi_host(full)[..., :code.info_bits]
@@ -768,3 +817,333 @@ class BlockErrorAccumulator(_FrameSweep):
         if frames <= 0:
             return 0.0
         return (frames * self.code.blocks - block_errors) * self.code.info_bits / (frames * self.cfg.data_elements)
+
+
+# ---- the LDPC-coded link (module docstring, "the LDPC-coded link"): integer NumPy, mirrored by csrc/k_linkldpc.hip ----
+
+LDPC_Z = _abi.AFT_LINK_LDPC_Z
+LDPC_MAX_EDGES = _abi.AFT_LINK_LDPC_MAX_EDGES
+LDPC_MIN_ROWS, LDPC_MAX_ROWS, LDPC_MAX_COLS = 3, 16, 32
+LDPC_RATES = {"1/2": (12, 24), "2/3": (8, 24), "3/4": (6, 24)}
+LDPC_L_MAX, LDPC_R_MAX = 8191, 127                           # posteriors fit int16, messages int8
+
+
+def _ldpc_shape(mb, nb) -> Tuple[int, int]:
+    for name, v in (("mb", mb), ("nb", nb)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name} = {v!r}: an integer")
+    mb, nb = int(mb), int(nb)
+    if not LDPC_MIN_ROWS <= mb <= LDPC_MAX_ROWS:
+        raise ValueError(f"mb = {mb}: a base matrix has {LDPC_MIN_ROWS} .. {LDPC_MAX_ROWS} rows")
+    if not mb < nb <= LDPC_MAX_COLS:
+        raise ValueError(f"nb = {nb}: a base matrix of {mb} rows has {mb + 1} .. {LDPC_MAX_COLS} columns")
+    return mb, nb
+
+
+def ldpc_parity_part(mb: int) -> np.ndarray:
+    """int32 ``[mb, mb]``: the parity columns ``kb .. nb-1`` of every base matrix of ``mb`` rows (-1: no block)."""
+    P = np.full((mb, mb), -1, dtype=np.int32)
+    P[0, 0] = P[mb - 1, 0] = 1
+    P[mb // 2, 0] = 0
+    for i in range(mb - 1):
+        P[i, 1 + i] = P[i + 1, 1 + i] = 0
+    return P
+
+
+def ldpc_base(mb: int, nb: int, seed: int = 0) -> np.ndarray:
+    """int32 ``[mb, nb - mb]``: the default information part (module docstring): three entries per column, their shifts from stream 9
+    of the hash of ``seed``, moved on to the first value that closes no 4-cycle."""
+    mb, nb = _ldpc_shape(mb, nb)
+    kb = nb - mb
+    S = np.full((mb, nb), -1, dtype=np.int64)
+    S[:, kb:] = ldpc_parity_part(mb)
+    offsets = (0, 1, mb // 2 - 1) if mb >= 8 else (0, 1, 2)
+    key = np.array([int(seed) & 0xFFFFFFFFFFFFFFFF], dtype=np.uint64)
+    for j in range(kb):
+        for t in range(3):
+            r = (j + offsets[t]) % mb
+            h = int(words(key, STREAM_LDPC_SHIFTS, 4 * j + t)[0] >> np.uint64(58))
+            refused = set()
+            for r2 in range(mb):
+                if r2 == r or S[r2, j] < 0:
+                    continue
+                for b in range(nb):
+                    if b != j and S[r, b] >= 0 and S[r2, b] >= 0:
+                        refused.add(int(S[r2, j] + S[r, b] - S[r2, b]) % LDPC_Z)
+            for c in range(LDPC_Z):
+                if (h + c) % LDPC_Z not in refused:
+                    S[r, j] = (h + c) % LDPC_Z
+                    break
+            else:
+                raise ValueError(f"ldpc_base({mb}, {nb}, seed={seed}): no shift without a 4-cycle at row {r} of column {j}")
+    return S[:, :kb].astype(np.int32)
+
+
+@dataclass(frozen=True)
+class LdpcConfig:
+    """A quasi-cyclic LDPC code (lifting 64) on a link: ``rate`` one of ``LDPC_RATES`` or ``(mb, nb)``, ``shifts`` the information part
+    int ``[mb][nb - mb]`` (None: ``ldpc_base(mb, nb, seed)``), the interleaver's ``stride`` (None: the golden-section default), the
+    quantiser's gain, the min-sum ``offset`` and ``max_iters``.  Derives what ``CodeConfig`` derives, plus ``base()`` and ``edges``;
+    refuses what ``aft_link_ldpc_f32`` refuses."""
+    link: LinkConfig = field(default_factory=LinkConfig)
+    rate: Union[str, Tuple[int, int]] = "1/2"
+    shifts: Optional[tuple] = None
+    seed: int = 0
+    stride: Optional[int] = None
+    qgain: float = 8.0
+    offset: int = 4
+    max_iters: int = 20
+
+    def __post_init__(self) -> None:
+        if not isinstance(self.link, LinkConfig):
+            raise ValueError(f"LdpcConfig needs a LinkConfig (got {type(self.link).__name__})")
+        if isinstance(self.rate, str):
+            if self.rate not in LDPC_RATES:
+                raise ValueError(f"rate = {self.rate!r}: one of {tuple(LDPC_RATES)}, or (mb, nb)")
+            mb, nb = LDPC_RATES[self.rate]
+        else:
+            try:
+                mb, nb = self.rate
+            except (TypeError, ValueError):
+                raise ValueError(f"rate = {self.rate!r}: one of {tuple(LDPC_RATES)}, or (mb, nb)") from None
+            mb, nb = _ldpc_shape(mb, nb)
+            object.__setattr__(self, "rate", (mb, nb))
+        object.__setattr__(self, "_shape", (mb, nb))
+        kb = nb - mb
+        if self.shifts is None:
+            table = ldpc_base(mb, nb, self.seed)
+        else:
+            table = np.asarray(self.shifts)
+            if table.shape != (mb, kb) or table.dtype.kind not in "iu":
+                raise ValueError(f"shifts: an integer table [{mb}][{kb}], got {table.dtype} {table.shape}")
+            if table.size and (table.min() < -1 or table.max() >= LDPC_Z):
+                raise ValueError(f"shifts: every entry is -1 (no block) or a shift in 0 .. {LDPC_Z - 1}")
+            empty = np.flatnonzero((table >= 0).sum(axis=0) == 0)
+            if empty.size:
+                raise ValueError(f"shifts: base column {int(empty[0])} has no entry")
+        object.__setattr__(self, "shifts", tuple(tuple(int(v) for v in row) for row in table))
+        if self.edges > LDPC_MAX_EDGES:
+            raise ValueError(f"shifts: {self.edges} entries in the base matrix, parity part included; at most {LDPC_MAX_EDGES}")
+        if self.blocks == 0:
+            raise ValueError(f"a frame carries {self.link.bits_per_frame} bits, fewer than the {self.coded_bits} coded bits of one block")
+        if self.info_bits_per_frame > 1 << 31:
+            raise ValueError(f"{self.blocks} blocks of {self.info_bits} information bits: more than 2^31, where the hash's index and the "
+                             f"int32 counts end")
+        U = self.used_bits
+        a = default_stride(U) if self.stride is None else self.stride
+        if isinstance(a, bool) or not isinstance(a, (int, np.integer)) or not 1 <= int(a) < U:
+            raise ValueError(f"stride = {a!r}: an integer in [1, {U})")
+        if math.gcd(int(a), U) != 1:
+            raise ValueError(f"stride = {a} is not coprime to the {U} used bits")
+        object.__setattr__(self, "stride", int(a))
+        with np.errstate(over="ignore", under="ignore"):
+            g = np.float32(self.qgain)
+        if not (np.isfinite(g) and g > 0):
+            raise ValueError(f"qgain = {self.qgain!r}: a finite positive float32")
+        object.__setattr__(self, "qgain", float(g))
+        for name, lo, hi in (("offset", 0, LDPC_R_MAX), ("max_iters", 1, 255)):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+                raise ValueError(f"{name} = {v!r}: an integer in {lo} .. {hi}")
+            object.__setattr__(self, name, int(v))
+
+    @property
+    def base_rows(self) -> int:
+        return self._shape[0]
+
+    @property
+    def base_cols(self) -> int:
+        return self._shape[1]
+
+    @property
+    def info_bits(self) -> int:
+        return LDPC_Z * (self.base_cols - self.base_rows)
+
+    @property
+    def coded_bits(self) -> int:
+        return LDPC_Z * self.base_cols
+
+    @property
+    def blocks(self) -> int:
+        return self.link.bits_per_frame // self.coded_bits
+
+    @property
+    def used_bits(self) -> int:
+        return self.blocks * self.coded_bits
+
+    @property
+    def stride_inverse(self) -> int:
+        return pow(self.stride, -1, self.used_bits)
+
+    @property
+    def info_bits_per_frame(self) -> int:
+        return self.blocks * self.info_bits
+
+    @property
+    def edges(self) -> int:
+        """The entries of the whole base matrix, parity part included."""
+        return int((self.base() >= 0).sum())
+
+    positions = CodeConfig.positions
+
+    def base(self) -> np.ndarray:
+        """int32 ``[mb, nb]``: the information part beside the parity part."""
+        mb, nb = self._shape
+        return np.concatenate([np.asarray(self.shifts, dtype=np.int32).reshape(mb, nb - mb), ldpc_parity_part(mb)], axis=1)
+
+    def layers(self):
+        """Per layer ``(cols int64 [d], var int64 [d, 64])``: its edges in increasing column order and, for each of its 64 rows
+        ``r``, the variable ``64 j + ((r + s) mod 64)`` of every edge."""
+        out, r = [], np.arange(LDPC_Z)
+        for row in self.base():
+            cols = np.flatnonzero(row >= 0)
+            out.append((cols, LDPC_Z * cols[:, None] + (r[None, :] + row[cols][:, None]) % LDPC_Z))
+        return out
+
+
+def ldpc_encode(cfg: LdpcConfig, u) -> np.ndarray:
+    """The codewords uint8 ``[..., n]`` of the information bits ``u`` ``[..., K]`` (0 / 1): ``u | p_0 | .. | p_{mb-1}``."""
+    u = np.asarray(u).astype(np.uint8)
+    mb, nb = cfg.base_rows, cfg.base_cols
+    kb, mid = nb - mb, mb // 2
+    if u.shape[-1] != cfg.info_bits:
+        raise ValueError(f"Expected {cfg.info_bits} information bits on the last axis, got {u.shape}")
+    blocks = u.reshape(*u.shape[:-1], kb, LDPC_Z)
+    rot = lambda x, s: np.roll(x, -int(s), axis=-1)  # noqa: E731  rot(x, s)[r] = x[(r + s) mod 64]
+    lam = np.zeros((*u.shape[:-1], mb, LDPC_Z), dtype=np.uint8)
+    for i, row in enumerate(cfg.shifts):
+        for j, s in enumerate(row):
+            if s >= 0:
+                lam[..., i, :] ^= rot(blocks[..., j, :], s)
+    p = np.zeros_like(lam)
+    p[..., 0, :] = np.bitwise_xor.reduce(lam, axis=-2)
+    p[..., 1, :] = lam[..., 0, :] ^ rot(p[..., 0, :], 1)
+    for i in range(1, mb - 1):
+        p[..., i + 1, :] = lam[..., i, :] ^ p[..., i, :] ^ (p[..., 0, :] if i == mid else 0)
+    return np.concatenate([u, p.reshape(*u.shape[:-1], mb * LDPC_Z)], axis=-1)
+
+
+def link_ldpc_encode_host(cfg: LdpcConfig, keys) -> Tuple[np.ndarray, np.ndarray]:
+    """The information bits uint8 ``[n, B, K]`` and the codewords uint8 ``[n, B, coded_bits]`` of the frames with ``keys``."""
+    keys = _keys64(keys)
+    B, K = cfg.blocks, cfg.info_bits
+    index = np.arange(B * K, dtype=np.uint64).reshape(1, B, K)
+    info = (words(keys[:, None, None], STREAM_CODE_BITS, index) >> np.uint64(63)).astype(np.uint8)
+    return info, ldpc_encode(cfg, info)
+
+
+def ldpc_syndrome_ok(cfg: LdpcConfig, x: np.ndarray) -> np.ndarray:
+    """bool ``[...]``: whether the hard bits ``x`` ``[..., n]`` satisfy all ``64 mb`` checks."""
+    x = np.asarray(x).astype(bool)
+    ok = np.ones(x.shape[:-1], dtype=bool)
+    for _, var in cfg.layers():
+        ok &= ~np.logical_xor.reduce(x[..., var], axis=-2).any(axis=-1)
+    return ok
+
+
+def ldpc_decode_host(cfg: LdpcConfig, z) -> Tuple[np.ndarray, np.ndarray]:
+    """The decoder of the definition on quantised inputs ``z`` int ``[..., n]``: ``(bits uint8 [..., K], iterations int64 [...])``.
+    Vectorised over the blocks and over the 64 rows of a layer; a block that has stopped is left alone."""
+    z = np.asarray(z, dtype=np.int32)
+    if z.shape[-1] != cfg.coded_bits:
+        raise ValueError(f"Expected {cfg.coded_bits} inputs on the last axis, got {z.shape}")
+    lead = z.shape[:-1]
+    L = z.reshape(-1, cfg.coded_bits).copy()
+    layers = cfg.layers()
+    msg = [np.zeros((L.shape[0], *var.shape), dtype=np.int32) for _, var in layers]
+    iterations = np.zeros(L.shape[0], dtype=np.int64)
+    active = np.arange(L.shape[0])
+    beta = cfg.offset
+    for it in range(1, cfg.max_iters + 1):
+        if active.size == 0:
+            break
+        La = L[active]
+        for i, (cols, var) in enumerate(layers):
+            Q = La[:, var] - msg[i][active]                                    # [A, d, 64]: all Q of the layer before any update
+            neg, mag = Q < 0, np.abs(Q)
+            tot = np.logical_xor.reduce(neg, axis=1, keepdims=True)
+            a = mag.argmin(axis=1)[:, None, :]                                 # the lowest e that attains the minimum
+            m1 = np.take_along_axis(mag, a, axis=1)
+            rest = mag.copy()
+            np.put_along_axis(rest, a, np.iinfo(np.int32).max, axis=1)
+            m2 = rest.min(axis=1, keepdims=True)
+            is_a = np.arange(len(cols))[None, :, None] == a
+            out = np.clip(np.where(is_a, m2, m1) - beta, 0, LDPC_R_MAX)
+            R = np.where(tot ^ neg, -out, out).astype(np.int32)
+            La[:, var] = np.clip(Q + R, -LDPC_L_MAX, LDPC_L_MAX)
+            msg[i][active] = R
+        L[active] = La
+        iterations[active] = it
+        active = active[~ldpc_syndrome_ok(cfg, La < 0)]
+    bits = (L[:, :cfg.info_bits] < 0).astype(np.uint8)
+    return bits.reshape(*lead, cfg.info_bits), iterations.reshape(lead)
+
+
+def link_ldpc_host(cfg: LdpcConfig, keys, llr) -> Tuple[np.ndarray, np.ndarray]:
+    """The LDPC-coded link's definition on ``llr`` ``[n, S, T, m]``, taken as the float32 numbers it rounds to: ``(counts int64 [n, 3] =
+    (information-bit errors, blocks with any error, iterations summed over the blocks) per frame, bits uint8 [n, B, K])``.  Needs no
+    library."""
+    if not isinstance(cfg, LdpcConfig):
+        raise ValueError(f"link_ldpc_host needs an LdpcConfig (got {type(cfg).__name__})")
+    keys = _keys64(keys)
+    (S, T), m, nf = cfg.link.sim.ofdm, cfg.link.bits_per_symbol, len(keys)
+    llr = np.asarray(llr)
+    if llr.shape != (nf, S, T, m):
+        raise ValueError(f"Expected llr of shape ({nf}, {S}, {T}, {m}), got {llr.shape}")
+    llr = llr.astype(np.float32).reshape(nf, S * T, m)
+    info, sent = link_ldpc_encode_host(cfg, keys)
+    bits, iterations = ldpc_decode_host(cfg, _decoder_input(cfg, keys, llr, sent))
+    wrong = bits != info
+    counts = np.stack([wrong.sum(axis=(1, 2)), wrong.any(axis=2).sum(axis=1), iterations.sum(axis=1)], axis=1).astype(np.int64)
+    return counts, bits
+
+
+class LdpcBlockErrorAccumulator(BlockErrorAccumulator):
+    """``BlockErrorAccumulator`` for an ``LdpcConfig``: the same ``update`` surface and results, an int64 ``[3]`` device tensor
+    (information-bit errors, block errors, iterations) and ``result_iterations``, the mean iterations per block.  On a HIP device a
+    batch is the launch of ``aft_link_soft_f32`` with its LLR output, the launch of ``aft_link_ldpc_f32`` on that tensor and one
+    integer add; nothing synchronises.  On a CPU device the host definitions run.  Each result is one read and, with several ranks,
+    one all-gather of four float64."""
+
+    def __init__(self, code: LdpcConfig, device, seed: int = 0, err_var: float = 0.0) -> None:
+        if not isinstance(code, LdpcConfig):
+            raise ValueError(f"LdpcBlockErrorAccumulator needs an LdpcConfig (got {type(code).__name__})")
+        self._open(code.link, device, seed, "LinkSoftPlan")
+        self.code = code
+        self.err_var = float(err_var)
+        if not self.err_var >= 0.0:
+            raise ValueError(f"err_var = {err_var!r}: a variance, at least 0")
+        self.errors = torch.zeros(3, dtype=torch.int64, device=self.device)     # information-bit errors, block errors, iterations
+        self._decode = self._one = None
+        if self._plan is not None:
+            from . import hip_ops
+            self._decode = hip_ops.LinkLdpcPlan(code, self.device)
+            self._one = torch.ones(1, dtype=torch.float32, device=self.device)
+        self._of_snr = (_SIGMA_OF_SNR, _SCALE_OF_SNR(self.err_var))
+
+    def update(self, est: Optional[torch.Tensor], ideal: torch.Tensor, meta: Optional[tuple] = None, *, frame_ids=None,
+               snr_db=None) -> None:
+        ops = self._operands(est, ideal, meta, frame_ids, snr_db, self._of_snr)
+        if ops is None:
+            return
+        b, H, E, keys, (sigma, scale) = ops
+        if self._plan is None:
+            llr = link_llrs_host(self.cfg, keys, H, E, sigma, scale)[1]
+            self.errors += torch.from_numpy(link_ldpc_host(self.code, keys, llr)[0].sum(axis=0))
+        else:
+            llr = self._launch(H, E, keys, sigma, scale, self._one, want_llr=True)[1]
+            self.errors += self._launch(llr, keys, plan=self._decode)[0].sum(dim=0, dtype=torch.int64)
+        self.frames += b
+
+    def _read4(self, group) -> Tuple[float, float, float, float]:
+        frames = torch.tensor([float(self.frames)], dtype=torch.float64, device=self.device)
+        return tuple(self._all_ranks(torch.cat([self.errors.to(torch.float64), frames]), group))
+
+    def _read(self, group) -> Tuple[float, float, float]:
+        bit_errors, block_errors, _, frames = self._read4(group)
+        return bit_errors, block_errors, frames
+
+    def result_iterations(self, group=None) -> float:
+        """Mean decoder iterations per block over all ranks; 0.0 for an empty sweep."""
+        _, _, iterations, frames = self._read4(group)
+        return iterations / (frames * self.code.blocks) if frames > 0 else 0.0

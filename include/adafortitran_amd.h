@@ -449,6 +449,49 @@ int aft_link_decode_f32(const aft_link *link, const float *llr /* [batch,S,T,m] 
                         int rate /* AFT_LINK_RATE_* */, unsigned long long stride, unsigned long long stride_inverse, float qgain,
                         int32_t *counts /* [batch][2] */, unsigned char *bits /* [batch,B,K] or NULL */, int batch, void *stream);
 
+/* ---- LDPC-coded link: a quasi-cyclic LDPC code and a layered min-sum decoder on those LLRs (adafortitran_amd/linksim.py holds the
+ * definition in full) ----
+ *
+ * The code sits on the link exactly where the convolutional code does, with its own n and K.
+ *   code        quasi-cyclic, lifting Z = 64.  Base matrix of mb = base_rows rows and nb = base_cols columns, 3 <= mb <= 16,
+ *               mb < nb <= 32, kb = nb - mb; n = 64 nb coded and K = 64 kb information bits.  An entry is -1 (no block) or a shift s in
+ *               0 .. 63: block (i, j) with shift s has, in its row r, its one at column (r + s) mod 64, so check 64 i + r contains
+ *               variable 64 j + ((r + s) mod 64)
+ *   parity part columns kb .. nb-1, fixed by structure, mid = mb / 2: column kb has shift 1 in rows 0 and mb-1 and shift 0 in row mid;
+ *               column kb + 1 + i (i = 0 .. mb-2) has shift 0 in rows i and i + 1
+ *   shifts      the information part, int32 [mb][kb]: every entry in -1 .. 63, every column with at least one entry, at most
+ *               AFT_LINK_LDPC_MAX_EDGES entries in the whole base matrix, parity part included
+ *   encoding    u_j the 64 bits of block column j, rot(x, s)[r] = x[(r + s) mod 64]: lam_i = XOR_j rot(u_j, S[i][j]) over the row's
+ *               information blocks; p_0 = XOR_i lam_i; p_1 = lam_0 ^ rot(p_0, 1); p_{i+1} = lam_i ^ p_i ^ (p_0 if i == mid else 0)
+ *               for i = 1 .. mb-2; the codeword is u | p_0 | .. | p_{mb-1}
+ *   position    blocks, filler, interleaver, information bits (stream 8), scrambler and quantiser as for the coded link above
+ *   decoder     layered offset min-sum, integer: posterior L_v = z_v, messages R = 0.  For iteration 1 .. max_iters and layer
+ *               i = 0 .. mb-1 (its edges e the base columns with an entry, increasing, parity included), each of its 64 rows on its own:
+ *               Q_e = L_v(e) - R_e (all Q of a layer before any update); neg_e = Q_e < 0; tot = XOR_e neg_e; m1 = min_e |Q_e| at the
+ *               lowest e that attains it, a; m2 = min_{e != a} |Q_e|; mag_e = min(max((m2 if e == a else m1) - offset, 0), 127);
+ *               R_e = -mag_e if tot ^ neg_e else +mag_e; L_v(e) = clamp(Q_e + R_e, -8191, 8191).  After each whole iteration
+ *               x_v = [L_v < 0]; the decoder stops when all 64 mb checks hold, or after max_iters.  The decoded bits are x_0 .. x_{K-1}
+ *   counts      (information-bit errors over the B K bits, blocks with any error, iterations run summed over the B blocks) per frame
+ * Everything after the quantiser is integer: a host evaluation of this definition agrees bit for bit. */
+#define AFT_LINK_LDPC_Z 64
+#define AFT_LINK_LDPC_MAX_EDGES 160   /* entries of a base matrix: their int8 messages are 10 KiB of LDS per code block */
+
+/* One launch, one workgroup per frame, one wave per code block and one lane per row of a circulant: counts int32 [batch][3] and, when
+ * bits is not NULL, the decoded information bits uint8 [batch, B, K] (both device memory) from llr float32 [batch, S, T, m] (device
+ * memory; what aft_link_soft_f32 writes) and keys uint64 [batch] (any device-addressable memory, pinned host memory included).
+ * `link` and `shifts` (HOST memory) are read during the call only; the base matrix travels to the kernel by value.  Every element of
+ * counts and bits is written (no initialisation needed); no atomics; no workspace; nothing is synchronised; a frame's outputs depend
+ * neither on batch, nor on its position in it, nor on the run, nor on whether bits is written.
+ * Nothing is launched on AFT_ERR_ARG (a NULL link / llr / keys / shifts / counts; keys not 8-byte or llr / shifts / counts not 4-byte
+ * aligned; batch < 1; qgain not finite and positive) and AFT_ERR_SHAPE (what aft_link_errors_f32 refuses; base_rows outside 3 .. 16;
+ * base_cols outside base_rows + 1 .. 32; offset outside 0 .. 127; max_iters outside 1 .. 255; a shift outside -1 .. 63; an information
+ * column without an entry; more than AFT_LINK_LDPC_MAX_EDGES entries; B = 0; B K above 2^31; a stride or stride_inverse that
+ * aft_link_decode_f32 would refuse for this U). */
+int aft_link_ldpc_f32(const aft_link *link, const float *llr /* [batch,S,T,m] */, const unsigned long long *keys, int base_rows,
+                      int base_cols, const int32_t *shifts /* HOST, [base_rows][base_cols - base_rows] */, unsigned long long stride,
+                      unsigned long long stride_inverse, float qgain, int offset, int max_iters, int32_t *counts /* [batch][3] */,
+                      unsigned char *bits /* [batch,B,K] or NULL */, int batch, void *stream);
+
 /* ---- training path of the encoder ---- */
 
 /* Gradients of one nn.TransformerEncoderLayer: same fields and shapes as aft_layer_weights,
