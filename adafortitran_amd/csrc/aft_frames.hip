@@ -1,5 +1,6 @@
 // aft_frames.hip -- the C ABI of the one-workgroup-per-frame kernels: the channel simulator, the LMMSE baseline and the link-level error
-// count.  Their structs start with the same four fields and two carry the pilot positions, so those checks are written once.
+// counts (single-branch, with receive diversity, coded).  Their structs start with the same four fields and two carry the pilot
+// positions, so those checks are written once.
 #include "aft_internal.h"
 
 using namespace aft;
@@ -261,6 +262,25 @@ int aft_link_ldpc_f32(const aft_link *link, const float *llr, const unsigned lon
     hipError_t e = launch_link_ldpc(*link, llr, keys, base_rows, base_cols, shifts, (unsigned)blocks, stride, qgain, offset, max_iters,
                                     counts, bits, batch, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? AFT_OK : hip_fail("link_ldpc", e);
+}
+
+int aft_link_mrc_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys,
+                     const float *sigma, const float *rho, const float *scale, const float *factors, int n_factors, int branches,
+                     int32_t *counts, float *loss, float *llr, int batch, void *stream) {
+    const char *who = "link mrc";
+    AFT_REQUIRE(link && ideal && est && keys && sigma && rho && scale && factors && counts && loss, "link mrc: NULL pointer argument");
+    AFT_REQUIRE(aligned(8, ideal, est, keys), "link mrc: ideal, est and keys must be 8-byte aligned");
+    AFT_REQUIRE(aligned(4, sigma, rho, scale, factors, counts, loss, llr),
+                "link mrc: sigma, rho, scale, factors, counts, loss and llr must be 4-byte aligned");
+    AFT_REQUIRE(batch >= 1, "link mrc: batch must be at least 1 (got %d)", batch);
+    AFT_REQUIRE(n_factors >= 1 && n_factors <= 8, "link mrc: n_factors = %d is outside 1..8", n_factors);
+    if (!within(who, "branches", branches, 1, AFT_LINK_MAX_BRANCHES)) return AFT_ERR_SHAPE;
+    AFT_REQUIRE(batch % branches == 0, "link mrc: batch = %d is not a multiple of branches = %d", batch, branches);
+    const int rc = check_link(who, *link);
+    if (rc != AFT_OK) return rc;
+    hipError_t e = launch_link_mrc(*link, ideal, est, keys, sigma, rho, scale, factors, n_factors, branches, counts, loss, llr, batch,
+                                   static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? AFT_OK : hip_fail("link_mrc", e);
 }
 
 }  // extern "C"

@@ -21,12 +21,10 @@
 // scale (min1 - min0) and, per factor, softplus of the LLR against its sent bit.  The K float sums stay in registers and are reduced in
 // a fixed order (shuffles, then the four waves through LDS); a thread takes the same element pairs whichever load form runs, so a
 // frame's loss depends neither on the batch, nor on the run, nor on the alignment of the bases, nor on whether the LLRs are stored.
-#include "frame_device.h"
+#include "link_device.h"
 
 namespace aft {
 namespace {
-
-constexpr int kLinkWaves = kFrameThreads / kWave;
 
 struct LinkArgs {
     aft_link c;
@@ -39,56 +37,9 @@ struct LinkArgs {
     int wide;                   // 1: 16-byte loads of ideal and est
 };
 
-// v in sorted[0 .. n): n <= 64
-__device__ __forceinline__ bool link_listed(const int *sorted, int n, int v) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (sorted[mid] < v) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo < n && sorted[lo] == v;
-}
-
-// level index of a Gray code of at most four bits: k ^ (k >> 1) = g
-__device__ __forceinline__ unsigned gray_level(unsigned g) {
-    g ^= g >> 1;
-    return g ^ (g >> 2);
-}
-
-// #{b in 1 .. L-1 : comp >= beta_b p}, beta_b p = (b - L/2) (2 d p): `step` is float(2 d p)
-template <int L>
-__device__ __forceinline__ unsigned decide(float comp, float step) {
-    unsigned k = 0;
-#pragma unroll
-    for (int b = 1; b < L; ++b) k += comp >= (float)(b - L / 2) * step ? 1u : 0u;
-    return k;
-}
-
 struct LinkCounts {
     int bits, symbols;
 };
-
-// What both kernels do first with a data element: the three words of the hash, the sent Gray codes, y = H x + noise, c = y conj(E) and
-// p = |E|^2.  Written once, so the hard and the soft kernel see the same bits of c and p.  M = bits per symbol.
-struct LinkFront {
-    unsigned gi, gq;            // the sent Gray codes of the I and the Q axis
-    float cr, ci, p;
-};
-
-template <int M>
-__device__ __forceinline__ LinkFront link_front(float d, unsigned long long kf, float sigma, unsigned q, float2 h, float2 e) {
-    constexpr int half = M / 2, L = 1 << half;
-    const unsigned w = (unsigned)(frame_word(kf, kStreamDataBits, q) >> (64 - M));
-    const unsigned gi = w >> half, gq = w & (unsigned)(L - 1);
-    const float xr = d * (float)(2 * (int)gray_level(gi) - (L - 1)), xi = d * (float)(2 * (int)gray_level(gq) - (L - 1));
-    const FrameNoise nz = frame_noise(kf, kStreamDataNoiseRadius, kStreamDataNoiseAngle, q, sigma);
-    const float yr = fmaf(nz.r, nz.c, fmaf(h.x, xr, -(h.y * xi)));
-    const float yi = fmaf(nz.r, nz.s, fmaf(h.x, xi, h.y * xr));
-    const float cr = fmaf(yr, e.x, yi * e.y);                   // y conj(E)
-    const float ci = fmaf(yi, e.x, -(yr * e.y));
-    return LinkFront{gi, gq, cr, ci, fmaf(e.x, e.x, e.y * e.y)};
-}
 
 // one instantiation per modulation order, so the boundary loops unroll
 template <int M>
@@ -159,9 +110,6 @@ __global__ __launch_bounds__(kFrameThreads) void link_errors_kernel(const LinkAr
 
 // ---- the soft half: max-log LLRs and the loss the achievable rate is read from (linksim.py "the soft link") ----
 
-constexpr int kMaxFactors = 8;
-constexpr float kInvLn2 = 1.44269504088896341f;
-
 struct LinkSoftArgs {
     aft_link c;
     const float2 *ideal, *est;
@@ -175,37 +123,6 @@ struct LinkSoftArgs {
     int store;                  // bytes per store of llr: 16, 8 or 4
 };
 
-// One axis: the L metrics mu_k = a_k (a_k p - 2 comp) in registers, and per bit of the Gray code (MSB first) the scaled difference of
-// the two minima.  Two roundings per metric (the fused multiply-add and the product) and nothing contracted behind the source's back.
-template <int L>
-__device__ __forceinline__ void link_axis_llrs(float d, float comp, float p, float scale, float *out) {
-#pragma clang fp contract(off)
-    constexpr int half = L == 2 ? 1 : L == 4 ? 2 : L == 8 ? 3 : 4;
-    const float m2c = -2.f * comp;
-    float mu[L];
-#pragma unroll
-    for (int k = 0; k < L; ++k) {
-        const float ak = d * (float)(2 * k - (L - 1));
-        mu[k] = ak * fmaf(ak, p, m2c);
-    }
-#pragma unroll
-    for (int j = 0; j < half; ++j) {
-        float m0 = 0.f, m1 = 0.f;
-        bool have0 = false, have1 = false;                      // constants once the loop over k is unrolled
-#pragma unroll
-        for (int k = 0; k < L; ++k) {
-            if (((k ^ (k >> 1)) >> (half - 1 - j)) & 1) {
-                m1 = have1 ? fminf(m1, mu[k]) : mu[k];
-                have1 = true;
-            } else {
-                m0 = have0 ? fminf(m0, mu[k]) : mu[k];
-                have0 = true;
-            }
-        }
-        out[j] = scale * (m1 - m0);
-    }
-}
-
 // A data element: its M LLRs into v (I-axis bits first, MSB first: the order of the sent word) and, for each factor, the sum over its
 // bits of softplus(z) = max(z, 0) + log1p(exp(-|z|)) in nats, z = -(1 - 2 b) factor Lambda with b the sent bit.
 template <int M>
@@ -217,35 +134,7 @@ __device__ __forceinline__ void link_soft_element(const LinkSoftArgs &a, unsigne
     const LinkFront f = link_front<M>(a.d, kf, sigma, q, h, e);
     link_axis_llrs<L>(a.d, f.cr, f.p, scale, v);
     link_axis_llrs<L>(a.d, f.ci, f.p, scale, v + half);
-#pragma unroll
-    for (int j = 0; j < M; ++j) {
-        const unsigned sent = ((j < half ? f.gi : f.gq) >> (half - 1 - j % half)) & 1u;
-        const float against = sent ? v[j] : -v[j];              // -(1 - 2 b) Lambda
-#pragma unroll
-        for (int k = 0; k < kMaxFactors; ++k)
-            if (k < a.n_factors) {
-                const float z = fac[k] * against;
-                acc[k] += fmaxf(z, 0.f) + log1pf(expf(-fabsf(z)));
-            }
-    }
-}
-
-// the n leading floats of v (n = M or 2 M, a multiple of the store's width) to dst
-template <int M>
-__device__ __forceinline__ void link_store_llrs(float *dst, const float *v, int n, int bytes) {
-    if (bytes == 16) {
-#pragma unroll
-        for (int j = 0; j < 2 * M; j += 4)
-            if (j < n) *reinterpret_cast<f32x4 *>(dst + j) = f32x4{v[j], v[j + 1], v[j + 2], v[j + 3]};
-    } else if (bytes == 8) {
-#pragma unroll
-        for (int j = 0; j < 2 * M; j += 2)
-            if (j < n) *reinterpret_cast<float2 *>(dst + j) = make_float2(v[j], v[j + 1]);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 2 * M; ++j)
-            if (j < n) dst[j] = v[j];
-    }
+    link_soft_losses<M>(v, f.gi, f.gq, fac, a.n_factors, acc);
 }
 
 // A thread takes the element pairs (2 i, 2 i + 1), i = tid, tid + 256, ..., whichever load form runs: the order of a frame's float
@@ -366,10 +255,7 @@ hipError_t launch_link_soft(const aft_link &link, const float *ideal, const floa
     const int m = link.bits_per_symbol, L = 1 << (m / 2);
     a.d = (float)sqrt(3.0 / (2.0 * ((double)L * L - 1.0)));
     a.wide = wide_ok(link.num_symbols, ideal, est);
-    // an element's m floats start at a multiple of 4 m bytes: every pair of elements starts on 16 bytes when m is 4 or 8, or when the
-    // frames hold an even number of elements (then every pair is whole, too)
-    const uintptr_t at = reinterpret_cast<uintptr_t>(llr);
-    a.store = at % 16 == 0 && (m % 4 == 0 || elems % 2 == 0) ? 16 : at % 8 == 0 ? 8 : 4;
+    a.store = link_llr_store_bytes(llr, m, elems);
     const dim3 grid((unsigned)batch), block(kFrameThreads);
     switch (m) {
         case 2: hipLaunchKernelGGL(link_soft_kernel<2>, grid, block, 0, st, a); break;

@@ -1,0 +1,166 @@
+// What the link kernels share (k_link.hip, k_linkmrc.hip), each written once, so every kernel sees the same bits: the pilot lookup, the
+// Gray map, the hard decision, the front of a data element -- split into the sent word (one per transmission) and a branch (one per
+// receive antenna: y = H x + noise, c = y conj(E), p = |E|^2) --, an axis's max-log LLRs, the softplus step of the loss and the LLR
+// store.  adafortitran_amd/linksim.py holds the definitions.
+#pragma once
+
+#include "frame_device.h"
+
+namespace aft {
+namespace {
+
+constexpr int kLinkWaves = kFrameThreads / kWave;
+
+// v in sorted[0 .. n): n <= 64
+__device__ __forceinline__ bool link_listed(const int *sorted, int n, int v) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (sorted[mid] < v) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < n && sorted[lo] == v;
+}
+
+// level index of a Gray code of at most four bits: k ^ (k >> 1) = g
+__device__ __forceinline__ unsigned gray_level(unsigned g) {
+    g ^= g >> 1;
+    return g ^ (g >> 2);
+}
+
+// #{b in 1 .. L-1 : comp >= beta_b p}, beta_b p = (b - L/2) (2 d p): `step` is float(2 d p)
+template <int L>
+__device__ __forceinline__ unsigned decide(float comp, float step) {
+    unsigned k = 0;
+#pragma unroll
+    for (int b = 1; b < L; ++b) k += comp >= (float)(b - L / 2) * step ? 1u : 0u;
+    return k;
+}
+
+// The sent word of a data element: one word of the counter-based hash of the transmission's key, its two Gray codes and the symbol
+// x = xr + j xi.  M = bits per symbol.
+struct LinkSent {
+    unsigned gi, gq;            // the sent Gray codes of the I and the Q axis
+    float xr, xi;
+};
+
+template <int M>
+__device__ __forceinline__ LinkSent link_sent(float d, unsigned long long kf, unsigned q) {
+    constexpr int half = M / 2, L = 1 << half;
+    const unsigned w = (unsigned)(frame_word(kf, kStreamDataBits, q) >> (64 - M));
+    const unsigned gi = w >> half, gq = w & (unsigned)(L - 1);
+    const float xr = d * (float)(2 * (int)gray_level(gi) - (L - 1)), xi = d * (float)(2 * (int)gray_level(gq) - (L - 1));
+    return LinkSent{gi, gq, xr, xi};
+}
+
+// One receive branch of a data element: the two noise words of the branch's own key, y = H x + noise, c = y conj(E) and p = |E|^2
+struct LinkBranch {
+    float cr, ci, p;
+};
+
+__device__ __forceinline__ LinkBranch link_branch(unsigned long long kf, float sigma, unsigned q, float xr, float xi, float2 h, float2 e) {
+    const FrameNoise nz = frame_noise(kf, kStreamDataNoiseRadius, kStreamDataNoiseAngle, q, sigma);
+    const float yr = fmaf(nz.r, nz.c, fmaf(h.x, xr, -(h.y * xi)));
+    const float yi = fmaf(nz.r, nz.s, fmaf(h.x, xi, h.y * xr));
+    const float cr = fmaf(yr, e.x, yi * e.y);                   // y conj(E)
+    const float ci = fmaf(yi, e.x, -(yr * e.y));
+    return LinkBranch{cr, ci, fmaf(e.x, e.x, e.y * e.y)};
+}
+
+// What the single-branch kernels do first with a data element: the sent word and its one branch, both from the frame's key.  Written
+// once, so the hard and the soft kernel see the same bits of c and p.
+struct LinkFront {
+    unsigned gi, gq;            // the sent Gray codes of the I and the Q axis
+    float cr, ci, p;
+};
+
+template <int M>
+__device__ __forceinline__ LinkFront link_front(float d, unsigned long long kf, float sigma, unsigned q, float2 h, float2 e) {
+    const LinkSent s = link_sent<M>(d, kf, q);
+    const LinkBranch b = link_branch(kf, sigma, q, s.xr, s.xi, h, e);
+    return LinkFront{s.gi, s.gq, b.cr, b.ci, b.p};
+}
+
+// ---- the soft half: max-log LLRs and the loss the achievable rate is read from (linksim.py "the soft link") ----
+
+constexpr int kMaxFactors = 8;
+constexpr float kInvLn2 = 1.44269504088896341f;
+
+// One axis: the L metrics mu_k = a_k (a_k p - 2 comp) in registers, and per bit of the Gray code (MSB first) the scaled difference of
+// the two minima.  Two roundings per metric (the fused multiply-add and the product) and nothing contracted behind the source's back.
+template <int L>
+__device__ __forceinline__ void link_axis_llrs(float d, float comp, float p, float scale, float *out) {
+#pragma clang fp contract(off)
+    constexpr int half = L == 2 ? 1 : L == 4 ? 2 : L == 8 ? 3 : 4;
+    const float m2c = -2.f * comp;
+    float mu[L];
+#pragma unroll
+    for (int k = 0; k < L; ++k) {
+        const float ak = d * (float)(2 * k - (L - 1));
+        mu[k] = ak * fmaf(ak, p, m2c);
+    }
+#pragma unroll
+    for (int j = 0; j < half; ++j) {
+        float m0 = 0.f, m1 = 0.f;
+        bool have0 = false, have1 = false;                      // constants once the loop over k is unrolled
+#pragma unroll
+        for (int k = 0; k < L; ++k) {
+            if (((k ^ (k >> 1)) >> (half - 1 - j)) & 1) {
+                m1 = have1 ? fminf(m1, mu[k]) : mu[k];
+                have1 = true;
+            } else {
+                m0 = have0 ? fminf(m0, mu[k]) : mu[k];
+                have0 = true;
+            }
+        }
+        out[j] = scale * (m1 - m0);
+    }
+}
+
+// The softplus step: for each of the n_factors factors, the sum over an element's M LLRs v (I-axis bits first, MSB first: the order of
+// the sent word) of softplus(z) = max(z, 0) + log1p(exp(-|z|)) in nats, z = -(1 - 2 b) factor Lambda with b the sent bit.
+template <int M>
+__device__ __forceinline__ void link_soft_losses(const float *v, unsigned gi, unsigned gq, const float (&fac)[kMaxFactors], int n_factors,
+                                                 float (&acc)[kMaxFactors]) {
+#pragma clang fp contract(off)
+    constexpr int half = M / 2;
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+        const unsigned sent = ((j < half ? gi : gq) >> (half - 1 - j % half)) & 1u;
+        const float against = sent ? v[j] : -v[j];              // -(1 - 2 b) Lambda
+#pragma unroll
+        for (int k = 0; k < kMaxFactors; ++k)
+            if (k < n_factors) {
+                const float z = fac[k] * against;
+                acc[k] += fmaxf(z, 0.f) + log1pf(expf(-fabsf(z)));
+            }
+    }
+}
+
+// the n leading floats of v (n = M or 2 M, a multiple of the store's width) to dst
+template <int M>
+__device__ __forceinline__ void link_store_llrs(float *dst, const float *v, int n, int bytes) {
+    if (bytes == 16) {
+#pragma unroll
+        for (int j = 0; j < 2 * M; j += 4)
+            if (j < n) *reinterpret_cast<f32x4 *>(dst + j) = f32x4{v[j], v[j + 1], v[j + 2], v[j + 3]};
+    } else if (bytes == 8) {
+#pragma unroll
+        for (int j = 0; j < 2 * M; j += 2)
+            if (j < n) *reinterpret_cast<float2 *>(dst + j) = make_float2(v[j], v[j + 1]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 2 * M; ++j)
+            if (j < n) dst[j] = v[j];
+    }
+}
+
+// bytes per store of an LLR tensor at `llr`: an element's m floats start at a multiple of 4 m bytes, so every pair of elements starts
+// on 16 bytes when m is 4 or 8, or when the frames hold an even number of elements (then every pair is whole, too)
+inline int link_llr_store_bytes(const float *llr, int m, unsigned long long elems) {
+    const uintptr_t at = reinterpret_cast<uintptr_t>(llr);
+    return at % 16 == 0 && (m % 4 == 0 || elems % 2 == 0) ? 16 : at % 8 == 0 ? 8 : 4;
+}
+
+}  // namespace
+}  // namespace aft

@@ -73,32 +73,36 @@ def _link_sweep(model, test_dataloaders, make_acc, read) -> Dict[int, float]:
 
 
 def get_link_stats(model: Optional[torch.nn.Module], test_dataloaders: List[Tuple[str, Iterable]], link_cfg, seed: int = 0,
-                   group=None) -> Dict[int, float]:
+                   group=None, branches: int = 1) -> Dict[int, float]:
     """Bit-error rate per loader on the link ``link_cfg`` (``linksim.LinkConfig``) defines: data symbols through each frame's true channel
     plus noise at the frame's SNR, equalised with the model's estimate; ``model=None`` is perfect channel knowledge.  Same sorting and
     keys as ``get_test_stats``; the estimate comes from ``forward_pass``, so every estimator here works; the counts accumulate on the
     device (``linksim.LinkAccumulator``) and are read once per loader.  A frame's data bits and noise are a function of
-    ``(seed, file_no)``, whichever estimator is measured: two estimators see the same link."""
-    return _link_sweep(model, test_dataloaders, lambda device: LinkAccumulator(link_cfg, device, seed), lambda acc: acc.result(group))
+    ``(seed, file_no)``, whichever estimator is measured: two estimators see the same link.
+    ``branches=R`` combines every R consecutive frames of a batch as the antennas of one receiver (``linksim``: "the diversity link");
+    every batch then holds a multiple of R frames."""
+    return _link_sweep(model, test_dataloaders, lambda device: LinkAccumulator(link_cfg, device, seed, branches),
+                       lambda acc: acc.result(group))
 
 
 def get_link_rates(model: Optional[torch.nn.Module], test_dataloaders: List[Tuple[str, Iterable]], link_cfg, seed: int = 0,
-                   factors=DEFAULT_FACTORS, group=None) -> Dict[int, float]:
+                   factors=DEFAULT_FACTORS, group=None, branches: int = 1) -> Dict[int, float]:
     """Achievable rate per loader in bit/symbol on the same link: the bit-interleaved coded-modulation rate (GMI) of the max-log LLRs a
     demapper forms with the model's estimate at the frame's SNR, the best of the LLR scale factors ``factors``; ``model=None`` is perfect
     channel knowledge.  Sorting, keys and the frames' bits and noise as ``get_link_stats``; the losses accumulate on the device
-    (``linksim.RateAccumulator``) and are read once per loader."""
-    return _link_sweep(model, test_dataloaders, lambda device: RateAccumulator(link_cfg, device, seed, factors),
+    (``linksim.RateAccumulator``) and are read once per loader.  ``branches`` as ``get_link_stats``: the rate is per transmission."""
+    return _link_sweep(model, test_dataloaders, lambda device: RateAccumulator(link_cfg, device, seed, factors, branches=branches),
                        lambda acc: acc.result_gmi(group))
 
 
 def get_link_bler(model: Optional[torch.nn.Module], test_dataloaders: List[Tuple[str, Iterable]], code_cfg, seed: int = 0,
-                  err_var: float = 0.0, group=None) -> Dict[int, float]:
+                  err_var: float = 0.0, group=None, branches: int = 1) -> Dict[int, float]:
     """Block-error rate per loader with a decoder in the loop: the code ``code_cfg`` rides on the same link and its decoder reads the
     max-log LLRs the demapper forms with the model's estimate -- a ``linksim.CodeConfig`` is the convolutional code with a Viterbi
     decoder (``linksim.BlockErrorAccumulator``), a ``linksim.LdpcConfig`` the quasi-cyclic LDPC code with a layered min-sum decoder
     (``linksim.LdpcBlockErrorAccumulator``); ``model=None`` is perfect channel knowledge.  Sorting, keys and the frames' bits and noise
-    as ``get_link_stats``; the counts accumulate on the device and are read once per loader."""
+    as ``get_link_stats``; the counts accumulate on the device and are read once per loader.  ``branches`` as ``get_link_stats``: the
+    decoder reads the combiner's LLRs with the leaders' keys."""
     accumulator = LdpcBlockErrorAccumulator if isinstance(code_cfg, LdpcConfig) else BlockErrorAccumulator
-    return _link_sweep(model, test_dataloaders, lambda device: accumulator(code_cfg, device, seed, err_var),
+    return _link_sweep(model, test_dataloaders, lambda device: accumulator(code_cfg, device, seed, err_var, branches),
                        lambda acc: acc.result(group))

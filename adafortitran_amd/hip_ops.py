@@ -553,6 +553,42 @@ class LinkSoftPlan(LinkPlan):
         return loss, llr
 
 
+class LinkMrcPlan(LinkPlan):
+    """Receive diversity on ``LinkPlan``'s link: maximum-ratio combining over ``branches`` consecutive frames (``linksim``: "the
+    diversity link").  ``plan(ideal, est, keys, sigma, rho, scale, factors, want_llr=False)`` -> ``(counts int32 [G, 2], loss float32
+    [G, K], llr float32 [G, S, T, m] or None)`` for the ``G = batch / branches`` groups on the plan's device: three ``torch.empty``
+    at the most, one ``ctypes`` call, one launch (``aft_link_mrc_f32``) on the current stream, no synchronisation.  ``rho`` (float32,
+    ``batch`` values) and ``scale`` (float32, ``G`` values: the leaders') are ``linksim.branch_weights``'; they and ``factors`` live
+    where ``keys`` and ``sigma`` may.  Everything else as ``LinkSoftPlan``."""
+    cpu_path = "linksim.link_mrc_host"
+
+    def __init__(self, cfg, device: torch.device, branches: int) -> None:
+        super().__init__(cfg, device)
+        if isinstance(branches, bool) or not isinstance(branches, int) or not 1 <= branches <= _abi.AFT_LINK_MAX_BRANCHES:
+            raise ValueError(f"branches = {branches!r}: an integer in 1 .. {_abi.AFT_LINK_MAX_BRANCHES}")
+        self.branches = branches
+
+    def __call__(self, ideal: torch.Tensor, est: torch.Tensor, keys: torch.Tensor, sigma: torch.Tensor, rho: torch.Tensor,
+                 scale: torch.Tensor, factors: torch.Tensor, want_llr: bool = False, lib=None):
+        lib = lib or _lib.load()
+        batch, ideal, est, keys, sigma = self._checked(ideal, est, keys, sigma)
+        if batch % self.branches:
+            raise ValueError(f"a batch of {batch} frames is not a multiple of branches = {self.branches}")
+        groups = batch // self.branches
+        rho = _in_place("rho", rho, torch.float32, self.device, batch)
+        scale = _in_place("scale", scale, torch.float32, self.device, groups)
+        if not torch.is_tensor(factors) or not 1 <= factors.numel() <= 8:
+            raise ValueError(f"factors must hold between 1 and 8 values, got {factors.numel() if torch.is_tensor(factors) else factors!r}")
+        factors = _in_place("factors", factors, torch.float32, self.device, factors.numel())
+        counts = torch.empty((groups, 2), dtype=torch.int32, device=self.device)                # the kernel writes every element
+        loss = torch.empty((groups, factors.numel()), dtype=torch.float32, device=self.device)
+        llr = torch.empty((groups, *self.grid, self.cfg.bits_per_symbol), dtype=torch.float32, device=self.device) if want_llr else None
+        _lib.check(lib.aft_link_mrc_f32(C.byref(self.link), ideal.data_ptr(), est.data_ptr(), keys.data_ptr(), sigma.data_ptr(),
+                                        rho.data_ptr(), scale.data_ptr(), factors.data_ptr(), factors.numel(), self.branches,
+                                        counts.data_ptr(), loss.data_ptr(), _ptr(llr), batch, _lib.current_stream_ptr(self.device)), lib)
+        return counts, loss, llr
+
+
 class LinkDecodePlan:
     """A coded link (``linksim.CodeConfig``) turned into ``aft_link_decode_f32``'s arguments ONCE.  ``plan(llr, keys, want_bits=False)``
     -> ``(counts int32 [batch, 2] = (information-bit errors, block errors) per frame, bits uint8 [batch, B, K] or None)`` on the plan's

@@ -60,6 +60,29 @@ relative ``e`` of that errs in ``Lambda_j`` by about ``2 e q``.  The loss is mon
 ``Lambda -+ e_lambda q`` (each bit moved towards, or away from, the sent bit) are an exact interval for every evaluation whose LLRs
 are within ``e_lambda q``.
 
+The diversity link.  Every number above is a single-antenna Rayleigh number: at the SNRs where 64- and 256-QAM operate such a link
+loses its blocks to deep fades of the true channel, not to the estimate.  Receivers have two or four antennas, each with its own
+channel estimate, combined before the demapper.  ``link_mrc_host`` (float64), ``aft_link_mrc_f32`` (csrc/k_linkmrc.hip, through
+``hip_ops.LinkMrcPlan``) and the ``branches=`` argument of the four accumulators and of the three sweeps of ``evaluation`` are maximum-
+ratio combining over R branches.  The estimators here are per-antenna by construction -- one frame is one antenna's grid -- so a batch
+of ``n`` frames with ``R = branches``, ``1 <= R <= 8`` and ``n % R == 0``, is ``G = n / R`` groups: group ``g`` is the frames
+``g R .. g R + R - 1``, its branches ``r = 0 .. R-1``, branch 0 its LEADER::
+
+    w, gi, gq, x   from the leader's key exactly as above (stream 5): one transmission per group; stream 5 of the other keys is unused
+    y_r  = H_r x + sigma_r sqrt(-ln u1) exp(j 2 pi u2)          u1, u2 from streams 6 and 7 of branch r's OWN key, sigma_r that frame's
+    c    = sum_r rho_r y_r conj(E_r),   p = sum_r rho_r |E_r|^2     summed in increasing r, starting from 0
+    rho_r = float32(scale_r / scale_leader)                      scale_* = llr_scale(snr, err_var) of the frame; the ratio is formed in
+                                                                 double and rounded once, so rho_0 = 1 exactly (``branch_weights``)
+
+This is maximum-ratio combining with per-branch noise variances and still has no division on the device; all ``rho`` are 1 when the
+branches share an SNR.  The hard decision, the bit and symbol errors, ``mu_k``, ``Delta_j``, ``Lambda_j = scale Delta_j`` with the
+LEADER's scale (one float32 per group) and the losses at the K factors are the single-branch definitions applied to this ``c`` and
+``p``, per group: counts ``[G, 2]``, loss ``[G, K]``, llr ``[G, S, T, m]``.  With ``R = 1`` every output is the single-branch one.  The
+margin and the LLR reach use ``reach = sum_r rho_r (|H_r||x| + |noise_r|) |E_r|``; flags, ``q`` and the loss interval are otherwise
+unchanged.  The coded links are unchanged downstream: the decoders read this LLR tensor with the leaders' keys (scrambler stream 5,
+information bits stream 8) and ``batch = G``.  What this models: R uncorrelated antennas, each estimated on its own.  It does not
+model antenna correlation, and it gives no array gain in the estimator itself (no estimator here sees more than one antenna's pilots).
+
 The coded link.  The rate says how much information the LLRs carry; a link-level user wants the same with a decoder in the loop: the
 block-error rate of coded blocks and the throughput that follows from it.  ``CodeConfig``, ``link_encode_host`` / ``link_decode_host``
 (integer NumPy), ``aft_link_decode_f32`` (csrc/k_linkcode.hip, through ``hip_ops.LinkDecodePlan``), ``BlockErrorAccumulator`` and
@@ -225,9 +248,8 @@ def _uniform(keys: np.ndarray, stream: int, q: np.ndarray) -> np.ndarray:
     return ((words(keys, stream, q) >> np.uint64(41)).astype(np.float64) + 0.5) * 2.0 ** -23
 
 
-def _front(cfg: LinkConfig, keys, ideal, est, sigma):
-    """What the hard and the soft definition share, in float64: the checked operands and, per element, the sent Gray codes ``gi`` / ``gq``,
-    ``c = y conj(E)``, ``p = |E|^2`` and the reach ``(|H||x| + |noise|) |E|`` of a component of ``c``."""
+def _checked(cfg: LinkConfig, keys, ideal, est, sigma):
+    """The operands of a definition, checked: ``(keys uint64 [n], H, E complex128 [n, S, T], sigma float64 [n])``."""
     keys = np.ascontiguousarray(keys)
     if keys.dtype == np.int64:
         keys = keys.view(np.uint64)
@@ -240,18 +262,38 @@ def _front(cfg: LinkConfig, keys, ideal, est, sigma):
     sigma = np.asarray(sigma, dtype=np.float64).reshape(-1)
     if sigma.shape != (n,):
         raise ValueError(f"sigma must hold one value per frame ({n}), got {sigma.size}")
-    m, L, d = cfg.bits_per_symbol, cfg.levels, cfg.d
+    return keys, H, E, sigma
+
+
+def _sent(cfg: LinkConfig, keys: np.ndarray):
+    """The sent word of every element of the transmissions with ``keys``: the Gray codes ``gi`` / ``gq`` and the symbol ``x``."""
+    (S, T), m, L, d = cfg.sim.ofdm, cfg.bits_per_symbol, cfg.levels, cfg.d
+    q = np.arange(S * T, dtype=np.uint64).reshape(1, S, T)
+    w = (words(keys[:, None, None], STREAM_DATA_BITS, q) >> np.uint64(64 - m)).astype(np.int64)
+    gi, gq = w >> (m // 2), w & (L - 1)
+    return gi, gq, d * ((2 * gray_level(gi) - (L - 1)) + 1j * (2 * gray_level(gq) - (L - 1)))
+
+
+def _branch(cfg: LinkConfig, keys: np.ndarray, H, E, sigma, x):
+    """One receive branch per key: ``c = y conj(E)`` with ``y = H x`` plus the noise of the branch's own key, ``p = |E|^2`` and the
+    reach ``(|H||x| + |noise|) |E|`` of a component of ``c``."""
+    S, T = cfg.sim.ofdm
     q = np.arange(S * T, dtype=np.uint64).reshape(1, S, T)
     kk = keys[:, None, None]
-    w = (words(kk, STREAM_DATA_BITS, q) >> np.uint64(64 - m)).astype(np.int64)
-    gi, gq = w >> (m // 2), w & (L - 1)
-    x = d * ((2 * gray_level(gi) - (L - 1)) + 1j * (2 * gray_level(gq) - (L - 1)))
     u1, u2 = _uniform(kk, STREAM_DATA_NOISE_RADIUS, q), _uniform(kk, STREAM_DATA_NOISE_ANGLE, q)
     noise = sigma[:, None, None] * np.sqrt(-np.log(u1)) * np.exp(2j * np.pi * u2)
     c = (H * x + noise) * E.conj()
     p = E.real ** 2 + E.imag ** 2
     reach = (np.abs(H) * np.abs(x) + np.abs(noise)) * np.abs(E)
-    return gi, gq, c, p, reach
+    return c, p, reach
+
+
+def _front(cfg: LinkConfig, keys, ideal, est, sigma):
+    """What the hard and the soft definition share, in float64: the checked operands and, per element, the sent Gray codes ``gi`` / ``gq``,
+    ``c = y conj(E)``, ``p = |E|^2`` and the reach ``(|H||x| + |noise|) |E|`` of a component of ``c``."""
+    keys, H, E, sigma = _checked(cfg, keys, ideal, est, sigma)
+    gi, gq, x = _sent(cfg, keys)
+    return (gi, gq, *_branch(cfg, keys, H, E, sigma, x))
 
 
 def link_errors_host(cfg: LinkConfig, keys, ideal, est, sigma, tau: Optional[float] = None):
@@ -259,7 +301,11 @@ def link_errors_host(cfg: LinkConfig, keys, ideal, est, sigma, tau: Optional[flo
     complex ``[n, S, T]``, ``sigma`` ``[n]`` -> ``counts`` int64 ``[n, 2]`` = (bit errors, symbol errors) per frame.  With ``tau``:
     ``(counts, errors, flags)``, ``errors`` int64 ``[n, S, T]`` the wrong bits of each element (0 at the pilots) and ``flags`` bool
     ``[n, S, T, 2]`` the flagged (element, axis) pairs at ``tau`` (module docstring; False at the pilots).  Needs no library."""
-    gi, gq, c, p, reach = _front(cfg, keys, ideal, est, sigma)
+    return _hard(cfg, *_front(cfg, keys, ideal, est, sigma), tau)
+
+
+def _hard(cfg: LinkConfig, gi, gq, c, p, reach, tau):
+    """The hard decision and the margins on ``c`` and ``p``: what ``link_errors_host`` returns."""
     (n, S, T), L, d = c.shape, cfg.levels, cfg.d
     mask = cfg.data_mask[None]
     if tau is not None:
@@ -305,7 +351,11 @@ def link_llrs_host(cfg: LinkConfig, keys, ideal, est, sigma, scale, factors=(1.0
     taken as the float32 numbers they are -> ``(loss float64 [n, K], llr float64 [n, S, T, m])``, the LLRs 0 at the pilots.  With
     ``e_lambda``: ``(loss, llr, loss_lo, loss_hi, q)``, ``q [n, S, T, m] = scale A (A p + 2 R)`` (0 at the pilots) and ``loss_lo`` /
     ``loss_hi`` the losses at ``Lambda -+ e_lambda q``, every bit moved towards / away from the sent bit.  Needs no library."""
-    gi, gq, c, p, reach = _front(cfg, keys, ideal, est, sigma)
+    return _soft(cfg, *_front(cfg, keys, ideal, est, sigma), scale, factors, e_lambda)
+
+
+def _soft(cfg: LinkConfig, gi, gq, c, p, reach, scale, factors, e_lambda):
+    """The LLRs and the losses on ``c`` and ``p``: what ``link_llrs_host`` returns."""
     (n, S, T), m, L, d = c.shape, cfg.bits_per_symbol, cfg.levels, cfg.d
     half = m // 2
     scale = np.asarray(scale, dtype=np.float32).astype(np.float64).reshape(-1)
@@ -337,6 +387,61 @@ def link_llrs_host(cfg: LinkConfig, keys, ideal, est, sigma, scale, factors=(1.0
     return loss, llr, losses(llr + sign * (e_lambda * q)), losses(llr - sign * (e_lambda * q)), q
 
 
+MAX_BRANCHES = _abi.AFT_LINK_MAX_BRANCHES
+
+
+def _branches(branches) -> int:
+    if isinstance(branches, bool) or not isinstance(branches, (int, np.integer)) or not 1 <= int(branches) <= MAX_BRANCHES:
+        raise ValueError(f"branches = {branches!r}: an integer in 1 .. {MAX_BRANCHES}")
+    return int(branches)
+
+
+def _grouped(n: int, branches: int) -> int:
+    if n % branches:
+        raise ValueError(f"a batch of {n} frames is not a multiple of branches = {branches}")
+    return n // branches
+
+
+def _weights(scale: np.ndarray, branches: int) -> Tuple[np.ndarray, np.ndarray]:
+    """``(rho float32 [n], the leaders' scale float32 [G])`` of the frames' float32 LLR scales ``[n]``."""
+    s = np.asarray(scale, dtype=np.float32).reshape(_grouped(np.size(scale), branches), branches)
+    rho = (s.astype(np.float64) / s[:, :1].astype(np.float64)).astype(np.float32)
+    return rho.reshape(-1), np.ascontiguousarray(s[:, 0])
+
+
+def branch_weights(snr_db, err_var: float = 0.0, branches: int = 1) -> Tuple[np.ndarray, np.ndarray]:
+    """The combiner's weights for frames at ``snr_db`` ``[n]`` (module docstring, "the diversity link"): ``(rho float32 [n], scale
+    float32 [G])``, ``rho_r = float32(scale_r / scale_leader)`` and ``scale`` the leaders' ``llr_scale(snr_db, err_var)``."""
+    return _weights(llr_scale(np.asarray(snr_db, dtype=np.float64).reshape(-1), err_var), _branches(branches))
+
+
+def link_mrc_host(cfg: LinkConfig, keys, ideal, est, sigma, rho, scale, branches, factors=(1.0,), tau: Optional[float] = None,
+                  e_lambda: Optional[float] = None):
+    """The diversity link (module docstring) in float64: ``keys`` / ``ideal`` / ``est`` / ``sigma`` as ``link_errors_host``'s for the
+    ``n`` frames, ``rho`` ``[n]`` and ``scale`` ``[G]`` taken as the float32 numbers they are (``branch_weights``), ``G = n / branches``
+    -> ``(counts int64 [G, 2], loss float64 [G, K], llr float64 [G, S, T, m])``.  With ``tau`` the wrong-bit map ``[G, S, T]`` and the
+    flags ``[G, S, T, 2]`` follow, with ``e_lambda`` then ``loss_lo``, ``loss_hi`` and ``q``: what ``link_errors_host`` and
+    ``link_llrs_host`` return, on the combined ``c``, ``p`` and reach.  Needs no library."""
+    R = _branches(branches)
+    keys, H, E, sigma = _checked(cfg, keys, ideal, est, sigma)
+    n = len(keys)
+    G = _grouped(n, R)
+    rho = np.asarray(rho, dtype=np.float32).astype(np.float64).reshape(-1)
+    if rho.shape != (n,):
+        raise ValueError(f"rho must hold one value per frame ({n}), got {rho.size}")
+    if np.size(scale) != G:
+        raise ValueError(f"scale must hold one value per group ({G}), got {np.size(scale)}")
+    gi, gq, x = _sent(cfg, keys[::R])                                             # one transmission per group: the leader's key
+    c = p = reach = 0.0
+    for r in range(R):                                                           # in increasing r, starting from 0
+        c_r, p_r, reach_r = _branch(cfg, keys[r::R], H[r::R], E[r::R], sigma[r::R], x)
+        w = rho[r::R, None, None]
+        c, p, reach = c + w * c_r, p + w * p_r, reach + w * reach_r
+    hard = _hard(cfg, gi, gq, c, p, reach, tau)
+    soft = _soft(cfg, gi, gq, c, p, reach, scale, factors, e_lambda)
+    return ((hard,) if tau is None else hard[:1]) + soft[:2] + (() if tau is None else hard[1:]) + soft[2:]
+
+
 # ---- the frame keys with torch ops, for frame numbers that live on the device (no synchronisation) ----
 
 def _s64(v: int) -> int:
@@ -363,21 +468,26 @@ def frame_keys_torch(seed: int, frame_ids: torch.Tensor) -> torch.Tensor:
 
 
 class _FrameSweep:
-    """What the accumulators of a sweep share: a batch's checked operands where the accumulator computes.  ``_operands`` returns None
+    """What the accumulators of a sweep share: a batch's checked operands where the accumulator computes, and the diversity link's
+    combiner (``_combine``) in front of whatever an accumulator measures when ``branches > 1``.  ``_operands`` returns None
     for an empty batch, else ``(b, H, E, keys, per_frame)``: on a CPU device NumPy arrays for the float64 definition, on a HIP device
     tensors for the plan -- frame numbers and SNRs that are host tensors are hashed and converted on the host and copied from pinned
     memory, device tensors with torch ops, so nothing synchronises.  ``per_frame`` holds one float32 ``[b]`` operand per entry of
     ``of_snr``, pairs ``(numpy function, torch function on a float64 tensor)`` of the SNR in dB."""
 
-    def _open(self, cfg: LinkConfig, device, seed: int, plan_name: str) -> None:
+    def _open(self, cfg: LinkConfig, device, seed: int, plan_name: str, branches: int = 1) -> None:
         if not isinstance(cfg, LinkConfig):
             raise ValueError(f"{type(self).__name__} needs a LinkConfig (got {type(cfg).__name__})")
         self.cfg, self.seed = cfg, int(seed)
+        self.branches = _branches(branches)
         self.device = torch.device(device)
         self._plan = None
         if self.device.type == "cuda":
             from . import hip_ops                  # loads the extension: a missing .so raises here, loudly
-            self._plan = getattr(hip_ops, plan_name)(cfg, self.device)
+            if self.branches == 1:
+                self._plan = getattr(hip_ops, plan_name)(cfg, self.device)
+            else:                                  # every measure of the diversity link comes from the combiner's one launch
+                self._plan = hip_ops.LinkMrcPlan(cfg, self.device, self.branches)
             self.device = self._plan.device
         self.frames = 0
 
@@ -434,6 +544,20 @@ class _FrameSweep:
         H = ideal.to(dev).contiguous()
         return b, H, (H if est is None else est.to(dev).contiguous()), keys_t, per_frame_t
 
+    def _combine(self, b, H, E, keys, sigma, scale, factors, factors_t, want_llr=False):
+        """A batch of the diversity link (``branches > 1``): ``(G, the leaders' keys, counts, loss, llr)`` from ``_operands``' pieces,
+        ``scale`` the frames' LLR scales.  On a CPU device the float64 definition on NumPy arrays, on a HIP device the launch of
+        ``aft_link_mrc_f32`` with the weights formed by torch ops on the device; nothing synchronises."""
+        R = self.branches
+        G = _grouped(b, R)
+        if self._plan is None:
+            rho, lead = _weights(scale, R)
+            return (G, keys[::R], *link_mrc_host(self.cfg, keys, H, E, sigma, rho, lead, R, factors))
+        s = scale.view(G, R).to(torch.float64)
+        rho = (s / s[:, :1]).to(torch.float32).reshape(-1)
+        out = self._launch(H, E, keys, sigma, rho, scale[::R].contiguous(), factors_t, want_llr=want_llr)
+        return (G, keys[::R].contiguous(), *out)
+
     def _launch(self, *args, plan=None, **kw):
         """The plan (``self._plan`` unless another is given) on the accumulator's device: the launch belongs to it, whichever device
         is current."""
@@ -466,14 +590,28 @@ class LinkAccumulator(_FrameSweep):
     device a batch is one launch of ``aft_link_errors_f32`` plus one small integer add into an int64 ``[2]`` device tensor: frame
     numbers and SNRs that are host tensors are hashed on the host and copied from pinned memory, device tensors are hashed with
     torch ops -- nothing synchronises.  On a CPU device the float64 definition runs.  ``result`` / ``result_ser`` close the sweep with
-    one read and, with several ranks, the same 16-byte all-gather as the MSE accumulator."""
+    one read and, with several ranks, the same 16-byte all-gather as the MSE accumulator.
 
-    def __init__(self, cfg: LinkConfig, device, seed: int = 0) -> None:
-        self._open(cfg, device, seed, "LinkPlan")
+    ``branches=R`` (module docstring, "the diversity link"; the same argument on the three accumulators below): every R consecutive
+    frames of a batch are the branches of one receiver, combined by one launch of ``aft_link_mrc_f32`` (on a CPU device by
+    ``link_mrc_host``) with the weights of ``branch_weights``; a batch that is no multiple of R raises ``ValueError``, ``frames``
+    counts the groups, and every rate is per transmission.  ``branches=1`` is the single-branch path, launch for launch."""
+
+    def __init__(self, cfg: LinkConfig, device, seed: int = 0, branches: int = 1) -> None:
+        self._open(cfg, device, seed, "LinkPlan", branches)
         self.errors = torch.zeros(2, dtype=torch.int64, device=self.device)     # bit errors, symbol errors
+        self._one = torch.ones(1, dtype=torch.float32, device=self.device) if self.branches > 1 and self._plan is not None else None
 
     def update(self, est: Optional[torch.Tensor], ideal: torch.Tensor, meta: Optional[tuple] = None, *, frame_ids=None,
                snr_db=None) -> None:
+        if self.branches > 1:
+            ops = self._operands(est, ideal, meta, frame_ids, snr_db, (_SIGMA_OF_SNR, _SCALE_OF_SNR(0.0)))
+            if ops is not None:
+                b, H, E, keys, (sigma, scale) = ops
+                groups, _, counts, _, _ = self._combine(b, H, E, keys, sigma, scale, (1.0,), self._one)
+                self.errors += (torch.from_numpy(counts) if self._plan is None else counts).sum(dim=0, dtype=torch.int64)
+                self.frames += groups
+            return
         ops = self._operands(est, ideal, meta, frame_ids, snr_db, (_SIGMA_OF_SNR,))
         if ops is None:
             return
@@ -512,8 +650,8 @@ class RateAccumulator(_FrameSweep):
     one all-gather of ``K + 1`` float64 (the K losses and the frames).  The losses are float sums: ranks that split a sweep differently
     agree to rounding, not bit for bit -- every rank of one sweep reports the same number."""
 
-    def __init__(self, cfg: LinkConfig, device, seed: int = 0, factors=(1.0,), err_var: float = 0.0) -> None:
-        self._open(cfg, device, seed, "LinkSoftPlan")
+    def __init__(self, cfg: LinkConfig, device, seed: int = 0, factors=(1.0,), err_var: float = 0.0, branches: int = 1) -> None:
+        self._open(cfg, device, seed, "LinkSoftPlan", branches)
         self.err_var = float(err_var)
         if not self.err_var >= 0.0:
             raise ValueError(f"err_var = {err_var!r}: a variance, at least 0")
@@ -529,7 +667,10 @@ class RateAccumulator(_FrameSweep):
         if ops is None:
             return
         b, H, E, keys, (sigma, scale) = ops
-        if self._plan is None:
+        if self.branches > 1:
+            b, _, _, loss, _ = self._combine(b, H, E, keys, sigma, scale, self.factors, self._factors_t)
+            self.loss += (torch.from_numpy(loss) if self._plan is None else loss).sum(dim=0, dtype=torch.float64)
+        elif self._plan is None:
             self.loss += torch.from_numpy(link_llrs_host(self.cfg, keys, H, E, sigma, scale, self.factors)[0].sum(axis=0))
         else:
             self.loss += self._launch(H, E, keys, sigma, scale, self._factors_t)[0].sum(dim=0, dtype=torch.float64)
@@ -766,10 +907,10 @@ class BlockErrorAccumulator(_FrameSweep):
     ``result`` is the block-error rate, ``result_ber`` the information-bit error rate, ``result_throughput`` the delivered information
     bits per data element; each is one read and, with several ranks, one all-gather of three float64."""
 
-    def __init__(self, code: CodeConfig, device, seed: int = 0, err_var: float = 0.0) -> None:
+    def __init__(self, code: CodeConfig, device, seed: int = 0, err_var: float = 0.0, branches: int = 1) -> None:
         if not isinstance(code, CodeConfig):
             raise ValueError(f"BlockErrorAccumulator needs a CodeConfig (got {type(code).__name__})")
-        self._open(code.link, device, seed, "LinkSoftPlan")
+        self._open(code.link, device, seed, "LinkSoftPlan", branches)
         self.code = code
         self.err_var = float(err_var)
         if not self.err_var >= 0.0:
@@ -788,7 +929,13 @@ class BlockErrorAccumulator(_FrameSweep):
         if ops is None:
             return
         b, H, E, keys, (sigma, scale) = ops
-        if self._plan is None:
+        if self.branches > 1:                      # the combiner's LLRs, then the decoder on the groups with the leaders' keys
+            b, keys, _, _, llr = self._combine(b, H, E, keys, sigma, scale, (1.0,), self._one, want_llr=True)
+            if self._plan is None:
+                self.errors += torch.from_numpy(link_decode_host(self.code, keys, llr)[0].sum(axis=0))
+            else:
+                self.errors += self._launch(llr, keys, plan=self._decode)[0].sum(dim=0, dtype=torch.int64)
+        elif self._plan is None:
             llr = link_llrs_host(self.cfg, keys, H, E, sigma, scale)[1]
             self.errors += torch.from_numpy(link_decode_host(self.code, keys, llr)[0].sum(axis=0))
         else:
@@ -1105,10 +1252,10 @@ class LdpcBlockErrorAccumulator(BlockErrorAccumulator):
     integer add; nothing synchronises.  On a CPU device the host definitions run.  Each result is one read and, with several ranks,
     one all-gather of four float64."""
 
-    def __init__(self, code: LdpcConfig, device, seed: int = 0, err_var: float = 0.0) -> None:
+    def __init__(self, code: LdpcConfig, device, seed: int = 0, err_var: float = 0.0, branches: int = 1) -> None:
         if not isinstance(code, LdpcConfig):
             raise ValueError(f"LdpcBlockErrorAccumulator needs an LdpcConfig (got {type(code).__name__})")
-        self._open(code.link, device, seed, "LinkSoftPlan")
+        self._open(code.link, device, seed, "LinkSoftPlan", branches)
         self.code = code
         self.err_var = float(err_var)
         if not self.err_var >= 0.0:
@@ -1127,7 +1274,13 @@ class LdpcBlockErrorAccumulator(BlockErrorAccumulator):
         if ops is None:
             return
         b, H, E, keys, (sigma, scale) = ops
-        if self._plan is None:
+        if self.branches > 1:                      # the combiner's LLRs, then the decoder on the groups with the leaders' keys
+            b, keys, _, _, llr = self._combine(b, H, E, keys, sigma, scale, (1.0,), self._one, want_llr=True)
+            if self._plan is None:
+                self.errors += torch.from_numpy(link_ldpc_host(self.code, keys, llr)[0].sum(axis=0))
+            else:
+                self.errors += self._launch(llr, keys, plan=self._decode)[0].sum(dim=0, dtype=torch.int64)
+        elif self._plan is None:
             llr = link_llrs_host(self.cfg, keys, H, E, sigma, scale)[1]
             self.errors += torch.from_numpy(link_ldpc_host(self.code, keys, llr)[0].sum(axis=0))
         else:

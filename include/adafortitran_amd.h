@@ -492,6 +492,33 @@ int aft_link_ldpc_f32(const aft_link *link, const float *llr /* [batch,S,T,m] */
                       unsigned long long stride_inverse, float qgain, int offset, int max_iters, int32_t *counts /* [batch][3] */,
                       unsigned char *bits /* [batch,B,K] or NULL */, int batch, void *stream);
 
+/* ---- receive diversity: maximum-ratio combining over R branches (adafortitran_amd/linksim.py "the diversity link") ----
+ *
+ * R uncorrelated receive antennas, each with its own channel and its own estimate: group g of a batch is the frames g R .. g R + R - 1,
+ * its branches r = 0 .. R-1, branch 0 its leader.  One transmission per group: w, gi, gq, x as aft_link_errors_f32's, from the
+ * LEADER's key (stream 5).
+ *   received    y_r = H_r x + sigma_r sqrt(-ln u1) exp(j 2 pi u2), u1 and u2 from streams 6 and 7 of branch r's OWN key
+ *   combined    c = sum_r rho_r y_r conj(E_r),  p = sum_r rho_r |E_r|^2, in increasing r: c = fma(rho_r, c_r, c), p = fma(rho_r, p_r, p)
+ *               rho float32 [batch], one weight per frame: rho_r = scale_r / scale_leader with scale the frame's LLR scale, so
+ *               rho_0 = 1; per-branch noise variances without a division on the device
+ *   decision, counts, mu_k, Delta_j, Lambda_j = scale Delta_j and loss[f] as aft_link_errors_f32's and aft_link_soft_f32's on this c
+ *               and p, with the LEADER's scale (one per group)
+ * With branches = 1 and rho = 1 counts are aft_link_errors_f32's and loss and llr aft_link_soft_f32's, bit for bit.
+ * One launch, one workgroup per group: counts int32 [batch / branches][2], loss float32 [batch / branches][n_factors] and, when llr
+ * is not NULL, llr float32 [batch / branches, S, T, m] (all device memory) from ideal and est complex64 [batch, S, T] (device
+ * memory), keys uint64 [batch], sigma and rho float32 [batch], scale float32 [batch / branches] and factors float32 [n_factors]
+ * (any device-addressable memory, pinned host memory included).  Every element of the outputs is written; no atomics, no workspace;
+ * nothing is synchronised; float sums run in a fixed order, so a group's outputs depend neither on batch, nor on its position in
+ * it, nor on the run, nor on the load and store forms (aft_link_soft_f32's), nor on whether llr is written.  The decoders
+ * (aft_link_decode_f32, aft_link_ldpc_f32) read this llr with the leaders' keys and batch / branches frames.
+ * Nothing is launched on AFT_ERR_ARG (what aft_link_soft_f32 refuses; a NULL rho / counts; rho / counts not 4-byte aligned; batch
+ * not a multiple of branches) and AFT_ERR_SHAPE (branches outside 1 .. AFT_LINK_MAX_BRANCHES; what aft_link_errors_f32 refuses). */
+#define AFT_LINK_MAX_BRANCHES 8
+int aft_link_mrc_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys,
+                     const float *sigma, const float *rho, const float *scale /* [batch / branches] */, const float *factors,
+                     int n_factors, int branches, int32_t *counts /* [groups][2] */, float *loss /* [groups][n_factors] */,
+                     float *llr /* [groups,S,T,m] or NULL */, int batch, void *stream);
+
 /* ---- training path of the encoder ---- */
 
 /* Gradients of one nn.TransformerEncoderLayer: same fields and shapes as aft_layer_weights,
