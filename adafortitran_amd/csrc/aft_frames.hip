@@ -1,6 +1,8 @@
 // aft_frames.hip -- the C ABI of the one-workgroup-per-frame kernels: the channel simulator, the LMMSE baseline and the link-level error
 // counts (single-branch, with receive diversity, coded).  Their structs start with the same four fields and two carry the pilot
 // positions, so those checks are written once.
+#include <initializer_list>
+
 #include "aft_internal.h"
 
 using namespace aft;
@@ -60,7 +62,7 @@ bool aligned(size_t bytes, const P *...p) {
     return (... | reinterpret_cast<uintptr_t>(p)) % bytes == 0;
 }
 
-// what both link entry points ask of the struct; 0 = fine
+// what every link entry point asks of the struct; 0 = fine
 int check_link(const char *who, const aft_link &l) {
     if (!grid_ok(who, l, INT32_MAX)) return AFT_ERR_SHAPE;
     if ((unsigned long long)l.num_scs * (unsigned long long)l.num_symbols > (1ull << 31)) {
@@ -96,6 +98,47 @@ bool stride_ok(const char *who, unsigned long long stride, unsigned long long st
         return false;
     }
     return true;
+}
+
+// What the three front-end entry points ask of their operands, in their order of precedence: ideal, est and keys, the `words` (4-byte
+// operands that must be there, listed as `names` in the message) and llr (4-byte, may be NULL), the batch, the factors and the branches
+// (an entry point without factors or branches passes 1), then the struct; 0 = fine
+int check_front(const char *who, const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys,
+                std::initializer_list<const void *> words, const char *names, const float *llr, int batch, int n_factors, int branches) {
+    bool there = link && ideal && est && keys;
+    uintptr_t low_bits = reinterpret_cast<uintptr_t>(llr);
+    for (const void *w : words) {
+        there = there && w;
+        low_bits |= reinterpret_cast<uintptr_t>(w);
+    }
+    AFT_REQUIRE(there, "%s: NULL pointer argument", who);
+    AFT_REQUIRE(aligned(8, ideal, est, keys), "%s: ideal, est and keys must be 8-byte aligned", who);
+    AFT_REQUIRE(low_bits % 4 == 0, "%s: %s must be 4-byte aligned", who, names);
+    AFT_REQUIRE(batch >= 1, "%s: batch must be at least 1 (got %d)", who, batch);
+    AFT_REQUIRE(n_factors >= 1 && n_factors <= 8, "%s: n_factors = %d is outside 1..8", who, n_factors);
+    if (!within(who, "branches", branches, 1, AFT_LINK_MAX_BRANCHES)) return AFT_ERR_SHAPE;
+    AFT_REQUIRE(batch % branches == 0, "%s: batch = %d is not a multiple of branches = %d", who, batch, branches);
+    return check_link(who, *link);
+}
+
+// What both decoder entry points compute from a block's coded and information bits and refuse: B = carried / coded blocks per frame
+// (at least one; B info at most 2^31) and the interleaver's stride over the B coded used bits; 0 = fine, *blocks = B
+int check_blocks(const char *who, const aft_link &l, unsigned long long coded, unsigned long long info, unsigned long long stride,
+                 unsigned long long stride_inverse, unsigned *blocks) {
+    const unsigned long long carried = (unsigned long long)l.bits_per_symbol *
+        ((unsigned long long)l.num_scs * l.num_symbols - (unsigned long long)l.pilot_scs * l.pilot_symbols);
+    const unsigned long long b = carried / coded, used = b * coded;
+    if (b == 0) {
+        set_error("%s: a frame carries %llu bits, fewer than the %llu coded bits of one block", who, carried, coded);
+        return AFT_ERR_SHAPE;
+    }
+    if (b * info > (1ull << 31)) {
+        set_error("%s: %llu blocks of %llu information bits: more than 2^31, where the hash's index and the int32 counts end", who, b, info);
+        return AFT_ERR_SHAPE;
+    }
+    if (!stride_ok(who, stride, stride_inverse, used)) return AFT_ERR_SHAPE;   // used >= 10: no block has fewer coded bits
+    *blocks = (unsigned)b;
+    return AFT_OK;
 }
 
 }  // namespace
@@ -145,11 +188,7 @@ int aft_lmmse_f32(const aft_lmmse *plan, const float *tables, const float *pilot
 
 int aft_link_errors_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys,
                         const float *sigma, int32_t *counts, int batch, void *stream) {
-    AFT_REQUIRE(link && ideal && est && keys && sigma && counts, "link errors: NULL pointer argument");
-    AFT_REQUIRE(aligned(8, ideal, est, keys), "link errors: ideal, est and keys must be 8-byte aligned");
-    AFT_REQUIRE(aligned(4, sigma, counts), "link errors: sigma and counts must be 4-byte aligned");
-    AFT_REQUIRE(batch >= 1, "link errors: batch must be at least 1 (got %d)", batch);
-    const int rc = check_link("link errors", *link);
+    const int rc = check_front("link errors", link, ideal, est, keys, {sigma, counts}, "sigma and counts", nullptr, batch, 1, 1);
     if (rc != AFT_OK) return rc;
     hipError_t e = launch_link_errors(*link, ideal, est, keys, sigma, counts, batch, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? AFT_OK : hip_fail("link_errors", e);
@@ -158,12 +197,8 @@ int aft_link_errors_f32(const aft_link *link, const float *ideal, const float *e
 int aft_link_soft_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys,
                       const float *sigma, const float *scale, const float *factors, int n_factors, float *loss, float *llr,
                       int batch, void *stream) {
-    AFT_REQUIRE(link && ideal && est && keys && sigma && scale && factors && loss, "link soft: NULL pointer argument");
-    AFT_REQUIRE(aligned(8, ideal, est, keys), "link soft: ideal, est and keys must be 8-byte aligned");
-    AFT_REQUIRE(aligned(4, sigma, scale, factors, loss, llr), "link soft: sigma, scale, factors, loss and llr must be 4-byte aligned");
-    AFT_REQUIRE(batch >= 1, "link soft: batch must be at least 1 (got %d)", batch);
-    AFT_REQUIRE(n_factors >= 1 && n_factors <= 8, "link soft: n_factors = %d is outside 1..8", n_factors);
-    const int rc = check_link("link soft", *link);
+    const int rc = check_front("link soft", link, ideal, est, keys, {sigma, scale, factors, loss}, "sigma, scale, factors, loss and llr", llr,
+                               batch, n_factors, 1);
     if (rc != AFT_OK) return rc;
     hipError_t e = launch_link_soft(*link, ideal, est, keys, sigma, scale, factors, n_factors, loss, llr, batch,
                                     static_cast<hipStream_t>(stream));
@@ -191,20 +226,10 @@ int aft_link_decode_f32(const aft_link *link, const float *llr, const unsigned l
     const unsigned long long coded = rate == AFT_LINK_RATE_1_2   ? 2 * steps
                                      : rate == AFT_LINK_RATE_2_3 ? 3 * (steps / 2) + 2 * (steps % 2)
                                                                  : 4 * (steps / 3) + (steps % 3 == 0 ? 0 : steps % 3 + 1);
-    const unsigned long long carried = (unsigned long long)link->bits_per_symbol *
-        ((unsigned long long)link->num_scs * link->num_symbols - (unsigned long long)link->pilot_scs * link->pilot_symbols);
-    const unsigned long long blocks = carried / coded, used = blocks * coded;
-    if (blocks == 0) {
-        set_error("%s: a frame carries %llu bits, fewer than the %llu coded bits of one block", who, carried, coded);
-        return AFT_ERR_SHAPE;
-    }
-    if (blocks * (unsigned long long)info_bits > (1ull << 31)) {
-        set_error("%s: %llu blocks of %d information bits: more than 2^31, where the hash's index and the int32 counts end", who, blocks,
-                  info_bits);
-        return AFT_ERR_SHAPE;
-    }
-    if (!stride_ok(who, stride, stride_inverse, used)) return AFT_ERR_SHAPE;   // used >= 10: no block has fewer coded bits
-    hipError_t e = launch_link_decode(*link, llr, keys, info_bits, rate, (unsigned)coded, (unsigned)blocks, stride, qgain,
+    unsigned blocks = 0;
+    const int rb = check_blocks(who, *link, coded, (unsigned long long)info_bits, stride, stride_inverse, &blocks);
+    if (rb != AFT_OK) return rb;
+    hipError_t e = launch_link_decode(*link, llr, keys, info_bits, rate, (unsigned)coded, blocks, stride, qgain,
                                       counts, bits, batch, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? AFT_OK : hip_fail("link_decode", e);
 }
@@ -246,20 +271,10 @@ int aft_link_ldpc_f32(const aft_link *link, const float *llr, const unsigned lon
         return AFT_ERR_SHAPE;
     }
     const unsigned long long coded = (unsigned long long)base_cols * AFT_LINK_LDPC_Z, info = (unsigned long long)kb * AFT_LINK_LDPC_Z;
-    const unsigned long long carried = (unsigned long long)link->bits_per_symbol *
-        ((unsigned long long)link->num_scs * link->num_symbols - (unsigned long long)link->pilot_scs * link->pilot_symbols);
-    const unsigned long long blocks = carried / coded, used = blocks * coded;
-    if (blocks == 0) {
-        set_error("%s: a frame carries %llu bits, fewer than the %llu coded bits of one block", who, carried, coded);
-        return AFT_ERR_SHAPE;
-    }
-    if (blocks * info > (1ull << 31)) {
-        set_error("%s: %llu blocks of %llu information bits: more than 2^31, where the hash's index and the int32 counts end", who, blocks,
-                  info);
-        return AFT_ERR_SHAPE;
-    }
-    if (!stride_ok(who, stride, stride_inverse, used)) return AFT_ERR_SHAPE;
-    hipError_t e = launch_link_ldpc(*link, llr, keys, base_rows, base_cols, shifts, (unsigned)blocks, stride, qgain, offset, max_iters,
+    unsigned blocks = 0;
+    const int rb = check_blocks(who, *link, coded, info, stride, stride_inverse, &blocks);
+    if (rb != AFT_OK) return rb;
+    hipError_t e = launch_link_ldpc(*link, llr, keys, base_rows, base_cols, shifts, blocks, stride, qgain, offset, max_iters,
                                     counts, bits, batch, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? AFT_OK : hip_fail("link_ldpc", e);
 }
@@ -267,16 +282,8 @@ int aft_link_ldpc_f32(const aft_link *link, const float *llr, const unsigned lon
 int aft_link_mrc_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys,
                      const float *sigma, const float *rho, const float *scale, const float *factors, int n_factors, int branches,
                      int32_t *counts, float *loss, float *llr, int batch, void *stream) {
-    const char *who = "link mrc";
-    AFT_REQUIRE(link && ideal && est && keys && sigma && rho && scale && factors && counts && loss, "link mrc: NULL pointer argument");
-    AFT_REQUIRE(aligned(8, ideal, est, keys), "link mrc: ideal, est and keys must be 8-byte aligned");
-    AFT_REQUIRE(aligned(4, sigma, rho, scale, factors, counts, loss, llr),
-                "link mrc: sigma, rho, scale, factors, counts, loss and llr must be 4-byte aligned");
-    AFT_REQUIRE(batch >= 1, "link mrc: batch must be at least 1 (got %d)", batch);
-    AFT_REQUIRE(n_factors >= 1 && n_factors <= 8, "link mrc: n_factors = %d is outside 1..8", n_factors);
-    if (!within(who, "branches", branches, 1, AFT_LINK_MAX_BRANCHES)) return AFT_ERR_SHAPE;
-    AFT_REQUIRE(batch % branches == 0, "link mrc: batch = %d is not a multiple of branches = %d", batch, branches);
-    const int rc = check_link(who, *link);
+    const int rc = check_front("link mrc", link, ideal, est, keys, {sigma, rho, scale, factors, counts, loss},
+                               "sigma, rho, scale, factors, counts, loss and llr", llr, batch, n_factors, branches);
     if (rc != AFT_OK) return rc;
     hipError_t e = launch_link_mrc(*link, ideal, est, keys, sigma, rho, scale, factors, n_factors, branches, counts, loss, llr, batch,
                                    static_cast<hipStream_t>(stream));

@@ -379,7 +379,7 @@ hipError_t launch_link_errors(const aft_link &link, const float *ideal, const fl
 hipError_t launch_link_soft(const aft_link &link, const float *ideal, const float *est, const unsigned long long *keys,
                             const float *sigma, const float *scale, const float *factors, int n_factors, float *loss, float *llr,
                             int batch, hipStream_t st);
-// receive diversity on the same link (k_linkmrc.hip): everything has passed aft_link_mrc_f32's checks; one workgroup per group of
+// receive diversity on the same link (k_link.hip): everything has passed aft_link_mrc_f32's checks; one workgroup per group of
 // `branches` frames, batch a multiple of it; llr may be NULL
 hipError_t launch_link_mrc(const aft_link &link, const float *ideal, const float *est, const unsigned long long *keys,
                            const float *sigma, const float *rho, const float *scale, const float *factors, int n_factors, int branches,

@@ -1,4 +1,4 @@
-// What the one-workgroup-per-frame kernels share (k_chansim.hip, k_lmmse.hip, k_link.hip, k_linkmrc.hip), each written once: the counter-based hash and
+// What the one-workgroup-per-frame kernels share (k_chansim.hip, k_lmmse.hip, k_link.hip), each written once: the counter-based hash and
 // its stream numbers, the Box-Muller noise, and the row-tile pass that writes a row-major [S, T] plane of complex values.  A frame's bits
 // are a function of these (adafortitran_amd/chansim.py and linksim.py hold the definitions and the float64 twins).
 #pragma once

@@ -1,7 +1,8 @@
-// What the link kernels share (k_link.hip, k_linkmrc.hip), each written once, so every kernel sees the same bits: the pilot lookup, the
-// Gray map, the hard decision, the front of a data element -- split into the sent word (one per transmission) and a branch (one per
-// receive antenna: y = H x + noise, c = y conj(E), p = |E|^2) --, an axis's max-log LLRs, the softplus step of the loss and the LLR
-// store.  adafortitran_amd/linksim.py holds the definitions.
+// What the link front end is made of (k_link.hip), each piece written once, so every instantiation sees the same bits: the pilot staging
+// and lookup, the pair loads, the Gray map, the hard decision, the front of a data element -- split into the sent word (one per
+// transmission) and a branch (one per receive antenna: y = H x + noise, c = y conj(E), p = |E|^2) --, the combiner's step, an axis's
+// max-log LLRs, the softplus step of the loss, the LLR store and the reduction of a workgroup's sums.  adafortitran_amd/linksim.py holds
+// the definitions.
 #pragma once
 
 #include "frame_device.h"
@@ -20,6 +21,39 @@ __device__ __forceinline__ bool link_listed(const int *sorted, int n, int v) {
         else hi = mid;
     }
     return lo < n && sorted[lo] == v;
+}
+
+// The pilot positions to LDS: the first wave the columns' list (at most 64), the second the rows' (at most 16).  The caller syncs.
+__device__ __forceinline__ void link_stage_pilots(const aft_link &c, int tid, int *psc, int *psym) {
+    AFT_DEV_ASSERT(c.pilot_scs >= 1 && c.pilot_scs <= AFT_CHANSIM_MAX_PILOT_SCS && c.pilot_symbols >= 1 &&
+                   c.pilot_symbols <= AFT_CHANSIM_MAX_PILOT_SYMBOLS);
+    if (tid < c.pilot_scs) psc[tid] = c.pilot_sc_index[tid];
+    if (tid >= kWave && tid - kWave < c.pilot_symbols) psym[tid - kWave] = c.pilot_symbol_index[tid - kWave];
+}
+
+// element q = s T + t is not a pilot position: two binary searches, the row's only when the column hit
+__device__ __forceinline__ bool link_is_data(const int *psc, int Ps, const int *psym, int Pt, unsigned T, unsigned q) {
+    const unsigned s = q / T, t = q - s * T;
+    return !(link_listed(psym, Pt, (int)t) && link_listed(psc, Ps, (int)s));
+}
+
+// The elements (q, q + 1) of a frame's H and E, hq and eq their element q: one 16-byte load each when `wide` (T even -- a pair never
+// straddles a row -- and both bases 16-byte aligned), one 8-byte load per element otherwise; the lone last element of an odd grid
+// (`two` false) leaves b zero.  One branch for both planes, so their loads issue together.
+struct LinkPair {
+    float2 a, b;
+};
+
+__device__ __forceinline__ void link_load_pairs(const float2 *hq, const float2 *eq, int wide, bool two, LinkPair &h, LinkPair &e) {
+    if (wide) {
+        const f32x4 hv = *reinterpret_cast<const f32x4 *>(hq), ev = *reinterpret_cast<const f32x4 *>(eq);
+        h = LinkPair{make_float2(hv[0], hv[1]), make_float2(hv[2], hv[3])};
+        e = LinkPair{make_float2(ev[0], ev[1]), make_float2(ev[2], ev[3])};
+    } else {
+        h.a = hq[0]; e.a = eq[0];
+        h.b = e.b = make_float2(0.f, 0.f);
+        if (two) { h.b = hq[1]; e.b = eq[1]; }
+    }
 }
 
 // level index of a Gray code of at most four bits: k ^ (k >> 1) = g
@@ -67,18 +101,11 @@ __device__ __forceinline__ LinkBranch link_branch(unsigned long long kf, float s
     return LinkBranch{cr, ci, fmaf(e.x, e.x, e.y * e.y)};
 }
 
-// What the single-branch kernels do first with a data element: the sent word and its one branch, both from the frame's key.  Written
-// once, so the hard and the soft kernel see the same bits of c and p.
-struct LinkFront {
-    unsigned gi, gq;            // the sent Gray codes of the I and the Q axis
-    float cr, ci, p;
-};
-
-template <int M>
-__device__ __forceinline__ LinkFront link_front(float d, unsigned long long kf, float sigma, unsigned q, float2 h, float2 e) {
-    const LinkSent s = link_sent<M>(d, kf, q);
-    const LinkBranch b = link_branch(kf, sigma, q, s.xr, s.xi, h, e);
-    return LinkFront{s.gi, s.gq, b.cr, b.ci, b.p};
+// The combiner's step: c += rho c_r, p += rho p_r, one fused multiply-add each, the product exact inside it
+__device__ __forceinline__ void link_combine(LinkBranch &sum, float rho, const LinkBranch &b) {
+    sum.cr = fmaf(rho, b.cr, sum.cr);
+    sum.ci = fmaf(rho, b.ci, sum.ci);
+    sum.p = fmaf(rho, b.p, sum.p);
 }
 
 // ---- the soft half: max-log LLRs and the loss the achievable rate is read from (linksim.py "the soft link") ----
@@ -153,6 +180,24 @@ __device__ __forceinline__ void link_store_llrs(float *dst, const float *v, int 
         for (int j = 0; j < 2 * M; ++j)
             if (j < n) dst[j] = v[j];
     }
+}
+
+// A workgroup's sum of one value per thread, in a fixed order: the wave by shuffles (kWave / 2 down to 1), whose result lane 0 leaves in
+// part[wave][slot] ...
+template <class T, int N>
+__device__ __forceinline__ void link_wave_sum(T v, int tid, T (*part)[N], int slot) {
+#pragma unroll
+    for (int o = kWave / 2; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    if ((tid & (kWave - 1)) == 0) part[tid / kWave][slot] = v;
+}
+
+// ... and, after a barrier, the four waves in index order
+template <class T, int N>
+__device__ __forceinline__ T link_block_sum(const T (*part)[N], int slot) {
+    T total = part[0][slot];
+#pragma unroll
+    for (int w = 1; w < kLinkWaves; ++w) total += part[w][slot];
+    return total;
 }
 
 // bytes per store of an LLR tensor at `llr`: an element's m floats start at a multiple of 4 m bytes, so every pair of elements starts

@@ -520,6 +520,12 @@ class LinkPlan:
         return (batch, ideal.contiguous(), est.contiguous(),   # held by the caller until after the launch is enqueued
                 _in_place("keys", keys, torch.int64, self.device, batch), _in_place("sigma", sigma, torch.float32, self.device, batch))
 
+    def _checked_factors(self, factors: torch.Tensor) -> torch.Tensor:
+        """The factors of a soft launch, checked: float32, 1 .. 8 values, on the plan's device or in pinned host memory."""
+        if not torch.is_tensor(factors) or not 1 <= factors.numel() <= 8:
+            raise ValueError(f"factors must hold between 1 and 8 values, got {factors.numel() if torch.is_tensor(factors) else factors!r}")
+        return _in_place("factors", factors, torch.float32, self.device, factors.numel())
+
     def __call__(self, ideal: torch.Tensor, est: torch.Tensor, keys: torch.Tensor, sigma: torch.Tensor, lib=None) -> torch.Tensor:
         lib = lib or _lib.load()
         batch, ideal, est, keys, sigma = self._checked(ideal, est, keys, sigma)
@@ -542,9 +548,7 @@ class LinkSoftPlan(LinkPlan):
         lib = lib or _lib.load()
         batch, ideal, est, keys, sigma = self._checked(ideal, est, keys, sigma)
         scale = _in_place("scale", scale, torch.float32, self.device, batch)
-        if not torch.is_tensor(factors) or not 1 <= factors.numel() <= 8:
-            raise ValueError(f"factors must hold between 1 and 8 values, got {factors.numel() if torch.is_tensor(factors) else factors!r}")
-        factors = _in_place("factors", factors, torch.float32, self.device, factors.numel())
+        factors = self._checked_factors(factors)
         loss = torch.empty((batch, factors.numel()), dtype=torch.float32, device=self.device)   # the kernel writes every element
         llr = torch.empty((batch, *self.grid, self.cfg.bits_per_symbol), dtype=torch.float32, device=self.device) if want_llr else None
         _lib.check(lib.aft_link_soft_f32(C.byref(self.link), ideal.data_ptr(), est.data_ptr(), keys.data_ptr(), sigma.data_ptr(),
@@ -577,9 +581,7 @@ class LinkMrcPlan(LinkPlan):
         groups = batch // self.branches
         rho = _in_place("rho", rho, torch.float32, self.device, batch)
         scale = _in_place("scale", scale, torch.float32, self.device, groups)
-        if not torch.is_tensor(factors) or not 1 <= factors.numel() <= 8:
-            raise ValueError(f"factors must hold between 1 and 8 values, got {factors.numel() if torch.is_tensor(factors) else factors!r}")
-        factors = _in_place("factors", factors, torch.float32, self.device, factors.numel())
+        factors = self._checked_factors(factors)
         counts = torch.empty((groups, 2), dtype=torch.int32, device=self.device)                # the kernel writes every element
         loss = torch.empty((groups, factors.numel()), dtype=torch.float32, device=self.device)
         llr = torch.empty((groups, *self.grid, self.cfg.bits_per_symbol), dtype=torch.float32, device=self.device) if want_llr else None
@@ -589,76 +591,67 @@ class LinkMrcPlan(LinkPlan):
         return counts, loss, llr
 
 
-class LinkDecodePlan:
+class _DecoderPlan:
+    """What the two decoder plans share: the code's link struct and LLR shape, and a call that checks ``llr`` and ``keys``, allocates
+    ``counts int32 [batch, width]`` and, when asked for, ``bits uint8 [batch, B, K]``, and makes the one ``ctypes`` call.  A subclass
+    names its config type, its CPU path, its entry point and the width of its counts, and gives the code's arguments as ``self.args``."""
+    config = cpu_path = entry = None
+    width = 2
+
+    def __init__(self, code, device: torch.device) -> None:
+        from . import linksim
+        name = type(self).__name__
+        if not isinstance(code, getattr(linksim, self.config)):
+            raise ValueError(f"{name} needs a linksim.{self.config} (got {type(code).__name__})")
+        self.device = _hip_device(device, name, self.cpu_path)
+        self.code = code
+        self.link = code.link.to_struct()                       # validated by the config itself; the entry point checks again
+        self.shape = (*code.link.sim.ofdm, code.link.bits_per_symbol)
+
+    def __call__(self, llr: torch.Tensor, keys: torch.Tensor, want_bits: bool = False, lib=None):
+        lib = lib or _lib.load()
+        if llr.dim() != 4 or tuple(llr.shape[1:]) != self.shape or llr.shape[0] < 1:
+            raise ValueError(f"Expected llr shape (B >= 1, {self.shape[0]}, {self.shape[1]}, {self.shape[2]}), got {tuple(llr.shape)}")
+        if llr.dtype != torch.float32:
+            raise ValueError(f"llr must be float32, got {llr.dtype}")
+        if llr.device != self.device:
+            raise ValueError(f"llr must live on {self.device} (it is on {llr.device})")
+        batch = llr.shape[0]
+        llr = llr.contiguous()                                  # held by the caller until after the launch is enqueued
+        keys = _in_place("keys", keys, torch.int64, self.device, batch)
+        counts = torch.empty((batch, self.width), dtype=torch.int32, device=self.device)    # the kernel writes every element
+        bits = torch.empty((batch, self.code.blocks, self.code.info_bits), dtype=torch.uint8, device=self.device) if want_bits else None
+        _lib.check(getattr(lib, self.entry)(C.byref(self.link), llr.data_ptr(), keys.data_ptr(), *self.args, counts.data_ptr(), _ptr(bits),
+                                            batch, _lib.current_stream_ptr(self.device)), lib)
+        return counts, bits
+
+
+class LinkDecodePlan(_DecoderPlan):
     """A coded link (``linksim.CodeConfig``) turned into ``aft_link_decode_f32``'s arguments ONCE.  ``plan(llr, keys, want_bits=False)``
     -> ``(counts int32 [batch, 2] = (information-bit errors, block errors) per frame, bits uint8 [batch, B, K] or None)`` on the plan's
     device: one ``ctypes`` call, one launch on the current stream, no synchronisation.  ``llr`` float32 ``[batch,S,T,m]`` (what
     ``LinkSoftPlan`` returns with ``want_llr``) lives on the plan's device; ``keys`` (int64, ``batch`` values) there or in pinned host
     memory, which the kernel reads in place.  The plan trusts its caller in one thing only: its device is the current one."""
+    config, cpu_path, entry = "CodeConfig", "linksim.link_decode_host", "aft_link_decode_f32"
 
     def __init__(self, code, device: torch.device) -> None:
-        from .linksim import CodeConfig
-        if not isinstance(code, CodeConfig):
-            raise ValueError(f"LinkDecodePlan needs a linksim.CodeConfig (got {type(code).__name__})")
-        self.device = _hip_device(device, "LinkDecodePlan", "linksim.link_decode_host")
-        self.code = code
-        self.link = code.link.to_struct()                       # validated by the config itself; the entry point checks again
-        self.shape = (*code.link.sim.ofdm, code.link.bits_per_symbol)
+        super().__init__(code, device)
         self.args = (code.info_bits, code.rate_code, code.stride, code.stride_inverse, code.qgain)
 
-    def __call__(self, llr: torch.Tensor, keys: torch.Tensor, want_bits: bool = False, lib=None):
-        lib = lib or _lib.load()
-        if llr.dim() != 4 or tuple(llr.shape[1:]) != self.shape or llr.shape[0] < 1:
-            raise ValueError(f"Expected llr shape (B >= 1, {self.shape[0]}, {self.shape[1]}, {self.shape[2]}), got {tuple(llr.shape)}")
-        if llr.dtype != torch.float32:
-            raise ValueError(f"llr must be float32, got {llr.dtype}")
-        if llr.device != self.device:
-            raise ValueError(f"llr must live on {self.device} (it is on {llr.device})")
-        batch = llr.shape[0]
-        llr = llr.contiguous()                                  # held by the caller until after the launch is enqueued
-        keys = _in_place("keys", keys, torch.int64, self.device, batch)
-        counts = torch.empty((batch, 2), dtype=torch.int32, device=self.device)             # the kernel writes every element
-        bits = torch.empty((batch, self.code.blocks, self.code.info_bits), dtype=torch.uint8, device=self.device) if want_bits else None
-        _lib.check(lib.aft_link_decode_f32(C.byref(self.link), llr.data_ptr(), keys.data_ptr(), *self.args, counts.data_ptr(), _ptr(bits),
-                                           batch, _lib.current_stream_ptr(self.device)), lib)
-        return counts, bits
 
-
-class LinkLdpcPlan:
+class LinkLdpcPlan(_DecoderPlan):
     """An LDPC-coded link (``linksim.LdpcConfig``) turned into ``aft_link_ldpc_f32``'s arguments ONCE.  ``plan(llr, keys,
     want_bits=False)`` -> ``(counts int32 [batch, 3] = (information-bit errors, block errors, iterations summed over the blocks) per
     frame, bits uint8 [batch, B, K] or None)`` on the plan's device: one ``ctypes`` call, one launch on the current stream, no
     synchronisation.  Operands as ``LinkDecodePlan``'s.  The plan trusts its caller in one thing only: its device is the current one."""
+    config, cpu_path, entry, width = "LdpcConfig", "linksim.link_ldpc_host", "aft_link_ldpc_f32", 3
 
     def __init__(self, code, device: torch.device) -> None:
-        from .linksim import LdpcConfig
-        if not isinstance(code, LdpcConfig):
-            raise ValueError(f"LinkLdpcPlan needs a linksim.LdpcConfig (got {type(code).__name__})")
-        self.device = _hip_device(device, "LinkLdpcPlan", "linksim.link_ldpc_host")
-        self.code = code
-        self.link = code.link.to_struct()                       # validated by the config itself; the entry point checks again
-        self.shape = (*code.link.sim.ofdm, code.link.bits_per_symbol)
+        super().__init__(code, device)
         kb = code.base_cols - code.base_rows
         self.shifts = (C.c_int32 * (code.base_rows * kb))(*(v for row in code.shifts for v in row))      # host memory, read per call
         self.args = (code.base_rows, code.base_cols, C.addressof(self.shifts), code.stride, code.stride_inverse, code.qgain, code.offset,
                      code.max_iters)
-
-    def __call__(self, llr: torch.Tensor, keys: torch.Tensor, want_bits: bool = False, lib=None):
-        lib = lib or _lib.load()
-        if llr.dim() != 4 or tuple(llr.shape[1:]) != self.shape or llr.shape[0] < 1:
-            raise ValueError(f"Expected llr shape (B >= 1, {self.shape[0]}, {self.shape[1]}, {self.shape[2]}), got {tuple(llr.shape)}")
-        if llr.dtype != torch.float32:
-            raise ValueError(f"llr must be float32, got {llr.dtype}")
-        if llr.device != self.device:
-            raise ValueError(f"llr must live on {self.device} (it is on {llr.device})")
-        batch = llr.shape[0]
-        llr = llr.contiguous()                                  # held by the caller until after the launch is enqueued
-        keys = _in_place("keys", keys, torch.int64, self.device, batch)
-        counts = torch.empty((batch, 3), dtype=torch.int32, device=self.device)             # the kernel writes every element
-        bits = torch.empty((batch, self.code.blocks, self.code.info_bits), dtype=torch.uint8, device=self.device) if want_bits else None
-        _lib.check(lib.aft_link_ldpc_f32(C.byref(self.link), llr.data_ptr(), keys.data_ptr(), *self.args, counts.data_ptr(), _ptr(bits),
-                                         batch, _lib.current_stream_ptr(self.device)), lib)
-        return counts, bits
 
 
 def ls_mse_db(ls: torch.Tensor, ideal: torch.Tensor) -> torch.Tensor:

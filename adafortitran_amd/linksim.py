@@ -62,7 +62,7 @@ are within ``e_lambda q``.
 
 The diversity link.  Every number above is a single-antenna Rayleigh number: at the SNRs where 64- and 256-QAM operate such a link
 loses its blocks to deep fades of the true channel, not to the estimate.  Receivers have two or four antennas, each with its own
-channel estimate, combined before the demapper.  ``link_mrc_host`` (float64), ``aft_link_mrc_f32`` (csrc/k_linkmrc.hip, through
+channel estimate, combined before the demapper.  ``link_mrc_host`` (float64), ``aft_link_mrc_f32`` (csrc/k_link.hip, through
 ``hip_ops.LinkMrcPlan``) and the ``branches=`` argument of the four accumulators and of the three sweeps of ``evaluation`` are maximum-
 ratio combining over R branches.  The estimators here are per-antenna by construction -- one frame is one antenna's grid -- so a batch
 of ``n`` frames with ``R = branches``, ``1 <= R <= 8`` and ``n % R == 0``, is ``G = n / R`` groups: group ``g`` is the frames
@@ -468,27 +468,36 @@ def frame_keys_torch(seed: int, frame_ids: torch.Tensor) -> torch.Tensor:
 
 
 class _FrameSweep:
-    """What the accumulators of a sweep share: a batch's checked operands where the accumulator computes, and the diversity link's
-    combiner (``_combine``) in front of whatever an accumulator measures when ``branches > 1``.  ``_operands`` returns None
-    for an empty batch, else ``(b, H, E, keys, per_frame)``: on a CPU device NumPy arrays for the float64 definition, on a HIP device
-    tensors for the plan -- frame numbers and SNRs that are host tensors are hashed and converted on the host and copied from pinned
-    memory, device tensors with torch ops, so nothing synchronises.  ``per_frame`` holds one float32 ``[b]`` operand per entry of
-    ``of_snr``, pairs ``(numpy function, torch function on a float64 tensor)`` of the SNR in dB."""
+    """What the accumulators of a sweep share: ``_measure`` turns a batch into what the accumulator asked ``_open`` for -- the counts, the
+    loss or the LLRs of the link, with the diversity link's combiner in front when ``branches > 1`` -- as tensors on the accumulator's
+    device, whichever device that is.  ``_operands`` returns None for an empty batch, else ``(b, H, E, keys, per_frame)``: on a CPU
+    device NumPy arrays for the float64 definition, on a HIP device tensors for the plan -- frame numbers and SNRs that are host
+    tensors are hashed and converted on the host and copied from pinned memory, device tensors with torch ops, so nothing
+    synchronises.  ``per_frame`` holds one float32 ``[b]`` operand per entry of ``of_snr``, pairs ``(numpy function, torch function on
+    a float64 tensor)`` of the SNR in dB."""
 
-    def _open(self, cfg: LinkConfig, device, seed: int, plan_name: str, branches: int = 1) -> None:
+    def _open(self, cfg: LinkConfig, device, seed: int, want: str, branches: int = 1, err_var: float = 0.0, factors=(1.0,)) -> None:
+        """``want``: which of ``"counts"``, ``"loss"`` and ``"llr"`` ``_measure`` computes."""
         if not isinstance(cfg, LinkConfig):
             raise ValueError(f"{type(self).__name__} needs a LinkConfig (got {type(cfg).__name__})")
-        self.cfg, self.seed = cfg, int(seed)
+        self.cfg, self.seed, self._want = cfg, int(seed), want
         self.branches = _branches(branches)
         self.device = torch.device(device)
+        soft = want != "counts"
         self._plan = None
         if self.device.type == "cuda":
             from . import hip_ops                  # loads the extension: a missing .so raises here, loudly
             if self.branches == 1:
-                self._plan = getattr(hip_ops, plan_name)(cfg, self.device)
+                self._plan = (hip_ops.LinkSoftPlan if soft else hip_ops.LinkPlan)(cfg, self.device)
             else:                                  # every measure of the diversity link comes from the combiner's one launch
                 self._plan = hip_ops.LinkMrcPlan(cfg, self.device, self.branches)
             self.device = self._plan.device
+        self.err_var = float(err_var)
+        if not self.err_var >= 0.0:
+            raise ValueError(f"err_var = {err_var!r}: a variance, at least 0")
+        self.factors = _factors(factors)
+        self._factors_t = None if self._plan is None else torch.from_numpy(self.factors).to(self.device)
+        self._of_snr = (_SIGMA_OF_SNR, _SCALE_OF_SNR(self.err_var)) if soft or self.branches > 1 else (_SIGMA_OF_SNR,)
         self.frames = 0
 
     def _stage(self, a: np.ndarray) -> torch.Tensor:
@@ -544,19 +553,44 @@ class _FrameSweep:
         H = ideal.to(dev).contiguous()
         return b, H, (H if est is None else est.to(dev).contiguous()), keys_t, per_frame_t
 
-    def _combine(self, b, H, E, keys, sigma, scale, factors, factors_t, want_llr=False):
-        """A batch of the diversity link (``branches > 1``): ``(G, the leaders' keys, counts, loss, llr)`` from ``_operands``' pieces,
-        ``scale`` the frames' LLR scales.  On a CPU device the float64 definition on NumPy arrays, on a HIP device the launch of
-        ``aft_link_mrc_f32`` with the weights formed by torch ops on the device; nothing synchronises."""
-        R = self.branches
+    def _measure(self, est, ideal, meta, frame_ids, snr_db):
+        """A batch of ``update``'s arguments: None for an empty one, else ``(groups, the leaders' keys, counts, loss, llr)`` on the
+        accumulator's device, of which the one ``_open`` was asked for is there (the others may be None).  On a CPU device the float64
+        definitions, which compute no soft output for counts alone; on a HIP device one launch -- ``aft_link_errors_f32`` for the
+        counts and ``aft_link_soft_f32`` for the loss and the LLRs of a single branch, ``aft_link_mrc_f32`` for any of them with
+        several, the weights formed by torch ops on the device -- and nothing synchronises."""
+        ops = self._operands(est, ideal, meta, frame_ids, snr_db, self._of_snr)
+        if ops is None:
+            return None
+        b, H, E, keys, (sigma, *scale) = ops       # scale: the frames' LLR scales, where the measure or the combiner needs them
+        R, want_llr = self.branches, self._want == "llr"
         G = _grouped(b, R)
+        counts = loss = llr = None
         if self._plan is None:
-            rho, lead = _weights(scale, R)
-            return (G, keys[::R], *link_mrc_host(self.cfg, keys, H, E, sigma, rho, lead, R, factors))
-        s = scale.view(G, R).to(torch.float64)
-        rho = (s / s[:, :1]).to(torch.float32).reshape(-1)
-        out = self._launch(H, E, keys, sigma, rho, scale[::R].contiguous(), factors_t, want_llr=want_llr)
-        return (G, keys[::R].contiguous(), *out)
+            if R > 1:
+                counts, loss, llr = link_mrc_host(self.cfg, keys, H, E, sigma, *_weights(scale[0], R), R, self.factors)
+            elif self._want == "counts":
+                counts = link_errors_host(self.cfg, keys, H, E, sigma)
+            else:
+                loss, llr = link_llrs_host(self.cfg, keys, H, E, sigma, scale[0], self.factors)
+            return (G, *(None if a is None else torch.from_numpy(a) for a in (keys[::R], counts, loss, llr)))
+        if R > 1:
+            s = scale[0].view(G, R).to(torch.float64)
+            rho = (s / s[:, :1]).to(torch.float32).reshape(-1)
+            counts, loss, llr = self._launch(H, E, keys, sigma, rho, scale[0][::R].contiguous(), self._factors_t, want_llr=want_llr)
+        elif self._want == "counts":
+            counts = self._launch(H, E, keys, sigma)
+        else:
+            loss, llr = self._launch(H, E, keys, sigma, scale[0], self._factors_t, want_llr=want_llr)
+        return G, keys[::R].contiguous(), counts, loss, llr
+
+    @staticmethod
+    def _total(per_group: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+        """A batch's sum over its groups, as ``dtype``.  Host tensors are summed by NumPy, which adds the groups in index order: float64
+        losses then add up as a caller of the definition adds them, bit for bit."""
+        if per_group.is_cuda:
+            return per_group.sum(dim=0, dtype=dtype)
+        return torch.from_numpy(per_group.numpy().sum(axis=0)).to(dtype)
 
     def _launch(self, *args, plan=None, **kw):
         """The plan (``self._plan`` unless another is given) on the accumulator's device: the launch belongs to it, whichever device
@@ -579,6 +613,7 @@ class _FrameSweep:
 
 
 _SIGMA_OF_SNR = (noise_sigma, lambda snr: torch.pow(10.0, -snr / 20.0))
+_SCALE_OF_SNR = lambda err_var: (lambda snr: llr_scale(snr, err_var), lambda snr: 1.0 / (torch.pow(10.0, -snr / 10.0) + err_var))  # noqa: E731
 
 
 class LinkAccumulator(_FrameSweep):
@@ -598,29 +633,16 @@ class LinkAccumulator(_FrameSweep):
     counts the groups, and every rate is per transmission.  ``branches=1`` is the single-branch path, launch for launch."""
 
     def __init__(self, cfg: LinkConfig, device, seed: int = 0, branches: int = 1) -> None:
-        self._open(cfg, device, seed, "LinkPlan", branches)
+        self._open(cfg, device, seed, "counts", branches)
         self.errors = torch.zeros(2, dtype=torch.int64, device=self.device)     # bit errors, symbol errors
-        self._one = torch.ones(1, dtype=torch.float32, device=self.device) if self.branches > 1 and self._plan is not None else None
 
     def update(self, est: Optional[torch.Tensor], ideal: torch.Tensor, meta: Optional[tuple] = None, *, frame_ids=None,
                snr_db=None) -> None:
-        if self.branches > 1:
-            ops = self._operands(est, ideal, meta, frame_ids, snr_db, (_SIGMA_OF_SNR, _SCALE_OF_SNR(0.0)))
-            if ops is not None:
-                b, H, E, keys, (sigma, scale) = ops
-                groups, _, counts, _, _ = self._combine(b, H, E, keys, sigma, scale, (1.0,), self._one)
-                self.errors += (torch.from_numpy(counts) if self._plan is None else counts).sum(dim=0, dtype=torch.int64)
-                self.frames += groups
-            return
-        ops = self._operands(est, ideal, meta, frame_ids, snr_db, (_SIGMA_OF_SNR,))
-        if ops is None:
-            return
-        b, H, E, keys, (sigma,) = ops
-        if self._plan is None:
-            self.errors += torch.from_numpy(link_errors_host(self.cfg, keys, H, E, sigma).sum(axis=0))
-        else:
-            self.errors += self._launch(H, E, keys, sigma).sum(dim=0, dtype=torch.int64)
-        self.frames += b
+        got = self._measure(est, ideal, meta, frame_ids, snr_db)
+        if got is not None:
+            groups, _, counts, _, _ = got
+            self.errors += self._total(counts, torch.int64)
+            self.frames += groups
 
     def local_pair(self, which: int = 0) -> torch.Tensor:
         """float64 ``[2]`` on the device: (bit errors, bits sent) -- with ``which=1`` (symbol errors, symbols sent).  Exact below 2^53."""
@@ -651,30 +673,16 @@ class RateAccumulator(_FrameSweep):
     agree to rounding, not bit for bit -- every rank of one sweep reports the same number."""
 
     def __init__(self, cfg: LinkConfig, device, seed: int = 0, factors=(1.0,), err_var: float = 0.0, branches: int = 1) -> None:
-        self._open(cfg, device, seed, "LinkSoftPlan", branches)
-        self.err_var = float(err_var)
-        if not self.err_var >= 0.0:
-            raise ValueError(f"err_var = {err_var!r}: a variance, at least 0")
-        self.factors = _factors(factors)
+        self._open(cfg, device, seed, "loss", branches, err_var, factors)
         self.loss = torch.zeros(len(self.factors), dtype=torch.float64, device=self.device)
-        self._factors_t = None if self._plan is None else torch.from_numpy(self.factors).to(self.device)
-        self._of_snr = (_SIGMA_OF_SNR, (lambda snr: llr_scale(snr, self.err_var),
-                                        lambda snr: 1.0 / (torch.pow(10.0, -snr / 10.0) + self.err_var)))
 
     def update(self, est: Optional[torch.Tensor], ideal: torch.Tensor, meta: Optional[tuple] = None, *, frame_ids=None,
                snr_db=None) -> None:
-        ops = self._operands(est, ideal, meta, frame_ids, snr_db, self._of_snr)
-        if ops is None:
-            return
-        b, H, E, keys, (sigma, scale) = ops
-        if self.branches > 1:
-            b, _, _, loss, _ = self._combine(b, H, E, keys, sigma, scale, self.factors, self._factors_t)
-            self.loss += (torch.from_numpy(loss) if self._plan is None else loss).sum(dim=0, dtype=torch.float64)
-        elif self._plan is None:
-            self.loss += torch.from_numpy(link_llrs_host(self.cfg, keys, H, E, sigma, scale, self.factors)[0].sum(axis=0))
-        else:
-            self.loss += self._launch(H, E, keys, sigma, scale, self._factors_t)[0].sum(dim=0, dtype=torch.float64)
-        self.frames += b
+        got = self._measure(est, ideal, meta, frame_ids, snr_db)
+        if got is not None:
+            groups, _, _, loss, _ = got
+            self.loss += self._total(loss, torch.float64)
+            self.frames += groups
 
     def result(self, group: Optional["torch.distributed.ProcessGroup"] = None) -> list:
         """The K rates in bit/symbol over all ranks, one per factor (0.0 each for an empty sweep)."""
@@ -896,9 +904,6 @@ def link_decode_host(code: CodeConfig, keys, llr) -> Tuple[np.ndarray, np.ndarra
     return counts, bits
 
 
-_SCALE_OF_SNR = lambda err_var: (lambda snr: llr_scale(snr, err_var), lambda snr: 1.0 / (torch.pow(10.0, -snr / 10.0) + err_var))  # noqa: E731
-
-
 class BlockErrorAccumulator(_FrameSweep):
     """Block errors of a sweep with a decoder in the loop (module docstring, "the coded link"), with ``LinkAccumulator``'s ``update``
     surface.  The LLRs are the soft link's at factor 1 with the scale ``llr_scale(snr_db, err_var)``.  On a HIP device a batch is the
@@ -907,60 +912,53 @@ class BlockErrorAccumulator(_FrameSweep):
     ``result`` is the block-error rate, ``result_ber`` the information-bit error rate, ``result_throughput`` the delivered information
     bits per data element; each is one read and, with several ranks, one all-gather of three float64."""
 
-    def __init__(self, code: CodeConfig, device, seed: int = 0, err_var: float = 0.0, branches: int = 1) -> None:
-        if not isinstance(code, CodeConfig):
-            raise ValueError(f"BlockErrorAccumulator needs a CodeConfig (got {type(code).__name__})")
-        self._open(code.link, device, seed, "LinkSoftPlan", branches)
+    #: what ``LdpcBlockErrorAccumulator`` changes: the config it accepts, the host decoder, the decoder's plan and the columns of ``errors``
+    _config, _needs, _host_decoder, _decoder_plan, _columns = CodeConfig, "a CodeConfig", staticmethod(link_decode_host), "LinkDecodePlan", 2
+
+    def __init__(self, code, device, seed: int = 0, err_var: float = 0.0, branches: int = 1) -> None:
+        if not isinstance(code, self._config):
+            raise ValueError(f"{type(self).__name__} needs {self._needs} (got {type(code).__name__})")
+        self._open(code.link, device, seed, "llr", branches, err_var)
         self.code = code
-        self.err_var = float(err_var)
-        if not self.err_var >= 0.0:
-            raise ValueError(f"err_var = {err_var!r}: a variance, at least 0")
-        self.errors = torch.zeros(2, dtype=torch.int64, device=self.device)     # information-bit errors, block errors
-        self._decode = self._one = None
+        self.errors = torch.zeros(self._columns, dtype=torch.int64, device=self.device)    # information-bit errors, block errors, ...
+        self._decode = None
         if self._plan is not None:
             from . import hip_ops
-            self._decode = hip_ops.LinkDecodePlan(code, self.device)
-            self._one = torch.ones(1, dtype=torch.float32, device=self.device)
-        self._of_snr = (_SIGMA_OF_SNR, _SCALE_OF_SNR(self.err_var))
+            self._decode = getattr(hip_ops, self._decoder_plan)(code, self.device)
+
+    def _decoded(self, llr: torch.Tensor, keys: torch.Tensor) -> torch.Tensor:
+        """The decoder's counts per group on the LLRs ``_measure`` returned: the host definition on a CPU device, the plan's launch on
+        a HIP device."""
+        if self._decode is None:
+            return torch.from_numpy(self._host_decoder(self.code, keys.numpy(), llr.numpy())[0])
+        return self._launch(llr, keys, plan=self._decode)[0]
 
     def update(self, est: Optional[torch.Tensor], ideal: torch.Tensor, meta: Optional[tuple] = None, *, frame_ids=None,
                snr_db=None) -> None:
-        ops = self._operands(est, ideal, meta, frame_ids, snr_db, self._of_snr)
-        if ops is None:
-            return
-        b, H, E, keys, (sigma, scale) = ops
-        if self.branches > 1:                      # the combiner's LLRs, then the decoder on the groups with the leaders' keys
-            b, keys, _, _, llr = self._combine(b, H, E, keys, sigma, scale, (1.0,), self._one, want_llr=True)
-            if self._plan is None:
-                self.errors += torch.from_numpy(link_decode_host(self.code, keys, llr)[0].sum(axis=0))
-            else:
-                self.errors += self._launch(llr, keys, plan=self._decode)[0].sum(dim=0, dtype=torch.int64)
-        elif self._plan is None:
-            llr = link_llrs_host(self.cfg, keys, H, E, sigma, scale)[1]
-            self.errors += torch.from_numpy(link_decode_host(self.code, keys, llr)[0].sum(axis=0))
-        else:
-            llr = self._launch(H, E, keys, sigma, scale, self._one, want_llr=True)[1]
-            self.errors += self._launch(llr, keys, plan=self._decode)[0].sum(dim=0, dtype=torch.int64)
-        self.frames += b
+        got = self._measure(est, ideal, meta, frame_ids, snr_db)
+        if got is not None:                        # the link's LLRs, then the decoder on the groups with the leaders' keys
+            groups, keys, _, _, llr = got
+            self.errors += self._total(self._decoded(llr, keys), torch.int64)
+            self.frames += groups
 
-    def _read(self, group) -> Tuple[float, float, float]:
+    def _read(self, group) -> list:
+        """The columns of ``errors``, then the frames, over all ranks."""
         frames = torch.tensor([float(self.frames)], dtype=torch.float64, device=self.device)
-        bit_errors, block_errors, frames = self._all_ranks(torch.cat([self.errors.to(torch.float64), frames]), group)
-        return bit_errors, block_errors, frames
+        return self._all_ranks(torch.cat([self.errors.to(torch.float64), frames]), group)
 
     def result(self, group: Optional["torch.distributed.ProcessGroup"] = None) -> float:
         """Global block-error rate over all ranks (integers summed: identical on every rank); 0.0 for an empty sweep."""
-        _, block_errors, frames = self._read(group)
+        _, block_errors, *_, frames = self._read(group)
         return block_errors / (frames * self.code.blocks) if frames > 0 else 0.0
 
     def result_ber(self, group=None) -> float:
         """Global information-bit error rate after decoding."""
-        bit_errors, _, frames = self._read(group)
+        bit_errors, *_, frames = self._read(group)
         return bit_errors / (frames * self.code.info_bits_per_frame) if frames > 0 else 0.0
 
     def result_throughput(self, group=None) -> float:
         """Information bits of the blocks decoded without error, per data element sent."""
-        _, block_errors, frames = self._read(group)
+        _, block_errors, *_, frames = self._read(group)
         if frames <= 0:
             return 0.0
         return (frames * self.code.blocks - block_errors) * self.code.info_bits / (frames * self.cfg.data_elements)
@@ -1252,51 +1250,9 @@ class LdpcBlockErrorAccumulator(BlockErrorAccumulator):
     integer add; nothing synchronises.  On a CPU device the host definitions run.  Each result is one read and, with several ranks,
     one all-gather of four float64."""
 
-    def __init__(self, code: LdpcConfig, device, seed: int = 0, err_var: float = 0.0, branches: int = 1) -> None:
-        if not isinstance(code, LdpcConfig):
-            raise ValueError(f"LdpcBlockErrorAccumulator needs an LdpcConfig (got {type(code).__name__})")
-        self._open(code.link, device, seed, "LinkSoftPlan", branches)
-        self.code = code
-        self.err_var = float(err_var)
-        if not self.err_var >= 0.0:
-            raise ValueError(f"err_var = {err_var!r}: a variance, at least 0")
-        self.errors = torch.zeros(3, dtype=torch.int64, device=self.device)     # information-bit errors, block errors, iterations
-        self._decode = self._one = None
-        if self._plan is not None:
-            from . import hip_ops
-            self._decode = hip_ops.LinkLdpcPlan(code, self.device)
-            self._one = torch.ones(1, dtype=torch.float32, device=self.device)
-        self._of_snr = (_SIGMA_OF_SNR, _SCALE_OF_SNR(self.err_var))
-
-    def update(self, est: Optional[torch.Tensor], ideal: torch.Tensor, meta: Optional[tuple] = None, *, frame_ids=None,
-               snr_db=None) -> None:
-        ops = self._operands(est, ideal, meta, frame_ids, snr_db, self._of_snr)
-        if ops is None:
-            return
-        b, H, E, keys, (sigma, scale) = ops
-        if self.branches > 1:                      # the combiner's LLRs, then the decoder on the groups with the leaders' keys
-            b, keys, _, _, llr = self._combine(b, H, E, keys, sigma, scale, (1.0,), self._one, want_llr=True)
-            if self._plan is None:
-                self.errors += torch.from_numpy(link_ldpc_host(self.code, keys, llr)[0].sum(axis=0))
-            else:
-                self.errors += self._launch(llr, keys, plan=self._decode)[0].sum(dim=0, dtype=torch.int64)
-        elif self._plan is None:
-            llr = link_llrs_host(self.cfg, keys, H, E, sigma, scale)[1]
-            self.errors += torch.from_numpy(link_ldpc_host(self.code, keys, llr)[0].sum(axis=0))
-        else:
-            llr = self._launch(H, E, keys, sigma, scale, self._one, want_llr=True)[1]
-            self.errors += self._launch(llr, keys, plan=self._decode)[0].sum(dim=0, dtype=torch.int64)
-        self.frames += b
-
-    def _read4(self, group) -> Tuple[float, float, float, float]:
-        frames = torch.tensor([float(self.frames)], dtype=torch.float64, device=self.device)
-        return tuple(self._all_ranks(torch.cat([self.errors.to(torch.float64), frames]), group))
-
-    def _read(self, group) -> Tuple[float, float, float]:
-        bit_errors, block_errors, _, frames = self._read4(group)
-        return bit_errors, block_errors, frames
+    _config, _needs, _host_decoder, _decoder_plan, _columns = LdpcConfig, "an LdpcConfig", staticmethod(link_ldpc_host), "LinkLdpcPlan", 3
 
     def result_iterations(self, group=None) -> float:
         """Mean decoder iterations per block over all ranks; 0.0 for an empty sweep."""
-        _, _, iterations, frames = self._read4(group)
+        _, _, iterations, frames = self._read(group)
         return iterations / (frames * self.code.blocks) if frames > 0 else 0.0

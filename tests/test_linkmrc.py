@@ -21,6 +21,7 @@ from test_linksoft import sent_bits
 
 MRC_GRIDS = {"default_120x14": 8, "odd_30x7": 16}           # frames [0, n) of seed 3: 1, 2, 4 and 8 branches divide both
 BRANCHES = (1, 2, 4, 8)
+MRC_ODD = "odd_last_alone_3x5"                              # its two frames: one group of two branches, or two of one
 _inputs = {}
 
 
@@ -28,7 +29,7 @@ def mrc_inputs(name):
     """(sim, keys uint64 [n], sigma float32 [n], snr float64 [n], ideal complex64 [n,S,T], {"lmmse": .., "ideal": ..}), made once per
     grid and read-only: ``test_linksim.link_inputs``' recipe on more frames, each at the SNR it was drawn with."""
     if name not in _inputs:
-        sim, n = GRIDS[name][0], MRC_GRIDS[name]
+        sim, n = GRIDS[name][0], MRC_GRIDS[name] if name in MRC_GRIDS else GRIDS[name][1]
         ideal, pilots, meta = simulate_frames_host(sim, SEED, np.arange(n))
         ideal, pilots = ideal.astype(np.complex64), pilots.astype(np.complex64)
         est = {"lmmse": lmmse_estimate_host(sim, pilots, meta).astype(np.complex64), "ideal": ideal}
@@ -73,6 +74,12 @@ def test_the_two_exact_extremes(R, m):
         if m == 2:                                                               # the estimates point the other way: every bit flips
             counts, _, _, _, flags = link_mrc_host(cfg, keys, ideal, -ideal, zero, rho, scale, R, tau=TAU_CAP)
             assert (counts[:, 0] == 2 * cfg.data_elements).all() and (counts[:, 1] == cfg.data_elements).all() and not flags.any()
+    if R == 2:                                     # the odd grid whose last element is data: the MSB of each axis flips at every m
+        sim, keys, sigma, snr, ideal, _ = mrc_inputs(MRC_ODD)
+        rho, scale = branch_weights(snr, 0.0, R)
+        zero = np.zeros_like(sigma)
+        assert not link_mrc_host(LinkConfig(sim, m), keys, ideal, ideal, zero, rho, scale, R)[0].any()
+        assert link_mrc_host(LinkConfig(sim, m), keys, ideal, -ideal, zero, rho, scale, R)[0].tolist() == [[28, 14]]
 
 
 def _received(cfg, keys, ideal, sigma, R):
@@ -253,13 +260,29 @@ def test_accumulators_and_sweeps_with_two_branches_on_the_host():
     assert get_link_rates(model, loaders, cfg, seed, branches=R) == {0: max(4 - v / (G * cfg.data_elements) for v in want["loss0"])}
     assert get_link_bler(model, loaders, code, seed, branches=R) == {0: want["conv0"][1] / (G * code.blocks)}
     assert get_link_bler(model, loaders, ldpc, seed, err_var, branches=R) == {0: want["ldpc"][1] / (G * ldpc.blocks)}
-    # one branch is today's path: the single-branch definition
-    single = LinkAccumulator(cfg, "cpu", seed)
-    single.update(model(batches[0][0]), batches[0][1], batches[0][2])
-    keys = frame_keys(seed, np.rint(batches[0][2][0].numpy().reshape(-1)).astype(np.int64))
-    assert single.branches == 1 and single.frames == 4
-    assert single.errors.tolist() == link_errors_host(cfg, keys, batches[0][1].numpy(), model(batches[0][0]).numpy(),
-                                                      noise_sigma(batches[0][2][1].numpy().reshape(-1))).sum(axis=0).tolist()
+    # one branch over the same frames: the four accumulators against the single-branch definitions called directly
+    hard1, rate1 = LinkAccumulator(cfg, "cpu", seed), RateAccumulator(cfg, "cpu", seed, factors, err_var)
+    conv1, lay1 = BlockErrorAccumulator(code, "cpu", seed, err_var), LdpcBlockErrorAccumulator(ldpc, "cpu", seed, err_var)
+    want1 = {"hard": np.zeros(2, np.int64), "loss": np.zeros(2), "conv": np.zeros(2, np.int64), "ldpc": np.zeros(3, np.int64)}
+    for pilots, ideal, meta in batches:
+        est = model(pilots)
+        for acc in (hard1, rate1, conv1, lay1):
+            acc.update(est, ideal, meta)
+        keys = frame_keys(seed, np.rint(meta[0].numpy().reshape(-1)).astype(np.int64))
+        snr = meta[1].numpy().reshape(-1)
+        want1["hard"] += link_errors_host(cfg, keys, ideal.numpy(), est.numpy(), noise_sigma(snr)).sum(axis=0)
+        loss, llr = link_llrs_host(cfg, keys, ideal.numpy(), est.numpy(), noise_sigma(snr), llr_scale(snr, err_var), factors)
+        want1["loss"] += loss.sum(axis=0)
+        want1["conv"] += link_decode_host(code, keys, llr.astype(np.float32))[0].sum(axis=0)
+        want1["ldpc"] += link_ldpc_host(ldpc, keys, llr.astype(np.float32))[0].sum(axis=0)
+    assert all(acc.branches == 1 and acc.frames == 12 for acc in (hard1, rate1, conv1, lay1))
+    assert hard1.errors.tolist() == want1["hard"].tolist() and hard1.result() == want1["hard"][0] / (12 * cfg.bits_per_frame)
+    np.testing.assert_allclose(rate1.loss.numpy(), want1["loss"], rtol=1e-12, atol=0)
+    np.testing.assert_allclose(rate1.result(), [4 - v / (12 * cfg.data_elements) for v in want1["loss"]], rtol=1e-12, atol=0)
+    assert conv1.errors.tolist() == want1["conv"].tolist() and conv1.result() == want1["conv"][1] / (12 * code.blocks)
+    assert lay1.errors.tolist() == want1["ldpc"].tolist() and lay1.result() == want1["ldpc"][1] / (12 * ldpc.blocks)
+    assert lay1.result_iterations() == want1["ldpc"][2] / (12 * ldpc.blocks)
+    assert want1["hard"][0] > want["hard"][0] > 0                                # the frames are not trivial: diversity removed errors
 
 
 def test_diversity_removes_errors():

@@ -6,7 +6,8 @@ own LLRs, and the physical orderings.
 
 The shapes are tests/test_linkmrc.py's ``mrc_inputs``: seed 3, frames 0..7 of the default grid (16-byte loads, 840 pairs over 256
 threads) and 0..15 of 30 x 7 (odd T: 8-byte loads, a ragged last pass), each frame at the SNR it was drawn with, so the weights are
-mixed (``rho`` reaches 316); R in (1, 2, 3, 4, 8), R = 3 on the first 6 and 15 frames.
+mixed (``rho`` reaches 316); R in (1, 2, 3, 4, 8), R = 3 on the first 6 and 15 frames.  With R = 1 and 2 also the two frames of 3 x 5
+(``MRC_ODD``: an odd number of elements whose last is data, alone in its pair).
 
 The bounds extend tests/test_linksim_gpu.py's ``derived_tau`` and tests/test_linksoft_gpu.py's ``derived_e_lambda`` to R branches, in
 units of the summed reach ``sum_r rho_r (|H_r||x| + |noise_r|) |E_r|`` (u = 2^-24, no fast-math; ``rho`` and ``scale`` are the same
@@ -38,7 +39,7 @@ from adafortitran_amd.linksim import (BITS_PER_SYMBOL, DEFAULT_FACTORS, BlockErr
                                       llr_scale, noise_sigma)
 from adafortitran_amd.lmmse import LmmseEstimator
 from test_chansim_gpu import _no_sync, _same_bits
-from test_linkmrc import MRC_GRIDS, mrc_inputs
+from test_linkmrc import MRC_GRIDS, MRC_ODD, mrc_inputs
 from test_linksim import SHARE_CAP, TAU_CAP, flagged_share
 from test_linksim_gpu import U, _dev, derived_tau as derived_tau_1
 from test_linksoft_gpu import FLOOR, derived_e_s
@@ -48,6 +49,8 @@ DEV = "cuda"
 POISON = -7777
 FACTORS = np.asarray(DEFAULT_FACTORS[:3], dtype=np.float32)
 BRANCHES = (1, 2, 3, 4, 8)
+#: every grid with the branches its frames allow: the odd grid whose last element is data has two frames
+CASES = tuple((name, BRANCHES) for name in MRC_GRIDS) + ((MRC_ODD, (1, 2)),)
 
 
 def derived_tau(R: int) -> float:
@@ -111,10 +114,10 @@ def _run(name, m, R, which="lmmse", want_llr=True, lib=None):
 def test_kernel_against_the_float64_definition(m):
     groups = with_flags = differing = 0
     worst_llr = 0.0
-    for name in MRC_GRIDS:
+    for name, branches in CASES:
         cfg = LinkConfig(mrc_inputs(name)[0], m)
         e_s = derived_e_s(cfg)
-        for R in BRANCHES:
+        for R in branches:
             for which in ("lmmse", "ideal"):
                 want_counts, _, want_llr, _, flags, lo, hi, q = _want(name, m, R, which)
                 counts, loss, llr = _run(name, m, R, which)
@@ -141,7 +144,7 @@ def test_kernel_against_the_float64_definition(m):
 
 @pytest.mark.parametrize("m", BITS_PER_SYMBOL)
 def test_one_branch_is_the_single_branch_kernels_bit_for_bit(m):
-    for name in MRC_GRIDS:
+    for name, _ in CASES:
         cfg = LinkConfig(mrc_inputs(name)[0], m)
         hard, soft = LinkPlan(cfg, DEV), LinkSoftPlan(cfg, DEV)
         for which in ("lmmse", "ideal"):
@@ -151,6 +154,28 @@ def test_one_branch_is_the_single_branch_kernels_bit_for_bit(m):
             want_loss, want_llr = soft(h, e, k, s, c, _dev(FACTORS), want_llr=True)
             assert torch.equal(counts, hard(h, e, k, s)) and torch.equal(loss, want_loss) and torch.equal(llr, want_llr)
             _same_bits([loss, llr], [want_loss, want_llr])                       # the sums start at -0: the sign of a zero, too
+    # the odd grid whose last element (14, at (2, 4)) is data and alone in its pair: written by both kernels into a poisoned LLR
+    # output, finite and not a pilot's zero, with one branch and with two; without it the counts of -H would read (26, 13)
+    cfg = LinkConfig(mrc_inputs(MRC_ODD)[0], m)
+    f = _dev(FACTORS)
+    for R in (1, 2):
+        n, _, ops = _operands(MRC_ODD, R)
+        G = n // R
+        counts = torch.full((G, 2), POISON, dtype=torch.int32, device=DEV)
+        loss, llr = torch.full((G, 3), float("nan"), device=DEV), torch.full((G, 3, 5, m), float("nan"), device=DEV)
+        _lib.check(_entry(_plan(MRC_ODD, m, R), ops, f, counts, loss, llr.data_ptr(), n))
+        _same_bits([counts, loss, llr], _run(MRC_ODD, m, R))
+        assert llr.isfinite().all() and (llr[:, 2, 4] != 0).all() and (llr[:, 1, 2] == 0).all()
+        k, s, rho, c, h, e = ops
+        zero = torch.zeros_like(s)
+        assert _plan(MRC_ODD, m, R)(h, -h, k, zero, rho, c, f)[0].tolist() == [[28, 14]] * G
+    k, s, rho, c, h, e = _operands(MRC_ODD, 1)[2]
+    soft_llr = torch.full((2, 3, 5, m), float("nan"), device=DEV)
+    soft_loss = torch.full((2, 3), float("nan"), device=DEV)
+    _lib.check(_lib.load().aft_link_soft_f32(ctypes.byref(cfg.to_struct()), h.data_ptr(), e.data_ptr(), k.data_ptr(), s.data_ptr(), c.data_ptr(),
+                                             f.data_ptr(), 3, soft_loss.data_ptr(), soft_llr.data_ptr(), 2, _lib.current_stream_ptr(h.device)))
+    _same_bits([soft_loss, soft_llr], _run(MRC_ODD, m, 1)[1:])
+    assert soft_llr.isfinite().all() and (soft_llr[:, 2, 4] != 0).all()
 
 
 @pytest.mark.parametrize("m", BITS_PER_SYMBOL)
@@ -223,6 +248,8 @@ def test_checked_build_gives_the_same_bits():
         for m in BITS_PER_SYMBOL:
             for R in (1, 3, 8):
                 _same_bits(_run(name, m, R, lib=lib), _run(name, m, R))
+    for m in BITS_PER_SYMBOL:
+        _same_bits(_run(MRC_ODD, m, 2, lib=lib), _run(MRC_ODD, m, 2))
 
 
 def test_what_the_plan_refuses():

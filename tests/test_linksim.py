@@ -32,6 +32,7 @@ GRIDS = {
     "pilot_bounds_128x40": (ChannelSimConfig(ofdm=(128, 40), pilot=(64, 16)), 2),
     "one_data_element_2x1": (ChannelSimConfig(ofdm=(2, 1), pilot=(1, 1)), 1),
     "no_data_element_1x1": (ChannelSimConfig(ofdm=(1, 1), pilot=(1, 1)), 1),
+    "odd_last_alone_3x5": (ChannelSimConfig(ofdm=(3, 5), pilot=(1, 1)), 2),     # pilot at (1, 2); element 14 is data, alone in its pair
 }
 _inputs = {}
 
@@ -96,10 +97,13 @@ def test_constellation_has_unit_mean_energy_and_a_gray_map(m):
 
 @pytest.mark.parametrize("m", BITS_PER_SYMBOL)
 def test_the_two_exact_extremes(m):
-    for name in ("default_120x14", "odd_30x7", "one_data_element_2x1", "no_data_element_1x1"):
+    for name in ("default_120x14", "odd_30x7", "one_data_element_2x1", "no_data_element_1x1", "odd_last_alone_3x5"):
         sim, keys, sigma, ideal, _ = link_inputs(name)
         cfg = LinkConfig(sim, m)
         zero = np.zeros_like(sigma)
+        if name == "odd_last_alone_3x5":           # the MSB of each axis flips at every m; a dropped last element would read (26, 13)
+            assert cfg.data_elements == 14 and cfg.data_mask[2, 4] and not cfg.data_mask[1, 2] and np.abs(ideal).min() > 0.5
+            assert link_errors_host(cfg, keys, ideal, -ideal, zero).tolist() == [[28, 14]] * 2
         counts, wrong, flags = link_errors_host(cfg, keys, ideal, ideal, zero, tau=TAU_CAP)
         assert counts.dtype == np.int64 and counts.shape == (len(keys), 2)
         assert not counts.any() and not wrong.any() and not flags.any()          # the estimate is the channel and there is no noise

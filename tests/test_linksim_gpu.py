@@ -10,6 +10,7 @@ The shapes (tests/test_linksim.py ``GRIDS``; estimates from ``lmmse_estimate_hos
     128 x 40, pilots 64 x 16, 2 frames            many elements per thread, the pilot lists at their bounds
     2 x 1, pilot 1 x 1, 1 frame                   one data element
     1 x 1, pilot 1 x 1, 1 frame                   no data element: counts (0, 0)
+    3 x 5, pilot 1 x 1 at (1, 2), 2 frames        an odd number of elements whose last is data: alone in the last pair
 
 The comparison rule.  A hard decision is a comparison ``comp >= beta_b p``; the device evaluates both sides in float32, so where the two
 sides are closer than its rounding error the decision may fall either way, and nowhere else.  The definition returns, per (element,
@@ -157,12 +158,14 @@ def test_kernel_against_the_float64_definition(m):
 
 @pytest.mark.parametrize("m", BITS_PER_SYMBOL)
 def test_exact_cases(m):
-    for name in ("default_120x14", "odd_30x7", "pilot_bounds_128x40", "one_data_element_2x1"):
+    for name in ("default_120x14", "odd_30x7", "pilot_bounds_128x40", "one_data_element_2x1", "odd_last_alone_3x5"):
         sim, keys, sigma, ideal, _ = link_inputs(name)
         cfg, plan, b = LinkConfig(sim, m), _plan(name, m), len(keys)
         k, h, zero = _dev(keys), _dev(ideal), torch.zeros(b, device=DEV)
         _poison_counts(b)
         assert not plan(h, h, k, zero).any()                                     # the estimate is the channel, no noise: no error
+        if name == "odd_last_alone_3x5":           # min |H| is 0.549: the MSB of each axis flips at every m; (26, 13) without element 14
+            assert plan(h, -h, k, zero).tolist() == [[28, 14]] * 2
         if m == 2:                                                               # the estimate points the other way: every bit flips
             assert plan(h, -h, k, zero).tolist() == [[2 * cfg.data_elements, cfg.data_elements]] * b
         # an estimate of exactly zero: both sides of every comparison are exact zeros, on the device and in the definition

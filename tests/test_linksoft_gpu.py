@@ -3,8 +3,8 @@ kernel's LLRs and losses against the float64 definition through the two derived 
 exact cases, independence of the batch, of the run and of the LLR output, operands in pinned memory, the 8- and 4-byte forms, no
 unwritten element, the checked build, the sweep without a synchronisation, the entry point's refusals.
 
-The shapes are tests/test_linksim_gpu.py's five (``GRIDS``: 120 x 14, odd 30 x 7, 128 x 40 with pilots 64 x 16, 2 x 1, 1 x 1) and, for the
-one path none of them takes with a data element -- a frame with an odd number of elements, whose last pair holds one -- 5 x 3.
+The shapes are tests/test_linksim_gpu.py's six (``GRIDS``: 120 x 14, odd 30 x 7, 128 x 40 with pilots 64 x 16, 2 x 1, 1 x 1, 3 x 5) and
+a second frame with an odd number of elements, whose last pair holds one: 5 x 3.
 
 The LLRs.  With u = 2^-24, every float32 operation within u of its result and no fast-math, in units of ``q = scale A (A p + 2 R)``
 (linksim's docstring: A the outermost level, R the reach of a component of c; every exact ``|mu_k| <= A (A p + 2 R) = Q``):
@@ -218,7 +218,8 @@ def test_exact_cases_through_the_entry_point_with_both_outputs_poisoned(m):
     """An estimate of exactly zero in frame 0: every metric is an exact zero, every LLR == 0 and every bit costs one bit.  Irregular
     pilot rows and columns: zeros exactly there.  Both outputs are filled with NaN first."""
     lib = _lib.load()
-    sims = [(name, _inputs(name)[0]) for name in ("default_120x14", "odd_30x7", ODD, "one_data_element_2x1", "no_data_element_1x1")]
+    sims = [(name, _inputs(name)[0]) for name in ("default_120x14", "odd_30x7", ODD, "one_data_element_2x1", "no_data_element_1x1",
+                                                  "odd_last_alone_3x5")]
     sims.append(("pilot_lists", ChannelSimConfig(pilot=(4, 3), pilot_scs=(0, 7, 118, 119), pilot_symbols=(0, 1, 13))))
     for name, sim in sims:
         cfg = LinkConfig(sim, m)
@@ -244,6 +245,8 @@ def test_exact_cases_through_the_entry_point_with_both_outputs_poisoned(m):
         _check_loss(cfg, got_loss, want)
         if name == "pilot_lists":
             assert (~cfg.data_mask).sum() == 12 and (got[1][cfg.data_mask] != 0).all()
+        if name == "odd_last_alone_3x5":           # element 14, alone in the last pair: written, and not with a pilot's zeros
+            assert cfg.data_mask[2, 4] and (got[1, 2, 4] != 0).all()
 
 
 @pytest.mark.parametrize("m", BITS_PER_SYMBOL)
