@@ -141,6 +141,37 @@ int check_blocks(const char *who, const aft_link &l, unsigned long long coded, u
     return AFT_OK;
 }
 
+// What both entry points with the QC-LDPC code ask of it: the base matrix's shape, the decoder's offset and max_iters, every shift of
+// the information part (host memory), a column without an entry, the number of entries
+bool ldpc_code_ok(const char *who, int base_rows, int base_cols, const int32_t *shifts, int offset, int max_iters) {
+    if (!within(who, "base_rows", base_rows, 3, 16) || !within(who, "base_cols", base_cols, base_rows + 1, 32) ||
+        !within(who, "offset", offset, 0, 127) || !within(who, "max_iters", max_iters, 1, 255))
+        return false;
+    const int kb = base_cols - base_rows;
+    int edges = 3 + 2 * (base_rows - 1);                        // the parity part
+    for (int j = 0; j < kb; ++j) {
+        int weight = 0;
+        for (int i = 0; i < base_rows; ++i) {
+            const int s = shifts[i * kb + j];
+            if (s < -1 || s >= AFT_LINK_LDPC_Z) {
+                set_error("%s: shifts[%d][%d] = %d is neither -1 nor a shift in 0..%d", who, i, j, s, AFT_LINK_LDPC_Z - 1);
+                return false;
+            }
+            weight += s >= 0 ? 1 : 0;
+        }
+        if (weight == 0) {
+            set_error("%s: base column %d has no entry", who, j);
+            return false;
+        }
+        edges += weight;
+    }
+    if (edges > AFT_LINK_LDPC_MAX_EDGES) {
+        set_error("%s: %d entries in the base matrix, parity part included; at most %d", who, edges, AFT_LINK_LDPC_MAX_EDGES);
+        return false;
+    }
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -245,31 +276,8 @@ int aft_link_ldpc_f32(const aft_link *link, const float *llr, const unsigned lon
     AFT_REQUIRE(std::isfinite(qgain) && qgain > 0.f, "link ldpc: qgain = %g must be finite and positive", (double)qgain);
     const int rc = check_link(who, *link);
     if (rc != AFT_OK) return rc;
-    if (!within(who, "base_rows", base_rows, 3, 16) || !within(who, "base_cols", base_cols, base_rows + 1, 32) ||
-        !within(who, "offset", offset, 0, 127) || !within(who, "max_iters", max_iters, 1, 255))
-        return AFT_ERR_SHAPE;
+    if (!ldpc_code_ok(who, base_rows, base_cols, shifts, offset, max_iters)) return AFT_ERR_SHAPE;
     const int kb = base_cols - base_rows;
-    int edges = 3 + 2 * (base_rows - 1);                        // the parity part
-    for (int j = 0; j < kb; ++j) {
-        int weight = 0;
-        for (int i = 0; i < base_rows; ++i) {
-            const int s = shifts[i * kb + j];
-            if (s < -1 || s >= AFT_LINK_LDPC_Z) {
-                set_error("%s: shifts[%d][%d] = %d is neither -1 nor a shift in 0..%d", who, i, j, s, AFT_LINK_LDPC_Z - 1);
-                return AFT_ERR_SHAPE;
-            }
-            weight += s >= 0 ? 1 : 0;
-        }
-        if (weight == 0) {
-            set_error("%s: base column %d has no entry", who, j);
-            return AFT_ERR_SHAPE;
-        }
-        edges += weight;
-    }
-    if (edges > AFT_LINK_LDPC_MAX_EDGES) {
-        set_error("%s: %d entries in the base matrix, parity part included; at most %d", who, edges, AFT_LINK_LDPC_MAX_EDGES);
-        return AFT_ERR_SHAPE;
-    }
     const unsigned long long coded = (unsigned long long)base_cols * AFT_LINK_LDPC_Z, info = (unsigned long long)kb * AFT_LINK_LDPC_Z;
     unsigned blocks = 0;
     const int rb = check_blocks(who, *link, coded, info, stride, stride_inverse, &blocks);
@@ -288,6 +296,38 @@ int aft_link_mrc_f32(const aft_link *link, const float *ideal, const float *est,
     hipError_t e = launch_link_mrc(*link, ideal, est, keys, sigma, rho, scale, factors, n_factors, branches, counts, loss, llr, batch,
                                    static_cast<hipStream_t>(stream));
     return e == hipSuccess ? AFT_OK : hip_fail("link_mrc", e);
+}
+
+int aft_link_harq_f32(const aft_link *link, const float *llr, const unsigned long long *keys, int base_rows, int base_cols,
+                      const int32_t *shifts, int tx_cols, int rounds, const int32_t *starts, unsigned long long stride,
+                      unsigned long long stride_inverse, float qgain, int offset, int max_iters, int32_t *counts, unsigned char *bits,
+                      int batch, void *stream) {
+    const char *who = "link harq";
+    AFT_REQUIRE(link && llr && keys && shifts && starts && counts, "link harq: NULL pointer argument");
+    AFT_REQUIRE(aligned(8, keys), "link harq: keys must be 8-byte aligned");
+    AFT_REQUIRE(aligned(4, llr, shifts, starts, counts), "link harq: llr, shifts, starts and counts must be 4-byte aligned");
+    AFT_REQUIRE(batch >= 1, "link harq: batch must be at least 1 (got %d)", batch);
+    AFT_REQUIRE(std::isfinite(qgain) && qgain > 0.f, "link harq: qgain = %g must be finite and positive", (double)qgain);
+    const int rc = check_link(who, *link);
+    if (rc != AFT_OK) return rc;
+    if (!within(who, "rounds", rounds, 1, AFT_LINK_HARQ_MAX_ROUNDS)) return AFT_ERR_SHAPE;
+    AFT_REQUIRE(batch % rounds == 0, "link harq: batch = %d is not a multiple of rounds = %d", batch, rounds);
+    if (!ldpc_code_ok(who, base_rows, base_cols, shifts, offset, max_iters)) return AFT_ERR_SHAPE;
+    const int kb = base_cols - base_rows;
+    if (!within(who, "tx_cols", tx_cols, kb + 1, base_cols)) return AFT_ERR_SHAPE;
+    for (int t = 0; t < rounds; ++t) {
+        if (starts[t] >= 0 && starts[t] < base_cols) continue;
+        set_error("%s: starts[%d] = %d is outside 0..%d", who, t, starts[t], base_cols - 1);
+        return AFT_ERR_SHAPE;
+    }
+    // a round's tx_cols block columns are what a block occupies on the link: B, U and the stride follow from them
+    const unsigned long long sent = (unsigned long long)tx_cols * AFT_LINK_LDPC_Z, info = (unsigned long long)kb * AFT_LINK_LDPC_Z;
+    unsigned blocks = 0;
+    const int rb = check_blocks(who, *link, sent, info, stride, stride_inverse, &blocks);
+    if (rb != AFT_OK) return rb;
+    hipError_t e = launch_link_harq(*link, llr, keys, base_rows, base_cols, shifts, tx_cols, rounds, starts, blocks, stride, qgain, offset,
+                                    max_iters, counts, bits, batch, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? AFT_OK : hip_fail("link_harq", e);
 }
 
 }  // extern "C"

@@ -397,6 +397,14 @@ int link_ldpc_waves(int base_cols, int edges, unsigned blocks);
 hipError_t launch_link_ldpc(const aft_link &link, const float *llr, const unsigned long long *keys, int base_rows, int base_cols,
                             const int32_t *shifts, unsigned blocks, unsigned long long stride, float qgain, int offset, int max_iters,
                             int32_t *counts, unsigned char *bits, int batch, hipStream_t st);
+// the HARQ link on that code (k_linkharq.hip): everything has passed aft_link_harq_f32's checks; shifts and starts [rounds] are host
+// tables read during the call; blocks = B of the definition; one workgroup per group of `rounds` frames, batch a multiple of it; bits
+// may be NULL.  link_harq_waves: the code blocks a workgroup holds at once (soft buffer, posteriors and messages fill LDS)
+int link_harq_waves(int base_cols, int edges, unsigned blocks);
+hipError_t launch_link_harq(const aft_link &link, const float *llr, const unsigned long long *keys, int base_rows, int base_cols,
+                            const int32_t *shifts, int tx_cols, int rounds, const int32_t *starts, unsigned blocks,
+                            unsigned long long stride, float qgain, int offset, int max_iters, int32_t *counts, unsigned char *bits,
+                            int batch, hipStream_t st);
 hipError_t launch_mse(const float *est, const float *ref, double *sum_sq, long long n_complex, hipStream_t st);
 hipError_t launch_fill_lds(float value, hipStream_t st);   // test hook: every CU's LDS filled with `value`
 hipError_t launch_peek_lds(float *out, int workgroups, int n, hipStream_t st);   // ... and what a kernel finds in its LDS at start

@@ -21,18 +21,13 @@
 //      all that is needed.  After an iteration lane c holds the hard word of block column c; the syndrome is lane reads only;
 //   5. a wave's three counts are sums over its blocks; the W waves' counts meet in LDS and three threads store the frame's triple.
 //
-// No atomics, no workspace: everything is integer after the quantiser, whose one float32 product and round-to-nearest-even are the
-// definition's.
-#include "linkcode_device.h"
+// Steps 2 and 4 -- the edge list, the codeword and the decoder -- are written once in linkldpc_device.h and shared with the HARQ link
+// (k_linkharq.hip).  No atomics, no workspace: everything is integer after the quantiser, whose one float32 product and
+// round-to-nearest-even are the definition's.
+#include "linkldpc_device.h"
 
 namespace aft {
 namespace {
-
-constexpr int kLdpcMaxWaves = 16;                               // waves (code blocks in flight) per workgroup
-constexpr int kLdpcMaxRows = 16, kLdpcMaxCols = 32;             // the base matrix
-constexpr size_t kLdpcLdsBudget = 150 * 1024;                   // posteriors and messages per workgroup (160 KiB less the static arrays)
-constexpr int kLdpcPosteriorMax = 8191, kLdpcMessageMax = 127;
-constexpr int kLdpcChunk = 4;                                   // edges of a layer whose LDS reads are in flight together
 
 struct LinkLdpcArgs {
     aft_link c;
@@ -43,49 +38,10 @@ struct LinkLdpcArgs {
     unsigned long long used, stride, used_inverse, stride64;    // U, the interleaver's stride, floor(2^64 / U), 64 stride mod U
     unsigned elems;                                             // S T - 1, as in k_link.hip
     unsigned blocks;                                            // B
-    int rows, cols, edges;                                      // mb, nb, the entries of the base matrix
     int offset, max_iters;
     float qgain;
-    unsigned short edge[AFT_LINK_LDPC_MAX_EDGES];               // layer by layer, columns increasing: column << 6 | shift
-    unsigned char first[kLdpcMaxRows + 1];                      // layer i's edges are first[i] .. first[i + 1] - 1
+    LdpcEdges base;                                             // mb, nb and the entries of the base matrix, layer by layer
 };
-
-__device__ __forceinline__ unsigned long long rot64(unsigned long long x, unsigned s) {       // rot(x, s)[r] = x[(r + s) mod 64]
-    return x >> s | x << ((64u - s) & 63u);
-}
-
-// A wave's LDS writes become visible to its own later reads from other lanes: requests of one wave are served in order, so this
-// only keeps the compiler from moving accesses across it.
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// A layer's edges, one per lane (a row has at most 32): a lane read makes an edge's word wave-uniform without an LDS round trip.
-struct LayerEdges {
-    int e0, deg, mine;
-    __device__ __forceinline__ unsigned word(int e) const { return (unsigned)__builtin_amdgcn_readlane(mine, e); }
-    // the variable of row `lane` on edge e: 64 column + ((lane + shift) mod 64)
-    __device__ __forceinline__ unsigned variable(int e, int lane) const {
-        const unsigned ed = word(e);
-        return (ed & ~63u) | (((unsigned)lane + ed) & 63u);
-    }
-};
-__device__ __forceinline__ LayerEdges layer_edges(const unsigned short *edge, const int *first, int i, int lane, int nb) {
-    LayerEdges le;
-    le.e0 = __builtin_amdgcn_readfirstlane(first[i]);
-    le.deg = __builtin_amdgcn_readfirstlane(first[i + 1]) - le.e0;
-    AFT_DEV_ASSERT(le.deg >= 2 && le.deg <= kLdpcMaxCols);
-    le.mine = lane < le.deg ? (int)edge[le.e0 + lane] : 0;
-    AFT_DEV_ASSERT((le.mine >> 6) < nb);                        // every variable it names lies inside the block's n posteriors
-    return le;
-}
-
-// the 64-bit word lane `c` holds in (lo, hi), wave-uniform
-__device__ __forceinline__ unsigned long long lane_word(int lo, int hi, int c) {
-    return (unsigned long long)(unsigned)__builtin_amdgcn_readlane(hi, c) << 32 | (unsigned)__builtin_amdgcn_readlane(lo, c);
-}
 
 __global__ __launch_bounds__(kLdpcMaxWaves *kWave) void link_ldpc_kernel(const LinkLdpcArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char state_all[];    // [waves]: posteriors int16 [n], messages int8 [edges][64]
@@ -100,14 +56,12 @@ __global__ __launch_bounds__(kLdpcMaxWaves *kWave) void link_ldpc_kernel(const L
     const int wave = __builtin_amdgcn_readfirstlane(tid / kWave);
     const size_t f = blockIdx.x;
     const int Ps = c.pilot_scs, Pt = c.pilot_symbols, m = c.bits_per_symbol;
-    const int mb = a.rows, nb = a.cols, kb = nb - mb, mid = mb / 2, edges = a.edges;
+    const int mb = a.base.rows, nb = a.base.cols, kb = nb - mb, edges = a.base.edges;
     const unsigned T = (unsigned)c.num_symbols, n = (unsigned)nb * kWave, K = (unsigned)kb * kWave;
     AFT_DEV_ASSERT(Ps >= 1 && Ps <= AFT_CHANSIM_MAX_PILOT_SCS && Pt >= 1 && Pt <= AFT_CHANSIM_MAX_PILOT_SYMBOLS && (unsigned)Pt <= T);
-    AFT_DEV_ASSERT(waves >= 1 && waves <= kLdpcMaxWaves && mb >= 3 && mb <= kLdpcMaxRows && nb > mb && nb <= kLdpcMaxCols);
-    AFT_DEV_ASSERT(edges >= 2 * mb && edges <= AFT_LINK_LDPC_MAX_EDGES && a.first[mb] == edges);
+    AFT_DEV_ASSERT(waves >= 1 && waves <= kLdpcMaxWaves);
     code_pilot_tables(c, tid, psc, before, psym);
-    for (int i = tid; i < edges; i += (int)blockDim.x) edge[i] = a.edge[i];
-    if (tid <= mb) first[tid] = a.first[tid];
+    ldpc_edge_tables(a.base, tid, (int)blockDim.x, edge, first);
     __syncthreads();
     const unsigned long long kf = a.keys[f];
     const float *llr = a.llr + f * ((size_t)a.elems + 1) * (size_t)m;
@@ -118,36 +72,8 @@ __global__ __launch_bounds__(kLdpcMaxWaves *kWave) void link_ldpc_kernel(const L
 
     int bit_errors = 0, block_errors = 0, iterations = 0;
     for (unsigned b = (unsigned)wave; b < a.blocks; b += (unsigned)waves) {
-        // the codeword: the information words from the hash, lam_i into `hard` for the moment, then the parity words
-        const unsigned info0 = b * K;                           // B K <= 2^31: the hash's index does not wrap
-        for (int j = 0; j < kb; ++j) {
-            const unsigned long long w = __ballot((frame_word(kf, kStreamCodeBits, info0 + (unsigned)(j * kWave + lane)) >> 63) != 0);
-            if (lane == 0) sent[j] = w;
-        }
-        wave_sync();
-        unsigned long long p0 = 0;
-        for (int i = 0; i < mb; ++i) {
-            unsigned long long lam = 0;
-            for (int e = first[i]; e < first[i + 1]; ++e) {
-                const unsigned ed = edge[e];
-                if ((int)(ed >> 6) < kb) lam ^= rot64(sent[ed >> 6], ed & 63u);
-            }
-            if (lane == 0) hard[i] = lam;
-            p0 ^= lam;
-        }
-        wave_sync();
-        {
-            unsigned long long p = hard[0] ^ rot64(p0, 1);      // p_1
-            if (lane == 0) {
-                sent[kb] = p0;
-                sent[kb + 1] = p;
-            }
-            for (int i = 1; i < mb - 1; ++i) {
-                p ^= hard[i] ^ (i == mid ? p0 : 0ull);
-                if (lane == 0) sent[kb + i + 1] = p;
-            }
-        }
-        wave_sync();
+        // the codeword: the information words from the hash, then the parity words.  B K <= 2^31: the hash's index does not wrap
+        ldpc_codeword(kf, b * K, edge, first, mb, nb, sent, hard, lane);
 
         // the inputs: coded bit i = 64 col + lane of the block sits at j = (b n + i) stride mod U
         unsigned long long j = code_mulmod((unsigned long long)b * n + (unsigned)lane, a.stride, a.used, a.used_inverse);
@@ -166,91 +92,17 @@ __global__ __launch_bounds__(kLdpcMaxWaves *kWave) void link_ldpc_kernel(const L
         for (int e = 0; e < edges; ++e) R[e * kWave + lane] = 0;
         wave_sync();
 
-        int ran = 0, hard_lo = 0, hard_hi = 0;                  // lane c holds the hard bits of block column c after an iteration
-        for (int it = 1; it <= a.max_iters; ++it) {
-            for (int i = 0; i < mb; ++i) {
-                const LayerEdges le = layer_edges(edge, first, i, lane, nb);
-                signed char *Rl = R + le.e0 * kWave + lane;
-                int m1 = 1 << 20, m2 = 1 << 20, at = -1;
-                bool tot = false;
-                for (int e = 0; e < le.deg; e += kLdpcChunk) {  // the chunk's loads are issued together: one LDS round trip, not four
-                    int q[kLdpcChunk];
-#pragma unroll
-                    for (int k = 0; k < kLdpcChunk; ++k) {
-                        const int ee = min(e + k, le.deg - 1);  // past the end: the last edge again, ignored below
-                        q[k] = (int)L[le.variable(ee, lane)] - (int)Rl[ee * kWave];
-                    }
-#pragma unroll
-                    for (int k = 0; k < kLdpcChunk; ++k) {
-                        const bool valid = e + k < le.deg;
-                        const int mag = valid ? (q[k] < 0 ? -q[k] : q[k]) : 1 << 20;
-                        tot ^= valid && q[k] < 0;
-                        if (mag < m1) {                         // the lowest e that attains the minimum
-                            m2 = m1;
-                            m1 = mag;
-                            at = e + k;
-                        } else if (mag < m2) {
-                            m2 = mag;
-                        }
-                    }
-                }
-                const int out1 = min(max(m1 - a.offset, 0), kLdpcMessageMax), out2 = min(max(m2 - a.offset, 0), kLdpcMessageMax);
-                for (int e = 0; e < le.deg; e += kLdpcChunk) {
-                    int q[kLdpcChunk];
-                    unsigned v[kLdpcChunk];
-#pragma unroll
-                    for (int k = 0; k < kLdpcChunk; ++k) {
-                        const int ee = min(e + k, le.deg - 1);
-                        v[k] = le.variable(ee, lane);
-                        q[k] = (int)L[v[k]] - (int)Rl[ee * kWave];
-                    }
-#pragma unroll
-                    for (int k = 0; k < kLdpcChunk; ++k) {
-                        if (e + k >= le.deg) break;             // wave-uniform
-                        const int mag = e + k == at ? out2 : out1;
-                        const int r = (tot != (q[k] < 0)) ? -mag : mag;
-                        Rl[(e + k) * kWave] = (signed char)r;
-                        L[v[k]] = (short)min(max(q[k] + r, -kLdpcPosteriorMax), kLdpcPosteriorMax);
-                    }
-                }
-                wave_sync();                                    // the next layer reads what other lanes wrote
-            }
-            ran = it;
-            for (int col = 0; col < nb; col += kLdpcChunk) {
-                short l[kLdpcChunk];
-#pragma unroll
-                for (int k = 0; k < kLdpcChunk; ++k) l[k] = L[min(col + k, nb - 1) * kWave + lane];
-#pragma unroll
-                for (int k = 0; k < kLdpcChunk; ++k) {          // past the last column: a lane whose word is never read
-                    const unsigned long long w = __ballot(l[k] < 0);
-                    if (lane == col + k) {
-                        hard_lo = (int)(unsigned)w;
-                        hard_hi = (int)(unsigned)(w >> 32);
-                    }
-                }
-            }
-            unsigned long long unsatisfied = 0;                 // wave-uniform: lane reads of the edges and of the hard words
-            for (int i = 0; i < mb; ++i) {
-                const LayerEdges le = layer_edges(edge, first, i, lane, nb);
-                unsigned long long s = 0;
-                for (int e = 0; e < le.deg; ++e) {
-                    const unsigned ed = le.word(e);
-                    s ^= rot64(lane_word(hard_lo, hard_hi, (int)(ed >> 6)), ed & 63u);
-                }
-                unsatisfied |= s;
-            }
-            if (unsatisfied == 0) break;
-        }
+        const LdpcDecoded d = ldpc_min_sum(L, R, edge, first, mb, nb, a.offset, a.max_iters, lane);
 
         unsigned long long wrong_any = 0;
         for (int col = 0; col < kb; ++col) {
-            const unsigned long long got = lane_word(hard_lo, hard_hi, col), wrong = got ^ sent[col];
+            const unsigned long long got = lane_word(d.hard_lo, d.hard_hi, col), wrong = got ^ sent[col];
             bit_errors += __popcll(wrong);
             wrong_any |= wrong;
             if (a.bits != nullptr) a.bits[(f * a.blocks + b) * (size_t)K + (unsigned)(col * kWave + lane)] = (unsigned char)(got >> lane & 1ull);
         }
         block_errors += wrong_any != 0 ? 1 : 0;
-        iterations += ran;
+        iterations += d.ran;
         wave_sync();                                            // the next block's words go where these were read
     }
     if (lane == 0) {
@@ -266,12 +118,13 @@ __global__ __launch_bounds__(kLdpcMaxWaves *kWave) void link_ldpc_kernel(const L
     }
 }
 
+size_t ldpc_state_bytes(int base_cols, int edges) {             // a block's posteriors and messages
+    return (size_t)base_cols * kWave * sizeof(short) + (size_t)edges * kWave;
+}
+
 }  // namespace
 
-int link_ldpc_waves(int base_cols, int edges, unsigned blocks) {
-    const size_t per_wave = (size_t)base_cols * kWave * sizeof(short) + (size_t)edges * kWave;
-    return (int)std::min<size_t>({(size_t)kLdpcMaxWaves, (size_t)blocks, std::max<size_t>(kLdpcLdsBudget / per_wave, 1)});
-}
+int link_ldpc_waves(int base_cols, int edges, unsigned blocks) { return ldpc_waves(ldpc_state_bytes(base_cols, edges), blocks); }
 
 hipError_t launch_link_ldpc(const aft_link &link, const float *llr, const unsigned long long *keys, int base_rows, int base_cols,
                             const int32_t *shifts, unsigned blocks, unsigned long long stride, float qgain, int offset, int max_iters,
@@ -281,30 +134,14 @@ hipError_t launch_link_ldpc(const aft_link &link, const float *llr, const unsign
     a.llr = llr; a.keys = keys; a.counts = counts; a.bits = bits;
     a.elems = (unsigned)((unsigned long long)link.num_scs * (unsigned long long)link.num_symbols - 1);
     a.blocks = blocks;
-    a.rows = base_rows; a.cols = base_cols; a.offset = offset; a.max_iters = max_iters; a.qgain = qgain;
+    a.offset = offset; a.max_iters = max_iters; a.qgain = qgain;
     a.used = (unsigned long long)blocks * (unsigned long long)(base_cols * kWave);
     a.stride = stride;
     a.stride64 = (unsigned long long)((unsigned __int128)stride * kWave % a.used);
     a.used_inverse = (unsigned long long)(((unsigned __int128)1 << 64) / a.used);      // used >= 256
-    // the edges layer by layer: the information part from the table, then the parity part (linksim.py "parity part")
-    const int kb = base_cols - base_rows, mid = base_rows / 2;
-    int edges = 0;
-    for (int i = 0; i < base_rows; ++i) {
-        a.first[i] = (unsigned char)edges;
-        for (int j = 0; j < base_cols; ++j) {
-            int s = -1;
-            if (j < kb) s = shifts[i * kb + j];
-            else if (j == kb) s = (i == 0 || i == base_rows - 1) ? 1 : i == mid ? 0 : -1;
-            else if (j - kb - 1 == i || j - kb == i) s = 0;     // column kb + 1 + t holds rows t and t + 1
-            if (s < 0) continue;
-            if (edges == AFT_LINK_LDPC_MAX_EDGES) return hipErrorInvalidValue;         // aft_link_ldpc_f32 has counted them
-            a.edge[edges++] = (unsigned short)(j << 6 | s);
-        }
-    }
-    a.first[base_rows] = (unsigned char)edges;
-    a.edges = edges;
-    const int waves = link_ldpc_waves(base_cols, edges, blocks);
-    const size_t lds = (size_t)waves * ((size_t)base_cols * kWave * sizeof(short) + (size_t)edges * kWave);
+    if (!ldpc_edge_list(base_rows, base_cols, shifts, a.base)) return hipErrorInvalidValue;   // aft_link_ldpc_f32 has counted them
+    const int waves = link_ldpc_waves(base_cols, a.base.edges, blocks);
+    const size_t lds = (size_t)waves * ldpc_state_bytes(base_cols, a.base.edges);
     static PerDeviceOnce lds_attr;
     const hipError_t e = ensure_dynamic_lds(lds_attr, reinterpret_cast<const void *>(link_ldpc_kernel), kLdpcLdsBudget);
     if (e != hipSuccess) return e;

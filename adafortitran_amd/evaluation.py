@@ -18,7 +18,8 @@ from typing import Dict, Iterable, List, Optional, Tuple
 import torch
 
 from .estimators import AdaFortiTranEstimator
-from .linksim import DEFAULT_FACTORS, BlockErrorAccumulator, LdpcBlockErrorAccumulator, LdpcConfig, LinkAccumulator, RateAccumulator
+from .linksim import (DEFAULT_FACTORS, BlockErrorAccumulator, HarqAccumulator, LdpcBlockErrorAccumulator, LdpcConfig, LinkAccumulator,
+                      RateAccumulator)
 from .lmmse import LmmseEstimator
 from .metrics import MseAccumulator, to_db
 
@@ -106,3 +107,15 @@ def get_link_bler(model: Optional[torch.nn.Module], test_dataloaders: List[Tuple
     accumulator = LdpcBlockErrorAccumulator if isinstance(code_cfg, LdpcConfig) else BlockErrorAccumulator
     return _link_sweep(model, test_dataloaders, lambda device: accumulator(code_cfg, device, seed, err_var, branches),
                        lambda acc: acc.result(group))
+
+
+def get_link_harq(model: Optional[torch.nn.Module], test_dataloaders: List[Tuple[str, Iterable]], harq_cfg, seed: int = 0,
+                  err_var: float = 0.0, group=None, branches: int = 1) -> Dict[int, float]:
+    """Throughput per loader under hybrid ARQ, in delivered information bits per data element sent (``linksim``: "The HARQ link"):
+    ``harq_cfg`` (``linksim.HarqConfig``) rate-matches an LDPC mother code, every ``rounds`` consecutive frames of a batch -- after the
+    combiner, with ``branches`` -- are the transmission rounds of one set of blocks, and a block is sent again until it decodes;
+    ``model=None`` is perfect channel knowledge.  Sorting, keys and the frames' bits and noise as ``get_link_stats``; the counts
+    accumulate on the device (``linksim.HarqAccumulator``) and are read once per loader.  Every batch holds a multiple of
+    ``branches * rounds`` frames."""
+    return _link_sweep(model, test_dataloaders, lambda device: HarqAccumulator(harq_cfg, device, seed, err_var, branches),
+                       lambda acc: acc.result_throughput(group))

@@ -592,11 +592,13 @@ class LinkMrcPlan(LinkPlan):
 
 
 class _DecoderPlan:
-    """What the two decoder plans share: the code's link struct and LLR shape, and a call that checks ``llr`` and ``keys``, allocates
-    ``counts int32 [batch, width]`` and, when asked for, ``bits uint8 [batch, B, K]``, and makes the one ``ctypes`` call.  A subclass
+    """What the decoder plans share: the code's link struct and LLR shape, and a call that checks ``llr`` and ``keys``, allocates
+    ``counts int32 [groups, width]`` and, when asked for, ``bits uint8 [groups, B, K]`` (a group is one frame, or the HARQ link's
+    ``rounds`` frames), and makes the one ``ctypes`` call.  A subclass
     names its config type, its CPU path, its entry point and the width of its counts, and gives the code's arguments as ``self.args``."""
     config = cpu_path = entry = None
     width = 2
+    frames_per_group = 1                                        # the frames behind one row of counts (the HARQ link: its rounds)
 
     def __init__(self, code, device: torch.device) -> None:
         from . import linksim
@@ -619,8 +621,11 @@ class _DecoderPlan:
         batch = llr.shape[0]
         llr = llr.contiguous()                                  # held by the caller until after the launch is enqueued
         keys = _in_place("keys", keys, torch.int64, self.device, batch)
-        counts = torch.empty((batch, self.width), dtype=torch.int32, device=self.device)    # the kernel writes every element
-        bits = torch.empty((batch, self.code.blocks, self.code.info_bits), dtype=torch.uint8, device=self.device) if want_bits else None
+        if batch % self.frames_per_group:
+            raise ValueError(f"a batch of {batch} frames is not a multiple of rounds = {self.frames_per_group}")
+        groups = batch // self.frames_per_group
+        counts = torch.empty((groups, self.width), dtype=torch.int32, device=self.device)   # the kernel writes every element
+        bits = torch.empty((groups, self.code.blocks, self.code.info_bits), dtype=torch.uint8, device=self.device) if want_bits else None
         _lib.check(getattr(lib, self.entry)(C.byref(self.link), llr.data_ptr(), keys.data_ptr(), *self.args, counts.data_ptr(), _ptr(bits),
                                             batch, _lib.current_stream_ptr(self.device)), lib)
         return counts, bits
@@ -652,6 +657,25 @@ class LinkLdpcPlan(_DecoderPlan):
         self.shifts = (C.c_int32 * (code.base_rows * kb))(*(v for row in code.shifts for v in row))      # host memory, read per call
         self.args = (code.base_rows, code.base_cols, C.addressof(self.shifts), code.stride, code.stride_inverse, code.qgain, code.offset,
                      code.max_iters)
+
+
+class LinkHarqPlan(_DecoderPlan):
+    """A HARQ link (``linksim.HarqConfig``) turned into ``aft_link_harq_f32``'s arguments ONCE.  ``plan(llr, keys, want_bits=False)`` ->
+    ``(counts int32 [G, 7], bits uint8 [G, B, K] or None)`` for the ``G = batch / rounds`` groups on the plan's device (``linksim``:
+    "The HARQ link" names the seven columns): one ``ctypes`` call, one launch on the current stream, no synchronisation.  ``llr``
+    float32 ``[batch,S,T,m]`` and ``keys`` as ``LinkDecodePlan``'s, ``batch`` a multiple of ``rounds``; the shift and start tables are
+    host arrays kept on the plan.  The plan trusts its caller in one thing only: its device is the current one."""
+    config, cpu_path, entry, width = "HarqConfig", "linksim.link_harq_host", "aft_link_harq_f32", _abi.AFT_LINK_HARQ_COUNTS
+
+    def __init__(self, harq, device: torch.device) -> None:
+        super().__init__(harq, device)
+        code = harq.code
+        kb = code.base_cols - code.base_rows
+        self.frames_per_group = harq.rounds
+        self.shifts = (C.c_int32 * (code.base_rows * kb))(*(v for row in code.shifts for v in row))      # host memory, read per call
+        self.starts = (C.c_int32 * harq.rounds)(*harq.starts)
+        self.args = (code.base_rows, code.base_cols, C.addressof(self.shifts), harq.tx_cols, harq.rounds, C.addressof(self.starts),
+                     harq.stride, harq.stride_inverse, code.qgain, code.offset, code.max_iters)
 
 
 def ls_mse_db(ls: torch.Tensor, ideal: torch.Tensor) -> torch.Tensor:

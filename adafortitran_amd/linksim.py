@@ -157,6 +157,39 @@ convolutional code's::
 Messages fit int8 and posteriors int16.  Rows of one layer share no variable (a block column holds at most one block per layer, and
 a circulant is a permutation), so the order of a layer's rows does not matter: tests/test_linkldpc.py decodes row by row over the
 expanded matrix and compares for equality.
+
+The HARQ link.  Every coded number above is a single-shot block-error rate at a fixed code rate.  A data channel runs hybrid ARQ: a
+block that fails is sent again, and the receiver adds the new soft bits to the old ones and decodes again, so an estimator's gain
+shows as fewer retransmissions and as throughput at SNRs where the single-shot rate is 1 for every estimator.  ``HarqConfig``,
+``link_harq_host`` (integer NumPy), ``aft_link_harq_f32`` (csrc/k_linkharq.hip, through ``hip_ops.LinkHarqPlan``), ``HarqAccumulator``
+and ``evaluation.get_link_harq`` are that surface::
+
+    mother code   an LdpcConfig ``code``: base matrix mb x nb, kb = nb - mb, n = 64 nb, K = 64 kb; encoder and decoder unchanged.  It
+                  must itself be valid on the link (N >= n); its own stride and blocks are not used
+    rate matching tx_cols = C with kb < C <= nb: a round sends E = 64 C coded bits per block.  rounds = Q in 1 .. 4
+                  (AFT_LINK_HARQ_MAX_ROUNDS).  starts = (s_0 .. s_{Q-1}), each in 0 .. nb-1: the block column where a round's window
+                  begins.  Transmitted bit e = 0 .. E-1 of round t is codeword bit v_t(e) = 64 ((s_t + e // 64) mod nb) + e % 64: a
+                  circular buffer in whole block columns.  mode "ir" (incremental redundancy) gives s_t = (t C) mod nb, each round
+                  continuing where the last ended; mode "chase" gives s_t = 0
+    position      N = m data_elements bits per frame, B = N // E blocks (B K <= 2^31), U = B E.  Transmitted bit e of block b sits at
+                  data-bit index j = ((b E + e) A) mod U, A the golden-section default_stride(U) or a given stride coprime to U; j maps
+                  to a grid element and a bit of its word exactly as on the coded links; filler and pilots are never read
+    groups        the LLR frames h Q .. h Q + Q - 1 (keys k_0 .. k_{Q-1}) are rounds 0 .. Q-1 of group h, k_0 its LEADER.
+                  u[b][i] = word(k_0, stream 8, b K + i) >> 63 and c = ldpc_encode(u).  Round t uses its OWN frame's sent words, w
+                  from stream 5 of k_t: scrambler s = w_j ^ c[v_t(e)], z_{t,b,e} = quantise((1 - 2 s) llr_t[j]) with the code's qgain
+    soft buffer   Z_t[b][v] = the sum over t' <= t and over e with v_{t'}(e) = v of z_{t',b,e}: an integer, |Z| <= 127 Q, 0 where
+                  nothing has been sent yet
+    attempts      after round t every block not yet acknowledged is decoded from scratch, L = Z_t and R = 0, with the offset,
+                  max_iters, layer order, clamps and syndrome stop rule of the LDPC-coded link.  A block is ACKNOWLEDGED iff its
+                  decoded information bits equal u -- an ideal CRC: a wrong codeword that satisfies the syndrome is not acknowledged.
+                  An acknowledged block runs no further attempt; later rounds' LLRs at its positions influence nothing
+    counts        int [groups][7] (AFT_LINK_HARQ_COUNTS): columns 0 .. 3 the blocks first acknowledged after round t (0 for t >= Q),
+                  4 the information-bit errors of the blocks never acknowledged, from their last attempt, 5 the blocks never
+                  acknowledged, 6 the iterations summed over all attempts run
+    bits          uint8 [groups, B, K]: each block's decoded information bits from the last attempt it ran
+
+With Q = 1, C = nb, s_0 = 0 and the same stride this is the LDPC-coded link: column 0 is B less its block errors, columns 4, 5 and 6
+its bit errors, block errors and iterations, and the bits are equal bit for bit.
 """
 from __future__ import annotations
 
@@ -1256,3 +1289,219 @@ class LdpcBlockErrorAccumulator(BlockErrorAccumulator):
         """Mean decoder iterations per block over all ranks; 0.0 for an empty sweep."""
         _, _, iterations, frames = self._read(group)
         return iterations / (frames * self.code.blocks) if frames > 0 else 0.0
+
+
+# ---- the HARQ link (module docstring, "The HARQ link"): integer NumPy, mirrored by csrc/k_linkharq.hip ----
+
+HARQ_MAX_ROUNDS = _abi.AFT_LINK_HARQ_MAX_ROUNDS
+HARQ_COUNTS = _abi.AFT_LINK_HARQ_COUNTS
+HARQ_MODES = ("ir", "chase")
+
+
+@dataclass(frozen=True)
+class HarqConfig:
+    """Hybrid ARQ on an LDPC-coded link: the mother code ``code`` (an ``LdpcConfig``, valid on its link), ``tx_cols`` = C of its nb block
+    columns per round, ``rounds`` = Q, the windows' ``starts`` (None: those of ``mode``, "ir" continuing round by round or "chase"
+    repeating the first) and the interleaver's ``stride`` over the ``B E`` used bits (None: the golden-section default).  Derives
+    ``tx_bits`` E, ``blocks`` B, ``used_bits`` U, ``stride_inverse``, ``info_bits_per_frame``, ``windows()`` and ``positions()``;
+    refuses what ``aft_link_harq_f32`` refuses."""
+    code: LdpcConfig
+    tx_cols: int
+    rounds: int = HARQ_MAX_ROUNDS
+    starts: Optional[tuple] = None
+    mode: str = "ir"
+    stride: Optional[int] = None
+
+    def __post_init__(self) -> None:
+        if not isinstance(self.code, LdpcConfig):
+            raise ValueError(f"HarqConfig needs an LdpcConfig as its mother code (got {type(self.code).__name__})")
+        mb, nb = self.code.base_rows, self.code.base_cols
+        kb = nb - mb
+        for name, lo, hi in (("tx_cols", kb + 1, nb), ("rounds", 1, HARQ_MAX_ROUNDS)):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+                raise ValueError(f"{name} = {v!r}: an integer in {lo} .. {hi}")
+            object.__setattr__(self, name, int(v))
+        if self.mode not in HARQ_MODES:
+            raise ValueError(f"mode = {self.mode!r}: one of {HARQ_MODES}")
+        if self.starts is None:
+            starts = [(t * self.tx_cols) % nb if self.mode == "ir" else 0 for t in range(self.rounds)]
+        else:
+            try:
+                starts = list(self.starts)
+            except TypeError:
+                raise ValueError(f"starts = {self.starts!r}: {self.rounds} block columns, one per round") from None
+            if len(starts) != self.rounds:
+                raise ValueError(f"starts = {self.starts!r}: {self.rounds} block columns, one per round")
+            for s in starts:
+                if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or not 0 <= int(s) < nb:
+                    raise ValueError(f"starts = {self.starts!r}: every start is a block column in 0 .. {nb - 1}")
+        object.__setattr__(self, "starts", tuple(int(s) for s in starts))
+        if self.blocks == 0:
+            raise ValueError(f"a frame carries {self.link.bits_per_frame} bits, fewer than the {self.tx_bits} coded bits of one block")
+        if self.info_bits_per_frame > 1 << 31:
+            raise ValueError(f"{self.blocks} blocks of {self.info_bits} information bits: more than 2^31, where the hash's index and the "
+                             f"int32 counts end")
+        U = self.used_bits
+        a = default_stride(U) if self.stride is None else self.stride
+        if isinstance(a, bool) or not isinstance(a, (int, np.integer)) or not 1 <= int(a) < U:
+            raise ValueError(f"stride = {a!r}: an integer in [1, {U})")
+        if math.gcd(int(a), U) != 1:
+            raise ValueError(f"stride = {a} is not coprime to the {U} used bits")
+        object.__setattr__(self, "stride", int(a))
+
+    @property
+    def link(self) -> LinkConfig:
+        return self.code.link
+
+    @property
+    def info_bits(self) -> int:
+        return self.code.info_bits
+
+    @property
+    def tx_bits(self) -> int:
+        """E: the coded bits of a block one round sends."""
+        return LDPC_Z * self.tx_cols
+
+    @property
+    def blocks(self) -> int:
+        return self.link.bits_per_frame // self.tx_bits
+
+    @property
+    def used_bits(self) -> int:
+        return self.blocks * self.tx_bits
+
+    @property
+    def stride_inverse(self) -> int:
+        return pow(self.stride, -1, self.used_bits)
+
+    @property
+    def info_bits_per_frame(self) -> int:
+        return self.blocks * self.info_bits
+
+    def windows(self) -> np.ndarray:
+        """int64 ``[Q, E]``: the codeword bit ``v_t(e)`` behind transmitted bit ``e`` of round ``t``."""
+        e = np.arange(self.tx_bits, dtype=np.int64)
+        s = np.asarray(self.starts, dtype=np.int64)[:, None]
+        return LDPC_Z * ((s + e[None, :] // LDPC_Z) % self.code.base_cols) + e[None, :] % LDPC_Z
+
+    def positions(self) -> np.ndarray:
+        """int64 ``[B, E]``: the data-bit index ``j = ((b E + e) stride) mod U`` of transmitted bit ``e`` of block ``b``."""
+        U, p = self.used_bits, np.arange(self.used_bits, dtype=np.int64)
+        if U <= 1 << 31:
+            j = (p * np.int64(self.stride)) % np.int64(U)
+        else:
+            j = np.array([(int(v) * self.stride) % U for v in p], dtype=np.int64)
+        return j.reshape(self.blocks, self.tx_bits)
+
+
+def link_harq_host(harq: HarqConfig, keys, llr) -> Tuple[np.ndarray, np.ndarray]:
+    """The HARQ link's definition on ``llr`` ``[G Q, S, T, m]``, taken as the float32 numbers it rounds to, with the ``G Q`` ``keys``:
+    ``(counts int64 [G, 7], bits uint8 [G, B, K])`` (module docstring, "The HARQ link").  Needs no library."""
+    if not isinstance(harq, HarqConfig):
+        raise ValueError(f"link_harq_host needs a HarqConfig (got {type(harq).__name__})")
+    keys = _keys64(keys)
+    code, cfg, Q = harq.code, harq.link, harq.rounds
+    (S, T), m, nf = cfg.sim.ofdm, cfg.bits_per_symbol, len(keys)
+    if nf == 0 or nf % Q:
+        raise ValueError(f"a batch of {nf} frames is not a positive multiple of rounds = {Q}")
+    llr = np.asarray(llr)
+    if llr.shape != (nf, S, T, m):
+        raise ValueError(f"Expected llr of shape ({nf}, {S}, {T}, {m}), got {llr.shape}")
+    llr = llr.astype(np.float32).reshape(nf, S * T, m)
+    G, B, K = nf // Q, harq.blocks, harq.info_bits
+    index = np.arange(B * K, dtype=np.uint64).reshape(1, B, K)
+    info = (words(keys[::Q, None, None], STREAM_CODE_BITS, index) >> np.uint64(63)).astype(np.uint8)     # the leaders'
+    sent = ldpc_encode(code, info)                                                # [G, B, n]
+    j = harq.positions()                                                          # [B, E]
+    q, k = np.flatnonzero(cfg.data_mask)[j // m], j % m
+    Z = np.zeros((G, B, code.coded_bits), dtype=np.int32)
+    acked = np.zeros((G, B), dtype=bool)
+    bits = np.zeros((G, B, K), dtype=np.uint8)
+    counts = np.zeros((G, HARQ_COUNTS), dtype=np.int64)
+    for t, v in enumerate(harq.windows()):                                        # a round's window holds every variable at most once
+        kt = keys[t::Q]
+        w = (words(kt[:, None, None], STREAM_DATA_BITS, q[None].astype(np.uint64)) >> (np.uint64(63) - k[None].astype(np.uint64))) & np.uint64(1)
+        scrambler = w.astype(np.uint8) ^ sent[:, :, v]
+        at = llr[t::Q][:, q, k]                                                   # [G, B, E]
+        Z[:, :, v] += quantise(np.where(scrambler == 1, -at, at), code.qgain)
+        todo = ~acked
+        if not todo.any():
+            break
+        got, iterations = ldpc_decode_host(code, Z[todo])
+        bits[todo] = got
+        ok = (got == info[todo]).all(axis=-1)
+        ran = np.zeros((G, B), dtype=np.int64)
+        ran[todo] = iterations
+        counts[:, 6] += ran.sum(axis=1)
+        first = np.zeros((G, B), dtype=bool)
+        first[todo] = ok
+        counts[:, t] = first.sum(axis=1)
+        acked |= first
+    wrong = (bits != info) & ~acked[:, :, None]
+    counts[:, 4] = wrong.sum(axis=(1, 2))
+    counts[:, 5] = (~acked).sum(axis=1)
+    return counts, bits
+
+
+class HarqAccumulator(BlockErrorAccumulator):
+    """A sweep under hybrid ARQ (module docstring, "The HARQ link") with ``BlockErrorAccumulator``'s ``update`` surface: a batch holds a
+    multiple of ``branches * rounds`` frames; the link's LLRs -- the combiner's, with branches -- and the leaders' keys are grouped
+    ``rounds`` at a time.  On a HIP device a batch is the launch that writes the LLRs, the launch of ``aft_link_harq_f32`` on that
+    tensor and one integer add into an int64 ``[7]`` device tensor; nothing synchronises.  On a CPU device the host definitions run.
+    ``result`` is the residual block-error rate after all rounds, ``result_bler_after(t)`` the one after round t,
+    ``result_transmissions`` the mean rounds a block used (a failed block counts all Q), ``result_throughput`` the delivered
+    information bits per data element actually sent and ``result_iterations`` the mean iterations per block over all its attempts;
+    each is one read and, with several ranks, one all-gather of eight float64."""
+
+    _config, _needs, _host_decoder, _decoder_plan, _columns = HarqConfig, "a HarqConfig", staticmethod(link_harq_host), "LinkHarqPlan", HARQ_COUNTS
+
+    def update(self, est: Optional[torch.Tensor], ideal: torch.Tensor, meta: Optional[tuple] = None, *, frame_ids=None,
+               snr_db=None) -> None:
+        if ideal.dim() >= 1 and ideal.shape[0] % (self.branches * self.code.rounds):
+            raise ValueError(f"a batch of {ideal.shape[0]} frames is not a multiple of branches * rounds = "
+                             f"{self.branches} * {self.code.rounds}")
+        super().update(est, ideal, meta, frame_ids=frame_ids, snr_db=snr_db)
+
+    def _tally(self, group):
+        """``(acked per round [4], blocks never acknowledged, iterations, all blocks)`` over all ranks: the blocks are counted, not
+        derived from the frames."""
+        *acked, _, failed, iterations, _ = self._read(group)
+        return acked, failed, iterations, sum(acked) + failed
+
+    def result(self, group: Optional["torch.distributed.ProcessGroup"] = None) -> float:
+        """Global residual block-error rate after all rounds (integers summed: identical on every rank); 0.0 for an empty sweep."""
+        _, failed, _, blocks = self._tally(group)
+        return failed / blocks if blocks > 0 else 0.0
+
+    def result_bler_after(self, t: int, group=None) -> float:
+        """The share of blocks not yet acknowledged after round ``t`` in 0 .. Q-1."""
+        if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not 0 <= int(t) < self.code.rounds:
+            raise ValueError(f"t = {t!r}: a round in 0 .. {self.code.rounds - 1}")
+        acked, _, _, blocks = self._tally(group)
+        return (blocks - sum(acked[:int(t) + 1])) / blocks if blocks > 0 else 0.0
+
+    def result_ber(self, group=None) -> float:
+        """Global residual information-bit error rate: the errors of the blocks never acknowledged over all information bits."""
+        bit_errors = self._read(group)[4]
+        _, _, _, blocks = self._tally(group)
+        return bit_errors / (blocks * self.code.info_bits) if blocks > 0 else 0.0
+
+    def _rounds_used(self, group):
+        acked, failed, _, blocks = self._tally(group)
+        return sum((t + 1) * a for t, a in enumerate(acked)) + self.code.rounds * failed, sum(acked), blocks
+
+    def result_transmissions(self, group=None) -> float:
+        """Mean rounds used per block; a block never acknowledged counts all Q."""
+        used, _, blocks = self._rounds_used(group)
+        return used / blocks if blocks > 0 else 0.0
+
+    def result_throughput(self, group=None) -> float:
+        """Information bits of the acknowledged blocks per data element actually sent: a block's round takes 1 / B of a frame."""
+        used, acked, blocks = self._rounds_used(group)
+        return self.code.info_bits * acked * self.code.blocks / (self.cfg.data_elements * used) if blocks > 0 else 0.0
+
+    def result_iterations(self, group=None) -> float:
+        """Mean decoder iterations per block, summed over all its attempts."""
+        _, _, iterations, blocks = self._tally(group)
+        return iterations / blocks if blocks > 0 else 0.0

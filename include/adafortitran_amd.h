@@ -519,6 +519,48 @@ int aft_link_mrc_f32(const aft_link *link, const float *ideal, const float *est,
                      int n_factors, int branches, int32_t *counts /* [groups][2] */, float *loss /* [groups][n_factors] */,
                      float *llr /* [groups,S,T,m] or NULL */, int batch, void *stream);
 
+/* ---- HARQ link: rate matching and soft combining on the LDPC-coded link (adafortitran_amd/linksim.py "The HARQ link" holds the
+ * definition in full) ----
+ *
+ * A block that fails is sent again, the receiver adds the new soft bits to the old ones and decodes again.
+ *   mother code   the LDPC-coded link's: base matrix mb x nb, kb = nb - mb, n = 64 nb, K = 64 kb; encoder and decoder unchanged
+ *   rate matching tx_cols = C, kb < C <= nb: a round sends E = 64 C coded bits per block.  rounds = Q in 1 .. AFT_LINK_HARQ_MAX_ROUNDS;
+ *                 starts[t] = s_t in 0 .. nb-1, the block column where round t's window begins.  Transmitted bit e = 0 .. E-1 of round
+ *                 t is codeword bit v_t(e) = 64 ((s_t + e / 64) mod nb) + e % 64: a circular buffer in whole block columns
+ *   position      N bits per frame as on the coded links, B = N / E blocks (integer division), U = B E; transmitted bit e of block b
+ *                 sits at data-bit index j = ((b E + e) stride) mod U, gcd(stride, U) = 1; j maps to a grid element and a bit of its
+ *                 word as on the coded links; filler and pilots are never read
+ *   groups        LLR frames h Q .. h Q + Q - 1 with keys k_0 .. k_{Q-1} are rounds 0 .. Q-1 of group h, k_0 its leader.
+ *                 u[b][i] = word(k_0, stream 8, b K + i) >> 63 and c = the codeword of u.  Round t uses its OWN frame's sent words
+ *                 w (stream 5 of k_t): scrambler s = w_j ^ c[v_t(e)], z_{t,b,e} = the coded links' quantiser of (1 - 2 s) llr_t[j]
+ *   soft buffer   Z_t[b][v] = sum over t' <= t and e with v_{t'}(e) = v of z_{t',b,e}: an integer, |Z| <= 127 Q, 0 where nothing was sent
+ *   attempts      after round t every block not yet acknowledged is decoded from scratch (L = Z_t, R = 0; offset, max_iters, layer
+ *                 order, clamps and stop rule the LDPC-coded link's).  A block is ACKNOWLEDGED iff its decoded information bits equal u
+ *                 (an ideal CRC) and then runs no further attempt: later rounds' LLRs at its positions influence nothing
+ *   counts        [0 .. 3] blocks first acknowledged after round t (0 for t >= Q); [4] information-bit errors of the blocks never
+ *                 acknowledged, from their last attempt; [5] blocks never acknowledged; [6] iterations summed over all attempts run
+ *   bits          each block's decoded information bits from the last attempt it ran
+ * With Q = 1, C = nb, s_0 = 0 and the same stride: counts [0] = B - block errors, [4], [5], [6] = aft_link_ldpc_f32's three counts,
+ * and the bits are equal bit for bit.  Everything after the quantiser is integer: a host evaluation agrees bit for bit. */
+#define AFT_LINK_HARQ_MAX_ROUNDS 4
+#define AFT_LINK_HARQ_COUNTS 7
+
+/* One launch, one workgroup per group, one wave per code block and one lane per row of a circulant: counts int32
+ * [batch / rounds][AFT_LINK_HARQ_COUNTS] and, when bits is not NULL, bits uint8 [batch / rounds, B, K] (both device memory) from llr
+ * float32 [batch, S, T, m] (device memory) and keys uint64 [batch] (any device-addressable memory, pinned host memory included).
+ * `link`, `shifts` and `starts` (HOST memory) are read during the call only.  Every element of counts and bits is written; no atomics;
+ * no workspace; nothing is synchronised; a group's outputs depend on its own Q keys and LLR frames only: neither on batch, nor on its
+ * position in it, nor on the run, nor on whether bits is written.
+ * Nothing is launched on AFT_ERR_ARG (what aft_link_ldpc_f32 gives it for; a NULL or misaligned starts; batch not a multiple of
+ * rounds) and AFT_ERR_SHAPE (what aft_link_ldpc_f32 refuses for the struct, the base matrix, offset and max_iters; rounds outside 1 ..
+ * AFT_LINK_HARQ_MAX_ROUNDS; tx_cols outside kb + 1 .. nb; a start outside 0 .. nb-1; B = 0; B K above 2^31; a stride not coprime to U
+ * or outside [1, U), or a stride_inverse that is not its inverse modulo U). */
+int aft_link_harq_f32(const aft_link *link, const float *llr /* [batch,S,T,m] */, const unsigned long long *keys, int base_rows,
+                      int base_cols, const int32_t *shifts /* HOST, [base_rows][base_cols - base_rows] */, int tx_cols, int rounds,
+                      const int32_t *starts /* HOST, [rounds] */, unsigned long long stride, unsigned long long stride_inverse,
+                      float qgain, int offset, int max_iters, int32_t *counts /* [batch / rounds][7] */,
+                      unsigned char *bits /* [batch / rounds,B,K] or NULL */, int batch, void *stream);
+
 /* ---- training path of the encoder ---- */
 
 /* Gradients of one nn.TransformerEncoderLayer: same fields and shapes as aft_layer_weights,
