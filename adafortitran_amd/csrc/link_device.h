@@ -1,8 +1,9 @@
 // What the link front end is made of (k_link.hip), each piece written once, so every instantiation sees the same bits: the pilot staging
 // and lookup, the pair loads, the Gray map, the hard decision, the front of a data element -- split into the sent word (one per
 // transmission) and a branch (one per receive antenna: y = H x + noise, c = y conj(E), p = |E|^2) --, the combiner's step, an axis's
-// max-log LLRs, the softplus step of the loss, the LLR store and the reduction of a workgroup's sums.  adafortitran_amd/linksim.py holds
-// the definitions.
+// max-log LLRs, the softplus step of the loss, the LLR store and the reduction of a workgroup's sums; and what two-stream detection
+// (k_linksm.hip) adds to them: the two-stream received sample, the Gram / matched sums, the adjugate detector with its LLR scale.
+// adafortitran_amd/linksim.py holds the definitions.
 #pragma once
 
 #include "frame_device.h"
@@ -106,6 +107,62 @@ __device__ __forceinline__ void link_combine(LinkBranch &sum, float rho, const L
     sum.cr = fmaf(rho, b.cr, sum.cr);
     sum.ci = fmaf(rho, b.ci, sum.ci);
     sum.p = fmaf(rho, b.p, sum.p);
+}
+
+// ---- two-stream spatial multiplexing (k_linksm.hip; linksim.py "the spatial-multiplexing link") ----
+
+// The received sample of one antenna under two streams, y = H0 x0 + H1 x1 + noise, with the noise words of the antenna's own key.
+// Stream 0's product is link_branch's own chain; stream 1's two products are added by fused multiply-adds and the noise last, so with
+// H1 = 0 the sample is link_branch's bit for bit.
+struct LinkSample {
+    float yr, yi;
+};
+
+__device__ __forceinline__ LinkSample link_sample2(unsigned long long kf, float sigma, unsigned q, const LinkSent &x0, const LinkSent &x1,
+                                                   float2 h0, float2 h1) {
+    const FrameNoise nz = frame_noise(kf, kStreamDataNoiseRadius, kStreamDataNoiseAngle, q, sigma);
+    float tr = fmaf(h0.x, x0.xr, -(h0.y * x0.xi));
+    float ti = fmaf(h0.x, x0.xi, h0.y * x0.xr);
+    tr = fmaf(-h1.y, x1.xi, fmaf(h1.x, x1.xr, tr));
+    ti = fmaf(h1.y, x1.xr, fmaf(h1.x, x1.xi, ti));
+    return LinkSample{fmaf(nz.r, nz.c, tr), fmaf(nz.r, nz.s, ti)};
+}
+
+// An element's eight sums over the antennas: the matched filters m_s = sum rho conj(E_s) y and the Gram matrix g00, g11, g01 = sum rho
+// conj(E_0) E_1.  Each term is link_branch's y conj(E) / |E|^2 chain and enters by one fused multiply-add, as link_combine's; the
+// sums start at -0.
+struct LinkSm {
+    float m0r, m0i, m1r, m1i, g00, g11, g01r, g01i;
+};
+
+__device__ __forceinline__ void link_sm_accumulate(LinkSm &a, float rho, const LinkSample &y, float2 e0, float2 e1) {
+    a.m0r = fmaf(rho, fmaf(y.yr, e0.x, y.yi * e0.y), a.m0r);
+    a.m0i = fmaf(rho, fmaf(y.yi, e0.x, -(y.yr * e0.y)), a.m0i);
+    a.m1r = fmaf(rho, fmaf(y.yr, e1.x, y.yi * e1.y), a.m1r);
+    a.m1i = fmaf(rho, fmaf(y.yi, e1.x, -(y.yr * e1.y)), a.m1i);
+    a.g00 = fmaf(rho, fmaf(e0.x, e0.x, e0.y * e0.y), a.g00);
+    a.g11 = fmaf(rho, fmaf(e1.x, e1.x, e1.y * e1.y), a.g11);
+    a.g01r = fmaf(rho, fmaf(e0.x, e1.x, e0.y * e1.y), a.g01r);
+    a.g01i = fmaf(rho, fmaf(e0.x, e1.y, -(e0.y * e1.x)), a.g01i);
+}
+
+// The adjugate detector of one stream: c = a_other m_self - gx m_other with gx = g01 for stream 0 and conj(g01) for stream 1,
+// p = g_self a_other - |g01|^2, and the LLR scale eff = scale / a_other (one correctly rounded division; 0 where a_other <= 0).
+// One body for both streams (`second` picks the roles), two roundings per product pair, nothing contracted behind the source's back.
+struct LinkDetected {
+    float cr, ci, p, eff;
+};
+
+__device__ __forceinline__ LinkDetected link_sm_detect(const LinkSm &a, float reg, float scale, bool second) {
+#pragma clang fp contract(off)
+    const float a00 = a.g00 + reg, a11 = a.g11 + reg;
+    const float ao = second ? a00 : a11, gs = second ? a.g11 : a.g00;
+    const float msr = second ? a.m1r : a.m0r, msi = second ? a.m1i : a.m0i;
+    const float mor = second ? a.m0r : a.m1r, moi = second ? a.m0i : a.m1i;
+    const float gxr = a.g01r, gxi = second ? -a.g01i : a.g01i;
+    const float tr = fmaf(gxr, mor, -(gxi * moi)), ti = fmaf(gxr, moi, gxi * mor);      // gx m_other
+    const float n01 = fmaf(a.g01r, a.g01r, a.g01i * a.g01i);
+    return LinkDetected{fmaf(ao, msr, -tr), fmaf(ao, msi, -ti), fmaf(gs, ao, -n01), ao > 0.f ? scale / ao : 0.f};
 }
 
 // ---- the soft half: max-log LLRs and the loss the achievable rate is read from (linksim.py "the soft link") ----

@@ -74,38 +74,43 @@ def _link_sweep(model, test_dataloaders, make_acc, read) -> Dict[int, float]:
 
 
 def get_link_stats(model: Optional[torch.nn.Module], test_dataloaders: List[Tuple[str, Iterable]], link_cfg, seed: int = 0,
-                   group=None, branches: int = 1) -> Dict[int, float]:
+                   group=None, branches: int = 1, streams: int = 1, detector: str = "mmse") -> Dict[int, float]:
     """Bit-error rate per loader on the link ``link_cfg`` (``linksim.LinkConfig``) defines: data symbols through each frame's true channel
     plus noise at the frame's SNR, equalised with the model's estimate; ``model=None`` is perfect channel knowledge.  Same sorting and
     keys as ``get_test_stats``; the estimate comes from ``forward_pass``, so every estimator here works; the counts accumulate on the
     device (``linksim.LinkAccumulator``) and are read once per loader.  A frame's data bits and noise are a function of
     ``(seed, file_no)``, whichever estimator is measured: two estimators see the same link.
     ``branches=R`` combines every R consecutive frames of a batch as the antennas of one receiver (``linksim``: "the diversity link");
-    every batch then holds a multiple of R frames."""
-    return _link_sweep(model, test_dataloaders, lambda device: LinkAccumulator(link_cfg, device, seed, branches),
+    every batch then holds a multiple of R frames.  ``streams=2`` with ``detector`` ``"zf"`` or ``"mmse"`` separates two transmit
+    streams on those R antennas (``linksim``: "the spatial-multiplexing link"): every batch holds a multiple of ``2 R`` frames, frame
+    ``r 2 + s`` of a group the pair (antenna r, stream s), and the rate is per stream."""
+    return _link_sweep(model, test_dataloaders, lambda device: LinkAccumulator(link_cfg, device, seed, branches, streams, detector),
                        lambda acc: acc.result(group))
 
 
 def get_link_rates(model: Optional[torch.nn.Module], test_dataloaders: List[Tuple[str, Iterable]], link_cfg, seed: int = 0,
-                   factors=DEFAULT_FACTORS, group=None, branches: int = 1) -> Dict[int, float]:
+                   factors=DEFAULT_FACTORS, group=None, branches: int = 1, streams: int = 1, detector: str = "mmse") -> Dict[int, float]:
     """Achievable rate per loader in bit/symbol on the same link: the bit-interleaved coded-modulation rate (GMI) of the max-log LLRs a
     demapper forms with the model's estimate at the frame's SNR, the best of the LLR scale factors ``factors``; ``model=None`` is perfect
     channel knowledge.  Sorting, keys and the frames' bits and noise as ``get_link_stats``; the losses accumulate on the device
-    (``linksim.RateAccumulator``) and are read once per loader.  ``branches`` as ``get_link_stats``: the rate is per transmission."""
-    return _link_sweep(model, test_dataloaders, lambda device: RateAccumulator(link_cfg, device, seed, factors, branches=branches),
+    (``linksim.RateAccumulator``) and are read once per loader.  ``branches``, ``streams`` and ``detector`` as ``get_link_stats``: the rate is per
+    transmission, with two streams per stream and symbol (the spectral efficiency is twice it)."""
+    return _link_sweep(model, test_dataloaders, lambda device: RateAccumulator(link_cfg, device, seed, factors, branches=branches,
+                                                                               streams=streams, detector=detector),
                        lambda acc: acc.result_gmi(group))
 
 
 def get_link_bler(model: Optional[torch.nn.Module], test_dataloaders: List[Tuple[str, Iterable]], code_cfg, seed: int = 0,
-                  err_var: float = 0.0, group=None, branches: int = 1) -> Dict[int, float]:
+                  err_var: float = 0.0, group=None, branches: int = 1, streams: int = 1, detector: str = "mmse") -> Dict[int, float]:
     """Block-error rate per loader with a decoder in the loop: the code ``code_cfg`` rides on the same link and its decoder reads the
     max-log LLRs the demapper forms with the model's estimate -- a ``linksim.CodeConfig`` is the convolutional code with a Viterbi
     decoder (``linksim.BlockErrorAccumulator``), a ``linksim.LdpcConfig`` the quasi-cyclic LDPC code with a layered min-sum decoder
     (``linksim.LdpcBlockErrorAccumulator``); ``model=None`` is perfect channel knowledge.  Sorting, keys and the frames' bits and noise
     as ``get_link_stats``; the counts accumulate on the device and are read once per loader.  ``branches`` as ``get_link_stats``: the
-    decoder reads the combiner's LLRs with the leaders' keys."""
+    decoder reads the combiner's LLRs with the leaders' keys; ``streams`` and ``detector`` likewise: the decoder reads each stream's
+    LLRs with the key of frame ``(0, s)``."""
     accumulator = LdpcBlockErrorAccumulator if isinstance(code_cfg, LdpcConfig) else BlockErrorAccumulator
-    return _link_sweep(model, test_dataloaders, lambda device: accumulator(code_cfg, device, seed, err_var, branches),
+    return _link_sweep(model, test_dataloaders, lambda device: accumulator(code_cfg, device, seed, err_var, branches, streams, detector),
                        lambda acc: acc.result(group))
 
 

@@ -591,6 +591,49 @@ class LinkMrcPlan(LinkPlan):
         return counts, loss, llr
 
 
+class LinkSmPlan(LinkPlan):
+    """Two-stream spatial multiplexing on ``LinkPlan``'s link: linear ZF / MMSE detection of ``streams = 2`` transmit streams on
+    ``branches`` receive antennas (``linksim``: "the spatial-multiplexing link"); frame ``g N R + r N + s`` of a batch is the pair
+    (antenna ``r``, stream ``s``) of group ``g``.  ``plan(ideal, est, keys, sigma, rho, scale, reg, factors, want_llr=False)`` ->
+    ``(counts int32 [G N, 2], loss float32 [G N, K], llr float32 [G N, S, T, m] or None)`` for the ``G = batch / (branches streams)``
+    groups on the plan's device, row ``g N + s`` stream ``s`` of group ``g`` (its key is frame ``(0, s)``'s): three ``torch.empty`` at
+    the most, one ``ctypes`` call, one launch (``aft_link_sm_f32``) on the current stream, no synchronisation.  ``rho`` (float32,
+    ``batch`` values), ``scale`` and ``reg`` (float32, ``G`` values: the leaders' LLR scale and the regulariser, 0 for zero forcing
+    and ``1 / scale`` for MMSE) are ``linksim.sm_weights``'; they and ``factors`` live where ``keys`` and ``sigma`` may.  Everything
+    else as ``LinkMrcPlan``."""
+    cpu_path = "linksim.link_sm_host"
+
+    def __init__(self, cfg, device: torch.device, branches: int, streams: int = 2) -> None:
+        super().__init__(cfg, device)
+        if isinstance(streams, bool) or not isinstance(streams, int) or streams != _abi.AFT_LINK_MAX_STREAMS:
+            raise ValueError(f"streams = {streams!r}: the spatial-multiplexing link separates {_abi.AFT_LINK_MAX_STREAMS} streams")
+        if isinstance(branches, bool) or not isinstance(branches, int) or not 2 <= branches <= _abi.AFT_LINK_MAX_BRANCHES:
+            raise ValueError(f"branches = {branches!r}: an integer in 2 .. {_abi.AFT_LINK_MAX_BRANCHES} (one antenna cannot separate "
+                             f"{streams} streams)")
+        self.branches, self.streams = branches, streams
+
+    def __call__(self, ideal: torch.Tensor, est: torch.Tensor, keys: torch.Tensor, sigma: torch.Tensor, rho: torch.Tensor,
+                 scale: torch.Tensor, reg: torch.Tensor, factors: torch.Tensor, want_llr: bool = False, lib=None):
+        lib = lib or _lib.load()
+        batch, ideal, est, keys, sigma = self._checked(ideal, est, keys, sigma)
+        if batch % (self.branches * self.streams):
+            raise ValueError(f"a batch of {batch} frames is not a multiple of branches * streams = {self.branches} * {self.streams}")
+        groups = batch // (self.branches * self.streams)
+        rows = groups * self.streams
+        rho = _in_place("rho", rho, torch.float32, self.device, batch)
+        scale = _in_place("scale", scale, torch.float32, self.device, groups)
+        reg = _in_place("reg", reg, torch.float32, self.device, groups)
+        factors = self._checked_factors(factors)
+        counts = torch.empty((rows, 2), dtype=torch.int32, device=self.device)                  # the kernel writes every element
+        loss = torch.empty((rows, factors.numel()), dtype=torch.float32, device=self.device)
+        llr = torch.empty((rows, *self.grid, self.cfg.bits_per_symbol), dtype=torch.float32, device=self.device) if want_llr else None
+        _lib.check(lib.aft_link_sm_f32(C.byref(self.link), ideal.data_ptr(), est.data_ptr(), keys.data_ptr(), sigma.data_ptr(),
+                                       rho.data_ptr(), scale.data_ptr(), reg.data_ptr(), factors.data_ptr(), factors.numel(),
+                                       self.branches, self.streams, counts.data_ptr(), loss.data_ptr(), _ptr(llr), batch,
+                                       _lib.current_stream_ptr(self.device)), lib)
+        return counts, loss, llr
+
+
 class _DecoderPlan:
     """What the decoder plans share: the code's link struct and LLR shape, and a call that checks ``llr`` and ``keys``, allocates
     ``counts int32 [groups, width]`` and, when asked for, ``bits uint8 [groups, B, K]`` (a group is one frame, or the HARQ link's

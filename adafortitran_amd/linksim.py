@@ -83,6 +83,41 @@ unchanged.  The coded links are unchanged downstream: the decoders read this LLR
 information bits stream 8) and ``batch = G``.  What this models: R uncorrelated antennas, each estimated on its own.  It does not
 model antenna correlation, and it gives no array gain in the estimator itself (no estimator here sees more than one antenna's pilots).
 
+The spatial-multiplexing link.  The receivers that have the antennas ``branches=`` models do not only combine: they separate two
+spatial streams, and there an error in the estimate leaks one stream into the other, amplified by the conditioning of the channel.
+``link_sm_host`` (float64), ``aft_link_sm_f32`` (csrc/k_linksm.hip, through ``hip_ops.LinkSmPlan``) and the ``streams=`` / ``detector=``
+arguments of the accumulators and of the three sweeps of ``evaluation`` are linear detection of ``N = streams = 2`` transmit streams
+on ``R = branches`` receive antennas, ``2 <= R <= 8``.  A batch of ``n`` frames with ``n % (N R) == 0`` is ``G = n / (N R)`` groups;
+frame ``g N R + r N + s`` is the pair (antenna ``r``, stream ``s``) of group ``g``, ``H_{r,s}`` its true channel and ``E_{r,s}`` its estimate
+(orthogonal pilots: each pair is estimated alone, at its own frame's SNR); frame ``(0, 0)`` is the group's LEADER::
+
+    sent        stream s sends w_s, gi_s, gq_s, x_s exactly as the single link does, from stream 5 of the key of frame (0, s)
+    received    y_r = H_{r,0} x_0 + H_{r,1} x_1 + sigma_r sqrt(-ln u1) exp(j 2 pi u2)     u1, u2 from streams 6, 7 of the key of frame (r, 0),
+                                                                                           sigma_r that frame's; keys / sigma / rho of frames (r, 1)
+                                                                                           beyond stream 5 of (0, 1) are not read
+    weights     rho_r = float32(scale_{(r,0)} / scale_leader) as branch_weights forms them; scale = the leader's llr_scale, one float32 per group
+    Gram        g00 = sum_r rho_r |E_r0|^2,  g11 = sum_r rho_r |E_r1|^2,  g01 = sum_r rho_r conj(E_r0) E_r1      increasing r, sums start at -0,
+    matched     m_s = sum_r rho_r conj(E_rs) y_r                                                                   one fma per term as the combiner's
+    regulariser reg float32 per group: 0 is zero forcing; float32(1 / scale) (formed in double, rounded once) is MMSE.  a00 = g00 + reg, a11 = g11 + reg
+    detector    c_0 = a11 m_0 - g01 m_1            p_0 = g00 a11 - |g01|^2         (the adjugate: no division; p_s is det(A) less the MMSE bias,
+                c_1 = a00 m_1 - conj(g01) m_0      p_1 = g11 a00 - |g01|^2          so comp >= beta_b p_s is the UNBIASED decision)
+    hard        per stream the single link's decision, bit and symbol errors on (c_s, p_s) against (gi_s, gq_s)
+    soft        eff_s = scale / a_other  (a11 for stream 0, a00 for stream 1; ONE correctly rounded float32 division; 0 where a_other <= 0)
+                Lambda_j = eff_s Delta_j(c_s, p_s),  mu_k, Delta_j, the bit order and loss_f exactly the soft link's; pilots carry 0
+    outputs     counts int [G, N, 2], loss [G, N, K], llr [G, N, S, T, m]: contiguous, so they read as G N frames with the keys of frames (0, s)
+
+Why the soft rule holds: with noise variance ``1 / scale`` after the weights, the post-detection SINR of stream ``s`` is ``p_s scale /
+a_other``, and that is the factor in front of ``|x^ - a_k|^2`` with ``x^ = c_s / p_s``.  The margin and the LLR reach follow the diversity
+link's, with reaches that sum absolute values through the adjugate: ``reach(y_r) = |H_r0||x_0| + |H_r1||x_1| + |noise_r|``, ``reach(m_s) =
+sum_r rho_r reach(y_r) |E_rs|``, ``G01 = sum_r rho_r |E_r0||E_r1|``, ``reach(c_0) = a11 reach(m_0) + G01 reach(m_1)`` and ``P_0 = g00 a11 +
+G01^2`` (stream 1 symmetric); the margin is ``|comp - beta_b p_s| / (reach(c_s) + |beta_b| P_s)`` and ``q = eff_s A (A P_s + 2 reach(c_s))``.
+The cancellation in ``p_s`` is inherent to separating two streams in float32 -- a nearly singular estimated channel has ``p_s`` far below
+``P_s`` -- which is why the reaches are sums of absolute values and why the share of flagged decisions is larger than on the one-stream
+links (tests/test_linksm.py holds the cap).  With an unheard second stream (``H_r1 = E_r1 = 0``) and ``reg scale = 1`` in powers of two,
+stream 0 is the diversity link on the frames ``(r, 0)``.  Every rate of this link is per stream and symbol: the spectral efficiency is
+N times it.  What this models: uncorrelated antennas, per-pair estimates, linear detection (zero forcing or MMSE).  It does not model
+antenna correlation, joint (ML / sphere) detection, successive cancellation, precoding, or ``N > 2``.
+
 The coded link.  The rate says how much information the LLRs carry; a link-level user wants the same with a decoder in the loop: the
 block-error rate of coded blocks and the throughput that follows from it.  ``CodeConfig``, ``link_encode_host`` / ``link_decode_host``
 (integer NumPy), ``aft_link_decode_f32`` (csrc/k_linkcode.hip, through ``hip_ops.LinkDecodePlan``), ``BlockErrorAccumulator`` and
@@ -307,14 +342,19 @@ def _sent(cfg: LinkConfig, keys: np.ndarray):
     return gi, gq, d * ((2 * gray_level(gi) - (L - 1)) + 1j * (2 * gray_level(gq) - (L - 1)))
 
 
-def _branch(cfg: LinkConfig, keys: np.ndarray, H, E, sigma, x):
-    """One receive branch per key: ``c = y conj(E)`` with ``y = H x`` plus the noise of the branch's own key, ``p = |E|^2`` and the
-    reach ``(|H||x| + |noise|) |E|`` of a component of ``c``."""
+def _noise(cfg: LinkConfig, keys: np.ndarray, sigma) -> np.ndarray:
+    """The data noise of the frames with ``keys``: ``sigma sqrt(-ln u1) exp(j 2 pi u2)``, complex128 ``[n, S, T]``."""
     S, T = cfg.sim.ofdm
     q = np.arange(S * T, dtype=np.uint64).reshape(1, S, T)
     kk = keys[:, None, None]
     u1, u2 = _uniform(kk, STREAM_DATA_NOISE_RADIUS, q), _uniform(kk, STREAM_DATA_NOISE_ANGLE, q)
-    noise = sigma[:, None, None] * np.sqrt(-np.log(u1)) * np.exp(2j * np.pi * u2)
+    return sigma[:, None, None] * np.sqrt(-np.log(u1)) * np.exp(2j * np.pi * u2)
+
+
+def _branch(cfg: LinkConfig, keys: np.ndarray, H, E, sigma, x):
+    """One receive branch per key: ``c = y conj(E)`` with ``y = H x`` plus the noise of the branch's own key, ``p = |E|^2`` and the
+    reach ``(|H||x| + |noise|) |E|`` of a component of ``c``."""
+    noise = _noise(cfg, keys, sigma)
     c = (H * x + noise) * E.conj()
     p = E.real ** 2 + E.imag ** 2
     reach = (np.abs(H) * np.abs(x) + np.abs(noise)) * np.abs(E)
@@ -337,8 +377,10 @@ def link_errors_host(cfg: LinkConfig, keys, ideal, est, sigma, tau: Optional[flo
     return _hard(cfg, *_front(cfg, keys, ideal, est, sigma), tau)
 
 
-def _hard(cfg: LinkConfig, gi, gq, c, p, reach, tau):
-    """The hard decision and the margins on ``c`` and ``p``: what ``link_errors_host`` returns."""
+def _hard(cfg: LinkConfig, gi, gq, c, p, reach, tau, p_reach=None):
+    """The hard decision and the margins on ``c`` and ``p``: what ``link_errors_host`` returns.  ``p_reach``: the reach of ``p`` where it
+    is not ``p`` itself (the spatial-multiplexing link, whose ``p`` is a difference)."""
+    p_reach = p if p_reach is None else p_reach
     (n, S, T), L, d = c.shape, cfg.levels, cfg.d
     mask = cfg.data_mask[None]
     if tau is not None:
@@ -350,7 +392,7 @@ def _hard(cfg: LinkConfig, gi, gq, c, p, reach, tau):
             beta = 2.0 * d * (b - L / 2)
             level += comp >= beta * p
             if tau is not None:
-                den = reach + abs(beta) * p
+                den = reach + abs(beta) * p_reach
                 margin = np.divide(np.abs(comp - beta * p), den, out=np.zeros_like(den), where=den > 0)
                 flags[..., axis] |= margin <= tau
         wrong += _POPCOUNT[sent ^ level ^ (level >> 1)]
@@ -387,13 +429,20 @@ def link_llrs_host(cfg: LinkConfig, keys, ideal, est, sigma, scale, factors=(1.0
     return _soft(cfg, *_front(cfg, keys, ideal, est, sigma), scale, factors, e_lambda)
 
 
-def _soft(cfg: LinkConfig, gi, gq, c, p, reach, scale, factors, e_lambda):
-    """The LLRs and the losses on ``c`` and ``p``: what ``link_llrs_host`` returns."""
+def _soft(cfg: LinkConfig, gi, gq, c, p, reach, scale, factors, e_lambda, p_reach=None):
+    """The LLRs and the losses on ``c`` and ``p``: what ``link_llrs_host`` returns.  ``scale`` float64 ``[n, S, T]`` is taken per element
+    as it is (the spatial-multiplexing link's ``eff``, with ``p_reach`` the reach of its ``p``)."""
     (n, S, T), m, L, d = c.shape, cfg.bits_per_symbol, cfg.levels, cfg.d
     half = m // 2
-    scale = np.asarray(scale, dtype=np.float32).astype(np.float64).reshape(-1)
-    if scale.shape != (n,):
-        raise ValueError(f"scale must hold one value per frame ({n}), got {scale.size}")
+    if np.ndim(scale) == 3:
+        scale = np.asarray(scale, dtype=np.float64).reshape(n, S * T)
+    else:
+        scale = np.asarray(scale, dtype=np.float32).astype(np.float64).reshape(-1)
+        if scale.shape != (n,):
+            raise ValueError(f"scale must hold one value per frame ({n}), got {scale.size}")
+        scale = scale[:, None]
+    scale = np.broadcast_to(scale, (n, S * T)).reshape(n, S, T)
+    p_reach = p if p_reach is None else p_reach
     factors = _factors(factors).astype(np.float64)
     k = np.arange(L)
     a, label = d * (2 * k - (L - 1)), k ^ (k >> 1)
@@ -406,7 +455,7 @@ def _soft(cfg: LinkConfig, gi, gq, c, p, reach, scale, factors, e_lambda):
             one = ((label >> (half - 1 - j)) & 1).astype(bool)
             llr[..., axis * half + j] = mu[..., one].min(axis=-1) - mu[..., ~one].min(axis=-1)
             sign[..., axis * half + j] = 1 - 2 * ((sent >> (half - 1 - j)) & 1)
-    llr *= scale[:, None, None, None] * mask
+    llr *= scale[..., None] * mask
 
     def losses(lam):
         z = -(sign * lam)
@@ -416,7 +465,7 @@ def _soft(cfg: LinkConfig, gi, gq, c, p, reach, scale, factors, e_lambda):
     if e_lambda is None:
         return loss, llr
     A = (L - 1) * d
-    q = np.broadcast_to((scale[:, None, None] * A * (A * p + 2.0 * reach))[..., None] * mask, llr.shape).copy()
+    q = np.broadcast_to((scale * A * (A * p_reach + 2.0 * reach))[..., None] * mask, llr.shape).copy()
     return loss, llr, losses(llr + sign * (e_lambda * q)), losses(llr - sign * (e_lambda * q)), q
 
 
@@ -429,10 +478,12 @@ def _branches(branches) -> int:
     return int(branches)
 
 
-def _grouped(n: int, branches: int) -> int:
+def _grouped(n: int, branches: int, streams: int = 1) -> int:
+    if streams > 1 and n % (branches * streams):
+        raise ValueError(f"a batch of {n} frames is not a multiple of branches * streams = {branches} * {streams}")
     if n % branches:
         raise ValueError(f"a batch of {n} frames is not a multiple of branches = {branches}")
-    return n // branches
+    return n // (branches * streams)
 
 
 def _weights(scale: np.ndarray, branches: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -475,6 +526,99 @@ def link_mrc_host(cfg: LinkConfig, keys, ideal, est, sigma, rho, scale, branches
     return ((hard,) if tau is None else hard[:1]) + soft[:2] + (() if tau is None else hard[1:]) + soft[2:]
 
 
+MAX_STREAMS = _abi.AFT_LINK_MAX_STREAMS
+DETECTORS = ("zf", "mmse")
+
+
+def _streams(streams) -> int:
+    if isinstance(streams, bool) or not isinstance(streams, (int, np.integer)) or int(streams) != MAX_STREAMS:
+        raise ValueError(f"streams = {streams!r}: the spatial-multiplexing link separates {MAX_STREAMS} streams")
+    return int(streams)
+
+
+def _sm_shape(n: int, branches, streams) -> Tuple[int, int, int]:
+    """``(G, R, N)`` of a spatial-multiplexing batch of ``n`` frames, checked."""
+    N, R = _streams(streams), _branches(branches)
+    if R < 2:
+        raise ValueError(f"branches = {R}: one antenna cannot separate {N} streams; an integer in 2 .. {MAX_BRANCHES}")
+    return _grouped(n, R, N), R, N
+
+
+def detector_reg(scale, detector: str) -> np.ndarray:
+    """The regulariser float32 ``[G]`` of the leaders' float32 LLR scales: 0 for ``"zf"``, ``float32(1 / scale)`` (formed in double,
+    rounded once) for ``"mmse"``."""
+    if detector not in DETECTORS:
+        raise ValueError(f"detector = {detector!r}: one of {DETECTORS}")
+    scale = np.asarray(scale, dtype=np.float32).reshape(-1)
+    if detector == "zf":
+        return np.zeros_like(scale)
+    return (1.0 / scale.astype(np.float64)).astype(np.float32)
+
+
+def sm_weights(snr_db, err_var: float = 0.0, branches: int = 2, streams: int = 2, detector: str = "mmse"):
+    """The detector's operands for frames at ``snr_db`` ``[n]`` in the spatial-multiplexing layout: ``(rho float32 [n], scale float32 [G],
+    reg float32 [G])``: ``branch_weights`` over the ``branches * streams`` frames of a group (the entries of frames ``(r, 1)`` are not
+    read) and ``detector_reg`` of the leaders' scale."""
+    n = np.size(snr_db)
+    _, R, N = _sm_shape(n, branches, streams)
+    rho, scale = _weights(llr_scale(np.asarray(snr_db, dtype=np.float64).reshape(-1), err_var), R * N)
+    return rho, scale, detector_reg(scale, detector)
+
+
+def link_sm_host(cfg: LinkConfig, keys, ideal, est, sigma, rho, scale, reg, branches, streams=2, factors=(1.0,),
+                 tau: Optional[float] = None, e_lambda: Optional[float] = None):
+    """The spatial-multiplexing link (module docstring) in float64: ``keys`` / ``ideal`` / ``est`` / ``sigma`` as ``link_errors_host``'s
+    for the ``n`` frames in the layout ``g N R + r N + s``, ``rho`` ``[n]``, ``scale`` and ``reg`` ``[G]`` taken as the float32 numbers they
+    are (``sm_weights``), ``G = n / (branches streams)`` -> ``(counts int64 [G, N, 2], loss float64 [G, N, K], llr float64
+    [G, N, S, T, m])``.  With ``tau`` the wrong-bit map ``[G, N, S, T]`` and the flags ``[G, N, S, T, 2]`` follow, with ``e_lambda`` then
+    ``loss_lo``, ``loss_hi`` and ``q``: the extras of ``link_mrc_host``, in its order, on the detector's ``c_s``, ``p_s``, reaches and
+    ``eff_s``.  Needs no library."""
+    keys, H, E, sigma = _checked(cfg, keys, ideal, est, sigma)
+    n, (S, T) = len(keys), cfg.sim.ofdm
+    G, R, N = _sm_shape(n, branches, streams)
+    rho = np.asarray(rho, dtype=np.float32).astype(np.float64).reshape(-1)
+    if rho.shape != (n,):
+        raise ValueError(f"rho must hold one value per frame ({n}), got {rho.size}")
+    if np.size(scale) != G:
+        raise ValueError(f"scale must hold one value per group ({G}), got {np.size(scale)}")
+    if np.size(reg) != G:
+        raise ValueError(f"reg must hold one value per group ({G}), got {np.size(reg)}")
+    scale = np.asarray(scale, dtype=np.float32).astype(np.float64).reshape(G, 1, 1)
+    reg = np.asarray(reg, dtype=np.float32).astype(np.float64).reshape(G, 1, 1)
+    keys, sigma, rho = keys.reshape(G, R, N), sigma.reshape(G, R, N), rho.reshape(G, R, N)
+    H, E = H.reshape(G, R, N, S, T), E.reshape(G, R, N, S, T)
+    sent = [_sent(cfg, np.ascontiguousarray(keys[:, 0, s])) for s in range(N)]   # one transmission per stream: the keys of frames (0, s)
+    x0, x1 = sent[0][2], sent[1][2]
+    m, gss, rm = [0.0, 0.0], [0.0, 0.0], [0.0, 0.0]
+    g01 = G01 = 0.0
+    for r in range(R):                                                           # in increasing r, starting from 0
+        noise = _noise(cfg, np.ascontiguousarray(keys[:, r, 0]), sigma[:, r, 0])
+        y = H[:, r, 0] * x0 + H[:, r, 1] * x1 + noise
+        ry = np.abs(H[:, r, 0]) * np.abs(x0) + np.abs(H[:, r, 1]) * np.abs(x1) + np.abs(noise)
+        w = rho[:, r, 0, None, None]
+        for s in range(N):
+            e = E[:, r, s]
+            m[s] = m[s] + w * (y * e.conj())
+            gss[s] = gss[s] + w * (e.real ** 2 + e.imag ** 2)
+            rm[s] = rm[s] + w * (ry * np.abs(e))
+        g01 = g01 + w * (E[:, r, 0].conj() * E[:, r, 1])
+        G01 = G01 + w * (np.abs(E[:, r, 0]) * np.abs(E[:, r, 1]))
+    a = [gss[0] + reg, gss[1] + reg]
+    n01 = g01.real ** 2 + g01.imag ** 2
+    c = np.stack([a[1] * m[0] - g01 * m[1], a[0] * m[1] - g01.conj() * m[0]], axis=1)              # [G, N, S, T]
+    p = np.stack([gss[0] * a[1] - n01, gss[1] * a[0] - n01], axis=1)
+    reach = np.stack([a[1] * rm[0] + G01 * rm[1], a[0] * rm[1] + G01 * rm[0]], axis=1)
+    P = np.stack([gss[0] * a[1] + G01 ** 2, gss[1] * a[0] + G01 ** 2], axis=1)
+    other = np.stack([a[1], a[0]], axis=1)
+    eff = np.divide(np.broadcast_to(scale[:, None], other.shape), other, out=np.zeros_like(other), where=other > 0)
+    flat = lambda v: v.reshape(G * N, S, T)  # noqa: E731
+    gi, gq = (flat(np.stack([sent[0][i], sent[1][i]], axis=1)) for i in (0, 1))
+    hard = _hard(cfg, gi, gq, flat(c), flat(p), flat(reach), tau, flat(P))
+    soft = _soft(cfg, gi, gq, flat(c), flat(p), flat(reach), flat(eff), factors, e_lambda, flat(P))
+    out = ((hard,) if tau is None else hard[:1]) + soft[:2] + (() if tau is None else hard[1:]) + soft[2:]
+    return tuple(v.reshape(G, N, *v.shape[1:]) for v in out)
+
+
 # ---- the frame keys with torch ops, for frame numbers that live on the device (no synchronisation) ----
 
 def _s64(v: int) -> int:
@@ -509,18 +653,28 @@ class _FrameSweep:
     synchronises.  ``per_frame`` holds one float32 ``[b]`` operand per entry of ``of_snr``, pairs ``(numpy function, torch function on
     a float64 tensor)`` of the SNR in dB."""
 
-    def _open(self, cfg: LinkConfig, device, seed: int, want: str, branches: int = 1, err_var: float = 0.0, factors=(1.0,)) -> None:
-        """``want``: which of ``"counts"``, ``"loss"`` and ``"llr"`` ``_measure`` computes."""
+    def _open(self, cfg: LinkConfig, device, seed: int, want: str, branches: int = 1, err_var: float = 0.0, factors=(1.0,),
+              streams: int = 1, detector: str = "mmse") -> None:
+        """``want``: which of ``"counts"``, ``"loss"`` and ``"llr"`` ``_measure`` computes.  ``streams=2``: the spatial-multiplexing
+        link with ``detector`` in front (``streams=1`` ignores it)."""
         if not isinstance(cfg, LinkConfig):
             raise ValueError(f"{type(self).__name__} needs a LinkConfig (got {type(cfg).__name__})")
         self.cfg, self.seed, self._want = cfg, int(seed), want
         self.branches = _branches(branches)
+        if isinstance(streams, bool) or not isinstance(streams, (int, np.integer)) or int(streams) not in (1, MAX_STREAMS):
+            raise ValueError(f"streams = {streams!r}: 1, or {MAX_STREAMS} for the spatial-multiplexing link")
+        self.streams, self.detector = int(streams), detector
+        if self.streams > 1:
+            _sm_shape(0, self.branches, self.streams)           # one antenna cannot separate two streams
+            detector_reg(np.ones(1, np.float32), detector)      # the detector's name
         self.device = torch.device(device)
         soft = want != "counts"
         self._plan = None
         if self.device.type == "cuda":
             from . import hip_ops                  # loads the extension: a missing .so raises here, loudly
-            if self.branches == 1:
+            if self.streams > 1:                   # every measure of the spatial-multiplexing link comes from the detector's one launch
+                self._plan = hip_ops.LinkSmPlan(cfg, self.device, self.branches, self.streams)
+            elif self.branches == 1:
                 self._plan = (hip_ops.LinkSoftPlan if soft else hip_ops.LinkPlan)(cfg, self.device)
             else:                                  # every measure of the diversity link comes from the combiner's one launch
                 self._plan = hip_ops.LinkMrcPlan(cfg, self.device, self.branches)
@@ -530,7 +684,7 @@ class _FrameSweep:
             raise ValueError(f"err_var = {err_var!r}: a variance, at least 0")
         self.factors = _factors(factors)
         self._factors_t = None if self._plan is None else torch.from_numpy(self.factors).to(self.device)
-        self._of_snr = (_SIGMA_OF_SNR, _SCALE_OF_SNR(self.err_var)) if soft or self.branches > 1 else (_SIGMA_OF_SNR,)
+        self._of_snr = (_SIGMA_OF_SNR, _SCALE_OF_SNR(self.err_var)) if soft or self.branches > 1 or self.streams > 1 else (_SIGMA_OF_SNR,)
         self.frames = 0
 
     def _stage(self, a: np.ndarray) -> torch.Tensor:
@@ -591,14 +745,29 @@ class _FrameSweep:
         accumulator's device, of which the one ``_open`` was asked for is there (the others may be None).  On a CPU device the float64
         definitions, which compute no soft output for counts alone; on a HIP device one launch -- ``aft_link_errors_f32`` for the
         counts and ``aft_link_soft_f32`` for the loss and the LLRs of a single branch, ``aft_link_mrc_f32`` for any of them with
-        several, the weights formed by torch ops on the device -- and nothing synchronises."""
+        several, the weights formed by torch ops on the device -- and nothing synchronises.  With ``streams=2`` the groups are the
+        ``G N`` stream-frames of the spatial-multiplexing link with the keys of frames ``(0, s)``: ``link_sm_host`` on a CPU device,
+        one launch of ``aft_link_sm_f32`` with ``rho`` and ``reg`` formed on the device on a HIP device."""
         ops = self._operands(est, ideal, meta, frame_ids, snr_db, self._of_snr)
         if ops is None:
             return None
         b, H, E, keys, (sigma, *scale) = ops       # scale: the frames' LLR scales, where the measure or the combiner needs them
-        R, want_llr = self.branches, self._want == "llr"
-        G = _grouped(b, R)
+        R, N, want_llr = self.branches, self.streams, self._want == "llr"
+        G = _grouped(b, R, N)
         counts = loss = llr = None
+        if N > 1:                                  # G N "frames": stream s of group g, with the key of frame (0, s)
+            if self._plan is None:
+                rho, lead = _weights(scale[0], R * N)
+                counts, loss, llr = (v.reshape(G * N, *v.shape[2:]) for v in link_sm_host(
+                    self.cfg, keys, H, E, sigma, rho, lead, detector_reg(lead, self.detector), R, N, self.factors))
+                sent = np.ascontiguousarray(keys.reshape(G, R, N)[:, 0, :]).reshape(-1)
+                return (G * N, *(torch.from_numpy(a) for a in (sent, counts, loss, llr)))
+            s = scale[0].view(G, R * N).to(torch.float64)
+            rho = (s / s[:, :1]).to(torch.float32).reshape(-1)
+            lead = scale[0][::R * N].contiguous()
+            reg = torch.zeros_like(lead) if self.detector == "zf" else (1.0 / lead.to(torch.float64)).to(torch.float32)
+            counts, loss, llr = self._launch(H, E, keys, sigma, rho, lead, reg, self._factors_t, want_llr=want_llr)
+            return G * N, keys.view(G, R, N)[:, 0, :].reshape(-1), counts, loss, llr
         if self._plan is None:
             if R > 1:
                 counts, loss, llr = link_mrc_host(self.cfg, keys, H, E, sigma, *_weights(scale[0], R), R, self.factors)
@@ -663,10 +832,18 @@ class LinkAccumulator(_FrameSweep):
     ``branches=R`` (module docstring, "the diversity link"; the same argument on the three accumulators below): every R consecutive
     frames of a batch are the branches of one receiver, combined by one launch of ``aft_link_mrc_f32`` (on a CPU device by
     ``link_mrc_host``) with the weights of ``branch_weights``; a batch that is no multiple of R raises ``ValueError``, ``frames``
-    counts the groups, and every rate is per transmission.  ``branches=1`` is the single-branch path, launch for launch."""
+    counts the groups, and every rate is per transmission.  ``branches=1`` is the single-branch path, launch for launch.
 
-    def __init__(self, cfg: LinkConfig, device, seed: int = 0, branches: int = 1) -> None:
-        self._open(cfg, device, seed, "counts", branches)
+    ``streams=2`` with ``detector`` ``"zf"`` or ``"mmse"`` (module docstring, "the spatial-multiplexing link"; the same arguments on
+    ``RateAccumulator``, ``BlockErrorAccumulator`` and ``LdpcBlockErrorAccumulator``, not on ``HarqAccumulator``): every ``2 R``
+    consecutive frames of a batch are the (antenna, stream) pairs of one receiver, ``R >= 2``, detected by one launch of
+    ``aft_link_sm_f32`` (on a CPU device by ``link_sm_host``) with ``rho`` and ``reg`` formed on the device without a synchronisation;
+    a batch that is no multiple of ``2 R`` raises ``ValueError``.  A batch yields ``G N`` "frames", stream ``s`` of group ``g`` with the
+    key of frame ``(0, s)``; ``frames`` counts them, and every rate is per stream and symbol: the spectral efficiency is N times it.
+    ``streams=1`` is today's path, launch for launch, and ignores ``detector``."""
+
+    def __init__(self, cfg: LinkConfig, device, seed: int = 0, branches: int = 1, streams: int = 1, detector: str = "mmse") -> None:
+        self._open(cfg, device, seed, "counts", branches, streams=streams, detector=detector)
         self.errors = torch.zeros(2, dtype=torch.int64, device=self.device)     # bit errors, symbol errors
 
     def update(self, est: Optional[torch.Tensor], ideal: torch.Tensor, meta: Optional[tuple] = None, *, frame_ids=None,
@@ -705,8 +882,9 @@ class RateAccumulator(_FrameSweep):
     one all-gather of ``K + 1`` float64 (the K losses and the frames).  The losses are float sums: ranks that split a sweep differently
     agree to rounding, not bit for bit -- every rank of one sweep reports the same number."""
 
-    def __init__(self, cfg: LinkConfig, device, seed: int = 0, factors=(1.0,), err_var: float = 0.0, branches: int = 1) -> None:
-        self._open(cfg, device, seed, "loss", branches, err_var, factors)
+    def __init__(self, cfg: LinkConfig, device, seed: int = 0, factors=(1.0,), err_var: float = 0.0, branches: int = 1,
+                 streams: int = 1, detector: str = "mmse") -> None:
+        self._open(cfg, device, seed, "loss", branches, err_var, factors, streams, detector)
         self.loss = torch.zeros(len(self.factors), dtype=torch.float64, device=self.device)
 
     def update(self, est: Optional[torch.Tensor], ideal: torch.Tensor, meta: Optional[tuple] = None, *, frame_ids=None,
@@ -948,10 +1126,11 @@ class BlockErrorAccumulator(_FrameSweep):
     #: what ``LdpcBlockErrorAccumulator`` changes: the config it accepts, the host decoder, the decoder's plan and the columns of ``errors``
     _config, _needs, _host_decoder, _decoder_plan, _columns = CodeConfig, "a CodeConfig", staticmethod(link_decode_host), "LinkDecodePlan", 2
 
-    def __init__(self, code, device, seed: int = 0, err_var: float = 0.0, branches: int = 1) -> None:
+    def __init__(self, code, device, seed: int = 0, err_var: float = 0.0, branches: int = 1, streams: int = 1,
+                 detector: str = "mmse") -> None:
         if not isinstance(code, self._config):
             raise ValueError(f"{type(self).__name__} needs {self._needs} (got {type(code).__name__})")
-        self._open(code.link, device, seed, "llr", branches, err_var)
+        self._open(code.link, device, seed, "llr", branches, err_var, streams=streams, detector=detector)
         self.code = code
         self.errors = torch.zeros(self._columns, dtype=torch.int64, device=self.device)    # information-bit errors, block errors, ...
         self._decode = None
@@ -1455,6 +1634,10 @@ class HarqAccumulator(BlockErrorAccumulator):
     each is one read and, with several ranks, one all-gather of eight float64."""
 
     _config, _needs, _host_decoder, _decoder_plan, _columns = HarqConfig, "a HarqConfig", staticmethod(link_harq_host), "LinkHarqPlan", HARQ_COUNTS
+
+    def __init__(self, code, device, seed: int = 0, err_var: float = 0.0, branches: int = 1) -> None:
+        # no ``streams``: a group's rounds are consecutive LLR frames, which would be the two streams of one group
+        super().__init__(code, device, seed, err_var, branches)
 
     def update(self, est: Optional[torch.Tensor], ideal: torch.Tensor, meta: Optional[tuple] = None, *, frame_ids=None,
                snr_db=None) -> None:

@@ -561,6 +561,42 @@ int aft_link_harq_f32(const aft_link *link, const float *llr /* [batch,S,T,m] */
                       float qgain, int offset, int max_iters, int32_t *counts /* [batch / rounds][7] */,
                       unsigned char *bits /* [batch / rounds,B,K] or NULL */, int batch, void *stream);
 
+/* ---- spatial multiplexing: two-stream ZF / MMSE detection on R antennas (adafortitran_amd/linksim.py "the spatial-multiplexing link") ----
+ *
+ * N = streams = 2 transmit streams on R = branches uncorrelated receive antennas, 2 <= R <= AFT_LINK_MAX_BRANCHES, every (antenna,
+ * stream) pair with its own channel and its own estimate: group g of a batch is the frames g N R .. g N R + N R - 1, frame
+ * g N R + r N + s the pair (antenna r, stream s), frame (0, 0) the group's leader.
+ *   sent        stream s sends w_s, gi_s, gq_s, x_s as aft_link_errors_f32's, from stream 5 of the key of frame (0, s)
+ *   received    y_r = H_r0 x_0 + H_r1 x_1 + sigma_r sqrt(-ln u1) exp(j 2 pi u2), u1 and u2 from streams 6 and 7 of the key of frame
+ *               (r, 0), sigma_r that frame's.  Stream 0's product is aft_link_mrc_f32's own chain, stream 1's two products are added by
+ *               fused multiply-adds, the noise last.  keys / sigma / rho of frames (r, 1) are not read beyond stream 5 of (0, 1)
+ *   Gram        g00 = sum_r rho_r |E_r0|^2, g11 = sum_r rho_r |E_r1|^2, g01 = sum_r rho_r conj(E_r0) E_r1, rho_r = rho of frame (r, 0)
+ *   matched     m_s = sum_r rho_r conj(E_rs) y_r: in increasing r, one fused multiply-add per term as the combiner's, sums start at -0
+ *   regulariser reg float32 [groups]: 0 is zero forcing, 1 / scale is MMSE.  a00 = g00 + reg, a11 = g11 + reg
+ *   detector    c_0 = a11 m_0 - g01 m_1,        p_0 = g00 a11 - |g01|^2     (the adjugate: no division; comp >= beta_b p_s is the
+ *               c_1 = a00 m_1 - conj(g01) m_0,  p_1 = g11 a00 - |g01|^2      unbiased decision)
+ *   decision, counts, mu_k, Delta_j and loss[f] as aft_link_errors_f32's and aft_link_soft_f32's on (c_s, p_s) against stream s's sent
+ *               word; Lambda_j = eff_s Delta_j with eff_s = scale / a_other (a11 for stream 0, a00 for stream 1: one correctly
+ *               rounded division; 0 where a_other <= 0) and the LEADER's scale (one per group)
+ * With H_r1 = E_r1 = 0 and reg scale = 1 in powers of two, stream 0's outputs are aft_link_mrc_f32's on the frames (r, 0), bit for bit.
+ * One launch, one workgroup per group: counts int32 [groups][streams][2], loss float32 [groups][streams][n_factors] and, when llr is
+ * not NULL, llr float32 [groups, streams, S, T, m] (all device memory; contiguous, so they read as groups * streams frames with the
+ * keys of frames (0, s)) from ideal and est complex64 [batch, S, T] (device memory), keys uint64 [batch], sigma and rho float32
+ * [batch], scale and reg float32 [groups] and factors float32 [n_factors] (any device-addressable memory, pinned host memory
+ * included).  Every element of the outputs is written; no atomics, no workspace; nothing is synchronised; float sums run in a fixed
+ * order, so a group's outputs depend neither on batch, nor on its position in it, nor on the run, nor on the load and store forms
+ * (aft_link_soft_f32's), nor on whether llr is written.  The decoders read this llr with the keys of frames (0, s) and
+ * groups * streams frames.
+ * Nothing is launched on AFT_ERR_ARG (what aft_link_mrc_f32 refuses; a NULL reg; reg not 4-byte aligned; batch not a multiple of
+ * branches * streams) and AFT_ERR_SHAPE (streams other than AFT_LINK_MAX_STREAMS; branches outside 2 .. AFT_LINK_MAX_BRANCHES; what
+ * aft_link_errors_f32 refuses). */
+#define AFT_LINK_MAX_STREAMS 2
+int aft_link_sm_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys,
+                    const float *sigma, const float *rho /* [batch] */, const float *scale /* [groups] */,
+                    const float *reg /* [groups] */, const float *factors, int n_factors, int branches, int streams,
+                    int32_t *counts /* [groups][streams][2] */, float *loss /* [groups][streams][n_factors] */,
+                    float *llr /* [groups,streams,S,T,m] or NULL */, int batch, void *stream);
+
 /* ---- training path of the encoder ---- */
 
 /* Gradients of one nn.TransformerEncoderLayer: same fields and shapes as aft_layer_weights,
