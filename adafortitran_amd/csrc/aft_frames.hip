@@ -350,4 +350,24 @@ int aft_link_sm_f32(const aft_link *link, const float *ideal, const float *est, 
     return e == hipSuccess ? AFT_OK : hip_fail("link_sm", e);
 }
 
+int aft_link_joint_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys, const float *sigma,
+                       const float *rho, const float *scale, const float *factors, int n_factors, int branches, int streams,
+                       int32_t *counts, float *loss, float *llr, int batch, void *stream) {
+    const char *who = "link joint";
+    // aft_link_sm_f32's checks, less the regulariser's
+    const int rc = check_front(who, link, ideal, est, keys, {sigma, rho, scale, factors, counts, loss},
+                               "sigma, rho, scale, factors, counts, loss and llr", llr, batch, n_factors, 1);
+    if (rc != AFT_OK) return rc;
+    if (streams != AFT_LINK_MAX_STREAMS) {
+        set_error("%s: streams = %d: the detector separates %d streams", who, streams, AFT_LINK_MAX_STREAMS);
+        return AFT_ERR_SHAPE;
+    }
+    if (!within(who, "branches", branches, 2, AFT_LINK_MAX_BRANCHES)) return AFT_ERR_SHAPE;
+    AFT_REQUIRE(batch % (branches * streams) == 0, "%s: batch = %d is not a multiple of branches * streams = %d * %d", who, batch,
+                branches, streams);
+    hipError_t e = launch_link_joint(*link, ideal, est, keys, sigma, rho, scale, factors, n_factors, branches, counts, loss, llr, batch,
+                                     static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? AFT_OK : hip_fail("link_joint", e);
+}
+
 }  // extern "C"

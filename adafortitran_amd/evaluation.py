@@ -83,7 +83,8 @@ def get_link_stats(model: Optional[torch.nn.Module], test_dataloaders: List[Tupl
     ``branches=R`` combines every R consecutive frames of a batch as the antennas of one receiver (``linksim``: "the diversity link");
     every batch then holds a multiple of R frames.  ``streams=2`` with ``detector`` ``"zf"`` or ``"mmse"`` separates two transmit
     streams on those R antennas (``linksim``: "the spatial-multiplexing link"): every batch holds a multiple of ``2 R`` frames, frame
-    ``r 2 + s`` of a group the pair (antenna r, stream s), and the rate is per stream."""
+    ``r 2 + s`` of a group the pair (antenna r, stream s), and the rate is per stream.  ``detector="joint"`` runs the joint max-log
+    demapper on the same frames instead of a linear detector (``linksim``: "the joint link")."""
     return _link_sweep(model, test_dataloaders, lambda device: LinkAccumulator(link_cfg, device, seed, branches, streams, detector),
                        lambda acc: acc.result(group))
 

@@ -634,6 +634,34 @@ class LinkSmPlan(LinkPlan):
         return counts, loss, llr
 
 
+class LinkJointPlan(LinkSmPlan):
+    """Joint max-log detection on ``LinkSmPlan``'s link and layout (``linksim``: "the joint link"): the exact max-log LLR of every bit
+    of both streams.  ``plan(ideal, est, keys, sigma, rho, scale, factors, want_llr=False)`` -> ``LinkSmPlan``'s three tensors: three
+    ``torch.empty`` at the most, one ``ctypes`` call, one launch (``aft_link_joint_f32``) on the current stream, no synchronisation.
+    There is no regulariser; everything else as ``LinkSmPlan``."""
+    cpu_path = "linksim.link_joint_host"
+
+    def __call__(self, ideal: torch.Tensor, est: torch.Tensor, keys: torch.Tensor, sigma: torch.Tensor, rho: torch.Tensor,
+                 scale: torch.Tensor, factors: torch.Tensor, want_llr: bool = False, lib=None):
+        lib = lib or _lib.load()
+        batch, ideal, est, keys, sigma = self._checked(ideal, est, keys, sigma)
+        if batch % (self.branches * self.streams):
+            raise ValueError(f"a batch of {batch} frames is not a multiple of branches * streams = {self.branches} * {self.streams}")
+        groups = batch // (self.branches * self.streams)
+        rows = groups * self.streams
+        rho = _in_place("rho", rho, torch.float32, self.device, batch)
+        scale = _in_place("scale", scale, torch.float32, self.device, groups)
+        factors = self._checked_factors(factors)
+        counts = torch.empty((rows, 2), dtype=torch.int32, device=self.device)                  # the kernel writes every element
+        loss = torch.empty((rows, factors.numel()), dtype=torch.float32, device=self.device)
+        llr = torch.empty((rows, *self.grid, self.cfg.bits_per_symbol), dtype=torch.float32, device=self.device) if want_llr else None
+        _lib.check(lib.aft_link_joint_f32(C.byref(self.link), ideal.data_ptr(), est.data_ptr(), keys.data_ptr(), sigma.data_ptr(),
+                                          rho.data_ptr(), scale.data_ptr(), factors.data_ptr(), factors.numel(), self.branches,
+                                          self.streams, counts.data_ptr(), loss.data_ptr(), _ptr(llr), batch,
+                                          _lib.current_stream_ptr(self.device)), lib)
+        return counts, loss, llr
+
+
 class _DecoderPlan:
     """What the decoder plans share: the code's link struct and LLR shape, and a call that checks ``llr`` and ``keys``, allocates
     ``counts int32 [groups, width]`` and, when asked for, ``bits uint8 [groups, B, K]`` (a group is one frame, or the HARQ link's

@@ -115,8 +115,44 @@ The cancellation in ``p_s`` is inherent to separating two streams in float32 -- 
 ``P_s`` -- which is why the reaches are sums of absolute values and why the share of flagged decisions is larger than on the one-stream
 links (tests/test_linksm.py holds the cap).  With an unheard second stream (``H_r1 = E_r1 = 0``) and ``reg scale = 1`` in powers of two,
 stream 0 is the diversity link on the frames ``(r, 0)``.  Every rate of this link is per stream and symbol: the spectral efficiency is
-N times it.  What this models: uncorrelated antennas, per-pair estimates, linear detection (zero forcing or MMSE).  It does not model
-antenna correlation, joint (ML / sphere) detection, successive cancellation, precoding, or ``N > 2``.
+N times it.  What this models: uncorrelated antennas, per-pair estimates, linear detection (zero forcing or MMSE; joint max-log
+detection is the next section).  It does not model antenna correlation, sphere or list detection, successive cancellation, precoding,
+or ``N > 2``.
+
+The joint link.  A linear detector on a 2 x 2 Rayleigh channel has diversity order 1; a receiver that ships two-stream reception runs a
+max-log joint demapper and gets order 2, and behind it an estimation error no longer leaks through an ill-conditioned inverse: it
+enters as a mismatched metric.  ``link_joint_host`` (float64), ``aft_link_joint_f32`` (csrc/k_linkjoint.hip, through
+``hip_ops.LinkJointPlan``) and ``detector="joint"`` (``JOINT_DETECTOR``; ``ALL_DETECTORS`` lists it after the linear ones) on the
+accumulators and sweeps with ``streams=2`` are that demapper.  The layout, the keys, ``sent``, ``received``, ``weights`` and the eight sums
+``m_0, m_1, g00, g11, g01`` are exactly the spatial-multiplexing link's: the same increasing ``r``, the same fused multiply-add per term,
+sums that start at -0.  There is no regulariser and no division.  For stream ``e`` with the other stream ``o``, ``A = (L-1) d``, levels
+``a_k`` and labels as on the soft link, and ``g_oe = g01`` for ``e = 1``, ``conj(g01)`` for ``e = 0``::
+
+    candidates   x_e = a_ki + j a_kq over all M = 2^m words of stream e
+    interference z(x_e) = m_o - g_oe x_e
+    inner min    r(x_e) = min_k mu_k(Re z, g_oo) + min_k mu_k(Im z, g_oo)         mu_k(comp, p) = a_k (a_k p - 2 comp): the soft link's metric
+    metric       f(x_e) = g_ee |x_e|^2 - 2 Re(conj(x_e) m_e) + r(x_e)            = min over x_o of sum_r rho_r |y_r - E_r0 x_0 - E_r1 x_1|^2, less a constant
+    Delta_j      = min{f(x_e) : bit_j(word) = 1} - min{f(x_e) : bit_j(word) = 0}    bit order: the sent word's, I-axis bits first, MSB first
+    LLR          Lambda_j = scale Delta_j        the leader's scale, one float32 per group; pilots carry 0
+    hard         bit j is decided 1 iff Lambda_j < 0; bit errors against the sent word, a symbol error where any bit is wrong
+    loss_f       the soft link's, on Lambda_j
+    outputs      counts int [G, N, 2], loss [G, N, K], llr [G, N, S, T, m], as the spatial-multiplexing link's
+
+Why: the weighted residual expands to ``const + sum_s (g_ss |x_s|^2 - 2 Re(conj(x_s) m_s)) + 2 Re(conj(x_0) g01 x_1)``, and for a fixed ``x_e``
+the terms in ``x_o`` are ``g_oo |x_o|^2 - 2 Re(conj(x_o) z)``, the sum over the two axes of ``mu_k`` on a component of ``z``: the best ``x_o``
+separates per axis.  So this is the exact max-log LLR of every bit of both streams in ``2 M`` candidate evaluations instead of ``M^2``.
+The hard decision is the sign of the stream's own LLRs; without ties it is the joint ML pair, and the definition never has to say which
+enumeration decides a stream.  What a float32 evaluation is compared through: ``Q = 2 A^2 (g00 + g11 + 2 G01) + 2 sqrt(2) A (reach(m_0) +
+reach(m_1))`` with ``reach(m_s)`` and ``G01`` the spatial-multiplexing link's.  Every term of every ``f`` is bounded by its share of ``Q``:
+``g_ee |x_e|^2 <= 2 A^2 g_ee`` and ``2 |x_e| |m_e| <= 2 sqrt(2) A reach(m_e)``; an axis of ``r`` is at most ``A^2 g_oo + 2 A |comp z|``, the two
+together ``2 A^2 g_oo + 2 sqrt(2) A |z|``, and ``|z| <= reach(m_o) + sqrt(2) A G01`` turns that into ``2 A^2 g_oo + 2 sqrt(2) A reach(m_o) +
+4 A^2 G01``; the shares add up to ``Q``, so ``|f| <= Q`` and ``|Delta_j| <= 2 Q``.  ``q = scale Q``; a data (element, stream, bit) is FLAGGED at
+``tau`` when ``|Delta_j| <= tau Q``: an evaluation whose ``Delta`` is within ``tau Q`` can decide only flagged bits differently, so a
+flagged bit moves a row's bit count by at most 1 and an (element, stream) with any flagged bit its symbol count by at most 1.  The
+loss interval is the soft link's, at ``Lambda -+ e_lambda q``.  With an unheard second stream (``H_r1 = E_r1 = 0``) stream 1's ``Delta``
+is exactly 0 and stream 0's LLRs are the diversity link's on the frames ``(r, 0)``.  What this models beyond the linear detectors: the
+joint max-log demapper.  It does not model sphere or list detection (nothing is pruned: every candidate is evaluated), successive
+cancellation, iterative detection and decoding, antenna correlation, or ``N > 2``.
 
 The coded link.  The rate says how much information the LLRs carry; a link-level user wants the same with a decoder in the loop: the
 block-error rate of coded blocks and the throughput that follows from it.  ``CodeConfig``, ``link_encode_host`` / ``link_decode_host``
@@ -574,6 +610,30 @@ def link_sm_host(cfg: LinkConfig, keys, ideal, est, sigma, rho, scale, reg, bran
     ``loss_lo``, ``loss_hi`` and ``q``: the extras of ``link_mrc_host``, in its order, on the detector's ``c_s``, ``p_s``, reaches and
     ``eff_s``.  Needs no library."""
     keys, H, E, sigma = _checked(cfg, keys, ideal, est, sigma)
+    (G, R, N, S, T), sent, m, gss, rm, g01, G01, scale = _sm_sums(cfg, keys, H, E, sigma, rho, scale, branches, streams)
+    if np.size(reg) != G:
+        raise ValueError(f"reg must hold one value per group ({G}), got {np.size(reg)}")
+    reg = np.asarray(reg, dtype=np.float32).astype(np.float64).reshape(G, 1, 1)
+    a = [gss[0] + reg, gss[1] + reg]
+    n01 = g01.real ** 2 + g01.imag ** 2
+    c = np.stack([a[1] * m[0] - g01 * m[1], a[0] * m[1] - g01.conj() * m[0]], axis=1)              # [G, N, S, T]
+    p = np.stack([gss[0] * a[1] - n01, gss[1] * a[0] - n01], axis=1)
+    reach = np.stack([a[1] * rm[0] + G01 * rm[1], a[0] * rm[1] + G01 * rm[0]], axis=1)
+    P = np.stack([gss[0] * a[1] + G01 ** 2, gss[1] * a[0] + G01 ** 2], axis=1)
+    other = np.stack([a[1], a[0]], axis=1)
+    eff = np.divide(np.broadcast_to(scale[:, None], other.shape), other, out=np.zeros_like(other), where=other > 0)
+    flat = lambda v: v.reshape(G * N, S, T)  # noqa: E731
+    gi, gq = (flat(np.stack([sent[0][i], sent[1][i]], axis=1)) for i in (0, 1))
+    hard = _hard(cfg, gi, gq, flat(c), flat(p), flat(reach), tau, flat(P))
+    soft = _soft(cfg, gi, gq, flat(c), flat(p), flat(reach), flat(eff), factors, e_lambda, flat(P))
+    out = ((hard,) if tau is None else hard[:1]) + soft[:2] + (() if tau is None else hard[1:]) + soft[2:]
+    return tuple(v.reshape(G, N, *v.shape[1:]) for v in out)
+
+
+def _sm_sums(cfg: LinkConfig, keys, H, E, sigma, rho, scale, branches, streams):
+    """What the two-stream definitions share, on checked operands: ``((G, R, N, S, T), sent, m, gss, rm, g01, G01, scale)`` -- the sent
+    words ``(gi, gq, x)`` per stream, the matched sums ``m_s``, the Gram sums ``g_ss`` and ``g01``, the reaches ``reach(m_s)`` and ``G01``,
+    each ``[G, S, T]``, and the leaders' scale as float64 ``[G, 1, 1]``."""
     n, (S, T) = len(keys), cfg.sim.ofdm
     G, R, N = _sm_shape(n, branches, streams)
     rho = np.asarray(rho, dtype=np.float32).astype(np.float64).reshape(-1)
@@ -581,10 +641,7 @@ def link_sm_host(cfg: LinkConfig, keys, ideal, est, sigma, rho, scale, reg, bran
         raise ValueError(f"rho must hold one value per frame ({n}), got {rho.size}")
     if np.size(scale) != G:
         raise ValueError(f"scale must hold one value per group ({G}), got {np.size(scale)}")
-    if np.size(reg) != G:
-        raise ValueError(f"reg must hold one value per group ({G}), got {np.size(reg)}")
     scale = np.asarray(scale, dtype=np.float32).astype(np.float64).reshape(G, 1, 1)
-    reg = np.asarray(reg, dtype=np.float32).astype(np.float64).reshape(G, 1, 1)
     keys, sigma, rho = keys.reshape(G, R, N), sigma.reshape(G, R, N), rho.reshape(G, R, N)
     H, E = H.reshape(G, R, N, S, T), E.reshape(G, R, N, S, T)
     sent = [_sent(cfg, np.ascontiguousarray(keys[:, 0, s])) for s in range(N)]   # one transmission per stream: the keys of frames (0, s)
@@ -603,20 +660,79 @@ def link_sm_host(cfg: LinkConfig, keys, ideal, est, sigma, rho, scale, reg, bran
             rm[s] = rm[s] + w * (ry * np.abs(e))
         g01 = g01 + w * (E[:, r, 0].conj() * E[:, r, 1])
         G01 = G01 + w * (np.abs(E[:, r, 0]) * np.abs(E[:, r, 1]))
-    a = [gss[0] + reg, gss[1] + reg]
-    n01 = g01.real ** 2 + g01.imag ** 2
-    c = np.stack([a[1] * m[0] - g01 * m[1], a[0] * m[1] - g01.conj() * m[0]], axis=1)              # [G, N, S, T]
-    p = np.stack([gss[0] * a[1] - n01, gss[1] * a[0] - n01], axis=1)
-    reach = np.stack([a[1] * rm[0] + G01 * rm[1], a[0] * rm[1] + G01 * rm[0]], axis=1)
-    P = np.stack([gss[0] * a[1] + G01 ** 2, gss[1] * a[0] + G01 ** 2], axis=1)
-    other = np.stack([a[1], a[0]], axis=1)
-    eff = np.divide(np.broadcast_to(scale[:, None], other.shape), other, out=np.zeros_like(other), where=other > 0)
-    flat = lambda v: v.reshape(G * N, S, T)  # noqa: E731
-    gi, gq = (flat(np.stack([sent[0][i], sent[1][i]], axis=1)) for i in (0, 1))
-    hard = _hard(cfg, gi, gq, flat(c), flat(p), flat(reach), tau, flat(P))
-    soft = _soft(cfg, gi, gq, flat(c), flat(p), flat(reach), flat(eff), factors, e_lambda, flat(P))
-    out = ((hard,) if tau is None else hard[:1]) + soft[:2] + (() if tau is None else hard[1:]) + soft[2:]
-    return tuple(v.reshape(G, N, *v.shape[1:]) for v in out)
+    return (G, R, N, S, T), sent, m, gss, rm, g01, G01, scale
+
+
+JOINT_DETECTOR = "joint"
+ALL_DETECTORS = DETECTORS + (JOINT_DETECTOR,)
+
+
+def _detector(detector) -> str:
+    """A detector's name, checked: the linear ones by ``detector_reg`` (which keeps refusing everything else), or ``"joint"``."""
+    if not (isinstance(detector, str) and detector == JOINT_DETECTOR):
+        detector_reg(np.ones(1, np.float32), detector)
+    return detector
+
+
+def link_joint_host(cfg: LinkConfig, keys, ideal, est, sigma, rho, scale, branches, streams=2, factors=(1.0,),
+                    tau: Optional[float] = None, e_lambda: Optional[float] = None):
+    """The joint link (module docstring) in float64: the operands of ``link_sm_host`` without ``reg`` -> ``link_sm_host``'s tuple, in its
+    order: ``(counts int64 [G, N, 2], loss float64 [G, N, K], llr float64 [G, N, S, T, m])``; with ``tau`` the wrong-bit map
+    ``[G, N, S, T]`` and the flags ``[G, N, S, T, m]`` (a data (element, stream, bit) with ``|Delta_j| <= tau Q``) follow, with ``e_lambda``
+    then ``loss_lo``, ``loss_hi`` (the losses at ``Lambda -+ e_lambda q``) and ``q = scale Q`` ``[G, N, S, T, m]``, 0 at the pilots.  Needs
+    no library."""
+    keys, H, E, sigma = _checked(cfg, keys, ideal, est, sigma)
+    (G, R, N, S, T), sent, ms, gss, rm, g01, G01, scale = _sm_sums(cfg, keys, H, E, sigma, rho, scale, branches, streams)
+    m, L, d = cfg.bits_per_symbol, cfg.levels, cfg.d
+    half = m // 2
+    factors = _factors(factors).astype(np.float64)
+    k = np.arange(L)
+    a, label = d * (2 * k - (L - 1)), k ^ (k >> 1)
+    A = (L - 1) * d
+    zero = np.zeros((G, S, T))                                                   # a batch of all-pilot grids keeps its shapes
+    mu = lambda comp, p: a * (a * p[..., None] - 2.0 * comp[..., None])  # noqa: E731     [..., L]: the soft link's metric
+    delta = np.empty((G, N, S, T, m))
+    for e in range(N):
+        o = 1 - e
+        g_oe = (g01 if e == 1 else np.conj(g01)) + zero
+        m_e, m_o, g_ee, g_oo = ms[e] + zero, ms[o] + zero, gss[e] + zero, gss[o] + zero
+        t_i, t_q = mu(m_e.real, g_ee), mu(m_e.imag, g_ee)                          # g_ee a^2 - 2 a comp, per axis
+        f = np.empty((G, S, T, L, L))                                             # [.., ki, kq]
+        for ki in range(L):
+            z = m_o[..., None] - g_oe[..., None] * (a[ki] + 1j * a)               # [G, S, T, kq]
+            r = mu(z.real, g_oo[..., None]).min(axis=-1) + mu(z.imag, g_oo[..., None]).min(axis=-1)
+            f[..., ki, :] = (t_i[..., ki, None] + t_q) + r
+        rows, cols = f.min(axis=-1), f.min(axis=-2)                               # over kq: the I axis's; over ki: the Q axis's
+        for axis, best in enumerate((rows, cols)):
+            for j in range(half):
+                one = ((label >> (half - 1 - j)) & 1).astype(bool)
+                delta[:, e, ..., axis * half + j] = best[..., one].min(axis=-1) - best[..., ~one].min(axis=-1)
+    mask = cfg.data_mask[None, None, :, :, None]
+    delta *= mask
+    llr = delta * scale[:, None, :, :, None]
+    gi, gq = (np.stack([sent[0][i], sent[1][i]], axis=1) for i in (0, 1))         # [G, N, S, T]
+    sign = np.empty((G, N, S, T, m))                                              # 1 - 2 b_j
+    for j in range(half):
+        sign[..., j] = 1 - 2 * ((gi >> (half - 1 - j)) & 1)
+        sign[..., half + j] = 1 - 2 * ((gq >> (half - 1 - j)) & 1)
+    wrong = (((llr < 0) != (sign < 0)) & (mask != 0)).sum(axis=-1)                # the sign rule against the sent bits
+    counts = np.stack([wrong.sum(axis=(2, 3)), (wrong > 0).sum(axis=(2, 3))], axis=-1).astype(np.int64)
+
+    def losses(lam):
+        z = -(sign * lam)
+        return np.stack([(np.logaddexp(0.0, fac * z) * mask).sum(axis=(2, 3, 4)) for fac in factors], axis=-1) / np.log(2.0)
+
+    out = (counts, losses(llr), llr)
+    if tau is None and e_lambda is None:
+        return out
+    Q = (2.0 * A * A * (gss[0] + gss[1] + 2.0 * G01) + 2.0 * np.sqrt(2.0) * A * (rm[0] + rm[1])) + zero
+    Q = np.broadcast_to(Q[:, None, :, :, None], delta.shape) * mask
+    if tau is not None:
+        out += (wrong, (np.abs(delta) <= tau * Q) & (mask != 0))
+    if e_lambda is not None:
+        q = scale[:, None, :, :, None] * Q
+        out += (losses(llr + sign * (e_lambda * q)), losses(llr - sign * (e_lambda * q)), q)
+    return out
 
 
 # ---- the frame keys with torch ops, for frame numbers that live on the device (no synchronisation) ----
@@ -666,14 +782,15 @@ class _FrameSweep:
         self.streams, self.detector = int(streams), detector
         if self.streams > 1:
             _sm_shape(0, self.branches, self.streams)           # one antenna cannot separate two streams
-            detector_reg(np.ones(1, np.float32), detector)      # the detector's name
+            _detector(detector)                                 # the detector's name: a linear one, or "joint"
         self.device = torch.device(device)
         soft = want != "counts"
         self._plan = None
         if self.device.type == "cuda":
             from . import hip_ops                  # loads the extension: a missing .so raises here, loudly
             if self.streams > 1:                   # every measure of the spatial-multiplexing link comes from the detector's one launch
-                self._plan = hip_ops.LinkSmPlan(cfg, self.device, self.branches, self.streams)
+                plan = hip_ops.LinkJointPlan if detector == JOINT_DETECTOR else hip_ops.LinkSmPlan
+                self._plan = plan(cfg, self.device, self.branches, self.streams)
             elif self.branches == 1:
                 self._plan = (hip_ops.LinkSoftPlan if soft else hip_ops.LinkPlan)(cfg, self.device)
             else:                                  # every measure of the diversity link comes from the combiner's one launch
@@ -747,7 +864,8 @@ class _FrameSweep:
         counts and ``aft_link_soft_f32`` for the loss and the LLRs of a single branch, ``aft_link_mrc_f32`` for any of them with
         several, the weights formed by torch ops on the device -- and nothing synchronises.  With ``streams=2`` the groups are the
         ``G N`` stream-frames of the spatial-multiplexing link with the keys of frames ``(0, s)``: ``link_sm_host`` on a CPU device,
-        one launch of ``aft_link_sm_f32`` with ``rho`` and ``reg`` formed on the device on a HIP device."""
+        one launch of ``aft_link_sm_f32`` with ``rho`` and ``reg`` formed on the device on a HIP device; with ``detector="joint"``
+        ``link_joint_host`` and one launch of ``aft_link_joint_f32``, which has no ``reg``."""
         ops = self._operands(est, ideal, meta, frame_ids, snr_db, self._of_snr)
         if ops is None:
             return None
@@ -758,13 +876,19 @@ class _FrameSweep:
         if N > 1:                                  # G N "frames": stream s of group g, with the key of frame (0, s)
             if self._plan is None:
                 rho, lead = _weights(scale[0], R * N)
-                counts, loss, llr = (v.reshape(G * N, *v.shape[2:]) for v in link_sm_host(
-                    self.cfg, keys, H, E, sigma, rho, lead, detector_reg(lead, self.detector), R, N, self.factors))
+                if self.detector == JOINT_DETECTOR:
+                    out = link_joint_host(self.cfg, keys, H, E, sigma, rho, lead, R, N, self.factors)
+                else:
+                    out = link_sm_host(self.cfg, keys, H, E, sigma, rho, lead, detector_reg(lead, self.detector), R, N, self.factors)
+                counts, loss, llr = (v.reshape(G * N, *v.shape[2:]) for v in out)
                 sent = np.ascontiguousarray(keys.reshape(G, R, N)[:, 0, :]).reshape(-1)
                 return (G * N, *(torch.from_numpy(a) for a in (sent, counts, loss, llr)))
             s = scale[0].view(G, R * N).to(torch.float64)
             rho = (s / s[:, :1]).to(torch.float32).reshape(-1)
             lead = scale[0][::R * N].contiguous()
+            if self.detector == JOINT_DETECTOR:                # no regulariser
+                counts, loss, llr = self._launch(H, E, keys, sigma, rho, lead, self._factors_t, want_llr=want_llr)
+                return G * N, keys.view(G, R, N)[:, 0, :].reshape(-1), counts, loss, llr
             reg = torch.zeros_like(lead) if self.detector == "zf" else (1.0 / lead.to(torch.float64)).to(torch.float32)
             counts, loss, llr = self._launch(H, E, keys, sigma, rho, lead, reg, self._factors_t, want_llr=want_llr)
             return G * N, keys.view(G, R, N)[:, 0, :].reshape(-1), counts, loss, llr
@@ -840,6 +964,8 @@ class LinkAccumulator(_FrameSweep):
     ``aft_link_sm_f32`` (on a CPU device by ``link_sm_host``) with ``rho`` and ``reg`` formed on the device without a synchronisation;
     a batch that is no multiple of ``2 R`` raises ``ValueError``.  A batch yields ``G N`` "frames", stream ``s`` of group ``g`` with the
     key of frame ``(0, s)``; ``frames`` counts them, and every rate is per stream and symbol: the spectral efficiency is N times it.
+    ``detector="joint"`` (module docstring, "the joint link") is the joint max-log demapper on the same frames: one launch of
+    ``aft_link_joint_f32`` (on a CPU device ``link_joint_host``), no regulariser.
     ``streams=1`` is today's path, launch for launch, and ignores ``detector``."""
 
     def __init__(self, cfg: LinkConfig, device, seed: int = 0, branches: int = 1, streams: int = 1, detector: str = "mmse") -> None:

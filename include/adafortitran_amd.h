@@ -597,6 +597,31 @@ int aft_link_sm_f32(const aft_link *link, const float *ideal, const float *est, 
                     int32_t *counts /* [groups][streams][2] */, float *loss /* [groups][streams][n_factors] */,
                     float *llr /* [groups,streams,S,T,m] or NULL */, int batch, void *stream);
 
+/* ---- joint detection: exact max-log LLRs of both streams of that link (adafortitran_amd/linksim.py "the joint link") ----
+ *
+ * The layout, keys, sent words, received samples, weights and the eight sums m_0, m_1, g00, g11, g01 are aft_link_sm_f32's, formed by
+ * the same operations in the same order.  There is no regulariser and no division.  For stream e with the other stream o,
+ * g_oe = g01 for e = 1 and conj(g01) for e = 0, a_k the L levels and mu_k(comp, p) = a_k (a_k p - 2 comp) as aft_link_soft_f32's:
+ *   candidates   x_e = a_ki + j a_kq over all M = 2^m words of stream e
+ *   interference z(x_e) = m_o - g_oe x_e
+ *   inner min    r(x_e) = min_k mu_k(Re z, g_oo) + min_k mu_k(Im z, g_oo)
+ *   metric       f(x_e) = g_ee |x_e|^2 - 2 Re(conj(x_e) m_e) + r(x_e): the minimum over x_o of the weighted residual
+ *                sum_r rho_r |y_r - E_r0 x_0 - E_r1 x_1|^2, less a constant
+ *   Delta_j      = min{f(x_e) : bit j of the word is 1} - min{f(x_e) : bit j is 0}, bit order as aft_link_soft_f32's
+ *   Lambda_j     = scale Delta_j with the LEADER's scale (one per group); pilots carry 0
+ *   hard         bit j is decided 1 iff Lambda_j < 0; bit errors against the sent word, a symbol error where any bit is wrong
+ *   loss[f]      as aft_link_soft_f32's on Lambda_j
+ * The exact max-log LLR of every bit of both streams in 2 M candidate evaluations per element: for a fixed x_e the best x_o
+ * separates per axis.  Finite operands give finite LLRs, all-zero estimates included (every LLR is 0 then).  Outputs, operands,
+ * memory rules and invariants are aft_link_sm_f32's: one launch, one workgroup per group, every element of the outputs written, no
+ * atomics, no workspace, nothing synchronised, a group's outputs a function of its own operands only.
+ * Nothing is launched on AFT_ERR_ARG and AFT_ERR_SHAPE: what aft_link_sm_f32 refuses, less what it says of reg. */
+int aft_link_joint_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys,
+                       const float *sigma, const float *rho /* [batch] */, const float *scale /* [groups] */,
+                       const float *factors, int n_factors, int branches, int streams,
+                       int32_t *counts /* [groups][streams][2] */, float *loss /* [groups][streams][n_factors] */,
+                       float *llr /* [groups,streams,S,T,m] or NULL */, int batch, void *stream);
+
 /* ---- training path of the encoder ---- */
 
 /* Gradients of one nn.TransformerEncoderLayer: same fields and shapes as aft_layer_weights,
