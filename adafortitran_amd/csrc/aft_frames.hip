@@ -121,6 +121,23 @@ int check_front(const char *who, const aft_link *link, const float *ideal, const
     return check_link(who, *link);
 }
 
+// What the two two-stream entry points ask: check_front with one branch -- the group of this link is branches * streams frames --,
+// then the streams, the branches and the batch against the group; 0 = fine
+int check_front2(const char *who, const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys,
+                 std::initializer_list<const void *> words, const char *names, const float *llr, int batch, int n_factors, int branches,
+                 int streams) {
+    const int rc = check_front(who, link, ideal, est, keys, words, names, llr, batch, n_factors, 1);
+    if (rc != AFT_OK) return rc;
+    if (streams != AFT_LINK_MAX_STREAMS) {
+        set_error("%s: streams = %d: the detector separates %d streams", who, streams, AFT_LINK_MAX_STREAMS);
+        return AFT_ERR_SHAPE;
+    }
+    if (!within(who, "branches", branches, 2, AFT_LINK_MAX_BRANCHES)) return AFT_ERR_SHAPE;
+    AFT_REQUIRE(batch % (branches * streams) == 0, "%s: batch = %d is not a multiple of branches * streams = %d * %d", who, batch,
+                branches, streams);
+    return AFT_OK;
+}
+
 // What both decoder entry points compute from a block's coded and information bits and refuse: B = carried / coded blocks per frame
 // (at least one; B info at most 2^31) and the interleaver's stride over the B coded used bits; 0 = fine, *blocks = B
 int check_blocks(const char *who, const aft_link &l, unsigned long long coded, unsigned long long info, unsigned long long stride,
@@ -333,40 +350,22 @@ int aft_link_harq_f32(const aft_link *link, const float *llr, const unsigned lon
 int aft_link_sm_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys, const float *sigma,
                     const float *rho, const float *scale, const float *reg, const float *factors, int n_factors, int branches,
                     int streams, int32_t *counts, float *loss, float *llr, int batch, void *stream) {
-    const char *who = "link sm";
-    // the front end's checks with one branch: the group of this link is branches * streams frames, checked below
-    const int rc = check_front(who, link, ideal, est, keys, {sigma, rho, scale, reg, factors, counts, loss},
-                               "sigma, rho, scale, reg, factors, counts, loss and llr", llr, batch, n_factors, 1);
+    const int rc = check_front2("link sm", link, ideal, est, keys, {sigma, rho, scale, reg, factors, counts, loss},
+                                "sigma, rho, scale, reg, factors, counts, loss and llr", llr, batch, n_factors, branches, streams);
     if (rc != AFT_OK) return rc;
-    if (streams != AFT_LINK_MAX_STREAMS) {
-        set_error("%s: streams = %d: the detector separates %d streams", who, streams, AFT_LINK_MAX_STREAMS);
-        return AFT_ERR_SHAPE;
-    }
-    if (!within(who, "branches", branches, 2, AFT_LINK_MAX_BRANCHES)) return AFT_ERR_SHAPE;
-    AFT_REQUIRE(batch % (branches * streams) == 0, "%s: batch = %d is not a multiple of branches * streams = %d * %d", who, batch,
-                branches, streams);
-    hipError_t e = launch_link_sm(*link, ideal, est, keys, sigma, rho, scale, reg, factors, n_factors, branches, counts, loss, llr, batch,
-                                  static_cast<hipStream_t>(stream));
+    hipError_t e = launch_link2(false, *link, ideal, est, keys, sigma, rho, scale, reg, factors, n_factors, branches, counts, loss, llr,
+                                batch, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? AFT_OK : hip_fail("link_sm", e);
 }
 
 int aft_link_joint_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys, const float *sigma,
                        const float *rho, const float *scale, const float *factors, int n_factors, int branches, int streams,
                        int32_t *counts, float *loss, float *llr, int batch, void *stream) {
-    const char *who = "link joint";
-    // aft_link_sm_f32's checks, less the regulariser's
-    const int rc = check_front(who, link, ideal, est, keys, {sigma, rho, scale, factors, counts, loss},
-                               "sigma, rho, scale, factors, counts, loss and llr", llr, batch, n_factors, 1);
+    const int rc = check_front2("link joint", link, ideal, est, keys, {sigma, rho, scale, factors, counts, loss},
+                                "sigma, rho, scale, factors, counts, loss and llr", llr, batch, n_factors, branches, streams);
     if (rc != AFT_OK) return rc;
-    if (streams != AFT_LINK_MAX_STREAMS) {
-        set_error("%s: streams = %d: the detector separates %d streams", who, streams, AFT_LINK_MAX_STREAMS);
-        return AFT_ERR_SHAPE;
-    }
-    if (!within(who, "branches", branches, 2, AFT_LINK_MAX_BRANCHES)) return AFT_ERR_SHAPE;
-    AFT_REQUIRE(batch % (branches * streams) == 0, "%s: batch = %d is not a multiple of branches * streams = %d * %d", who, batch,
-                branches, streams);
-    hipError_t e = launch_link_joint(*link, ideal, est, keys, sigma, rho, scale, factors, n_factors, branches, counts, loss, llr, batch,
-                                     static_cast<hipStream_t>(stream));
+    hipError_t e = launch_link2(true, *link, ideal, est, keys, sigma, rho, scale, nullptr, factors, n_factors, branches, counts, loss, llr,
+                                batch, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? AFT_OK : hip_fail("link_joint", e);
 }
 

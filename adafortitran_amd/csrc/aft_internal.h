@@ -405,16 +405,12 @@ hipError_t launch_link_harq(const aft_link &link, const float *llr, const unsign
                             const int32_t *shifts, int tx_cols, int rounds, const int32_t *starts, unsigned blocks,
                             unsigned long long stride, float qgain, int offset, int max_iters, int32_t *counts, unsigned char *bits,
                             int batch, hipStream_t st);
-// two-stream spatial multiplexing on the same link (k_linksm.hip): everything has passed aft_link_sm_f32's checks; one workgroup per
-// group of branches * 2 frames, batch a multiple of it; llr may be NULL
-hipError_t launch_link_sm(const aft_link &link, const float *ideal, const float *est, const unsigned long long *keys,
-                          const float *sigma, const float *rho, const float *scale, const float *reg, const float *factors,
-                          int n_factors, int branches, int32_t *counts, float *loss, float *llr, int batch, hipStream_t st);
-// joint max-log detection of the same two streams (k_linkjoint.hip): everything has passed aft_link_joint_f32's checks; the launch
-// shape is launch_link_sm's; llr may be NULL
-hipError_t launch_link_joint(const aft_link &link, const float *ideal, const float *est, const unsigned long long *keys,
-                             const float *sigma, const float *rho, const float *scale, const float *factors, int n_factors,
-                             int branches, int32_t *counts, float *loss, float *llr, int batch, hipStream_t st);
+// two streams on the same link (k_linksm.hip), separated by the linear ZF / MMSE detector or, with `joint`, the joint max-log demapper
+// (reg is NULL then): everything has passed aft_link_sm_f32's or aft_link_joint_f32's checks; one workgroup per group of branches * 2
+// frames, batch a multiple of it; llr may be NULL
+hipError_t launch_link2(bool joint, const aft_link &link, const float *ideal, const float *est, const unsigned long long *keys,
+                        const float *sigma, const float *rho, const float *scale, const float *reg, const float *factors, int n_factors,
+                        int branches, int32_t *counts, float *loss, float *llr, int batch, hipStream_t st);
 hipError_t launch_mse(const float *est, const float *ref, double *sum_sq, long long n_complex, hipStream_t st);
 hipError_t launch_fill_lds(float value, hipStream_t st);   // test hook: every CU's LDS filled with `value`
 hipError_t launch_peek_lds(float *out, int workgroups, int n, hipStream_t st);   // ... and what a kernel finds in its LDS at start

@@ -29,28 +29,10 @@
 //   link_errors_kernel  (aft_link_errors_f32)  counts,              one branch
 //   link_soft_kernel    (aft_link_soft_f32)    losses and LLRs,     one branch
 //   link_mrc_kernel     (aft_link_mrc_f32)     counts, losses, LLRs, R branches; with R = 1 bit for bit both of the above
-#include <type_traits>
-
 #include "link_device.h"
 
 namespace aft {
 namespace {
-
-// the union of what the three instantiations read and write; a pointer an instantiation does not use is NULL
-struct LinkArgs {
-    aft_link c;
-    const float2 *ideal, *est;
-    const unsigned long long *keys;
-    const float *sigma, *rho, *scale, *factors;
-    int *counts;
-    float *loss, *llr;          // llr may be NULL where there is a loss
-    unsigned elems;             // S T - 1 fits; S T itself may be 2^31
-    float d, d2;                // float(sqrt(3 / (2 (L^2 - 1)))) and twice that
-    int n_factors;              // 1 .. kMaxFactors
-    int branches;               // 1 .. AFT_LINK_MAX_BRANCHES
-    int wide;                   // 1: 16-byte loads of ideal and est
-    int store;                  // bytes per store of llr: 16, 8 or 4
-};
 
 // One instantiation per modulation order, so the boundary loops unroll.  Counts: the bit and symbol errors.  Soft: the losses and, when
 // a.llr is there, the LLRs.  Branches: a.branches frames per group, combined with a.rho; otherwise one frame is the group.
@@ -194,40 +176,6 @@ __global__ __launch_bounds__(kFrameThreads) void link_soft_kernel(const LinkArgs
 template <int M>
 __global__ __launch_bounds__(kFrameThreads) void link_mrc_kernel(const LinkArgs a) {
     link_walk<M, true, true, true>(a);
-}
-
-// The arguments of a launch from the entry point's: the three launchers pass NULL (and 1 factor, 1 branch) for what they do not have.
-LinkArgs link_args(const aft_link &link, const float *ideal, const float *est, const unsigned long long *keys, const float *sigma,
-                   const float *rho, const float *scale, const float *factors, int n_factors, int branches, int32_t *counts,
-                   float *loss, float *llr) {
-    LinkArgs a{};
-    a.c = link;
-    a.ideal = reinterpret_cast<const float2 *>(ideal);
-    a.est = reinterpret_cast<const float2 *>(est);
-    a.keys = keys; a.sigma = sigma; a.rho = rho; a.scale = scale; a.factors = factors;
-    a.counts = counts; a.loss = loss; a.llr = llr;
-    a.n_factors = n_factors; a.branches = branches;
-    const unsigned long long elems = (unsigned long long)link.num_scs * (unsigned long long)link.num_symbols;
-    a.elems = (unsigned)(elems - 1);
-    const int m = link.bits_per_symbol, L = 1 << (m / 2);
-    a.d = (float)sqrt(3.0 / (2.0 * ((double)L * L - 1.0)));
-    a.d2 = 2.f * a.d;
-    a.wide = wide_ok(link.num_symbols, ideal, est);
-    a.store = link_llr_store_bytes(llr, m, elems);
-    return a;
-}
-
-// launch(std::integral_constant<int, M>) enqueues the kernel's instantiation for M = a.c.bits_per_symbol
-template <class Launch>
-hipError_t link_dispatch(int m, Launch &&launch) {
-    switch (m) {
-        case 2: launch(std::integral_constant<int, 2>{}); break;
-        case 4: launch(std::integral_constant<int, 4>{}); break;
-        case 6: launch(std::integral_constant<int, 6>{}); break;
-        case 8: launch(std::integral_constant<int, 8>{}); break;
-        default: return hipErrorInvalidValue;           // the entry point has refused it
-    }
-    return hipGetLastError();
 }
 
 }  // namespace

@@ -1,8 +1,9 @@
-// Two-stream spatial multiplexing on the link (include/adafortitran_amd.h "spatial multiplexing"; adafortitran_amd/linksim.py "the
-// spatial-multiplexing link" is the definition and the float64 twin): linear ZF / MMSE detection of N = 2 streams on R antennas.  One
-// workgroup per GROUP of 2 R consecutive frames -- frame r 2 + s is the pair (antenna r, stream s) --, one launch per batch; a group's
-// counts, losses and LLRs are a function of its own keys, noise scales, weights, true channels and estimates and of its leader's LLR
-// scale and regulariser only.  The walk is k_link.hip's link_walk with the combiner replaced by the detector:
+// The two-stream link (include/adafortitran_amd.h "spatial multiplexing", "joint detection"; adafortitran_amd/linksim.py "the
+// spatial-multiplexing link" and "the joint link" are the definitions and the float64 twins): N = 2 streams on R antennas, ONE frame
+// walk, link2_walk, and two detectors in its step 4.  One workgroup per GROUP of 2 R consecutive frames -- frame r 2 + s is the pair
+// (antenna r, stream s) --, one launch per batch; a group's counts, losses and LLRs are a function of its own keys, noise scales,
+// weights, true channels and estimates and of its leader's LLR scale (and, for the linear detector, regulariser) only.  The walk is
+// k_link.hip's link_walk with the combiner replaced by a detector:
 //
 //   1. the pilot positions go to LDS and the R keys, noise scales and weights of the frames (r, 0); the key of frame (0, 1) is the
 //      second stream's;
@@ -14,22 +15,43 @@
 //      y_r = H_r0 x_0 + H_r1 x_1 + noise (link_sample2: stream 0's product is link_branch's chain, stream 1's products are added by
 //      fused multiply-adds, the noise last) and adds the eight sums of the element (link_sm_accumulate: m_0, m_1, g00, g11, g01), one
 //      fused multiply-add per term in increasing r, the sums starting at -0;
-//   4. the two demappers run after it, in a stream loop around an element loop, neither unrolled: one copy of the soft code (at m = 8
-//      it is about 50 KB).  Per (stream, element) the adjugate detector (link_sm_detect: c_s, p_s, eff_s = scale / a_other) and then
-//      link_walk's measures on them: the hard decision against the stream's sent Gray codes, the max-log LLRs eff_s (min1 - min0)
-//      and, per factor, softplus of the LLR against its sent bit.  A stream's LLRs of the pair leave by link_store_llrs, in the
-//      soft link's store forms;
+//   4. the detector runs after it, in a stream loop around an element loop, neither unrolled: one copy of its code (the linear one
+//      is about 50 KB at m = 8).  Per (stream, element) it turns the eight sums into the M LLRs and the number of wrong bits; the
+//      loss is link_soft_losses on those LLRs, per factor softplus of the LLR against its sent bit, and a stream's LLRs of the pair
+//      leave by link_store_llrs, in the soft link's store forms.
+//        linear (link2_linear)  the adjugate detector (link_sm_detect: c_s, p_s, eff_s = scale / a_other) and then link_walk's
+//          measures on them: the hard decision against the stream's sent Gray codes and the max-log LLRs eff_s (min1 - min0);
+//        joint (link2_joint)  the exact max-log LLR of every bit, 2 M candidate evaluations per element instead of M^2, because for
+//          a fixed symbol of one stream the best symbol of the other separates per axis (link_joint_llrs).  For stream e with the
+//          other stream o, over the candidates x_e = a_ki + j a_kq, ki outside (a rolled loop) and kq inside (unrolled: the L column
+//          minima and the L Q-axis terms t(kq) = mu_kq(Im m_e, g_ee) live in registers under constant indices):
+//            per row        a_ki, t(ki) = mu_ki(Re m_e, g_ee) and the row's share of z: base = m_o - g_oe a_ki, two fused
+//                           multiply-adds;
+//            per candidate  z = base - j g_oe a_kq, two more (the four of z(x_e) = m_o - g_oe x_e, the a_ki terms first); per axis of
+//                           z the inner minimum over the L / 2 positive levels of fma(-2 a_k, |comp|, a_k^2 g_oo) -- mu_k of the
+//                           level on comp's side; the mirrored level is never smaller --; f = (t(ki) + t(kq)) + (r_I + r_Q); the
+//                           row and the column minimum;
+//            per row        the I-axis bits' two minima take the row minimum by the Gray label of ki;
+//            at the end     the Q-axis bits' two minima take the column minima by the labels of kq; Lambda_j = scale (min1 - min0).
+//          The two axes of z run as one float2: z's second fused multiply-add and each level's are one v_pk_fma_f32 for both axes
+//          (the same correctly rounded results as two scalar ones), so a candidate is 1 + L / 2 packed fused multiply-adds, L minima
+//          of the two scans, 3 additions and 2 minima: 3 L / 2 + 6 VALU operations by the source (30 at 256-QAM; the compiled row of
+//          16 candidates is 544, 34 each, with the |comp| masks and moves) and 2 m + L live minima; no LDS.  The hard decision is
+//          the sign of the stream's own LLRs (bit j is 1 iff Lambda_j < 0), counted against the sent Gray codes;
 //   5. per stream the two integer counts and the K float sums stay in registers and are reduced in link_walk's fixed order: shuffles
 //      in the wave, then the four waves through LDS.
 //
 // No atomics and no workspace: a group's outputs depend neither on the batch, nor on its position in it, nor on the run, nor on the
 // load or store form or the alignment of the bases, nor on whether the LLRs are stored.  Rounding: the build has no fast-math, and
 // without it the compiler's default for HIP is a correctly rounded float32 division (-fhip-fp32-correctly-rounded-divide-sqrt), so
-// `scale / a_other` is ONE rounding; every product is a fused multiply-add chain written as such, and the detector and the soft
-// pieces are compiled under `fp contract(off)`, so nothing is contracted behind the source.  With an unheard second stream
-// (H_r1 = E_r1 = 0) and reg scale = 1 in powers of two, stream 0 is link_mrc_kernel's output on the frames (r, 0), bit for bit.
-#include <type_traits>
-
+// the linear detector's `scale / a_other` is ONE rounding (the joint one has no division anywhere); every product is a fused
+// multiply-add chain written as such, and the detectors and the soft pieces are compiled under `fp contract(off)`, so nothing is
+// contracted behind the source.  Linear: with an unheard second stream (H_r1 = E_r1 = 0) and reg scale = 1 in powers of two, stream 0
+// is link_mrc_kernel's output on the frames (r, 0), bit for bit.  Joint: the minima start at +infinity and every bit has candidates on
+// both sides, so finite operands give finite LLRs; all-zero estimates give f = 0 for every candidate and LLRs of 0.
+//
+//   link_sm_kernel     (aft_link_sm_f32)     the linear ZF / MMSE detector
+//   link_joint_kernel  (aft_link_joint_f32)  the joint max-log demapper
 #include "link_device.h"
 
 namespace aft {
@@ -37,24 +59,43 @@ namespace {
 
 constexpr int kSmStreams = AFT_LINK_MAX_STREAMS;
 
-struct LinkSmArgs {
-    aft_link c;
-    const float2 *ideal, *est;
-    const unsigned long long *keys;
-    const float *sigma, *rho, *scale, *reg, *factors;
-    int *counts;
-    float *loss, *llr;          // llr may be NULL
-    unsigned elems;             // S T - 1 fits; S T itself may be 2^31
-    float d, d2;                // float(sqrt(3 / (2 (L^2 - 1)))) and twice that
-    int n_factors;              // 1 .. kMaxFactors
-    int branches;               // 2 .. AFT_LINK_MAX_BRANCHES
-    int wide;                   // 1: 16-byte loads of ideal and est
-    int store;                  // bytes per store of llr: 16, 8 or 4
+// link_args' struct and, per group, the linear detector's regulariser: NULL, and never read, on the joint launch
+struct Link2Args : LinkArgs {
+    const float *reg;
 };
 
+// Step 4, linear: the M LLRs of stream `second` of an element with the sums e into w -- I-axis bits first, MSB first, the order of the
+// sent word --; returns the number of bits decided against the sent Gray codes gi, gq.  (The codes by value and w by pointer: with
+// the sent word and the array by reference link_joint_kernel<2> takes 4 more VGPRs.)
 template <int M>
-__global__ __launch_bounds__(kFrameThreads) void link_sm_kernel(const LinkSmArgs a) {
+__device__ __forceinline__ int link2_linear(float d, float d2, const LinkSm &e, float reg, float scale, bool second, unsigned gi,
+                                            unsigned gq, float *w) {
     constexpr int half = M / 2, L = 1 << half;
+    const LinkDetected m = link_sm_detect(e, reg, scale, second);
+    const float step = d2 * m.p;
+    const unsigned ki = decide<L>(m.cr, step), kq = decide<L>(m.ci, step);
+    link_axis_llrs<L>(d, m.cr, m.p, m.eff, w);
+    link_axis_llrs<L>(d, m.ci, m.p, m.eff, w + half);
+    return __popc(gi ^ ki ^ (ki >> 1)) + __popc(gq ^ kq ^ (kq >> 1));
+}
+
+// Step 4, joint: the same results from link_joint_llrs; the decided Gray codes are the signs of the LLRs
+template <int M>
+__device__ __forceinline__ int link2_joint(float d, const LinkSm &e, float scale, bool second, unsigned gi, unsigned gq, float *w) {
+    constexpr int half = M / 2;
+    link_joint_llrs<M>(d, e, scale, second, w);
+    unsigned hi = 0, hq = 0;                                    // bit j is 1 iff its LLR is negative
+#pragma unroll
+    for (int j = 0; j < half; ++j) {
+        hi = (hi << 1) | (w[j] < 0.f ? 1u : 0u);
+        hq = (hq << 1) | (w[half + j] < 0.f ? 1u : 0u);
+    }
+    return __popc(gi ^ hi) + __popc(gq ^ hq);
+}
+
+// One instantiation per modulation order and detector
+template <int M, bool Joint>
+__device__ __forceinline__ void link2_walk(const Link2Args &a) {
     __shared__ int psc[AFT_CHANSIM_MAX_PILOT_SCS], psym[AFT_CHANSIM_MAX_PILOT_SYMBOLS];
     __shared__ unsigned long long bkey[AFT_LINK_MAX_BRANCHES];
     __shared__ float bsigma[AFT_LINK_MAX_BRANCHES], brho[AFT_LINK_MAX_BRANCHES];
@@ -77,7 +118,9 @@ __global__ __launch_bounds__(kFrameThreads) void link_sm_kernel(const LinkSmArgs
     }
     __syncthreads();
     const unsigned long long k0 = bkey[0], k1 = a.keys[first + 1];      // one transmission per stream: the keys of frames (0, s)
-    const float scale = a.scale[g], reg = a.reg[g];
+    const float scale = a.scale[g];
+    float reg = 0.f;
+    if constexpr (!Joint) reg = a.reg[g];
     float fac[kMaxFactors], acc0[kMaxFactors], acc1[kMaxFactors];
 #pragma unroll
     for (int k = 0; k < kMaxFactors; ++k) {
@@ -112,7 +155,7 @@ __global__ __launch_bounds__(kFrameThreads) void link_sm_kernel(const LinkSmArgs
             if (d1) link_sm_accumulate(e1, rho, link_sample2(kf, sr, q + 1, s01, s11, h0.b, h1.b), g0.b, g1.b);
         }
 #pragma unroll 1
-        for (int t = 0; t < kSmStreams; ++t) {                  // the stream; the element inside: one copy of the demapper
+        for (int t = 0; t < kSmStreams; ++t) {                  // the stream; the element inside: one copy of the detector
             float v[2 * M], acc[kMaxFactors];
 #pragma unroll
             for (int j = 0; j < 2 * M; ++j) v[j] = 0.f;         // what a pilot position carries
@@ -123,15 +166,12 @@ __global__ __launch_bounds__(kFrameThreads) void link_sm_kernel(const LinkSmArgs
             for (int s = 0; s < 2; ++s) {
                 if (s ? d1 : d0) {
                     const LinkSent x = t ? (s ? s11 : s10) : (s ? s01 : s00);
-                    const LinkDetected m = link_sm_detect(s ? e1 : e0, reg, scale, t != 0);
-                    const float step = a.d2 * m.p;
-                    const unsigned ki = decide<L>(m.cr, step), kq = decide<L>(m.ci, step);
-                    const int wrong = __popc(x.gi ^ ki ^ (ki >> 1)) + __popc(x.gq ^ kq ^ (kq >> 1));
+                    float w[M];
+                    int wrong;
+                    if constexpr (Joint) wrong = link2_joint<M>(a.d, s ? e1 : e0, scale, t != 0, x.gi, x.gq, w);
+                    else wrong = link2_linear<M>(a.d, a.d2, s ? e1 : e0, reg, scale, t != 0, x.gi, x.gq, w);
                     bits += wrong;
                     symbols += wrong != 0 ? 1 : 0;
-                    float w[M];                                 // the M LLRs: I-axis bits first, MSB first, the order of the sent word
-                    link_axis_llrs<L>(a.d, m.cr, m.p, m.eff, w);
-                    link_axis_llrs<L>(a.d, m.ci, m.p, m.eff, w + half);
                     link_soft_losses<M>(w, x.gi, x.gq, fac, nf, acc);
 #pragma unroll
                     for (int j = 0; j < M; ++j) {
@@ -169,34 +209,27 @@ __global__ __launch_bounds__(kFrameThreads) void link_sm_kernel(const LinkSmArgs
     if (tid >= kWave && tid < kWave + 2 * kSmStreams) a.counts[2 * kSmStreams * g + (tid - kWave)] = link_block_sum(ipart, tid - kWave);
 }
 
+template <int M>
+__global__ __launch_bounds__(kFrameThreads) void link_sm_kernel(const Link2Args a) {
+    link2_walk<M, false>(a);
+}
+
+template <int M>
+__global__ __launch_bounds__(kFrameThreads) void link_joint_kernel(const Link2Args a) {
+    link2_walk<M, true>(a);
+}
+
 }  // namespace
 
-hipError_t launch_link_sm(const aft_link &link, const float *ideal, const float *est, const unsigned long long *keys,
-                          const float *sigma, const float *rho, const float *scale, const float *reg, const float *factors,
-                          int n_factors, int branches, int32_t *counts, float *loss, float *llr, int batch, hipStream_t st) {
-    LinkSmArgs a{};
-    a.c = link;
-    a.ideal = reinterpret_cast<const float2 *>(ideal);
-    a.est = reinterpret_cast<const float2 *>(est);
-    a.keys = keys; a.sigma = sigma; a.rho = rho; a.scale = scale; a.reg = reg; a.factors = factors;
-    a.counts = counts; a.loss = loss; a.llr = llr;
-    a.n_factors = n_factors; a.branches = branches;
-    const unsigned long long elems = (unsigned long long)link.num_scs * (unsigned long long)link.num_symbols;
-    a.elems = (unsigned)(elems - 1);
-    const int m = link.bits_per_symbol, L = 1 << (m / 2);
-    a.d = (float)sqrt(3.0 / (2.0 * ((double)L * L - 1.0)));
-    a.d2 = 2.f * a.d;
-    a.wide = wide_ok(link.num_symbols, ideal, est);
-    a.store = link_llr_store_bytes(llr, m, elems);
+hipError_t launch_link2(bool joint, const aft_link &link, const float *ideal, const float *est, const unsigned long long *keys,
+                        const float *sigma, const float *rho, const float *scale, const float *reg, const float *factors, int n_factors,
+                        int branches, int32_t *counts, float *loss, float *llr, int batch, hipStream_t st) {
+    const Link2Args a{link_args(link, ideal, est, keys, sigma, rho, scale, factors, n_factors, branches, counts, loss, llr), reg};
     const dim3 grid((unsigned)(batch / (branches * kSmStreams)));
-    switch (m) {
-        case 2: hipLaunchKernelGGL(link_sm_kernel<2>, grid, dim3(kFrameThreads), 0, st, a); break;
-        case 4: hipLaunchKernelGGL(link_sm_kernel<4>, grid, dim3(kFrameThreads), 0, st, a); break;
-        case 6: hipLaunchKernelGGL(link_sm_kernel<6>, grid, dim3(kFrameThreads), 0, st, a); break;
-        case 8: hipLaunchKernelGGL(link_sm_kernel<8>, grid, dim3(kFrameThreads), 0, st, a); break;
-        default: return hipErrorInvalidValue;           // the entry point has refused it
-    }
-    return hipGetLastError();
+    return link_dispatch(link.bits_per_symbol, [&](auto m) {
+        if (joint) hipLaunchKernelGGL(link_joint_kernel<decltype(m)::value>, grid, dim3(kFrameThreads), 0, st, a);
+        else hipLaunchKernelGGL(link_sm_kernel<decltype(m)::value>, grid, dim3(kFrameThreads), 0, st, a);
+    });
 }
 
 }  // namespace aft

@@ -1,10 +1,13 @@
 // What the link front end is made of (k_link.hip), each piece written once, so every instantiation sees the same bits: the pilot staging
 // and lookup, the pair loads, the Gray map, the hard decision, the front of a data element -- split into the sent word (one per
 // transmission) and a branch (one per receive antenna: y = H x + noise, c = y conj(E), p = |E|^2) --, the combiner's step, an axis's
-// max-log LLRs, the softplus step of the loss, the LLR store and the reduction of a workgroup's sums; and what two-stream detection
-// (k_linksm.hip) adds to them: the two-stream received sample, the Gram / matched sums, the adjugate detector with its LLR scale.
+// max-log LLRs, the softplus step of the loss, the LLR store, the reduction of a workgroup's sums and, on the host, a launch's
+// arguments and its dispatch on the modulation order; and what two-stream detection (k_linksm.hip) adds to them: the two-stream
+// received sample, the Gram / matched sums, the adjugate detector with its LLR scale and the joint max-log demapper.
 // adafortitran_amd/linksim.py holds the definitions.
 #pragma once
+
+#include <type_traits>
 
 #include "frame_device.h"
 
@@ -165,6 +168,89 @@ __device__ __forceinline__ LinkDetected link_sm_detect(const LinkSm &a, float re
     return LinkDetected{fmaf(ao, msr, -tr), fmaf(ao, msi, -ti), fmaf(gs, ao, -n01), ao > 0.f ? scale / ao : 0.f};
 }
 
+// ---- joint max-log detection of the two streams (k_linksm.hip; linksim.py "the joint link") ----
+
+// r = min_k mu_k(z.x, p) + min_k mu_k(z.y, p), mu_k(comp, p) = a_k (a_k p - 2 comp): both axes of z at once, each scanned over the
+// positive levels against |comp| -- neg2a[i] = -2 a and pk[i] = a^2 p of level a = (2 i + 1) d.  The two axes' fused multiply-adds
+// are one packed instruction (v_pk_fma_f32: the same two correctly rounded results), which matters where one wave owns a SIMD
+template <int H>
+__device__ __forceinline__ float link_joint_inner_min(f32x2 z, const float (&neg2a)[H], const float (&pk)[H]) {
+#pragma clang fp contract(off)
+    const f32x2 c = f32x2{fabsf(z.x), fabsf(z.y)};
+    f32x2 best = __builtin_elementwise_fma(f32x2{neg2a[0], neg2a[0]}, c, f32x2{pk[0], pk[0]});
+#pragma unroll
+    for (int i = 1; i < H; ++i) {
+        const f32x2 mu = __builtin_elementwise_fma(f32x2{neg2a[i], neg2a[i]}, c, f32x2{pk[i], pk[i]});
+        best = f32x2{fminf(best.x, mu.x), fminf(best.y, mu.y)};
+    }
+    return best.x + best.y;
+}
+
+// The M max-log LLRs of stream e (`second` picks the roles) from an element's eight sums: out[j] = scale (min1 - min0) of
+// f(x_e) = g_ee |x_e|^2 - 2 Re(conj(x_e) m_e) + min over x_o of (g_oo |x_o|^2 - 2 Re(conj(x_o) (m_o - g_oe x_e))), I-axis bits first,
+// MSB first: the order of the sent word.
+template <int M>
+__device__ __forceinline__ void link_joint_llrs(float d, const LinkSm &a, float scale, bool second, float *out) {
+#pragma clang fp contract(off)
+    constexpr int half = M / 2, L = 1 << half, H = L / 2;
+    const float ge = second ? a.g11 : a.g00, go = second ? a.g00 : a.g11;
+    const float mer = second ? a.m1r : a.m0r, mei = second ? a.m1i : a.m0i;
+    const float mor = second ? a.m0r : a.m1r, moi = second ? a.m0i : a.m1i;
+    const float gxr = a.g01r, gxi = second ? a.g01i : -a.g01i;  // g_oe: g01 for stream 1, conj(g01) for stream 0
+    float neg2a[H], pk[H];
+#pragma unroll
+    for (int i = 0; i < H; ++i) {
+        const float ak = d * (float)(2 * i + 1);
+        neg2a[i] = -2.f * ak;
+        pk[i] = (ak * ak) * go;
+    }
+    const float m2q = -2.f * mei, m2i = -2.f * mer;
+    float tq[L], col[L];
+#pragma unroll
+    for (int k = 0; k < L; ++k) {
+        const float ak = d * (float)(2 * k - (L - 1));
+        tq[k] = ak * fmaf(ak, ge, m2q);
+        col[k] = INFINITY;
+    }
+    float i0[half], i1[half];
+#pragma unroll
+    for (int j = 0; j < half; ++j) i0[j] = i1[j] = INFINITY;
+#pragma unroll 1
+    for (int ki = 0; ki < L; ++ki) {
+        const float ai = d * (float)(2 * ki - (L - 1));
+        const float ti = ai * fmaf(ai, ge, m2i);
+        const f32x2 base = f32x2{fmaf(-gxr, ai, mor), fmaf(-gxi, ai, moi)}, turn = f32x2{gxi, -gxr};    // z = base - j g_oe a_kq
+        float row = INFINITY;
+#pragma unroll
+        for (int kq = 0; kq < L; ++kq) {
+            const float aq = d * (float)(2 * kq - (L - 1));
+            const f32x2 z = __builtin_elementwise_fma(turn, f32x2{aq, aq}, base);
+            const float r = link_joint_inner_min<H>(z, neg2a, pk);
+            const float f = (ti + tq[kq]) + r;
+            row = fminf(row, f);
+            col[kq] = fminf(col[kq], f);
+        }
+        const unsigned label = (unsigned)ki ^ ((unsigned)ki >> 1);
+#pragma unroll
+        for (int j = 0; j < half; ++j) {
+            const bool one = (label >> (half - 1 - j)) & 1u;
+            i1[j] = one ? fminf(i1[j], row) : i1[j];
+            i0[j] = one ? i0[j] : fminf(i0[j], row);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < half; ++j) {
+        float q0 = INFINITY, q1 = INFINITY;
+#pragma unroll
+        for (int k = 0; k < L; ++k) {
+            if (((k ^ (k >> 1)) >> (half - 1 - j)) & 1) q1 = fminf(q1, col[k]);
+            else q0 = fminf(q0, col[k]);
+        }
+        out[j] = scale * (i1[j] - i0[j]);
+        out[half + j] = scale * (q1 - q0);
+    }
+}
+
 // ---- the soft half: max-log LLRs and the loss the achievable rate is read from (linksim.py "the soft link") ----
 
 constexpr int kMaxFactors = 8;
@@ -262,6 +348,58 @@ __device__ __forceinline__ T link_block_sum(const T (*part)[N], int slot) {
 inline int link_llr_store_bytes(const float *llr, int m, unsigned long long elems) {
     const uintptr_t at = reinterpret_cast<uintptr_t>(llr);
     return at % 16 == 0 && (m % 4 == 0 || elems % 2 == 0) ? 16 : at % 8 == 0 ? 8 : 4;
+}
+
+// ---- a launch's arguments and its dispatch on the modulation order (k_link.hip, k_linksm.hip) ----
+
+// the union of what the front end's kernels read and write; a pointer an instantiation does not use is NULL
+struct LinkArgs {
+    aft_link c;
+    const float2 *ideal, *est;
+    const unsigned long long *keys;
+    const float *sigma, *rho, *scale, *factors;
+    int *counts;
+    float *loss, *llr;          // llr may be NULL where there is a loss
+    unsigned elems;             // S T - 1 fits; S T itself may be 2^31
+    float d, d2;                // float(sqrt(3 / (2 (L^2 - 1)))) and twice that
+    int n_factors;              // 1 .. kMaxFactors
+    int branches;               // 1 .. AFT_LINK_MAX_BRANCHES
+    int wide;                   // 1: 16-byte loads of ideal and est
+    int store;                  // bytes per store of llr: 16, 8 or 4
+};
+
+// The arguments of a launch from the entry point's: a launcher passes NULL (and 1 factor, 1 branch) for what it does not have.
+inline LinkArgs link_args(const aft_link &link, const float *ideal, const float *est, const unsigned long long *keys, const float *sigma,
+                          const float *rho, const float *scale, const float *factors, int n_factors, int branches, int32_t *counts,
+                          float *loss, float *llr) {
+    LinkArgs a{};
+    a.c = link;
+    a.ideal = reinterpret_cast<const float2 *>(ideal);
+    a.est = reinterpret_cast<const float2 *>(est);
+    a.keys = keys; a.sigma = sigma; a.rho = rho; a.scale = scale; a.factors = factors;
+    a.counts = counts; a.loss = loss; a.llr = llr;
+    a.n_factors = n_factors; a.branches = branches;
+    const unsigned long long elems = (unsigned long long)link.num_scs * (unsigned long long)link.num_symbols;
+    a.elems = (unsigned)(elems - 1);
+    const int m = link.bits_per_symbol, L = 1 << (m / 2);
+    a.d = (float)sqrt(3.0 / (2.0 * ((double)L * L - 1.0)));
+    a.d2 = 2.f * a.d;
+    a.wide = wide_ok(link.num_symbols, ideal, est);
+    a.store = link_llr_store_bytes(llr, m, elems);
+    return a;
+}
+
+// launch(std::integral_constant<int, M>) enqueues the kernel's instantiation for M = a.c.bits_per_symbol
+template <class Launch>
+hipError_t link_dispatch(int m, Launch &&launch) {
+    switch (m) {
+        case 2: launch(std::integral_constant<int, 2>{}); break;
+        case 4: launch(std::integral_constant<int, 4>{}); break;
+        case 6: launch(std::integral_constant<int, 6>{}); break;
+        case 8: launch(std::integral_constant<int, 8>{}); break;
+        default: return hipErrorInvalidValue;           // the entry point has refused it
+    }
+    return hipGetLastError();
 }
 
 }  // namespace

@@ -5,6 +5,7 @@ csrc/*.hip.  Nothing in this module falls back to PyTorch math.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Dict, Optional
 
 import numpy as np
@@ -526,6 +527,29 @@ class LinkPlan:
             raise ValueError(f"factors must hold between 1 and 8 values, got {factors.numel() if torch.is_tensor(factors) else factors!r}")
         return _in_place("factors", factors, torch.float32, self.device, factors.numel())
 
+    def _grouped(self, entry: str, ideal, est, keys, sigma, rho, per_group, factors, want_llr: bool, lib):
+        """What the grouped front ends (``LinkMrcPlan``, ``LinkSmPlan``, ``LinkJointPlan``) share.  ``self.group`` is the group's
+        width, ``(branches,)`` or ``(branches, streams)``, passed to ``entry`` as it stands; ``per_group`` names the float32 operands
+        with one value per group, in the entry point's order.  Returns ``(counts, loss, llr)`` for ``groups * streams`` rows."""
+        lib = lib or _lib.load()
+        batch, ideal, est, keys, sigma = self._checked(ideal, est, keys, sigma)
+        if batch % math.prod(self.group):
+            raise ValueError(f"a batch of {batch} frames is not a multiple of {' * '.join(('branches', 'streams')[:len(self.group)])} = "
+                             f"{' * '.join(map(str, self.group))}")
+        groups = batch // math.prod(self.group)
+        rows = groups * math.prod(self.group[1:])
+        rho = _in_place("rho", rho, torch.float32, self.device, batch)
+        per_group = [_in_place(name, t, torch.float32, self.device, groups) for name, t in per_group]
+        factors = self._checked_factors(factors)
+        counts = torch.empty((rows, 2), dtype=torch.int32, device=self.device)                  # the kernel writes every element
+        loss = torch.empty((rows, factors.numel()), dtype=torch.float32, device=self.device)
+        llr = torch.empty((rows, *self.grid, self.cfg.bits_per_symbol), dtype=torch.float32, device=self.device) if want_llr else None
+        _lib.check(getattr(lib, entry)(C.byref(self.link), ideal.data_ptr(), est.data_ptr(), keys.data_ptr(), sigma.data_ptr(),
+                                       rho.data_ptr(), *(t.data_ptr() for t in per_group), factors.data_ptr(), factors.numel(),
+                                       *self.group, counts.data_ptr(), loss.data_ptr(), _ptr(llr), batch,
+                                       _lib.current_stream_ptr(self.device)), lib)
+        return counts, loss, llr
+
     def __call__(self, ideal: torch.Tensor, est: torch.Tensor, keys: torch.Tensor, sigma: torch.Tensor, lib=None) -> torch.Tensor:
         lib = lib or _lib.load()
         batch, ideal, est, keys, sigma = self._checked(ideal, est, keys, sigma)
@@ -570,25 +594,11 @@ class LinkMrcPlan(LinkPlan):
         super().__init__(cfg, device)
         if isinstance(branches, bool) or not isinstance(branches, int) or not 1 <= branches <= _abi.AFT_LINK_MAX_BRANCHES:
             raise ValueError(f"branches = {branches!r}: an integer in 1 .. {_abi.AFT_LINK_MAX_BRANCHES}")
-        self.branches = branches
+        self.branches, self.group = branches, (branches,)
 
     def __call__(self, ideal: torch.Tensor, est: torch.Tensor, keys: torch.Tensor, sigma: torch.Tensor, rho: torch.Tensor,
                  scale: torch.Tensor, factors: torch.Tensor, want_llr: bool = False, lib=None):
-        lib = lib or _lib.load()
-        batch, ideal, est, keys, sigma = self._checked(ideal, est, keys, sigma)
-        if batch % self.branches:
-            raise ValueError(f"a batch of {batch} frames is not a multiple of branches = {self.branches}")
-        groups = batch // self.branches
-        rho = _in_place("rho", rho, torch.float32, self.device, batch)
-        scale = _in_place("scale", scale, torch.float32, self.device, groups)
-        factors = self._checked_factors(factors)
-        counts = torch.empty((groups, 2), dtype=torch.int32, device=self.device)                # the kernel writes every element
-        loss = torch.empty((groups, factors.numel()), dtype=torch.float32, device=self.device)
-        llr = torch.empty((groups, *self.grid, self.cfg.bits_per_symbol), dtype=torch.float32, device=self.device) if want_llr else None
-        _lib.check(lib.aft_link_mrc_f32(C.byref(self.link), ideal.data_ptr(), est.data_ptr(), keys.data_ptr(), sigma.data_ptr(),
-                                        rho.data_ptr(), scale.data_ptr(), factors.data_ptr(), factors.numel(), self.branches,
-                                        counts.data_ptr(), loss.data_ptr(), _ptr(llr), batch, _lib.current_stream_ptr(self.device)), lib)
-        return counts, loss, llr
+        return self._grouped("aft_link_mrc_f32", ideal, est, keys, sigma, rho, [("scale", scale)], factors, want_llr, lib)
 
 
 class LinkSmPlan(LinkPlan):
@@ -610,28 +620,11 @@ class LinkSmPlan(LinkPlan):
         if isinstance(branches, bool) or not isinstance(branches, int) or not 2 <= branches <= _abi.AFT_LINK_MAX_BRANCHES:
             raise ValueError(f"branches = {branches!r}: an integer in 2 .. {_abi.AFT_LINK_MAX_BRANCHES} (one antenna cannot separate "
                              f"{streams} streams)")
-        self.branches, self.streams = branches, streams
+        self.branches, self.streams, self.group = branches, streams, (branches, streams)
 
     def __call__(self, ideal: torch.Tensor, est: torch.Tensor, keys: torch.Tensor, sigma: torch.Tensor, rho: torch.Tensor,
                  scale: torch.Tensor, reg: torch.Tensor, factors: torch.Tensor, want_llr: bool = False, lib=None):
-        lib = lib or _lib.load()
-        batch, ideal, est, keys, sigma = self._checked(ideal, est, keys, sigma)
-        if batch % (self.branches * self.streams):
-            raise ValueError(f"a batch of {batch} frames is not a multiple of branches * streams = {self.branches} * {self.streams}")
-        groups = batch // (self.branches * self.streams)
-        rows = groups * self.streams
-        rho = _in_place("rho", rho, torch.float32, self.device, batch)
-        scale = _in_place("scale", scale, torch.float32, self.device, groups)
-        reg = _in_place("reg", reg, torch.float32, self.device, groups)
-        factors = self._checked_factors(factors)
-        counts = torch.empty((rows, 2), dtype=torch.int32, device=self.device)                  # the kernel writes every element
-        loss = torch.empty((rows, factors.numel()), dtype=torch.float32, device=self.device)
-        llr = torch.empty((rows, *self.grid, self.cfg.bits_per_symbol), dtype=torch.float32, device=self.device) if want_llr else None
-        _lib.check(lib.aft_link_sm_f32(C.byref(self.link), ideal.data_ptr(), est.data_ptr(), keys.data_ptr(), sigma.data_ptr(),
-                                       rho.data_ptr(), scale.data_ptr(), reg.data_ptr(), factors.data_ptr(), factors.numel(),
-                                       self.branches, self.streams, counts.data_ptr(), loss.data_ptr(), _ptr(llr), batch,
-                                       _lib.current_stream_ptr(self.device)), lib)
-        return counts, loss, llr
+        return self._grouped("aft_link_sm_f32", ideal, est, keys, sigma, rho, [("scale", scale), ("reg", reg)], factors, want_llr, lib)
 
 
 class LinkJointPlan(LinkSmPlan):
@@ -643,23 +636,7 @@ class LinkJointPlan(LinkSmPlan):
 
     def __call__(self, ideal: torch.Tensor, est: torch.Tensor, keys: torch.Tensor, sigma: torch.Tensor, rho: torch.Tensor,
                  scale: torch.Tensor, factors: torch.Tensor, want_llr: bool = False, lib=None):
-        lib = lib or _lib.load()
-        batch, ideal, est, keys, sigma = self._checked(ideal, est, keys, sigma)
-        if batch % (self.branches * self.streams):
-            raise ValueError(f"a batch of {batch} frames is not a multiple of branches * streams = {self.branches} * {self.streams}")
-        groups = batch // (self.branches * self.streams)
-        rows = groups * self.streams
-        rho = _in_place("rho", rho, torch.float32, self.device, batch)
-        scale = _in_place("scale", scale, torch.float32, self.device, groups)
-        factors = self._checked_factors(factors)
-        counts = torch.empty((rows, 2), dtype=torch.int32, device=self.device)                  # the kernel writes every element
-        loss = torch.empty((rows, factors.numel()), dtype=torch.float32, device=self.device)
-        llr = torch.empty((rows, *self.grid, self.cfg.bits_per_symbol), dtype=torch.float32, device=self.device) if want_llr else None
-        _lib.check(lib.aft_link_joint_f32(C.byref(self.link), ideal.data_ptr(), est.data_ptr(), keys.data_ptr(), sigma.data_ptr(),
-                                          rho.data_ptr(), scale.data_ptr(), factors.data_ptr(), factors.numel(), self.branches,
-                                          self.streams, counts.data_ptr(), loss.data_ptr(), _ptr(llr), batch,
-                                          _lib.current_stream_ptr(self.device)), lib)
-        return counts, loss, llr
+        return self._grouped("aft_link_joint_f32", ideal, est, keys, sigma, rho, [("scale", scale)], factors, want_llr, lib)
 
 
 class _DecoderPlan:

@@ -121,7 +121,7 @@ or ``N > 2``.
 
 The joint link.  A linear detector on a 2 x 2 Rayleigh channel has diversity order 1; a receiver that ships two-stream reception runs a
 max-log joint demapper and gets order 2, and behind it an estimation error no longer leaks through an ill-conditioned inverse: it
-enters as a mismatched metric.  ``link_joint_host`` (float64), ``aft_link_joint_f32`` (csrc/k_linkjoint.hip, through
+enters as a mismatched metric.  ``link_joint_host`` (float64), ``aft_link_joint_f32`` (csrc/k_linksm.hip, through
 ``hip_ops.LinkJointPlan``) and ``detector="joint"`` (``JOINT_DETECTOR``; ``ALL_DETECTORS`` lists it after the linear ones) on the
 accumulators and sweeps with ``streams=2`` are that demapper.  The layout, the keys, ``sent``, ``received``, ``weights`` and the eight sums
 ``m_0, m_1, g00, g11, g01`` are exactly the spatial-multiplexing link's: the same increasing ``r``, the same fused multiply-add per term,
@@ -465,6 +465,31 @@ def link_llrs_host(cfg: LinkConfig, keys, ideal, est, sigma, scale, factors=(1.0
     return _soft(cfg, *_front(cfg, keys, ideal, est, sigma), scale, factors, e_lambda)
 
 
+def _gray_split(metric: np.ndarray, half: int) -> list:
+    """Per bit ``j`` of an axis's Gray label (MSB first) the minimum of ``metric [..., L]`` over the levels whose bit is 1 less the
+    minimum over those whose bit is 0: ``half`` arrays."""
+    k = np.arange(metric.shape[-1])
+    ones = [((((k ^ (k >> 1)) >> (half - 1 - j)) & 1).astype(bool)) for j in range(half)]
+    return [metric[..., one].min(axis=-1) - metric[..., ~one].min(axis=-1) for one in ones]
+
+
+def _sent_signs(gi: np.ndarray, gq: np.ndarray, half: int) -> np.ndarray:
+    """``1 - 2 b_j`` of the sent Gray codes ``[...]`` -> float64 ``[..., m]``, I-axis bits first, MSB first."""
+    sign = np.empty((*gi.shape, 2 * half))
+    for axis, sent in enumerate((gi, gq)):
+        for j in range(half):
+            sign[..., axis * half + j] = 1 - 2 * ((sent >> (half - 1 - j)) & 1)
+    return sign
+
+
+def _losses_at(sign: np.ndarray, mask: np.ndarray, factors: np.ndarray):
+    """``lam [..., S, T, m]`` -> the losses ``[..., K]`` of the LLRs ``lam`` against the sent bits at the factors, in bits."""
+    def losses(lam):
+        z = -(sign * lam)
+        return np.stack([(np.logaddexp(0.0, f * z) * mask).sum(axis=(-3, -2, -1)) for f in factors], axis=-1) / np.log(2.0)
+    return losses
+
+
 def _soft(cfg: LinkConfig, gi, gq, c, p, reach, scale, factors, e_lambda, p_reach=None):
     """The LLRs and the losses on ``c`` and ``p``: what ``link_llrs_host`` returns.  ``scale`` float64 ``[n, S, T]`` is taken per element
     as it is (the spatial-multiplexing link's ``eff``, with ``p_reach`` the reach of its ``p``)."""
@@ -480,23 +505,16 @@ def _soft(cfg: LinkConfig, gi, gq, c, p, reach, scale, factors, e_lambda, p_reac
     scale = np.broadcast_to(scale, (n, S * T)).reshape(n, S, T)
     p_reach = p if p_reach is None else p_reach
     factors = _factors(factors).astype(np.float64)
-    k = np.arange(L)
-    a, label = d * (2 * k - (L - 1)), k ^ (k >> 1)
+    a = d * (2 * np.arange(L) - (L - 1))
     mask = cfg.data_mask[None, :, :, None]
     llr = np.empty((n, S, T, m))
-    sign = np.empty((n, S, T, m))                              # 1 - 2 b_j
-    for axis, (comp, sent) in enumerate(((c.real, gi), (c.imag, gq))):
+    for axis, comp in enumerate((c.real, c.imag)):
         mu = a * (a * p[..., None] - 2.0 * comp[..., None])                      # [n, S, T, L]
-        for j in range(half):
-            one = ((label >> (half - 1 - j)) & 1).astype(bool)
-            llr[..., axis * half + j] = mu[..., one].min(axis=-1) - mu[..., ~one].min(axis=-1)
-            sign[..., axis * half + j] = 1 - 2 * ((sent >> (half - 1 - j)) & 1)
+        for j, delta in enumerate(_gray_split(mu, half)):
+            llr[..., axis * half + j] = delta
     llr *= scale[..., None] * mask
-
-    def losses(lam):
-        z = -(sign * lam)
-        return np.stack([(np.logaddexp(0.0, f * z) * mask).sum(axis=(1, 2, 3)) for f in factors], axis=1) / np.log(2.0)
-
+    sign = _sent_signs(gi, gq, half)                           # 1 - 2 b_j
+    losses = _losses_at(sign, mask, factors)
     loss = losses(llr)
     if e_lambda is None:
         return loss, llr
@@ -686,8 +704,7 @@ def link_joint_host(cfg: LinkConfig, keys, ideal, est, sigma, rho, scale, branch
     m, L, d = cfg.bits_per_symbol, cfg.levels, cfg.d
     half = m // 2
     factors = _factors(factors).astype(np.float64)
-    k = np.arange(L)
-    a, label = d * (2 * k - (L - 1)), k ^ (k >> 1)
+    a = d * (2 * np.arange(L) - (L - 1))
     A = (L - 1) * d
     zero = np.zeros((G, S, T))                                                   # a batch of all-pilot grids keeps its shapes
     mu = lambda comp, p: a * (a * p[..., None] - 2.0 * comp[..., None])  # noqa: E731     [..., L]: the soft link's metric
@@ -704,24 +721,17 @@ def link_joint_host(cfg: LinkConfig, keys, ideal, est, sigma, rho, scale, branch
             f[..., ki, :] = (t_i[..., ki, None] + t_q) + r
         rows, cols = f.min(axis=-1), f.min(axis=-2)                               # over kq: the I axis's; over ki: the Q axis's
         for axis, best in enumerate((rows, cols)):
-            for j in range(half):
-                one = ((label >> (half - 1 - j)) & 1).astype(bool)
-                delta[:, e, ..., axis * half + j] = best[..., one].min(axis=-1) - best[..., ~one].min(axis=-1)
+            for j, split in enumerate(_gray_split(best, half)):
+                delta[:, e, ..., axis * half + j] = split
     mask = cfg.data_mask[None, None, :, :, None]
     delta *= mask
     llr = delta * scale[:, None, :, :, None]
     gi, gq = (np.stack([sent[0][i], sent[1][i]], axis=1) for i in (0, 1))         # [G, N, S, T]
-    sign = np.empty((G, N, S, T, m))                                              # 1 - 2 b_j
-    for j in range(half):
-        sign[..., j] = 1 - 2 * ((gi >> (half - 1 - j)) & 1)
-        sign[..., half + j] = 1 - 2 * ((gq >> (half - 1 - j)) & 1)
+    sign = _sent_signs(gi, gq, half)                                              # 1 - 2 b_j
     wrong = (((llr < 0) != (sign < 0)) & (mask != 0)).sum(axis=-1)                # the sign rule against the sent bits
     counts = np.stack([wrong.sum(axis=(2, 3)), (wrong > 0).sum(axis=(2, 3))], axis=-1).astype(np.int64)
 
-    def losses(lam):
-        z = -(sign * lam)
-        return np.stack([(np.logaddexp(0.0, fac * z) * mask).sum(axis=(2, 3, 4)) for fac in factors], axis=-1) / np.log(2.0)
-
+    losses = _losses_at(sign, mask, factors)
     out = (counts, losses(llr), llr)
     if tau is None and e_lambda is None:
         return out
@@ -870,45 +880,58 @@ class _FrameSweep:
         if ops is None:
             return None
         b, H, E, keys, (sigma, *scale) = ops       # scale: the frames' LLR scales, where the measure or the combiner needs them
-        R, N, want_llr = self.branches, self.streams, self._want == "llr"
-        G = _grouped(b, R, N)
+        G = _grouped(b, self.branches, self.streams)
+        measure = self._measure_host if self._plan is None else self._measure_device
+        return (G * self.streams, *measure(G, H, E, keys, sigma, scale))
+
+    def _measure_host(self, G, H, E, keys, sigma, scale):
+        """The float64 definitions on NumPy operands: ``(the leaders' keys, counts, loss, llr)`` as host tensors."""
+        R, N = self.branches, self.streams
         counts = loss = llr = None
         if N > 1:                                  # G N "frames": stream s of group g, with the key of frame (0, s)
-            if self._plan is None:
-                rho, lead = _weights(scale[0], R * N)
-                if self.detector == JOINT_DETECTOR:
-                    out = link_joint_host(self.cfg, keys, H, E, sigma, rho, lead, R, N, self.factors)
-                else:
-                    out = link_sm_host(self.cfg, keys, H, E, sigma, rho, lead, detector_reg(lead, self.detector), R, N, self.factors)
-                counts, loss, llr = (v.reshape(G * N, *v.shape[2:]) for v in out)
-                sent = np.ascontiguousarray(keys.reshape(G, R, N)[:, 0, :]).reshape(-1)
-                return (G * N, *(torch.from_numpy(a) for a in (sent, counts, loss, llr)))
-            s = scale[0].view(G, R * N).to(torch.float64)
-            rho = (s / s[:, :1]).to(torch.float32).reshape(-1)
-            lead = scale[0][::R * N].contiguous()
-            if self.detector == JOINT_DETECTOR:                # no regulariser
-                counts, loss, llr = self._launch(H, E, keys, sigma, rho, lead, self._factors_t, want_llr=want_llr)
-                return G * N, keys.view(G, R, N)[:, 0, :].reshape(-1), counts, loss, llr
-            reg = torch.zeros_like(lead) if self.detector == "zf" else (1.0 / lead.to(torch.float64)).to(torch.float32)
-            counts, loss, llr = self._launch(H, E, keys, sigma, rho, lead, reg, self._factors_t, want_llr=want_llr)
-            return G * N, keys.view(G, R, N)[:, 0, :].reshape(-1), counts, loss, llr
-        if self._plan is None:
+            rho, lead = _weights(scale[0], R * N)
+            if self.detector == JOINT_DETECTOR:
+                out = link_joint_host(self.cfg, keys, H, E, sigma, rho, lead, R, N, self.factors)
+            else:
+                out = link_sm_host(self.cfg, keys, H, E, sigma, rho, lead, detector_reg(lead, self.detector), R, N, self.factors)
+            counts, loss, llr = (v.reshape(G * N, *v.shape[2:]) for v in out)
+            sent = np.ascontiguousarray(keys.reshape(G, R, N)[:, 0, :]).reshape(-1)
+        else:
+            sent = keys[::R]
             if R > 1:
                 counts, loss, llr = link_mrc_host(self.cfg, keys, H, E, sigma, *_weights(scale[0], R), R, self.factors)
             elif self._want == "counts":
                 counts = link_errors_host(self.cfg, keys, H, E, sigma)
             else:
                 loss, llr = link_llrs_host(self.cfg, keys, H, E, sigma, scale[0], self.factors)
-            return (G, *(None if a is None else torch.from_numpy(a) for a in (keys[::R], counts, loss, llr)))
+        return tuple(None if a is None else torch.from_numpy(a) for a in (sent, counts, loss, llr))
+
+    @staticmethod
+    def _device_weights(scale: torch.Tensor, width: int):
+        """``_weights`` by torch ops on the device: ``(rho [b], the leaders' scale [b / width])`` of groups of ``width`` frames."""
+        s = scale.view(-1, width).to(torch.float64)
+        return (s / s[:, :1]).to(torch.float32).reshape(-1), scale[::width].contiguous()
+
+    def _measure_device(self, G, H, E, keys, sigma, scale):
+        """The plan's one launch on device operands: ``(the leaders' keys, counts, loss, llr)`` on the device."""
+        R, N, want_llr = self.branches, self.streams, self._want == "llr"
+        counts = loss = llr = None
+        if N > 1:                                  # the detectors differ in one operand: the joint one has no regulariser
+            rho, lead = self._device_weights(scale[0], R * N)
+            if self.detector == JOINT_DETECTOR:
+                reg = ()
+            else:
+                reg = (torch.zeros_like(lead) if self.detector == "zf" else (1.0 / lead.to(torch.float64)).to(torch.float32),)
+            counts, loss, llr = self._launch(H, E, keys, sigma, rho, lead, *reg, self._factors_t, want_llr=want_llr)
+            return keys.view(G, R, N)[:, 0, :].reshape(-1), counts, loss, llr
         if R > 1:
-            s = scale[0].view(G, R).to(torch.float64)
-            rho = (s / s[:, :1]).to(torch.float32).reshape(-1)
-            counts, loss, llr = self._launch(H, E, keys, sigma, rho, scale[0][::R].contiguous(), self._factors_t, want_llr=want_llr)
+            rho, lead = self._device_weights(scale[0], R)
+            counts, loss, llr = self._launch(H, E, keys, sigma, rho, lead, self._factors_t, want_llr=want_llr)
         elif self._want == "counts":
             counts = self._launch(H, E, keys, sigma)
         else:
             loss, llr = self._launch(H, E, keys, sigma, scale[0], self._factors_t, want_llr=want_llr)
-        return G, keys[::R].contiguous(), counts, loss, llr
+        return keys[::R].contiguous(), counts, loss, llr
 
     @staticmethod
     def _total(per_group: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:

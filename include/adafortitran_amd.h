@@ -579,6 +579,7 @@ int aft_link_harq_f32(const aft_link *link, const float *llr /* [batch,S,T,m] */
  *               word; Lambda_j = eff_s Delta_j with eff_s = scale / a_other (a11 for stream 0, a00 for stream 1: one correctly
  *               rounded division; 0 where a_other <= 0) and the LEADER's scale (one per group)
  * With H_r1 = E_r1 = 0 and reg scale = 1 in powers of two, stream 0's outputs are aft_link_mrc_f32's on the frames (r, 0), bit for bit.
+ * (aft_link_joint_f32 below is the same frame walk with a joint max-log demapper in the detector's place.)
  * One launch, one workgroup per group: counts int32 [groups][streams][2], loss float32 [groups][streams][n_factors] and, when llr is
  * not NULL, llr float32 [groups, streams, S, T, m] (all device memory; contiguous, so they read as groups * streams frames with the
  * keys of frames (0, s)) from ideal and est complex64 [batch, S, T] (device memory), keys uint64 [batch], sigma and rho float32
@@ -600,7 +601,8 @@ int aft_link_sm_f32(const aft_link *link, const float *ideal, const float *est, 
 /* ---- joint detection: exact max-log LLRs of both streams of that link (adafortitran_amd/linksim.py "the joint link") ----
  *
  * The layout, keys, sent words, received samples, weights and the eight sums m_0, m_1, g00, g11, g01 are aft_link_sm_f32's, formed by
- * the same operations in the same order.  There is no regulariser and no division.  For stream e with the other stream o,
+ * the same code: one frame walk serves both entry points, and only what turns an element's eight sums into LLRs and decisions
+ * differs.  There is no regulariser and no division.  For stream e with the other stream o,
  * g_oe = g01 for e = 1 and conj(g01) for e = 0, a_k the L levels and mu_k(comp, p) = a_k (a_k p - 2 comp) as aft_link_soft_f32's:
  *   candidates   x_e = a_ki + j a_kq over all M = 2^m words of stream e
  *   interference z(x_e) = m_o - g_oe x_e

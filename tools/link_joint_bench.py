@@ -2,14 +2,16 @@
 """What joint max-log detection on the two-stream link (linksim "the joint link", aft_link_joint_f32) costs on one MI355X, and what it
 measures beside the MMSE detector.
 
-    python tools/link_joint_bench.py [--out profiles/link_joint_bench.json] [--sections k,b] [--frames 128]
+    python tools/link_joint_bench.py [--out profiles/link_joint_bench.json] [--sections k,b] [--frames 128] [--base-lib PATH]
 
 Sections, each run as a child process of its own under a time limit (the parent touches no GPU and stops at the first failure):
   k   link_joint_kernel at m = 2, 4, 6 and 8 on 2 x 2 and 2 x 4, at one factor with its LLR output, as device-event time over many
       back-to-back launches, in alternating rounds with link_sm_kernel (aft_link_sm_f32, MMSE) on the SAME frames: at G = 32 groups
       (a 128-frame batch at R = 2: 32 workgroups on 256 compute units) and at G = 256 (one workgroup per compute unit).  Both read
       the same bytes, hash the same words and form the same eight sums; the joint kernel then evaluates 2 M candidates per data
-      element where the linear one runs two L-level demappers.  The same tree and the same process: a description, not a target;
+      element where the linear one runs two L-level demappers.  The same tree and the same process: a description, not a target.
+      With ``--base-lib PATH`` (another build of the library with the same ABI, loaded beside this one) every variant also runs on
+      that library in the same alternating rounds, and ``vs_base`` holds this build's median over the other's per variant;
   b   bit-error rate, achievable rate per stream (GMI, the best of the default factor grid) and LDPC block-error rate (rate 1/2) at
       16-QAM over the simulator's SNR grid at a mid delay spread and Doppler, make_pack sets of ``--frames`` frames, 2 x R with R = 2
       and 4, joint beside MMSE: perfect channel knowledge, the LMMSE estimate (on the device) and the interpolated LS estimate.
@@ -39,9 +41,11 @@ NOTE = ("device-event time per call over 100 back-to-back calls, 5 alternating r
 
 def section_k(a):
     import torch
+    from adafortitran_amd import _lib
     from adafortitran_amd.hip_ops import LinkJointPlan, LinkSmPlan
     from adafortitran_amd.linksim import LinkConfig
     one = torch.ones(1, device="cuda")
+    libs = {"": None, **({"_base": _lib.load_path(a.base_lib)} if a.base_lib else {})}      # None: this tree's library
     variants = {}
     for G in GROUP_COUNTS:
         for R in BRANCHES:
@@ -51,9 +55,16 @@ def section_k(a):
             reg = (1.0 / lead.double()).float()
             for m in KERNEL_BITS:
                 link = LinkConfig(cfg, m)
-                variants[f"joint_m{m}_r{R}_g{G}"] = lambda p=LinkJointPlan(link, "cuda", R), t=(ideal, est, keys, sigma, rho, lead): p(*t, one, want_llr=True)
-                variants[f"sm_m{m}_r{R}_g{G}"] = lambda p=LinkSmPlan(link, "cuda", R), t=(ideal, est, keys, sigma, rho, lead, reg): p(*t, one, want_llr=True)
+                for tag, lib in libs.items():
+                    variants[f"joint_m{m}_r{R}_g{G}{tag}"] = \
+                        lambda p=LinkJointPlan(link, "cuda", R), t=(ideal, est, keys, sigma, rho, lead), lib=lib: p(*t, one, want_llr=True, lib=lib)
+                    variants[f"sm_m{m}_r{R}_g{G}{tag}"] = \
+                        lambda p=LinkSmPlan(link, "cuda", R), t=(ideal, est, keys, sigma, rho, lead, reg), lib=lib: p(*t, one, want_llr=True, lib=lib)
     out = _measure(variants)
+    if a.base_lib:
+        ratios = {k: round(out[k]["median_us"] / out.pop(k + "_base")["median_us"], 4) for k in list(out) if not k.endswith("_base")}
+        out["vs_base"] = {"base_lib": os.path.basename(a.base_lib), "median_over_base_median": ratios,
+                          "largest": max(ratios.values()), "smallest": min(ratios.values())}
     data = 1680 - 24                                             # data elements of the default grid
     for G in GROUP_COUNTS:
         for R in BRANCHES:
@@ -116,6 +127,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "link_joint_bench.json"))
     ap.add_argument("--sections", default="k,b")
     ap.add_argument("--frames", type=int, default=128)
+    ap.add_argument("--base-lib", default="", help="section k: another build of the library to time every variant on as well")
     ap.add_argument("--child", default="")
     a = ap.parse_args()
     if a.frames < 1 or a.frames % (128 if a.frames > 128 else 2 * max(BRANCHES)):
@@ -131,7 +143,7 @@ def main():
     status = 0
     for name in a.sections.split(","):
         cmd = ["timeout", "-k", "10", str(LIMITS[name]), sys.executable, os.path.abspath(__file__), "--child", name,
-               "--frames", str(a.frames)]
+               "--frames", str(a.frames), "--base-lib", a.base_lib]
         res = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
         if res.returncode != 0:          # nothing more is started on the GPU after a failure
             print(f"link_joint_bench.py: section {name} ended with status {res.returncode}; stopping", file=sys.stderr)
