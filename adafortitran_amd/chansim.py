@@ -22,6 +22,34 @@ cover the circle uniformly) and ``E[H[s+d,t] conj H[s,t]] = sum_p pw_p exp(-j 2 
 Random words are counter-based on ``synth._splitmix64``: ``word(seed, g, stream, index) = sm(sm(sm(seed) ^ g) ^ (stream << 32 | index))``
 with the streams below.  The configuration the definition sees is the one the device sees: the tables are rounded to float32 ONCE
 (``ChannelSimConfig.tables``), the two spacing-times-condition products are formed in float64 and rounded to float32 once.
+
+Antenna correlation: Kronecker frame groups.  ``antennas = (R, N)`` (receive antennas by transmit streams) makes every
+``G = R N <= AFT_CHANSIM_MAX_GROUP = 16`` consecutive frames the antennas of ONE receiver: global frame ``g`` is member ``a = g % G`` of
+group ``g // G``, ``a = r N + s`` -- the frame order the links' ``branches=`` (``r``) and ``streams=`` (``r 2 + s``) already group by.
+``rx_correlation`` / ``tx_correlation`` give the R x R and N x N correlation matrices: ``None`` the identity, a real or complex scalar
+``rho``, ``|rho| < 1``, the exponential model ``C[i][j] = rho^(i-j)`` for ``i >= j`` and its conjugate above the diagonal, or a
+Hermitian positive-definite matrix with unit diagonal.  ``tables()["mix"]`` is ``L = kron(chol(C_rx), chol(C_tx))`` (lower Cholesky
+factors, so ``L`` is lower triangular in the order ``a = r N + s``), formed in float64 and rounded to complex64 ONCE; the entries above
+the diagonal are exact zeros, and with both correlations ``None`` it is the exact identity.  For frame ``g`` of a configuration with
+``G > 1``, ``lead = G (g // G)``:
+
+* conditions: the three condition indices are picked from the LEADER's key ``frame_keys(seed, lead)`` -- the members of a group share
+  SNR, delay spread and Doppler (``frame_conditions``, ``SynthLoader``'s meta and ``make_pack`` follow);
+* source gains: for ``j = 0 .. a``, ``z_j[p][t]`` is ``h_p(t)`` above (``amp_p`` included) from the angle and phase streams of the key
+  of frame ``lead + j``, at the group's Doppler;
+* mixing: ``h_a[p][t] = sum_{j <= a} L[a][j] z_j[p][t]``, in increasing ``j`` from ``+0``; on the device one complex term is two fused
+  multiply-adds per component, the form of the pilot sum: ``re = fmaf(L.re, z.re, fmaf(-L.im, z.im, re))``,
+  ``im = fmaf(L.re, z.im, fmaf(L.im, z.re, im))``;
+* everything after that is the ungrouped frame's: the delay phasors and the sum over the taps at the group's delay spread, the pilot
+  noise from frame ``g``'s OWN noise streams at the group's ``noise_sigma``;
+* the frame's key stays ``frame_keys(seed, g)``: the link draws its bits and data noise exactly as before.
+
+A frame is still a pure function of ``(seed, g)``.  The sources are independent with the statistics above, so
+``E[H_a[s,t] conj(H_b[s',t'])] = (L L^H)[a][b] r_f(s-s') r_t(t-t')`` with ``L L^H = C_rx (x) C_tx`` up to the one float32 rounding of
+``L``; the diagonal of ``L L^H`` is 1, so every frame ALONE has exactly the second-order statistics of an ungrouped frame (which is why
+``lmmse.py`` needs no change).  ``simulate_frames_host`` evaluates this in float64 on the float32-rounded ``mix`` for any vector of frame
+numbers, forming the sources it needs itself; ``aft_channel_sim_group_f32`` is the device's entry point.  With ``antennas = (1, 1)``
+(the default) nothing above applies: frames are independent draws with their own conditions, bit for bit what they were.
 """
 from __future__ import annotations
 
@@ -68,6 +96,9 @@ class ChannelSimConfig:
     snr_db: Sequence[float] = tuple(float(v) for v in _SNR_GRID)
     delay_spread_ns: Sequence[float] = tuple(float(v) for v in _DS_GRID)
     doppler_hz: Sequence[float] = tuple(float(v) for v in _DOP_GRID)
+    antennas: Tuple[int, int] = (1, 1)
+    rx_correlation: Union[None, complex, Sequence] = None
+    tx_correlation: Union[None, complex, Sequence] = None
 
     def __post_init__(self) -> None:
         S, T = (int(v) for v in self.ofdm)
@@ -106,6 +137,25 @@ class ChannelSimConfig:
             raise ValueError("delay_spread_ns and doppler_hz must not be negative")
         if not (self.subcarrier_spacing_hz > 0 and self.symbol_period_s > 0):
             raise ValueError("subcarrier_spacing_hz and symbol_period_s must be positive")
+        try:
+            R, N = (int(v) for v in self.antennas)
+        except (TypeError, ValueError):
+            raise ValueError(f"antennas = {self.antennas!r}: need (receive antennas, transmit streams)") from None
+        if R < 1 or N < 1 or R * N > _abi.AFT_CHANSIM_MAX_GROUP:
+            raise ValueError(f"antennas = ({R}, {N}): both at least 1 and at most {_abi.AFT_CHANSIM_MAX_GROUP} frames in a group")
+        set_("antennas", (R, N))
+        set_("rx_correlation", _correlation("rx_correlation", self.rx_correlation, R))
+        set_("tx_correlation", _correlation("tx_correlation", self.tx_correlation, N))
+
+    @property
+    def group(self) -> int:
+        """G = R N: the frames of one receiver."""
+        return self.antennas[0] * self.antennas[1]
+
+    def mix(self) -> np.ndarray:
+        """complex64 ``[G, G]``: ``kron(chol(C_rx), chol(C_tx))``, formed in float64 and rounded once; lower triangular."""
+        chol = lambda c, n: np.eye(n, dtype=np.complex128) if c is None else np.linalg.cholesky(_matrix(c, n))  # noqa: E731
+        return np.kron(chol(self.rx_correlation, self.antennas[0]), chol(self.tx_correlation, self.antennas[1])).astype(np.complex64)
 
     def tables(self) -> Dict[str, np.ndarray]:
         """The numbers the definition works with, rounded to float32 exactly as ``aft_chansim`` carries them."""
@@ -122,6 +172,7 @@ class ChannelSimConfig:
             # the launcher forms these two the same way: double products, one rounding
             "delay_turns": (np.float64(self.subcarrier_spacing_hz) * ds.astype(np.float64) * 1e-9).astype(np.float32),
             "doppler_turns": (dop.astype(np.float64) * np.float64(self.symbol_period_s)).astype(np.float32),
+            "mix": self.mix(),
         }
 
     def fill_grid(self, struct):
@@ -143,6 +194,46 @@ class ChannelSimConfig:
             for i, v in enumerate(t[name]):
                 arr[i] = float(v)
         return sim
+
+
+def _matrix(c, n: int) -> np.ndarray:
+    """The [n, n] correlation matrix of a validated correlation: the exponential model of a scalar, or the matrix itself."""
+    if isinstance(c, np.ndarray):
+        return c
+    i = np.arange(n)
+    d = i[:, None] - i[None, :]
+    return np.where(d >= 0, complex(c) ** np.maximum(d, 0), np.conj(complex(c)) ** np.maximum(-d, 0))
+
+
+def _correlation(name: str, given, n: int):
+    """A correlation as the config keeps it: None, a complex scalar, or a read-only complex128 [n, n] matrix; ValueError otherwise."""
+    if given is None:
+        return None
+    try:
+        c = np.asarray(given, dtype=np.complex128)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}: not a number or a matrix of numbers") from None
+    if not np.isfinite(c).all():
+        raise ValueError(f"{name} has a non-finite entry")
+    if n == 1:
+        if (c.ndim == 0 and c == 0) or (c.shape == (1, 1) and abs(c[0, 0] - 1) <= 1e-12):
+            return None                                          # the trivial correlation of one antenna
+        raise ValueError(f"{name} given for a dimension of size 1")
+    if c.ndim == 0:
+        if not abs(c) < 1:
+            raise ValueError(f"{name} = {complex(c)}: the exponential model needs |rho| < 1")
+        return complex(c)
+    if c.shape != (n, n):
+        raise ValueError(f"{name} has shape {c.shape}: need a scalar or a [{n}, {n}] matrix")
+    if np.abs(c - c.conj().T).max() > 1e-12 or np.abs(np.diag(c) - 1).max() > 1e-12:
+        raise ValueError(f"{name} must be Hermitian with a unit diagonal (to 1e-12)")
+    try:
+        np.linalg.cholesky(c)
+    except np.linalg.LinAlgError:
+        raise ValueError(f"{name} is not positive definite") from None
+    c = c.copy()
+    c.setflags(write=False)
+    return c
 
 
 # ---- the hash: written once, mirrored by csrc/frame_device.h ----------------------------------------------------------------
@@ -168,11 +259,18 @@ def _pick(keys: np.ndarray, which: int, n: int) -> np.ndarray:
 
 def frame_conditions(cfg: ChannelSimConfig, seed: int, frame_ids) -> np.ndarray:
     """float32 ``[n, 3]``: the (snr_db, delay_spread_ns, doppler_hz) of each frame -- integer arithmetic on the hash, so host and
-    device agree exactly."""
-    return _conditions(cfg.tables(), frame_keys(seed, frame_ids))[0]
+    device agree exactly.  With a grouped configuration they are the LEADER's: one pick per group."""
+    return _conditions(cfg.tables(), frame_keys(seed, _leaders(cfg, frame_ids)))[0]
+
+
+def _leaders(cfg: ChannelSimConfig, frame_ids) -> np.ndarray:
+    """The frame whose key picks each frame's conditions: the frame itself, or the first of its group."""
+    g = np.asarray(frame_ids, dtype=np.int64)
+    return g if cfg.group == 1 else g - g % cfg.group
 
 
 def _conditions(t: Dict[str, np.ndarray], keys: np.ndarray):
+    """(meta float32 [n, 3], the three index vectors) from the keys that pick the conditions: the LEADERS' with a grouped configuration."""
     idx = [_pick(keys, k, len(t[name])) for k, name in enumerate(("snr_db", "delay_spread_ns", "doppler_hz"))]
     meta = np.stack([t["snr_db"][idx[0]], t["delay_spread_ns"][idx[1]], t["doppler_hz"][idx[2]]], axis=1).astype(np.float32)
     return meta, idx
@@ -187,14 +285,27 @@ def simulate_frames_host(cfg: ChannelSimConfig, seed: int, frame_ids, return_noi
     S, T = cfg.ofdm
     Ps, Pt = cfg.pilot
     P, M = len(t["tap_delay"]), cfg.rays
-    meta, (i_snr, i_ds, i_dop) = _conditions(t, keys)
-    kk = keys[:, None, None]
-    ray = (16 * np.arange(P)[:, None] + np.arange(M)[None, :])[None]                                       # [1,P,M]
-    u = (words(kk, STREAM_ANGLE, ray) >> np.uint64(44)).astype(np.float64) * 2.0 ** -20
-    phase = (words(kk, STREAM_PHASE, ray) >> np.uint64(40)).astype(np.float64) * 2.0 ** -24                # turns
-    rate = t["doppler_turns"].astype(np.float64)[i_dop][:, None, None] * np.cos(2.0 * np.pi * (np.arange(M)[None, None, :] + u) / M)
-    turns = rate[..., None] * np.arange(T)[None, None, None, :] + phase[..., None]                         # [n,P,M,T]
-    gain = t["tap_amp"].astype(np.float64)[None, :, None] * np.exp(2j * np.pi * (turns - np.floor(turns))).sum(axis=2)   # [n,P,T]
+    G = cfg.group
+    meta, (i_snr, i_ds, i_dop) = _conditions(t, keys if G == 1 else frame_keys(seed, _leaders(cfg, frame_ids)))
+
+    def tap_gains(kk, i_dop):                                                                              # [len(kk),P,T]
+        kk = kk[:, None, None]
+        ray = (16 * np.arange(P)[:, None] + np.arange(M)[None, :])[None]                                   # [1,P,M]
+        u = (words(kk, STREAM_ANGLE, ray) >> np.uint64(44)).astype(np.float64) * 2.0 ** -20
+        phase = (words(kk, STREAM_PHASE, ray) >> np.uint64(40)).astype(np.float64) * 2.0 ** -24            # turns
+        rate = t["doppler_turns"].astype(np.float64)[i_dop][:, None, None] * np.cos(2.0 * np.pi * (np.arange(M)[None, None, :] + u) / M)
+        turns = rate[..., None] * np.arange(T)[None, None, None, :] + phase[..., None]                     # [n,P,M,T]
+        return t["tap_amp"].astype(np.float64)[None, :, None] * np.exp(2j * np.pi * (turns - np.floor(turns))).sum(axis=2)
+
+    if G == 1:
+        gain = tap_gains(keys, i_dop)
+    else:                                                        # the sources of every group that occurs, once; then row a of `mix`
+        g = np.asarray(frame_ids, dtype=np.int64)
+        lead, where = np.unique(g - g % G, return_inverse=True)
+        dop_of = np.empty(len(lead), dtype=np.int64)
+        dop_of[where] = i_dop
+        z = tap_gains(frame_keys(seed, (lead[:, None] + np.arange(G)[None, :]).ravel()), np.repeat(dop_of, G)).reshape(len(lead), G, P, T)
+        gain = np.einsum("nj,njpt->npt", t["mix"].astype(np.complex128)[g % G], z[where])
     per_sc = t["delay_turns"].astype(np.float64)[i_ds][:, None] * t["tap_delay"].astype(np.float64)[None, :]             # [n,P]
     x = per_sc[:, :, None] * np.arange(S)[None, None, :]                                                   # [n,P,S]
     phasor = np.exp(-2j * np.pi * (x - np.floor(x)))
@@ -224,6 +335,8 @@ def make_pack(cfg: ChannelSimConfig, n: int, seed: int, snr_db=None, delay_sprea
     an estimator has to beat."""
     if n < 1:
         raise ValueError(f"make_pack needs n >= 1 (got {n})")
+    if n % cfg.group:
+        raise ValueError(f"make_pack needs whole groups: n = {n} is not a multiple of the {cfg.group} frames of antennas = {cfg.antennas}")
     cfg = _pinned(cfg, snr_db, delay_spread_ns, doppler_hz)
     ideal, pilots, cond = simulate_frames_host(cfg, seed, np.arange(n))
     ideal, pilots = ideal.astype(np.complex64), pilots.astype(np.complex64)
@@ -274,7 +387,11 @@ class SynthLoader:
 
     On a HIP device a batch is one launch of ``aft_channel_sim_f32`` on the consumer's current stream plus the host's own evaluation
     of the same hash for the meta tensors: no device read, no ``.item()``, no side stream, no copy in either direction.  On
-    ``device="cpu"`` the float64 definition is evaluated and rounded to complex64."""
+    ``device="cpu"`` the float64 definition is evaluated and rounded to complex64.
+
+    With a grouped configuration (``cfg.antennas``, G frames per group) the unit of all of the above is the GROUP: ``batch_size`` and
+    ``frames_per_epoch`` must be multiples of G, the ranks share out, wrap and drop whole groups, ``epoch_frames`` returns whole groups in
+    order, and a batch is one launch of ``aft_channel_sim_group_f32``.  With G = 1 nothing changes."""
 
     def __init__(self, cfg: ChannelSimConfig, batch_size: int, frames_per_epoch: int, device: Union[str, torch.device] = "cpu",
                  seed: int = 0, rank: int = 0, world_size: int = 1, drop_last: bool = False, fresh_each_epoch: bool = True) -> None:
@@ -283,6 +400,10 @@ class SynthLoader:
         if frames_per_epoch < 1:
             raise ValueError(f"frames_per_epoch must be at least 1 (got {frames_per_epoch})")
         self.cfg, self.batch_size, self.n = cfg, int(batch_size), int(frames_per_epoch)
+        self._G = cfg.group
+        if self.batch_size % self._G or self.n % self._G:
+            raise ValueError(f"batch_size = {batch_size} and frames_per_epoch = {frames_per_epoch} must be multiples of the {self._G} "
+                             f"frames of antennas = {cfg.antennas}")
         self.device = torch.device(device)
         self.seed, self.rank, self.world_size = int(seed), int(rank), int(world_size)
         self.drop_last, self.fresh_each_epoch = bool(drop_last), bool(fresh_each_epoch)
@@ -297,38 +418,42 @@ class SynthLoader:
     def set_epoch(self, epoch: int) -> None:
         self.epoch = int(epoch)
 
-    def _samples(self) -> int:
-        return self.n // self.world_size if self.drop_last else -(-self.n // self.world_size)
+    def _samples(self) -> int:                                  # this rank's groups of an epoch (frames, with G = 1)
+        units = self.n // self._G
+        return units // self.world_size if self.drop_last else -(-units // self.world_size)
 
     def __len__(self) -> int:
-        m = self._samples()
-        return m // self.batch_size if self.drop_last else -(-m // self.batch_size)
+        m, per_batch = self._samples(), self.batch_size // self._G
+        return m // per_batch if self.drop_last else -(-m // per_batch)
 
     def epoch_frames(self, epoch: int) -> np.ndarray:
-        """The global frame numbers this rank visits in ``epoch``, in order (int64)."""
-        count = len(self) * self.batch_size if self.drop_last else self._samples()
-        base = epoch * self.n if self.fresh_each_epoch else 0
-        return base + (self.rank + self.world_size * np.arange(count, dtype=np.int64)) % self.n
+        """The global frame numbers this rank visits in ``epoch``, in order (int64): whole groups with a grouped configuration."""
+        G, units = self._G, self.n // self._G
+        count = len(self) * (self.batch_size // G) if self.drop_last else self._samples()
+        base = epoch * units if self.fresh_each_epoch else 0
+        group = base + (self.rank + self.world_size * np.arange(count, dtype=np.int64)) % units
+        return group if G == 1 else (group[:, None] * G + np.arange(G, dtype=np.int64)[None, :]).ravel()
 
     def __iter__(self) -> Iterator[Tuple[torch.Tensor, torch.Tensor, tuple]]:
         epoch, self.epoch = self.epoch, self.epoch + 1
         return self._batches(epoch)
 
     def _meta(self, frames: np.ndarray) -> tuple:
-        cond = _conditions(self._tables, frame_keys(self.seed, frames))[0]
+        cond = _conditions(self._tables, frame_keys(self.seed, _leaders(self.cfg, frames)))[0]
         m = torch.from_numpy(np.concatenate([frames.astype(np.float32)[:, None], cond, np.zeros((len(frames), 1), np.float32)], axis=1))
         return (m[:, 0:1], m[:, 1:2], m[:, 2:3], m[:, 3:4], m[:, 4:5], [tuple(CHANNEL_TYPE for _ in frames)])
 
     def _batches(self, epoch: int):
         frames = self.epoch_frames(epoch)
-        base = epoch * self.n if self.fresh_each_epoch else 0
+        G, units = self._G, self.n // self._G                    # the launch counts groups: positions, base and modulo in groups
+        base = epoch * units if self.fresh_each_epoch else 0
         for lo in range(0, len(frames), self.batch_size):
             part = frames[lo:lo + self.batch_size]
             if self._plan is None:
                 ideal, pilots, _ = simulate_frames_host(self.cfg, self.seed, part)
                 yield torch.from_numpy(pilots.astype(np.complex64)), torch.from_numpy(ideal.astype(np.complex64)), self._meta(part)
                 continue
-            args = (self.seed, base, self.rank + self.world_size * lo, self.world_size, self.n, len(part))
+            args = (self.seed, base, self.rank + self.world_size * (lo // G), self.world_size, units, len(part))
             if torch.cuda.current_device() != self.device.index:    # the launch belongs to the loader's device, whichever is current
                 with torch.cuda.device(self.device):
                     ideal, pilots, _ = self._plan(*args)

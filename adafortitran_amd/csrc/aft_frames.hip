@@ -189,29 +189,55 @@ bool ldpc_code_ok(const char *who, int base_rows, int base_cols, const int32_t *
     return true;
 }
 
+// What both simulator entry points ask: the pointers, the batch, the group rx x tx (the ungrouped entry point passes 1 x 1 and no
+// mix), the frame (group) numbers -- every FRAME number stays below 2^63 --, the struct, and a finite mix; 0 = fine
+int check_chansim(const char *who, const aft_chansim *sim, const float *mix, int rx, int tx, long long base, long long start,
+                  long long stride, long long modulo, int batch, const float *ideal, const float *pilots, const float *meta) {
+    AFT_REQUIRE(sim && ideal && pilots && meta, "%s: NULL pointer argument", who);
+    AFT_REQUIRE(aligned(8, ideal, pilots), "%s: ideal and pilots must be 8-byte aligned", who);
+    AFT_REQUIRE(aligned(4, meta, mix), "%s: %s must be 4-byte aligned", who, mix ? "meta and mix" : "meta");
+    AFT_REQUIRE(batch >= 1, "%s: batch must be at least 1 (got %d)", who, batch);
+    if (!within(who, "rx", rx, 1, AFT_CHANSIM_MAX_GROUP) || !within(who, "tx", tx, 1, AFT_CHANSIM_MAX_GROUP) ||
+        !within(who, "rx * tx", rx * tx, 1, AFT_CHANSIM_MAX_GROUP))
+        return AFT_ERR_SHAPE;
+    const int group = rx * tx;
+    AFT_REQUIRE(batch % group == 0, "%s: batch = %d is not a multiple of rx * tx = %d * %d", who, batch, rx, tx);
+    const long long far = (1LL << 62) / group;
+    AFT_REQUIRE(base >= 0 && start >= 0 && stride >= 1 && modulo >= 1 && base < far && modulo < far && start < far &&
+                    stride <= (far - start) / (batch / group),
+                "%s: bad frame numbers (base %lld, start %lld, stride %lld, modulo %lld: base, start >= 0, stride, modulo >= 1, "
+                "all frame numbers below 2^62)", who, base, start, stride, modulo);
+    if (!grid_ok(who, *sim, 1 << 20) || !within(who, "taps", sim->taps, 1, AFT_CHANSIM_MAX_TAPS) ||
+        !within(who, "rays", sim->rays, 1, AFT_CHANSIM_MAX_RAYS) || !within(who, "n_snr", sim->n_snr, 1, AFT_CHANSIM_MAX_VALUES) ||
+        !within(who, "n_ds", sim->n_ds, 1, AFT_CHANSIM_MAX_VALUES) || !within(who, "n_dop", sim->n_dop, 1, AFT_CHANSIM_MAX_VALUES) ||
+        !pilot_index_ok(who, *sim, false))
+        return AFT_ERR_SHAPE;
+    for (int i = 0; mix && i < group * (group + 1); ++i)
+        AFT_REQUIRE(std::isfinite(mix[i]), "%s: mix[%d] = %g is not finite", who, i, (double)mix[i]);
+    return AFT_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 int aft_channel_sim_f32(const aft_chansim *sim, unsigned long long seed, long long base, long long start, long long stride,
                         long long modulo, int batch, float *ideal, float *pilots, float *meta, void *stream) {
-    const char *who = "channel sim";
-    AFT_REQUIRE(sim && ideal && pilots && meta, "channel sim: NULL pointer argument");
-    AFT_REQUIRE(aligned(8, ideal, pilots), "channel sim: ideal and pilots must be 8-byte aligned");
-    AFT_REQUIRE(aligned(4, meta), "channel sim: meta must be 4-byte aligned");
-    AFT_REQUIRE(batch >= 1, "channel sim: batch must be at least 1 (got %d)", batch);
-    const long long far = 1LL << 62;
-    AFT_REQUIRE(base >= 0 && start >= 0 && stride >= 1 && modulo >= 1 && base < far && modulo < far && start < far &&
-                    stride <= (far - start) / batch,
-                "channel sim: bad frame numbers (base %lld, start %lld, stride %lld, modulo %lld: base, start >= 0, stride, modulo >= 1, "
-                "all frame numbers below 2^62)", base, start, stride, modulo);
-    if (!grid_ok(who, *sim, 1 << 20) || !within(who, "taps", sim->taps, 1, AFT_CHANSIM_MAX_TAPS) ||
-        !within(who, "rays", sim->rays, 1, AFT_CHANSIM_MAX_RAYS) || !within(who, "n_snr", sim->n_snr, 1, AFT_CHANSIM_MAX_VALUES) ||
-        !within(who, "n_ds", sim->n_ds, 1, AFT_CHANSIM_MAX_VALUES) || !within(who, "n_dop", sim->n_dop, 1, AFT_CHANSIM_MAX_VALUES) ||
-        !pilot_index_ok(who, *sim, false))
-        return AFT_ERR_SHAPE;
+    const int rc = check_chansim("channel sim", sim, nullptr, 1, 1, base, start, stride, modulo, batch, ideal, pilots, meta);
+    if (rc != AFT_OK) return rc;
     hipError_t e = launch_channel_sim(*sim, seed, base, start, stride, modulo, batch, ideal, pilots, meta, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? AFT_OK : hip_fail("channel_sim", e);
+}
+
+int aft_channel_sim_group_f32(const aft_chansim *sim, int rx, int tx, const float *mix, unsigned long long seed, long long base,
+                              long long start, long long stride, long long modulo, int batch, float *ideal, float *pilots,
+                              float *meta, void *stream) {
+    AFT_REQUIRE(mix, "channel sim group: NULL pointer argument");
+    const int rc = check_chansim("channel sim group", sim, mix, rx, tx, base, start, stride, modulo, batch, ideal, pilots, meta);
+    if (rc != AFT_OK) return rc;
+    hipError_t e = launch_channel_sim_group(*sim, rx * tx, mix, seed, base, start, stride, modulo, batch, ideal, pilots, meta,
+                                            static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? AFT_OK : hip_fail("channel_sim_group", e);
 }
 
 size_t aft_lmmse_table_floats(const aft_lmmse *plan) {

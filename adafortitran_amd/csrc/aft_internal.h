@@ -365,6 +365,11 @@ hipError_t launch_frame_gather(const float *ideal_all, const float *pilots_all, 
 // the channel simulator (k_chansim.hip): `sim` has passed aft_channel_sim_f32's checks
 hipError_t launch_channel_sim(const aft_chansim &sim, unsigned long long seed, long long base, long long start, long long stride,
                               long long modulo, int batch, float *ideal, float *pilots, float *meta, hipStream_t st);
+// ... its grouped instantiation: `group` = rx * tx frames per group, `mix_packed` (host) the packed lower triangle of the mixing matrix;
+// base, start, stride and modulo count groups, batch is a multiple of `group`
+hipError_t launch_channel_sim_group(const aft_chansim &sim, int group, const float *mix_packed, unsigned long long seed, long long base,
+                                    long long start, long long stride, long long modulo, int batch, float *ideal, float *pilots,
+                                    float *meta, hipStream_t st);
 
 // the LMMSE baseline estimator (k_lmmse.hip): `plan` has passed aft_lmmse_f32's checks; the two sizes are the per-delay-spread and
 // per-Doppler blocks of the table image (include/adafortitran_amd.h)

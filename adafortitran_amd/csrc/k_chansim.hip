@@ -16,6 +16,14 @@
 // Phases are formed in TURNS and reduced with x - floor(x) (exact in floating point) before sincospi, so the evaluation error of the
 // sine does not grow with the argument; what does grow is the rounding of the turn count itself (2^-24 relative), which is what the
 // bound of tests/test_chansim_gpu.py is made of.  No atomics, no reads of device buffers (lane-indexed table entries are read from the kernel-argument segment), every output element written exactly once.
+//
+// The grouped instantiation (aft_channel_sim_group_f32; chansim.py "antenna correlation"): still one workgroup per output frame, member
+// a of a group of G = rx * tx frames.  The conditions are hashed from the LEADER's key; the gain pass of a tile (pilot-symbol gains
+// included) runs once per source j = 0 .. a -- a wave-uniform loop that stops at a, `mix` being lower triangular --: the ray table of
+// frame lead + j is re-staged into the one `ray` array, and a thread adds L[a][j] z_j to the SAME (p, t) items it owns in every pass, so
+// the accumulation in `gain` / `pgain` needs no atomics and no barrier of its own (two barriers per source fence the ray table).  The
+// main pass and the pilots' noise (the frame's OWN key) are the ungrouped kernel's.  L[a][j] comes from the kernel-argument segment by a
+// wave-uniform index.  LDS is 12 KB in both instantiations -- ray 4 KB, gain 4 KB, pgain 4 KB -- whatever T and G are.
 #include "frame_device.h"
 
 namespace aft {
@@ -30,7 +38,18 @@ struct ChanSimArgs {
     float2 *ideal, *pilots;
     float *meta;
     int wide;                                      // 1: 16-byte stores into ideal
+    static constexpr bool kGrouped = false;
 };
+
+// The grouped launch: the ungrouped arguments (base, start, stride and modulo count GROUPS here) and the packed lower triangle of `mix`,
+// row a at a (a + 1) / 2: 136 complex values for the largest group
+constexpr int kMixPacked = AFT_CHANSIM_MAX_GROUP * (AFT_CHANSIM_MAX_GROUP + 1) / 2;
+struct ChanSimGroupArgs : ChanSimArgs {
+    int group;                                     // G = rx * tx
+    float2 mix[kMixPacked];
+    static constexpr bool kGrouped = true;
+};
+static_assert(sizeof(ChanSimGroupArgs) <= 4096, "kernel arguments travel by value: HIP's limit is 4 KB");
 
 __device__ __forceinline__ int sim_pick(unsigned long long kf, unsigned which, int n) {
     return (int)(((unsigned)(frame_word(kf, kStreamCondition, which) >> 40) * (unsigned)n) >> 24);    // 24-bit word x n <= 16: fits 32 bits
@@ -55,21 +74,8 @@ __device__ __forceinline__ float2 delay_phasor(const aft_chansim &c, float tau, 
     return make_float2(z.x, -z.y);
 }
 
-__global__ __launch_bounds__(kFrameThreads) void channel_sim_kernel(const ChanSimArgs a) {
-    __shared__ float2 ray[AFT_CHANSIM_MAX_TAPS * AFT_CHANSIM_MAX_RAYS];
-    __shared__ float2 gain[AFT_CHANSIM_MAX_TAPS][kFrameTile];
-    __shared__ float2 pgain[AFT_CHANSIM_MAX_TAPS][AFT_CHANSIM_MAX_PILOT_SYMBOLS];
-    const aft_chansim &c = a.c;
-    const int tid = threadIdx.x;
-    const size_t b = blockIdx.x;
-    const int S = c.num_scs, T = c.num_symbols, P = c.taps, M = c.rays, Ps = c.pilot_scs, Pt = c.pilot_symbols;
-    const unsigned long long g = a.base + (a.start + b * a.stride) % a.modulo;
-    const unsigned long long kf = splitmix64(a.seed_key ^ g);
-    const int i_snr = sim_pick(kf, 0, c.n_snr), i_ds = sim_pick(kf, 1, c.n_ds), i_dop = sim_pick(kf, 2, c.n_dop);
-    AFT_DEV_ASSERT(i_snr < c.n_snr && i_ds < c.n_ds && i_dop < c.n_dop);
-    if (tid < 3) a.meta[3 * b + tid] = tid == 0 ? c.snr_db[i_snr] : tid == 1 ? c.delay_spread_ns[i_ds] : c.doppler_hz[i_dop];
-    const float dop = a.doppler_turns[i_dop], tau = a.delay_turns[i_ds], sigma = c.noise_sigma[i_snr];
-
+// the frame's ray table: (turns per symbol, phase in turns) per (tap, ray), from the angle and phase streams of key `kf`
+__device__ __forceinline__ void stage_rays(float2 *ray, unsigned long long kf, float dop, int P, int M, int tid) {
     for (int i = tid; i < P * M; i += kFrameThreads) {
         const int p = i / M, m = i - p * M;
         const unsigned idx = 16u * p + m;
@@ -78,19 +84,83 @@ __global__ __launch_bounds__(kFrameThreads) void channel_sim_kernel(const ChanSi
         const float phase = (float)(unsigned)(frame_word(kf, kStreamRayPhase, idx) >> 40) * 0x1p-24f;
         ray[i] = make_float2(dop * cospif(2.f * turn), phase);
     }
-    __syncthreads();
+}
+
+template <class Args>
+__global__ __launch_bounds__(kFrameThreads) void channel_sim_kernel(const Args a) {
+    constexpr bool kGrouped = Args::kGrouped;
+    __shared__ float2 ray[AFT_CHANSIM_MAX_TAPS * AFT_CHANSIM_MAX_RAYS];
+    __shared__ float2 gain[AFT_CHANSIM_MAX_TAPS][kFrameTile];
+    __shared__ float2 pgain[AFT_CHANSIM_MAX_TAPS][AFT_CHANSIM_MAX_PILOT_SYMBOLS];
+    const aft_chansim &c = a.c;
+    const int tid = threadIdx.x;
+    const size_t b = blockIdx.x;
+    const int S = c.num_scs, T = c.num_symbols, P = c.taps, M = c.rays, Ps = c.pilot_scs, Pt = c.pilot_symbols;
+    // ungrouped: g the frame, kc = kf its key.  Grouped: output frame b is member `member` of group base + (start + (b / G) stride) %
+    // modulo; kc, the LEADER's key, picks the conditions and kf, the frame's own, draws the pilots' noise
+    unsigned long long g, lead = 0;
+    int member = 0;
+    if constexpr (kGrouped) {
+        member = (int)(b % (size_t)a.group);
+        lead = (a.base + (a.start + (b / (size_t)a.group) * a.stride) % a.modulo) * (unsigned long long)a.group;
+        g = lead + (unsigned long long)member;
+    } else {
+        g = a.base + (a.start + b * a.stride) % a.modulo;
+    }
+    const unsigned long long kf = splitmix64(a.seed_key ^ g);
+    const unsigned long long kc = kGrouped ? splitmix64(a.seed_key ^ lead) : kf;
+    const int i_snr = sim_pick(kc, 0, c.n_snr), i_ds = sim_pick(kc, 1, c.n_ds), i_dop = sim_pick(kc, 2, c.n_dop);
+    AFT_DEV_ASSERT(i_snr < c.n_snr && i_ds < c.n_ds && i_dop < c.n_dop);
+    if (tid < 3) a.meta[3 * b + tid] = tid == 0 ? c.snr_db[i_snr] : tid == 1 ? c.delay_spread_ns[i_ds] : c.doppler_hz[i_dop];
+    const float dop = a.doppler_turns[i_dop], tau = a.delay_turns[i_ds], sigma = c.noise_sigma[i_snr];
+
+    if constexpr (!kGrouped) {                                  // written out, not stage_rays(): the ungrouped instruction stream stays as it was
+        for (int i = tid; i < P * M; i += kFrameThreads) {
+            const int p = i / M, m = i - p * M;
+            const unsigned idx = 16u * p + m;
+            const float u = (float)(unsigned)(frame_word(kf, kStreamRayAngle, idx) >> 44) * 0x1p-20f;    // m + u is exact: 4 + 20 bits
+            const float turn = ((float)m + u) / (float)M;
+            const float phase = (float)(unsigned)(frame_word(kf, kStreamRayPhase, idx) >> 40) * 0x1p-24f;
+            ray[i] = make_float2(dop * cospif(2.f * turn), phase);
+        }
+        __syncthreads();
+    }
 
     for (int t0 = 0; t0 < T; t0 += kFrameTile) {
         const bool first = t0 == 0;
-        if (!first) __syncthreads();                                    // the previous tile's readers are done with `gain`
-        for (int i = tid; i < P * kFrameTile + (first ? P * Pt : 0); i += kFrameThreads) {
-            if (i < P * kFrameTile) {
-                const int p = i / kFrameTile, tt = i - p * kFrameTile;
-                gain[p][tt] = t0 + tt < T ? tap_gain(c, ray, p, t0 + tt) : make_float2(0.f, 0.f);
-            } else {
-                const int q = i - P * kFrameTile, p = q / Pt, j = q - p * Pt;
-                AFT_DEV_ASSERT(p < P && c.pilot_symbol_index[j] >= 0 && c.pilot_symbol_index[j] < T);
-                pgain[p][j] = tap_gain(c, ray, p, c.pilot_symbol_index[j]);
+        if constexpr (kGrouped) {
+            AFT_DEV_ASSERT(member < a.group && a.group <= AFT_CHANSIM_MAX_GROUP);
+            for (int j = 0; j <= member; ++j) {
+                if (!first || j > 0) __syncthreads();                   // the readers of `ray` (and the previous tile's of `gain`) are done
+                stage_rays(ray, splitmix64(a.seed_key ^ (lead + (unsigned long long)j)), dop, P, M, tid);
+                __syncthreads();
+                const float2 l = a.mix[member * (member + 1) / 2 + j];
+                for (int i = tid; i < P * kFrameTile + (first ? P * Pt : 0); i += kFrameThreads) {    // item i has one owner in every pass
+                    if (i < P * kFrameTile) {
+                        const int p = i / kFrameTile, tt = i - p * kFrameTile;
+                        float2 h = j == 0 ? make_float2(0.f, 0.f) : gain[p][tt];
+                        cfma(h, l, t0 + tt < T ? tap_gain(c, ray, p, t0 + tt) : make_float2(0.f, 0.f));
+                        gain[p][tt] = h;
+                    } else {
+                        const int q = i - P * kFrameTile, p = q / Pt, k = q - p * Pt;
+                        AFT_DEV_ASSERT(p < P && c.pilot_symbol_index[k] >= 0 && c.pilot_symbol_index[k] < T);
+                        float2 h = j == 0 ? make_float2(0.f, 0.f) : pgain[p][k];
+                        cfma(h, l, tap_gain(c, ray, p, c.pilot_symbol_index[k]));
+                        pgain[p][k] = h;
+                    }
+                }
+            }
+        } else {
+            if (!first) __syncthreads();                                // the previous tile's readers are done with `gain`
+            for (int i = tid; i < P * kFrameTile + (first ? P * Pt : 0); i += kFrameThreads) {
+                if (i < P * kFrameTile) {
+                    const int p = i / kFrameTile, tt = i - p * kFrameTile;
+                    gain[p][tt] = t0 + tt < T ? tap_gain(c, ray, p, t0 + tt) : make_float2(0.f, 0.f);
+                } else {
+                    const int q = i - P * kFrameTile, p = q / Pt, j = q - p * Pt;
+                    AFT_DEV_ASSERT(p < P && c.pilot_symbol_index[j] >= 0 && c.pilot_symbol_index[j] < T);
+                    pgain[p][j] = tap_gain(c, ray, p, c.pilot_symbol_index[j]);
+                }
             }
         }
         __syncthreads();
@@ -128,9 +198,10 @@ __global__ __launch_bounds__(kFrameThreads) void channel_sim_kernel(const ChanSi
 
 }  // namespace
 
-hipError_t launch_channel_sim(const aft_chansim &sim, unsigned long long seed, long long base, long long start, long long stride,
-                              long long modulo, int batch, float *ideal, float *pilots, float *meta, hipStream_t st) {
-    ChanSimArgs a{};
+namespace {
+
+void fill_args(ChanSimArgs &a, const aft_chansim &sim, unsigned long long seed, long long base, long long start, long long stride,
+               long long modulo, float *ideal, float *pilots, float *meta) {
     a.c = sim;
     for (int i = 0; i < AFT_CHANSIM_MAX_VALUES; ++i) {
         a.delay_turns[i] = i < sim.n_ds ? (float)(sim.subcarrier_spacing_hz * (double)sim.delay_spread_ns[i] * 1e-9) : 0.f;
@@ -141,7 +212,26 @@ hipError_t launch_channel_sim(const aft_chansim &sim, unsigned long long seed, l
     a.stride = (unsigned long long)stride; a.modulo = (unsigned long long)modulo;
     a.ideal = reinterpret_cast<float2 *>(ideal); a.pilots = reinterpret_cast<float2 *>(pilots); a.meta = meta;
     a.wide = wide_ok(sim.num_symbols, ideal);
-    hipLaunchKernelGGL(channel_sim_kernel, dim3((unsigned)batch), dim3(kFrameThreads), 0, st, a);
+}
+
+}  // namespace
+
+hipError_t launch_channel_sim(const aft_chansim &sim, unsigned long long seed, long long base, long long start, long long stride,
+                              long long modulo, int batch, float *ideal, float *pilots, float *meta, hipStream_t st) {
+    ChanSimArgs a{};
+    fill_args(a, sim, seed, base, start, stride, modulo, ideal, pilots, meta);
+    hipLaunchKernelGGL(channel_sim_kernel<ChanSimArgs>, dim3((unsigned)batch), dim3(kFrameThreads), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_channel_sim_group(const aft_chansim &sim, int group, const float *mix_packed, unsigned long long seed, long long base,
+                                    long long start, long long stride, long long modulo, int batch, float *ideal, float *pilots,
+                                    float *meta, hipStream_t st) {
+    ChanSimGroupArgs a{};
+    fill_args(a, sim, seed, base, start, stride, modulo, ideal, pilots, meta);
+    a.group = group;
+    for (int i = 0; i < group * (group + 1) / 2; ++i) a.mix[i] = make_float2(mix_packed[2 * i], mix_packed[2 * i + 1]);
+    hipLaunchKernelGGL(channel_sim_kernel<ChanSimGroupArgs>, dim3((unsigned)batch), dim3(kFrameThreads), 0, st, a);
     return hipGetLastError();
 }
 

@@ -426,6 +426,9 @@ class ChannelSimPlan:
     ``plan(seed, base, start, stride, modulo, batch)`` -> ``(ideal complex64 [batch,S,T], pilots complex64 [batch,Ps,Pt], meta float32
     [batch,3])`` on the plan's device: three ``torch.empty``, one ``ctypes`` call, one launch (``aft_channel_sim_f32``) on the current
     stream of that device, no upload and no synchronisation.  Output frame b is global frame ``base + (start + b * stride) % modulo``.
+    With a grouped configuration (``cfg.antennas``, G = R N frames per group) the launch is ``aft_channel_sim_group_f32``, the four
+    position arguments count GROUPS -- output frame b is member ``b % G`` of group ``base + (start + (b // G) * stride) % modulo`` --
+    and ``batch``, still in frames, is a multiple of G; the packed ``mix`` is host memory the plan keeps.
     The plan trusts its caller in one thing only: its device is the current one."""
 
     def __init__(self, cfg, device: torch.device) -> None:
@@ -433,6 +436,8 @@ class ChannelSimPlan:
         self.cfg = cfg
         self.sim = cfg.to_struct()                              # validated by the config itself; the entry point checks again
         self.grid, self.pilot = tuple(cfg.ofdm), tuple(cfg.pilot)
+        self.antennas, self.group = tuple(cfg.antennas), cfg.group
+        self.mix = pack_mix(cfg.mix()) if self.group > 1 else None
 
     def __call__(self, seed: int, base: int, start: int, stride: int, modulo: int, batch: int, lib=None):
         lib = lib or _lib.load()
@@ -440,9 +445,22 @@ class ChannelSimPlan:
         ideal = torch.empty((batch, *self.grid), dtype=torch.complex64, device=dev)      # the kernel writes every element
         pilots = torch.empty((batch, *self.pilot), dtype=torch.complex64, device=dev)
         meta = torch.empty((batch, 3), dtype=torch.float32, device=dev)
+        if self.group > 1:
+            _lib.check(lib.aft_channel_sim_group_f32(self.sim, *self.antennas, self.mix.ctypes.data, seed & 0xFFFFFFFFFFFFFFFF, base, start,
+                                                     stride, modulo, batch, ideal.data_ptr(), pilots.data_ptr(), meta.data_ptr(),
+                                                     _lib.current_stream_ptr(dev)), lib)
+            return ideal, pilots, meta
         _lib.check(lib.aft_channel_sim_f32(self.sim, seed & 0xFFFFFFFFFFFFFFFF, base, start, stride, modulo, batch, ideal.data_ptr(),
                                            pilots.data_ptr(), meta.data_ptr(), _lib.current_stream_ptr(dev)), lib)
         return ideal, pilots, meta
+
+
+def pack_mix(mix) -> np.ndarray:
+    """The lower triangle of a complex ``[G, G]`` mixing matrix as ``aft_channel_sim_group_f32`` reads it: float32, row a's
+    ``L[a][0 .. a]`` as (re, im) pairs at float offset ``a (a + 1)``."""
+    m = np.asarray(mix, dtype=np.complex64)
+    rows, cols = np.tril_indices(m.shape[0])                    # row-major over the lower triangle
+    return np.ascontiguousarray(m[rows, cols]).view(np.float32)
 
 
 class LmmsePlan:

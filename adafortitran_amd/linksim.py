@@ -80,8 +80,12 @@ LEADER's scale (one float32 per group) and the losses at the K factors are the s
 ``p``, per group: counts ``[G, 2]``, loss ``[G, K]``, llr ``[G, S, T, m]``.  With ``R = 1`` every output is the single-branch one.  The
 margin and the LLR reach use ``reach = sum_r rho_r (|H_r||x| + |noise_r|) |E_r|``; flags, ``q`` and the loss interval are otherwise
 unchanged.  The coded links are unchanged downstream: the decoders read this LLR tensor with the leaders' keys (scrambler stream 5,
-information bits stream 8) and ``batch = G``.  What this models: R uncorrelated antennas, each estimated on its own.  It does not
-model antenna correlation, and it gives no array gain in the estimator itself (no estimator here sees more than one antenna's pilots).
+information bits stream 8) and ``batch = G``.  What this models: R antennas, each estimated on its own.  Antenna correlation is not
+this kernel's to model -- the estimators are per antenna, so a correlated channel has to be the channel the pilots saw --: it comes
+from the simulator, ``ChannelSimConfig(antennas=(R, 1), rx_correlation=...)`` (chansim.py, "Kronecker frame groups"), whose groups are
+these R frames and share one SNR, delay spread and Doppler.  With an ungrouped configuration the R frames are independent draws -- the
+best case for the combiner -- each with its own conditions unless the caller pins them.  The link gives no array gain in the
+estimator itself (no estimator here sees more than one antenna's pilots).
 
 The spatial-multiplexing link.  The receivers that have the antennas ``branches=`` models do not only combine: they separate two
 spatial streams, and there an error in the estimate leaks one stream into the other, amplified by the conditioning of the channel.
@@ -115,9 +119,12 @@ The cancellation in ``p_s`` is inherent to separating two streams in float32 -- 
 ``P_s`` -- which is why the reaches are sums of absolute values and why the share of flagged decisions is larger than on the one-stream
 links (tests/test_linksm.py holds the cap).  With an unheard second stream (``H_r1 = E_r1 = 0``) and ``reg scale = 1`` in powers of two,
 stream 0 is the diversity link on the frames ``(r, 0)``.  Every rate of this link is per stream and symbol: the spectral efficiency is
-N times it.  What this models: uncorrelated antennas, per-pair estimates, linear detection (zero forcing or MMSE; joint max-log
-detection is the next section).  It does not model antenna correlation, sphere or list detection, successive cancellation, precoding,
-or ``N > 2``.
+N times it.  What this models: per-pair estimates and linear detection (zero forcing or MMSE; joint max-log detection is the next
+section).  Antenna correlation, which decides how well two streams separate at all, comes from the simulator:
+``ChannelSimConfig(antennas=(R, 2), rx_correlation=..., tx_correlation=...)`` makes these ``2 R`` frames one correlated group with
+shared conditions (chansim.py, "Kronecker frame groups"); with an ungrouped configuration the pairs are independent draws with their
+own conditions unless the caller pins them.  It does not model sphere or list detection, successive cancellation, precoding, or
+``N > 2``.
 
 The joint link.  A linear detector on a 2 x 2 Rayleigh channel has diversity order 1; a receiver that ships two-stream reception runs a
 max-log joint demapper and gets order 2, and behind it an estimation error no longer leaks through an ill-conditioned inverse: it
@@ -151,8 +158,9 @@ together ``2 A^2 g_oo + 2 sqrt(2) A |z|``, and ``|z| <= reach(m_o) + sqrt(2) A G
 flagged bit moves a row's bit count by at most 1 and an (element, stream) with any flagged bit its symbol count by at most 1.  The
 loss interval is the soft link's, at ``Lambda -+ e_lambda q``.  With an unheard second stream (``H_r1 = E_r1 = 0``) stream 1's ``Delta``
 is exactly 0 and stream 0's LLRs are the diversity link's on the frames ``(r, 0)``.  What this models beyond the linear detectors: the
-joint max-log demapper.  It does not model sphere or list detection (nothing is pruned: every candidate is evaluated), successive
-cancellation, iterative detection and decoding, antenna correlation, or ``N > 2``.
+joint max-log demapper.  Antenna correlation comes from the simulator's grouped configurations, as for the linear detectors.  It does
+not model sphere or list detection (nothing is pruned: every candidate is evaluated), successive cancellation, iterative detection
+and decoding, or ``N > 2``.
 
 The coded link.  The rate says how much information the LLRs carry; a link-level user wants the same with a decoder in the loop: the
 block-error rate of coded blocks and the throughput that follows from it.  ``CodeConfig``, ``link_encode_host`` / ``link_decode_host``

@@ -304,6 +304,27 @@ typedef struct aft_chansim {
 int aft_channel_sim_f32(const aft_chansim *sim, unsigned long long seed, long long base, long long start, long long stride,
                         long long modulo, int batch, float *ideal, float *pilots, float *meta, void *stream);
 
+/* Antenna correlation (chansim.py "antenna correlation: Kronecker frame groups"): G = rx * tx consecutive frames are the antennas of
+ * one receiver, member a = r tx + s of group g / G.  `mix` is the lower-triangular complex G x G matrix L = chol(C_rx) (x) chol(C_tx),
+ * host memory, PACKED by rows: row a holds L[a][0 .. a] as (re, im) pairs at float offset a (a + 1), G (G + 1) floats in all.  For
+ * frame g with lead = G (g / G):
+ *   the three conditions are picked from the LEADER's key kf(lead): a group shares snr, delay spread and doppler;
+ *   z_j[p][t], j = 0 .. a, is h_p(t) above from the ray streams of kf(lead + j) at the group's doppler;
+ *   h_a[p][t] = sum_{j <= a} L[a][j] z_j[p][t], in increasing j from +0, one term being two fused multiply-adds per component:
+ *     re = fma(L.re, z.re, fma(-L.im, z.im, re)),  im = fma(L.re, z.im, fma(L.im, z.re, im));
+ *   H and the pilots follow as above from h_a, the group's delay spread and noise_sigma, and frame g's OWN noise streams.
+ * base, start, stride and modulo count GROUPS: output frame b is member b mod G of group base + ((start + (b / G) stride) mod modulo);
+ * batch counts frames.  Everything else is aft_channel_sim_f32's: the outputs, the store forms, one workgroup per frame, one launch,
+ * no atomics, nothing synchronised; `sim` and `mix` are read during the call only.  With rx = tx = 1 the frames are
+ * aft_channel_sim_f32's scaled by mix[0] (one frame per group).
+ * Nothing is launched on AFT_ERR_ARG (aft_channel_sim_f32's, where the bound on frame numbers is 2^62 / G for groups; a NULL or
+ * 4-byte-misaligned mix; a non-finite entry of mix; batch not a multiple of G) and AFT_ERR_SHAPE (aft_channel_sim_f32's; rx or tx
+ * below 1 or rx * tx above AFT_CHANSIM_MAX_GROUP). */
+#define AFT_CHANSIM_MAX_GROUP 16   /* the link's 8 branches x 2 streams */
+int aft_channel_sim_group_f32(const aft_chansim *sim, int rx, int tx, const float *mix, unsigned long long seed, long long base,
+                              long long start, long long stride, long long modulo, int batch, float *ideal, float *pilots,
+                              float *meta, void *stream);
+
 /* ---- the LMMSE (Wiener) baseline estimator (adafortitran_amd/lmmse.py holds the definition) ----
  *
  * The best linear estimator of the simulator's channel from its pilots, for the second-order statistics the simulator is defined
