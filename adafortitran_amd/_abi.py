@@ -64,6 +64,7 @@ AFT_LINK_CODE_MAX_INFO_BITS = 4090
 AFT_LINK_LDPC_Z, AFT_LINK_LDPC_MAX_EDGES = 64, 160
 AFT_LINK_MAX_BRANCHES = 8
 AFT_LINK_MAX_STREAMS = 2
+AFT_LINK_PAIR_TIME, AFT_LINK_PAIR_FREQUENCY = 0, 1
 AFT_LINK_HARQ_MAX_ROUNDS, AFT_LINK_HARQ_COUNTS = 4, 7
 
 
@@ -228,6 +229,7 @@ SIGNATURES = {
                                     C.c_float, C.c_int, C.c_int, vp, vp, C.c_int, vp]),
     "aft_link_sm_f32": (C.c_int, [C.POINTER(AftLink), vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]),
     "aft_link_joint_f32": (C.c_int, [C.POINTER(AftLink), vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]),
+    "aft_link_alamouti_f32": (C.c_int, [C.POINTER(AftLink), vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]),
     # training path
     "aft_encoder_tape_bytes": (C.c_size_t, [cfgp, C.c_int]),
     "aft_encoder_train_scratch_bytes": (C.c_size_t, [cfgp, C.c_int]),

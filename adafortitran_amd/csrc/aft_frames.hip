@@ -138,6 +138,22 @@ int check_front2(const char *who, const aft_link *link, const float *ideal, cons
     return AFT_OK;
 }
 
+// What the transmit-diversity entry point asks: check_front with one branch -- the group of this link is branches * 2 frames, the
+// pairs (receive antenna, transmit antenna) --, then the branches, the pairing and the batch against the group; 0 = fine
+int check_front_pairs(const char *who, const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys,
+                      std::initializer_list<const void *> words, const char *names, const float *llr, int batch, int n_factors,
+                      int branches, int pairing) {
+    const int rc = check_front(who, link, ideal, est, keys, words, names, llr, batch, n_factors, 1);
+    if (rc != AFT_OK) return rc;
+    if (!within(who, "branches", branches, 1, AFT_LINK_MAX_BRANCHES)) return AFT_ERR_SHAPE;
+    if (pairing != AFT_LINK_PAIR_TIME && pairing != AFT_LINK_PAIR_FREQUENCY) {
+        set_error("%s: pairing = %d is neither AFT_LINK_PAIR_TIME nor AFT_LINK_PAIR_FREQUENCY", who, pairing);
+        return AFT_ERR_SHAPE;
+    }
+    AFT_REQUIRE(batch % (branches * 2) == 0, "%s: batch = %d is not a multiple of branches * 2 = %d * 2", who, batch, branches);
+    return AFT_OK;
+}
+
 // What both decoder entry points compute from a block's coded and information bits and refuse: B = carried / coded blocks per frame
 // (at least one; B info at most 2^31) and the interleaver's stride over the B coded used bits; 0 = fine, *blocks = B
 int check_blocks(const char *who, const aft_link &l, unsigned long long coded, unsigned long long info, unsigned long long stride,
@@ -393,6 +409,17 @@ int aft_link_joint_f32(const aft_link *link, const float *ideal, const float *es
     hipError_t e = launch_link2(true, *link, ideal, est, keys, sigma, rho, scale, nullptr, factors, n_factors, branches, counts, loss, llr,
                                 batch, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? AFT_OK : hip_fail("link_joint", e);
+}
+
+int aft_link_alamouti_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys, const float *sigma,
+                          const float *rho, const float *scale, const float *factors, int n_factors, int branches, int pairing,
+                          int32_t *counts, float *loss, float *llr, int batch, void *stream) {
+    const int rc = check_front_pairs("link alamouti", link, ideal, est, keys, {sigma, rho, scale, factors, counts, loss},
+                                     "sigma, rho, scale, factors, counts, loss and llr", llr, batch, n_factors, branches, pairing);
+    if (rc != AFT_OK) return rc;
+    hipError_t e = launch_link_alamouti(*link, ideal, est, keys, sigma, rho, scale, factors, n_factors, branches, pairing, counts, loss,
+                                        llr, batch, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? AFT_OK : hip_fail("link_alamouti", e);
 }
 
 }  // extern "C"

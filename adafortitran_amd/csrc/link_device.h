@@ -3,7 +3,8 @@
 // transmission) and a branch (one per receive antenna: y = H x + noise, c = y conj(E), p = |E|^2) --, the combiner's step, an axis's
 // max-log LLRs, the softplus step of the loss, the LLR store, the reduction of a workgroup's sums and, on the host, a launch's
 // arguments and its dispatch on the modulation order; and what two-stream detection (k_linksm.hip) adds to them: the two-stream
-// received sample, the Gram / matched sums, the adjugate detector with its LLR scale and the joint max-log demapper.
+// received sample, the Gram / matched sums, the adjugate detector with its LLR scale and the joint max-log demapper; and what transmit
+// diversity (k_linkalamouti.hip) adds: a line's k-th data element, the Alamouti combiner's step and the store of one element's LLRs.
 // adafortitran_amd/linksim.py holds the definitions.
 #pragma once
 
@@ -251,6 +252,48 @@ __device__ __forceinline__ void link_joint_llrs(float d, const LinkSm &a, float 
     }
 }
 
+// ---- transmit diversity: Alamouti pairs over time or frequency (k_linkalamouti.hip; linksim.py "the transmit-diversity link") ----
+
+// The position in its line of the line's k-th data element, k from 0: `pilots` is the sorted list of the line's n pilot positions
+// (n = 0: a line without pilots, position k); every pilot at or below the running position moves it one on.  k is below the line's
+// number of data elements, so the result is inside the line.
+__device__ __forceinline__ unsigned link_line_data(const int *pilots, int n, unsigned k) {
+    unsigned pos = k;
+    for (int i = 0; i < n && (unsigned)pilots[i] <= pos; ++i) ++pos;
+    return pos;
+}
+
+// y conj(E), link_branch's chain of a product and a fused multiply-add per component; E conj(y) is its conjugate
+struct LinkTerm {
+    float r, i;
+};
+
+__device__ __forceinline__ LinkTerm link_matched(const LinkSample &y, float2 e) {
+    return LinkTerm{fmaf(y.yr, e.x, y.yi * e.y), fmaf(y.yi, e.x, -(y.yr * e.y))};
+}
+
+__device__ __forceinline__ float link_norm(float2 e) {
+    return fmaf(e.x, e.x, e.y * e.y);
+}
+
+// One antenna's share of the six sums of a pair (a, b) from its samples y[a], y[b] and its estimates E_r0, E_r1 at a and at b:
+//   c_a += rho (conj(E_r0[a]) y[a] + E_r1[b] conj(y[b])),  p_a += rho (|E_r0[a]|^2 + |E_r1[b]|^2)
+//   c_b += rho (conj(E_r1[a]) y[a] - E_r0[b] conj(y[b])),  p_b += rho (|E_r1[a]|^2 + |E_r0[b]|^2)
+// the term at a before the term at b, one fused multiply-add per term as link_combine's; negation and conjugation are exact.  A lone
+// element is the pair with y[b] = E_r1[a] = E_r0[b] = E_r1[b] = 0: its c_a and p_a are link_combine's of link_branch on the frame (r, 0).
+__device__ __forceinline__ void link_alamouti_accumulate(LinkBranch &ma, LinkBranch &mb, float rho, const LinkSample &ya,
+                                                         const LinkSample &yb, float2 e0a, float2 e1a, float2 e0b, float2 e1b) {
+#pragma clang fp contract(off)
+    const LinkTerm a0 = link_matched(ya, e0a), a1 = link_matched(ya, e1a);      // conj(E_r0[a]) y[a], conj(E_r1[a]) y[a]
+    const LinkTerm b0 = link_matched(yb, e0b), b1 = link_matched(yb, e1b);      // the conjugates of E_r0[b] conj(y[b]), E_r1[b] conj(y[b])
+    ma.cr = fmaf(rho, b1.r, fmaf(rho, a0.r, ma.cr));
+    ma.ci = fmaf(rho, -b1.i, fmaf(rho, a0.i, ma.ci));
+    ma.p = fmaf(rho, link_norm(e1b), fmaf(rho, link_norm(e0a), ma.p));
+    mb.cr = fmaf(rho, -b0.r, fmaf(rho, a1.r, mb.cr));
+    mb.ci = fmaf(rho, b0.i, fmaf(rho, a1.i, mb.ci));
+    mb.p = fmaf(rho, link_norm(e0b), fmaf(rho, link_norm(e1a), mb.p));
+}
+
 // ---- the soft half: max-log LLRs and the loss the achievable rate is read from (linksim.py "the soft link") ----
 
 constexpr int kMaxFactors = 8;
@@ -325,6 +368,22 @@ __device__ __forceinline__ void link_store_llrs(float *dst, const float *v, int 
     }
 }
 
+// ONE element's M floats w to dst, for a walk that does not visit the elements in the pairs (2 i, 2 i + 1): `bytes` is
+// link_llr_element_store_bytes', 16 only where M is a multiple of 4
+template <int M>
+__device__ __forceinline__ void link_store_element_llrs(float *dst, const float (&w)[M], int bytes) {
+    if (M % 4 == 0 && bytes == 16) {
+#pragma unroll
+        for (int j = 0; j + 3 < M; j += 4) *reinterpret_cast<f32x4 *>(dst + j) = f32x4{w[j], w[j + 1], w[j + 2], w[j + 3]};
+    } else if (bytes >= 8) {
+#pragma unroll
+        for (int j = 0; j < M; j += 2) *reinterpret_cast<float2 *>(dst + j) = make_float2(w[j], w[j + 1]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < M; ++j) dst[j] = w[j];
+    }
+}
+
 // A workgroup's sum of one value per thread, in a fixed order: the wave by shuffles (kWave / 2 down to 1), whose result lane 0 leaves in
 // part[wave][slot] ...
 template <class T, int N>
@@ -350,7 +409,14 @@ inline int link_llr_store_bytes(const float *llr, int m, unsigned long long elem
     return at % 16 == 0 && (m % 4 == 0 || elems % 2 == 0) ? 16 : at % 8 == 0 ? 8 : 4;
 }
 
-// ---- a launch's arguments and its dispatch on the modulation order (k_link.hip, k_linksm.hip) ----
+// bytes per store of ONE element's m floats at `llr` (link_store_element_llrs): an element starts at a multiple of 4 m bytes, which is
+// a multiple of 16 when m is 4 or 8 and of 8 always
+inline int link_llr_element_store_bytes(const float *llr, int m) {
+    const uintptr_t at = reinterpret_cast<uintptr_t>(llr);
+    return at % 16 == 0 && m % 4 == 0 ? 16 : at % 8 == 0 ? 8 : 4;
+}
+
+// ---- a launch's arguments and its dispatch on the modulation order (k_link.hip, k_linksm.hip, k_linkalamouti.hip) ----
 
 // the union of what the front end's kernels read and write; a pointer an instantiation does not use is NULL
 struct LinkArgs {

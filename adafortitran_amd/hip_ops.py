@@ -514,6 +514,7 @@ class LinkPlan:
     live there or in pinned host memory, which the kernel reads in place.  The plan trusts its caller in one thing only: its device
     is the current one."""
     cpu_path = "linksim.link_errors_host"
+    pairs = False                                               # True: a group is branches * 2 frames and yields one row (LinkAlamoutiPlan)
 
     def __init__(self, cfg, device: torch.device) -> None:
         from .linksim import LinkConfig
@@ -548,14 +549,18 @@ class LinkPlan:
     def _grouped(self, entry: str, ideal, est, keys, sigma, rho, per_group, factors, want_llr: bool, lib):
         """What the grouped front ends (``LinkMrcPlan``, ``LinkSmPlan``, ``LinkJointPlan``) share.  ``self.group`` is the group's
         width, ``(branches,)`` or ``(branches, streams)``, passed to ``entry`` as it stands; ``per_group`` names the float32 operands
-        with one value per group, in the entry point's order.  Returns ``(counts, loss, llr)`` for ``groups * streams`` rows."""
+        with one value per group, in the entry point's order.  Returns ``(counts, loss, llr)`` for ``groups * streams`` rows.
+        ``LinkAlamoutiPlan`` sets ``self.pairs``: its group is ``branches * 2`` frames that yield ONE row, and ``self.group`` is
+        ``(branches, pairing)``."""
         lib = lib or _lib.load()
         batch, ideal, est, keys, sigma = self._checked(ideal, est, keys, sigma)
-        if batch % math.prod(self.group):
-            raise ValueError(f"a batch of {batch} frames is not a multiple of {' * '.join(('branches', 'streams')[:len(self.group)])} = "
-                             f"{' * '.join(map(str, self.group))}")
-        groups = batch // math.prod(self.group)
-        rows = groups * math.prod(self.group[1:])
+        pairs = self.pairs
+        shape = (self.group[0], 2) if pairs else self.group
+        if batch % math.prod(shape):
+            raise ValueError(f"a batch of {batch} frames is not a multiple of "
+                             f"{' * '.join(('branches', '2' if pairs else 'streams')[:len(shape)])} = {' * '.join(map(str, shape))}")
+        groups = batch // math.prod(shape)
+        rows = groups if pairs else groups * math.prod(self.group[1:])
         rho = _in_place("rho", rho, torch.float32, self.device, batch)
         per_group = [_in_place(name, t, torch.float32, self.device, groups) for name, t in per_group]
         factors = self._checked_factors(factors)
@@ -655,6 +660,33 @@ class LinkJointPlan(LinkSmPlan):
     def __call__(self, ideal: torch.Tensor, est: torch.Tensor, keys: torch.Tensor, sigma: torch.Tensor, rho: torch.Tensor,
                  scale: torch.Tensor, factors: torch.Tensor, want_llr: bool = False, lib=None):
         return self._grouped("aft_link_joint_f32", ideal, est, keys, sigma, rho, [("scale", scale)], factors, want_llr, lib)
+
+
+class LinkAlamoutiPlan(LinkPlan):
+    """Transmit diversity on ``LinkPlan``'s link: two transmit antennas send ONE stream as Alamouti pairs over adjacent data symbols
+    (``pairing="time"``) or subcarriers (``"frequency"``) and ``branches`` receive antennas combine (``linksim``: "the transmit-diversity
+    link"); frame ``g 2R + r 2 + s`` of a batch is the pair (receive antenna ``r``, transmit antenna ``s``) of group ``g``.
+    ``plan(ideal, est, keys, sigma, rho, scale, factors, want_llr=False)`` -> ``(counts int32 [G, 2], loss float32 [G, K], llr float32
+    [G, S, T, m] or None)`` for the ``G = batch / (2 branches)`` groups on the plan's device: three ``torch.empty`` at the most, one
+    ``ctypes`` call, one launch (``aft_link_alamouti_f32``) on the current stream, no synchronisation.  ``rho`` (float32, ``batch``
+    values) and ``scale`` (float32, ``G`` values: the leaders') are ``linksim.alamouti_weights``'; they and ``factors`` live where
+    ``keys`` and ``sigma`` may.  Everything else as ``LinkMrcPlan``."""
+    cpu_path = "linksim.link_alamouti_host"
+    pairs = True
+
+    def __init__(self, cfg, device: torch.device, branches: int, pairing: str = "time") -> None:
+        super().__init__(cfg, device)
+        from .linksim import PAIRINGS
+        if not isinstance(pairing, str) or pairing not in PAIRINGS:
+            raise ValueError(f"pairing = {pairing!r}: one of {PAIRINGS}")
+        if isinstance(branches, bool) or not isinstance(branches, int) or not 1 <= branches <= _abi.AFT_LINK_MAX_BRANCHES:
+            raise ValueError(f"branches = {branches!r}: an integer in 1 .. {_abi.AFT_LINK_MAX_BRANCHES}")
+        self.branches, self.pairing = branches, pairing
+        self.group = (branches, (_abi.AFT_LINK_PAIR_TIME, _abi.AFT_LINK_PAIR_FREQUENCY)[PAIRINGS.index(pairing)])
+
+    def __call__(self, ideal: torch.Tensor, est: torch.Tensor, keys: torch.Tensor, sigma: torch.Tensor, rho: torch.Tensor,
+                 scale: torch.Tensor, factors: torch.Tensor, want_llr: bool = False, lib=None):
+        return self._grouped("aft_link_alamouti_f32", ideal, est, keys, sigma, rho, [("scale", scale)], factors, want_llr, lib)
 
 
 class _DecoderPlan:

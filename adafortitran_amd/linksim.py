@@ -85,7 +85,8 @@ this kernel's to model -- the estimators are per antenna, so a correlated channe
 from the simulator, ``ChannelSimConfig(antennas=(R, 1), rx_correlation=...)`` (chansim.py, "Kronecker frame groups"), whose groups are
 these R frames and share one SNR, delay spread and Doppler.  With an ungrouped configuration the R frames are independent draws -- the
 best case for the combiner -- each with its own conditions unless the caller pins them.  The link gives no array gain in the
-estimator itself (no estimator here sees more than one antenna's pilots).
+estimator itself (no estimator here sees more than one antenna's pilots).  Diversity at the transmitter -- two antennas sending
+one stream as Alamouti pairs in front of this combiner -- is "the transmit-diversity link" below (``tx_diversity=``).
 
 The spatial-multiplexing link.  The receivers that have the antennas ``branches=`` models do not only combine: they separate two
 spatial streams, and there an error in the estimate leaks one stream into the other, amplified by the conditioning of the channel.
@@ -124,7 +125,8 @@ section).  Antenna correlation, which decides how well two streams separate at a
 ``ChannelSimConfig(antennas=(R, 2), rx_correlation=..., tx_correlation=...)`` makes these ``2 R`` frames one correlated group with
 shared conditions (chansim.py, "Kronecker frame groups"); with an ungrouped configuration the pairs are independent draws with their
 own conditions unless the caller pins them.  It does not model sphere or list detection, successive cancellation, precoding, or
-``N > 2``.
+``N > 2``.  The same two transmit antennas sending ONE stream as Alamouti pairs are "the transmit-diversity link" below
+(``tx_diversity=``).
 
 The joint link.  A linear detector on a 2 x 2 Rayleigh channel has diversity order 1; a receiver that ships two-stream reception runs a
 max-log joint demapper and gets order 2, and behind it an estimation error no longer leaks through an ill-conditioned inverse: it
@@ -161,6 +163,45 @@ is exactly 0 and stream 0's LLRs are the diversity link's on the frames ``(r, 0)
 joint max-log demapper.  Antenna correlation comes from the simulator's grouped configurations, as for the linear detectors.  It does
 not model sphere or list detection (nothing is pruned: every candidate is evaluated), successive cancellation, iterative detection
 and decoding, or ``N > 2``.
+
+The transmit-diversity link.  The third standard two-antenna mode sends ONE stream from two transmit antennas as Alamouti pairs:
+space-time block coding over adjacent symbols or space-frequency block coding over adjacent subcarriers, what cell-edge and control
+transmissions of current OFDM systems run.  The pair is orthogonal only while the channel is equal across its two elements: time
+pairing breaks with Doppler, frequency pairing with delay spread, and an estimation error shows up neither through an inverse nor
+through a mismatched joint metric but as residual cross-talk between the two symbols of a pair.  ``link_alamouti_host`` (float64),
+``alamouti_pairs``, ``alamouti_weights``, ``aft_link_alamouti_f32`` (csrc/k_linkalamouti.hip, through ``hip_ops.LinkAlamoutiPlan``)
+and the ``tx_diversity=`` argument (one of ``PAIRINGS``) of the accumulators and of the three sweeps of ``evaluation`` are that link.
+A batch of ``n`` frames with ``R = branches``, ``1 <= R <= 8`` and ``n % (2 R) == 0`` is ``G = n / (2 R)`` groups; frame
+``g 2R + r 2 + s`` is the pair (receive antenna ``r``, transmit antenna ``s``) of group ``g`` -- the order of ``streams=2`` and of
+``ChannelSimConfig(antennas=(R, 2))`` --, ``H_rs`` its true channel and ``E_rs`` its estimate; frame ``(0, 0)`` is the LEADER::
+
+    lines      pairing "time": a line is a subcarrier s, its elements in increasing t;  pairing "frequency": a line is a symbol t, its
+               elements in increasing s.  The DATA elements of a line in increasing order are d_0, d_1, ...; (d_2i, d_2i+1) is a pair
+               (a, b), whether or not pilots lie between them; a line with an odd number of data elements leaves its last one LONE
+    sent       every data element e sends w, gi, gq, x exactly as the single link does, from stream 5 of the LEADER's key at q_e = s T + t:
+               one transmission per group, m data_elements bits (the code has rate 1)
+    transmit   pair: antenna 0 sends x_a at a and -conj(x_b) at b; antenna 1 sends x_b at a and conj(x_a) at b.  Lone: antenna 0 sends x,
+               antenna 1 nothing.  Each antenna sends at unit mean energy, as each stream of the spatial-multiplexing link does
+    received   y_r[e] = H_r0[e] t0[e] + H_r1[e] t1[e] + sigma_r sqrt(-ln u1) exp(j 2 pi u2)      u1, u2 from streams 6, 7 of the key of frame
+               (r, 0) at q_e, sigma_r that frame's; keys, sigma and rho of the frames (r, 1) are not read
+    weights    rho_r = float32(scale_(r,0) / scale_leader) as branch_weights forms them over the 2 R frames; scale the leader's, one per group
+    combiner   c_a = sum_r rho_r (conj(E_r0[a]) y_r[a] + E_r1[b] conj(y_r[b]))        p_a = sum_r rho_r (|E_r0[a]|^2 + |E_r1[b]|^2)
+               c_b = sum_r rho_r (conj(E_r1[a]) y_r[a] - E_r0[b] conj(y_r[b]))        p_b = sum_r rho_r (|E_r1[a]|^2 + |E_r0[b]|^2)
+               lone: c = sum_r rho_r conj(E_r0) y_r,  p = sum_r rho_r |E_r0|^2        (the diversity link's element on the frames (r, 0))
+               increasing r; within r the term at a before the term at b; one fused multiply-add per term, as link_combine's
+    hard/soft  the single link's decision, bit and symbol errors, mu_k, Delta_j, Lambda_j = scale Delta_j and loss_f on (c, p); pilots carry 0
+    outputs    counts int [G, 2], loss [G, K], llr [G, S, T, m]: the diversity link's shapes, read by the decoders with the leaders' keys
+
+Why the soft rule is the diversity link's: after the weights the noise of ``c`` has variance ``p / scale``, so ``scale`` stands in front
+of ``p |x^ - a_k|^2`` exactly as there; there is no division and no regulariser.  Reaches, margins and ``q`` follow the diversity link's
+with ``reach(y_r[e]) = |H_r0[e]||t0[e]| + |H_r1[e]||t1[e]| + |noise|`` and ``reach(c)`` the combiner's sum with every factor replaced
+by its absolute value; ``p`` is a sum of non-negative terms, so ``p_reach = p``.  With an unheard second antenna (``H_r1 = E_r1 = 0``)
+the first and the lone elements are the diversity link's on the frames ``(r, 0)``.  What this models: the linear Alamouti combiner,
+which assumes the channel equal over a pair.  What is measured is the cross-talk left by channel variation inside a pair, by estimate
+errors and by antenna correlation; correlation comes from the simulator, ``ChannelSimConfig(antennas=(R, 2), ...)``, whose groups are
+these ``2 R`` frames.  The SNR is per transmit antenna, as on the spatial-multiplexing link: a comparison at equal total power
+evaluates this link 3.01 dB lower.  It does not model joint detection of the two symbols of a pair, more than two transmit antennas,
+precoding or antenna selection; HARQ is not covered (``HarqAccumulator`` has no ``tx_diversity``).
 
 The coded link.  The rate says how much information the LLRs carry; a link-level user wants the same with a decoder in the loop: the
 block-error rate of coded blocks and the throughput that follows from it.  ``CodeConfig``, ``link_encode_host`` / ``link_decode_host``
@@ -753,6 +794,108 @@ def link_joint_host(cfg: LinkConfig, keys, ideal, est, sigma, rho, scale, branch
     return out
 
 
+# ---- the transmit-diversity link (module docstring, "The transmit-diversity link"): float64 NumPy, mirrored by csrc/k_linkalamouti.hip ----
+
+PAIRINGS = ("time", "frequency")
+
+
+def _pairing(pairing) -> int:
+    """The library's constant of a pairing's name, checked."""
+    if not isinstance(pairing, str) or pairing not in PAIRINGS:
+        raise ValueError(f"pairing = {pairing!r}: one of {PAIRINGS}")
+    return (_abi.AFT_LINK_PAIR_TIME, _abi.AFT_LINK_PAIR_FREQUENCY)[PAIRINGS.index(pairing)]
+
+
+def _tx_grouped(n: int, branches: int) -> int:
+    if n % (branches * 2):
+        raise ValueError(f"a batch of {n} frames is not a multiple of branches * 2 = {branches} * 2")
+    return n // (branches * 2)
+
+
+def alamouti_pairs(cfg: LinkConfig, pairing: str = "time") -> Tuple[np.ndarray, np.ndarray]:
+    """The Alamouti pairs of a grid: ``(role int8 [S, T], partner int64 [S, T])``.  ``role`` is -1 at a pilot, 0 at the first element
+    of a pair, 1 at its second and 2 at a lone element; ``partner`` is the flat index ``s T + t`` of the other element of the pair, and
+    a pilot's or a lone element's own.  A line is a subcarrier for ``"time"`` and a symbol for ``"frequency"``; its data elements in
+    increasing order pair up two by two, whether or not pilots lie between them."""
+    _pairing(pairing)
+    S, T = cfg.sim.ofdm
+    mask = cfg.data_mask
+    flat = np.arange(S * T, dtype=np.int64).reshape(S, T)
+    role, partner = np.full((S, T), -1, dtype=np.int8), flat.copy()
+    if pairing == "frequency":                                                   # the lines are the columns: work on the transposed views
+        mask, flat, role_v, partner_v = mask.T, flat.T, role.T, partner.T
+    else:
+        role_v, partner_v = role, partner
+    for line in range(mask.shape[0]):
+        data = np.flatnonzero(mask[line])
+        pairs = len(data) // 2
+        a, b = data[0:2 * pairs:2], data[1:2 * pairs:2]
+        role_v[line, a], role_v[line, b] = 0, 1
+        partner_v[line, a], partner_v[line, b] = flat[line, b], flat[line, a]
+        if len(data) % 2:
+            role_v[line, data[-1]] = 2
+    return role, partner
+
+
+def alamouti_weights(snr_db, err_var: float = 0.0, branches: int = 1) -> Tuple[np.ndarray, np.ndarray]:
+    """The combiner's operands for frames at ``snr_db`` ``[n]`` in the transmit-diversity layout: ``(rho float32 [n], scale float32
+    [G])``, ``branch_weights`` over the ``2 * branches`` frames of a group (the entries of frames ``(r, 1)`` are not read)."""
+    R = _branches(branches)
+    snr = np.asarray(snr_db, dtype=np.float64).reshape(-1)
+    _tx_grouped(snr.size, R)
+    return _weights(llr_scale(snr, err_var), 2 * R)
+
+
+def link_alamouti_host(cfg: LinkConfig, keys, ideal, est, sigma, rho, scale, branches, pairing: str = "time", factors=(1.0,),
+                       tau: Optional[float] = None, e_lambda: Optional[float] = None):
+    """The transmit-diversity link (module docstring) in float64: ``keys`` / ``ideal`` / ``est`` / ``sigma`` as ``link_errors_host``'s
+    for the ``n`` frames in the layout ``g 2R + r 2 + s``, ``rho`` ``[n]`` and ``scale`` ``[G]`` taken as the float32 numbers they are
+    (``alamouti_weights``), ``G = n / (2 branches)`` -> ``link_mrc_host``'s tuple, in its order: ``(counts int64 [G, 2], loss float64
+    [G, K], llr float64 [G, S, T, m])``; with ``tau`` the wrong-bit map ``[G, S, T]`` and the flags ``[G, S, T, 2]`` follow, with
+    ``e_lambda`` then ``loss_lo``, ``loss_hi`` and ``q``, on the combiner's ``c``, ``p`` and reach.  Needs no library."""
+    R = _branches(branches)
+    role, partner = alamouti_pairs(cfg, pairing)
+    keys, H, E, sigma = _checked(cfg, keys, ideal, est, sigma)
+    n, (S, T) = len(keys), cfg.sim.ofdm
+    G = _tx_grouped(n, R)
+    rho = np.asarray(rho, dtype=np.float32).astype(np.float64).reshape(-1)
+    if rho.shape != (n,):
+        raise ValueError(f"rho must hold one value per frame ({n}), got {rho.size}")
+    if np.size(scale) != G:
+        raise ValueError(f"scale must hold one value per group ({G}), got {np.size(scale)}")
+    W = 2 * R
+    gi, gq, x = _sent(cfg, keys[::W])                                             # one transmission per group: the leader's key
+    at = partner.reshape(-1)
+    other = lambda v: v.reshape(G, S * T)[:, at].reshape(G, S, T)  # noqa: E731     a [G, S, T] array at every element's partner
+    first, second = role == 0, role == 1                                          # pilots and lone elements: neither
+    xo = other(x)
+    # what the two antennas send at every element: (x_a, x_b) at a, (-conj(x_b), conj(x_a)) at b, (x, 0) at a lone element
+    t0 = np.where(second, -np.conj(x), x)
+    t1 = np.where(first, xo, np.where(second, np.conj(xo), 0.0))
+    c = p = reach = 0.0
+    for r in range(R):                                                           # in increasing r, starting from 0
+        sl = slice(2 * r, None, W)                                               # the frames (r, 0); (r, 1) follow them
+        H0, H1, E0, E1 = H[sl], H[2 * r + 1::W], E[sl], E[2 * r + 1::W]
+        noise = _noise(cfg, keys[sl], sigma[sl])
+        y = H0 * t0 + H1 * t1 + noise
+        ry = np.abs(H0) * np.abs(t0) + np.abs(H1) * np.abs(t1) + np.abs(noise)
+        yo, ryo, E0o, E1o = other(y), other(ry), other(E0), other(E1)
+        n0, n1 = E0.real ** 2 + E0.imag ** 2, E1.real ** 2 + E1.imag ** 2
+        # (the term at a, the term at b) of c, of p and of the reach, per role of the element
+        # (y conj(E) in _branch's operand order: with H_r1 = E_r1 = 0 the first and lone elements are link_mrc_host's bit for bit)
+        ca = np.where(second, yo * E1o.conj(), y * E0.conj())
+        cb = np.where(first, yo.conj() * E1o, np.where(second, -(y.conj() * E0), 0.0))
+        pa = np.where(second, other(n1), n0)
+        pb = np.where(first, other(n1), np.where(second, n0, 0.0))
+        ra = np.where(second, np.abs(E1o) * ryo, np.abs(E0) * ry)
+        rb = np.where(first, np.abs(E1o) * ryo, np.where(second, np.abs(E0) * ry, 0.0))
+        w = rho[sl, None, None]
+        c, p, reach = (c + w * ca) + w * cb, (p + w * pa) + w * pb, (reach + w * ra) + w * rb
+    hard = _hard(cfg, gi, gq, c, p, reach, tau)
+    soft = _soft(cfg, gi, gq, c, p, reach, scale, factors, e_lambda)
+    return ((hard,) if tau is None else hard[:1]) + soft[:2] + (() if tau is None else hard[1:]) + soft[2:]
+
+
 # ---- the frame keys with torch ops, for frame numbers that live on the device (no synchronisation) ----
 
 def _s64(v: int) -> int:
@@ -780,24 +923,31 @@ def frame_keys_torch(seed: int, frame_ids: torch.Tensor) -> torch.Tensor:
 
 class _FrameSweep:
     """What the accumulators of a sweep share: ``_measure`` turns a batch into what the accumulator asked ``_open`` for -- the counts, the
-    loss or the LLRs of the link, with the diversity link's combiner in front when ``branches > 1`` -- as tensors on the accumulator's
-    device, whichever device that is.  ``_operands`` returns None for an empty batch, else ``(b, H, E, keys, per_frame)``: on a CPU
+    loss or the LLRs of the link, with the diversity link's combiner in front when ``branches > 1``, the two-stream detector with
+    ``streams=2`` or the Alamouti combiner with ``tx_diversity`` -- as tensors on the accumulator's device, whichever device that is.  ``_operands`` returns None for an empty batch, else ``(b, H, E, keys, per_frame)``: on a CPU
     device NumPy arrays for the float64 definition, on a HIP device tensors for the plan -- frame numbers and SNRs that are host
     tensors are hashed and converted on the host and copied from pinned memory, device tensors with torch ops, so nothing
     synchronises.  ``per_frame`` holds one float32 ``[b]`` operand per entry of ``of_snr``, pairs ``(numpy function, torch function on
     a float64 tensor)`` of the SNR in dB."""
 
     def _open(self, cfg: LinkConfig, device, seed: int, want: str, branches: int = 1, err_var: float = 0.0, factors=(1.0,),
-              streams: int = 1, detector: str = "mmse") -> None:
+              streams: int = 1, detector: str = "mmse", tx_diversity: Optional[str] = None) -> None:
         """``want``: which of ``"counts"``, ``"loss"`` and ``"llr"`` ``_measure`` computes.  ``streams=2``: the spatial-multiplexing
-        link with ``detector`` in front (``streams=1`` ignores it)."""
+        link with ``detector`` in front (``streams=1`` ignores it).  ``tx_diversity``: None, or the pairing of the transmit-diversity
+        link in front (one stream; ``detector`` is ignored)."""
         if not isinstance(cfg, LinkConfig):
             raise ValueError(f"{type(self).__name__} needs a LinkConfig (got {type(cfg).__name__})")
         self.cfg, self.seed, self._want = cfg, int(seed), want
         self.branches = _branches(branches)
         if isinstance(streams, bool) or not isinstance(streams, (int, np.integer)) or int(streams) not in (1, MAX_STREAMS):
             raise ValueError(f"streams = {streams!r}: 1, or {MAX_STREAMS} for the spatial-multiplexing link")
-        self.streams, self.detector = int(streams), detector
+        self.streams, self.detector, self.tx_diversity = int(streams), detector, tx_diversity
+        if tx_diversity is not None:
+            _pairing(tx_diversity)
+            if self.streams != 1:
+                raise ValueError(f"tx_diversity = {tx_diversity!r} sends one stream from two antennas: streams must be 1 (got {self.streams})")
+        # frames per group: the branches, times the two transmit antennas or the streams
+        self._width =self.branches * (2 if tx_diversity is not None else self.streams)
         if self.streams > 1:
             _sm_shape(0, self.branches, self.streams)           # one antenna cannot separate two streams
             _detector(detector)                                 # the detector's name: a linear one, or "joint"
@@ -806,7 +956,9 @@ class _FrameSweep:
         self._plan = None
         if self.device.type == "cuda":
             from . import hip_ops                  # loads the extension: a missing .so raises here, loudly
-            if self.streams > 1:                   # every measure of the spatial-multiplexing link comes from the detector's one launch
+            if tx_diversity is not None:           # every measure of the transmit-diversity link comes from the combiner's one launch
+                self._plan = hip_ops.LinkAlamoutiPlan(cfg, self.device, self.branches, tx_diversity)
+            elif self.streams > 1:                 # every measure of the spatial-multiplexing link comes from the detector's one launch
                 plan = hip_ops.LinkJointPlan if detector == JOINT_DETECTOR else hip_ops.LinkSmPlan
                 self._plan = plan(cfg, self.device, self.branches, self.streams)
             elif self.branches == 1:
@@ -819,7 +971,7 @@ class _FrameSweep:
             raise ValueError(f"err_var = {err_var!r}: a variance, at least 0")
         self.factors = _factors(factors)
         self._factors_t = None if self._plan is None else torch.from_numpy(self.factors).to(self.device)
-        self._of_snr = (_SIGMA_OF_SNR, _SCALE_OF_SNR(self.err_var)) if soft or self.branches > 1 or self.streams > 1 else (_SIGMA_OF_SNR,)
+        self._of_snr = (_SIGMA_OF_SNR, _SCALE_OF_SNR(self.err_var)) if soft or self._width > 1 else (_SIGMA_OF_SNR,)
         self.frames = 0
 
     def _stage(self, a: np.ndarray) -> torch.Tensor:
@@ -883,12 +1035,14 @@ class _FrameSweep:
         several, the weights formed by torch ops on the device -- and nothing synchronises.  With ``streams=2`` the groups are the
         ``G N`` stream-frames of the spatial-multiplexing link with the keys of frames ``(0, s)``: ``link_sm_host`` on a CPU device,
         one launch of ``aft_link_sm_f32`` with ``rho`` and ``reg`` formed on the device on a HIP device; with ``detector="joint"``
-        ``link_joint_host`` and one launch of ``aft_link_joint_f32``, which has no ``reg``."""
+        ``link_joint_host`` and one launch of ``aft_link_joint_f32``, which has no ``reg``.  With ``tx_diversity`` the groups are the
+        ``G`` transmissions of the transmit-diversity link with the leaders' keys: ``link_alamouti_host`` on a CPU device, one launch
+        of ``aft_link_alamouti_f32`` with ``rho`` formed on the device on a HIP device."""
         ops = self._operands(est, ideal, meta, frame_ids, snr_db, self._of_snr)
         if ops is None:
             return None
         b, H, E, keys, (sigma, *scale) = ops       # scale: the frames' LLR scales, where the measure or the combiner needs them
-        G = _grouped(b, self.branches, self.streams)
+        G = _tx_grouped(b, self.branches) if self.tx_diversity is not None else _grouped(b, self.branches, self.streams)
         measure = self._measure_host if self._plan is None else self._measure_device
         return (G * self.streams, *measure(G, H, E, keys, sigma, scale))
 
@@ -896,7 +1050,11 @@ class _FrameSweep:
         """The float64 definitions on NumPy operands: ``(the leaders' keys, counts, loss, llr)`` as host tensors."""
         R, N = self.branches, self.streams
         counts = loss = llr = None
-        if N > 1:                                  # G N "frames": stream s of group g, with the key of frame (0, s)
+        if self.tx_diversity is not None:          # G transmissions from two antennas, with the leaders' keys
+            counts, loss, llr = link_alamouti_host(self.cfg, keys, H, E, sigma, *_weights(scale[0], 2 * R), R, self.tx_diversity,
+                                                   self.factors)
+            sent = keys[::2 * R]
+        elif N > 1:                                # G N "frames": stream s of group g, with the key of frame (0, s)
             rho, lead = _weights(scale[0], R * N)
             if self.detector == JOINT_DETECTOR:
                 out = link_joint_host(self.cfg, keys, H, E, sigma, rho, lead, R, N, self.factors)
@@ -924,6 +1082,10 @@ class _FrameSweep:
         """The plan's one launch on device operands: ``(the leaders' keys, counts, loss, llr)`` on the device."""
         R, N, want_llr = self.branches, self.streams, self._want == "llr"
         counts = loss = llr = None
+        if self.tx_diversity is not None:          # the weights of the frames (r, 0) against the leader's, over the 2 R frames of a group
+            rho, lead = self._device_weights(scale[0], 2 * R)
+            counts, loss, llr = self._launch(H, E, keys, sigma, rho, lead, self._factors_t, want_llr=want_llr)
+            return keys[::2 * R].contiguous(), counts, loss, llr
         if N > 1:                                  # the detectors differ in one operand: the joint one has no regulariser
             rho, lead = self._device_weights(scale[0], R * N)
             if self.detector == JOINT_DETECTOR:
@@ -997,10 +1159,20 @@ class LinkAccumulator(_FrameSweep):
     key of frame ``(0, s)``; ``frames`` counts them, and every rate is per stream and symbol: the spectral efficiency is N times it.
     ``detector="joint"`` (module docstring, "the joint link") is the joint max-log demapper on the same frames: one launch of
     ``aft_link_joint_f32`` (on a CPU device ``link_joint_host``), no regulariser.
-    ``streams=1`` is today's path, launch for launch, and ignores ``detector``."""
+    ``streams=1`` is today's path, launch for launch, and ignores ``detector``.
 
-    def __init__(self, cfg: LinkConfig, device, seed: int = 0, branches: int = 1, streams: int = 1, detector: str = "mmse") -> None:
-        self._open(cfg, device, seed, "counts", branches, streams=streams, detector=detector)
+    ``tx_diversity="time"`` or ``"frequency"`` (module docstring, "the transmit-diversity link"; the same keyword on ``RateAccumulator``,
+    ``BlockErrorAccumulator`` and ``LdpcBlockErrorAccumulator``, not on ``HarqAccumulator``): every ``2 R`` consecutive frames of a batch
+    are the (receive antenna, transmit antenna) pairs of one receiver, ``R = branches`` in 1 .. 8, and the two transmit antennas send
+    ONE stream as Alamouti pairs over adjacent data symbols or subcarriers, combined by one launch of ``aft_link_alamouti_f32`` (on a
+    CPU device by ``link_alamouti_host``) with ``rho`` formed on the device without a synchronisation.  ``streams`` must be 1
+    (``ValueError`` otherwise), ``detector`` is ignored, a batch that is no multiple of ``2 R`` raises ``ValueError``; a batch yields
+    ``G`` rows with the leaders' keys and ``frames`` counts them.  The SNR is per transmit antenna.  ``tx_diversity=None`` is today's
+    path, launch for launch."""
+
+    def __init__(self, cfg: LinkConfig, device, seed: int = 0, branches: int = 1, streams: int = 1, detector: str = "mmse", *,
+                 tx_diversity: Optional[str] = None) -> None:
+        self._open(cfg, device, seed, "counts", branches, streams=streams, detector=detector, tx_diversity=tx_diversity)
         self.errors = torch.zeros(2, dtype=torch.int64, device=self.device)     # bit errors, symbol errors
 
     def update(self, est: Optional[torch.Tensor], ideal: torch.Tensor, meta: Optional[tuple] = None, *, frame_ids=None,
@@ -1037,11 +1209,12 @@ class RateAccumulator(_FrameSweep):
     tensor ``[K]``; nothing synchronises.  On a CPU device the float64 definition runs.  ``result`` returns the K rates in bit/symbol
     (``m - loss / data elements``; a rate may be negative), ``result_gmi`` their maximum; either is one read and, with several ranks,
     one all-gather of ``K + 1`` float64 (the K losses and the frames).  The losses are float sums: ranks that split a sweep differently
-    agree to rounding, not bit for bit -- every rank of one sweep reports the same number."""
+    agree to rounding, not bit for bit -- every rank of one sweep reports the same number.  ``branches``, ``streams``, ``detector`` and
+    ``tx_diversity`` as ``LinkAccumulator``'s: with ``tx_diversity`` the rate is per transmission of the two antennas."""
 
     def __init__(self, cfg: LinkConfig, device, seed: int = 0, factors=(1.0,), err_var: float = 0.0, branches: int = 1,
-                 streams: int = 1, detector: str = "mmse") -> None:
-        self._open(cfg, device, seed, "loss", branches, err_var, factors, streams, detector)
+                 streams: int = 1, detector: str = "mmse", *, tx_diversity: Optional[str] = None) -> None:
+        self._open(cfg, device, seed, "loss", branches, err_var, factors, streams, detector, tx_diversity)
         self.loss = torch.zeros(len(self.factors), dtype=torch.float64, device=self.device)
 
     def update(self, est: Optional[torch.Tensor], ideal: torch.Tensor, meta: Optional[tuple] = None, *, frame_ids=None,
@@ -1278,16 +1451,18 @@ class BlockErrorAccumulator(_FrameSweep):
     launch of ``aft_link_soft_f32`` with its LLR output, the launch of ``aft_link_decode_f32`` on that tensor, and one integer add into
     an int64 ``[2]`` device tensor; nothing synchronises.  On a CPU device the host definitions run (float64 LLRs rounded to float32).
     ``result`` is the block-error rate, ``result_ber`` the information-bit error rate, ``result_throughput`` the delivered information
-    bits per data element; each is one read and, with several ranks, one all-gather of three float64."""
+    bits per data element; each is one read and, with several ranks, one all-gather of three float64.  ``branches``, ``streams``,
+    ``detector`` and ``tx_diversity`` as ``LinkAccumulator``'s: with ``tx_diversity`` the LLRs are ``aft_link_alamouti_f32``'s (on a
+    CPU device ``link_alamouti_host``'s) and the decoder reads them with the leaders' keys."""
 
     #: what ``LdpcBlockErrorAccumulator`` changes: the config it accepts, the host decoder, the decoder's plan and the columns of ``errors``
     _config, _needs, _host_decoder, _decoder_plan, _columns = CodeConfig, "a CodeConfig", staticmethod(link_decode_host), "LinkDecodePlan", 2
 
     def __init__(self, code, device, seed: int = 0, err_var: float = 0.0, branches: int = 1, streams: int = 1,
-                 detector: str = "mmse") -> None:
+                 detector: str = "mmse", *, tx_diversity: Optional[str] = None) -> None:
         if not isinstance(code, self._config):
             raise ValueError(f"{type(self).__name__} needs {self._needs} (got {type(code).__name__})")
-        self._open(code.link, device, seed, "llr", branches, err_var, streams=streams, detector=detector)
+        self._open(code.link, device, seed, "llr", branches, err_var, streams=streams, detector=detector, tx_diversity=tx_diversity)
         self.code = code
         self.errors = torch.zeros(self._columns, dtype=torch.int64, device=self.device)    # information-bit errors, block errors, ...
         self._decode = None
@@ -1617,7 +1792,7 @@ class LdpcBlockErrorAccumulator(BlockErrorAccumulator):
     (information-bit errors, block errors, iterations) and ``result_iterations``, the mean iterations per block.  On a HIP device a
     batch is the launch of ``aft_link_soft_f32`` with its LLR output, the launch of ``aft_link_ldpc_f32`` on that tensor and one
     integer add; nothing synchronises.  On a CPU device the host definitions run.  Each result is one read and, with several ranks,
-    one all-gather of four float64."""
+    one all-gather of four float64.  ``branches``, ``streams``, ``detector`` and ``tx_diversity`` as ``BlockErrorAccumulator``'s."""
 
     _config, _needs, _host_decoder, _decoder_plan, _columns = LdpcConfig, "an LdpcConfig", staticmethod(link_ldpc_host), "LinkLdpcPlan", 3
 
@@ -1793,7 +1968,8 @@ class HarqAccumulator(BlockErrorAccumulator):
     _config, _needs, _host_decoder, _decoder_plan, _columns = HarqConfig, "a HarqConfig", staticmethod(link_harq_host), "LinkHarqPlan", HARQ_COUNTS
 
     def __init__(self, code, device, seed: int = 0, err_var: float = 0.0, branches: int = 1) -> None:
-        # no ``streams``: a group's rounds are consecutive LLR frames, which would be the two streams of one group
+        # no ``streams``: a group's rounds are consecutive LLR frames, which would be the two streams of one group; no ``tx_diversity``:
+        # HARQ over Alamouti pairs is not defined here
         super().__init__(code, device, seed, err_var, branches)
 
     def update(self, est: Optional[torch.Tensor], ideal: torch.Tensor, meta: Optional[tuple] = None, *, frame_ids=None,

@@ -645,6 +645,47 @@ int aft_link_joint_f32(const aft_link *link, const float *ideal, const float *es
                        int32_t *counts /* [groups][streams][2] */, float *loss /* [groups][streams][n_factors] */,
                        float *llr /* [groups,streams,S,T,m] or NULL */, int batch, void *stream);
 
+/* ---- transmit diversity: Alamouti pairs over time or frequency (adafortitran_amd/linksim.py "the transmit-diversity link") ----
+ *
+ * Two transmit antennas send ONE stream as Alamouti pairs, R = branches receive antennas combine, 1 <= R <= AFT_LINK_MAX_BRANCHES:
+ * group g of a batch is the frames g 2 R .. g 2 R + 2 R - 1, frame g 2 R + r 2 + s the pair (receive antenna r, transmit antenna s) --
+ * aft_link_sm_f32's order --, frame (0, 0) the group's leader.
+ *   lines       pairing AFT_LINK_PAIR_TIME: a line is a subcarrier, its elements in increasing symbol; AFT_LINK_PAIR_FREQUENCY: a
+ *               line is a symbol, its elements in increasing subcarrier.  The DATA elements of a line in increasing order are
+ *               d_0, d_1, ...; (d_2i, d_2i+1) is a pair (a, b), whether or not pilots lie between them; the last data element of
+ *               a line with an odd number of them is LONE
+ *   sent        every data element sends w, gi, gq, x as aft_link_errors_f32's, from stream 5 of the LEADER's key: one transmission
+ *               per group, m data_elements bits
+ *   transmit    pair: antenna 0 sends x_a at a and -conj(x_b) at b, antenna 1 sends x_b at a and conj(x_a) at b; lone: antenna 0
+ *               sends x, antenna 1 nothing
+ *   received    y_r[e] = H_r0[e] t0[e] + H_r1[e] t1[e] + sigma_r sqrt(-ln u1) exp(j 2 pi u2), u1 and u2 from streams 6 and 7 of the
+ *               key of frame (r, 0) at e, sigma_r that frame's (aft_link_sm_f32's sample); keys, sigma and rho of frames (r, 1) are
+ *               not read
+ *   combiner    c_a = sum_r rho_r (conj(E_r0[a]) y_r[a] + E_r1[b] conj(y_r[b])),  p_a = sum_r rho_r (|E_r0[a]|^2 + |E_r1[b]|^2)
+ *               c_b = sum_r rho_r (conj(E_r1[a]) y_r[a] - E_r0[b] conj(y_r[b])),  p_b = sum_r rho_r (|E_r1[a]|^2 + |E_r0[b]|^2)
+ *               lone: c = sum_r rho_r conj(E_r0) y_r, p = sum_r rho_r |E_r0|^2; rho_r = rho of frame (r, 0); increasing r, within r
+ *               the term at a before the term at b, one fused multiply-add per term, sums start at -0
+ *   decision, counts, mu_k, Delta_j, Lambda_j = scale Delta_j (the LEADER's scale, one per group) and loss[f] as aft_link_mrc_f32's
+ *               on (c, p); pilots carry 0
+ * The linear Alamouti combiner, which assumes the channel equal over a pair: what is measured is the cross-talk that channel variation
+ * inside a pair and estimation errors leave.  With H_r1 = E_r1 = 0 the LLRs at first and lone elements are aft_link_mrc_f32's on the
+ * frames (r, 0), bit for bit.
+ * One launch, one workgroup per group: counts int32 [groups][2], loss float32 [groups][n_factors] and, when llr is not NULL, llr
+ * float32 [groups, S, T, m] (all device memory) -- aft_link_mrc_f32's outputs, read by the decoders with the leaders' keys -- from
+ * ideal and est complex64 [batch, S, T] (device memory), keys uint64 [batch], sigma and rho float32 [batch], scale float32 [groups]
+ * and factors float32 [n_factors] (any device-addressable memory, pinned host memory included).  Every element of the outputs is
+ * written; no atomics, no workspace; nothing is synchronised; float sums run in a fixed order, so a group's outputs depend neither on
+ * batch, nor on its position in it, nor on the run, nor on the alignment of the bases, nor on whether llr is written.
+ * Nothing is launched on AFT_ERR_ARG (what aft_link_mrc_f32 refuses; batch not a multiple of branches * 2) and AFT_ERR_SHAPE (branches
+ * outside 1 .. AFT_LINK_MAX_BRANCHES; a pairing other than the two below; what aft_link_errors_f32 refuses). */
+#define AFT_LINK_PAIR_TIME 0
+#define AFT_LINK_PAIR_FREQUENCY 1
+int aft_link_alamouti_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys,
+                          const float *sigma, const float *rho /* [batch] */, const float *scale /* [groups] */,
+                          const float *factors, int n_factors, int branches, int pairing,
+                          int32_t *counts /* [groups][2] */, float *loss /* [groups][n_factors] */,
+                          float *llr /* [groups,S,T,m] or NULL */, int batch, void *stream);
+
 /* ---- training path of the encoder ---- */
 
 /* Gradients of one nn.TransformerEncoderLayer: same fields and shapes as aft_layer_weights,
