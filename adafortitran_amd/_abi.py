@@ -65,6 +65,7 @@ AFT_LINK_LDPC_Z, AFT_LINK_LDPC_MAX_EDGES = 64, 160
 AFT_LINK_MAX_BRANCHES = 8
 AFT_LINK_MAX_STREAMS = 2
 AFT_LINK_PAIR_TIME, AFT_LINK_PAIR_FREQUENCY = 0, 1
+AFT_LINK_MAX_SUBBANDS = 1024
 AFT_LINK_HARQ_MAX_ROUNDS, AFT_LINK_HARQ_COUNTS = 4, 7
 
 
@@ -230,6 +231,7 @@ SIGNATURES = {
     "aft_link_sm_f32": (C.c_int, [C.POINTER(AftLink), vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]),
     "aft_link_joint_f32": (C.c_int, [C.POINTER(AftLink), vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]),
     "aft_link_alamouti_f32": (C.c_int, [C.POINTER(AftLink), vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]),
+    "aft_link_precoded_f32": (C.c_int, [C.POINTER(AftLink), vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp]),
     # training path
     "aft_encoder_tape_bytes": (C.c_size_t, [cfgp, C.c_int]),
     "aft_encoder_train_scratch_bytes": (C.c_size_t, [cfgp, C.c_int]),

@@ -422,4 +422,24 @@ int aft_link_alamouti_f32(const aft_link *link, const float *ideal, const float 
     return e == hipSuccess ? AFT_OK : hip_fail("link_alamouti", e);
 }
 
+// Every refusal of this entry point is AFT_ERR_ARG, the struct's included: check_front with one branch -- the group of this link is
+// branches * 2 frames --, then the branches, the batch against the group and the subbands against the grid
+int aft_link_precoded_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys, const float *sigma,
+                          const float *rho, const float *scale, const float *factors, int n_factors, int branches, int subband,
+                          int32_t *counts, float *loss, float *llr, int32_t *pmi, int batch, void *stream) {
+    const char *who = "link precoded";
+    if (check_front(who, link, ideal, est, keys, {sigma, rho, scale, factors, counts, loss, pmi},
+                    "sigma, rho, scale, factors, counts, loss, pmi and llr", llr, batch, n_factors, 1) != AFT_OK)
+        return AFT_ERR_ARG;
+    if (!within(who, "branches", branches, 1, AFT_LINK_MAX_BRANCHES)) return AFT_ERR_ARG;
+    AFT_REQUIRE(batch % (branches * 2) == 0, "%s: batch = %d is not a multiple of branches * 2 = %d * 2", who, batch, branches);
+    if (!within(who, "subband", subband, 1, link->num_scs)) return AFT_ERR_ARG;
+    const int n_sub = (link->num_scs - 1) / subband + 1;
+    AFT_REQUIRE(n_sub <= AFT_LINK_MAX_SUBBANDS, "%s: subband = %d makes %d subbands of the %d subcarriers, more than %d", who, subband,
+                n_sub, link->num_scs, AFT_LINK_MAX_SUBBANDS);
+    hipError_t e = launch_link_precoded(*link, ideal, est, keys, sigma, rho, scale, factors, n_factors, branches, subband, counts, loss,
+                                        llr, pmi, batch, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? AFT_OK : hip_fail("link_precoded", e);
+}
+
 }  // extern "C"

@@ -422,6 +422,13 @@ hipError_t launch_link2(bool joint, const aft_link &link, const float *ideal, co
 hipError_t launch_link_alamouti(const aft_link &link, const float *ideal, const float *est, const unsigned long long *keys,
                                 const float *sigma, const float *rho, const float *scale, const float *factors, int n_factors,
                                 int branches, int pairing, int32_t *counts, float *loss, float *llr, int batch, hipStream_t st);
+// closed-loop precoding on the same link (k_linkprecode.hip): a codebook precoder per subband of `subband` subcarriers, chosen from
+// the estimates; everything has passed aft_link_precoded_f32's checks; one workgroup per group of branches * 2 frames, batch a
+// multiple of it; llr may be NULL, pmi [groups][ceil(S / subband)] not
+hipError_t launch_link_precoded(const aft_link &link, const float *ideal, const float *est, const unsigned long long *keys,
+                                const float *sigma, const float *rho, const float *scale, const float *factors, int n_factors,
+                                int branches, int subband, int32_t *counts, float *loss, float *llr, int32_t *pmi, int batch,
+                                hipStream_t st);
 hipError_t launch_mse(const float *est, const float *ref, double *sum_sq, long long n_complex, hipStream_t st);
 hipError_t launch_fill_lds(float value, hipStream_t st);   // test hook: every CU's LDS filled with `value`
 hipError_t launch_peek_lds(float *out, int workgroups, int n, hipStream_t st);   // ... and what a kernel finds in its LDS at start

@@ -4,7 +4,9 @@
 // max-log LLRs, the softplus step of the loss, the LLR store, the reduction of a workgroup's sums and, on the host, a launch's
 // arguments and its dispatch on the modulation order; and what two-stream detection (k_linksm.hip) adds to them: the two-stream
 // received sample, the Gram / matched sums, the adjugate detector with its LLR scale and the joint max-log demapper; and what transmit
-// diversity (k_linkalamouti.hip) adds: a line's k-th data element, the Alamouti combiner's step and the store of one element's LLRs.
+// diversity (k_linkalamouti.hip) adds: a line's k-th data element, the Alamouti combiner's step and the store of one element's LLRs;
+// and what closed-loop precoding (k_linkprecode.hip) adds: the exact product with a codebook entry, a subband's selection sum and its
+// decision, and the combiner's step on the effective estimate.
 // adafortitran_amd/linksim.py holds the definitions.
 #pragma once
 
@@ -294,6 +296,43 @@ __device__ __forceinline__ void link_alamouti_accumulate(LinkBranch &ma, LinkBra
     mb.p = fmaf(rho, link_norm(e0b), fmaf(rho, link_norm(e1a), mb.p));
 }
 
+// ---- closed-loop precoding: a codebook precoder per subband (k_linkprecode.hip; linksim.py "the closed-loop link") ----
+
+// q_i z for the codebook q_0 .. q_3 = 1, -1, j, -j: a swap and negations, exact
+__device__ __forceinline__ float2 link_mul_q(int i, float2 z) {
+    const float2 t = (i & 2) ? make_float2(-z.y, z.x) : z;      // j z
+    return (i & 1) ? make_float2(-t.x, -t.y) : t;
+}
+
+// One (element, antenna) term of a subband's sum g += rho conj(E_r0) E_r1: the product is link_sm_accumulate's g01 chain, and it
+// enters by one fused multiply-add per component
+__device__ __forceinline__ void link_pmi_accumulate(float &gr, float &gi, float rho, float2 e0, float2 e1) {
+    gr = fmaf(rho, fmaf(e0.x, e1.x, e0.y * e1.y), gr);
+    gi = fmaf(rho, fmaf(e0.x, e1.y, -(e0.y * e1.x)), gi);
+}
+
+// The precoder of a subband from its sum g: the LOWEST index i that attains the maximum of v_i = Re(q_i g) = (Re g, -Re g, -Im g,
+// Im g); g = 0 gives 0
+__device__ __forceinline__ int link_pmi(float gr, float gi) {
+    const float v[4] = {gr, -gr, -gi, gi};
+    int best = 0;
+    float top = v[0];
+#pragma unroll
+    for (int i = 1; i < 4; ++i)
+        if (v[i] > top) { top = v[i]; best = i; }
+    return best;
+}
+
+// One antenna's share of the combiner's sums under the precoder q: with the effective estimate e = E_r0 + qE_r1 (qe1 = q E_r1 is
+// exact, the sum is one rounding per component), c += rho y conj(e) and p += rho |e|^2: link_branch's chain per term, link_combine's
+// fused multiply-add per sum.  With E_r1 = 0 it is link_combine of link_branch on the frame (r, 0).
+__device__ __forceinline__ void link_precoded_accumulate(LinkBranch &m, float rho, const LinkSample &y, float2 e0, float2 qe1) {
+#pragma clang fp contract(off)
+    const float2 e = make_float2(e0.x + qe1.x, e0.y + qe1.y);
+    const LinkTerm t = link_matched(y, e);
+    link_combine(m, rho, LinkBranch{t.r, t.i, link_norm(e)});
+}
+
 // ---- the soft half: max-log LLRs and the loss the achievable rate is read from (linksim.py "the soft link") ----
 
 constexpr int kMaxFactors = 8;
@@ -416,7 +455,7 @@ inline int link_llr_element_store_bytes(const float *llr, int m) {
     return at % 16 == 0 && m % 4 == 0 ? 16 : at % 8 == 0 ? 8 : 4;
 }
 
-// ---- a launch's arguments and its dispatch on the modulation order (k_link.hip, k_linksm.hip, k_linkalamouti.hip) ----
+// ---- a launch's arguments and its dispatch on the modulation order (k_link.hip, k_linksm.hip, k_linkalamouti.hip, k_linkprecode.hip) ----
 
 // the union of what the front end's kernels read and write; a pointer an instantiation does not use is NULL
 struct LinkArgs {

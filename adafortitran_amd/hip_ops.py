@@ -515,6 +515,7 @@ class LinkPlan:
     is the current one."""
     cpu_path = "linksim.link_errors_host"
     pairs = False                                               # True: a group is branches * 2 frames and yields one row (LinkAlamoutiPlan)
+    n_sub = None                                                # an integer: the launch also writes pmi int32 [rows, n_sub] (LinkPrecodedPlan)
 
     def __init__(self, cfg, device: torch.device) -> None:
         from .linksim import LinkConfig
@@ -551,7 +552,8 @@ class LinkPlan:
         width, ``(branches,)`` or ``(branches, streams)``, passed to ``entry`` as it stands; ``per_group`` names the float32 operands
         with one value per group, in the entry point's order.  Returns ``(counts, loss, llr)`` for ``groups * streams`` rows.
         ``LinkAlamoutiPlan`` sets ``self.pairs``: its group is ``branches * 2`` frames that yield ONE row, and ``self.group`` is
-        ``(branches, pairing)``."""
+        ``(branches, pairing)``.  ``LinkPrecodedPlan`` sets ``self.pairs`` and ``self.n_sub``: ``self.group`` is ``(branches,
+        subband)``, the entry point takes ``pmi int32 [rows, n_sub]`` behind ``llr``, and ``(counts, loss, llr, pmi)`` is returned."""
         lib = lib or _lib.load()
         batch, ideal, est, keys, sigma = self._checked(ideal, est, keys, sigma)
         pairs = self.pairs
@@ -567,11 +569,12 @@ class LinkPlan:
         counts = torch.empty((rows, 2), dtype=torch.int32, device=self.device)                  # the kernel writes every element
         loss = torch.empty((rows, factors.numel()), dtype=torch.float32, device=self.device)
         llr = torch.empty((rows, *self.grid, self.cfg.bits_per_symbol), dtype=torch.float32, device=self.device) if want_llr else None
+        pmi = () if self.n_sub is None else (torch.empty((rows, self.n_sub), dtype=torch.int32, device=self.device),)
         _lib.check(getattr(lib, entry)(C.byref(self.link), ideal.data_ptr(), est.data_ptr(), keys.data_ptr(), sigma.data_ptr(),
                                        rho.data_ptr(), *(t.data_ptr() for t in per_group), factors.data_ptr(), factors.numel(),
-                                       *self.group, counts.data_ptr(), loss.data_ptr(), _ptr(llr), batch,
+                                       *self.group, counts.data_ptr(), loss.data_ptr(), _ptr(llr), *(t.data_ptr() for t in pmi), batch,
                                        _lib.current_stream_ptr(self.device)), lib)
-        return counts, loss, llr
+        return (counts, loss, llr, *pmi)
 
     def __call__(self, ideal: torch.Tensor, est: torch.Tensor, keys: torch.Tensor, sigma: torch.Tensor, lib=None) -> torch.Tensor:
         lib = lib or _lib.load()
@@ -687,6 +690,36 @@ class LinkAlamoutiPlan(LinkPlan):
     def __call__(self, ideal: torch.Tensor, est: torch.Tensor, keys: torch.Tensor, sigma: torch.Tensor, rho: torch.Tensor,
                  scale: torch.Tensor, factors: torch.Tensor, want_llr: bool = False, lib=None):
         return self._grouped("aft_link_alamouti_f32", ideal, est, keys, sigma, rho, [("scale", scale)], factors, want_llr, lib)
+
+
+class LinkPrecodedPlan(LinkPlan):
+    """Closed-loop rank-1 precoding on ``LinkPlan``'s link: two transmit antennas send ONE stream co-phased by a codebook precoder
+    ``(1, q)``, ``q`` one of ``1, -1, j, -j``, which the receiver picks per subband of ``subband`` subcarriers from the estimates, and
+    ``branches`` receive antennas combine (``linksim``: "the closed-loop link"); frame ``g 2R + r 2 + s`` of a batch is the pair
+    (receive antenna ``r``, transmit antenna ``s``) of group ``g``.  ``plan(ideal, est, keys, sigma, rho, scale, factors,
+    want_llr=False)`` -> ``(counts int32 [G, 2], loss float32 [G, K], llr float32 [G, S, T, m] or None, pmi int32 [G, n_sub])`` for the
+    ``G = batch / (2 branches)`` groups on the plan's device, ``n_sub = ceil(S / subband)``: four ``torch.empty`` at the most, one
+    ``ctypes`` call, one launch (``aft_link_precoded_f32``) on the current stream, no synchronisation.  ``rho`` (float32, ``batch``
+    values) and ``scale`` (float32, ``G`` values: the leaders') are ``linksim.precoding_weights``'; they and ``factors`` live where
+    ``keys`` and ``sigma`` may.  Everything else as ``LinkMrcPlan``."""
+    cpu_path = "linksim.link_precoded_host"
+    pairs = True
+
+    def __init__(self, cfg, device: torch.device, branches: int, subband: int) -> None:
+        super().__init__(cfg, device)
+        if isinstance(branches, bool) or not isinstance(branches, int) or not 1 <= branches <= _abi.AFT_LINK_MAX_BRANCHES:
+            raise ValueError(f"branches = {branches!r}: an integer in 1 .. {_abi.AFT_LINK_MAX_BRANCHES}")
+        S = self.grid[0]
+        if isinstance(subband, bool) or not isinstance(subband, int) or not 1 <= subband <= S:
+            raise ValueError(f"subband = {subband!r}: an integer in 1 .. {S} subcarriers")
+        self.n_sub = -(-S // subband)
+        if self.n_sub > _abi.AFT_LINK_MAX_SUBBANDS:
+            raise ValueError(f"subband = {subband} makes {self.n_sub} subbands of the {S} subcarriers, more than {_abi.AFT_LINK_MAX_SUBBANDS}")
+        self.branches, self.subband, self.group = branches, subband, (branches, subband)
+
+    def __call__(self, ideal: torch.Tensor, est: torch.Tensor, keys: torch.Tensor, sigma: torch.Tensor, rho: torch.Tensor,
+                 scale: torch.Tensor, factors: torch.Tensor, want_llr: bool = False, lib=None):
+        return self._grouped("aft_link_precoded_f32", ideal, est, keys, sigma, rho, [("scale", scale)], factors, want_llr, lib)
 
 
 class _DecoderPlan:

@@ -201,7 +201,50 @@ which assumes the channel equal over a pair.  What is measured is the cross-talk
 errors and by antenna correlation; correlation comes from the simulator, ``ChannelSimConfig(antennas=(R, 2), ...)``, whose groups are
 these ``2 R`` frames.  The SNR is per transmit antenna, as on the spatial-multiplexing link: a comparison at equal total power
 evaluates this link 3.01 dB lower.  It does not model joint detection of the two symbols of a pair, more than two transmit antennas,
-precoding or antenna selection; HARQ is not covered (``HarqAccumulator`` has no ``tx_diversity``).
+or antenna selection; HARQ is not covered (``HarqAccumulator`` has no ``tx_diversity``).  The same two antennas co-phased by a
+precoder the receiver feeds back are "the closed-loop link" below (``precoding_subband=``).
+
+The closed-loop link.  The fourth standard two-antenna mode is the only one in which the channel estimate also acts at the
+TRANSMITTER: in closed-loop rank-1 precoding the receiver picks a precoder from a small codebook using its estimates and reports the
+index, a precoding matrix indicator (PMI), per subband; the two transmit antennas then send one stream co-phased by that precoder.  A
+poor estimate hurts twice there: it picks the wrong precoder, and beamforming gain turns into loss; it then also mismatches the
+combiner.  ``link_precoded_host`` (float64), ``precoding_subbands``, ``precoding_pmi_host``, ``precoding_weights``,
+``aft_link_precoded_f32`` (csrc/k_linkprecode.hip, through ``hip_ops.LinkPrecodedPlan``) and the ``precoding_subband=`` argument of
+the accumulators and of the three sweeps of ``evaluation`` are that link.  A batch of ``n`` frames with ``R = branches``,
+``1 <= R <= 8`` and ``n % (2 R) == 0`` is ``G = n / (2 R)`` groups; frame ``g 2R + r 2 + s`` is the pair (receive antenna ``r``,
+transmit antenna ``s``) of group ``g`` -- the order of ``streams=2``, of ``tx_diversity=`` and of ``ChannelSimConfig(antennas=(R, 2))``
+--; frame ``(0, 0)`` is the LEADER.  ``B = precoding_subband`` with ``1 <= B <= S``::
+
+    subbands   subband b = subcarriers b B .. min(S, (b+1) B) - 1, all T symbols; n_sub = ceil(S / B) (the last may be short; B = S is one
+               wideband PMI).  n_sub <= AFT_LINK_MAX_SUBBANDS = 1024, else refused
+    codebook   q_0 .. q_3 = 1, -1, j, -j; the precoder of index i is (1, q_i): antenna 0 sends x, antenna 1 sends q_i x.  Multiplying by q_i is
+               a swap and negations: exact.  Each antenna sends at unit mean energy, as on the other two-antenna links
+    selection  g_b = sum over the subband's S_b T elements (pilot positions included: the estimate is defined everywhere) and over r of
+               rho_r conj(E_r0) E_r1;   v = (Re g_b, -Re g_b, -Im g_b, Im g_b) = Re(q_i g_b);   pmi_b = the LOWEST i that attains max v
+               (g_b = 0 gives 0).  rho_r = the weights of the frames (r, 0), as alamouti_weights forms them (precoding_weights)
+    sent       every data element sends w, gi, gq, x as the single link does, from stream 5 of the LEADER's key: one transmission per group
+    received   y_r = H_r0 x + H_r1 (q x) + sigma_r sqrt(-ln u1) exp(j 2 pi u2)     q = q_pmi of the element's subband; u1, u2 from streams 6, 7 of the
+               key of frame (r, 0), sigma_r that frame's; keys / sigma / rho of frames (r, 1) are not read
+               (evaluated as H_r0 x + (q H_r1) x -- device: link_sample2 on (H_r0, q H_r1) with x1 = x -- so that the bits do not
+               depend on a common turn of H_r1 and E_r1 by a power of j: q H_r1 is then the same number)
+    effective  e_r = E_r0 + q E_r1       one rounding per component on the device
+    combiner   c = sum_r rho_r y_r conj(e_r),  p = sum_r rho_r |e_r|^2     link_branch's chain per term, link_combine's fused multiply-add per sum,
+               increasing r, starting value as link_mrc_kernel's
+    hard/soft  the single link's decision, bit and symbol errors, mu_k, Delta_j, Lambda_j = scale Delta_j (leader's scale) and loss_f on (c, p);
+               pilots carry 0
+    outputs    counts int [G, 2], loss [G, K], llr [G, S, T, m] (the diversity link's shapes), and pmi int32 [G, n_sub]
+
+Reaches for the comparison of a float32 evaluation follow the diversity link's: ``reach(y_r) = |H_r0||x| + |H_r1||x| + |noise|``,
+``reach(e_r) = |E_r0| + |E_r1|``, ``reach(c) = sum rho reach(y_r) reach(e_r)`` and ``p_reach = sum rho reach(e_r)^2``: ``p`` is no longer
+a sum of exact non-negative inputs, because ``e_r`` cancels.  The selection gets its own margin: with ``Gr_b = sum rho_r |E_r0||E_r1|``
+over the subband, subband ``b`` is PMI-FLAGGED at ``tau_pmi`` when (largest ``v`` - second largest ``v``) ``<= tau_pmi Gr_b``; an
+evaluation whose ``g_b`` is within ``tau_pmi Gr_b / 2`` per component can choose differently only at flagged subbands.  With an
+unheard second antenna (``H_r1 = E_r1 = 0``) every PMI is 0 and the link is the diversity link on the frames ``(r, 0)``.  What this
+models: instantaneous, error-free feedback of one PMI per subband, chosen from the same estimates the combiner uses, over all T symbols
+(non-causal under Doppler); the total power is twice the single link's, so a comparison at equal total power evaluates this link
+3.01 dB lower, as for Alamouti.  Open loop needs no feedback and has no array gain; closed loop has array gain exactly as far as the
+estimate is good and the subband is narrower than the coherence bandwidth.  It does not model feedback delay or quantised CQI, rank
+adaptation and rank-2 codebooks, more than two transmit antennas, or HARQ (``HarqAccumulator`` gets no keyword).
 
 The coded link.  The rate says how much information the LLRs carry; a link-level user wants the same with a decoder in the loop: the
 block-error rate of coded blocks and the throughput that follows from it.  ``CodeConfig``, ``link_encode_host`` / ``link_decode_host``
@@ -896,6 +939,119 @@ def link_alamouti_host(cfg: LinkConfig, keys, ideal, est, sigma, rho, scale, bra
     return ((hard,) if tau is None else hard[:1]) + soft[:2] + (() if tau is None else hard[1:]) + soft[2:]
 
 
+# ---- the closed-loop link (module docstring, "The closed-loop link"): float64 NumPy, mirrored by csrc/k_linkprecode.hip ----
+
+CODEBOOK = (1.0 + 0.0j, -1.0 + 0.0j, 1.0j, -1.0j)           # q_0 .. q_3; the precoder of index i is (1, q_i)
+MAX_SUBBANDS = _abi.AFT_LINK_MAX_SUBBANDS
+
+#: the weights of the closed-loop link: the same frames (r, 0) of the same groups of 2 R frames
+precoding_weights = alamouti_weights
+
+
+def _subband(cfg: LinkConfig, subband) -> int:
+    """The subband width in subcarriers, checked against the grid."""
+    S = cfg.sim.ofdm[0]
+    if isinstance(subband, bool) or not isinstance(subband, (int, np.integer)) or not 1 <= int(subband) <= S:
+        raise ValueError(f"precoding_subband = {subband!r}: an integer in 1 .. {S} subcarriers")
+    if -(-S // int(subband)) > MAX_SUBBANDS:
+        raise ValueError(f"precoding_subband = {subband} makes {-(-S // int(subband))} subbands of the {S} subcarriers, more than {MAX_SUBBANDS}")
+    return int(subband)
+
+
+def precoding_subbands(cfg: LinkConfig, subband: int) -> Tuple[np.ndarray, int]:
+    """The subbands of a grid: ``(index int64 [S], n_sub)``, ``index[s] = s // subband`` the subband of subcarrier ``s`` and
+    ``n_sub = ceil(S / subband)``; the last subband is short where ``subband`` does not divide ``S``."""
+    B, S = _subband(cfg, subband), cfg.sim.ofdm[0]
+    return np.arange(S, dtype=np.int64) // B, -(-S // B)
+
+
+def _mul_q(i, z: np.ndarray) -> np.ndarray:
+    """``q_i z`` for the codebook indices ``i`` (broadcast against ``z``): a swap and negations, exact."""
+    i = np.broadcast_to(np.asarray(i, dtype=np.int64), z.shape)
+    turn, neg = (i & 2) != 0, (i & 1) != 0
+    re, im = np.where(turn, -z.imag, z.real), np.where(turn, z.real, z.imag)
+    out = np.empty(z.shape, dtype=np.complex128)
+    out.real, out.imag = np.where(neg, -re, re), np.where(neg, -im, im)
+    return out
+
+
+def _rho_of(rho, n: int) -> np.ndarray:
+    rho = np.asarray(rho, dtype=np.float32).astype(np.float64).reshape(-1)
+    if rho.shape != (n,):
+        raise ValueError(f"rho must hold one value per frame ({n}), got {rho.size}")
+    return rho
+
+
+def precoding_pmi_host(cfg: LinkConfig, est, rho, branches, subband, tau_pmi: Optional[float] = None):
+    """The selection of the closed-loop link (module docstring) in float64: ``est`` complex ``[n, S, T]`` and ``rho`` ``[n]`` in the
+    layout ``g 2R + r 2 + s`` -> ``pmi int32 [G, n_sub]``, per subband the lowest index that attains the maximum of ``Re(q_i g_b)``.
+    With ``tau_pmi``: ``(pmi, flags bool [G, n_sub])``, the PMI-flagged subbands."""
+    R = _branches(branches)
+    index, n_sub = precoding_subbands(cfg, subband)
+    S, T = cfg.sim.ofdm
+    E = np.asarray(est).astype(np.complex128)
+    if E.ndim != 3 or E.shape[1:] != (S, T):
+        raise ValueError(f"Expected est of shape (n, {S}, {T}), got {E.shape}")
+    n = E.shape[0]
+    G, W = _tx_grouped(n, R), 2 * R
+    rho = _rho_of(rho, n)
+    gr, gi, gross = np.zeros((G, S)), np.zeros((G, S)), np.zeros((G, S))        # per subcarrier: the sums over t and r
+    for r in range(R):
+        E0, E1, w = E[2 * r::W], E[2 * r + 1::W], rho[2 * r::W, None]
+        gr += w * (E0.real * E1.real + E0.imag * E1.imag).sum(axis=2)             # conj(E_r0) E_r1
+        gi += w * (E0.real * E1.imag - E0.imag * E1.real).sum(axis=2)
+        gross += w * (np.abs(E0) * np.abs(E1)).sum(axis=2)
+    starts = np.flatnonzero(np.diff(index, prepend=-1))
+    gr, gi, gross = (np.add.reduceat(v, starts, axis=1) for v in (gr, gi, gross))
+    v = np.stack([gr, -gr, -gi, gi], axis=-1)                                     # Re(q_i g_b)
+    pmi = v.argmax(axis=-1).astype(np.int32)                                      # the first index that attains the maximum
+    if tau_pmi is None:
+        return pmi
+    top = np.sort(v, axis=-1)
+    return pmi, (top[..., 3] - top[..., 2]) <= tau_pmi * gross
+
+
+def link_precoded_host(cfg: LinkConfig, keys, ideal, est, sigma, rho, scale, branches, subband, factors=(1.0,),
+                       tau: Optional[float] = None, e_lambda: Optional[float] = None, pmi=None):
+    """The closed-loop link (module docstring) in float64: ``keys`` / ``ideal`` / ``est`` / ``sigma`` as ``link_errors_host``'s for the
+    ``n`` frames in the layout ``g 2R + r 2 + s``, ``rho`` ``[n]`` and ``scale`` ``[G]`` taken as the float32 numbers they are
+    (``precoding_weights``), ``G = n / (2 branches)`` -> ``link_alamouti_host``'s tuple with ``pmi`` appended: ``(counts int64 [G, 2],
+    loss float64 [G, K], llr float64 [G, S, T, m], pmi int32 [G, n_sub])``; with ``tau`` the wrong-bit map ``[G, S, T]`` and the flags
+    ``[G, S, T, 2]`` follow the LLRs, with ``e_lambda`` then ``loss_lo``, ``loss_hi`` and ``q``, on the combiner's ``c``, ``p`` and
+    reaches; ``pmi`` stays last.  A given ``pmi`` ``[G, n_sub]`` (values 0 .. 3) replaces the selection.  Needs no library."""
+    R = _branches(branches)
+    index, n_sub = precoding_subbands(cfg, subband)
+    keys, H, E, sigma = _checked(cfg, keys, ideal, est, sigma)
+    n, (S, T) = len(keys), cfg.sim.ofdm
+    G, W = _tx_grouped(n, R), 2 * R
+    rho = _rho_of(rho, n)
+    if np.size(scale) != G:
+        raise ValueError(f"scale must hold one value per group ({G}), got {np.size(scale)}")
+    if pmi is None:
+        pmi = precoding_pmi_host(cfg, E, rho, R, subband)
+    else:
+        pmi = np.asarray(pmi)
+        if pmi.shape != (G, n_sub) or pmi.dtype.kind not in "iu" or pmi.min() < 0 or pmi.max() > 3:
+            raise ValueError(f"pmi must hold integers in 0 .. 3 of shape ({G}, {n_sub}), got {pmi.dtype} {pmi.shape}")
+        pmi = pmi.astype(np.int32)
+    at = pmi[:, index][:, :, None]                                               # [G, S, 1]: every subcarrier's index
+    gi, gq, x = _sent(cfg, keys[::W])                                             # one transmission per group: the leader's key
+    c = p = reach = p_reach = 0.0
+    for r in range(R):                                                           # in increasing r, starting from 0
+        sl = slice(2 * r, None, W)                                               # the frames (r, 0); (r, 1) follow them
+        H0, H1, E0, E1 = H[sl], H[2 * r + 1::W], E[sl], E[2 * r + 1::W]
+        noise = _noise(cfg, keys[sl], sigma[sl])
+        y = (H0 * x + _mul_q(at, H1) * x) + noise                                # with H_r1 = 0: _branch's sample
+        e = E0 + _mul_q(at, E1)
+        ry, re = (np.abs(H0) + np.abs(H1)) * np.abs(x) + np.abs(noise), np.abs(E0) + np.abs(E1)
+        w = rho[sl, None, None]
+        c, p = c + w * (y * e.conj()), p + w * (e.real ** 2 + e.imag ** 2)
+        reach, p_reach = reach + w * (ry * re), p_reach + w * (re * re)
+    hard = _hard(cfg, gi, gq, c, p, reach, tau, p_reach)
+    soft = _soft(cfg, gi, gq, c, p, reach, scale, factors, e_lambda, p_reach)
+    return ((hard,) if tau is None else hard[:1]) + soft[:2] + (() if tau is None else hard[1:]) + soft[2:] + (pmi,)
+
+
 # ---- the frame keys with torch ops, for frame numbers that live on the device (no synchronisation) ----
 
 def _s64(v: int) -> int:
@@ -931,10 +1087,12 @@ class _FrameSweep:
     a float64 tensor)`` of the SNR in dB."""
 
     def _open(self, cfg: LinkConfig, device, seed: int, want: str, branches: int = 1, err_var: float = 0.0, factors=(1.0,),
-              streams: int = 1, detector: str = "mmse", tx_diversity: Optional[str] = None) -> None:
+              streams: int = 1, detector: str = "mmse", tx_diversity: Optional[str] = None,
+              precoding_subband: Optional[int] = None) -> None:
         """``want``: which of ``"counts"``, ``"loss"`` and ``"llr"`` ``_measure`` computes.  ``streams=2``: the spatial-multiplexing
         link with ``detector`` in front (``streams=1`` ignores it).  ``tx_diversity``: None, or the pairing of the transmit-diversity
-        link in front (one stream; ``detector`` is ignored)."""
+        link in front (one stream; ``detector`` is ignored).  ``precoding_subband``: None, or the subband width of the closed-loop
+        link in front (one stream, no ``tx_diversity``; ``detector`` is ignored)."""
         if not isinstance(cfg, LinkConfig):
             raise ValueError(f"{type(self).__name__} needs a LinkConfig (got {type(cfg).__name__})")
         self.cfg, self.seed, self._want = cfg, int(seed), want
@@ -946,8 +1104,15 @@ class _FrameSweep:
             _pairing(tx_diversity)
             if self.streams != 1:
                 raise ValueError(f"tx_diversity = {tx_diversity!r} sends one stream from two antennas: streams must be 1 (got {self.streams})")
+        self.precoding_subband = None
+        if precoding_subband is not None:
+            if self.streams != 1 or tx_diversity is not None:
+                raise ValueError(f"precoding_subband = {precoding_subband!r} sends one precoded stream from two antennas: streams must "
+                                 f"be 1 (got {self.streams}) and tx_diversity None (got {tx_diversity!r})")
+            self.precoding_subband = _subband(cfg, precoding_subband)
+        self._pairs = tx_diversity is not None or self.precoding_subband is not None      # a group is 2 R frames and yields one row
         # frames per group: the branches, times the two transmit antennas or the streams
-        self._width =self.branches * (2 if tx_diversity is not None else self.streams)
+        self._width =self.branches * (2 if self._pairs else self.streams)
         if self.streams > 1:
             _sm_shape(0, self.branches, self.streams)           # one antenna cannot separate two streams
             _detector(detector)                                 # the detector's name: a linear one, or "joint"
@@ -956,7 +1121,9 @@ class _FrameSweep:
         self._plan = None
         if self.device.type == "cuda":
             from . import hip_ops                  # loads the extension: a missing .so raises here, loudly
-            if tx_diversity is not None:           # every measure of the transmit-diversity link comes from the combiner's one launch
+            if self.precoding_subband is not None:  # every measure of the closed-loop link comes from its one launch
+                self._plan = hip_ops.LinkPrecodedPlan(cfg, self.device, self.branches, self.precoding_subband)
+            elif tx_diversity is not None:         # every measure of the transmit-diversity link comes from the combiner's one launch
                 self._plan = hip_ops.LinkAlamoutiPlan(cfg, self.device, self.branches, tx_diversity)
             elif self.streams > 1:                 # every measure of the spatial-multiplexing link comes from the detector's one launch
                 plan = hip_ops.LinkJointPlan if detector == JOINT_DETECTOR else hip_ops.LinkSmPlan
@@ -973,6 +1140,9 @@ class _FrameSweep:
         self._factors_t = None if self._plan is None else torch.from_numpy(self.factors).to(self.device)
         self._of_snr = (_SIGMA_OF_SNR, _SCALE_OF_SNR(self.err_var)) if soft or self._width > 1 else (_SIGMA_OF_SNR,)
         self.frames = 0
+        if self.precoding_subband is not None:     # how often each precoder was chosen, summed on the device
+            self._pmi_counts = torch.zeros(4, dtype=torch.int64, device=self.device)
+            self._pmi_index = torch.arange(4, dtype=torch.int32, device=self.device)
 
     def _stage(self, a: np.ndarray) -> torch.Tensor:
         return torch.from_numpy(a).pin_memory().to(self.device, non_blocking=True)
@@ -1037,12 +1207,14 @@ class _FrameSweep:
         one launch of ``aft_link_sm_f32`` with ``rho`` and ``reg`` formed on the device on a HIP device; with ``detector="joint"``
         ``link_joint_host`` and one launch of ``aft_link_joint_f32``, which has no ``reg``.  With ``tx_diversity`` the groups are the
         ``G`` transmissions of the transmit-diversity link with the leaders' keys: ``link_alamouti_host`` on a CPU device, one launch
-        of ``aft_link_alamouti_f32`` with ``rho`` formed on the device on a HIP device."""
+        of ``aft_link_alamouti_f32`` with ``rho`` formed on the device on a HIP device.  With ``precoding_subband`` the same groups on
+        the closed-loop link: ``link_precoded_host`` or one launch of ``aft_link_precoded_f32``, and one add of the batch's PMIs into
+        the histogram ``pmi_histogram`` reads."""
         ops = self._operands(est, ideal, meta, frame_ids, snr_db, self._of_snr)
         if ops is None:
             return None
         b, H, E, keys, (sigma, *scale) = ops       # scale: the frames' LLR scales, where the measure or the combiner needs them
-        G = _tx_grouped(b, self.branches) if self.tx_diversity is not None else _grouped(b, self.branches, self.streams)
+        G = _tx_grouped(b, self.branches) if self._pairs else _grouped(b, self.branches, self.streams)
         measure = self._measure_host if self._plan is None else self._measure_device
         return (G * self.streams, *measure(G, H, E, keys, sigma, scale))
 
@@ -1050,7 +1222,12 @@ class _FrameSweep:
         """The float64 definitions on NumPy operands: ``(the leaders' keys, counts, loss, llr)`` as host tensors."""
         R, N = self.branches, self.streams
         counts = loss = llr = None
-        if self.tx_diversity is not None:          # G transmissions from two antennas, with the leaders' keys
+        if self.precoding_subband is not None:     # G precoded transmissions from two antennas, with the leaders' keys
+            counts, loss, llr, pmi = link_precoded_host(self.cfg, keys, H, E, sigma, *_weights(scale[0], 2 * R), R,
+                                                        self.precoding_subband, self.factors)
+            self._count_pmi(torch.from_numpy(pmi))
+            sent = keys[::2 * R]
+        elif self.tx_diversity is not None:        # G transmissions from two antennas, with the leaders' keys
             counts, loss, llr = link_alamouti_host(self.cfg, keys, H, E, sigma, *_weights(scale[0], 2 * R), R, self.tx_diversity,
                                                    self.factors)
             sent = keys[::2 * R]
@@ -1082,9 +1259,11 @@ class _FrameSweep:
         """The plan's one launch on device operands: ``(the leaders' keys, counts, loss, llr)`` on the device."""
         R, N, want_llr = self.branches, self.streams, self._want == "llr"
         counts = loss = llr = None
-        if self.tx_diversity is not None:          # the weights of the frames (r, 0) against the leader's, over the 2 R frames of a group
+        if self._pairs:                            # the weights of the frames (r, 0) against the leader's, over the 2 R frames of a group
             rho, lead = self._device_weights(scale[0], 2 * R)
-            counts, loss, llr = self._launch(H, E, keys, sigma, rho, lead, self._factors_t, want_llr=want_llr)
+            counts, loss, llr, *pmi = self._launch(H, E, keys, sigma, rho, lead, self._factors_t, want_llr=want_llr)
+            if pmi:                                # the closed-loop link's fourth output
+                self._count_pmi(pmi[0])
             return keys[::2 * R].contiguous(), counts, loss, llr
         if N > 1:                                  # the detectors differ in one operand: the joint one has no regulariser
             rho, lead = self._device_weights(scale[0], R * N)
@@ -1102,6 +1281,16 @@ class _FrameSweep:
         else:
             loss, llr = self._launch(H, E, keys, sigma, scale[0], self._factors_t, want_llr=want_llr)
         return keys[::R].contiguous(), counts, loss, llr
+
+    def _count_pmi(self, pmi: torch.Tensor) -> None:
+        """A batch's PMIs ``[G, n_sub]`` into the histogram: one comparison against 0 .. 3, one sum, one add; nothing synchronises."""
+        self._pmi_counts += (pmi.reshape(-1, 1) == self._pmi_index).sum(dim=0)
+
+    def pmi_histogram(self, group=None) -> list:
+        """How often each of the four precoders was chosen over the sweep, all ranks: four integers; one read, as the result's."""
+        if self.precoding_subband is None:
+            raise ValueError("pmi_histogram needs precoding_subband: no other link chooses a precoder")
+        return [int(v) for v in self._all_ranks(self._pmi_counts.to(torch.float64), group)]
 
     @staticmethod
     def _total(per_group: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
@@ -1168,11 +1357,19 @@ class LinkAccumulator(_FrameSweep):
     CPU device by ``link_alamouti_host``) with ``rho`` formed on the device without a synchronisation.  ``streams`` must be 1
     (``ValueError`` otherwise), ``detector`` is ignored, a batch that is no multiple of ``2 R`` raises ``ValueError``; a batch yields
     ``G`` rows with the leaders' keys and ``frames`` counts them.  The SNR is per transmit antenna.  ``tx_diversity=None`` is today's
-    path, launch for launch."""
+    path, launch for launch.
+
+    ``precoding_subband=B`` (module docstring, "the closed-loop link"; the same keyword on the same four accumulators): the same
+    ``2 R`` frames per group, the two transmit antennas sending ONE stream co-phased by a codebook precoder that the receiver picks
+    per subband of ``B`` subcarriers from the estimate, by one launch of ``aft_link_precoded_f32`` (on a CPU device by
+    ``link_precoded_host``).  ``streams`` must be 1 and ``tx_diversity`` None (``ValueError`` otherwise), ``detector`` is ignored; rows,
+    keys, ``frames`` and the SNR as under ``tx_diversity``.  ``pmi_histogram()`` reads how often each of the four precoders was
+    chosen, summed on the device by one add per batch.  ``precoding_subband=None`` is today's path, launch for launch."""
 
     def __init__(self, cfg: LinkConfig, device, seed: int = 0, branches: int = 1, streams: int = 1, detector: str = "mmse", *,
-                 tx_diversity: Optional[str] = None) -> None:
-        self._open(cfg, device, seed, "counts", branches, streams=streams, detector=detector, tx_diversity=tx_diversity)
+                 tx_diversity: Optional[str] = None, precoding_subband: Optional[int] = None) -> None:
+        self._open(cfg, device, seed, "counts", branches, streams=streams, detector=detector, tx_diversity=tx_diversity,
+                   precoding_subband=precoding_subband)
         self.errors = torch.zeros(2, dtype=torch.int64, device=self.device)     # bit errors, symbol errors
 
     def update(self, est: Optional[torch.Tensor], ideal: torch.Tensor, meta: Optional[tuple] = None, *, frame_ids=None,
@@ -1213,8 +1410,9 @@ class RateAccumulator(_FrameSweep):
     ``tx_diversity`` as ``LinkAccumulator``'s: with ``tx_diversity`` the rate is per transmission of the two antennas."""
 
     def __init__(self, cfg: LinkConfig, device, seed: int = 0, factors=(1.0,), err_var: float = 0.0, branches: int = 1,
-                 streams: int = 1, detector: str = "mmse", *, tx_diversity: Optional[str] = None) -> None:
-        self._open(cfg, device, seed, "loss", branches, err_var, factors, streams, detector, tx_diversity)
+                 streams: int = 1, detector: str = "mmse", *, tx_diversity: Optional[str] = None,
+                 precoding_subband: Optional[int] = None) -> None:
+        self._open(cfg, device, seed, "loss", branches, err_var, factors, streams, detector, tx_diversity, precoding_subband)
         self.loss = torch.zeros(len(self.factors), dtype=torch.float64, device=self.device)
 
     def update(self, est: Optional[torch.Tensor], ideal: torch.Tensor, meta: Optional[tuple] = None, *, frame_ids=None,
@@ -1459,10 +1657,11 @@ class BlockErrorAccumulator(_FrameSweep):
     _config, _needs, _host_decoder, _decoder_plan, _columns = CodeConfig, "a CodeConfig", staticmethod(link_decode_host), "LinkDecodePlan", 2
 
     def __init__(self, code, device, seed: int = 0, err_var: float = 0.0, branches: int = 1, streams: int = 1,
-                 detector: str = "mmse", *, tx_diversity: Optional[str] = None) -> None:
+                 detector: str = "mmse", *, tx_diversity: Optional[str] = None, precoding_subband: Optional[int] = None) -> None:
         if not isinstance(code, self._config):
             raise ValueError(f"{type(self).__name__} needs {self._needs} (got {type(code).__name__})")
-        self._open(code.link, device, seed, "llr", branches, err_var, streams=streams, detector=detector, tx_diversity=tx_diversity)
+        self._open(code.link, device, seed, "llr", branches, err_var, streams=streams, detector=detector, tx_diversity=tx_diversity,
+                   precoding_subband=precoding_subband)
         self.code = code
         self.errors = torch.zeros(self._columns, dtype=torch.int64, device=self.device)    # information-bit errors, block errors, ...
         self._decode = None
@@ -1968,8 +2167,8 @@ class HarqAccumulator(BlockErrorAccumulator):
     _config, _needs, _host_decoder, _decoder_plan, _columns = HarqConfig, "a HarqConfig", staticmethod(link_harq_host), "LinkHarqPlan", HARQ_COUNTS
 
     def __init__(self, code, device, seed: int = 0, err_var: float = 0.0, branches: int = 1) -> None:
-        # no ``streams``: a group's rounds are consecutive LLR frames, which would be the two streams of one group; no ``tx_diversity``:
-        # HARQ over Alamouti pairs is not defined here
+        # no ``streams``: a group's rounds are consecutive LLR frames, which would be the two streams of one group; no ``tx_diversity``
+        # and no ``precoding_subband``: HARQ over Alamouti pairs or precoded transmissions is not defined here
         super().__init__(code, device, seed, err_var, branches)
 
     def update(self, est: Optional[torch.Tensor], ideal: torch.Tensor, meta: Optional[tuple] = None, *, frame_ids=None,

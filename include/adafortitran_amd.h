@@ -686,6 +686,49 @@ int aft_link_alamouti_f32(const aft_link *link, const float *ideal, const float 
                           int32_t *counts /* [groups][2] */, float *loss /* [groups][n_factors] */,
                           float *llr /* [groups,S,T,m] or NULL */, int batch, void *stream);
 
+/* ---- closed-loop precoding: a codebook precoder per subband (adafortitran_amd/linksim.py "the closed-loop link") ----
+ *
+ * Two transmit antennas send ONE stream co-phased by a rank-1 precoder that the receiver picks per subband from its own estimates (the
+ * precoding matrix indicator, PMI), R = branches receive antennas combine, 1 <= R <= AFT_LINK_MAX_BRANCHES: group g of a batch is the
+ * frames g 2 R .. g 2 R + 2 R - 1, frame g 2 R + r 2 + s the pair (receive antenna r, transmit antenna s) -- aft_link_sm_f32's and
+ * aft_link_alamouti_f32's order --, frame (0, 0) the group's leader.  B = subband, 1 <= B <= S.
+ *   subbands    subband b = subcarriers b B .. min(S, (b + 1) B) - 1, all T symbols; n_sub = ceil(S / B) (the last may be short; B = S
+ *               is one wideband PMI); n_sub <= AFT_LINK_MAX_SUBBANDS
+ *   codebook    q_0 .. q_3 = 1, -1, j, -j; the precoder of index i is (1, q_i): antenna 0 sends x, antenna 1 sends q_i x
+ *   selection   g_b = sum over the subband's elements (pilot positions included) and over r of rho_r conj(E_r0) E_r1;
+ *               v = (Re g_b, -Re g_b, -Im g_b, Im g_b) = Re(q_i g_b); pmi_b = the LOWEST i that attains max v (g_b = 0 gives 0);
+ *               rho_r = rho of frame (r, 0).  One team of W threads per subband, W a power of two in 8 .. 256 fixed by S, T and B:
+ *               thread l adds its elements l, l + W, ... in increasing order, within an element the antennas in increasing r, one
+ *               fused multiply-add per component; the team's sums are added by shuffles, then wave by wave
+ *   sent        every data element sends w, gi, gq, x as aft_link_errors_f32's, from stream 5 of the LEADER's key: one transmission
+ *               per group
+ *   received    y_r = H_r0 x + (q H_r1) x + sigma_r sqrt(-ln u1) exp(j 2 pi u2), q = q_pmi of the element's subband (q H_r1 is
+ *               exact), u1 and u2 from streams 6 and 7 of the key of frame (r, 0), sigma_r that frame's (aft_link_sm_f32's sample);
+ *               keys, sigma and rho of frames (r, 1) are not read
+ *   effective   e_r = E_r0 + q E_r1, one rounding per component
+ *   combiner    c = sum_r rho_r y_r conj(e_r), p = sum_r rho_r |e_r|^2; increasing r, one fused multiply-add per term, sums start at -0
+ *   decision, counts, mu_k, Delta_j, Lambda_j = scale Delta_j (the LEADER's scale, one per group) and loss[f] as aft_link_mrc_f32's
+ *               on (c, p); pilots carry 0
+ * Feedback is instantaneous and free of errors: one PMI per subband, from the same estimates the combiner uses.  With H_r1 = E_r1 = 0
+ * every PMI is 0 and the LLRs are aft_link_mrc_f32's on the frames (r, 0), bit for bit; turning H_r1 and E_r1 by a power of j permutes
+ * the PMIs and leaves counts, losses and LLRs as they are, bit for bit.
+ * One launch, one workgroup per group: counts int32 [groups][2], loss float32 [groups][n_factors], pmi int32 [groups][n_sub] (values
+ * 0 .. 3) and, when llr is not NULL, llr float32 [groups, S, T, m] (all device memory) from ideal and est complex64 [batch, S, T]
+ * (device memory), keys uint64 [batch], sigma and rho float32 [batch], scale float32 [groups] and factors float32 [n_factors] (any
+ * device-addressable memory, pinned host memory included).  Every element of the outputs is written; no atomics, no workspace; nothing
+ * is synchronised; float sums run in a fixed order, so a group's outputs depend neither on batch, nor on its position in it, nor on the
+ * run, nor on the alignment of the bases, nor on whether llr is written.
+ * Every refusal is AFT_ERR_ARG and launches nothing: a NULL pointer (llr excepted) or a misaligned one, batch < 1 or not a multiple of
+ * branches * 2, branches outside 1 .. AFT_LINK_MAX_BRANCHES, subband outside 1 .. S, more than AFT_LINK_MAX_SUBBANDS subbands,
+ * n_factors outside 1 .. 8, and what aft_link_errors_f32 refuses of the struct (bits_per_symbol among it). */
+#define AFT_LINK_MAX_SUBBANDS 1024
+int aft_link_precoded_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys,
+                          const float *sigma, const float *rho /* [batch] */, const float *scale /* [groups] */,
+                          const float *factors, int n_factors, int branches, int subband,
+                          int32_t *counts /* [groups][2] */, float *loss /* [groups][n_factors] */,
+                          float *llr /* [groups,S,T,m] or NULL */, int32_t *pmi /* [groups][n_sub], not NULL */, int batch,
+                          void *stream);
+
 /* ---- training path of the encoder ---- */
 
 /* Gradients of one nn.TransformerEncoderLayer: same fields and shapes as aft_layer_weights,
