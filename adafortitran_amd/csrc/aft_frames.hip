@@ -411,6 +411,19 @@ int aft_link_joint_f32(const aft_link *link, const float *ideal, const float *es
     return e == hipSuccess ? AFT_OK : hip_fail("link_joint", e);
 }
 
+// aft_link_sm_f32's checks; stats may be NULL as llr may, and is 4-byte aligned where it is given
+int aft_link_sic_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys, const float *sigma,
+                     const float *rho, const float *scale, const float *reg, const float *factors, int n_factors, int branches,
+                     int streams, int32_t *counts, float *loss, float *llr, int32_t *stats, int batch, void *stream) {
+    const int rc = check_front2("link sic", link, ideal, est, keys, {sigma, rho, scale, reg, factors, counts, loss},
+                                "sigma, rho, scale, reg, factors, counts, loss, llr and stats", llr, batch, n_factors, branches, streams);
+    if (rc != AFT_OK) return rc;
+    AFT_REQUIRE(aligned(4, stats), "link sic: sigma, rho, scale, reg, factors, counts, loss, llr and stats must be 4-byte aligned");
+    hipError_t e = launch_link_sic(*link, ideal, est, keys, sigma, rho, scale, reg, factors, n_factors, branches, counts, loss, llr, stats,
+                                   batch, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? AFT_OK : hip_fail("link_sic", e);
+}
+
 int aft_link_alamouti_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys, const float *sigma,
                           const float *rho, const float *scale, const float *factors, int n_factors, int branches, int pairing,
                           int32_t *counts, float *loss, float *llr, int batch, void *stream) {

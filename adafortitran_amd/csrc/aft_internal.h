@@ -416,6 +416,11 @@ hipError_t launch_link_harq(const aft_link &link, const float *llr, const unsign
 hipError_t launch_link2(bool joint, const aft_link &link, const float *ideal, const float *est, const unsigned long long *keys,
                         const float *sigma, const float *rho, const float *scale, const float *reg, const float *factors, int n_factors,
                         int branches, int32_t *counts, float *loss, float *llr, int batch, hipStream_t st);
+// the same two streams by ordered successive cancellation (k_linksm.hip): everything has passed aft_link_sic_f32's checks, which are
+// aft_link_sm_f32's; llr and stats [groups][3] may be NULL
+hipError_t launch_link_sic(const aft_link &link, const float *ideal, const float *est, const unsigned long long *keys,
+                           const float *sigma, const float *rho, const float *scale, const float *reg, const float *factors, int n_factors,
+                           int branches, int32_t *counts, float *loss, float *llr, int32_t *stats, int batch, hipStream_t st);
 // transmit diversity on the same link (k_linkalamouti.hip): Alamouti pairs over time (pairing AFT_LINK_PAIR_TIME) or frequency;
 // everything has passed aft_link_alamouti_f32's checks; one workgroup per group of branches * 2 frames, batch a multiple of it; llr
 // may be NULL

@@ -1,6 +1,6 @@
 // The two-stream link (include/adafortitran_amd.h "spatial multiplexing", "joint detection"; adafortitran_amd/linksim.py "the
 // spatial-multiplexing link" and "the joint link" are the definitions and the float64 twins): N = 2 streams on R antennas, ONE frame
-// walk, link2_walk, and two detectors in its step 4.  One workgroup per GROUP of 2 R consecutive frames -- frame r 2 + s is the pair
+// walk, link2_walk, and three detectors in its step 4.  One workgroup per GROUP of 2 R consecutive frames -- frame r 2 + s is the pair
 // (antenna r, stream s) --, one launch per batch; a group's counts, losses and LLRs are a function of its own keys, noise scales,
 // weights, true channels and estimates and of its leader's LLR scale (and, for the linear detector, regulariser) only.  The walk is
 // k_link.hip's link_walk with the combiner replaced by a detector:
@@ -38,6 +38,17 @@
 //          of the two scans, 3 additions and 2 minima: 3 L / 2 + 6 VALU operations by the source (30 at 256-QAM; the compiled row of
 //          16 candidates is 544, 34 each, with the |comp| masks and moves) and 2 m + L live minima; no LDS.  The hard decision is
 //          the sign of the stream's own LLRs (bit j is 1 iff Lambda_j < 0), counted against the sent Gray codes;
+//        successive cancellation (link2_sic; linksim.py "the successive-cancellation link")  the order is per element, so step 4 is an
+//          element loop around both streams, neither unrolled: still one copy of the linear detector's code.  f = g11 > g00 picks
+//          the first stream; its stage is link2_linear's calls (link_sm_detect, decide, link_axis_llrs), so its LLRs and decisions
+//          are the linear kernel's bits for that (element, stream).  The decided levels a_ki + j a_kq (link_level: link_sent's
+//          expression) leave the other stream's matched sum by four fused multiply-adds (link_sic_cancel: c_o = m_o - gx x^,
+//          p_o = g_oo), and the second stage is link_walk's measures on (c_o, p_o) with the group's scale: no regulariser, no
+//          division, no second walk over the antennas.  The 2 M LLRs of an element are all that is live; a stream loop (rolled)
+//          then routes them BY STREAM into the losses, the counts and the store (link_store_element_llrs: an element at a time),
+//          so the decoders read the tensor as they read the other detectors'.  Three more integers per thread -- elements detected
+//          in swapped order, first decisions with a symbol error, of those the ones whose other stream is wrong too -- are reduced
+//          with the counts; no scratch;
 //   5. per stream the two integer counts and the K float sums stay in registers and are reduced in link_walk's fixed order: shuffles
 //      in the wave, then the four waves through LDS.
 //
@@ -52,6 +63,7 @@
 //
 //   link_sm_kernel     (aft_link_sm_f32)     the linear ZF / MMSE detector
 //   link_joint_kernel  (aft_link_joint_f32)  the joint max-log demapper
+//   link_sic_kernel    (aft_link_sic_f32)    ordered successive cancellation: the linear detector, then a diversity stage
 #include "link_device.h"
 
 namespace aft {
@@ -59,10 +71,16 @@ namespace {
 
 constexpr int kSmStreams = AFT_LINK_MAX_STREAMS;
 
-// link_args' struct and, per group, the linear detector's regulariser: NULL, and never read, on the joint launch
+// link_args' struct and, per group, the linear detector's regulariser: NULL, and never read, on the joint launch; the
+// successive-cancellation launch's three integers per group, which may be NULL
 struct Link2Args : LinkArgs {
     const float *reg;
+    int *stats;
 };
+
+// the detector of an instantiation's step 4
+constexpr int kLinear = 0, kJoint = 1, kSic = 2;
+constexpr int kSicStats = 3;
 
 // Step 4, linear: the M LLRs of stream `second` of an element with the sums e into w -- I-axis bits first, MSB first, the order of the
 // sent word --; returns the number of bits decided against the sent Gray codes gi, gq.  (The codes by value and w by pointer: with
@@ -93,14 +111,43 @@ __device__ __forceinline__ int link2_joint(float d, const LinkSm &e, float scale
     return __popc(gi ^ hi) + __popc(gq ^ hq);
 }
 
+// Step 4, successive cancellation: BOTH streams of an element with the sums e, because the order is per element.  The first stage is
+// link2_linear's calls on stream f (link_sm_detect, decide, link_axis_llrs) and keeps the decided levels; the second stage takes the
+// decided symbol out of the other stream's matched sum (link_sic_cancel) and is link_walk's measures on (c_o, g_oo, scale).  wf and wo
+// take the M LLRs of the first and of the second detected stream; returns their wrong bits against the sent Gray codes.
+struct LinkSicWrong {
+    int first, other;
+};
+
+template <int M>
+__device__ __forceinline__ LinkSicWrong link2_sic(float d, float d2, const LinkSm &e, float reg, float scale, bool f, const LinkSent &xf,
+                                                  const LinkSent &xo, float *wf, float *wo) {
+    constexpr int half = M / 2, L = 1 << half;
+    const LinkDetected m = link_sm_detect(e, reg, scale, f);
+    const float step = d2 * m.p;
+    const unsigned ki = decide<L>(m.cr, step), kq = decide<L>(m.ci, step);
+    link_axis_llrs<L>(d, m.cr, m.p, m.eff, wf);
+    link_axis_llrs<L>(d, m.ci, m.p, m.eff, wf + half);
+    const LinkBranch c = link_sic_cancel(e, f, link_level<L>(d, ki), link_level<L>(d, kq));
+    const float step2 = d2 * c.p;
+    const unsigned oi = decide<L>(c.cr, step2), oq = decide<L>(c.ci, step2);
+    link_axis_llrs<L>(d, c.cr, c.p, scale, wo);
+    link_axis_llrs<L>(d, c.ci, c.p, scale, wo + half);
+    const int first = __popc(xf.gi ^ ki ^ (ki >> 1)) + __popc(xf.gq ^ kq ^ (kq >> 1));
+    const int other = __popc(xo.gi ^ oi ^ (oi >> 1)) + __popc(xo.gq ^ oq ^ (oq >> 1));
+    return LinkSicWrong{first, other};
+}
+
 // One instantiation per modulation order and detector
-template <int M, bool Joint>
+template <int M, int Det>
 __device__ __forceinline__ void link2_walk(const Link2Args &a) {
+    constexpr bool Joint = Det == kJoint;
+    constexpr int kCounts = kSmStreams * 2 + (Det == kSic ? kSicStats : 0);
     __shared__ int psc[AFT_CHANSIM_MAX_PILOT_SCS], psym[AFT_CHANSIM_MAX_PILOT_SYMBOLS];
     __shared__ unsigned long long bkey[AFT_LINK_MAX_BRANCHES];
     __shared__ float bsigma[AFT_LINK_MAX_BRANCHES], brho[AFT_LINK_MAX_BRANCHES];
     __shared__ float part[kLinkWaves][kSmStreams * kMaxFactors];
-    __shared__ int ipart[kLinkWaves][kSmStreams * 2];
+    __shared__ int ipart[kLinkWaves][kCounts];
     const aft_link &c = a.c;
     const int tid = threadIdx.x;
     const size_t g = blockIdx.x;
@@ -131,6 +178,7 @@ __device__ __forceinline__ void link2_walk(const Link2Args &a) {
     const float2 *hp = a.ideal + first * frame, *ep = a.est + first * frame;
     float *lp = a.llr != nullptr ? a.llr + g * kSmStreams * frame * M : nullptr;
     int bits0 = 0, symbols0 = 0, bits1 = 0, symbols1 = 0;
+    int swapped = 0, first_wrong = 0, both_wrong = 0;           // the successive-cancellation launch's three integers
     const unsigned pairs = (last >> 1) + 1;                     // the last pair of an odd grid holds one element
     for (unsigned i = tid; i < pairs; i += kFrameThreads) {      // pairs <= 2^30: the index cannot wrap
         const unsigned q = 2 * i;
@@ -154,46 +202,96 @@ __device__ __forceinline__ void link2_walk(const Link2Args &a) {
             if (d0) link_sm_accumulate(e0, rho, link_sample2(kf, sr, q, s00, s10, h0.a, h1.a), g0.a, g1.a);
             if (d1) link_sm_accumulate(e1, rho, link_sample2(kf, sr, q + 1, s01, s11, h0.b, h1.b), g0.b, g1.b);
         }
+        if constexpr (Det == kSic) {
 #pragma unroll 1
-        for (int t = 0; t < kSmStreams; ++t) {                  // the stream; the element inside: one copy of the detector
-            float v[2 * M], acc[kMaxFactors];
+            for (int s = 0; s < 2; ++s) {                       // the element; both streams inside: one copy of the two stages
+                if (!(s == 0 || two)) break;
+                const bool data = s ? d1 : d0;
+                float wf[M], wo[M];
 #pragma unroll
-            for (int j = 0; j < 2 * M; ++j) v[j] = 0.f;         // what a pilot position carries
-#pragma unroll
-            for (int k = 0; k < kMaxFactors; ++k) acc[k] = t ? acc1[k] : acc0[k];
-            int bits = 0, symbols = 0;
+                for (int j = 0; j < M; ++j) wf[j] = wo[j] = 0.f;     // what a pilot position carries
+                bool f = false;
+                LinkSicWrong wrong{0, 0};
+                if (data) {
+                    const LinkSm e = s ? e1 : e0;
+                    f = link_sic_second_first(e);
+                    const LinkSent x0 = s ? s01 : s00, x1 = s ? s11 : s10;
+                    wrong = link2_sic<M>(a.d, a.d2, e, reg, scale, f, f ? x1 : x0, f ? x0 : x1, wf, wo);
+                    swapped += f ? 1 : 0;
+                    first_wrong += wrong.first != 0 ? 1 : 0;
+                    both_wrong += wrong.first != 0 && wrong.other != 0 ? 1 : 0;
+                }
 #pragma unroll 1
-            for (int s = 0; s < 2; ++s) {
-                if (s ? d1 : d0) {
-                    const LinkSent x = t ? (s ? s11 : s10) : (s ? s01 : s00);
+                for (int t = 0; t < kSmStreams; ++t) {          // by STREAM, not by detection order: the decoders' layout
+                    const bool is_first = (t != 0) == f;
                     float w[M];
-                    int wrong;
-                    if constexpr (Joint) wrong = link2_joint<M>(a.d, s ? e1 : e0, scale, t != 0, x.gi, x.gq, w);
-                    else wrong = link2_linear<M>(a.d, a.d2, s ? e1 : e0, reg, scale, t != 0, x.gi, x.gq, w);
-                    bits += wrong;
-                    symbols += wrong != 0 ? 1 : 0;
-                    link_soft_losses<M>(w, x.gi, x.gq, fac, nf, acc);
 #pragma unroll
-                    for (int j = 0; j < M; ++j) {
-                        if (s) v[M + j] = w[j];
-                        else v[j] = w[j];
+                    for (int j = 0; j < M; ++j) w[j] = is_first ? wf[j] : wo[j];
+                    if (data) {
+                        const LinkSent x = t ? (s ? s11 : s10) : (s ? s01 : s00);
+                        const int wr = is_first ? wrong.first : wrong.other;
+                        float acc[kMaxFactors];
+#pragma unroll
+                        for (int k = 0; k < kMaxFactors; ++k) acc[k] = t ? acc1[k] : acc0[k];
+                        link_soft_losses<M>(w, x.gi, x.gq, fac, nf, acc);
+#pragma unroll
+                        for (int k = 0; k < kMaxFactors; ++k) {
+                            if (t) acc1[k] = acc[k];
+                            else acc0[k] = acc[k];
+                        }
+                        if (t) { bits1 += wr; symbols1 += wr != 0 ? 1 : 0; }
+                        else { bits0 += wr; symbols0 += wr != 0 ? 1 : 0; }
                     }
+                    if (lp != nullptr) link_store_element_llrs<M>(lp + ((size_t)t * frame + q + s) * M, w, a.store);
                 }
             }
+        } else {
+#pragma unroll 1
+            for (int t = 0; t < kSmStreams; ++t) {              // the stream; the element inside: one copy of the detector
+                float v[2 * M], acc[kMaxFactors];
 #pragma unroll
-            for (int k = 0; k < kMaxFactors; ++k) {
-                if (t) acc1[k] = acc[k];
-                else acc0[k] = acc[k];
+                for (int j = 0; j < 2 * M; ++j) v[j] = 0.f;     // what a pilot position carries
+#pragma unroll
+                for (int k = 0; k < kMaxFactors; ++k) acc[k] = t ? acc1[k] : acc0[k];
+                int bits = 0, symbols = 0;
+#pragma unroll 1
+                for (int s = 0; s < 2; ++s) {
+                    if (s ? d1 : d0) {
+                        const LinkSent x = t ? (s ? s11 : s10) : (s ? s01 : s00);
+                        float w[M];
+                        int wrong;
+                        if constexpr (Joint) wrong = link2_joint<M>(a.d, s ? e1 : e0, scale, t != 0, x.gi, x.gq, w);
+                        else wrong = link2_linear<M>(a.d, a.d2, s ? e1 : e0, reg, scale, t != 0, x.gi, x.gq, w);
+                        bits += wrong;
+                        symbols += wrong != 0 ? 1 : 0;
+                        link_soft_losses<M>(w, x.gi, x.gq, fac, nf, acc);
+#pragma unroll
+                        for (int j = 0; j < M; ++j) {
+                            if (s) v[M + j] = w[j];
+                            else v[j] = w[j];
+                        }
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < kMaxFactors; ++k) {
+                    if (t) acc1[k] = acc[k];
+                    else acc0[k] = acc[k];
+                }
+                if (t) { bits1 += bits; symbols1 += symbols; }
+                else { bits0 += bits; symbols0 += symbols; }
+                if (lp != nullptr) link_store_llrs<M>(lp + ((size_t)t * frame + q) * M, v, two ? 2 * M : M, a.store);
             }
-            if (t) { bits1 += bits; symbols1 += symbols; }
-            else { bits0 += bits; symbols0 += symbols; }
-            if (lp != nullptr) link_store_llrs<M>(lp + ((size_t)t * frame + q) * M, v, two ? 2 * M : M, a.store);
         }
     }
     link_wave_sum(bits0, tid, ipart, 0);
     link_wave_sum(symbols0, tid, ipart, 1);
     link_wave_sum(bits1, tid, ipart, 2);
     link_wave_sum(symbols1, tid, ipart, 3);
+    if constexpr (Det == kSic) {
+        link_wave_sum(swapped, tid, ipart, 4);
+        link_wave_sum(first_wrong, tid, ipart, 5);
+        link_wave_sum(both_wrong, tid, ipart, 6);
+    }
 #pragma unroll
     for (int k = 0; k < kMaxFactors; ++k)
         if (k < nf) {
@@ -207,16 +305,25 @@ __device__ __forceinline__ void link2_walk(const Link2Args &a) {
     }
     // the second wave: per stream the bit errors, then the symbol errors
     if (tid >= kWave && tid < kWave + 2 * kSmStreams) a.counts[2 * kSmStreams * g + (tid - kWave)] = link_block_sum(ipart, tid - kWave);
+    if constexpr (Det == kSic) {                                // the third wave: swapped order, first-decision errors, propagated errors
+        if (a.stats != nullptr && tid >= 2 * kWave && tid < 2 * kWave + kSicStats)
+            a.stats[kSicStats * g + (tid - 2 * kWave)] = link_block_sum(ipart, 2 * kSmStreams + (tid - 2 * kWave));
+    }
 }
 
 template <int M>
 __global__ __launch_bounds__(kFrameThreads) void link_sm_kernel(const Link2Args a) {
-    link2_walk<M, false>(a);
+    link2_walk<M, kLinear>(a);
 }
 
 template <int M>
 __global__ __launch_bounds__(kFrameThreads) void link_joint_kernel(const Link2Args a) {
-    link2_walk<M, true>(a);
+    link2_walk<M, kJoint>(a);
+}
+
+template <int M>
+__global__ __launch_bounds__(kFrameThreads) void link_sic_kernel(const Link2Args a) {
+    link2_walk<M, kSic>(a);
 }
 
 }  // namespace
@@ -224,11 +331,22 @@ __global__ __launch_bounds__(kFrameThreads) void link_joint_kernel(const Link2Ar
 hipError_t launch_link2(bool joint, const aft_link &link, const float *ideal, const float *est, const unsigned long long *keys,
                         const float *sigma, const float *rho, const float *scale, const float *reg, const float *factors, int n_factors,
                         int branches, int32_t *counts, float *loss, float *llr, int batch, hipStream_t st) {
-    const Link2Args a{link_args(link, ideal, est, keys, sigma, rho, scale, factors, n_factors, branches, counts, loss, llr), reg};
+    const Link2Args a{link_args(link, ideal, est, keys, sigma, rho, scale, factors, n_factors, branches, counts, loss, llr), reg, nullptr};
     const dim3 grid((unsigned)(batch / (branches * kSmStreams)));
     return link_dispatch(link.bits_per_symbol, [&](auto m) {
         if (joint) hipLaunchKernelGGL(link_joint_kernel<decltype(m)::value>, grid, dim3(kFrameThreads), 0, st, a);
         else hipLaunchKernelGGL(link_sm_kernel<decltype(m)::value>, grid, dim3(kFrameThreads), 0, st, a);
+    });
+}
+
+hipError_t launch_link_sic(const aft_link &link, const float *ideal, const float *est, const unsigned long long *keys,
+                           const float *sigma, const float *rho, const float *scale, const float *reg, const float *factors, int n_factors,
+                           int branches, int32_t *counts, float *loss, float *llr, int32_t *stats, int batch, hipStream_t st) {
+    Link2Args a{link_args(link, ideal, est, keys, sigma, rho, scale, factors, n_factors, branches, counts, loss, llr), reg, stats};
+    a.store = link_llr_element_store_bytes(llr, link.bits_per_symbol);      // an element's LLRs leave on their own: the order is per element
+    const dim3 grid((unsigned)(batch / (branches * kSmStreams)));
+    return link_dispatch(link.bits_per_symbol, [&](auto m) {
+        hipLaunchKernelGGL(link_sic_kernel<decltype(m)::value>, grid, dim3(kFrameThreads), 0, st, a);
     });
 }
 

@@ -3,7 +3,8 @@
 // transmission) and a branch (one per receive antenna: y = H x + noise, c = y conj(E), p = |E|^2) --, the combiner's step, an axis's
 // max-log LLRs, the softplus step of the loss, the LLR store, the reduction of a workgroup's sums and, on the host, a launch's
 // arguments and its dispatch on the modulation order; and what two-stream detection (k_linksm.hip) adds to them: the two-stream
-// received sample, the Gram / matched sums, the adjugate detector with its LLR scale and the joint max-log demapper; and what transmit
+// received sample, the Gram / matched sums, the adjugate detector with its LLR scale, the order, the decided level and the cancellation
+// of the successive-cancellation detector and the joint max-log demapper; and what transmit
 // diversity (k_linkalamouti.hip) adds: a line's k-th data element, the Alamouti combiner's step and the store of one element's LLRs;
 // and what closed-loop precoding (k_linkprecode.hip) adds: the exact product with a codebook entry, a subband's selection sum and its
 // decision, and the combiner's step on the effective estimate.
@@ -169,6 +170,30 @@ __device__ __forceinline__ LinkDetected link_sm_detect(const LinkSm &a, float re
     const float tr = fmaf(gxr, mor, -(gxi * moi)), ti = fmaf(gxr, moi, gxi * mor);      // gx m_other
     const float n01 = fmaf(a.g01r, a.g01r, a.g01i * a.g01i);
     return LinkDetected{fmaf(ao, msr, -tr), fmaf(ao, msi, -ti), fmaf(gs, ao, -n01), ao > 0.f ? scale / ao : 0.f};
+}
+
+// ---- successive cancellation of the two streams (k_linksm.hip; linksim.py "the successive-cancellation link") ----
+
+// The detection order of an element: true iff stream 1 is detected first, g11 > g00 (a tie and NaN give stream 0).  This is the order
+// of the linear detector's post-detection SINRs for every reg >= 0: p_0 a00 - p_1 a11 = (g00 - g11) det(A).
+__device__ __forceinline__ bool link_sic_second_first(const LinkSm &a) {
+    return a.g11 > a.g00;
+}
+
+// The level a_k = d (2 k - (L - 1)) of a decided index, by link_sent's expression: a correct decision is the very float32 that was sent
+template <int L>
+__device__ __forceinline__ float link_level(float d, unsigned k) {
+    return d * (float)(2 * (int)k - (L - 1));
+}
+
+// The second stage's operands: the decided symbol xr + j xi of the first stream taken out of the other stream's matched sum,
+// c_o = m_o - gx x^ with gx = g01 when the other stream is 0 (`second_first`) and conj(g01) when it is 1, two fused multiply-adds per
+// component, the x^.im term first; p_o = g_oo, the diversity link's p: no regulariser, no division.
+__device__ __forceinline__ LinkBranch link_sic_cancel(const LinkSm &a, bool second_first, float xr, float xi) {
+#pragma clang fp contract(off)
+    const float mor = second_first ? a.m0r : a.m1r, moi = second_first ? a.m0i : a.m1i;
+    const float gxr = a.g01r, gxi = second_first ? a.g01i : -a.g01i;
+    return LinkBranch{fmaf(-gxr, xr, fmaf(gxi, xi, mor)), fmaf(-gxr, xi, fmaf(-gxi, xr, moi)), second_first ? a.g00 : a.g11};
 }
 
 // ---- joint max-log detection of the two streams (k_linksm.hip; linksim.py "the joint link") ----

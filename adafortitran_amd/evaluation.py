@@ -85,7 +85,8 @@ def get_link_stats(model: Optional[torch.nn.Module], test_dataloaders: List[Tupl
     every batch then holds a multiple of R frames.  ``streams=2`` with ``detector`` ``"zf"`` or ``"mmse"`` separates two transmit
     streams on those R antennas (``linksim``: "the spatial-multiplexing link"): every batch holds a multiple of ``2 R`` frames, frame
     ``r 2 + s`` of a group the pair (antenna r, stream s), and the rate is per stream.  ``detector="joint"`` runs the joint max-log
-    demapper on the same frames instead of a linear detector (``linksim``: "the joint link").  ``tx_diversity="time"`` or
+    demapper on the same frames instead of a linear detector (``linksim``: "the joint link"), ``detector="sic"`` ordered MMSE-SIC
+    (``linksim``: "the successive-cancellation link").  ``tx_diversity="time"`` or
     ``"frequency"`` sends ONE stream from two transmit antennas as Alamouti pairs over adjacent data symbols or subcarriers
     (``linksim``: "the transmit-diversity link"): every batch holds a multiple of ``2 R`` frames in the same order, ``streams`` must
     be 1, ``detector`` is ignored, and the SNR is per transmit antenna.  ``precoding_subband=B`` sends ONE stream from the same two

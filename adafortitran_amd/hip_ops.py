@@ -516,6 +516,7 @@ class LinkPlan:
     cpu_path = "linksim.link_errors_host"
     pairs = False                                               # True: a group is branches * 2 frames and yields one row (LinkAlamoutiPlan)
     n_sub = None                                                # an integer: the launch also writes pmi int32 [rows, n_sub] (LinkPrecodedPlan)
+    n_stats = None                                              # an integer: the launch also writes stats int32 [groups, n_stats] (LinkSicPlan)
 
     def __init__(self, cfg, device: torch.device) -> None:
         from .linksim import LinkConfig
@@ -548,12 +549,14 @@ class LinkPlan:
         return _in_place("factors", factors, torch.float32, self.device, factors.numel())
 
     def _grouped(self, entry: str, ideal, est, keys, sigma, rho, per_group, factors, want_llr: bool, lib):
-        """What the grouped front ends (``LinkMrcPlan``, ``LinkSmPlan``, ``LinkJointPlan``) share.  ``self.group`` is the group's
+        """What the grouped front ends (``LinkMrcPlan``, ``LinkSmPlan``, ``LinkJointPlan``, ``LinkSicPlan``) share.  ``self.group`` is the group's
         width, ``(branches,)`` or ``(branches, streams)``, passed to ``entry`` as it stands; ``per_group`` names the float32 operands
         with one value per group, in the entry point's order.  Returns ``(counts, loss, llr)`` for ``groups * streams`` rows.
         ``LinkAlamoutiPlan`` sets ``self.pairs``: its group is ``branches * 2`` frames that yield ONE row, and ``self.group`` is
         ``(branches, pairing)``.  ``LinkPrecodedPlan`` sets ``self.pairs`` and ``self.n_sub``: ``self.group`` is ``(branches,
-        subband)``, the entry point takes ``pmi int32 [rows, n_sub]`` behind ``llr``, and ``(counts, loss, llr, pmi)`` is returned."""
+        subband)``, the entry point takes ``pmi int32 [rows, n_sub]`` behind ``llr``, and ``(counts, loss, llr, pmi)`` is returned.
+        ``LinkSicPlan`` sets ``self.n_stats``: the entry point takes ``stats int32 [groups, n_stats]`` behind ``llr``, and ``(counts,
+        loss, llr, stats)`` is returned."""
         lib = lib or _lib.load()
         batch, ideal, est, keys, sigma = self._checked(ideal, est, keys, sigma)
         pairs = self.pairs
@@ -570,6 +573,8 @@ class LinkPlan:
         loss = torch.empty((rows, factors.numel()), dtype=torch.float32, device=self.device)
         llr = torch.empty((rows, *self.grid, self.cfg.bits_per_symbol), dtype=torch.float32, device=self.device) if want_llr else None
         pmi = () if self.n_sub is None else (torch.empty((rows, self.n_sub), dtype=torch.int32, device=self.device),)
+        if self.n_stats is not None:                            # one row per GROUP: the order is an element's, not a stream's
+            pmi = (torch.empty((groups, self.n_stats), dtype=torch.int32, device=self.device),)
         _lib.check(getattr(lib, entry)(C.byref(self.link), ideal.data_ptr(), est.data_ptr(), keys.data_ptr(), sigma.data_ptr(),
                                        rho.data_ptr(), *(t.data_ptr() for t in per_group), factors.data_ptr(), factors.numel(),
                                        *self.group, counts.data_ptr(), loss.data_ptr(), _ptr(llr), *(t.data_ptr() for t in pmi), batch,
@@ -663,6 +668,23 @@ class LinkJointPlan(LinkSmPlan):
     def __call__(self, ideal: torch.Tensor, est: torch.Tensor, keys: torch.Tensor, sigma: torch.Tensor, rho: torch.Tensor,
                  scale: torch.Tensor, factors: torch.Tensor, want_llr: bool = False, lib=None):
         return self._grouped("aft_link_joint_f32", ideal, est, keys, sigma, rho, [("scale", scale)], factors, want_llr, lib)
+
+
+class LinkSicPlan(LinkSmPlan):
+    """Ordered successive cancellation on ``LinkSmPlan``'s link and layout (``linksim``: "the successive-cancellation link"): per
+    element the stream with the larger Gram diagonal is detected by the linear detector, its decided symbol is cancelled from the
+    matched sums, and the other stream is combined as a diversity link.  ``plan(ideal, est, keys, sigma, rho, scale, reg, factors,
+    want_llr=False)`` -> ``LinkSmPlan``'s three tensors, indexed by stream, and ``stats int32 [G, 3]`` per group (data elements
+    detected in swapped order, first decisions with a symbol error, of those the elements whose other stream is wrong too): four
+    ``torch.empty`` at the most, one ``ctypes`` call, one launch (``aft_link_sic_f32``) on the current stream, no synchronisation.
+    ``reg`` is any float32 ``>= 0`` per group (``linksim.detector_reg(scale, "mmse")`` for MMSE-SIC); everything else as
+    ``LinkSmPlan``."""
+    cpu_path = "linksim.link_sic_host"
+    n_stats = 3
+
+    def __call__(self, ideal: torch.Tensor, est: torch.Tensor, keys: torch.Tensor, sigma: torch.Tensor, rho: torch.Tensor,
+                 scale: torch.Tensor, reg: torch.Tensor, factors: torch.Tensor, want_llr: bool = False, lib=None):
+        return self._grouped("aft_link_sic_f32", ideal, est, keys, sigma, rho, [("scale", scale), ("reg", reg)], factors, want_llr, lib)
 
 
 class LinkAlamoutiPlan(LinkPlan):

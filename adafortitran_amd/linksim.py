@@ -124,8 +124,8 @@ N times it.  What this models: per-pair estimates and linear detection (zero for
 section).  Antenna correlation, which decides how well two streams separate at all, comes from the simulator:
 ``ChannelSimConfig(antennas=(R, 2), rx_correlation=..., tx_correlation=...)`` makes these ``2 R`` frames one correlated group with
 shared conditions (chansim.py, "Kronecker frame groups"); with an ungrouped configuration the pairs are independent draws with their
-own conditions unless the caller pins them.  It does not model sphere or list detection, successive cancellation, precoding, or
-``N > 2``.  The same two transmit antennas sending ONE stream as Alamouti pairs are "the transmit-diversity link" below
+own conditions unless the caller pins them.  It does not model sphere or list detection, precoding, or ``N > 2``; ordered
+successive cancellation behind this detector is "the successive-cancellation link" below (``detector="sic"``).  The same two transmit antennas sending ONE stream as Alamouti pairs are "the transmit-diversity link" below
 (``tx_diversity=``).
 
 The joint link.  A linear detector on a 2 x 2 Rayleigh channel has diversity order 1; a receiver that ships two-stream reception runs a
@@ -161,8 +161,53 @@ flagged bit moves a row's bit count by at most 1 and an (element, stream) with a
 loss interval is the soft link's, at ``Lambda -+ e_lambda q``.  With an unheard second stream (``H_r1 = E_r1 = 0``) stream 1's ``Delta``
 is exactly 0 and stream 0's LLRs are the diversity link's on the frames ``(r, 0)``.  What this models beyond the linear detectors: the
 joint max-log demapper.  Antenna correlation comes from the simulator's grouped configurations, as for the linear detectors.  It does
-not model sphere or list detection (nothing is pruned: every candidate is evaluated), successive cancellation, iterative detection
-and decoding, or ``N > 2``.
+not model sphere or list detection (nothing is pruned: every candidate is evaluated), iterative detection and decoding, or
+``N > 2``; successive cancellation is the next section.
+
+The successive-cancellation link.  The third textbook receiver for two streams (V-BLAST, MMSE-SIC) decides one stream with the linear
+detector, rebuilds that stream's contribution from its own estimates, subtracts it and combines the other stream as a plain diversity
+link.  It is the only receiver here in which an estimate error passes through a DECISION: a good estimate gives the second stream full
+receive diversity at the linear detector's cost; a poor one fails twice, because a wrong first decision is subtracted with the wrong
+gain.  ``link_sic_host`` (float64), ``aft_link_sic_f32`` (csrc/k_linksm.hip, through ``hip_ops.LinkSicPlan``) and ``detector="sic"``
+(``SIC_DETECTOR``; ``LINK2_DETECTORS`` lists it after ``ALL_DETECTORS``) on the accumulators and sweeps with ``streams=2`` are that
+receiver.  The layout, the keys, ``sent``, ``received``, ``weights``, the eight sums ``m_0, m_1, g00, g11, g01``, ``reg`` (float32 per
+group, any value ``>= 0``; ``detector="sic"`` forms the MMSE one, ``detector_reg(scale, "mmse")``) and ``scale`` are exactly the
+spatial-multiplexing link's: the same operands, the same increasing ``r``, the same fused multiply-add per term, sums that start at
+-0.  Per data element::
+
+    order      f = 1 iff g11 > g00, else f = 0 (a tie and NaN give 0); o = 1 - f.  This IS the order of the linear detector's post-detection
+               SINRs p_s scale / a_other for every reg >= 0: p_0 a00 - p_1 a11 = (g00 - g11) det(A), det(A) = a00 a11 - |g01|^2 >= 0
+    first      stream f: the linear detector's c_f, p_f, eff_f; its hard decision ki, kq, bit and symbol errors and LLRs
+               eff_f Delta_j(c_f, p_f): exactly the spatial-multiplexing link's numbers for that (element, stream)
+    decided    x^ = a_ki + j a_kq, a_k = d (2 k - (L - 1)), formed by the sent symbol's expression, so a correct decision is the very
+               float32 symbol that was sent
+    cancel     gx = g01 when o = 0, conj(g01) when o = 1  (= sum_r rho_r conj(E_ro) E_rf)
+               c_o = m_o - gx x^,  p_o = g_oo.   Device: re = fma(-gx.re, x^.re, fma(gx.im, x^.im, m_o.re)),
+               im = fma(-gx.re, x^.im, fma(-gx.im, x^.re, m_o.im))
+    second     stream o: the DIVERSITY link's decision, errors, mu_k, Delta_j and Lambda_j = scale Delta_j(c_o, p_o), with the group's scale.
+               No regulariser, no division.  After the weights the noise of c_o has variance p_o / scale, as on the diversity link
+    outputs    counts int [G, N, 2], loss [G, N, K], llr [G, N, S, T, m]: indexed BY STREAM, not by detection order, so the decoders read
+               them as they read the other two detectors'.  stats int32 [G, 3] per group: data elements with f = 1; data elements whose
+               first decision is a symbol error; of those, elements where stream o also has a symbol error
+
+Why the order needs no SINR: ``p_0 a00 - p_1 a11 = g00 a00 a11 - g11 a00 a11 + |g01|^2 (a11 - a00)`` and ``a11 - a00 = g11 - g00``, so the
+difference is ``(g00 - g11) (a00 a11 - |g01|^2)``; the determinant is non-negative by Cauchy-Schwarz, hence ``SINR_1 > SINR_0`` exactly
+when ``g11 > g00`` (tests/test_linksic.py compares the two).  The cancellation works on the sums themselves: the antennas are not
+walked a second time and the second stage has no division.  Reaches: the first stage uses the spatial-multiplexing link's; the
+second ``reach(c_o) = reach(m_o) + G01 |x^|`` and ``p_reach = p_o``, a sum of non-negative terms.  What a float32 evaluation is compared
+through: a data element is ORDER-FLAGGED at ``tau`` when ``|g00 - g11| <= tau (g00 + g11)``, and DEPENDENT when it is order-flagged or
+either axis of its first decision is flagged by the spatial-multiplexing link's margin.  At a dependent element the second stream's
+outputs may differ freely -- its bit count by at most ``m``, its symbol count by at most 1, and its LLRs are only bounded, by
+``2 q_dep`` with ``q_dep = scale A (A g_oo + 2 (reach(m_o) + sqrt(2) A G01))`` (every ``|x^| <= sqrt(2) A``) --; an order-flagged element
+is dependent for BOTH streams (either may be the second one; the first-detected one is bounded by the linear detector's ``2 q``).
+At every other element the second stream has its own flags and ``q = scale A (A p_o + 2 reach(c_o))``, as on the diversity link;
+dependent bits of the second stream take ``-+ 2 q_dep`` in the loss interval.  ``link_sic_host(..., genie=True)`` is host only: it
+cancels the SENT symbol of stream ``f`` instead of the decided one, the propagation-free bound.  With an unheard second stream
+(``H_r1 = E_r1 = 0``) stream 0 is detected first everywhere and is the spatial-multiplexing link's stream 0 (the diversity link on the
+frames ``(r, 0)`` for ``reg scale = 1`` in powers of two), and stream 1's LLRs are 0; with ``E_r1 = conj(E_r0)`` the Gram diagonal ties
+and stream 0 is detected first everywhere.  ``sic_propagation()`` of a sweep reads the three integers as shares.  What this models:
+symbol-level, ordered, hard-decision MMSE-SIC on per-pair estimates.  It does not model codeword-level or soft cancellation,
+iterative detection and decoding, ``N > 2``, or HARQ (``HarqAccumulator`` gets no keyword, as today).
 
 The transmit-diversity link.  The third standard two-antenna mode sends ONE stream from two transmit antennas as Alamouti pairs:
 space-time block coding over adjacent symbols or space-frequency block coding over adjacent subcarriers, what cell-edge and control
@@ -778,8 +823,9 @@ ALL_DETECTORS = DETECTORS + (JOINT_DETECTOR,)
 
 
 def _detector(detector) -> str:
-    """A detector's name, checked: the linear ones by ``detector_reg`` (which keeps refusing everything else), or ``"joint"``."""
-    if not (isinstance(detector, str) and detector == JOINT_DETECTOR):
+    """A detector's name, checked: the linear ones by ``detector_reg`` (which keeps refusing everything else), ``"joint"`` or
+    ``"sic"``."""
+    if not (isinstance(detector, str) and detector in (JOINT_DETECTOR, "sic")):
         detector_reg(np.ones(1, np.float32), detector)
     return detector
 
@@ -834,6 +880,99 @@ def link_joint_host(cfg: LinkConfig, keys, ideal, est, sigma, rho, scale, branch
     if e_lambda is not None:
         q = scale[:, None, :, :, None] * Q
         out += (losses(llr + sign * (e_lambda * q)), losses(llr - sign * (e_lambda * q)), q)
+    return out
+
+
+# ---- the successive-cancellation link (module docstring, "The successive-cancellation link"): float64 NumPy, mirrored by csrc/k_linksm.hip ----
+
+SIC_DETECTOR = "sic"
+LINK2_DETECTORS = ALL_DETECTORS + (SIC_DETECTOR,)           # every detector of the two-stream link; ALL_DETECTORS stays the first three
+SIC_STATS = 3                                               # swapped order, first-decision symbol errors, of those the propagated ones
+
+
+def _levels(cfg: LinkConfig, comp: np.ndarray, p: np.ndarray) -> np.ndarray:
+    """The decided level index of an axis: ``#{b in 1 .. L-1 : comp >= beta_b p}``."""
+    L, d = cfg.levels, cfg.d
+    level = np.zeros(comp.shape, dtype=np.int64)
+    for b in range(1, L):
+        level += comp >= (2.0 * d * (b - L / 2)) * p
+    return level
+
+
+def link_sic_host(cfg: LinkConfig, keys, ideal, est, sigma, rho, scale, reg, branches, streams=2, factors=(1.0,),
+                  tau: Optional[float] = None, e_lambda: Optional[float] = None, genie: bool = False):
+    """The successive-cancellation link (module docstring) in float64: the operands of ``link_sm_host``, ``reg`` any float32 ``>= 0`` per
+    group -> ``(counts int64 [G, N, 2], loss float64 [G, N, K], llr float64 [G, N, S, T, m], stats int64 [G, 3])``, the first three
+    indexed by stream.  With ``tau`` the wrong-bit map ``[G, N, S, T]``, the flags ``[G, N, S, T, 2]`` (the first-detected stream's by the
+    spatial-multiplexing link's margin, the other stream's by the diversity link's on ``(c_o, p_o)``) and the dependent map uint8
+    ``[G, S, T]`` follow: 0, 1 at a dependent element (there the SECOND stream's outputs may differ freely) and 2 at an order-flagged
+    one (there both streams' may).  With ``e_lambda`` then ``loss_lo``, ``loss_hi`` and ``q [G, N, S, T, m]``: at a dependent (element,
+    stream) ``q`` is ``q_dep`` (at an order-flagged element the larger of ``q_dep`` and the linear detector's ``q``), the LLR is only
+    known to lie within ``2 q (1 + e_lambda)`` of 0, and the loss interval takes those two ends.  ``genie=True`` cancels the SENT symbol
+    of the first stream instead of the decided one: the propagation-free bound.  Needs no library."""
+    keys, H, E, sigma = _checked(cfg, keys, ideal, est, sigma)
+    (G, R, N, S, T), sent, ms, gss, rm, g01, G01, scale = _sm_sums(cfg, keys, H, E, sigma, rho, scale, branches, streams)
+    if np.size(reg) != G:
+        raise ValueError(f"reg must hold one value per group ({G}), got {np.size(reg)}")
+    reg = np.asarray(reg, dtype=np.float32).astype(np.float64).reshape(G, 1, 1)
+    m, L, d = cfg.bits_per_symbol, cfg.levels, cfg.d
+    half, A = m // 2, (L - 1) * d
+    zero = np.zeros((G, S, T))                                                   # a batch of all-pilot grids keeps its shapes
+    ms, gss, rm = [v + zero for v in ms], [v + zero for v in gss], [v + zero for v in rm]
+    g01, G01, scale = g01 + zero, G01 + zero, scale + zero
+    # the linear detector of both streams, as link_sm_host forms it
+    a = [gss[0] + reg, gss[1] + reg]
+    n01 = g01.real ** 2 + g01.imag ** 2
+    c_lin = [a[1] * ms[0] - g01 * ms[1], a[0] * ms[1] - g01.conj() * ms[0]]
+    p_lin = [gss[0] * a[1] - n01, gss[1] * a[0] - n01]
+    reach_lin = [a[1] * rm[0] + G01 * rm[1], a[0] * rm[1] + G01 * rm[0]]
+    P_lin = [gss[0] * a[1] + G01 ** 2, gss[1] * a[0] + G01 ** 2]
+    eff = [np.divide(scale, a[1 - s], out=np.zeros_like(zero), where=a[1 - s] > 0) for s in range(N)]
+    with np.errstate(invalid="ignore"):
+        f = gss[1] > gss[0]                                                      # stream 1 first; a tie and NaN give stream 0
+    pick = lambda v: np.where(f, v[1], v[0])  # noqa: E731                        the first-detected stream's
+    other = lambda v: np.where(f, v[0], v[1])  # noqa: E731                       the second's
+    c_f, p_f = pick(c_lin), pick(p_lin)
+    if genie:
+        xhat = pick([sent[0][2], sent[1][2]])
+    else:
+        xhat = d * ((2 * _levels(cfg, c_f.real, p_f) - (L - 1)) + 1j * (2 * _levels(cfg, c_f.imag, p_f) - (L - 1)))
+    gx = np.where(f, g01, g01.conj())                                            # g01 when the other stream is 0
+    c_o, p_o, reach_o = other(ms) - gx * xhat, other(gss), other(rm) + G01 * np.abs(xhat)
+    first = np.stack([~f, f], axis=1)                                            # [G, N, S, T]: stream s is the first-detected one
+    by_stream = lambda lin, sec: np.where(first, np.stack(lin, axis=1), sec[:, None])  # noqa: E731
+    c, p, reach = by_stream(c_lin, c_o), by_stream(p_lin, p_o), by_stream(reach_lin, reach_o)
+    p_reach, sc = by_stream(P_lin, p_o), by_stream(eff, scale)
+    flat = lambda v: v.reshape(G * N, S, T)  # noqa: E731
+    gi, gq = (np.stack([sent[0][i], sent[1][i]], axis=1) for i in (0, 1))         # [G, N, S, T]
+    counts, wrong, flags = _hard(cfg, flat(gi), flat(gq), flat(c), flat(p), flat(reach), -1.0 if tau is None else tau, flat(p_reach))
+    loss, llr = _soft(cfg, flat(gi), flat(gq), flat(c), flat(p), flat(reach), flat(sc), factors, None, flat(p_reach))
+    counts, wrong, flags, loss, llr = (v.reshape(G, N, *v.shape[1:]) for v in (counts, wrong, flags, loss, llr))
+    mask = cfg.data_mask[None]
+    wrong_f, wrong_o = np.where(f, wrong[:, 1], wrong[:, 0]), np.where(f, wrong[:, 0], wrong[:, 1])
+    stats = np.stack([(f & mask).sum(axis=(1, 2)), (wrong_f > 0).sum(axis=(1, 2)), ((wrong_f > 0) & (wrong_o > 0)).sum(axis=(1, 2))],
+                     axis=1).astype(np.int64)
+    out = (counts, loss, llr, stats)
+    if tau is None and e_lambda is None:
+        return out
+    t = 0.0 if tau is None else tau
+    order = (np.abs(gss[0] - gss[1]) <= t * (gss[0] + gss[1])) & mask            # the order itself may differ
+    dependent = order | (np.where(first, flags.any(axis=-1), False).any(axis=1) & mask)
+    if tau is not None:
+        out += (wrong, flags, dependent.astype(np.uint8) + order)
+    if e_lambda is not None:
+        q_own = sc * A * (A * p_reach + 2.0 * reach)
+        q_lin = np.stack(eff, axis=1) * A * (A * np.stack(P_lin, axis=1) + 2.0 * np.stack(reach_lin, axis=1))
+        q_dep = scale[:, None] * A * (A * np.stack(gss, axis=1) + 2.0 * (np.stack(rm, axis=1) + np.sqrt(2.0) * A * G01[:, None]))
+        free = (dependent[:, None] & ~first) | order[:, None]                    # [G, N, S, T]: this stream's outputs may differ freely
+        q = np.where(free, np.where(order[:, None], np.maximum(q_lin, q_dep), q_dep), q_own) * mask[:, None]
+        q = np.broadcast_to(q[..., None], llr.shape).copy()
+        sign = _sent_signs(gi, gq, half)
+        losses = _losses_at(sign, cfg.data_mask[None, None, :, :, None], _factors(factors).astype(np.float64))
+        end = 2.0 * q * (1.0 + e_lambda)
+        toward = np.where(free[..., None], sign * end, llr + sign * (e_lambda * q))
+        away = np.where(free[..., None], -sign * end, llr - sign * (e_lambda * q))
+        out += (losses(toward), losses(away), q)
     return out
 
 
@@ -1115,7 +1254,7 @@ class _FrameSweep:
         self._width =self.branches * (2 if self._pairs else self.streams)
         if self.streams > 1:
             _sm_shape(0, self.branches, self.streams)           # one antenna cannot separate two streams
-            _detector(detector)                                 # the detector's name: a linear one, or "joint"
+            _detector(detector)                                 # the detector's name: a linear one, "joint" or "sic"
         self.device = torch.device(device)
         soft = want != "counts"
         self._plan = None
@@ -1126,7 +1265,7 @@ class _FrameSweep:
             elif tx_diversity is not None:         # every measure of the transmit-diversity link comes from the combiner's one launch
                 self._plan = hip_ops.LinkAlamoutiPlan(cfg, self.device, self.branches, tx_diversity)
             elif self.streams > 1:                 # every measure of the spatial-multiplexing link comes from the detector's one launch
-                plan = hip_ops.LinkJointPlan if detector == JOINT_DETECTOR else hip_ops.LinkSmPlan
+                plan = {JOINT_DETECTOR: hip_ops.LinkJointPlan, SIC_DETECTOR: hip_ops.LinkSicPlan}.get(detector, hip_ops.LinkSmPlan)
                 self._plan = plan(cfg, self.device, self.branches, self.streams)
             elif self.branches == 1:
                 self._plan = (hip_ops.LinkSoftPlan if soft else hip_ops.LinkPlan)(cfg, self.device)
@@ -1143,6 +1282,9 @@ class _FrameSweep:
         if self.precoding_subband is not None:     # how often each precoder was chosen, summed on the device
             self._pmi_counts = torch.zeros(4, dtype=torch.int64, device=self.device)
             self._pmi_index = torch.arange(4, dtype=torch.int32, device=self.device)
+        self._sic = self.streams > 1 and detector == SIC_DETECTOR
+        if self._sic:                              # the launches' three integers, summed on the device
+            self._sic_stats = torch.zeros(SIC_STATS, dtype=torch.int64, device=self.device)
 
     def _stage(self, a: np.ndarray) -> torch.Tensor:
         return torch.from_numpy(a).pin_memory().to(self.device, non_blocking=True)
@@ -1205,7 +1347,9 @@ class _FrameSweep:
         several, the weights formed by torch ops on the device -- and nothing synchronises.  With ``streams=2`` the groups are the
         ``G N`` stream-frames of the spatial-multiplexing link with the keys of frames ``(0, s)``: ``link_sm_host`` on a CPU device,
         one launch of ``aft_link_sm_f32`` with ``rho`` and ``reg`` formed on the device on a HIP device; with ``detector="joint"``
-        ``link_joint_host`` and one launch of ``aft_link_joint_f32``, which has no ``reg``.  With ``tx_diversity`` the groups are the
+        ``link_joint_host`` and one launch of ``aft_link_joint_f32``, which has no ``reg``; with ``detector="sic"`` ``link_sic_host`` and
+        one launch of ``aft_link_sic_f32`` with the MMSE ``reg``, and one add of the batch's three integers into the sums
+        ``sic_propagation`` reads.  With ``tx_diversity`` the groups are the
         ``G`` transmissions of the transmit-diversity link with the leaders' keys: ``link_alamouti_host`` on a CPU device, one launch
         of ``aft_link_alamouti_f32`` with ``rho`` formed on the device on a HIP device.  With ``precoding_subband`` the same groups on
         the closed-loop link: ``link_precoded_host`` or one launch of ``aft_link_precoded_f32``, and one add of the batch's PMIs into
@@ -1235,6 +1379,9 @@ class _FrameSweep:
             rho, lead = _weights(scale[0], R * N)
             if self.detector == JOINT_DETECTOR:
                 out = link_joint_host(self.cfg, keys, H, E, sigma, rho, lead, R, N, self.factors)
+            elif self._sic:                        # MMSE-SIC: the first stage is the MMSE detector
+                *out, stats = link_sic_host(self.cfg, keys, H, E, sigma, rho, lead, detector_reg(lead, "mmse"), R, N, self.factors)
+                self._sic_stats += torch.from_numpy(stats.sum(axis=0))
             else:
                 out = link_sm_host(self.cfg, keys, H, E, sigma, rho, lead, detector_reg(lead, self.detector), R, N, self.factors)
             counts, loss, llr = (v.reshape(G * N, *v.shape[2:]) for v in out)
@@ -1270,8 +1417,10 @@ class _FrameSweep:
             if self.detector == JOINT_DETECTOR:
                 reg = ()
             else:
-                reg = (torch.zeros_like(lead) if self.detector == "zf" else (1.0 / lead.to(torch.float64)).to(torch.float32),)
-            counts, loss, llr = self._launch(H, E, keys, sigma, rho, lead, *reg, self._factors_t, want_llr=want_llr)
+                reg = (torch.zeros_like(lead) if self.detector == "zf" else (1.0 / lead.to(torch.float64)).to(torch.float32),)   # "sic": MMSE's
+            counts, loss, llr, *stats = self._launch(H, E, keys, sigma, rho, lead, *reg, self._factors_t, want_llr=want_llr)
+            if stats:                              # the successive-cancellation link's fourth output: one sum, one add
+                self._sic_stats += stats[0].sum(dim=0, dtype=torch.int64)
             return keys.view(G, R, N)[:, 0, :].reshape(-1), counts, loss, llr
         if R > 1:
             rho, lead = self._device_weights(scale[0], R)
@@ -1291,6 +1440,16 @@ class _FrameSweep:
         if self.precoding_subband is None:
             raise ValueError("pmi_histogram needs precoding_subband: no other link chooses a precoder")
         return [int(v) for v in self._all_ranks(self._pmi_counts.to(torch.float64), group)]
+
+    def sic_propagation(self, group=None) -> tuple:
+        """What successive cancellation did over the sweep, all ranks: ``(the share of data elements detected in swapped order -- stream
+        1 first --, the symbol-error rate of the first decision, the share of first-decision errors followed by a symbol error of the
+        other stream)``; 0.0 where a denominator is 0.  Summed on the device by one add per batch; one read, as the result's."""
+        if not self._sic:
+            raise ValueError('sic_propagation needs streams=2 and detector="sic": no other link cancels a decided stream')
+        elements = torch.tensor([self.frames // self.streams * self.cfg.data_elements], dtype=torch.float64, device=self.device)
+        swapped, wrong, both, elements = self._all_ranks(torch.cat([self._sic_stats.to(torch.float64), elements]), group)
+        return (swapped / elements if elements > 0 else 0.0, wrong / elements if elements > 0 else 0.0, both / wrong if wrong > 0 else 0.0)
 
     @staticmethod
     def _total(per_group: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
@@ -1348,6 +1507,8 @@ class LinkAccumulator(_FrameSweep):
     key of frame ``(0, s)``; ``frames`` counts them, and every rate is per stream and symbol: the spectral efficiency is N times it.
     ``detector="joint"`` (module docstring, "the joint link") is the joint max-log demapper on the same frames: one launch of
     ``aft_link_joint_f32`` (on a CPU device ``link_joint_host``), no regulariser.
+    ``detector="sic"`` (module docstring, "the successive-cancellation link") is ordered MMSE-SIC on the same frames: one launch of
+    ``aft_link_sic_f32`` (on a CPU device ``link_sic_host``) with the MMSE regulariser; ``sic_propagation()`` reads what it propagated.
     ``streams=1`` is today's path, launch for launch, and ignores ``detector``.
 
     ``tx_diversity="time"`` or ``"frequency"`` (module docstring, "the transmit-diversity link"; the same keyword on ``RateAccumulator``,

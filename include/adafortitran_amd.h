@@ -729,6 +729,32 @@ int aft_link_precoded_f32(const aft_link *link, const float *ideal, const float 
                           float *llr /* [groups,S,T,m] or NULL */, int32_t *pmi /* [groups][n_sub], not NULL */, int batch,
                           void *stream);
 
+/* ---- successive cancellation: ordered MMSE-SIC of the two streams (adafortitran_amd/linksim.py "the successive-cancellation link") ----
+ *
+ * The layout, keys, sent words, received samples, weights, the eight sums, reg and scale are aft_link_sm_f32's, formed by the same
+ * code: the third detector of the one frame walk.  Per data element:
+ *   order      f = 1 iff g11 > g00, else 0 (a tie and NaN give 0), o = 1 - f: the order of the linear detector's post-detection SINRs
+ *              for every reg >= 0, because p_0 a00 - p_1 a11 = (g00 - g11) det(A)
+ *   first      stream f: aft_link_sm_f32's c_f, p_f, eff_f, decision ki, kq, errors and LLRs for that (element, stream), bit for bit
+ *   decided    x^ = a_ki + j a_kq, a_k = d (2 k - (L - 1)) formed as the sent symbol is: a correct decision is the float32 that was sent
+ *   cancel     c_o = m_o - gx x^, gx = g01 for o = 0 and conj(g01) for o = 1; p_o = g_oo.  re = fma(-gx.re, x^.re, fma(gx.im, x^.im,
+ *              m_o.re)), im = fma(-gx.re, x^.im, fma(-gx.im, x^.re, m_o.im))
+ *   second     stream o: aft_link_mrc_f32's decision, errors, mu_k, Delta_j and Lambda_j = scale Delta_j on (c_o, p_o) with the LEADER's
+ *              scale: no regulariser, no division
+ * counts, loss and llr are aft_link_sm_f32's tensors, indexed BY STREAM, not by detection order.  stats int32 [groups][3] (device
+ * memory; may be NULL, as llr may) holds per group the data elements with f = 1, the data elements whose first decision is a symbol
+ * error and, of those, the elements where stream o has a symbol error too.  One launch, one workgroup per group, every element of
+ * the outputs written, no atomics, no workspace, nothing synchronised; a group's outputs depend neither on batch, nor on its
+ * position in it, nor on the run, nor on the load and store forms, nor on whether llr or stats is written.  With H_r1 = E_r1 = 0
+ * stream 0 is detected first everywhere and stream 1's LLRs are 0.
+ * Nothing is launched on AFT_ERR_ARG and AFT_ERR_SHAPE: what aft_link_sm_f32 refuses, and a stats that is not 4-byte aligned. */
+int aft_link_sic_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys,
+                     const float *sigma, const float *rho /* [batch] */, const float *scale /* [groups] */,
+                     const float *reg /* [groups] */, const float *factors, int n_factors, int branches, int streams,
+                     int32_t *counts /* [groups][streams][2] */, float *loss /* [groups][streams][n_factors] */,
+                     float *llr /* [groups,streams,S,T,m] or NULL */, int32_t *stats /* [groups][3] or NULL */, int batch,
+                     void *stream);
+
 /* ---- training path of the encoder ---- */
 
 /* Gradients of one nn.TransformerEncoderLayer: same fields and shapes as aft_layer_weights,
