@@ -233,6 +233,10 @@ SIGNATURES = {
     "aft_link_alamouti_f32": (C.c_int, [C.POINTER(AftLink), vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]),
     "aft_link_precoded_f32": (C.c_int, [C.POINTER(AftLink), vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp]),
     "aft_link_sic_f32": (C.c_int, [C.POINTER(AftLink), vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp]),
+    "aft_link_cancel_f32": (C.c_int, [C.POINTER(AftLink), vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp,
+                                      C.c_int, vp]),
+    "aft_link_ldpc_masked_f32": (C.c_int, [C.POINTER(AftLink), vp, vp, C.c_int, C.c_int, vp, C.c_ulonglong, C.c_ulonglong, C.c_float, C.c_int,
+                                           C.c_int, vp, C.c_int, vp, vp, C.c_int, vp]),
     # training path
     "aft_encoder_tape_bytes": (C.c_size_t, [cfgp, C.c_int]),
     "aft_encoder_train_scratch_bytes": (C.c_size_t, [cfgp, C.c_int]),

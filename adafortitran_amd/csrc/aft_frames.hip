@@ -324,15 +324,17 @@ int aft_link_decode_f32(const aft_link *link, const float *llr, const unsigned l
     return e == hipSuccess ? AFT_OK : hip_fail("link_decode", e);
 }
 
-int aft_link_ldpc_f32(const aft_link *link, const float *llr, const unsigned long long *keys, int base_rows, int base_cols,
-                      const int32_t *shifts, unsigned long long stride, unsigned long long stride_inverse, float qgain, int offset,
-                      int max_iters, int32_t *counts, unsigned char *bits, int batch, void *stream) {
-    const char *who = "link ldpc";
-    AFT_REQUIRE(link && llr && keys && shifts && counts, "link ldpc: NULL pointer argument");
-    AFT_REQUIRE(aligned(8, keys), "link ldpc: keys must be 8-byte aligned");
-    AFT_REQUIRE(aligned(4, llr, shifts, counts), "link ldpc: llr, shifts and counts must be 4-byte aligned");
-    AFT_REQUIRE(batch >= 1, "link ldpc: batch must be at least 1 (got %d)", batch);
-    AFT_REQUIRE(std::isfinite(qgain) && qgain > 0.f, "link ldpc: qgain = %g must be finite and positive", (double)qgain);
+// What both LDPC decoder entry points do after their own operands: aft_link_ldpc_f32's checks under the caller's name, then the launch --
+// the masked kernel where mask is given (aft_link_ldpc_masked_f32 has checked it and its stride)
+static int link_ldpc_checked(const char *who, const char *what, const aft_link *link, const float *llr, const unsigned long long *keys,
+                             int base_rows, int base_cols, const int32_t *shifts, unsigned long long stride,
+                             unsigned long long stride_inverse, float qgain, int offset, int max_iters, int32_t *counts, unsigned char *bits,
+                             const int32_t *mask, int mask_stride, int batch, void *stream) {
+    AFT_REQUIRE(link && llr && keys && shifts && counts, "%s: NULL pointer argument", who);
+    AFT_REQUIRE(aligned(8, keys), "%s: keys must be 8-byte aligned", who);
+    AFT_REQUIRE(aligned(4, llr, shifts, counts), "%s: llr, shifts and counts must be 4-byte aligned", who);
+    AFT_REQUIRE(batch >= 1, "%s: batch must be at least 1 (got %d)", who, batch);
+    AFT_REQUIRE(std::isfinite(qgain) && qgain > 0.f, "%s: qgain = %g must be finite and positive", who, (double)qgain);
     const int rc = check_link(who, *link);
     if (rc != AFT_OK) return rc;
     if (!ldpc_code_ok(who, base_rows, base_cols, shifts, offset, max_iters)) return AFT_ERR_SHAPE;
@@ -342,8 +344,27 @@ int aft_link_ldpc_f32(const aft_link *link, const float *llr, const unsigned lon
     const int rb = check_blocks(who, *link, coded, info, stride, stride_inverse, &blocks);
     if (rb != AFT_OK) return rb;
     hipError_t e = launch_link_ldpc(*link, llr, keys, base_rows, base_cols, shifts, blocks, stride, qgain, offset, max_iters,
-                                    counts, bits, batch, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? AFT_OK : hip_fail("link_ldpc", e);
+                                    counts, bits, mask, mask_stride, batch, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? AFT_OK : hip_fail(what, e);
+}
+
+int aft_link_ldpc_f32(const aft_link *link, const float *llr, const unsigned long long *keys, int base_rows, int base_cols,
+                      const int32_t *shifts, unsigned long long stride, unsigned long long stride_inverse, float qgain, int offset,
+                      int max_iters, int32_t *counts, unsigned char *bits, int batch, void *stream) {
+    return link_ldpc_checked("link ldpc", "link_ldpc", link, llr, keys, base_rows, base_cols, shifts, stride, stride_inverse, qgain, offset,
+                             max_iters, counts, bits, nullptr, 0, batch, stream);
+}
+
+// aft_link_ldpc_f32's checks after its own: the mask is there, 4-byte aligned, and read at a stride of at least one word
+int aft_link_ldpc_masked_f32(const aft_link *link, const float *llr, const unsigned long long *keys, int base_rows, int base_cols,
+                             const int32_t *shifts, unsigned long long stride, unsigned long long stride_inverse, float qgain, int offset,
+                             int max_iters, const int32_t *mask, int mask_stride, int32_t *counts, unsigned char *bits, int batch,
+                             void *stream) {
+    AFT_REQUIRE(mask, "link ldpc masked: NULL pointer argument");
+    AFT_REQUIRE(aligned(4, mask), "link ldpc masked: mask must be 4-byte aligned");
+    AFT_REQUIRE(mask_stride >= 1, "link ldpc masked: mask_stride must be at least 1 (got %d)", mask_stride);
+    return link_ldpc_checked("link ldpc masked", "link_ldpc_masked", link, llr, keys, base_rows, base_cols, shifts, stride, stride_inverse,
+                             qgain, offset, max_iters, counts, bits, mask, mask_stride, batch, stream);
 }
 
 int aft_link_mrc_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys,
@@ -422,6 +443,22 @@ int aft_link_sic_f32(const aft_link *link, const float *ideal, const float *est,
     hipError_t e = launch_link_sic(*link, ideal, est, keys, sigma, rho, scale, reg, factors, n_factors, branches, counts, loss, llr, stats,
                                    batch, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? AFT_OK : hip_fail("link_sic", e);
+}
+
+// aft_link_sm_f32's checks less reg; failed is there, 4-byte aligned and read at a stride of at least one word; state may be NULL as llr
+// may, and is 4-byte aligned where it is given
+int aft_link_cancel_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys, const float *sigma,
+                        const float *rho, const float *scale, const float *factors, int n_factors, int branches, int streams,
+                        const int32_t *failed, int failed_stride, int32_t *counts, float *loss, float *llr, int32_t *state, int batch,
+                        void *stream) {
+    const int rc = check_front2("link cancel", link, ideal, est, keys, {sigma, rho, scale, factors, failed, counts, loss},
+                                "sigma, rho, scale, factors, failed, counts, loss, llr and state", llr, batch, n_factors, branches, streams);
+    if (rc != AFT_OK) return rc;
+    AFT_REQUIRE(aligned(4, state), "link cancel: sigma, rho, scale, factors, failed, counts, loss, llr and state must be 4-byte aligned");
+    AFT_REQUIRE(failed_stride >= 1, "link cancel: failed_stride must be at least 1 (got %d)", failed_stride);
+    hipError_t e = launch_link_cancel(*link, ideal, est, keys, sigma, rho, scale, factors, n_factors, branches, failed, failed_stride, counts,
+                                      loss, llr, state, batch, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? AFT_OK : hip_fail("link_cancel", e);
 }
 
 int aft_link_alamouti_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys, const float *sigma,

@@ -397,11 +397,12 @@ hipError_t launch_link_decode(const aft_link &link, const float *llr, const unsi
                               unsigned char *bits, int batch, hipStream_t st);
 // the LDPC-coded link's layered min-sum decoder (k_linkldpc.hip): everything has passed aft_link_ldpc_f32's checks; shifts is the host
 // table [base_rows][base_cols - base_rows], read during the call; bits may be NULL.  link_ldpc_waves: the code blocks a workgroup
-// decodes at once (their posteriors and messages fill LDS)
+// decodes at once (their posteriors and messages fill LDS).  mask NULL: aft_link_ldpc_f32's kernel; otherwise aft_link_ldpc_masked_f32's,
+// the same body, which decodes frame f only where mask[f mask_stride] is not 0
 int link_ldpc_waves(int base_cols, int edges, unsigned blocks);
 hipError_t launch_link_ldpc(const aft_link &link, const float *llr, const unsigned long long *keys, int base_rows, int base_cols,
                             const int32_t *shifts, unsigned blocks, unsigned long long stride, float qgain, int offset, int max_iters,
-                            int32_t *counts, unsigned char *bits, int batch, hipStream_t st);
+                            int32_t *counts, unsigned char *bits, const int32_t *mask, int mask_stride, int batch, hipStream_t st);
 // the HARQ link on that code (k_linkharq.hip): everything has passed aft_link_harq_f32's checks; shifts and starts [rounds] are host
 // tables read during the call; blocks = B of the definition; one workgroup per group of `rounds` frames, batch a multiple of it; bits
 // may be NULL.  link_harq_waves: the code blocks a workgroup holds at once (soft buffer, posteriors and messages fill LDS)
@@ -421,6 +422,12 @@ hipError_t launch_link2(bool joint, const aft_link &link, const float *ideal, co
 hipError_t launch_link_sic(const aft_link &link, const float *ideal, const float *est, const unsigned long long *keys,
                            const float *sigma, const float *rho, const float *scale, const float *reg, const float *factors, int n_factors,
                            int branches, int32_t *counts, float *loss, float *llr, int32_t *stats, int batch, hipStream_t st);
+// the second pass of codeword-level cancellation on the same two streams (k_linksm.hip): everything has passed aft_link_cancel_f32's
+// checks; failed[(g 2 + s) failed_stride] is the first pass's block-error count; llr and state [groups][2] may be NULL
+hipError_t launch_link_cancel(const aft_link &link, const float *ideal, const float *est, const unsigned long long *keys,
+                              const float *sigma, const float *rho, const float *scale, const float *factors, int n_factors, int branches,
+                              const int32_t *failed, int failed_stride, int32_t *counts, float *loss, float *llr, int32_t *state,
+                              int batch, hipStream_t st);
 // transmit diversity on the same link (k_linkalamouti.hip): Alamouti pairs over time (pairing AFT_LINK_PAIR_TIME) or frequency;
 // everything has passed aft_link_alamouti_f32's checks; one workgroup per group of branches * 2 frames, batch a multiple of it; llr
 // may be NULL

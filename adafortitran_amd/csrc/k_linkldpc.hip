@@ -24,6 +24,9 @@
 // Steps 2 and 4 -- the edge list, the codeword and the decoder -- are written once in linkldpc_device.h and shared with the HARQ link
 // (k_linkharq.hip).  No atomics, no workspace: everything is integer after the quantiser, whose one float32 product and
 // round-to-nearest-even are the definition's.
+//
+//   link_ldpc_kernel<LinkLdpcArgs>        (aft_link_ldpc_f32)         every frame is decoded
+//   link_ldpc_kernel<LinkLdpcMaskedArgs>  (aft_link_ldpc_masked_f32)  the same body; a frame whose mask word is 0 stores zeros and leaves first
 #include "linkldpc_device.h"
 
 namespace aft {
@@ -43,7 +46,19 @@ struct LinkLdpcArgs {
     LdpcEdges base;                                             // mb, nb and the entries of the base matrix, layer by layer
 };
 
-__global__ __launch_bounds__(kLdpcMaxWaves *kWave) void link_ldpc_kernel(const LinkLdpcArgs a) {
+// what the masked launch adds: one word per frame, mask[f mask_stride]; a frame whose word is 0 is not decoded.  Its own struct: the
+// unmasked kernel's arguments stay as they are
+struct LinkLdpcMaskedArgs : LinkLdpcArgs {
+    const int *mask;
+    int mask_stride;
+};
+
+// The kernel, once: Args = LinkLdpcArgs is aft_link_ldpc_f32's, Args = LinkLdpcMaskedArgs aft_link_ldpc_masked_f32's, whose workgroups
+// read their frame's mask word first -- wave-uniform -- and, where it is 0, store the frame's zeros (three counts, and B K bits when
+// asked for) and leave before any barrier and before any LLR is read.
+template <class Args>
+__global__ __launch_bounds__(kLdpcMaxWaves *kWave) void link_ldpc_kernel(const Args a) {
+    constexpr bool Masked = std::is_same<Args, LinkLdpcMaskedArgs>::value;
     extern __shared__ __attribute__((aligned(16))) unsigned char state_all[];    // [waves]: posteriors int16 [n], messages int8 [edges][64]
     __shared__ int psc[AFT_CHANSIM_MAX_PILOT_SCS], psym[AFT_CHANSIM_MAX_PILOT_SYMBOLS];
     __shared__ unsigned before[AFT_CHANSIM_MAX_PILOT_SCS];
@@ -60,6 +75,17 @@ __global__ __launch_bounds__(kLdpcMaxWaves *kWave) void link_ldpc_kernel(const L
     const unsigned T = (unsigned)c.num_symbols, n = (unsigned)nb * kWave, K = (unsigned)kb * kWave;
     AFT_DEV_ASSERT(Ps >= 1 && Ps <= AFT_CHANSIM_MAX_PILOT_SCS && Pt >= 1 && Pt <= AFT_CHANSIM_MAX_PILOT_SYMBOLS && (unsigned)Pt <= T);
     AFT_DEV_ASSERT(waves >= 1 && waves <= kLdpcMaxWaves);
+    if constexpr (Masked) {
+        AFT_DEV_ASSERT(a.mask_stride >= 1);
+        if (__builtin_amdgcn_readfirstlane(a.mask[f * (size_t)a.mask_stride]) == 0) {      // the whole workgroup: no barrier has been met
+            if (tid < 3) a.counts[3 * f + tid] = 0;
+            if (a.bits != nullptr) {
+                const size_t per_frame = (size_t)a.blocks * K;  // B K <= 2^31
+                for (size_t i = (size_t)tid; i < per_frame; i += blockDim.x) a.bits[f * per_frame + i] = 0;
+            }
+            return;
+        }
+    }
     code_pilot_tables(c, tid, psc, before, psym);
     ldpc_edge_tables(a.base, tid, (int)blockDim.x, edge, first);
     __syncthreads();
@@ -128,8 +154,8 @@ int link_ldpc_waves(int base_cols, int edges, unsigned blocks) { return ldpc_wav
 
 hipError_t launch_link_ldpc(const aft_link &link, const float *llr, const unsigned long long *keys, int base_rows, int base_cols,
                             const int32_t *shifts, unsigned blocks, unsigned long long stride, float qgain, int offset, int max_iters,
-                            int32_t *counts, unsigned char *bits, int batch, hipStream_t st) {
-    LinkLdpcArgs a{};
+                            int32_t *counts, unsigned char *bits, const int32_t *mask, int mask_stride, int batch, hipStream_t st) {
+    LinkLdpcMaskedArgs a{};
     a.c = link;
     a.llr = llr; a.keys = keys; a.counts = counts; a.bits = bits;
     a.elems = (unsigned)((unsigned long long)link.num_scs * (unsigned long long)link.num_symbols - 1);
@@ -142,10 +168,19 @@ hipError_t launch_link_ldpc(const aft_link &link, const float *llr, const unsign
     if (!ldpc_edge_list(base_rows, base_cols, shifts, a.base)) return hipErrorInvalidValue;   // aft_link_ldpc_f32 has counted them
     const int waves = link_ldpc_waves(base_cols, a.base.edges, blocks);
     const size_t lds = (size_t)waves * ldpc_state_bytes(base_cols, a.base.edges);
-    static PerDeviceOnce lds_attr;
-    const hipError_t e = ensure_dynamic_lds(lds_attr, reinterpret_cast<const void *>(link_ldpc_kernel), kLdpcLdsBudget);
+    if (mask == nullptr) {
+        static PerDeviceOnce lds_attr;
+        const hipError_t e = ensure_dynamic_lds(lds_attr, reinterpret_cast<const void *>(link_ldpc_kernel<LinkLdpcArgs>), kLdpcLdsBudget);
+        if (e != hipSuccess) return e;
+        const LinkLdpcArgs plain = a;
+        hipLaunchKernelGGL(link_ldpc_kernel<LinkLdpcArgs>, dim3((unsigned)batch), dim3((unsigned)(waves * kWave)), lds, st, plain);
+        return hipGetLastError();
+    }
+    a.mask = mask; a.mask_stride = mask_stride;                 // the masked instantiation of the same body
+    static PerDeviceOnce masked_lds_attr;
+    const hipError_t e = ensure_dynamic_lds(masked_lds_attr, reinterpret_cast<const void *>(link_ldpc_kernel<LinkLdpcMaskedArgs>), kLdpcLdsBudget);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(link_ldpc_kernel, dim3((unsigned)batch), dim3((unsigned)(waves * kWave)), lds, st, a);
+    hipLaunchKernelGGL(link_ldpc_kernel<LinkLdpcMaskedArgs>, dim3((unsigned)batch), dim3((unsigned)(waves * kWave)), lds, st, a);
     return hipGetLastError();
 }
 

@@ -1,7 +1,7 @@
 // The two-stream link (include/adafortitran_amd.h "spatial multiplexing", "joint detection"; adafortitran_amd/linksim.py "the
-// spatial-multiplexing link" and "the joint link" are the definitions and the float64 twins): N = 2 streams on R antennas, ONE frame
-// walk, link2_walk, and three detectors in its step 4.  One workgroup per GROUP of 2 R consecutive frames -- frame r 2 + s is the pair
-// (antenna r, stream s) --, one launch per batch; a group's counts, losses and LLRs are a function of its own keys, noise scales,
+// spatial-multiplexing link", "the joint link", "the successive-cancellation link" and "the codeword-cancellation link" are the
+// definitions and the float64 twins): N = 2 streams on R antennas, ONE frame walk, link2_walk, and four detectors in its step 4.
+// One workgroup per GROUP of 2 R consecutive frames -- frame r 2 + s is the pair (antenna r, stream s) --, one launch per batch; a group's counts, losses and LLRs are a function of its own keys, noise scales,
 // weights, true channels and estimates and of its leader's LLR scale (and, for the linear detector, regulariser) only.  The walk is
 // k_link.hip's link_walk with the combiner replaced by a detector:
 //
@@ -49,6 +49,18 @@
 //          so the decoders read the tensor as they read the other detectors'.  Three more integers per thread -- elements detected
 //          in swapped order, first decisions with a symbol error, of those the ones whose other stream is wrong too -- are reduced
 //          with the counts; no scratch;
+//        codeword cancellation (link2_cancel; linksim.py "the codeword-cancellation link")  the second pass of a receiver that
+//          cancels a stream only after its decoder has acknowledged it.  `failed` holds the first pass's block-error count per
+//          (group, stream), read at a stride (the LDPC decoder's counts in place: counts + 1, stride 3); every thread forms
+//          redo_s = failed_s != 0 && failed_other == 0 from two wave-uniform words, so AT MOST ONE stream of a group is detected
+//          again.  A group without one skips the pilot lookup, the hashing and the antenna walk by a uniform branch and its pair
+//          loop only stores zeros.  Otherwise stream t = the one with redo: the SENT symbol of the acknowledged stream (link_sent's
+//          levels: an acknowledged codeword re-encodes to the sent bits) leaves m_t by link_sic_cancel's four fused multiply-adds,
+//          and link_walk's measures run on (c_t, g_tt) with the group's scale -- link2_sic's second stage, call for call, with the
+//          sent levels in the decided ones' place.  There is no stream loop: the detected stream's sums run in stream 0's registers
+//          and change places with the zeros after the walk when it is stream 1.  The element's eight sums are COPIED (`e = s ? e1 :
+//          e0`, as link2_sic's caller does): handed on as a reference to one of the two, both sets stayed in scratch, 68 bytes a
+//          lane.  The other stream's counts, losses and LLRs are zeros; state[g][s] = redo_s;
 //   5. per stream the two integer counts and the K float sums stay in registers and are reduced in link_walk's fixed order: shuffles
 //      in the wave, then the four waves through LDS.
 //
@@ -64,6 +76,7 @@
 //   link_sm_kernel     (aft_link_sm_f32)     the linear ZF / MMSE detector
 //   link_joint_kernel  (aft_link_joint_f32)  the joint max-log demapper
 //   link_sic_kernel    (aft_link_sic_f32)    ordered successive cancellation: the linear detector, then a diversity stage
+//   link_cancel_kernel (aft_link_cancel_f32) codeword cancellation: the acknowledged stream's sent symbol out, then a diversity stage
 #include "link_device.h"
 
 namespace aft {
@@ -78,8 +91,16 @@ struct Link2Args : LinkArgs {
     int *stats;
 };
 
+// what the codeword-cancellation launch adds: the first pass's block-error counts, failed[(g 2 + s) failed_stride], and the flags it
+// forms from them, state [groups][2], which may be NULL.  Its own struct: the other three kernels' arguments stay as they are
+struct LinkCancelArgs : Link2Args {
+    const int *failed;
+    int failed_stride;
+    int *state;
+};
+
 // the detector of an instantiation's step 4
-constexpr int kLinear = 0, kJoint = 1, kSic = 2;
+constexpr int kLinear = 0, kJoint = 1, kSic = 2, kCancel = 3;
 constexpr int kSicStats = 3;
 
 // Step 4, linear: the M LLRs of stream `second` of an element with the sums e into w -- I-axis bits first, MSB first, the order of the
@@ -138,9 +159,23 @@ __device__ __forceinline__ LinkSicWrong link2_sic(float d, float d2, const LinkS
     return LinkSicWrong{first, other};
 }
 
-// One instantiation per modulation order and detector
-template <int M, int Det>
-__device__ __forceinline__ void link2_walk(const Link2Args &a) {
+// Step 4, codeword cancellation: the M LLRs of stream `second` of an element with the sums e into w after the SENT symbol xr + j xi of
+// the other stream has left its matched sum -- link2_sic's second stage with the sent levels --; returns the wrong bits against gi, gq
+template <int M>
+__device__ __forceinline__ int link2_cancel(float d, float d2, const LinkSm &e, float scale, bool second, float xr, float xi, unsigned gi,
+                                            unsigned gq, float *w) {
+    constexpr int half = M / 2, L = 1 << half;
+    const LinkBranch c = link_sic_cancel(e, !second, xr, xi);
+    const float step2 = d2 * c.p;
+    const unsigned oi = decide<L>(c.cr, step2), oq = decide<L>(c.ci, step2);
+    link_axis_llrs<L>(d, c.cr, c.p, scale, w);
+    link_axis_llrs<L>(d, c.ci, c.p, scale, w + half);
+    return __popc(gi ^ oi ^ (oi >> 1)) + __popc(gq ^ oq ^ (oq >> 1));
+}
+
+// One instantiation per modulation order and detector; Args is Link2Args, or LinkCancelArgs for the codeword-cancellation detector
+template <int M, int Det, class Args>
+__device__ __forceinline__ void link2_walk(const Args &a) {
     constexpr bool Joint = Det == kJoint;
     constexpr int kCounts = kSmStreams * 2 + (Det == kSic ? kSicStats : 0);
     __shared__ int psc[AFT_CHANSIM_MAX_PILOT_SCS], psym[AFT_CHANSIM_MAX_PILOT_SYMBOLS];
@@ -167,7 +202,16 @@ __device__ __forceinline__ void link2_walk(const Link2Args &a) {
     const unsigned long long k0 = bkey[0], k1 = a.keys[first + 1];      // one transmission per stream: the keys of frames (0, s)
     const float scale = a.scale[g];
     float reg = 0.f;
-    if constexpr (!Joint) reg = a.reg[g];
+    if constexpr (Det == kLinear || Det == kSic) reg = a.reg[g];
+    bool redo0 = false, redo1 = false;                          // codeword cancellation: wave-uniform, at most one of them set
+    if constexpr (Det == kCancel) {
+        AFT_DEV_ASSERT(a.failed_stride >= 1);
+        const size_t at = g * (size_t)kSmStreams * (size_t)a.failed_stride;
+        const int f0 = __builtin_amdgcn_readfirstlane(a.failed[at]), f1 = __builtin_amdgcn_readfirstlane(a.failed[at + (size_t)a.failed_stride]);
+        redo0 = f0 != 0 && f1 == 0;
+        redo1 = f1 != 0 && f0 == 0;
+    }
+    const bool go = Det != kCancel || redo0 || redo1;           // a constant for the other detectors
     float fac[kMaxFactors], acc0[kMaxFactors], acc1[kMaxFactors];
 #pragma unroll
     for (int k = 0; k < kMaxFactors; ++k) {
@@ -184,7 +228,7 @@ __device__ __forceinline__ void link2_walk(const Link2Args &a) {
         const unsigned q = 2 * i;
         const bool two = q < last;
         AFT_DEV_ASSERT(q <= last && (two || !a.wide));
-        const bool d0 = link_is_data(psc, Ps, psym, Pt, T, q), d1 = two && link_is_data(psc, Ps, psym, Pt, T, q + 1);
+        const bool d0 = go && link_is_data(psc, Ps, psym, Pt, T, q), d1 = go && two && link_is_data(psc, Ps, psym, Pt, T, q + 1);
         const LinkSent none{0u, 0u, 0.f, 0.f};
         LinkSent s00 = none, s01 = none, s10 = none, s11 = none;     // s<stream><element>
         if (d0) { s00 = link_sent<M>(a.d, k0, q); s10 = link_sent<M>(a.d, k1, q); }
@@ -192,7 +236,7 @@ __device__ __forceinline__ void link2_walk(const Link2Args &a) {
         const LinkSm zero{-0.f, -0.f, -0.f, -0.f, -0.f, -0.f, -0.f, -0.f};      // x + (-0) = x for every x
         LinkSm e0 = zero, e1 = zero;                            // the sums of elements q and q + 1
 #pragma unroll 1
-        for (int r = 0; r < R; ++r) {
+        for (int r = 0; r < (go ? R : 0); ++r) {
             LinkPair h0{}, g0{}, h1{}, g1{};                    // H and E of the pairs (r, 0) and (r, 1)
             const size_t at = (size_t)(kSmStreams * r) * frame + q;
             link_load_pairs(hp + at, ep + at, a.wide, two, h0, g0);
@@ -245,6 +289,36 @@ __device__ __forceinline__ void link2_walk(const Link2Args &a) {
                     if (lp != nullptr) link_store_element_llrs<M>(lp + ((size_t)t * frame + q + s) * M, w, a.store);
                 }
             }
+        } else if constexpr (Det == kCancel) {
+            // at most one stream of the group is detected again: stream 1 iff redo1 (wave-uniform).  Its sums run in acc0, bits0 and
+            // symbols0 whichever stream it is -- they change places with the other stream's zeros after the walk --, and the other
+            // stream stores zeros.  Without a redo d0 and d1 are false: nothing is detected and both streams store zeros
+            float v[2 * M], none[2 * M];
+#pragma unroll
+            for (int j = 0; j < 2 * M; ++j) v[j] = none[j] = 0.f;   // what a pilot position and a stream without redo carry
+#pragma unroll 1
+            for (int s = 0; s < 2; ++s) {                       // the element: one copy of the detector
+                if (s ? d1 : d0) {
+                    const LinkSent x0 = s ? s01 : s00, x1 = s ? s11 : s10;
+                    const LinkSent x = redo1 ? x1 : x0, xo = redo1 ? x0 : x1;
+                    const LinkSm e = s ? e1 : e0;
+                    float w[M];
+                    const int wrong = link2_cancel<M>(a.d, a.d2, e, scale, redo1, xo.xr, xo.xi, x.gi, x.gq, w);
+                    bits0 += wrong;
+                    symbols0 += wrong != 0 ? 1 : 0;
+                    link_soft_losses<M>(w, x.gi, x.gq, fac, nf, acc0);
+#pragma unroll
+                    for (int j = 0; j < M; ++j) {
+                        if (s) v[M + j] = w[j];
+                        else v[j] = w[j];
+                    }
+                }
+            }
+            if (lp != nullptr) {
+                const size_t again = redo1 ? 1 : 0;
+                link_store_llrs<M>(lp + (again * frame + q) * M, v, two ? 2 * M : M, a.store);
+                link_store_llrs<M>(lp + ((1 - again) * frame + q) * M, none, two ? 2 * M : M, a.store);
+            }
         } else {
 #pragma unroll 1
             for (int t = 0; t < kSmStreams; ++t) {              // the stream; the element inside: one copy of the detector
@@ -283,6 +357,17 @@ __device__ __forceinline__ void link2_walk(const Link2Args &a) {
             }
         }
     }
+    if constexpr (Det == kCancel) {
+        if (redo1) {                                            // wave-uniform: the sums are stream 1's, stream 0's are the zeros
+            bits1 = bits0; symbols1 = symbols0;
+            bits0 = symbols0 = 0;
+#pragma unroll
+            for (int k = 0; k < kMaxFactors; ++k) {
+                acc1[k] = acc0[k];
+                acc0[k] = 0.f;
+            }
+        }
+    }
     link_wave_sum(bits0, tid, ipart, 0);
     link_wave_sum(symbols0, tid, ipart, 1);
     link_wave_sum(bits1, tid, ipart, 2);
@@ -309,6 +394,10 @@ __device__ __forceinline__ void link2_walk(const Link2Args &a) {
         if (a.stats != nullptr && tid >= 2 * kWave && tid < 2 * kWave + kSicStats)
             a.stats[kSicStats * g + (tid - 2 * kWave)] = link_block_sum(ipart, 2 * kSmStreams + (tid - 2 * kWave));
     }
+    if constexpr (Det == kCancel) {                             // the third wave: the two flags
+        if (a.state != nullptr && tid >= 2 * kWave && tid < 2 * kWave + kSmStreams)
+            a.state[kSmStreams * g + (tid - 2 * kWave)] = (tid - 2 * kWave ? redo1 : redo0) ? 1 : 0;
+    }
 }
 
 template <int M>
@@ -324,6 +413,11 @@ __global__ __launch_bounds__(kFrameThreads) void link_joint_kernel(const Link2Ar
 template <int M>
 __global__ __launch_bounds__(kFrameThreads) void link_sic_kernel(const Link2Args a) {
     link2_walk<M, kSic>(a);
+}
+
+template <int M>
+__global__ __launch_bounds__(kFrameThreads) void link_cancel_kernel(const LinkCancelArgs a) {
+    link2_walk<M, kCancel>(a);
 }
 
 }  // namespace
@@ -347,6 +441,18 @@ hipError_t launch_link_sic(const aft_link &link, const float *ideal, const float
     const dim3 grid((unsigned)(batch / (branches * kSmStreams)));
     return link_dispatch(link.bits_per_symbol, [&](auto m) {
         hipLaunchKernelGGL(link_sic_kernel<decltype(m)::value>, grid, dim3(kFrameThreads), 0, st, a);
+    });
+}
+
+hipError_t launch_link_cancel(const aft_link &link, const float *ideal, const float *est, const unsigned long long *keys,
+                              const float *sigma, const float *rho, const float *scale, const float *factors, int n_factors, int branches,
+                              const int32_t *failed, int failed_stride, int32_t *counts, float *loss, float *llr, int32_t *state,
+                              int batch, hipStream_t st) {
+    const LinkCancelArgs a{{link_args(link, ideal, est, keys, sigma, rho, scale, factors, n_factors, branches, counts, loss, llr), nullptr,
+                            nullptr}, failed, failed_stride, state};
+    const dim3 grid((unsigned)(batch / (branches * kSmStreams)));
+    return link_dispatch(link.bits_per_symbol, [&](auto m) {
+        hipLaunchKernelGGL(link_cancel_kernel<decltype(m)::value>, grid, dim3(kFrameThreads), 0, st, a);
     });
 }
 

@@ -19,7 +19,7 @@ import torch
 
 from .estimators import AdaFortiTranEstimator
 from .linksim import (DEFAULT_FACTORS, BlockErrorAccumulator, HarqAccumulator, LdpcBlockErrorAccumulator, LdpcConfig, LinkAccumulator,
-                      RateAccumulator)
+                      RateAccumulator, _refuse_cwsic)
 from .lmmse import LmmseEstimator
 from .metrics import MseAccumulator, to_db
 
@@ -91,7 +91,9 @@ def get_link_stats(model: Optional[torch.nn.Module], test_dataloaders: List[Tupl
     (``linksim``: "the transmit-diversity link"): every batch holds a multiple of ``2 R`` frames in the same order, ``streams`` must
     be 1, ``detector`` is ignored, and the SNR is per transmit antenna.  ``precoding_subband=B`` sends ONE stream from the same two
     antennas co-phased by a codebook precoder picked per subband of ``B`` subcarriers from the estimate (``linksim``: "the closed-loop
-    link"): the same groups of ``2 R`` frames, ``streams`` must be 1 and ``tx_diversity`` None."""
+    link"): the same groups of ``2 R`` frames, ``streams`` must be 1 and ``tx_diversity`` None.  ``detector="cwsic"`` is refused: no
+    decoder runs here (``get_link_bler`` with an ``LdpcConfig`` has it)."""
+    _refuse_cwsic(detector, "get_link_stats", 'detector="sic" is the symbol-level cancellation it runs')
     return _link_sweep(model, test_dataloaders,
                        lambda device: LinkAccumulator(link_cfg, device, seed, branches, streams, detector, tx_diversity=tx_diversity,
                                                       precoding_subband=precoding_subband),
@@ -106,7 +108,9 @@ def get_link_rates(model: Optional[torch.nn.Module], test_dataloaders: List[Tupl
     channel knowledge.  Sorting, keys and the frames' bits and noise as ``get_link_stats``; the losses accumulate on the device
     (``linksim.RateAccumulator``) and are read once per loader.  ``branches``, ``streams`` and ``detector`` as ``get_link_stats``: the rate is per
     transmission, with two streams per stream and symbol (the spectral efficiency is twice it).  ``tx_diversity`` as
-    ``get_link_stats``: the rate of the one stream the two antennas send; ``precoding_subband`` likewise."""
+    ``get_link_stats``: the rate of the one stream the two antennas send; ``precoding_subband`` likewise.  ``detector="cwsic"`` is
+    refused, as by ``get_link_stats``."""
+    _refuse_cwsic(detector, "get_link_rates", 'detector="sic" is the symbol-level cancellation it runs')
     return _link_sweep(model, test_dataloaders, lambda device: RateAccumulator(link_cfg, device, seed, factors, branches=branches,
                                                                                streams=streams, detector=detector,
                                                                                tx_diversity=tx_diversity,
@@ -124,7 +128,9 @@ def get_link_bler(model: Optional[torch.nn.Module], test_dataloaders: List[Tuple
     as ``get_link_stats``; the counts accumulate on the device and are read once per loader.  ``branches`` as ``get_link_stats``: the
     decoder reads the combiner's LLRs with the leaders' keys; ``streams`` and ``detector`` likewise: the decoder reads each stream's
     LLRs with the key of frame ``(0, s)``; ``tx_diversity`` as ``get_link_stats``: the decoder reads the Alamouti combiner's LLRs with
-    the leaders' keys; ``precoding_subband`` likewise, on the closed-loop link's LLRs."""
+    the leaders' keys; ``precoding_subband`` likewise, on the closed-loop link's LLRs.  ``detector="cwsic"`` with ``streams=2`` and an
+    ``LdpcConfig`` is codeword-level cancellation (``linksim``: "the codeword-cancellation link"): the rate returned is the one AFTER
+    the second pass; an accumulator of one's own (``LdpcBlockErrorAccumulator``) also reads ``result_first_pass`` and ``cwsic_stats``."""
     accumulator = LdpcBlockErrorAccumulator if isinstance(code_cfg, LdpcConfig) else BlockErrorAccumulator
     return _link_sweep(model, test_dataloaders,
                        lambda device: accumulator(code_cfg, device, seed, err_var, branches, streams, detector, tx_diversity=tx_diversity,

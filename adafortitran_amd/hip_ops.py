@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Dict, Optional
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
@@ -687,6 +687,58 @@ class LinkSicPlan(LinkSmPlan):
         return self._grouped("aft_link_sic_f32", ideal, est, keys, sigma, rho, [("scale", scale), ("reg", reg)], factors, want_llr, lib)
 
 
+def _strided_words(name: str, t: torch.Tensor, device: torch.device, count: int) -> Tuple[int, int]:
+    """``(address, stride in int32 units)`` of the int32 words a kernel on ``device`` reads IN PLACE through a one-dimensional view of
+    ``count`` elements with a positive stride -- a column of the decoder's counts, say -- on the device or in pinned host memory."""
+    if not torch.is_tensor(t) or t.dtype != torch.int32:
+        raise ValueError(f"{name} must be torch.int32, got {t.dtype if torch.is_tensor(t) else type(t).__name__}")
+    if t.dim() != 1 or t.numel() != count:
+        raise ValueError(f"{name} must hold one value per row ({count}) in one dimension, got shape {tuple(t.shape)}")
+    stride = t.stride(0) if count > 1 else 1
+    if stride < 1:
+        raise ValueError(f"{name} must be read at a stride of at least 1 (its view has stride {stride})")
+    if not _readable_in_place(t, device):
+        raise ValueError(f"{name} must live on {device} or in pinned host memory (it is on {t.device}, not pinned)")
+    return t.data_ptr(), stride
+
+
+class LinkCancelPlan(LinkSmPlan):
+    """The second pass of codeword-level cancellation on ``LinkSmPlan``'s link and layout (``linksim``: "the codeword-cancellation
+    link"): a stream whose first-pass decoding failed while the other stream's passed is detected again after the acknowledged
+    stream's SENT symbol has left its matched sum.  ``plan(ideal, est, keys, sigma, rho, scale, failed, factors, want_llr=False,
+    want_state=True)`` -> ``LinkSmPlan``'s three tensors -- zeros for every stream that is not detected again -- and ``state int32
+    [G, 2]`` (1 where a stream was detected again; None without ``want_state``): four ``torch.empty`` at the most, one ``ctypes``
+    call, one launch (``aft_link_cancel_f32``) on the current stream, no synchronisation.  ``failed`` is a one-dimensional int32 view
+    of ``2 G`` first-pass block-error counts, row ``g 2 + s`` stream ``s`` of group ``g``, with any positive stride -- column 1 of
+    ``LinkLdpcPlan``'s counts as it stands -- on the plan's device or in pinned host memory; the kernel reads it in place.  There is no
+    ``reg``; everything else as ``LinkSmPlan``."""
+    cpu_path = "linksim.link_cancel_host"
+
+    def __call__(self, ideal: torch.Tensor, est: torch.Tensor, keys: torch.Tensor, sigma: torch.Tensor, rho: torch.Tensor,
+                 scale: torch.Tensor, failed: torch.Tensor, factors: torch.Tensor, want_llr: bool = False, want_state: bool = True,
+                 lib=None):
+        lib = lib or _lib.load()
+        batch, ideal, est, keys, sigma = self._checked(ideal, est, keys, sigma)
+        width = self.branches * self.streams
+        if batch % width:
+            raise ValueError(f"a batch of {batch} frames is not a multiple of branches * streams = {self.branches} * {self.streams}")
+        groups = batch // width
+        rows = groups * self.streams
+        rho = _in_place("rho", rho, torch.float32, self.device, batch)
+        scale = _in_place("scale", scale, torch.float32, self.device, groups)
+        failed_ptr, failed_stride = _strided_words("failed", failed, self.device, rows)
+        factors = self._checked_factors(factors)
+        counts = torch.empty((rows, 2), dtype=torch.int32, device=self.device)                  # the kernel writes every element
+        loss = torch.empty((rows, factors.numel()), dtype=torch.float32, device=self.device)
+        llr = torch.empty((rows, *self.grid, self.cfg.bits_per_symbol), dtype=torch.float32, device=self.device) if want_llr else None
+        state = torch.empty((groups, self.streams), dtype=torch.int32, device=self.device) if want_state else None
+        _lib.check(lib.aft_link_cancel_f32(C.byref(self.link), ideal.data_ptr(), est.data_ptr(), keys.data_ptr(), sigma.data_ptr(),
+                                           rho.data_ptr(), scale.data_ptr(), factors.data_ptr(), factors.numel(), self.branches,
+                                           self.streams, failed_ptr, failed_stride, counts.data_ptr(), loss.data_ptr(), _ptr(llr),
+                                           _ptr(state), batch, _lib.current_stream_ptr(self.device)), lib)
+        return counts, loss, llr, state
+
+
 class LinkAlamoutiPlan(LinkPlan):
     """Transmit diversity on ``LinkPlan``'s link: two transmit antennas send ONE stream as Alamouti pairs over adjacent data symbols
     (``pairing="time"``) or subcarriers (``"frequency"``) and ``branches`` receive antennas combine (``linksim``: "the transmit-diversity
@@ -763,7 +815,9 @@ class _DecoderPlan:
         self.link = code.link.to_struct()                       # validated by the config itself; the entry point checks again
         self.shape = (*code.link.sim.ofdm, code.link.bits_per_symbol)
 
-    def __call__(self, llr: torch.Tensor, keys: torch.Tensor, want_bits: bool = False, lib=None):
+    def __call__(self, llr: torch.Tensor, keys: torch.Tensor, want_bits: bool = False, lib=None, *, _entry=None, _selection=None):
+        """``_entry`` / ``_selection``: a subclass's second entry point and what it takes between the code's arguments and ``counts``
+        (``LinkLdpcPlan``'s mask), as a function of the batch."""
         lib = lib or _lib.load()
         if llr.dim() != 4 or tuple(llr.shape[1:]) != self.shape or llr.shape[0] < 1:
             raise ValueError(f"Expected llr shape (B >= 1, {self.shape[0]}, {self.shape[1]}, {self.shape[2]}), got {tuple(llr.shape)}")
@@ -777,10 +831,11 @@ class _DecoderPlan:
         if batch % self.frames_per_group:
             raise ValueError(f"a batch of {batch} frames is not a multiple of rounds = {self.frames_per_group}")
         groups = batch // self.frames_per_group
+        selection = () if _selection is None else _selection(batch)
         counts = torch.empty((groups, self.width), dtype=torch.int32, device=self.device)   # the kernel writes every element
         bits = torch.empty((groups, self.code.blocks, self.code.info_bits), dtype=torch.uint8, device=self.device) if want_bits else None
-        _lib.check(getattr(lib, self.entry)(C.byref(self.link), llr.data_ptr(), keys.data_ptr(), *self.args, counts.data_ptr(), _ptr(bits),
-                                            batch, _lib.current_stream_ptr(self.device)), lib)
+        _lib.check(getattr(lib, _entry or self.entry)(C.byref(self.link), llr.data_ptr(), keys.data_ptr(), *self.args, *selection,
+                                                      counts.data_ptr(), _ptr(bits), batch, _lib.current_stream_ptr(self.device)), lib)
         return counts, bits
 
 
@@ -810,6 +865,16 @@ class LinkLdpcPlan(_DecoderPlan):
         self.shifts = (C.c_int32 * (code.base_rows * kb))(*(v for row in code.shifts for v in row))      # host memory, read per call
         self.args = (code.base_rows, code.base_cols, C.addressof(self.shifts), code.stride, code.stride_inverse, code.qgain, code.offset,
                      code.max_iters)
+
+    def __call__(self, llr: torch.Tensor, keys: torch.Tensor, want_bits: bool = False, lib=None, mask: Optional[torch.Tensor] = None):
+        """``mask=None``: ``aft_link_ldpc_f32``.  ``mask``: a one-dimensional int32 view of ``batch`` words with any positive stride, on
+        the plan's device or in pinned host memory, read in place by ``aft_link_ldpc_masked_f32`` -- the same kernel body --: a frame
+        whose word is 0 is not decoded and gets counts ``(0, 0, 0)`` and zero bits; every other frame gets ``aft_link_ldpc_f32``'s
+        outputs, bit for bit."""
+        if mask is None:
+            return super().__call__(llr, keys, want_bits, lib)
+        return super().__call__(llr, keys, want_bits, lib, _entry="aft_link_ldpc_masked_f32",
+                                _selection=lambda batch: _strided_words("mask", mask, self.device, batch))
 
 
 class LinkHarqPlan(_DecoderPlan):

@@ -209,6 +209,43 @@ and stream 0 is detected first everywhere.  ``sic_propagation()`` of a sweep rea
 symbol-level, ordered, hard-decision MMSE-SIC on per-pair estimates.  It does not model codeword-level or soft cancellation,
 iterative detection and decoding, ``N > 2``, or HARQ (``HarqAccumulator`` gets no keyword, as today).
 
+The codeword-cancellation link.  Symbol-level cancellation trusts hard symbol decisions, and most wrong first decisions repeat on the
+other stream.  A two-codeword receiver cancels AFTER the decoder: a stream is subtracted only once its CRC has passed, so nothing wrong
+is ever cancelled, and the estimate matters twice -- the receiver cancels ``E_ro x_o``, not ``H_ro x_o``, so the estimation error of the
+cancelled stream stays behind as interference.  ``link_cancel_host`` (float64), ``cwsic_redetect``, ``link_cwsic_host``,
+``aft_link_cancel_f32`` (csrc/k_linksm.hip, through ``hip_ops.LinkCancelPlan``), ``aft_link_ldpc_masked_f32`` (csrc/k_linkldpc.hip,
+``hip_ops.LinkLdpcPlan(..., mask=)``) and ``detector="cwsic"`` (``CWSIC_DETECTOR``; ``CODED_DETECTORS`` lists it after
+``LINK2_DETECTORS``) on ``LdpcBlockErrorAccumulator`` and ``evaluation.get_link_bler`` are that receiver.  Two streams on ``R = 2 .. 8``
+antennas with the frame layout, keys, samples, weights and sums of the spatial-multiplexing link; an LDPC code on each stream; a
+stream's transport block is the ``B`` blocks of its frame::
+
+    first pass   MMSE detection of both streams: exactly link_sm_host / aft_link_sm_f32 with reg = float32(1 / scale); then LDPC decoding
+                 of both: exactly link_ldpc_host / aft_link_ldpc_f32 on the 2 G frames with the keys of frames (0, s).
+                 failed[g][s] = (the stream's block-error count != 0): an ideal CRC over all its blocks
+    flags        redo[g][s] = failed[g][s] and not failed[g][1 - s]  (cwsic_redetect).  Both pass or both fail: nothing more happens
+    cancel       for a stream s with redo, o = 1 - s, per data element:  c = m_s - g_so x_o,  g_so = g01 for s = 0 and conj(g01) for s = 1,
+                 x_o the SENT symbol of stream o (an acknowledged codeword re-encodes to exactly the sent bits; filler bits are known
+                 to the receiver);  p = g_ss.   Device: the successive-cancellation link's four fused multiply-adds (link_sic_cancel)
+    re-detect    the diversity link's hard decision, errors, mu_k, Delta_j, Lambda_j = scale Delta_j and losses on (c, p) with the
+                 group's scale: no regulariser, no division -- the successive-cancellation link's second stage with the sent symbol,
+                 what link_sic_host(genie=True) computes for its second-detected stream.  A stream without redo has all-zero
+                 outputs in this stage: LLRs, counts and losses
+    second pass  LDPC decoding of the re-detected streams only (aft_link_ldpc_masked_f32 with the flags as its mask: a frame whose
+                 word is 0 is not decoded and counts (0, 0, 0))
+    final        a stream's bit and block errors are the second pass's where redo, the first pass's elsewhere; its iterations are
+                 the sum of both passes
+
+The residual ``(H_ro - E_ro) x_o`` that an imperfect estimate leaves in ``c`` is NOT modelled in the scale: the same simplification as the
+successive-cancellation link's second stage, and the reason the share of re-detected streams that decode separates the estimators.
+Blocks that a re-detected stream had acknowledged in the first pass are not kept separately: the unit is the stream, a known
+simplification (a re-detected stream may lose a block it had; a per-block union would only lower the numbers).  Reaches for the
+comparison of a float32 evaluation are the successive-cancellation link's second stage: ``reach(c) = reach(m_s) + G01 |x_o|`` and
+``p_reach = g_ss``, with the sent symbol exact on both sides; flags, ``q`` and the loss interval as on the diversity link.  With an
+unheard other stream (``H_ro = E_ro = 0``) a re-detected stream 0 is the diversity link on the frames ``(r, 0)``.  What this models:
+hard, codeword-level, one-shot cancellation behind an ideal CRC.  It does not model a per-block union, soft or iterative cancellation,
+HARQ, or ``N > 2``; ``"cwsic"`` is refused wherever no LDPC decoder runs (``LinkAccumulator``, ``RateAccumulator``,
+``BlockErrorAccumulator``, ``HarqAccumulator``, ``streams=1``, ``tx_diversity=``, ``precoding_subband=``).
+
 The transmit-diversity link.  The third standard two-antenna mode sends ONE stream from two transmit antennas as Alamouti pairs:
 space-time block coding over adjacent symbols or space-frequency block coding over adjacent subcarriers, what cell-edge and control
 transmissions of current OFDM systems run.  The pair is orthogonal only while the channel is equal across its two elements: time
@@ -976,6 +1013,89 @@ def link_sic_host(cfg: LinkConfig, keys, ideal, est, sigma, rho, scale, reg, bra
     return out
 
 
+# ---- the codeword-cancellation link (module docstring, "The codeword-cancellation link"): float64 / integer NumPy, mirrored by
+# ---- csrc/k_linksm.hip (the cancel detector) and csrc/k_linkldpc.hip (the masked decoder) ----
+
+CWSIC_DETECTOR = "cwsic"
+#: every name ``detector=`` takes somewhere; ``"cwsic"`` only on ``LdpcBlockErrorAccumulator`` and ``evaluation.get_link_bler``
+CODED_DETECTORS = LINK2_DETECTORS + (CWSIC_DETECTOR,)
+_CWSIC_ONLY = ('detector="cwsic" decodes between its two detections: it runs on LdpcBlockErrorAccumulator(code, device, branches=R, '
+               'streams=2, detector="cwsic") and evaluation.get_link_bler(..., detector="cwsic") with an LdpcConfig only')
+
+
+def _refuse_cwsic(detector, what: str, instead: str) -> None:
+    if isinstance(detector, str) and detector == CWSIC_DETECTOR:
+        raise ValueError(f'{what} has no detector="cwsic": {_CWSIC_ONLY}; {instead}')
+
+
+def cwsic_redetect(failed) -> np.ndarray:
+    """Step 2 of the codeword-cancellation link: ``failed`` ``[..., 2]`` (anything non-zero counts as failed: block-error counts do) ->
+    bool ``[..., 2]``, ``redo[..., s] = failed[..., s] and not failed[..., 1 - s]``.  At most one stream of a group is set."""
+    failed = np.asarray(failed) != 0
+    if failed.ndim < 1 or failed.shape[-1] != MAX_STREAMS:
+        raise ValueError(f"failed must hold {MAX_STREAMS} streams on its last axis, got shape {failed.shape}")
+    return failed & ~failed[..., ::-1]
+
+
+def link_cancel_host(cfg: LinkConfig, keys, ideal, est, sigma, rho, scale, branches, redo, streams=2, factors=(1.0,),
+                     tau: Optional[float] = None, e_lambda: Optional[float] = None):
+    """Step 3 of the codeword-cancellation link (module docstring) in float64: the operands of ``link_sm_host`` without ``reg``, and
+    ``redo`` bool ``[G, N]`` (``cwsic_redetect``; at most one stream per group) -> ``(counts int64 [G, N, 2], loss float64 [G, N, K], llr
+    float64 [G, N, S, T, m])``, all zeros for a stream without ``redo``.  With ``tau`` the wrong-bit map ``[G, N, S, T]`` and the flags
+    ``[G, N, S, T, 2]`` follow, with ``e_lambda`` then ``loss_lo``, ``loss_hi`` and ``q``: what ``link_sic_host`` returns for its second
+    stream, on ``reach = reach(m_s) + G01 |x_o|`` and ``p_reach = g_ss``; zeros (False) without ``redo``.  Needs no library."""
+    keys, H, E, sigma = _checked(cfg, keys, ideal, est, sigma)
+    (G, R, N, S, T), sent, ms, gss, rm, g01, G01, scale = _sm_sums(cfg, keys, H, E, sigma, rho, scale, branches, streams)
+    redo = np.asarray(redo)
+    if redo.shape != (G, N) or redo.dtype != np.bool_:
+        raise ValueError(f"redo must be bool of shape ({G}, {N}), got {redo.dtype} {redo.shape}")
+    if (redo.sum(axis=1) > 1).any():
+        raise ValueError("redo: at most one stream of a group is detected again (cwsic_redetect)")
+    zero = np.zeros((G, S, T))                                                   # a batch of all-pilot grids keeps its shapes
+    c = np.stack([(ms[0] + zero) - g01 * sent[1][2], (ms[1] + zero) - np.conj(g01) * sent[0][2]], axis=1)    # m_s - g_so x_o
+    p = np.stack([gss[0] + zero, gss[1] + zero], axis=1)
+    reach = np.stack([(rm[0] + zero) + G01 * np.abs(sent[1][2]), (rm[1] + zero) + G01 * np.abs(sent[0][2])], axis=1)
+    sc = np.broadcast_to((scale + zero)[:, None], c.shape)
+    flat = lambda v: np.ascontiguousarray(v).reshape(G * N, S, T)  # noqa: E731
+    gi, gq = (flat(np.stack([sent[0][i], sent[1][i]], axis=1)) for i in (0, 1))
+    hard = _hard(cfg, gi, gq, flat(c), flat(p), flat(reach), tau)
+    soft = _soft(cfg, gi, gq, flat(c), flat(p), flat(reach), flat(sc), factors, e_lambda)
+    out = ((hard,) if tau is None else hard[:1]) + soft[:2] + (() if tau is None else hard[1:]) + soft[2:]
+    out = tuple(v.reshape(G, N, *v.shape[1:]) for v in out)
+    keep = lambda v: np.where(redo.reshape(G, N, *(1,) * (v.ndim - 2)), v, np.zeros((), v.dtype))  # noqa: E731   without redo: zeros
+    return tuple(keep(v) for v in out)
+
+
+def link_cwsic_host(code: "LdpcConfig", keys, ideal, est, sigma, rho, scale, reg, branches):
+    """The codeword-cancellation link (module docstring) on its host twins: the operands of ``link_sm_host`` for the two streams, ``reg``
+    the first pass's (``detector_reg(scale, "mmse")`` by the definition) -> ``(first int64 [G, 2, 3], redo bool [G, 2], second int64
+    [G, 2, 3], final int64 [G, 2, 3])``: the decoder's counts (information-bit errors, block errors, iterations) of the first pass,
+    the flags, the second pass's counts (zeros without ``redo``) and the final ones -- the second pass's bit and block errors where
+    ``redo``, the first pass's elsewhere, the iterations of both passes summed.  Needs no library."""
+    if not isinstance(code, LdpcConfig):
+        raise ValueError(f"link_cwsic_host needs an LdpcConfig (got {type(code).__name__})")
+    cfg = code.link
+    llr = link_sm_host(cfg, keys, ideal, est, sigma, rho, scale, reg, branches)[2]
+    G, N = llr.shape[:2]
+    sent_keys = np.ascontiguousarray(_keys64(keys).reshape(G, -1, N)[:, 0, :]).reshape(-1)       # the keys of frames (0, s)
+    first = link_ldpc_host(code, sent_keys, llr.reshape(G * N, *llr.shape[2:]))[0].reshape(G, N, 3)
+    redo = cwsic_redetect(first[..., 1])
+    second = np.zeros_like(first)
+    if redo.any():                                                               # decode the streams detected again, and only them
+        again = link_cancel_host(cfg, keys, ideal, est, sigma, rho, scale, branches, redo)[2]
+        pick = redo.reshape(-1)
+        second.reshape(G * N, 3)[pick] = link_ldpc_host(code, sent_keys[pick], again.reshape(G * N, *again.shape[2:])[pick])[0]
+    return first, redo, second, cwsic_final(first, redo, second)
+
+
+def cwsic_final(first, redo, second) -> np.ndarray:
+    """Step 4: the second pass's bit and block errors where ``redo``, the first pass's elsewhere; the iterations of both passes."""
+    first, second = np.asarray(first), np.asarray(second)
+    final = np.where(np.asarray(redo, dtype=bool)[..., None], second, first)
+    final[..., 2] = first[..., 2] + second[..., 2]
+    return final
+
+
 # ---- the transmit-diversity link (module docstring, "The transmit-diversity link"): float64 NumPy, mirrored by csrc/k_linkalamouti.hip ----
 
 PAIRINGS = ("time", "frequency")
@@ -1225,6 +1345,8 @@ class _FrameSweep:
     synchronises.  ``per_frame`` holds one float32 ``[b]`` operand per entry of ``of_snr``, pairs ``(numpy function, torch function on
     a float64 tensor)`` of the SNR in dB."""
 
+    _runs_cwsic = False                            # detector="cwsic" needs the LDPC decoder between its detections: one subclass has it
+
     def _open(self, cfg: LinkConfig, device, seed: int, want: str, branches: int = 1, err_var: float = 0.0, factors=(1.0,),
               streams: int = 1, detector: str = "mmse", tx_diversity: Optional[str] = None,
               precoding_subband: Optional[int] = None) -> None:
@@ -1239,6 +1361,14 @@ class _FrameSweep:
         if isinstance(streams, bool) or not isinstance(streams, (int, np.integer)) or int(streams) not in (1, MAX_STREAMS):
             raise ValueError(f"streams = {streams!r}: 1, or {MAX_STREAMS} for the spatial-multiplexing link")
         self.streams, self.detector, self.tx_diversity = int(streams), detector, tx_diversity
+        self._cwsic = isinstance(detector, str) and detector == CWSIC_DETECTOR
+        if self._cwsic:                            # codeword cancellation decodes between its detections: one accumulator runs it
+            if not self._runs_cwsic:
+                _refuse_cwsic(detector, type(self).__name__, 'detector="sic" is the symbol-level cancellation this accumulator runs')
+            if self.streams != MAX_STREAMS or tx_diversity is not None or precoding_subband is not None:
+                raise ValueError(f'detector="cwsic" cancels one of {MAX_STREAMS} spatial streams: streams must be {MAX_STREAMS} (got '
+                                 f"{self.streams}), tx_diversity None (got {tx_diversity!r}) and precoding_subband None (got "
+                                 f'{precoding_subband!r}); one stream from two antennas has nothing to cancel -- use detector="mmse" there')
         if tx_diversity is not None:
             _pairing(tx_diversity)
             if self.streams != 1:
@@ -1254,7 +1384,7 @@ class _FrameSweep:
         self._width =self.branches * (2 if self._pairs else self.streams)
         if self.streams > 1:
             _sm_shape(0, self.branches, self.streams)           # one antenna cannot separate two streams
-            _detector(detector)                                 # the detector's name: a linear one, "joint" or "sic"
+            _detector("mmse" if self._cwsic else detector)      # the detector's name: a linear one, "joint" or "sic"; "cwsic" starts as MMSE
         self.device = torch.device(device)
         soft = want != "counts"
         self._plan = None
@@ -2152,12 +2282,86 @@ class LdpcBlockErrorAccumulator(BlockErrorAccumulator):
     (information-bit errors, block errors, iterations) and ``result_iterations``, the mean iterations per block.  On a HIP device a
     batch is the launch of ``aft_link_soft_f32`` with its LLR output, the launch of ``aft_link_ldpc_f32`` on that tensor and one
     integer add; nothing synchronises.  On a CPU device the host definitions run.  Each result is one read and, with several ranks,
-    one all-gather of four float64.  ``branches``, ``streams``, ``detector`` and ``tx_diversity`` as ``BlockErrorAccumulator``'s."""
+    one all-gather of four float64.  ``branches``, ``streams``, ``detector`` and ``tx_diversity`` as ``BlockErrorAccumulator``'s; with
+    ``streams=2`` this accumulator alone also takes ``detector="cwsic"``, codeword-level cancellation (``__init__``)."""
 
     _config, _needs, _host_decoder, _decoder_plan, _columns = LdpcConfig, "an LdpcConfig", staticmethod(link_ldpc_host), "LinkLdpcPlan", 3
+    _runs_cwsic = True
+
+    def __init__(self, code, device, seed: int = 0, err_var: float = 0.0, branches: int = 1, streams: int = 1,
+                 detector: str = "mmse", *, tx_diversity: Optional[str] = None, precoding_subband: Optional[int] = None) -> None:
+        """``streams=2, detector="cwsic"`` (module docstring, "the codeword-cancellation link"): MMSE detection and decoding of both
+        streams, then a stream that failed while the other passed is detected again with the acknowledged codeword cancelled, and decoded
+        again.  On a HIP device a batch is four launches -- ``aft_link_sm_f32``, ``aft_link_ldpc_f32``, ``aft_link_cancel_f32`` reading
+        the decoder's block errors in place, ``aft_link_ldpc_masked_f32`` reading the cancel kernel's flags -- and a ``torch.where`` and
+        three integer adds on the device; nothing synchronises.  On a CPU device ``link_cwsic_host`` runs.  ``result``, ``result_ber``
+        and ``result_throughput`` give the values AFTER cancellation, ``result_iterations`` both passes summed, ``result_first_pass`` the
+        block-error rate before cancellation (the ``detector="mmse"`` sweep's ``result``) and ``cwsic_stats`` what the second pass did."""
+        super().__init__(code, device, seed, err_var, branches, streams, detector, tx_diversity=tx_diversity,
+                         precoding_subband=precoding_subband)
+        if self._cwsic:
+            self._first = torch.zeros(3, dtype=torch.int64, device=self.device)          # the first pass's three counts
+            self._second = torch.zeros(3, dtype=torch.int64, device=self.device)         # streams detected again; of those decoded; groups both failed
+            self._cancel = None
+            if self._plan is not None:
+                from . import hip_ops
+                self._cancel = hip_ops.LinkCancelPlan(code.link, self.device, self.branches, self.streams)
+
+    def update(self, est: Optional[torch.Tensor], ideal: torch.Tensor, meta: Optional[tuple] = None, *, frame_ids=None,
+               snr_db=None) -> None:
+        if not self._cwsic:
+            return super().update(est, ideal, meta, frame_ids=frame_ids, snr_db=snr_db)
+        ops = self._operands(est, ideal, meta, frame_ids, snr_db, self._of_snr)
+        if ops is None:
+            return
+        b, H, E, keys, (sigma, scale) = ops
+        R, N = self.branches, self.streams
+        G = _grouped(b, R, N)
+        if self._plan is None:                     # the host twins, whole
+            rho, lead = _weights(scale, R * N)
+            first, redo, second, _ = link_cwsic_host(self.code, keys, H, E, sigma, rho, lead, detector_reg(lead, "mmse"), R)
+            first, second = (torch.from_numpy(v.reshape(G * N, 3)) for v in (first, second))
+            redo = torch.from_numpy(redo.reshape(G * N))
+        else:                                      # four launches; every operand of a later one is an earlier one's output, in place
+            rho, lead = self._device_weights(scale, R * N)
+            reg = (1.0 / lead.to(torch.float64)).to(torch.float32)
+            sent = keys.view(G, R, N)[:, 0, :].reshape(-1)
+            llr = self._launch(H, E, keys, sigma, rho, lead, reg, self._factors_t, want_llr=True)[2]
+            first = self._launch(llr, sent, plan=self._decode)[0]
+            _, _, llr, state = self._launch(H, E, keys, sigma, rho, lead, first[:, 1], self._factors_t, want_llr=True, plan=self._cancel)
+            second = self._launch(llr, sent, plan=self._decode, mask=state.view(-1))[0]
+            redo = state.view(-1) != 0
+        final = torch.where(redo[:, None], second, first)
+        final[:, 2] = first[:, 2] + second[:, 2]                                         # a stream without redo ran no second pass: 0
+        both = (first[:, 1].reshape(G, N) != 0).all(dim=1)
+        self.errors += self._total(final, torch.int64)
+        self._first += self._total(first, torch.int64)
+        self._second += torch.stack([redo.sum(), (redo & (second[:, 1] == 0)).sum(), both.sum()]).to(torch.int64)
+        self.frames += G * N
+
+    def _need_cwsic(self, what: str) -> None:
+        if not self._cwsic:
+            raise ValueError(f'{what} needs streams=2 and detector="cwsic": no other link decodes twice')
+
+    def result_first_pass(self, group=None) -> float:
+        """The block-error rate BEFORE cancellation over all ranks: what ``detector="mmse"`` gives on the same updates."""
+        self._need_cwsic("result_first_pass")
+        frames = torch.tensor([float(self.frames)], dtype=torch.float64, device=self.device)
+        _, block_errors, _, frames = self._all_ranks(torch.cat([self._first.to(torch.float64), frames]), group)
+        return block_errors / (frames * self.code.blocks) if frames > 0 else 0.0
+
+    def cwsic_stats(self, group=None) -> tuple:
+        """What the second pass did over the sweep, all ranks: ``(the share of streams detected again, the share of those streams then
+        decoded without a block error, the share of groups in which both streams failed -- where nothing can be cancelled)``; 0.0 where
+        a denominator is 0.  Summed on the device by one add per batch; one read, as the result's."""
+        self._need_cwsic("cwsic_stats")
+        frames = torch.tensor([float(self.frames)], dtype=torch.float64, device=self.device)
+        again, decoded, both, frames = self._all_ranks(torch.cat([self._second.to(torch.float64), frames]), group)
+        groups = frames / self.streams
+        return (again / frames if frames > 0 else 0.0, decoded / again if again > 0 else 0.0, both / groups if groups > 0 else 0.0)
 
     def result_iterations(self, group=None) -> float:
-        """Mean decoder iterations per block over all ranks; 0.0 for an empty sweep."""
+        """Mean decoder iterations per block over all ranks -- with ``detector="cwsic"`` both passes summed --; 0.0 for an empty sweep."""
         _, _, iterations, frames = self._read(group)
         return iterations / (frames * self.code.blocks) if frames > 0 else 0.0
 
@@ -2327,9 +2531,13 @@ class HarqAccumulator(BlockErrorAccumulator):
 
     _config, _needs, _host_decoder, _decoder_plan, _columns = HarqConfig, "a HarqConfig", staticmethod(link_harq_host), "LinkHarqPlan", HARQ_COUNTS
 
-    def __init__(self, code, device, seed: int = 0, err_var: float = 0.0, branches: int = 1) -> None:
+    def __init__(self, code, device, seed: int = 0, err_var: float = 0.0, branches: int = 1, **unknown) -> None:
         # no ``streams``: a group's rounds are consecutive LLR frames, which would be the two streams of one group; no ``tx_diversity``
-        # and no ``precoding_subband``: HARQ over Alamouti pairs or precoded transmissions is not defined here
+        # and no ``precoding_subband``: HARQ over Alamouti pairs or precoded transmissions is not defined here; no ``detector``: one
+        # stream has none.  A keyword it does not have stays a TypeError; ``detector="cwsic"`` is told where codeword cancellation runs
+        if unknown:
+            _refuse_cwsic(unknown.get("detector"), "HarqAccumulator", "HARQ runs on one stream, combined over `branches`")
+            raise TypeError(f"HarqAccumulator.__init__() got an unexpected keyword argument {next(iter(unknown))!r}")
         super().__init__(code, device, seed, err_var, branches)
 
     def update(self, est: Optional[torch.Tensor], ideal: torch.Tensor, meta: Optional[tuple] = None, *, frame_ids=None,

@@ -755,6 +755,53 @@ int aft_link_sic_f32(const aft_link *link, const float *ideal, const float *est,
                      float *llr /* [groups,streams,S,T,m] or NULL */, int32_t *stats /* [groups][3] or NULL */, int batch,
                      void *stream);
 
+/* ---- codeword-level cancellation: decode, cancel, detect again (adafortitran_amd/linksim.py "the codeword-cancellation link") ----
+ *
+ * A two-codeword receiver cancels a stream only after its decoder has acknowledged it (an ideal CRC: the decoded information bits
+ * equal the sent ones), so nothing wrong is ever cancelled.  The receiver is four launches: aft_link_sm_f32 with the MMSE reg and
+ * aft_link_ldpc_f32 on its llr (the first pass), then the two entry points below (the second pass).
+ *
+ * aft_link_cancel_f32: the layout, keys, sent words, received samples, weights, the eight sums and scale are aft_link_sm_f32's, formed
+ * by the same code: the fourth detector of the one frame walk.  There is no reg.
+ *   failed     int32, any device-addressable memory: failed[(g 2 + s) failed_stride] is the first pass's block-error count of stream s of
+ *              group g, failed_stride >= 1 in int32 units (aft_link_ldpc_f32's counts + 1 with stride 3 reads them in place)
+ *   redo       redo_s = failed_s != 0 and failed_(1-s) == 0: at most one stream per group; formed by the kernel, wave-uniform
+ *   cancel     for the stream s with redo, o = 1 - s, per data element: c_s = m_s - gx x_o with x_o the SENT symbol of stream o (an
+ *              acknowledged codeword re-encodes to the sent bits; filler bits are known) and gx = g01 for s = 0, conj(g01) for s = 1,
+ *              by aft_link_sic_f32's four fused multiply-adds; p_s = g_ss
+ *   detect     aft_link_mrc_f32's decision, errors, mu_k, Delta_j, Lambda_j = scale Delta_j and loss[f] on (c_s, p_s) with the LEADER's
+ *              scale: no regulariser, no division.  The residual (H_ro - E_ro) x_o that an imperfect estimate leaves is not modelled in
+ *              the scale, as in aft_link_sic_f32's second stage
+ *   outputs    counts, loss and llr are aft_link_sm_f32's tensors; a stream without redo has zeros in all three.  state int32
+ *              [groups][streams] (device memory; may be NULL, as llr may) holds redo_s as 0 / 1.  A group without a redo reads no
+ *              channel and hashes nothing
+ * One launch, one workgroup per group, every element of the outputs written, no atomics, no workspace, no division, nothing
+ * synchronised; a group's outputs depend neither on batch, nor on its position in it, nor on the run, nor on the load and store forms,
+ * nor on whether llr or state is written.  Where aft_link_sic_f32 detected stream s second after a correct first decision, the LLRs
+ * here are its second-stage LLRs bit for bit; with H_r1 = E_r1 = 0 stream 0 is aft_link_mrc_f32's on the frames (r, 0), bit for bit.
+ * Nothing is launched on AFT_ERR_ARG and AFT_ERR_SHAPE: what aft_link_sm_f32 refuses, less what it says of reg; a NULL or misaligned
+ * failed; failed_stride < 1; a state that is not 4-byte aligned. */
+int aft_link_cancel_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys,
+                        const float *sigma, const float *rho /* [batch] */, const float *scale /* [groups] */,
+                        const float *factors, int n_factors, int branches, int streams,
+                        const int32_t *failed /* [(groups * streams - 1) * failed_stride + 1] */, int failed_stride,
+                        int32_t *counts /* [groups][streams][2] */, float *loss /* [groups][streams][n_factors] */,
+                        float *llr /* [groups,streams,S,T,m] or NULL */, int32_t *state /* [groups][streams] or NULL */, int batch,
+                        void *stream);
+
+/* aft_link_ldpc_masked_f32: aft_link_ldpc_f32 on the frames a mask selects -- a second instantiation of the same kernel body.
+ * mask int32 (any device-addressable memory): frame f is decoded iff mask[f mask_stride] != 0, mask_stride >= 1 in int32 units
+ * (aft_link_cancel_f32's state with stride 1 selects the streams it detected again).  A selected frame gets exactly
+ * aft_link_ldpc_f32's counts and bits, bit for bit; a frame that is not selected gets counts (0, 0, 0) and, when bits is not NULL,
+ * zeros in its rows of bits: its workgroup leaves by a uniform branch before it reads an LLR.  Every element of counts and bits is
+ * written; the memory rules and invariants are aft_link_ldpc_f32's.
+ * Nothing is launched on AFT_ERR_ARG and AFT_ERR_SHAPE: what aft_link_ldpc_f32 refuses; a NULL or misaligned mask; mask_stride < 1. */
+int aft_link_ldpc_masked_f32(const aft_link *link, const float *llr /* [batch,S,T,m] */, const unsigned long long *keys, int base_rows,
+                             int base_cols, const int32_t *shifts /* HOST, [base_rows][base_cols - base_rows] */,
+                             unsigned long long stride, unsigned long long stride_inverse, float qgain, int offset, int max_iters,
+                             const int32_t *mask /* [(batch - 1) * mask_stride + 1] */, int mask_stride,
+                             int32_t *counts /* [batch][3] */, unsigned char *bits /* [batch,B,K] or NULL */, int batch, void *stream);
+
 /* ---- training path of the encoder ---- */
 
 /* Gradients of one nn.TransformerEncoderLayer: same fields and shapes as aft_layer_weights,
