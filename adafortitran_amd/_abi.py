@@ -59,6 +59,7 @@ class AftStepControl(C.Structure):
 AFT_CHANSIM_MAX_TAPS, AFT_CHANSIM_MAX_RAYS, AFT_CHANSIM_MAX_VALUES = 32, 16, 16
 AFT_CHANSIM_MAX_PILOT_SCS, AFT_CHANSIM_MAX_PILOT_SYMBOLS = 64, 16
 AFT_CHANSIM_MAX_GROUP = 16
+AFT_CHANSIM_MAX_SLOTS = 4096
 AFT_LINK_RATE_1_2, AFT_LINK_RATE_2_3, AFT_LINK_RATE_3_4 = 0, 1, 2
 AFT_LINK_CODE_MAX_INFO_BITS = 4090
 AFT_LINK_LDPC_Z, AFT_LINK_LDPC_MAX_EDGES = 64, 160
@@ -217,6 +218,8 @@ SIGNATURES = {
     "aft_channel_sim_f32": (C.c_int, [C.POINTER(AftChanSim), C.c_ulonglong] + [C.c_longlong] * 4 + [C.c_int, vp, vp, vp, vp]),
     "aft_channel_sim_group_f32": (C.c_int, [C.POINTER(AftChanSim), C.c_int, C.c_int, vp, C.c_ulonglong] + [C.c_longlong] * 4 +
                                   [C.c_int, vp, vp, vp, vp]),
+    "aft_channel_sim_seq_f32": (C.c_int, [C.POINTER(AftChanSim), C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_ulonglong] +
+                                [C.c_longlong] * 4 + [C.c_int, vp, vp, vp, vp]),
     "aft_lmmse_table_floats": (C.c_size_t, [C.POINTER(AftLmmse)]),
     "aft_lmmse_f32": (C.c_int, [C.POINTER(AftLmmse), vp, vp, vp, vp, vp, vp, C.c_int, vp]),
     "aft_link_errors_f32": (C.c_int, [C.POINTER(AftLink), vp, vp, vp, vp, vp, C.c_int, vp]),
@@ -232,6 +235,8 @@ SIGNATURES = {
     "aft_link_joint_f32": (C.c_int, [C.POINTER(AftLink), vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]),
     "aft_link_alamouti_f32": (C.c_int, [C.POINTER(AftLink), vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]),
     "aft_link_precoded_f32": (C.c_int, [C.POINTER(AftLink), vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp]),
+    "aft_link_precoded_delayed_f32": (C.c_int, [C.POINTER(AftLink), vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                vp, vp, vp, vp, C.c_int, vp]),
     "aft_link_sic_f32": (C.c_int, [C.POINTER(AftLink), vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp]),
     "aft_link_cancel_f32": (C.c_int, [C.POINTER(AftLink), vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp,
                                       C.c_int, vp]),

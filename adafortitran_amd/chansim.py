@@ -50,6 +50,30 @@ A frame is still a pure function of ``(seed, g)``.  The sources are independent 
 ``lmmse.py`` needs no change).  ``simulate_frames_host`` evaluates this in float64 on the float32-rounded ``mix`` for any vector of frame
 numbers, forming the sources it needs itself; ``aft_channel_sim_group_f32`` is the device's entry point.  With ``antennas = (1, 1)``
 (the default) nothing above applies: frames are independent draws with their own conditions, bit for bit what they were.
+
+Time continuity: slot sequences.  ``slots = K`` and ``slot_symbols = L`` (``None``: ``L = T``, back-to-back slots; ``L > T`` leaves a gap of
+``L - T`` symbols between slots) make every ``K G`` consecutive frames K consecutive SLOTS of one fading process, ``K L <=
+AFT_CHANSIM_MAX_SLOTS = 4096`` symbols.  Global frame ``g`` is in sequence ``seq = g // (K G)``, ``lead = seq K G``, slot
+``k = (g - lead) // G``, member ``a = g % G``: slot-major, the antennas inside a slot, so a slot's G frames are exactly the group the links'
+``branches=`` / ``streams=`` / ``precoding_subband=`` consume.  For frame ``g`` of a configuration with ``K > 1``:
+
+* conditions: the three condition indices are picked from the SEQUENCE leader's key ``frame_keys(seed, lead)`` -- a whole sequence shares
+  SNR, delay spread and Doppler (``frame_conditions``, ``SynthLoader``'s meta and ``make_pack`` follow);
+* sources: ``z_j``, ``j = 0 .. a``, use the angle and phase streams of the key of frame ``lead + j`` -- the sequence's leader plus ``j``, the
+  same rays in every slot;
+* time: slot ``k`` evaluates the rays at the absolute symbol ``k L + t``.  So that float32 error does not grow in the sine's argument, a ray
+  (turns per symbol ``rate``, phase ``phi`` in turns) first gets its slot's start phase ``phi_k = frac(fma(rate, float(k L), phi))``,
+  ``frac(x) = x - floor(x)``, ``k L`` exact in float32; the phase in the slot is then ``fma(rate, t, phi_k)`` as for one slot.  With ``k = 0``
+  ``phi_0 = phi`` exactly, ``phi`` lying in ``[0, 1)``.  The float64 twin does the same operations in float64;
+* everything else is the grouped frame's: the mixing by ``L[a][j]``, the delay phasors and the sum over the taps, the pilot noise from frame
+  ``g``'s OWN noise streams; the frame's key stays ``frame_keys(seed, g)``, so the links draw fresh bits and noise in every slot.
+
+A frame is still a pure function of ``(seed, g)``, and ``E[H_k[s,t] conj(H_k'[s,t'])] = J0(2 pi f_D ((k - k') L + t - t') T_sym)``: the
+slots of a sequence are one stretch of the process, which is what delayed feedback and retransmissions over a slow channel need.  A time
+shift of rays with independent uniform phases is another draw of the same process, so every frame ALONE keeps exactly the second-order
+statistics of an ungrouped frame (``lmmse.py`` and the estimators need no change).  ``simulate_frames_host`` evaluates this for any vector
+of frame numbers; ``aft_channel_sim_seq_f32`` is the device's entry point, whose position arguments count SEQUENCES.  With ``slots = 1``
+(the default) nothing of this paragraph applies, launch for launch.
 """
 from __future__ import annotations
 
@@ -99,6 +123,8 @@ class ChannelSimConfig:
     antennas: Tuple[int, int] = (1, 1)
     rx_correlation: Union[None, complex, Sequence] = None
     tx_correlation: Union[None, complex, Sequence] = None
+    slots: int = 1
+    slot_symbols: Optional[int] = None
 
     def __post_init__(self) -> None:
         S, T = (int(v) for v in self.ofdm)
@@ -146,11 +172,25 @@ class ChannelSimConfig:
         set_("antennas", (R, N))
         set_("rx_correlation", _correlation("rx_correlation", self.rx_correlation, R))
         set_("tx_correlation", _correlation("tx_correlation", self.tx_correlation, N))
+        K, L = self.slots, T if self.slot_symbols is None else self.slot_symbols
+        if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in (K, L)) or K < 1:
+            raise ValueError(f"slots = {self.slots!r}, slot_symbols = {self.slot_symbols!r}: slots an integer of at least 1, slot_symbols "
+                             f"an integer or None")
+        if L < T:
+            raise ValueError(f"slot_symbols = {L}: a slot spans at least the {T} symbols of the grid")
+        if K > 1 and K * L > _abi.AFT_CHANSIM_MAX_SLOTS:
+            raise ValueError(f"slots * slot_symbols = {K} * {L}: a sequence spans at most {_abi.AFT_CHANSIM_MAX_SLOTS} symbols")
+        set_("slots", int(K))
+        set_("slot_symbols", int(L))
 
     @property
     def group(self) -> int:
         """G = R N: the frames of one receiver."""
         return self.antennas[0] * self.antennas[1]
+
+    def sequence(self) -> int:
+        """K G: the frames of one slot sequence (the group's G with ``slots = 1``)."""
+        return self.slots * self.group
 
     def mix(self) -> np.ndarray:
         """complex64 ``[G, G]``: ``kron(chol(C_rx), chol(C_tx))``, formed in float64 and rounded once; lower triangular."""
@@ -259,14 +299,14 @@ def _pick(keys: np.ndarray, which: int, n: int) -> np.ndarray:
 
 def frame_conditions(cfg: ChannelSimConfig, seed: int, frame_ids) -> np.ndarray:
     """float32 ``[n, 3]``: the (snr_db, delay_spread_ns, doppler_hz) of each frame -- integer arithmetic on the hash, so host and
-    device agree exactly.  With a grouped configuration they are the LEADER's: one pick per group."""
+    device agree exactly.  With a grouped configuration they are the LEADER's: one pick per group, and one per sequence with ``slots > 1``."""
     return _conditions(cfg.tables(), frame_keys(seed, _leaders(cfg, frame_ids)))[0]
 
 
 def _leaders(cfg: ChannelSimConfig, frame_ids) -> np.ndarray:
-    """The frame whose key picks each frame's conditions: the frame itself, or the first of its group."""
+    """The frame whose key picks each frame's conditions: the frame itself, or the first of its group (of its sequence)."""
     g = np.asarray(frame_ids, dtype=np.int64)
-    return g if cfg.group == 1 else g - g % cfg.group
+    return g if cfg.sequence() == 1 else g - g % cfg.sequence()
 
 
 def _conditions(t: Dict[str, np.ndarray], keys: np.ndarray):
@@ -285,27 +325,33 @@ def simulate_frames_host(cfg: ChannelSimConfig, seed: int, frame_ids, return_noi
     S, T = cfg.ofdm
     Ps, Pt = cfg.pilot
     P, M = len(t["tap_delay"]), cfg.rays
-    G = cfg.group
-    meta, (i_snr, i_ds, i_dop) = _conditions(t, keys if G == 1 else frame_keys(seed, _leaders(cfg, frame_ids)))
+    G, K = cfg.group, cfg.slots
+    meta, (i_snr, i_ds, i_dop) = _conditions(t, keys if G * K == 1 else frame_keys(seed, _leaders(cfg, frame_ids)))
 
-    def tap_gains(kk, i_dop):                                                                              # [len(kk),P,T]
+    def tap_gains(kk, i_dop, first=None):                        # [len(kk),P,T]; first: the slots' first absolute symbols, k L
         kk = kk[:, None, None]
         ray = (16 * np.arange(P)[:, None] + np.arange(M)[None, :])[None]                                   # [1,P,M]
         u = (words(kk, STREAM_ANGLE, ray) >> np.uint64(44)).astype(np.float64) * 2.0 ** -20
         phase = (words(kk, STREAM_PHASE, ray) >> np.uint64(40)).astype(np.float64) * 2.0 ** -24            # turns
         rate = t["doppler_turns"].astype(np.float64)[i_dop][:, None, None] * np.cos(2.0 * np.pi * (np.arange(M)[None, None, :] + u) / M)
+        if first is not None:                                    # the slot's start phase, reduced: phi_k = frac(rate k L + phi)
+            phase = rate * first.astype(np.float64)[:, None, None] + phase
+            phase = phase - np.floor(phase)
         turns = rate[..., None] * np.arange(T)[None, None, None, :] + phase[..., None]                     # [n,P,M,T]
         return t["tap_amp"].astype(np.float64)[None, :, None] * np.exp(2j * np.pi * (turns - np.floor(turns))).sum(axis=2)
 
-    if G == 1:
+    if G * K == 1:
         gain = tap_gains(keys, i_dop)
     else:                                                        # the sources of every group that occurs, once; then row a of `mix`
         g = np.asarray(frame_ids, dtype=np.int64)
-        lead, where = np.unique(g - g % G, return_inverse=True)
-        dop_of = np.empty(len(lead), dtype=np.int64)
+        unit, where = np.unique(g // G, return_inverse=True)    # a group: slot unit % K of the sequence unit // K
+        lead = unit // K * (K * G)                               # the sources' keys are the sequence leader's plus j, whatever the slot
+        dop_of = np.empty(len(unit), dtype=np.int64)
         dop_of[where] = i_dop
-        z = tap_gains(frame_keys(seed, (lead[:, None] + np.arange(G)[None, :]).ravel()), np.repeat(dop_of, G)).reshape(len(lead), G, P, T)
-        gain = np.einsum("nj,njpt->npt", t["mix"].astype(np.complex128)[g % G], z[where])
+        first = np.repeat(unit % K * cfg.slot_symbols, G) if K > 1 else None
+        z = tap_gains(frame_keys(seed, (lead[:, None] + np.arange(G)[None, :]).ravel()), np.repeat(dop_of, G), first)
+        z = z.reshape(len(unit), G, P, T)
+        gain = np.einsum("nj,njpt->npt", t["mix"].astype(np.complex128)[g % G], z[where]) if G > 1 else z[where, 0]
     per_sc = t["delay_turns"].astype(np.float64)[i_ds][:, None] * t["tap_delay"].astype(np.float64)[None, :]             # [n,P]
     x = per_sc[:, :, None] * np.arange(S)[None, None, :]                                                   # [n,P,S]
     phasor = np.exp(-2j * np.pi * (x - np.floor(x)))
@@ -335,8 +381,9 @@ def make_pack(cfg: ChannelSimConfig, n: int, seed: int, snr_db=None, delay_sprea
     an estimator has to beat."""
     if n < 1:
         raise ValueError(f"make_pack needs n >= 1 (got {n})")
-    if n % cfg.group:
-        raise ValueError(f"make_pack needs whole groups: n = {n} is not a multiple of the {cfg.group} frames of antennas = {cfg.antennas}")
+    if n % cfg.sequence():
+        raise ValueError(f"make_pack needs whole {'groups' if cfg.slots == 1 else 'sequences'}: n = {n} is not a multiple of the "
+                         f"{cfg.sequence()} frames of {_unit_text(cfg)}")
     cfg = _pinned(cfg, snr_db, delay_spread_ns, doppler_hz)
     ideal, pilots, cond = simulate_frames_host(cfg, seed, np.arange(n))
     ideal, pilots = ideal.astype(np.complex64), pilots.astype(np.complex64)
@@ -350,6 +397,11 @@ def make_pack(cfg: ChannelSimConfig, n: int, seed: int, snr_db=None, delay_sprea
     meta[:, 1:4] = cond
     return {"h_ideal": ideal, "h_ls_sparse": sparse, "h_ls_full": ls_interpolate(cfg, pilots), "meta": meta,
             "channel_type": np.asarray([CHANNEL_TYPE] * n)}
+
+
+def _unit_text(cfg: ChannelSimConfig) -> str:
+    """What the frames of one unit -- a group, or a sequence of slots of groups -- are the frames of, for an error message."""
+    return f"antennas = {cfg.antennas}" if cfg.slots == 1 else f"slots = {cfg.slots} x antennas = {cfg.antennas}"
 
 
 def ls_interpolate(cfg: ChannelSimConfig, pilots: np.ndarray) -> np.ndarray:
@@ -391,7 +443,8 @@ class SynthLoader:
 
     With a grouped configuration (``cfg.antennas``, G frames per group) the unit of all of the above is the GROUP: ``batch_size`` and
     ``frames_per_epoch`` must be multiples of G, the ranks share out, wrap and drop whole groups, ``epoch_frames`` returns whole groups in
-    order, and a batch is one launch of ``aft_channel_sim_group_f32``.  With G = 1 nothing changes."""
+    order, and a batch is one launch of ``aft_channel_sim_group_f32``.  With G = 1 nothing changes.  With slot sequences (``cfg.slots``
+    = K > 1) the unit is the SEQUENCE of ``K G`` frames in the same way, and a batch is one launch of ``aft_channel_sim_seq_f32``."""
 
     def __init__(self, cfg: ChannelSimConfig, batch_size: int, frames_per_epoch: int, device: Union[str, torch.device] = "cpu",
                  seed: int = 0, rank: int = 0, world_size: int = 1, drop_last: bool = False, fresh_each_epoch: bool = True) -> None:
@@ -400,10 +453,10 @@ class SynthLoader:
         if frames_per_epoch < 1:
             raise ValueError(f"frames_per_epoch must be at least 1 (got {frames_per_epoch})")
         self.cfg, self.batch_size, self.n = cfg, int(batch_size), int(frames_per_epoch)
-        self._G = cfg.group
+        self._G = cfg.sequence()                                 # the unit: a group, or a sequence of slots of groups
         if self.batch_size % self._G or self.n % self._G:
             raise ValueError(f"batch_size = {batch_size} and frames_per_epoch = {frames_per_epoch} must be multiples of the {self._G} "
-                             f"frames of antennas = {cfg.antennas}")
+                             f"frames of {_unit_text(cfg)}")
         self.device = torch.device(device)
         self.seed, self.rank, self.world_size = int(seed), int(rank), int(world_size)
         self.drop_last, self.fresh_each_epoch = bool(drop_last), bool(fresh_each_epoch)

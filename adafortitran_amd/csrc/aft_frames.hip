@@ -206,9 +206,12 @@ bool ldpc_code_ok(const char *who, int base_rows, int base_cols, const int32_t *
 }
 
 // What both simulator entry points ask: the pointers, the batch, the group rx x tx (the ungrouped entry point passes 1 x 1 and no
-// mix), the frame (group) numbers -- every FRAME number stays below 2^63 --, the struct, and a finite mix; 0 = fine
+// mix), the frame (group) numbers -- every FRAME number stays below 2^63 --, the struct, and a finite mix; 0 = fine.  The sequence entry
+// point passes its slots (the others 1): the unit that base, start, stride and modulo count, and batch is a multiple of, is then the
+// sequence of slots * rx * tx frames
 int check_chansim(const char *who, const aft_chansim *sim, const float *mix, int rx, int tx, long long base, long long start,
-                  long long stride, long long modulo, int batch, const float *ideal, const float *pilots, const float *meta) {
+                  long long stride, long long modulo, int batch, const float *ideal, const float *pilots, const float *meta,
+                  int slots = 1) {
     AFT_REQUIRE(sim && ideal && pilots && meta, "%s: NULL pointer argument", who);
     AFT_REQUIRE(aligned(8, ideal, pilots), "%s: ideal and pilots must be 8-byte aligned", who);
     AFT_REQUIRE(aligned(4, meta, mix), "%s: %s must be 4-byte aligned", who, mix ? "meta and mix" : "meta");
@@ -217,10 +220,14 @@ int check_chansim(const char *who, const aft_chansim *sim, const float *mix, int
         !within(who, "rx * tx", rx * tx, 1, AFT_CHANSIM_MAX_GROUP))
         return AFT_ERR_SHAPE;
     const int group = rx * tx;
-    AFT_REQUIRE(batch % group == 0, "%s: batch = %d is not a multiple of rx * tx = %d * %d", who, batch, rx, tx);
-    const long long far = (1LL << 62) / group;
+    const int unit = slots * group;                            // slots <= AFT_CHANSIM_MAX_SLOTS: checked by the caller
+    if (slots == 1)
+        AFT_REQUIRE(batch % group == 0, "%s: batch = %d is not a multiple of rx * tx = %d * %d", who, batch, rx, tx);
+    else
+        AFT_REQUIRE(batch % unit == 0, "%s: batch = %d is not a multiple of slots * rx * tx = %d * %d * %d", who, batch, slots, rx, tx);
+    const long long far = (1LL << 62) / unit;
     AFT_REQUIRE(base >= 0 && start >= 0 && stride >= 1 && modulo >= 1 && base < far && modulo < far && start < far &&
-                    stride <= (far - start) / (batch / group),
+                    stride <= (far - start) / (batch / unit),
                 "%s: bad frame numbers (base %lld, start %lld, stride %lld, modulo %lld: base, start >= 0, stride, modulo >= 1, "
                 "all frame numbers below 2^62)", who, base, start, stride, modulo);
     if (!grid_ok(who, *sim, 1 << 20) || !within(who, "taps", sim->taps, 1, AFT_CHANSIM_MAX_TAPS) ||
@@ -254,6 +261,24 @@ int aft_channel_sim_group_f32(const aft_chansim *sim, int rx, int tx, const floa
     hipError_t e = launch_channel_sim_group(*sim, rx * tx, mix, seed, base, start, stride, modulo, batch, ideal, pilots, meta,
                                             static_cast<hipStream_t>(stream));
     return e == hipSuccess ? AFT_OK : hip_fail("channel_sim_group", e);
+}
+
+// The group entry point's checks with the sequence as the unit, after the slots: slots and slots * slot_symbols within
+// AFT_CHANSIM_MAX_SLOTS, slot_symbols no shorter than the grid (AFT_ERR_SHAPE, as a dimension beyond its bound)
+int aft_channel_sim_seq_f32(const aft_chansim *sim, int rx, int tx, const float *mix, int slots, int slot_symbols,
+                            unsigned long long seed, long long base, long long start, long long stride, long long modulo, int batch,
+                            float *ideal, float *pilots, float *meta, void *stream) {
+    const char *who = "channel sim seq";
+    AFT_REQUIRE(mix && sim, "channel sim seq: NULL pointer argument");
+    if (!within(who, "slots", slots, 1, AFT_CHANSIM_MAX_SLOTS) ||
+        !within(who, "slot_symbols", slot_symbols, sim->num_symbols > 1 ? sim->num_symbols : 1, AFT_CHANSIM_MAX_SLOTS) ||
+        !within(who, "slots * slot_symbols", slots * slot_symbols, 1, AFT_CHANSIM_MAX_SLOTS))
+        return AFT_ERR_SHAPE;
+    const int rc = check_chansim(who, sim, mix, rx, tx, base, start, stride, modulo, batch, ideal, pilots, meta, slots);
+    if (rc != AFT_OK) return rc;
+    hipError_t e = launch_channel_sim_seq(*sim, rx * tx, mix, slots, slot_symbols, seed, base, start, stride, modulo, batch, ideal, pilots,
+                                          meta, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? AFT_OK : hip_fail("channel_sim_seq", e);
 }
 
 size_t aft_lmmse_table_floats(const aft_lmmse *plan) {
@@ -490,6 +515,30 @@ int aft_link_precoded_f32(const aft_link *link, const float *ideal, const float 
     hipError_t e = launch_link_precoded(*link, ideal, est, keys, sigma, rho, scale, factors, n_factors, branches, subband, counts, loss,
                                         llr, pmi, batch, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? AFT_OK : hip_fail("link_precoded", e);
+}
+
+// aft_link_precoded_f32's refusals, then the slots, the delay and the batch against the sequence of slots * branches * 2 frames
+int aft_link_precoded_delayed_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys,
+                                  const float *sigma, const float *rho, const float *scale, const float *factors, int n_factors,
+                                  int branches, int subband, int slots, int delay, int32_t *counts, float *loss, float *llr,
+                                  int32_t *pmi, int batch, void *stream) {
+    const char *who = "link precoded delayed";
+    if (check_front(who, link, ideal, est, keys, {sigma, rho, scale, factors, counts, loss, pmi},
+                    "sigma, rho, scale, factors, counts, loss, pmi and llr", llr, batch, n_factors, 1) != AFT_OK)
+        return AFT_ERR_ARG;
+    if (!within(who, "branches", branches, 1, AFT_LINK_MAX_BRANCHES)) return AFT_ERR_ARG;
+    AFT_REQUIRE(batch % (branches * 2) == 0, "%s: batch = %d is not a multiple of branches * 2 = %d * 2", who, batch, branches);
+    if (!within(who, "subband", subband, 1, link->num_scs)) return AFT_ERR_ARG;
+    const int n_sub = (link->num_scs - 1) / subband + 1;
+    AFT_REQUIRE(n_sub <= AFT_LINK_MAX_SUBBANDS, "%s: subband = %d makes %d subbands of the %d subcarriers, more than %d", who, subband,
+                n_sub, link->num_scs, AFT_LINK_MAX_SUBBANDS);
+    AFT_REQUIRE(slots >= 1, "%s: slots must be at least 1 (got %d)", who, slots);
+    AFT_REQUIRE(delay >= 0 && delay < slots, "%s: delay = %d is outside 0 .. slots - 1 = %d", who, delay, slots - 1);
+    AFT_REQUIRE((batch / (branches * 2)) % slots == 0, "%s: batch = %d is not a multiple of slots * 2 * branches = %d * 2 * %d", who, batch,
+                slots, branches);
+    hipError_t e = launch_link_precoded_delayed(*link, ideal, est, keys, sigma, rho, scale, factors, n_factors, branches, subband, slots,
+                                                delay, counts, loss, llr, pmi, batch, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? AFT_OK : hip_fail("link_precoded_delayed", e);
 }
 
 }  // extern "C"

@@ -370,6 +370,11 @@ hipError_t launch_channel_sim(const aft_chansim &sim, unsigned long long seed, l
 hipError_t launch_channel_sim_group(const aft_chansim &sim, int group, const float *mix_packed, unsigned long long seed, long long base,
                                     long long start, long long stride, long long modulo, int batch, float *ideal, float *pilots,
                                     float *meta, hipStream_t st);
+// ... and its sequence instantiation: `slots` slots of `group` frames per sequence, `slot_symbols` symbols from one slot's start to the
+// next; base, start, stride and modulo count sequences, batch is a multiple of slots * group
+hipError_t launch_channel_sim_seq(const aft_chansim &sim, int group, const float *mix_packed, int slots, int slot_symbols,
+                                  unsigned long long seed, long long base, long long start, long long stride, long long modulo,
+                                  int batch, float *ideal, float *pilots, float *meta, hipStream_t st);
 
 // the LMMSE baseline estimator (k_lmmse.hip): `plan` has passed aft_lmmse_f32's checks; the two sizes are the per-delay-spread and
 // per-Doppler blocks of the table image (include/adafortitran_amd.h)
@@ -441,6 +446,12 @@ hipError_t launch_link_precoded(const aft_link &link, const float *ideal, const 
                                 const float *sigma, const float *rho, const float *scale, const float *factors, int n_factors,
                                 int branches, int subband, int32_t *counts, float *loss, float *llr, int32_t *pmi, int batch,
                                 hipStream_t st);
+// ... with delayed feedback: the batch is whole sequences of `slots` groups, slot k >= delay is sent with the PMIs selected from slot
+// k - delay; one workgroup per OUTPUT group, (slots - delay) per sequence; everything has passed aft_link_precoded_delayed_f32's checks
+hipError_t launch_link_precoded_delayed(const aft_link &link, const float *ideal, const float *est, const unsigned long long *keys,
+                                        const float *sigma, const float *rho, const float *scale, const float *factors, int n_factors,
+                                        int branches, int subband, int slots, int delay, int32_t *counts, float *loss, float *llr,
+                                        int32_t *pmi, int batch, hipStream_t st);
 hipError_t launch_mse(const float *est, const float *ref, double *sum_sq, long long n_complex, hipStream_t st);
 hipError_t launch_fill_lds(float value, hipStream_t st);   // test hook: every CU's LDS filled with `value`
 hipError_t launch_peek_lds(float *out, int workgroups, int n, hipStream_t st);   // ... and what a kernel finds in its LDS at start

@@ -23,7 +23,14 @@
 // frame lead + j is re-staged into the one `ray` array, and a thread adds L[a][j] z_j to the SAME (p, t) items it owns in every pass, so
 // the accumulation in `gain` / `pgain` needs no atomics and no barrier of its own (two barriers per source fence the ray table).  The
 // main pass and the pilots' noise (the frame's OWN key) are the ungrouped kernel's.  L[a][j] comes from the kernel-argument segment by a
-// wave-uniform index.  LDS is 12 KB in both instantiations -- ray 4 KB, gain 4 KB, pgain 4 KB -- whatever T and G are.
+// wave-uniform index.  LDS is 12 KB in every instantiation -- ray 4 KB, gain 4 KB, pgain 4 KB -- whatever T, G and K are.
+//
+// The sequence instantiation (aft_channel_sim_seq_f32; chansim.py "time continuity"): the grouped kernel on K G frames per sequence,
+// slot-major.  Output frame b is member b % G of slot (b / G) % K of its sequence; the conditions and the sources' keys come from the
+// SEQUENCE's leader, and the slot enters in one place only: stage_rays_slot moves every ray's phase to the slot's first symbol,
+// phi_k = frac(fma(rate, float(k L), phi)) -- one fused multiply-add and one floor per ray, k L exact in float32 -- so tap_gain and
+// everything after it are untouched and the float32 error of a phase does not grow with the slot's distance.  With k = 0 the phase is
+// the grouped kernel's bit for bit (phi is in [0, 1)).
 #include "frame_device.h"
 
 namespace aft {
@@ -39,6 +46,7 @@ struct ChanSimArgs {
     float *meta;
     int wide;                                      // 1: 16-byte stores into ideal
     static constexpr bool kGrouped = false;
+    static constexpr bool kSeq = false;
 };
 
 // The grouped launch: the ungrouped arguments (base, start, stride and modulo count GROUPS here) and the packed lower triangle of `mix`,
@@ -49,7 +57,13 @@ struct ChanSimGroupArgs : ChanSimArgs {
     float2 mix[kMixPacked];
     static constexpr bool kGrouped = true;
 };
-static_assert(sizeof(ChanSimGroupArgs) <= 4096, "kernel arguments travel by value: HIP's limit is 4 KB");
+// The sequence launch: the grouped arguments (base, start, stride and modulo count SEQUENCES here), the slots of a sequence and the
+// symbols from one slot's start to the next
+struct ChanSimSeqArgs : ChanSimGroupArgs {
+    int slots, slot_symbols;
+    static constexpr bool kSeq = true;
+};
+static_assert(sizeof(ChanSimSeqArgs) <= 4096, "kernel arguments travel by value: HIP's limit is 4 KB");
 
 __device__ __forceinline__ int sim_pick(unsigned long long kf, unsigned which, int n) {
     return (int)(((unsigned)(frame_word(kf, kStreamCondition, which) >> 40) * (unsigned)n) >> 24);    // 24-bit word x n <= 16: fits 32 bits
@@ -86,9 +100,23 @@ __device__ __forceinline__ void stage_rays(float2 *ray, unsigned long long kf, f
     }
 }
 
+// ... and the table of a later slot of the same rays: the phase moved to the slot's first symbol `first` = float(k L), reduced to [0, 1)
+__device__ __forceinline__ void stage_rays_slot(float2 *ray, unsigned long long kf, float dop, float first, int P, int M, int tid) {
+    for (int i = tid; i < P * M; i += kFrameThreads) {
+        const int p = i / M, m = i - p * M;
+        const unsigned idx = 16u * p + m;
+        const float u = (float)(unsigned)(frame_word(kf, kStreamRayAngle, idx) >> 44) * 0x1p-20f;        // m + u is exact: 4 + 20 bits
+        const float turn = ((float)m + u) / (float)M;
+        const float phase = (float)(unsigned)(frame_word(kf, kStreamRayPhase, idx) >> 40) * 0x1p-24f;
+        const float rate = dop * cospif(2.f * turn);
+        const float x = fmaf(rate, first, phase);
+        ray[i] = make_float2(rate, x - floorf(x));
+    }
+}
+
 template <class Args>
 __global__ __launch_bounds__(kFrameThreads) void channel_sim_kernel(const Args a) {
-    constexpr bool kGrouped = Args::kGrouped;
+    constexpr bool kGrouped = Args::kGrouped, kSeq = Args::kSeq;
     __shared__ float2 ray[AFT_CHANSIM_MAX_TAPS * AFT_CHANSIM_MAX_RAYS];
     __shared__ float2 gain[AFT_CHANSIM_MAX_TAPS][kFrameTile];
     __shared__ float2 pgain[AFT_CHANSIM_MAX_TAPS][AFT_CHANSIM_MAX_PILOT_SYMBOLS];
@@ -100,7 +128,17 @@ __global__ __launch_bounds__(kFrameThreads) void channel_sim_kernel(const Args a
     // modulo; kc, the LEADER's key, picks the conditions and kf, the frame's own, draws the pilots' noise
     unsigned long long g, lead = 0;
     int member = 0;
-    if constexpr (kGrouped) {
+    [[maybe_unused]] float first_symbol = 0.f;                 // the sequence kernel: float(k L), the slot's first absolute symbol
+    if constexpr (kSeq) {
+        // output frame b is member b % G of group `unit` = b / G of the batch, slot unit % K of the batch's sequence unit / K
+        const size_t unit = b / (size_t)a.group, seq = unit / (size_t)a.slots;
+        const int slot = (int)(unit - seq * (size_t)a.slots);
+        AFT_DEV_ASSERT(a.slots >= 1 && a.slot_symbols >= c.num_symbols && (long long)a.slots * a.slot_symbols <= AFT_CHANSIM_MAX_SLOTS);
+        member = (int)(b % (size_t)a.group);
+        lead = (a.base + (a.start + seq * a.stride) % a.modulo) * (unsigned long long)(a.group * a.slots);
+        g = lead + (unsigned long long)(slot * a.group + member);
+        first_symbol = (float)(slot * a.slot_symbols);
+    } else if constexpr (kGrouped) {
         member = (int)(b % (size_t)a.group);
         lead = (a.base + (a.start + (b / (size_t)a.group) * a.stride) % a.modulo) * (unsigned long long)a.group;
         g = lead + (unsigned long long)member;
@@ -132,7 +170,10 @@ __global__ __launch_bounds__(kFrameThreads) void channel_sim_kernel(const Args a
             AFT_DEV_ASSERT(member < a.group && a.group <= AFT_CHANSIM_MAX_GROUP);
             for (int j = 0; j <= member; ++j) {
                 if (!first || j > 0) __syncthreads();                   // the readers of `ray` (and the previous tile's of `gain`) are done
-                stage_rays(ray, splitmix64(a.seed_key ^ (lead + (unsigned long long)j)), dop, P, M, tid);
+                if constexpr (kSeq)
+                    stage_rays_slot(ray, splitmix64(a.seed_key ^ (lead + (unsigned long long)j)), dop, first_symbol, P, M, tid);
+                else
+                    stage_rays(ray, splitmix64(a.seed_key ^ (lead + (unsigned long long)j)), dop, P, M, tid);
                 __syncthreads();
                 const float2 l = a.mix[member * (member + 1) / 2 + j];
                 for (int i = tid; i < P * kFrameTile + (first ? P * Pt : 0); i += kFrameThreads) {    // item i has one owner in every pass
@@ -232,6 +273,19 @@ hipError_t launch_channel_sim_group(const aft_chansim &sim, int group, const flo
     a.group = group;
     for (int i = 0; i < group * (group + 1) / 2; ++i) a.mix[i] = make_float2(mix_packed[2 * i], mix_packed[2 * i + 1]);
     hipLaunchKernelGGL(channel_sim_kernel<ChanSimGroupArgs>, dim3((unsigned)batch), dim3(kFrameThreads), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_channel_sim_seq(const aft_chansim &sim, int group, const float *mix_packed, int slots, int slot_symbols,
+                                  unsigned long long seed, long long base, long long start, long long stride, long long modulo,
+                                  int batch, float *ideal, float *pilots, float *meta, hipStream_t st) {
+    ChanSimSeqArgs a{};
+    fill_args(a, sim, seed, base, start, stride, modulo, ideal, pilots, meta);
+    a.group = group;
+    for (int i = 0; i < group * (group + 1) / 2; ++i) a.mix[i] = make_float2(mix_packed[2 * i], mix_packed[2 * i + 1]);
+    a.slots = slots;
+    a.slot_symbols = slot_symbols;
+    hipLaunchKernelGGL(channel_sim_kernel<ChanSimSeqArgs>, dim3((unsigned)batch), dim3(kFrameThreads), 0, st, a);
     return hipGetLastError();
 }
 

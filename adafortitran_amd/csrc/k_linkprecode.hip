@@ -38,17 +38,26 @@
 // every sum of step 2 is 0, every PMI 0, the sample link_branch's and e_r = E_r0: the LLRs are link_mrc_kernel's on the frames
 // (r, 0), bit for bit.
 //
-//   link_precoded_kernel<M>  (aft_link_precoded_f32)
+// Delayed feedback (aft_link_precoded_delayed_f32; linksim.py "delayed feedback"): the batch is whole sequences of K slots, a slot one
+// group, and slot k >= d is sent with the PMIs selected from slot k - d.  The same walk, one workgroup per OUTPUT group
+// o = seq (K - d) + (k - d): step 2 reads the estimates and the weights rho of the FEEDBACK group seq K + k - d, steps 1 and 3 to 5 read the
+// TRANSMIT group seq K + k (true channels, estimates, keys, noise scales, weights, LLR scale), and every output is indexed by o.  Two
+// group numbers are all that differs: no second body, no workspace, no copy; with d = 0 they coincide and the kernel is
+// link_precoded_kernel's, bit for bit.
+//
+//   link_precoded_kernel<M>        (aft_link_precoded_f32)
+//   link_precode_delayed_kernel<M> (aft_link_precoded_delayed_f32)
 #include "link_device.h"
 
 namespace aft {
 namespace {
 
 // link_args' struct, the subband width in subcarriers, the number of subbands, the threads that sum one subband and the PMI output
-// [groups][n_sub]
+// [groups][n_sub]; the delayed kernel's slots per sequence and delay in slots behind them
 struct LinkPrecodeArgs : LinkArgs {
     int subband, n_sub, team;
     int *pmi;
+    int slots, delay;
 };
 
 // The threads that sum one subband: the power of two at or above the elements of a whole subband in 8 .. kWave, doubled up to
@@ -60,8 +69,8 @@ inline int link_precode_team(unsigned long long elements, int n_sub) {
     return w;
 }
 
-// One instantiation per modulation order
-template <int M>
+// One instantiation per modulation order and per feedback form
+template <int M, bool kDelayed>
 __device__ __forceinline__ void link_precoded_walk(const LinkPrecodeArgs &a) {
     constexpr int half = M / 2, L = 1 << half;
     __shared__ int psc[AFT_CHANSIM_MAX_PILOT_SCS], psym[AFT_CHANSIM_MAX_PILOT_SYMBOLS];
@@ -71,6 +80,7 @@ __device__ __forceinline__ void link_precoded_walk(const LinkPrecodeArgs &a) {
     __shared__ int ipart[kLinkWaves][2];
     __shared__ signed char table[AFT_LINK_MAX_SUBBANDS];       // the subbands' PMIs
     __shared__ float gpart[kLinkWaves][2];                      // the waves' sums of a team of several waves
+    __shared__ float frho[kDelayed ? AFT_LINK_MAX_BRANCHES : 1];  // the delayed kernel: the weights of the feedback group's frames (r, 0)
     const aft_link &c = a.c;
     const int tid = threadIdx.x;
     const size_t g = blockIdx.x;
@@ -80,17 +90,28 @@ __device__ __forceinline__ void link_precoded_walk(const LinkPrecodeArgs &a) {
     AFT_DEV_ASSERT(R >= 1 && R <= AFT_LINK_MAX_BRANCHES);
     AFT_DEV_ASSERT(B >= 1 && B <= S && n_sub == (S - 1) / B + 1 && n_sub <= AFT_LINK_MAX_SUBBANDS);
     AFT_DEV_ASSERT(a.team >= 8 && a.team <= kFrameThreads && (a.team & (a.team - 1)) == 0);
-    const size_t first = g * (size_t)(2 * R);                   // the group's leader, frame (0, 0)
+    // g numbers the outputs.  The inputs: gt the group that is sent, gf the group the PMIs are selected from -- both g without a delay
+    size_t gt = g, gf = g;
+    if constexpr (kDelayed) {
+        AFT_DEV_ASSERT(a.slots >= 1 && a.delay >= 0 && a.delay < a.slots);
+        const size_t sent = (size_t)(a.slots - a.delay), seq = g / sent;
+        gt = seq * (size_t)a.slots + (size_t)a.delay + (g - seq * sent);
+        gf = gt - (size_t)a.delay;
+    }
+    const size_t first = gt * (size_t)(2 * R);                  // the group's leader, frame (0, 0)
     link_stage_pilots(c, tid, psc, psym);
     if (tid >= 2 * kWave && tid - 2 * kWave < R) {              // the frames (r, 0): the antennas' noise keys, noise scales and weights
         const int r = tid - 2 * kWave;
         bkey[r] = a.keys[first + 2 * r];
         bsigma[r] = a.sigma[first + 2 * r];
         brho[r] = a.rho[first + 2 * r];
+        if constexpr (kDelayed) frho[r] = a.rho[gf * (size_t)(2 * R) + 2 * r];
     }
     __syncthreads();
     const size_t frame = (size_t)last + 1;                      // elements per frame
     const float2 *hp = a.ideal + first * frame, *ep = a.est + first * frame;
+    const float2 *sp = kDelayed ? a.est + gf * (size_t)(2 * R) * frame : ep;     // the estimates and weights the selection reads
+    const float *srho = kDelayed ? frho : brho;
     // the selection: team `team` the subbands team, team + teams, ..., one per round; every thread makes every round
     const unsigned W = (unsigned)a.team, teams = kFrameThreads / W, team = (unsigned)tid / W, l = (unsigned)tid & (W - 1);
     const unsigned rounds = (n_sub + teams - 1) / teams;
@@ -103,9 +124,9 @@ __device__ __forceinline__ void link_precoded_walk(const LinkPrecodeArgs &a) {
             const unsigned q0 = s0 * T, n = (s1 - s0) * T;      // n <= S T <= 2^31: e + W does not wrap
             AFT_DEV_ASSERT(s0 < S && (size_t)q0 + n <= frame);
             for (unsigned e = l; e < n; e += W) {
-                const float2 *eq = ep + q0 + e;
+                const float2 *eq = sp + q0 + e;
                 for (int r = 0; r < R; ++r)
-                    link_pmi_accumulate(gr, gi, brho[r], eq[(size_t)(2 * r) * frame], eq[(size_t)(2 * r + 1) * frame]);
+                    link_pmi_accumulate(gr, gi, srho[r], eq[(size_t)(2 * r) * frame], eq[(size_t)(2 * r + 1) * frame]);
             }
         }
 #pragma unroll
@@ -139,7 +160,7 @@ __device__ __forceinline__ void link_precoded_walk(const LinkPrecodeArgs &a) {
     }
     __syncthreads();
     const unsigned long long kl = bkey[0];                      // one transmission per group: the leader's key
-    const float scale = a.scale[g];
+    const float scale = a.scale[gt];
     float fac[kMaxFactors], acc[kMaxFactors];
 #pragma unroll
     for (int k = 0; k < kMaxFactors; ++k) {
@@ -192,7 +213,12 @@ __device__ __forceinline__ void link_precoded_walk(const LinkPrecodeArgs &a) {
 
 template <int M>
 __global__ __launch_bounds__(kFrameThreads) void link_precoded_kernel(const LinkPrecodeArgs a) {
-    link_precoded_walk<M>(a);
+    link_precoded_walk<M, false>(a);
+}
+
+template <int M>
+__global__ __launch_bounds__(kFrameThreads) void link_precode_delayed_kernel(const LinkPrecodeArgs a) {
+    link_precoded_walk<M, true>(a);
 }
 
 }  // namespace
@@ -203,12 +229,28 @@ hipError_t launch_link_precoded(const aft_link &link, const float *ideal, const 
                                 hipStream_t st) {
     const int n_sub = (link.num_scs - 1) / subband + 1;
     LinkPrecodeArgs a{link_args(link, ideal, est, keys, sigma, rho, scale, factors, n_factors, branches, counts, loss, llr), subband,
-                      n_sub, link_precode_team((unsigned long long)subband * (unsigned long long)link.num_symbols, n_sub), pmi};
+                      n_sub, link_precode_team((unsigned long long)subband * (unsigned long long)link.num_symbols, n_sub), pmi, 1, 0};
     a.wide = 0;                                                 // this walk loads and stores element by element
     a.store = link_llr_element_store_bytes(llr, link.bits_per_symbol);
     const dim3 grid((unsigned)(batch / (2 * branches)));
     return link_dispatch(link.bits_per_symbol, [&](auto m) {
         hipLaunchKernelGGL(link_precoded_kernel<decltype(m)::value>, grid, dim3(kFrameThreads), 0, st, a);
+    });
+}
+
+hipError_t launch_link_precoded_delayed(const aft_link &link, const float *ideal, const float *est, const unsigned long long *keys,
+                                        const float *sigma, const float *rho, const float *scale, const float *factors, int n_factors,
+                                        int branches, int subband, int slots, int delay, int32_t *counts, float *loss, float *llr,
+                                        int32_t *pmi, int batch, hipStream_t st) {
+    const int n_sub = (link.num_scs - 1) / subband + 1;
+    LinkPrecodeArgs a{link_args(link, ideal, est, keys, sigma, rho, scale, factors, n_factors, branches, counts, loss, llr), subband,
+                      n_sub, link_precode_team((unsigned long long)subband * (unsigned long long)link.num_symbols, n_sub), pmi, slots,
+                      delay};
+    a.wide = 0;                                                 // this walk loads and stores element by element
+    a.store = link_llr_element_store_bytes(llr, link.bits_per_symbol);
+    const dim3 grid((unsigned)(batch / (2 * branches) / slots * (slots - delay)));     // the output groups
+    return link_dispatch(link.bits_per_symbol, [&](auto m) {
+        hipLaunchKernelGGL(link_precode_delayed_kernel<decltype(m)::value>, grid, dim3(kFrameThreads), 0, st, a);
     });
 }
 

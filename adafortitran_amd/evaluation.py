@@ -75,7 +75,8 @@ def _link_sweep(model, test_dataloaders, make_acc, read) -> Dict[int, float]:
 
 def get_link_stats(model: Optional[torch.nn.Module], test_dataloaders: List[Tuple[str, Iterable]], link_cfg, seed: int = 0,
                    group=None, branches: int = 1, streams: int = 1, detector: str = "mmse",
-                   tx_diversity: Optional[str] = None, precoding_subband: Optional[int] = None) -> Dict[int, float]:
+                   tx_diversity: Optional[str] = None, precoding_subband: Optional[int] = None, precoding_delay: int = 0,
+                   slots: int = 1) -> Dict[int, float]:
     """Bit-error rate per loader on the link ``link_cfg`` (``linksim.LinkConfig``) defines: data symbols through each frame's true channel
     plus noise at the frame's SNR, equalised with the model's estimate; ``model=None`` is perfect channel knowledge.  Same sorting and
     keys as ``get_test_stats``; the estimate comes from ``forward_pass``, so every estimator here works; the counts accumulate on the
@@ -91,36 +92,41 @@ def get_link_stats(model: Optional[torch.nn.Module], test_dataloaders: List[Tupl
     (``linksim``: "the transmit-diversity link"): every batch holds a multiple of ``2 R`` frames in the same order, ``streams`` must
     be 1, ``detector`` is ignored, and the SNR is per transmit antenna.  ``precoding_subband=B`` sends ONE stream from the same two
     antennas co-phased by a codebook precoder picked per subband of ``B`` subcarriers from the estimate (``linksim``: "the closed-loop
-    link"): the same groups of ``2 R`` frames, ``streams`` must be 1 and ``tx_diversity`` None.  ``detector="cwsic"`` is refused: no
+    link"): the same groups of ``2 R`` frames, ``streams`` must be 1 and ``tx_diversity`` None.  ``precoding_delay=d`` with ``slots=K``
+    applies PMIs selected ``d`` slots earlier on loaders of ``ChannelSimConfig(slots=K)`` (``linksim``: "delayed feedback"): every batch
+    holds whole sequences of ``K 2 R`` frames, and the rate counts the transmitted slots only.  ``detector="cwsic"`` is refused: no
     decoder runs here (``get_link_bler`` with an ``LdpcConfig`` has it)."""
     _refuse_cwsic(detector, "get_link_stats", 'detector="sic" is the symbol-level cancellation it runs')
     return _link_sweep(model, test_dataloaders,
                        lambda device: LinkAccumulator(link_cfg, device, seed, branches, streams, detector, tx_diversity=tx_diversity,
-                                                      precoding_subband=precoding_subband),
+                                                      precoding_subband=precoding_subband, precoding_delay=precoding_delay, slots=slots),
                        lambda acc: acc.result(group))
 
 
 def get_link_rates(model: Optional[torch.nn.Module], test_dataloaders: List[Tuple[str, Iterable]], link_cfg, seed: int = 0,
                    factors=DEFAULT_FACTORS, group=None, branches: int = 1, streams: int = 1, detector: str = "mmse",
-                   tx_diversity: Optional[str] = None, precoding_subband: Optional[int] = None) -> Dict[int, float]:
+                   tx_diversity: Optional[str] = None, precoding_subband: Optional[int] = None, precoding_delay: int = 0,
+                   slots: int = 1) -> Dict[int, float]:
     """Achievable rate per loader in bit/symbol on the same link: the bit-interleaved coded-modulation rate (GMI) of the max-log LLRs a
     demapper forms with the model's estimate at the frame's SNR, the best of the LLR scale factors ``factors``; ``model=None`` is perfect
     channel knowledge.  Sorting, keys and the frames' bits and noise as ``get_link_stats``; the losses accumulate on the device
     (``linksim.RateAccumulator``) and are read once per loader.  ``branches``, ``streams`` and ``detector`` as ``get_link_stats``: the rate is per
     transmission, with two streams per stream and symbol (the spectral efficiency is twice it).  ``tx_diversity`` as
-    ``get_link_stats``: the rate of the one stream the two antennas send; ``precoding_subband`` likewise.  ``detector="cwsic"`` is
-    refused, as by ``get_link_stats``."""
+    ``get_link_stats``: the rate of the one stream the two antennas send; ``precoding_subband``, ``precoding_delay`` and ``slots``
+    likewise.  ``detector="cwsic"`` is refused, as by ``get_link_stats``."""
     _refuse_cwsic(detector, "get_link_rates", 'detector="sic" is the symbol-level cancellation it runs')
     return _link_sweep(model, test_dataloaders, lambda device: RateAccumulator(link_cfg, device, seed, factors, branches=branches,
                                                                                streams=streams, detector=detector,
                                                                                tx_diversity=tx_diversity,
-                                                                               precoding_subband=precoding_subband),
+                                                                               precoding_subband=precoding_subband,
+                                                                               precoding_delay=precoding_delay, slots=slots),
                        lambda acc: acc.result_gmi(group))
 
 
 def get_link_bler(model: Optional[torch.nn.Module], test_dataloaders: List[Tuple[str, Iterable]], code_cfg, seed: int = 0,
                   err_var: float = 0.0, group=None, branches: int = 1, streams: int = 1, detector: str = "mmse",
-                  tx_diversity: Optional[str] = None, precoding_subband: Optional[int] = None) -> Dict[int, float]:
+                  tx_diversity: Optional[str] = None, precoding_subband: Optional[int] = None, precoding_delay: int = 0,
+                  slots: int = 1) -> Dict[int, float]:
     """Block-error rate per loader with a decoder in the loop: the code ``code_cfg`` rides on the same link and its decoder reads the
     max-log LLRs the demapper forms with the model's estimate -- a ``linksim.CodeConfig`` is the convolutional code with a Viterbi
     decoder (``linksim.BlockErrorAccumulator``), a ``linksim.LdpcConfig`` the quasi-cyclic LDPC code with a layered min-sum decoder
@@ -128,13 +134,14 @@ def get_link_bler(model: Optional[torch.nn.Module], test_dataloaders: List[Tuple
     as ``get_link_stats``; the counts accumulate on the device and are read once per loader.  ``branches`` as ``get_link_stats``: the
     decoder reads the combiner's LLRs with the leaders' keys; ``streams`` and ``detector`` likewise: the decoder reads each stream's
     LLRs with the key of frame ``(0, s)``; ``tx_diversity`` as ``get_link_stats``: the decoder reads the Alamouti combiner's LLRs with
-    the leaders' keys; ``precoding_subband`` likewise, on the closed-loop link's LLRs.  ``detector="cwsic"`` with ``streams=2`` and an
+    the leaders' keys; ``precoding_subband`` likewise, on the closed-loop link's LLRs, and with ``precoding_delay`` and ``slots`` on
+    the transmitted slots' LLRs with the transmit slots' leader keys.  ``detector="cwsic"`` with ``streams=2`` and an
     ``LdpcConfig`` is codeword-level cancellation (``linksim``: "the codeword-cancellation link"): the rate returned is the one AFTER
     the second pass; an accumulator of one's own (``LdpcBlockErrorAccumulator``) also reads ``result_first_pass`` and ``cwsic_stats``."""
     accumulator = LdpcBlockErrorAccumulator if isinstance(code_cfg, LdpcConfig) else BlockErrorAccumulator
     return _link_sweep(model, test_dataloaders,
                        lambda device: accumulator(code_cfg, device, seed, err_var, branches, streams, detector, tx_diversity=tx_diversity,
-                                                  precoding_subband=precoding_subband),
+                                                  precoding_subband=precoding_subband, precoding_delay=precoding_delay, slots=slots),
                        lambda acc: acc.result(group))
 
 

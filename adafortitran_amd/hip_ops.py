@@ -429,6 +429,9 @@ class ChannelSimPlan:
     With a grouped configuration (``cfg.antennas``, G = R N frames per group) the launch is ``aft_channel_sim_group_f32``, the four
     position arguments count GROUPS -- output frame b is member ``b % G`` of group ``base + (start + (b // G) * stride) % modulo`` --
     and ``batch``, still in frames, is a multiple of G; the packed ``mix`` is host memory the plan keeps.
+    With slot sequences (``cfg.slots`` = K > 1) the launch is ``aft_channel_sim_seq_f32``, the four position arguments count SEQUENCES
+    of ``K G`` frames -- output frame b is member ``b % G`` of slot ``(b // G) % K`` of sequence ``base + (start + (b // (K G)) * stride)
+    % modulo`` -- and ``batch`` is a multiple of ``K G``.  With ``slots = 1`` the launches are the ones above.
     The plan trusts its caller in one thing only: its device is the current one."""
 
     def __init__(self, cfg, device: torch.device) -> None:
@@ -437,7 +440,8 @@ class ChannelSimPlan:
         self.sim = cfg.to_struct()                              # validated by the config itself; the entry point checks again
         self.grid, self.pilot = tuple(cfg.ofdm), tuple(cfg.pilot)
         self.antennas, self.group = tuple(cfg.antennas), cfg.group
-        self.mix = pack_mix(cfg.mix()) if self.group > 1 else None
+        self.slots, self.slot_symbols = cfg.slots, cfg.slot_symbols
+        self.mix = pack_mix(cfg.mix()) if self.group > 1 or self.slots > 1 else None
 
     def __call__(self, seed: int, base: int, start: int, stride: int, modulo: int, batch: int, lib=None):
         lib = lib or _lib.load()
@@ -445,6 +449,11 @@ class ChannelSimPlan:
         ideal = torch.empty((batch, *self.grid), dtype=torch.complex64, device=dev)      # the kernel writes every element
         pilots = torch.empty((batch, *self.pilot), dtype=torch.complex64, device=dev)
         meta = torch.empty((batch, 3), dtype=torch.float32, device=dev)
+        if self.slots > 1:
+            _lib.check(lib.aft_channel_sim_seq_f32(self.sim, *self.antennas, self.mix.ctypes.data, self.slots, self.slot_symbols,
+                                                   seed & 0xFFFFFFFFFFFFFFFF, base, start, stride, modulo, batch, ideal.data_ptr(),
+                                                   pilots.data_ptr(), meta.data_ptr(), _lib.current_stream_ptr(dev)), lib)
+            return ideal, pilots, meta
         if self.group > 1:
             _lib.check(lib.aft_channel_sim_group_f32(self.sim, *self.antennas, self.mix.ctypes.data, seed & 0xFFFFFFFFFFFFFFFF, base, start,
                                                      stride, modulo, batch, ideal.data_ptr(), pilots.data_ptr(), meta.data_ptr(),
@@ -517,6 +526,7 @@ class LinkPlan:
     pairs = False                                               # True: a group is branches * 2 frames and yields one row (LinkAlamoutiPlan)
     n_sub = None                                                # an integer: the launch also writes pmi int32 [rows, n_sub] (LinkPrecodedPlan)
     n_stats = None                                              # an integer: the launch also writes stats int32 [groups, n_stats] (LinkSicPlan)
+    slots, delay = 1, 0                                         # slots > 1: sequences of `slots` groups, feedback `delay` slots old (LinkPrecodedPlan)
 
     def __init__(self, cfg, device: torch.device) -> None:
         from .linksim import LinkConfig
@@ -566,6 +576,11 @@ class LinkPlan:
                              f"{' * '.join(('branches', '2' if pairs else 'streams')[:len(shape)])} = {' * '.join(map(str, shape))}")
         groups = batch // math.prod(shape)
         rows = groups if pairs else groups * math.prod(self.group[1:])
+        seq = (self.slots, self.delay)                          # LinkPrecodedPlan with delayed feedback: compact output rows
+        if seq[0] > 1:
+            if groups % seq[0]:
+                raise ValueError(f"a batch of {batch} frames is not a multiple of slots * 2 * branches = {seq[0]} * 2 * {shape[0]}")
+            rows = groups // seq[0] * (seq[0] - seq[1])
         rho = _in_place("rho", rho, torch.float32, self.device, batch)
         per_group = [_in_place(name, t, torch.float32, self.device, groups) for name, t in per_group]
         factors = self._checked_factors(factors)
@@ -577,7 +592,7 @@ class LinkPlan:
             pmi = (torch.empty((groups, self.n_stats), dtype=torch.int32, device=self.device),)
         _lib.check(getattr(lib, entry)(C.byref(self.link), ideal.data_ptr(), est.data_ptr(), keys.data_ptr(), sigma.data_ptr(),
                                        rho.data_ptr(), *(t.data_ptr() for t in per_group), factors.data_ptr(), factors.numel(),
-                                       *self.group, counts.data_ptr(), loss.data_ptr(), _ptr(llr), *(t.data_ptr() for t in pmi), batch,
+                                       *self.group, *(seq if seq[0] > 1 else ()), counts.data_ptr(), loss.data_ptr(), _ptr(llr), *(t.data_ptr() for t in pmi), batch,
                                        _lib.current_stream_ptr(self.device)), lib)
         return (counts, loss, llr, *pmi)
 
@@ -775,12 +790,21 @@ class LinkPrecodedPlan(LinkPlan):
     ``G = batch / (2 branches)`` groups on the plan's device, ``n_sub = ceil(S / subband)``: four ``torch.empty`` at the most, one
     ``ctypes`` call, one launch (``aft_link_precoded_f32``) on the current stream, no synchronisation.  ``rho`` (float32, ``batch``
     values) and ``scale`` (float32, ``G`` values: the leaders') are ``linksim.precoding_weights``'; they and ``factors`` live where
-    ``keys`` and ``sigma`` may.  Everything else as ``LinkMrcPlan``."""
+    ``keys`` and ``sigma`` may.  Everything else as ``LinkMrcPlan``.
+
+    Delayed feedback: with ``slots = K > 1`` the batch is whole sequences of K groups (the slots of ``ChannelSimConfig(slots=K)``) and
+    slot ``k >= delay`` is sent with the PMIs selected from slot ``k - delay`` of its sequence; slots ``k < delay`` are warm-up.  The four
+    outputs have ``(G / K) (K - delay)`` rows, row ``seq (K - delay) + (k - delay)``, ``pmi`` the APPLIED indices; the inputs, ``scale``
+    included, stay indexed by input frame or group.  One launch of ``aft_link_precoded_delayed_f32``; with ``slots = 1`` (then ``delay =
+    0``) the launch is ``aft_link_precoded_f32`` as it was."""
     cpu_path = "linksim.link_precoded_host"
     pairs = True
 
-    def __init__(self, cfg, device: torch.device, branches: int, subband: int) -> None:
+    def __init__(self, cfg, device: torch.device, branches: int, subband: int, slots: int = 1, delay: int = 0) -> None:
         super().__init__(cfg, device)
+        if any(isinstance(v, bool) or not isinstance(v, int) for v in (slots, delay)) or slots < 1 or not 0 <= delay < slots:
+            raise ValueError(f"slots = {slots!r}, delay = {delay!r}: integers with slots >= 1 and 0 <= delay < slots")
+        self.slots, self.delay = slots, delay
         if isinstance(branches, bool) or not isinstance(branches, int) or not 1 <= branches <= _abi.AFT_LINK_MAX_BRANCHES:
             raise ValueError(f"branches = {branches!r}: an integer in 1 .. {_abi.AFT_LINK_MAX_BRANCHES}")
         S = self.grid[0]
@@ -793,7 +817,9 @@ class LinkPrecodedPlan(LinkPlan):
 
     def __call__(self, ideal: torch.Tensor, est: torch.Tensor, keys: torch.Tensor, sigma: torch.Tensor, rho: torch.Tensor,
                  scale: torch.Tensor, factors: torch.Tensor, want_llr: bool = False, lib=None):
-        return self._grouped("aft_link_precoded_f32", ideal, est, keys, sigma, rho, [("scale", scale)], factors, want_llr, lib)
+        if self.slots == 1:
+            return self._grouped("aft_link_precoded_f32", ideal, est, keys, sigma, rho, [("scale", scale)], factors, want_llr, lib)
+        return self._grouped("aft_link_precoded_delayed_f32", ideal, est, keys, sigma, rho, [("scale", scale)], factors, want_llr, lib)
 
 
 class _DecoderPlan:

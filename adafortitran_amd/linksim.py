@@ -325,8 +325,27 @@ unheard second antenna (``H_r1 = E_r1 = 0``) every PMI is 0 and the link is the 
 models: instantaneous, error-free feedback of one PMI per subband, chosen from the same estimates the combiner uses, over all T symbols
 (non-causal under Doppler); the total power is twice the single link's, so a comparison at equal total power evaluates this link
 3.01 dB lower, as for Alamouti.  Open loop needs no feedback and has no array gain; closed loop has array gain exactly as far as the
-estimate is good and the subband is narrower than the coherence bandwidth.  It does not model feedback delay or quantised CQI, rank
+estimate is good and the subband is narrower than the coherence bandwidth.  It does not model quantised CQI, feedback errors, rank
 adaptation and rank-2 codebooks, more than two transmit antennas, or HARQ (``HarqAccumulator`` gets no keyword).
+
+Delayed feedback.  How much of that gain survives when the precoder was chosen ``d`` slots ago, from an estimate of a channel that has
+since moved: ``link_precoded_host(..., slots=K, delay=d)``, ``0 <= d < K`` (``precoding_pmi_host`` follows),
+``aft_link_precoded_delayed_f32`` (the same kernel body, through ``hip_ops.LinkPrecodedPlan(..., slots=K, delay=d)``) and
+``precoding_delay=d`` with ``slots=K`` on the accumulators and the sweeps.  The batch is whole SEQUENCES of K slots, a slot one group
+of ``2 R`` frames -- the order of ``ChannelSimConfig(slots=K, antennas=(R, 2))``, whose slots are K consecutive stretches of one fading
+process --: ``G = Q K`` input groups, input group ``seq K + k`` slot ``k`` of sequence ``seq``::
+
+    warm-up    slots k < d of a sequence are not transmitted and produce no output
+    selection  slot k >= d is transmitted with, per subband, the PMI selected from the estimates and rho of slot k - d of the same sequence:
+               the selection above, operation for operation, on the FEEDBACK group
+    the rest   the received samples, e_r = E_r0 + q E_r1, the combiner, the decision, the LLRs and the losses use the TRANSMIT slot's own
+               H, E, keys, sigma, rho and scale, exactly as above
+    outputs    compact: output group o = seq (K - d) + (k - d); counts, loss, llr and pmi have Q (K - d) rows; pmi is the APPLIED index
+
+With ``d = 0`` every slot is its own feedback slot: the link above, bit for bit, whatever K.  The receiver still combines with the
+effective estimate of the precoder that was applied (it knows what it fed back), so a stale PMI costs array gain, not a mismatch.
+``frames`` and every rate count transmitted groups only.  Not modelled: quantised CQI, feedback errors, rank adaptation, more than two
+transmit antennas, HARQ over precoded transmissions.
 
 The coded link.  The rate says how much information the LLRs carry; a link-level user wants the same with a decoder in the loop: the
 block-error rate of coded blocks and the throughput that follows from it.  ``CodeConfig``, ``link_encode_host`` / ``link_decode_host``
@@ -1241,11 +1260,35 @@ def _rho_of(rho, n: int) -> np.ndarray:
     return rho
 
 
-def precoding_pmi_host(cfg: LinkConfig, est, rho, branches, subband, tau_pmi: Optional[float] = None):
+def delayed_groups(groups: int, slots, delay) -> Tuple[np.ndarray, np.ndarray]:
+    """Delayed feedback (module docstring) on ``groups`` input groups in sequences of ``slots``: ``(transmit, feedback)``, int64
+    ``[groups / slots * (slots - delay)]`` each -- output group ``o = seq (K - d) + (k - d)`` sends input group ``seq K + k`` with the
+    PMIs selected from input group ``seq K + k - d``."""
+    if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in (slots, delay)) or slots < 1 or not 0 <= delay < slots:
+        raise ValueError(f"slots = {slots!r}, delay = {delay!r}: integers with slots >= 1 and 0 <= delay < slots")
+    K, d = int(slots), int(delay)
+    if groups % K:
+        raise ValueError(f"{groups} groups are not whole sequences of slots = {K}")
+    sent = (np.arange(groups // K, dtype=np.int64)[:, None] * K + np.arange(d, K, dtype=np.int64)[None, :]).reshape(-1)
+    return sent, sent - d
+
+
+def _group_frames(groups: np.ndarray, width: int) -> np.ndarray:
+    """The frames of the given groups of ``width`` frames, in order."""
+    return (groups[:, None] * width + np.arange(width, dtype=np.int64)[None, :]).reshape(-1)
+
+
+def precoding_pmi_host(cfg: LinkConfig, est, rho, branches, subband, tau_pmi: Optional[float] = None, slots: int = 1, delay: int = 0):
     """The selection of the closed-loop link (module docstring) in float64: ``est`` complex ``[n, S, T]`` and ``rho`` ``[n]`` in the
     layout ``g 2R + r 2 + s`` -> ``pmi int32 [G, n_sub]``, per subband the lowest index that attains the maximum of ``Re(q_i g_b)``.
-    With ``tau_pmi``: ``(pmi, flags bool [G, n_sub])``, the PMI-flagged subbands."""
+    With ``tau_pmi``: ``(pmi, flags bool [G, n_sub])``, the PMI-flagged subbands.  With ``slots`` / ``delay`` ("delayed feedback") the
+    rows are the compact output groups': the selection on each transmitted slot's FEEDBACK group."""
     R = _branches(branches)
+    if slots != 1 or delay != 0:
+        E, rho = np.asarray(est), np.asarray(rho).reshape(-1)
+        _, feedback = delayed_groups(_tx_grouped(E.shape[0], R), slots, delay)
+        at = _group_frames(feedback, 2 * R)
+        return precoding_pmi_host(cfg, E[at], rho[at], R, subband, tau_pmi)
     index, n_sub = precoding_subbands(cfg, subband)
     S, T = cfg.sim.ofdm
     E = np.asarray(est).astype(np.complex128)
@@ -1271,14 +1314,30 @@ def precoding_pmi_host(cfg: LinkConfig, est, rho, branches, subband, tau_pmi: Op
 
 
 def link_precoded_host(cfg: LinkConfig, keys, ideal, est, sigma, rho, scale, branches, subband, factors=(1.0,),
-                       tau: Optional[float] = None, e_lambda: Optional[float] = None, pmi=None):
+                       tau: Optional[float] = None, e_lambda: Optional[float] = None, pmi=None, slots: int = 1, delay: int = 0):
     """The closed-loop link (module docstring) in float64: ``keys`` / ``ideal`` / ``est`` / ``sigma`` as ``link_errors_host``'s for the
     ``n`` frames in the layout ``g 2R + r 2 + s``, ``rho`` ``[n]`` and ``scale`` ``[G]`` taken as the float32 numbers they are
     (``precoding_weights``), ``G = n / (2 branches)`` -> ``link_alamouti_host``'s tuple with ``pmi`` appended: ``(counts int64 [G, 2],
     loss float64 [G, K], llr float64 [G, S, T, m], pmi int32 [G, n_sub])``; with ``tau`` the wrong-bit map ``[G, S, T]`` and the flags
     ``[G, S, T, 2]`` follow the LLRs, with ``e_lambda`` then ``loss_lo``, ``loss_hi`` and ``q``, on the combiner's ``c``, ``p`` and
-    reaches; ``pmi`` stays last.  A given ``pmi`` ``[G, n_sub]`` (values 0 .. 3) replaces the selection.  Needs no library."""
+    reaches; ``pmi`` stays last.  A given ``pmi`` ``[G, n_sub]`` (values 0 .. 3) replaces the selection.  Needs no library.
+    ``slots=K, delay=d`` is "delayed feedback" (module docstring): the ``G = Q K`` groups are Q sequences of K slots, slot ``k >= d`` is
+    sent with the PMIs selected from ``est`` and ``rho`` of slot ``k - d``, and every output has the ``Q (K - d)`` compact rows; the
+    inputs, ``scale`` included, stay indexed by input frame or group."""
     R = _branches(branches)
+    if slots != 1 or delay != 0:                                # the link on the transmit groups, with the feedback groups' selection
+        keys, ideal, est, sigma, rho, scale = (np.asarray(v) for v in (keys, ideal, est, sigma, rho, scale))
+        if keys.ndim != 1 or any(v.shape[:1] != keys.shape for v in (ideal, est)) or sigma.size != keys.size or rho.size != keys.size:
+            raise ValueError("keys, ideal, est, sigma and rho must hold one entry per frame")
+        groups = _tx_grouped(len(keys), R)
+        if scale.size != groups:
+            raise ValueError(f"scale must hold one value per group ({groups}), got {scale.size}")
+        sent, feedback = delayed_groups(groups, slots, delay)
+        at, fb = _group_frames(sent, 2 * R), _group_frames(feedback, 2 * R)
+        if pmi is None:
+            pmi = precoding_pmi_host(cfg, est[fb], rho.reshape(-1)[fb], R, subband)
+        return link_precoded_host(cfg, keys[at], ideal[at], est[at], sigma.reshape(-1)[at], rho.reshape(-1)[at], scale.reshape(-1)[sent], R,
+                                  subband, factors, tau, e_lambda, pmi)
     index, n_sub = precoding_subbands(cfg, subband)
     keys, H, E, sigma = _checked(cfg, keys, ideal, est, sigma)
     n, (S, T) = len(keys), cfg.sim.ofdm
@@ -1349,11 +1408,13 @@ class _FrameSweep:
 
     def _open(self, cfg: LinkConfig, device, seed: int, want: str, branches: int = 1, err_var: float = 0.0, factors=(1.0,),
               streams: int = 1, detector: str = "mmse", tx_diversity: Optional[str] = None,
-              precoding_subband: Optional[int] = None) -> None:
+              precoding_subband: Optional[int] = None, precoding_delay: int = 0, slots: int = 1) -> None:
         """``want``: which of ``"counts"``, ``"loss"`` and ``"llr"`` ``_measure`` computes.  ``streams=2``: the spatial-multiplexing
         link with ``detector`` in front (``streams=1`` ignores it).  ``tx_diversity``: None, or the pairing of the transmit-diversity
         link in front (one stream; ``detector`` is ignored).  ``precoding_subband``: None, or the subband width of the closed-loop
-        link in front (one stream, no ``tx_diversity``; ``detector`` is ignored)."""
+        link in front (one stream, no ``tx_diversity``; ``detector`` is ignored).  ``precoding_delay`` / ``slots``: the closed-loop link
+        with feedback ``precoding_delay`` slots old on sequences of ``slots`` groups ("delayed feedback"); 0 is the instantaneous link,
+        launch for launch, whatever ``slots``."""
         if not isinstance(cfg, LinkConfig):
             raise ValueError(f"{type(self).__name__} needs a LinkConfig (got {type(cfg).__name__})")
         self.cfg, self.seed, self._want = cfg, int(seed), want
@@ -1379,6 +1440,17 @@ class _FrameSweep:
                 raise ValueError(f"precoding_subband = {precoding_subband!r} sends one precoded stream from two antennas: streams must "
                                  f"be 1 (got {self.streams}) and tx_diversity None (got {tx_diversity!r})")
             self.precoding_subband = _subband(cfg, precoding_subband)
+        if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in (precoding_delay, slots)) or precoding_delay < 0 \
+                or slots < 1:
+            raise ValueError(f"precoding_delay = {precoding_delay!r}, slots = {slots!r}: integers, the delay at least 0 and slots at least 1")
+        self.precoding_delay, self.slots = int(precoding_delay), int(slots)
+        if self.precoding_delay > 0:
+            if self.precoding_subband is None:
+                raise ValueError(f"precoding_delay = {precoding_delay} delays the PMI feedback of the closed-loop link: give "
+                                 f"precoding_subband= as well (no other link has feedback to delay)")
+            if self.slots <= self.precoding_delay:
+                raise ValueError(f"precoding_delay = {precoding_delay} needs sequences longer than the delay: use slots >= "
+                                 f"{self.precoding_delay + 1} (got slots = {slots}) on batches from ChannelSimConfig(slots=...)")
         self._pairs = tx_diversity is not None or self.precoding_subband is not None      # a group is 2 R frames and yields one row
         # frames per group: the branches, times the two transmit antennas or the streams
         self._width =self.branches * (2 if self._pairs else self.streams)
@@ -1391,7 +1463,8 @@ class _FrameSweep:
         if self.device.type == "cuda":
             from . import hip_ops                  # loads the extension: a missing .so raises here, loudly
             if self.precoding_subband is not None:  # every measure of the closed-loop link comes from its one launch
-                self._plan = hip_ops.LinkPrecodedPlan(cfg, self.device, self.branches, self.precoding_subband)
+                delayed = (self.slots, self.precoding_delay) if self.precoding_delay > 0 else ()
+                self._plan = hip_ops.LinkPrecodedPlan(cfg, self.device, self.branches, self.precoding_subband, *delayed)
             elif tx_diversity is not None:         # every measure of the transmit-diversity link comes from the combiner's one launch
                 self._plan = hip_ops.LinkAlamoutiPlan(cfg, self.device, self.branches, tx_diversity)
             elif self.streams > 1:                 # every measure of the spatial-multiplexing link comes from the detector's one launch
@@ -1483,13 +1556,18 @@ class _FrameSweep:
         ``G`` transmissions of the transmit-diversity link with the leaders' keys: ``link_alamouti_host`` on a CPU device, one launch
         of ``aft_link_alamouti_f32`` with ``rho`` formed on the device on a HIP device.  With ``precoding_subband`` the same groups on
         the closed-loop link: ``link_precoded_host`` or one launch of ``aft_link_precoded_f32``, and one add of the batch's PMIs into
-        the histogram ``pmi_histogram`` reads."""
+        the histogram ``pmi_histogram`` reads; with ``precoding_delay`` the batch is whole sequences of ``slots`` groups, the one launch
+        is ``aft_link_precoded_delayed_f32``'s, and the groups returned are the transmitted ones, with the transmit slots' leader keys."""
         ops = self._operands(est, ideal, meta, frame_ids, snr_db, self._of_snr)
         if ops is None:
             return None
         b, H, E, keys, (sigma, *scale) = ops       # scale: the frames' LLR scales, where the measure or the combiner needs them
         G = _tx_grouped(b, self.branches) if self._pairs else _grouped(b, self.branches, self.streams)
         measure = self._measure_host if self._plan is None else self._measure_device
+        if self.precoding_delay > 0:               # whole sequences; the warm-up slots of each yield no row
+            if G % self.slots:
+                raise ValueError(f"a batch of {b} frames is not a multiple of slots * 2 * branches = {self.slots} * 2 * {self.branches}")
+            return (G // self.slots * (self.slots - self.precoding_delay), *measure(G, H, E, keys, sigma, scale))
         return (G * self.streams, *measure(G, H, E, keys, sigma, scale))
 
     def _measure_host(self, G, H, E, keys, sigma, scale):
@@ -1497,10 +1575,13 @@ class _FrameSweep:
         R, N = self.branches, self.streams
         counts = loss = llr = None
         if self.precoding_subband is not None:     # G precoded transmissions from two antennas, with the leaders' keys
+            delayed = dict(slots=self.slots, delay=self.precoding_delay) if self.precoding_delay > 0 else {}
             counts, loss, llr, pmi = link_precoded_host(self.cfg, keys, H, E, sigma, *_weights(scale[0], 2 * R), R,
-                                                        self.precoding_subband, self.factors)
+                                                        self.precoding_subband, self.factors, **delayed)
             self._count_pmi(torch.from_numpy(pmi))
             sent = keys[::2 * R]
+            if delayed:                            # the leaders of the transmit slots
+                sent = np.ascontiguousarray(sent[delayed_groups(G, self.slots, self.precoding_delay)[0]])
         elif self.tx_diversity is not None:        # G transmissions from two antennas, with the leaders' keys
             counts, loss, llr = link_alamouti_host(self.cfg, keys, H, E, sigma, *_weights(scale[0], 2 * R), R, self.tx_diversity,
                                                    self.factors)
@@ -1541,6 +1622,8 @@ class _FrameSweep:
             counts, loss, llr, *pmi = self._launch(H, E, keys, sigma, rho, lead, self._factors_t, want_llr=want_llr)
             if pmi:                                # the closed-loop link's fourth output
                 self._count_pmi(pmi[0])
+            if self.precoding_delay > 0:           # the leaders of the transmit slots: a strided view, then one copy
+                return keys[::2 * R].view(-1, self.slots)[:, self.precoding_delay:].reshape(-1), counts, loss, llr
             return keys[::2 * R].contiguous(), counts, loss, llr
         if N > 1:                                  # the detectors differ in one operand: the joint one has no regulariser
             rho, lead = self._device_weights(scale[0], R * N)
@@ -1655,12 +1738,21 @@ class LinkAccumulator(_FrameSweep):
     per subband of ``B`` subcarriers from the estimate, by one launch of ``aft_link_precoded_f32`` (on a CPU device by
     ``link_precoded_host``).  ``streams`` must be 1 and ``tx_diversity`` None (``ValueError`` otherwise), ``detector`` is ignored; rows,
     keys, ``frames`` and the SNR as under ``tx_diversity``.  ``pmi_histogram()`` reads how often each of the four precoders was
-    chosen, summed on the device by one add per batch.  ``precoding_subband=None`` is today's path, launch for launch."""
+    chosen, summed on the device by one add per batch.  ``precoding_subband=None`` is today's path, launch for launch.
+
+    ``precoding_delay=d`` with ``slots=K`` (module docstring, "delayed feedback"; the same keywords on the same four accumulators,
+    not on ``HarqAccumulator``): every ``K`` consecutive groups of a batch are the slots of one sequence -- batches of
+    ``ChannelSimConfig(slots=K, antennas=(R, 2))`` --, slot ``k >= d`` is sent with the PMIs selected ``d`` slots earlier and the first
+    ``d`` slots of a sequence are warm-up: one launch of ``aft_link_precoded_delayed_f32`` (on a CPU device ``link_precoded_host`` with
+    ``slots`` and ``delay``).  ``frames`` and every rate count the transmitted groups only, ``pmi_histogram()`` the APPLIED precoders.
+    Needs ``precoding_subband`` and ``slots > d`` (``ValueError`` otherwise); a batch that is no multiple of ``K 2 R`` frames raises
+    ``ValueError``.  ``precoding_delay=0`` is the instantaneous path, launch for launch, whatever ``slots``."""
 
     def __init__(self, cfg: LinkConfig, device, seed: int = 0, branches: int = 1, streams: int = 1, detector: str = "mmse", *,
-                 tx_diversity: Optional[str] = None, precoding_subband: Optional[int] = None) -> None:
+                 tx_diversity: Optional[str] = None, precoding_subband: Optional[int] = None, precoding_delay: int = 0,
+                 slots: int = 1) -> None:
         self._open(cfg, device, seed, "counts", branches, streams=streams, detector=detector, tx_diversity=tx_diversity,
-                   precoding_subband=precoding_subband)
+                   precoding_subband=precoding_subband, precoding_delay=precoding_delay, slots=slots)
         self.errors = torch.zeros(2, dtype=torch.int64, device=self.device)     # bit errors, symbol errors
 
     def update(self, est: Optional[torch.Tensor], ideal: torch.Tensor, meta: Optional[tuple] = None, *, frame_ids=None,
@@ -1702,8 +1794,9 @@ class RateAccumulator(_FrameSweep):
 
     def __init__(self, cfg: LinkConfig, device, seed: int = 0, factors=(1.0,), err_var: float = 0.0, branches: int = 1,
                  streams: int = 1, detector: str = "mmse", *, tx_diversity: Optional[str] = None,
-                 precoding_subband: Optional[int] = None) -> None:
-        self._open(cfg, device, seed, "loss", branches, err_var, factors, streams, detector, tx_diversity, precoding_subband)
+                 precoding_subband: Optional[int] = None, precoding_delay: int = 0, slots: int = 1) -> None:
+        self._open(cfg, device, seed, "loss", branches, err_var, factors, streams, detector, tx_diversity, precoding_subband,
+                   precoding_delay, slots)
         self.loss = torch.zeros(len(self.factors), dtype=torch.float64, device=self.device)
 
     def update(self, est: Optional[torch.Tensor], ideal: torch.Tensor, meta: Optional[tuple] = None, *, frame_ids=None,
@@ -1948,11 +2041,12 @@ class BlockErrorAccumulator(_FrameSweep):
     _config, _needs, _host_decoder, _decoder_plan, _columns = CodeConfig, "a CodeConfig", staticmethod(link_decode_host), "LinkDecodePlan", 2
 
     def __init__(self, code, device, seed: int = 0, err_var: float = 0.0, branches: int = 1, streams: int = 1,
-                 detector: str = "mmse", *, tx_diversity: Optional[str] = None, precoding_subband: Optional[int] = None) -> None:
+                 detector: str = "mmse", *, tx_diversity: Optional[str] = None, precoding_subband: Optional[int] = None,
+                 precoding_delay: int = 0, slots: int = 1) -> None:
         if not isinstance(code, self._config):
             raise ValueError(f"{type(self).__name__} needs {self._needs} (got {type(code).__name__})")
         self._open(code.link, device, seed, "llr", branches, err_var, streams=streams, detector=detector, tx_diversity=tx_diversity,
-                   precoding_subband=precoding_subband)
+                   precoding_subband=precoding_subband, precoding_delay=precoding_delay, slots=slots)
         self.code = code
         self.errors = torch.zeros(self._columns, dtype=torch.int64, device=self.device)    # information-bit errors, block errors, ...
         self._decode = None
@@ -2289,7 +2383,8 @@ class LdpcBlockErrorAccumulator(BlockErrorAccumulator):
     _runs_cwsic = True
 
     def __init__(self, code, device, seed: int = 0, err_var: float = 0.0, branches: int = 1, streams: int = 1,
-                 detector: str = "mmse", *, tx_diversity: Optional[str] = None, precoding_subband: Optional[int] = None) -> None:
+                 detector: str = "mmse", *, tx_diversity: Optional[str] = None, precoding_subband: Optional[int] = None,
+                 precoding_delay: int = 0, slots: int = 1) -> None:
         """``streams=2, detector="cwsic"`` (module docstring, "the codeword-cancellation link"): MMSE detection and decoding of both
         streams, then a stream that failed while the other passed is detected again with the acknowledged codeword cancelled, and decoded
         again.  On a HIP device a batch is four launches -- ``aft_link_sm_f32``, ``aft_link_ldpc_f32``, ``aft_link_cancel_f32`` reading
@@ -2298,7 +2393,7 @@ class LdpcBlockErrorAccumulator(BlockErrorAccumulator):
         and ``result_throughput`` give the values AFTER cancellation, ``result_iterations`` both passes summed, ``result_first_pass`` the
         block-error rate before cancellation (the ``detector="mmse"`` sweep's ``result``) and ``cwsic_stats`` what the second pass did."""
         super().__init__(code, device, seed, err_var, branches, streams, detector, tx_diversity=tx_diversity,
-                         precoding_subband=precoding_subband)
+                         precoding_subband=precoding_subband, precoding_delay=precoding_delay, slots=slots)
         if self._cwsic:
             self._first = torch.zeros(3, dtype=torch.int64, device=self.device)          # the first pass's three counts
             self._second = torch.zeros(3, dtype=torch.int64, device=self.device)         # streams detected again; of those decoded; groups both failed

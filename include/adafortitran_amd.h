@@ -325,6 +325,29 @@ int aft_channel_sim_group_f32(const aft_chansim *sim, int rx, int tx, const floa
                               long long start, long long stride, long long modulo, int batch, float *ideal, float *pilots,
                               float *meta, void *stream);
 
+/* Time continuity (chansim.py "time continuity: slot sequences"): K = slots consecutive groups are K consecutive SLOTS of one fading
+ * process, L = slot_symbols symbols from one slot's start to the next (L >= T; L > T leaves a gap).  Every K G consecutive frames, G =
+ * rx * tx, are one sequence, slot-major: for frame g, seq = g / (K G), lead = seq K G, slot k = (g - lead) / G, member a = g mod G.
+ *   the three conditions are picked from the SEQUENCE leader's key kf(lead): a sequence shares snr, delay spread and doppler;
+ *   z_j, j = 0 .. a, uses the ray streams of kf(lead + j), the same rays in every slot, evaluated at the absolute symbol k L + t: a ray
+ *     (rate = doppler_hz symbol_period_s cos(2 pi a) turns per symbol, phase f) first gets the slot's start phase
+ *     f_k = frac(fma(rate, float(k L), f)), frac(x) = x - floor(x), k L exact in float; the phase at symbol t of the slot is then
+ *     fma(rate, t, f_k), reduced as above.  f_0 = f exactly;
+ *   the mixing, H and the pilots follow as in aft_channel_sim_group_f32, with frame g's OWN noise streams.
+ * base, start, stride and modulo count SEQUENCES: output frame b is member b mod G of slot (b / G) mod K of sequence
+ * base + ((start + (b / (K G)) stride) mod modulo); batch counts frames.  mix is aft_channel_sim_group_f32's (two floats, 1 and 0, for
+ * rx = tx = 1).  Everything else is aft_channel_sim_group_f32's: one workgroup per frame, one launch, no atomics; with slots = 1 the
+ * outputs are that entry point's, bit for bit, and slot 0 of sequence q is its group q K.
+ * Nothing is launched on AFT_ERR_ARG (aft_channel_sim_group_f32's, where the bound on frame numbers is 2^62 / (K G) for sequences; batch
+ * not a multiple of K G) and AFT_ERR_SHAPE (aft_channel_sim_group_f32's; slots below 1, slot_symbols below T, or slots, slot_symbols or
+ * slots * slot_symbols above AFT_CHANSIM_MAX_SLOTS). */
+/* the symbols a sequence may span: k L is far inside float's exact integers, and the rounding of a start phase, 2^-24 (rate k L + 1)
+ * turns, stays below 3e-5 turns at 0.1 turns per symbol */
+#define AFT_CHANSIM_MAX_SLOTS 4096
+int aft_channel_sim_seq_f32(const aft_chansim *sim, int rx, int tx, const float *mix, int slots, int slot_symbols,
+                            unsigned long long seed, long long base, long long start, long long stride, long long modulo, int batch,
+                            float *ideal, float *pilots, float *meta, void *stream);
+
 /* ---- the LMMSE (Wiener) baseline estimator (adafortitran_amd/lmmse.py holds the definition) ----
  *
  * The best linear estimator of the simulator's channel from its pilots, for the second-order statistics the simulator is defined
@@ -728,6 +751,23 @@ int aft_link_precoded_f32(const aft_link *link, const float *ideal, const float 
                           int32_t *counts /* [groups][2] */, float *loss /* [groups][n_factors] */,
                           float *llr /* [groups,S,T,m] or NULL */, int32_t *pmi /* [groups][n_sub], not NULL */, int batch,
                           void *stream);
+
+/* Delayed feedback (linksim.py "delayed feedback"): the batch is whole sequences of K = slots groups -- the slots of
+ * aft_channel_sim_seq_f32 --, input group seq K + k slot k of sequence seq, and d = delay, 0 <= d < K.  Slots k < d are warm-up: not sent,
+ * no output.  Slot k >= d is sent with, per subband, the PMI selected as above from est and rho of slot k - d of the same sequence; the
+ * received samples, the effective estimates, the combiner, the decision, the LLRs and the losses use the sent slot's own ideal, est,
+ * keys, sigma, rho and scale, exactly as above.  Outputs are compact: output group o = seq (K - d) + (k - d), groups_out =
+ * (groups / K) (K - d); counts, loss, llr and pmi have groups_out rows and pmi is the APPLIED index.  Inputs are indexed by input frame
+ * or group (scale by input group).  The same kernel body, one workgroup per output group, no workspace, no atomics, no copies; with
+ * d = 0 the outputs are aft_link_precoded_f32's, bit for bit.
+ * Every refusal is AFT_ERR_ARG and launches nothing: aft_link_precoded_f32's, slots < 1, delay outside 0 .. slots - 1, batch not a
+ * multiple of slots * 2 * branches. */
+int aft_link_precoded_delayed_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys,
+                                  const float *sigma, const float *rho /* [batch] */, const float *scale /* [groups] */,
+                                  const float *factors, int n_factors, int branches, int subband, int slots, int delay,
+                                  int32_t *counts /* [groups_out][2] */, float *loss /* [groups_out][n_factors] */,
+                                  float *llr /* [groups_out,S,T,m] or NULL */, int32_t *pmi /* [groups_out][n_sub], not NULL */,
+                                  int batch, void *stream);
 
 /* ---- successive cancellation: ordered MMSE-SIC of the two streams (adafortitran_amd/linksim.py "the successive-cancellation link") ----
  *
