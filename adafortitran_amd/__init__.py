@@ -9,7 +9,7 @@ Package contents (only what the hot path needs):
   config         YAML/pydantic config surface
   synth          deterministic synthetic weights + inputs
   metrics        channel-MSE metric (device reduction + RCCL all-gather)
-  lmmse          the LMMSE (Wiener) baseline of the channel simulator: definition, closed-form MSE, nn.Module
+  lmmse          the LMMSE (Wiener) baseline of the channel simulator, one slot or a window of slots: definition, closed-form MSE, nn.Module
 """
 from .config import ModelConfig, SystemConfig, load_config  # noqa: F401
 from .estimators import (AdaFortiTranEstimator, BaseFortiTranEstimator, FortiTranEstimator,  # noqa: F401

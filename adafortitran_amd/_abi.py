@@ -60,6 +60,7 @@ AFT_CHANSIM_MAX_TAPS, AFT_CHANSIM_MAX_RAYS, AFT_CHANSIM_MAX_VALUES = 32, 16, 16
 AFT_CHANSIM_MAX_PILOT_SCS, AFT_CHANSIM_MAX_PILOT_SYMBOLS = 64, 16
 AFT_CHANSIM_MAX_GROUP = 16
 AFT_CHANSIM_MAX_SLOTS = 4096
+AFT_LMMSE_MAX_WINDOW_PILOTS = 32
 AFT_LINK_RATE_1_2, AFT_LINK_RATE_2_3, AFT_LINK_RATE_3_4 = 0, 1, 2
 AFT_LINK_CODE_MAX_INFO_BITS = 4090
 AFT_LINK_LDPC_Z, AFT_LINK_LDPC_MAX_EDGES = 64, 160
@@ -222,6 +223,8 @@ SIGNATURES = {
                                 [C.c_longlong] * 4 + [C.c_int, vp, vp, vp, vp]),
     "aft_lmmse_table_floats": (C.c_size_t, [C.POINTER(AftLmmse)]),
     "aft_lmmse_f32": (C.c_int, [C.POINTER(AftLmmse), vp, vp, vp, vp, vp, vp, C.c_int, vp]),
+    "aft_lmmse_seq_table_floats": (C.c_size_t, [C.POINTER(AftLmmse), C.c_int]),
+    "aft_lmmse_seq_f32": (C.c_int, [C.POINTER(AftLmmse)] + [C.c_int] * 4 + [vp, vp, vp, vp, vp, vp, C.c_int, vp]),
     "aft_link_errors_f32": (C.c_int, [C.POINTER(AftLink), vp, vp, vp, vp, vp, C.c_int, vp]),
     "aft_link_soft_f32": (C.c_int, [C.POINTER(AftLink), vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp]),
     "aft_link_decode_f32": (C.c_int, [C.POINTER(AftLink), vp, vp, C.c_int, C.c_int, C.c_ulonglong, C.c_ulonglong, C.c_float, vp, vp,

@@ -57,6 +57,17 @@ int check_lmmse(const aft_lmmse *p) {
     return AFT_OK;
 }
 
+// what the multi-slot form adds to the plan's checks; 0 = fine.  group = 1, slots = window = 1, horizon = 0 always pass
+int check_lmmse_seq(const aft_lmmse *p, int group, int slots, int window, int horizon) {
+    const char *who = "lmmse seq";
+    if (!within(who, "group", group, 1, AFT_CHANSIM_MAX_GROUP) || !within(who, "slots", slots, 1, AFT_CHANSIM_MAX_SLOTS) ||
+        !within(who, "window", window, 1, slots) ||
+        !within(who, "window * pilot_symbols", window * p->pilot_symbols, 1, AFT_LMMSE_MAX_WINDOW_PILOTS) ||
+        !within(who, "horizon", horizon, 0, slots - 1))
+        return AFT_ERR_SHAPE;
+    return AFT_OK;
+}
+
 template <class... P>
 bool aligned(size_t bytes, const P *...p) {
     return (... | reinterpret_cast<uintptr_t>(p)) % bytes == 0;
@@ -299,6 +310,30 @@ int aft_lmmse_f32(const aft_lmmse *plan, const float *tables, const float *pilot
                 plan->fixed_snr, (const void *)ds, plan->fixed_ds, (const void *)dop, plan->fixed_dop);
     hipError_t e = launch_lmmse(*plan, tables, pilots, snr, ds, dop, est, batch, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? AFT_OK : hip_fail("lmmse", e);
+}
+
+size_t aft_lmmse_seq_table_floats(const aft_lmmse *plan, int window) {
+    if (plan == nullptr || check_lmmse(plan) != AFT_OK || check_lmmse_seq(plan, 1, AFT_CHANSIM_MAX_SLOTS, window, 0) != AFT_OK) return 0;
+    return (size_t)plan->n_ds * lmmse_fblock_floats(*plan) + (size_t)plan->n_dop * lmmse_seq_tblock_floats(*plan, window);
+}
+
+int aft_lmmse_seq_f32(const aft_lmmse *plan, int group, int slots, int window, int horizon, const float *tables, const float *pilots,
+                      const float *snr, const float *ds, const float *dop, float *est, int batch, void *stream) {
+    AFT_REQUIRE(plan && tables && pilots && est, "lmmse seq: NULL pointer argument");
+    AFT_REQUIRE(aligned(8, tables, pilots, est), "lmmse seq: tables, pilots and est must be 8-byte aligned");
+    AFT_REQUIRE(aligned(4, snr, ds, dop), "lmmse seq: the condition arrays must be 4-byte aligned");
+    AFT_REQUIRE(batch >= 1, "lmmse seq: batch must be at least 1 (got %d)", batch);
+    int rc = check_lmmse(plan);
+    if (rc == AFT_OK) rc = check_lmmse_seq(plan, group, slots, window, horizon);
+    if (rc != AFT_OK) return rc;
+    AFT_REQUIRE(batch % (slots * group) == 0, "lmmse seq: batch = %d is not a multiple of slots * group = %d * %d: whole sequences only",
+                batch, slots, group);
+    AFT_REQUIRE((snr || plan->fixed_snr >= 0) && (ds || plan->fixed_ds >= 0) && (dop || plan->fixed_dop >= 0),
+                "lmmse seq: NULL condition array whose fixed_* index is -1 (snr %p / %d, ds %p / %d, dop %p / %d)", (const void *)snr,
+                plan->fixed_snr, (const void *)ds, plan->fixed_ds, (const void *)dop, plan->fixed_dop);
+    hipError_t e = launch_lmmse_seq(*plan, group, slots, window, horizon, tables, pilots, snr, ds, dop, est, batch,
+                                    static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? AFT_OK : hip_fail("lmmse_seq", e);
 }
 
 int aft_link_errors_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys,

@@ -382,6 +382,12 @@ size_t lmmse_fblock_floats(const aft_lmmse &plan);
 size_t lmmse_tblock_floats(const aft_lmmse &plan);
 hipError_t launch_lmmse(const aft_lmmse &plan, const float *tables, const float *pilots, const float *snr, const float *ds,
                         const float *dop, float *est, int batch, hipStream_t st);
+// ... and its multi-slot instantiation: everything has passed aft_lmmse_seq_f32's checks; a Doppler's block of the image is then the
+// `window` sub-blocks for w = 1 .. window, lmmse_seq_tblock_floats in all
+size_t lmmse_seq_tblock_floats(const aft_lmmse &plan, int window);
+hipError_t launch_lmmse_seq(const aft_lmmse &plan, int group, int slots, int window, int horizon, const float *tables,
+                            const float *pilots, const float *snr, const float *ds, const float *dop, float *est, int batch,
+                            hipStream_t st);
 // the link-level error count (k_link.hip): `link` has passed aft_link_errors_f32's checks
 hipError_t launch_link_errors(const aft_link &link, const float *ideal, const float *est, const unsigned long long *keys,
                               const float *sigma, int32_t *counts, int batch, hipStream_t st);

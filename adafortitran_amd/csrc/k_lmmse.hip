@@ -14,6 +14,13 @@
 //      16-byte stores (T even, base 16-byte aligned; 8-byte stores otherwise) -- the row-tile pass of frame_device.h, shared with
 //      the simulator, which is what lets T be anything: LDS holds one tile whatever the grid's length.
 //
+// The multi-slot form (lmmse_seq_kernel, aft_lmmse_seq_f32) is the same body over a WINDOW of slots: target frame (seq, k, m) of a
+// batch of K-slot sequences of groups of G frames reads the pilots of member m in the w = min(W, k - h + 1) slots that end at slot
+// k - h, side by side along time (P is [Ps, w Pt]; step 2 gathers them from the w source frames), and the Doppler tables are those of
+// w: `Pt` becomes `w Pt` in steps 2 to 4, nothing else changes.  A frame with no slot to look at (k < h) skips steps 1 to 3 and runs
+// step 4 over zero terms: +0 everywhere through the same stores, nothing read.  LDS: two [64][32] complex tiles and the time tile,
+// 40 KB, static; a second instantiation with [64][16] tiles (24 KB, this file's other kernel's) takes the windows that fit it.
+//
 // No atomics, every output element written exactly once.  The rounding behind tests/test_lmmse_gpu.py's bound: every product stage is a
 // chain of fused multiply-adds in sequence, the table entries are float32 roundings of the host's double tables.
 #include "frame_device.h"
@@ -21,7 +28,7 @@
 namespace aft {
 namespace {
 
-constexpr int kLmMaxPs = AFT_CHANSIM_MAX_PILOT_SCS, kLmMaxPt = AFT_CHANSIM_MAX_PILOT_SYMBOLS;
+constexpr int kLmMaxPs = AFT_CHANSIM_MAX_PILOT_SCS, kLmMaxPt = AFT_CHANSIM_MAX_PILOT_SYMBOLS, kLmMaxPw = AFT_LMMSE_MAX_WINDOW_PILOTS;
 
 struct LmmseArgs {
     aft_lmmse c;
@@ -31,7 +38,22 @@ struct LmmseArgs {
     float2 *est;
     unsigned long long fblock, tblock;      // floats per delay-spread block / per Doppler block of the image
     int wide;                               // 1: 16-byte stores into est
+    static constexpr bool kSeq = false;
+    [[maybe_unused]] static constexpr int kMaxPw = kLmMaxPt; // the widest pilot matrix a frame filters
 };
+
+template <int kPw>                          // the widest window, in pilot symbols, this instantiation's LDS holds
+struct LmmseSeqArgs : LmmseArgs {
+    int group, slots, window, horizon;      // G, K, W, h; tblock is a Doppler's W sub-blocks
+    static constexpr bool kSeq = true;
+    [[maybe_unused]] static constexpr int kMaxPw = kPw;
+};
+
+// floats of a Doppler's sub-blocks 1 .. w - 1, each v Pt (v Pt + T + 1) floats: where sub-block w starts inside the Doppler's block
+__host__ __device__ inline unsigned long long lmmse_wblock_offset(unsigned long long Pt, unsigned long long T, unsigned long long w) {
+    const unsigned long long m = w - 1;
+    return Pt * Pt * (m * (m + 1) * (2 * m + 1) / 6) + Pt * (T + 1) * (m * (m + 1) / 2);
+}
 
 // index of the value nearest to v: |v - value[i]| in double (exact for two floats of like size), ties to the lower index, NaN -> 0
 __device__ __forceinline__ int nearest(const float *value, int n, float v) {
@@ -44,27 +66,50 @@ __device__ __forceinline__ int nearest(const float *value, int n, float v) {
     return best;
 }
 
-__global__ __launch_bounds__(kFrameThreads) void lmmse_kernel(const LmmseArgs a) {
-    __shared__ float2 pc[kLmMaxPs * kLmMaxPt];       // the pilots, then C = D o Y
-    __shared__ float2 y1[kLmMaxPs * kLmMaxPt];       // U_f^H P
-    __shared__ float2 v[kLmMaxPs][kFrameTile];       // C T'^T, one time tile
+// The body of both kernels.  pc: the pilots, then C = D o Y; y1: U_f^H P (both [Ps][Pw], Pw <= Args::kMaxPw); v: C T'^T, one time tile.
+template <class Args>
+__device__ __forceinline__ void lmmse_body(const Args &a, float2 *pc, float2 *y1, float2 (*v)[kFrameTile]) {
     const aft_lmmse &c = a.c;
     const int tid = threadIdx.x;
     const size_t b = blockIdx.x;
-    const int S = c.num_scs, T = c.num_symbols, Ps = c.pilot_scs, Pt = c.pilot_symbols;
-    const int i_snr = c.fixed_snr >= 0 ? c.fixed_snr : nearest(c.snr_db, c.n_snr, a.snr[b]);
-    const int i_ds = c.fixed_ds >= 0 ? c.fixed_ds : nearest(c.delay_spread_ns, c.n_ds, a.ds[b]);
-    const int i_dop = c.fixed_dop >= 0 ? c.fixed_dop : nearest(c.doppler_hz, c.n_dop, a.dop[b]);
+    const int S = c.num_scs, T = c.num_symbols, Ps = c.pilot_scs;
+    int w = 1;                                                                       // slots in the frame's window; 0: none, est = 0
+    size_t first = b;                                                                // the oldest source frame
+    int hop = 0;                                                                     // frames from one source to the next
+    if constexpr (Args::kSeq) {
+        const int unit = a.slots * a.group;
+        const size_t seq = b / (size_t)unit;
+        const int r = (int)(b - seq * (size_t)unit), k = r / a.group, m = r - k * a.group, n = k - a.horizon + 1;
+        w = n <= 0 ? 0 : min(a.window, n);
+        hop = a.group;
+        first = (seq * (size_t)a.slots + (size_t)max(k - a.horizon - w + 1, 0)) * (size_t)a.group + (size_t)m;
+        AFT_DEV_ASSERT(k >= 0 && k < a.slots && w <= a.window && (w == 0 || k - a.horizon - w + 1 >= 0));
+    }
+    const bool live = w > 0;
+    const int Pt = c.pilot_symbols * w;                                              // the window's pilot symbols, w Pt
+    const int Pk = live ? Ps : 0;                                                    // terms of the last product: none without a window
+    const int i_snr = !live ? 0 : c.fixed_snr >= 0 ? c.fixed_snr : nearest(c.snr_db, c.n_snr, a.snr[b]);
+    const int i_ds = !live ? 0 : c.fixed_ds >= 0 ? c.fixed_ds : nearest(c.delay_spread_ns, c.n_ds, a.ds[b]);
+    const int i_dop = !live ? 0 : c.fixed_dop >= 0 ? c.fixed_dop : nearest(c.doppler_hz, c.n_dop, a.dop[b]);
     AFT_DEV_ASSERT(i_snr >= 0 && i_snr < c.n_snr && i_ds >= 0 && i_ds < c.n_ds && i_dop >= 0 && i_dop < c.n_dop);
-    AFT_DEV_ASSERT(Ps >= 1 && Ps <= kLmMaxPs && Pt >= 1 && Pt <= kLmMaxPt);
+    AFT_DEV_ASSERT(Ps >= 1 && Ps <= kLmMaxPs && Pt >= 0 && Pt <= Args::kMaxPw);
     const float sigma2 = c.noise_var[i_snr];
     const float *fb = a.tables + (size_t)i_ds * a.fblock, *tb = a.tables + (size_t)c.n_ds * a.fblock + (size_t)i_dop * a.tblock;
+    if constexpr (Args::kSeq) tb += lmmse_wblock_offset(c.pilot_symbols, T, live ? w : 1);
     const float2 *ufh = reinterpret_cast<const float2 *>(fb);                       // [Ps(k)][Ps(i)]
     const float2 *fp = ufh + (size_t)Ps * Ps;                                        // [Ps(k)][S]
     const float *lf = fb + 2 * ((size_t)Ps * Ps + (size_t)Ps * S);                   // [Ps]
     const float *ut = tb, *tp = tb + Pt * Pt, *lt = tp + (size_t)Pt * T;             // [Pt(j)][Pt(l)], [Pt(l)][T], [Pt]
 
-    for (int i = tid; i < Ps * Pt; i += kFrameThreads) pc[i] = a.pilots[b * (size_t)(Ps * Pt) + i];
+    for (int i = tid; i < Ps * Pt; i += kFrameThreads) {
+        if constexpr (Args::kSeq) {                                                  // column q of row r: symbol j of the window's slot q / Pt
+            const int p1 = c.pilot_symbols, r = i / Pt, q = i - r * Pt, sl = q / p1, j = q - sl * p1;
+            AFT_DEV_ASSERT(sl < w && r < Ps);
+            pc[i] = a.pilots[(first + (size_t)sl * (size_t)hop) * (size_t)(Ps * p1) + (size_t)(r * p1 + j)];
+        } else {
+            pc[i] = a.pilots[b * (size_t)(Ps * Pt) + i];
+        }
+    }
     __syncthreads();
     for (int i = tid; i < Ps * Pt; i += kFrameThreads) {                            // y1[k][j] = sum_i conj(U_f[i][k]) P[i][j]
         const int k = i / Pt, j = i - k * Pt;
@@ -116,7 +161,7 @@ __global__ __launch_bounds__(kFrameThreads) void lmmse_kernel(const LmmseArgs a)
             float2 acc[kFrameCols];
 #pragma unroll
             for (int j = 0; j < kFrameCols; ++j) acc[j] = make_float2(0.f, 0.f);
-            for (int k = 0; k < Ps; ++k) {
+            for (int k = 0; k < Pk; ++k) {
                 AFT_DEV_ASSERT(s < S && col + kFrameCols <= kFrameTile);
                 const float2 f = fp[(size_t)k * S + s];
 #pragma unroll
@@ -127,6 +172,23 @@ __global__ __launch_bounds__(kFrameThreads) void lmmse_kernel(const LmmseArgs a)
             store_row_piece(a.est + (b * S + s) * (size_t)T + t0 + col, acc, n, a.wide);
         }
     }
+}
+
+__global__ __launch_bounds__(kFrameThreads) void lmmse_kernel(const LmmseArgs a) {
+    __shared__ float2 pc[kLmMaxPs * kLmMaxPt];
+    __shared__ float2 y1[kLmMaxPs * kLmMaxPt];
+    __shared__ float2 v[kLmMaxPs][kFrameTile];
+    lmmse_body(a, pc, y1, v);
+}
+
+// kPw = 32: 40 KB of LDS, any window; kPw = 16: the single-slot kernel's 24 KB, for windows of at most 16 pilot symbols (two more
+// workgroups per CU).  The same body: a frame's bits do not depend on which of the two ran.
+template <int kPw>
+__global__ __launch_bounds__(kFrameThreads) void lmmse_seq_kernel(const LmmseSeqArgs<kPw> a) {
+    __shared__ float2 pc[kLmMaxPs * kPw];
+    __shared__ float2 y1[kLmMaxPs * kPw];
+    __shared__ float2 v[kLmMaxPs][kFrameTile];
+    lmmse_body(a, pc, y1, v);
 }
 
 }  // namespace
@@ -141,9 +203,15 @@ size_t lmmse_tblock_floats(const aft_lmmse &p) {
     return Pt * Pt + Pt * (size_t)p.num_symbols + Pt;
 }
 
-hipError_t launch_lmmse(const aft_lmmse &plan, const float *tables, const float *pilots, const float *snr, const float *ds,
-                        const float *dop, float *est, int batch, hipStream_t st) {
-    LmmseArgs a{};
+size_t lmmse_seq_tblock_floats(const aft_lmmse &p, int window) {
+    return (size_t)lmmse_wblock_offset((unsigned long long)p.pilot_symbols, (unsigned long long)p.num_symbols, (unsigned long long)window + 1);
+}
+
+namespace {
+
+template <class Args>
+void fill_args(Args &a, const aft_lmmse &plan, const float *tables, const float *pilots, const float *snr, const float *ds,
+               const float *dop, float *est) {
     a.c = plan;
     a.tables = tables;
     a.pilots = reinterpret_cast<const float2 *>(pilots);
@@ -152,7 +220,29 @@ hipError_t launch_lmmse(const aft_lmmse &plan, const float *tables, const float 
     a.fblock = lmmse_fblock_floats(plan);
     a.tblock = lmmse_tblock_floats(plan);
     a.wide = wide_ok(plan.num_symbols, est);
+}
+
+}  // namespace
+
+hipError_t launch_lmmse(const aft_lmmse &plan, const float *tables, const float *pilots, const float *snr, const float *ds,
+                        const float *dop, float *est, int batch, hipStream_t st) {
+    LmmseArgs a{};
+    fill_args(a, plan, tables, pilots, snr, ds, dop, est);
     hipLaunchKernelGGL(lmmse_kernel, dim3((unsigned)batch), dim3(kFrameThreads), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_lmmse_seq(const aft_lmmse &plan, int group, int slots, int window, int horizon, const float *tables,
+                            const float *pilots, const float *snr, const float *ds, const float *dop, float *est, int batch,
+                            hipStream_t st) {
+    auto launch = [&](auto a) {
+        fill_args(a, plan, tables, pilots, snr, ds, dop, est);
+        a.tblock = lmmse_seq_tblock_floats(plan, window);
+        a.group = group; a.slots = slots; a.window = window; a.horizon = horizon;
+        hipLaunchKernelGGL(lmmse_seq_kernel<decltype(a)::kMaxPw>, dim3((unsigned)batch), dim3(kFrameThreads), 0, st, a);
+    };
+    if (window * plan.pilot_symbols <= kLmMaxPt) launch(LmmseSeqArgs<kLmMaxPt>{});
+    else launch(LmmseSeqArgs<kLmMaxPw>{});
     return hipGetLastError();
 }
 

@@ -488,8 +488,8 @@ class LmmsePlan:
         self.fixed = (self.plan.fixed_snr, self.plan.fixed_ds, self.plan.fixed_dop)
         self.grid, self.pilot = tuple(self.tables.cfg.ofdm), tuple(self.tables.cfg.pilot)
         if image is None:
-            image = torch.from_numpy(self.tables.image()).to(self.device)
-        floats = _lib.load().aft_lmmse_table_floats(C.byref(self.plan))
+            image = torch.from_numpy(self._host_image()).to(self.device)
+        floats = self._image_floats(_lib.load())
         if image.dtype != torch.float32 or image.device != self.device or not image.is_contiguous() or image.numel() != floats:
             raise ValueError(f"the table image must be {floats} contiguous float32 values on {self.device} (got {image.numel()} "
                              f"{image.dtype} on {image.device})")
@@ -510,9 +510,41 @@ class LmmsePlan:
                 continue
             conds.append(_in_place(name, c, torch.float32, self.device, batch))
         est = torch.empty((batch, *self.grid), dtype=torch.complex64, device=self.device)   # the kernel writes every element
-        _lib.check(lib.aft_lmmse_f32(C.byref(self.plan), self.image.data_ptr(), pil.data_ptr(), *(_ptr(c) for c in conds),
-                                     est.data_ptr(), batch, _lib.current_stream_ptr(self.device)), lib)
+        _lib.check(self._launch(lib, pil.data_ptr(), [_ptr(c) for c in conds], est.data_ptr(), batch), lib)
         return est
+
+    def _host_image(self) -> np.ndarray:
+        return self.tables.image()
+
+    def _image_floats(self, lib) -> int:
+        return lib.aft_lmmse_table_floats(C.byref(self.plan))
+
+    def _launch(self, lib, pilots: int, conds, est: int, batch: int) -> int:
+        return lib.aft_lmmse_f32(C.byref(self.plan), self.image.data_ptr(), pilots, *conds, est, batch, _lib.current_stream_ptr(self.device))
+
+
+class LmmseSeqPlan(LmmsePlan):
+    """``LmmsePlan`` for the multi-slot estimator (``lmmse.LmmseTables(cfg, window, horizon)``): the image is ``seq_image()`` and
+    ``plan(pilots, snr, ds, dop)`` is one launch of ``aft_lmmse_seq_f32`` over a batch of WHOLE sequences in order (``batch`` a multiple of
+    ``slots * group``; the entry point refuses anything else).  Everything else is ``LmmsePlan``'s: inputs on the device or in pinned
+    host memory, None for a condition that ``assume`` pins, ``lib=`` for another build of the library."""
+
+    def __init__(self, cfg, device: torch.device, assume=None, image: Optional[torch.Tensor] = None) -> None:
+        from .lmmse import LmmseTables
+        tables = cfg if isinstance(cfg, LmmseTables) else LmmseTables(cfg)
+        self.group, self.slots = tables.cfg.group, tables.cfg.slots
+        self.window, self.horizon = tables.window, tables.horizon
+        super().__init__(tables, device, assume=assume, image=image)
+
+    def _host_image(self) -> np.ndarray:
+        return self.tables.seq_image()
+
+    def _image_floats(self, lib) -> int:
+        return lib.aft_lmmse_seq_table_floats(C.byref(self.plan), self.window)
+
+    def _launch(self, lib, pilots: int, conds, est: int, batch: int) -> int:
+        return lib.aft_lmmse_seq_f32(C.byref(self.plan), self.group, self.slots, self.window, self.horizon, self.image.data_ptr(), pilots,
+                                     *conds, est, batch, _lib.current_stream_ptr(self.device))
 
 
 class LinkPlan:

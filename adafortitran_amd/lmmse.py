@@ -21,6 +21,20 @@ which is ``R_hp (R_pp + sigma2 I)^-1 p`` with ``R_pp = R_f (x) R_t`` written in 
 float32 the inverse loses 5e-4 of |est|max where cond(R_pp + sigma2 I) is 2e4; the eigenbasis form stays at float32's own rounding),
 and the tables are per delay spread and per Doppler, never per condition triple.  Eigenvalues are clamped at 0 from below.
 
+Smoothing and prediction over slot sequences.  On a sequence configuration (``slots = K``, ``slot_symbols = L``, groups of G) the
+statistics are known ACROSS slots too -- ``r_t`` at the absolute symbol -- so the best linear estimate of slot ``k`` from the pilots of
+the last ``W`` slots up to slot ``k - h`` can be written down as well (``LmmseTables(cfg, window=W, horizon=h)``).  Frame ``(seq, k, a)``,
+index ``(seq K + k) G + a``: with ``n = k - h + 1`` the estimate is all zeros when ``n <= 0`` (no observation); otherwise ``w = min(W, n)``
+and the observations are member ``a``'s pilots of slots ``k - h - w + 1 .. k - h``, oldest first, side by side along time, ``P [Ps, w Pt]``.
+Their symbols sit at ``q_(i,j) = (i - (w - 1) - h) L + sym_j`` relative to the target slot's symbol 0, and::
+
+    R_t^(w) = r_t(q - q') = U_t^(w) diag(lt^(w)) U_t^(w)T     T'^(w) = r_t(t - q) U_t^(w)  [T, w Pt]
+    est = F' [ D o (U_f^H P U_t^(w)) ] T'^(w)T,               D[k][l] = 1 / (lf[k] lt^(w)[l] + sigma2)
+
+-- the same Kronecker eigenbasis form with ``w Pt`` for ``Pt``; the frequency tables are untouched and the design point is the TARGET
+frame's.  ``lmmse_seq_estimate_host`` is the float64 twin, ``aft_lmmse_seq_f32`` (``hip_ops.LmmseSeqPlan``) the device's one launch per
+batch, ``LmmseEstimator(cfg, window=W, horizon=h)`` the module.  ``W = 1, h = 0`` is the single-slot estimator, table for table.
+
 Which design point a frame uses: per condition the index of the NEAREST table value (``|v - value[i]|`` in float64, ties to the lower
 index, NaN to index 0) -- a total function, no error path; ``assume=dict(snr_db=.., delay_spread_ns=.., doppler_hz=..)`` pins any of the
 three for every frame, whatever its meta says (the mismatched, or robust, receiver); a pinned value is chosen by nearest value too.
@@ -37,6 +51,7 @@ from . import _abi
 from .chansim import ChannelSimConfig
 
 CONDITIONS = ("snr_db", "delay_spread_ns", "doppler_hz")
+MAX_WINDOW = 16                                                  # slots a window may span
 
 
 def j0(x, n: Optional[int] = None) -> np.ndarray:
@@ -88,15 +103,36 @@ def _check_assume(assume) -> Dict[str, float]:
     return out
 
 
+def _check_window(cfg: ChannelSimConfig, window, horizon) -> Tuple[int, int]:
+    """(window, horizon) as integers, or the refusal that names the fix."""
+    if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in (window, horizon)):
+        raise ValueError(f"window = {window!r}, horizon = {horizon!r}: both must be integers")
+    W, h, K, Pt = int(window), int(horizon), cfg.slots, cfg.pilot[1]
+    if not 1 <= W <= MAX_WINDOW:
+        raise ValueError(f"window = {W} is outside 1..{MAX_WINDOW}: choose a window of 1 to {MAX_WINDOW} slots")
+    if W * Pt > _abi.AFT_LMMSE_MAX_WINDOW_PILOTS:
+        raise ValueError(f"window * Pt = {W} * {Pt} = {W * Pt} pilot symbols exceed the {_abi.AFT_LMMSE_MAX_WINDOW_PILOTS} a window may "
+                         f"hold: use window <= {_abi.AFT_LMMSE_MAX_WINDOW_PILOTS // Pt}")
+    if (W > 1 or h != 0) and K == 1:
+        raise ValueError(f"window = {W}, horizon = {h} need a slot sequence: build the ChannelSimConfig with slots > 1 (it has slots = 1)")
+    if not 0 <= h < K:
+        raise ValueError(f"horizon = {h} is outside 0..{K - 1}: a prediction looks at most slots - 1 = {K - 1} slots ahead")
+    return W, h
+
+
 class LmmseTables:
     """The estimator's tables for one ``ChannelSimConfig``: float64 (``sigma2 [n_snr]``; per delay spread ``lam_f [Ps]``, ``u_f
     [Ps, Ps]``, ``f [S, Ps]`` = F'; per Doppler ``lam_t [Pt]``, ``u_t [Pt, Pt]``, ``t [T, Pt]`` = T') and ``image()``, the float32
-    array ``aft_lmmse_f32`` reads (include/adafortitran_amd.h documents its layout)."""
+    array ``aft_lmmse_f32`` reads (include/adafortitran_amd.h documents its layout).  With ``window > 1`` or ``horizon > 0`` (module
+    docstring; the config must have ``slots > 1``) it also holds, per Doppler, the lists ``lam_t_w``, ``u_t_w``, ``t_w`` over
+    ``w = 1 .. window`` (entry ``w - 1``: ``[w Pt]``, ``[w Pt, w Pt]``, ``[T, w Pt]``), and ``seq_image()`` is what ``aft_lmmse_seq_f32``
+    reads.  The defaults leave the object and ``image()`` as they are without the two keywords."""
 
-    def __init__(self, cfg: ChannelSimConfig) -> None:
+    def __init__(self, cfg: ChannelSimConfig, window: int = 1, horizon: int = 0) -> None:
         if not isinstance(cfg, ChannelSimConfig):
             raise ValueError(f"LmmseTables needs a chansim.ChannelSimConfig (got {type(cfg).__name__})")
         self.cfg = cfg
+        self.window, self.horizon = _check_window(cfg, window, horizon)
         t = cfg.tables()
         S, T = cfg.ofdm
         self.values = {k: t[k].astype(np.float64) for k in CONDITIONS}
@@ -117,6 +153,41 @@ class LmmseTables:
             self.lam_t.append(np.maximum(lam, 0.0))
             self.u_t.append(u)
             self.t.append(self.r_t(np.arange(T)[:, None] - self.sym[None, :], i) @ u)
+        if self.multi_slot:                                      # per Doppler the lists over w = 1 .. W (entry w - 1)
+            self.lam_t_w, self.u_t_w, self.t_w = [], [], []
+            for i in range(len(self.doppler_turns)):
+                lams, us, ts = [], [], []
+                for w in range(1, self.window + 1):
+                    q = self.window_symbols(w)
+                    lam, u = np.linalg.eigh(self.r_t(q[:, None] - q[None, :], i))
+                    lams.append(np.maximum(lam, 0.0))
+                    us.append(u)
+                    ts.append(self.r_t(np.arange(T)[:, None] - q[None, :], i) @ u)
+                self.lam_t_w.append(lams)
+                self.u_t_w.append(us)
+                self.t_w.append(ts)
+
+    @property
+    def multi_slot(self) -> bool:
+        return self.window > 1 or self.horizon > 0
+
+    def window_symbols(self, w: int) -> np.ndarray:
+        """The ``w Pt`` pilot symbols of a window of ``w`` slots that ends ``horizon`` slots before the target slot, relative to the
+        target slot's symbol 0, oldest first: ``(i - (w - 1) - horizon) L + sym_j``."""
+        slot = (np.arange(w) - (w - 1) - self.horizon) * self.cfg.slot_symbols
+        return (slot[:, None] + self.sym[None, :]).reshape(-1)
+
+    def slot_window(self, k) -> np.ndarray:
+        """``w`` of slot ``k``: ``min(window, k - horizon + 1)``, 0 where there is nothing to look at."""
+        return np.clip(np.asarray(k, dtype=np.int64) - self.horizon + 1, 0, self.window)
+
+    def time(self, i_dop: int, w: int):
+        """``(lt^(w) [w Pt], U_t^(w) [w Pt, w Pt], T'^(w) [T, w Pt])`` of a Doppler."""
+        if not 1 <= w <= self.window:
+            raise ValueError(f"w = {w} is outside 1..{self.window}, the window these tables were built for")
+        if not self.multi_slot:
+            return self.lam_t[i_dop], self.u_t[i_dop], self.t[i_dop]
+        return self.lam_t_w[i_dop][w - 1], self.u_t_w[i_dop][w - 1], self.t_w[i_dop][w - 1]
 
     def r_f(self, d, i_ds: int) -> np.ndarray:
         """Frequency correlation at subcarrier lag ``d`` (complex128, d's shape)."""
@@ -141,9 +212,10 @@ class LmmseTables:
         a = _check_assume(assume)
         return tuple(int(nearest_index(self.values[name], a[name])) if name in a else -1 for name in CONDITIONS)
 
-    def gain(self, i_snr: int, i_ds: int, i_dop: int) -> np.ndarray:
-        """D [Ps, Pt] of a design point."""
-        return 1.0 / (self.lam_f[i_ds][:, None] * self.lam_t[i_dop][None, :] + self.sigma2[i_snr])
+    def gain(self, i_snr: int, i_ds: int, i_dop: int, w: Optional[int] = None) -> np.ndarray:
+        """D [Ps, Pt] of a design point; with ``w`` the window's, [Ps, w Pt]."""
+        lam_t = self.lam_t[i_dop] if w is None else self.time(i_dop, w)[0]
+        return 1.0 / (self.lam_f[i_ds][:, None] * lam_t[None, :] + self.sigma2[i_snr])
 
     def image(self) -> np.ndarray:
         """The float32 table image of ``aft_lmmse_f32``."""
@@ -154,6 +226,20 @@ class LmmseTables:
             parts += [pairs(u.conj().T), pairs(f.T), lam, np.zeros(Ps & 1)]
         for lam, u, t in zip(self.lam_t, self.u_t, self.t):
             parts += [u.reshape(-1), t.T.reshape(-1), lam]
+        return np.concatenate(parts).astype(np.float32)
+
+    def seq_image(self) -> np.ndarray:
+        """The float32 table image of ``aft_lmmse_seq_f32``: the frequency blocks of ``image()``, then per Doppler the ``window``
+        sub-blocks ``U_t^(w)``, ``T'^(w)`` (l-major), ``lt^(w)`` for ``w = 1 .. window``.  With ``window = 1, horizon = 0`` it is ``image()``."""
+        Ps = self.cfg.pilot[0]
+        pairs = lambda z: np.stack([z.real, z.imag], axis=-1).reshape(-1)  # noqa: E731
+        parts = []
+        for lam, u, f in zip(self.lam_f, self.u_f, self.f):
+            parts += [pairs(u.conj().T), pairs(f.T), lam, np.zeros(Ps & 1)]
+        for i in range(len(self.doppler_turns)):
+            for w in range(1, self.window + 1):
+                lam, u, t = self.time(i, w)
+                parts += [u.reshape(-1), t.T.reshape(-1), lam]
         return np.concatenate(parts).astype(np.float32)
 
     def to_struct(self, assume=None) -> "_abi.AftLmmse":
@@ -198,27 +284,85 @@ def lmmse_estimate_host(cfg: Union[ChannelSimConfig, LmmseTables], pilots, condi
     return out
 
 
+def _seq_tables(tables: Union[ChannelSimConfig, LmmseTables], window, horizon) -> LmmseTables:
+    """The tables a multi-slot call works with: ``tables`` itself when ``window`` / ``horizon`` (None: its own) fit it."""
+    if not isinstance(tables, LmmseTables):
+        return LmmseTables(tables, 1 if window is None else window, 0 if horizon is None else horizon)
+    W, h = tables.window if window is None else window, tables.horizon if horizon is None else horizon
+    if h == tables.horizon and 1 <= W <= tables.window:          # a shorter window of the same horizon is among its lists
+        return tables
+    return LmmseTables(tables.cfg, W, h)
+
+
+def lmmse_seq_estimate_host(tables: Union[ChannelSimConfig, LmmseTables], pilots, conditions, assume=None) -> np.ndarray:
+    """The multi-slot definition in float64 (module docstring): pilots ``[n, Ps, Pt]`` of whole sequences in order (``n`` a multiple of
+    ``K G``) and conditions ``[n, 3]`` -> complex128 ``[n, S, T]``.  Window and horizon are the tables' (``LmmseTables(cfg, window,
+    horizon)``; a bare config means 1 and 0, the single-slot estimator).  A frame's design point comes from its OWN row of
+    ``conditions``.  Needs no library."""
+    tb = _tables(tables)
+    cfg = tb.cfg
+    pilots = np.asarray(pilots).astype(np.complex128)
+    if pilots.ndim != 3 or pilots.shape[1:] != tuple(cfg.pilot):
+        raise ValueError(f"Expected pilot shape (n, {cfg.pilot[0]}, {cfg.pilot[1]}), got {pilots.shape}")
+    K, G, n = cfg.slots, cfg.group, len(pilots)
+    if n % (K * G):
+        raise ValueError(f"{n} frames are not whole sequences: pass a multiple of slots * group = {K} * {G} = {K * G} frames, in "
+                         f"sequence order")
+    if conditions is None:
+        if min(tb.fixed(assume)) < 0:
+            raise ValueError("conditions are required unless assume pins all three")
+        conditions = np.zeros((n, 3))
+    i_snr, i_ds, i_dop = tb.indices(conditions, assume)
+    if len(i_snr) != n:
+        raise ValueError(f"{n} frames but {len(i_snr)} rows of conditions")
+    Ps, Pt = cfg.pilot
+    out = np.zeros((n, *cfg.ofdm), dtype=np.complex128)
+    frame = np.arange(n)
+    ws = tb.slot_window(frame // G % K)
+    key = (i_snr * 1024 + i_ds * 32 + i_dop) * 64 + ws
+    for k in np.unique(key[ws > 0]):
+        sel = np.nonzero(key == k)[0]
+        a, d, e, w = int(i_snr[sel[0]]), int(i_ds[sel[0]]), int(i_dop[sel[0]]), int(ws[sel[0]])
+        _, u_t, t = tb.time(e, w)
+        src = sel[:, None] - (tb.horizon + w - 1 - np.arange(w))[None, :] * G                 # [m, w], oldest first
+        p = pilots[src].transpose(0, 2, 1, 3).reshape(len(sel), Ps, w * Pt) if w > 1 or tb.horizon else pilots[sel]
+        y = np.einsum("ik,nij,jl->nkl", tb.u_f[d].conj(), p, u_t) * tb.gain(a, d, e, w)[None]
+        out[sel] = np.einsum("sk,nkl,tl->nst", tb.f[d], y, t)
+    return out
+
+
 def lmmse_predicted_mse(cfg: Union[ChannelSimConfig, LmmseTables], snr_db: float, delay_spread_ns: float, doppler_hz: float,
-                        assume=None) -> float:
+                        assume=None, window: Optional[int] = None, horizon: Optional[int] = None, slot: Optional[int] = None) -> float:
     """The closed-form MSE per grid element of the estimator on frames drawn at the given condition (its nearest table values).
     Matched: ``1 - (1 / ST) sum_{s,t} sum_{k,l} |F'_sk|^2 T'_tl^2 D_kl``.  With ``assume`` the estimator ``W`` is that of the pinned
     design while the statistics are the true ones: ``1 - 2 Re diag(W R_ph) + diag(W (R_pp + sigma2 I) W^H)``, averaged over the grid
-    (full matrices: host only)."""
-    tb = _tables(cfg)
+    (full matrices: host only).
+    ``window`` / ``horizon`` (None: the tables' own, 1 and 0 for a config): the multi-slot estimator's MSE on a slot with a FULL
+    window -- the same expressions over ``T'^(W)`` and over the window's pilot set.  ``slot=k`` gives slot k's value instead, with its
+    shorter window ``w = min(W, k - h + 1)`` early in a sequence, and 1.0 (``E|H|^2``) where there is nothing to look at."""
+    tb = _seq_tables(cfg, window, horizon)
+    w = int(tb.window if window is None else window)
+    if slot is not None:
+        if not 0 <= int(slot) < tb.cfg.slots:
+            raise ValueError(f"slot = {slot} is outside 0..{tb.cfg.slots - 1}")
+        w = int(min(w, int(slot) - tb.horizon + 1))
+        if w <= 0:
+            return 1.0
     true = tuple(int(v[0]) for v in tb.indices([[snr_db, delay_spread_ns, doppler_hz]]))
     used = tuple(int(v[0]) for v in tb.indices([[snr_db, delay_spread_ns, doppler_hz]], assume))
     S, T = tb.cfg.ofdm
     if used == true:
         a, d, e = true
-        return float(1.0 - np.einsum("sk,tl,kl->", np.abs(tb.f[d]) ** 2, tb.t[e] ** 2, tb.gain(a, d, e)) / (S * T))
+        return float(1.0 - np.einsum("sk,tl,kl->", np.abs(tb.f[d]) ** 2, tb.time(e, w)[2] ** 2, tb.gain(a, d, e, w)) / (S * T))
     a, d, e = used
-    w = (np.kron(tb.f[d], tb.t[e]) * tb.gain(a, d, e).reshape(-1)[None, :]) @ np.kron(tb.u_f[d], tb.u_t[e]).conj().T      # [ST, PsPt]
+    _, u_t, t_p = tb.time(e, w)
+    w_mat = (np.kron(tb.f[d], t_p) * tb.gain(a, d, e, w).reshape(-1)[None, :]) @ np.kron(tb.u_f[d], u_t).conj().T          # [ST, Ps wPt]
     a, d, e = true
-    s, t = np.arange(S), np.arange(T)
-    r_ph = np.kron(tb.r_f(tb.sc[:, None] - s[None, :], d), tb.r_t(tb.sym[:, None] - t[None, :], e))                        # [PsPt, ST]
-    r_pp = np.kron(tb.r_f(tb.sc[:, None] - tb.sc[None, :], d), tb.r_t(tb.sym[:, None] - tb.sym[None, :], e))
+    s, t, q = np.arange(S), np.arange(T), tb.window_symbols(w)
+    r_ph = np.kron(tb.r_f(tb.sc[:, None] - s[None, :], d), tb.r_t(q[:, None] - t[None, :], e))                             # [Ps wPt, ST]
+    r_pp = np.kron(tb.r_f(tb.sc[:, None] - tb.sc[None, :], d), tb.r_t(q[:, None] - q[None, :], e))
     r_pp = r_pp + tb.sigma2[a] * np.eye(len(r_pp))
-    per = 1.0 - 2.0 * np.real((w * r_ph.T).sum(axis=1)) + np.real(((w @ r_pp) * w.conj()).sum(axis=1))
+    per = 1.0 - 2.0 * np.real((w_mat * r_ph.T).sum(axis=1)) + np.real(((w_mat @ r_pp) * w_mat.conj()).sum(axis=1))
     return float(per.mean())
 
 
@@ -229,16 +373,24 @@ class LmmseEstimator(nn.Module):
 
     On a HIP device a forward is ONE launch of ``aft_lmmse_f32`` on the current stream: CPU pilots and CPU conditions are placed in a
     slot of the pinned ring (``estimators._InputStager``) which the kernel reads in place -- no copy is enqueued, nothing is read back,
-    nothing synchronises.  On the CPU the float64 definition is evaluated and rounded to complex64."""
+    nothing synchronises.  On the CPU the float64 definition is evaluated and rounded to complex64.
 
-    def __init__(self, cfg: ChannelSimConfig, assume=None) -> None:
+    ``window=W`` / ``horizon=h`` (module docstring, "smoothing and prediction over slot sequences"; the defaults are the single-slot
+    estimator, launch for launch): slot k of every sequence is estimated from the pilots of the last W slots up to slot k - h.  A batch
+    must then hold WHOLE sequences in order (``B`` a multiple of ``slots * group``), as ``SynthLoader``, ``make_pack`` and an unshuffled
+    ``ResidentLoader`` deliver them; the forward is one launch of ``aft_lmmse_seq_f32`` through the same pinned ring, and on the CPU
+    ``lmmse_seq_estimate_host``."""
+
+    def __init__(self, cfg: ChannelSimConfig, assume=None, window: int = 1, horizon: int = 0) -> None:
         super().__init__()
-        self.tables = LmmseTables(cfg)
+        self.tables = LmmseTables(cfg, window, horizon)
+        self.window, self.horizon = self.tables.window, self.tables.horizon
         self.cfg = cfg
         self.assume = _check_assume(assume)
         self.fixed = self.tables.fixed(self.assume)
         self.ofdm_size, self.pilot_size = tuple(cfg.ofdm), tuple(cfg.pilot)
-        self.register_buffer("table_image", torch.from_numpy(self.tables.image()), persistent=False)
+        image = self.tables.seq_image() if self.tables.multi_slot else self.tables.image()
+        self.register_buffer("table_image", torch.from_numpy(image), persistent=False)
         self._plan = None
         self._stager = None
 
@@ -251,9 +403,16 @@ class LmmseEstimator(nn.Module):
         if img.dtype != torch.float32:
             raise ValueError(f"the LMMSE table image must stay float32 on the HIP device (it is {img.dtype})")
         if self._plan is None or self._plan.image.data_ptr() != img.data_ptr():
-            from .hip_ops import LmmsePlan         # loads the extension: a missing .so raises here, loudly
-            self._plan = LmmsePlan(self.tables, img.device, assume=self.assume, image=img)
+            from .hip_ops import LmmsePlan, LmmseSeqPlan   # loads the extension: a missing .so raises here, loudly
+            plan = LmmseSeqPlan if self.tables.multi_slot else LmmsePlan
+            self._plan = plan(self.tables, img.device, assume=self.assume, image=img)
         return self._plan
+
+    def steady_slots(self) -> range:
+        """``range(W - 1 + h, K)``: the slots of a sequence whose window is full.  The evaluation sweep (``evaluation.get_test_stats``)
+        averages over ALL slots, the warm-up slots before these included (their shorter windows, and the all-zero estimates of the first
+        ``h`` slots, whose error is ``|H|^2``); a per-slot figure has to select these slots itself."""
+        return range(self.window - 1 + self.horizon, self.cfg.slots)
 
     def forward(self, pilot_symbols: torch.Tensor, meta_data: Optional[tuple] = None) -> torch.Tensor:
         if pilot_symbols.dim() != 3 or tuple(pilot_symbols.shape[1:]) != self.pilot_size:
@@ -261,6 +420,10 @@ class LmmseEstimator(nn.Module):
         if pilot_symbols.dtype != torch.complex64:
             raise ValueError(f"pilot_symbols must be complex64, got {pilot_symbols.dtype}")
         B = pilot_symbols.shape[0]
+        unit = self.cfg.sequence()
+        if self.tables.multi_slot and B % unit:
+            raise ValueError(f"window = {self.window}, horizon = {self.horizon} need whole sequences in order: the batch of {B} frames "
+                             f"is not a multiple of slots * group = {self.cfg.slots} * {self.cfg.group} = {unit}")
         conds = None
         if meta_data is not None:
             _, snr, ds, dop, _, _ = meta_data
@@ -272,7 +435,8 @@ class LmmseEstimator(nn.Module):
         dev = self.table_image.device
         if dev.type != "cuda":
             cond = None if conds is None else np.stack([c.detach().cpu().reshape(-1).double().numpy() for c in conds], axis=1)
-            est = lmmse_estimate_host(self.tables, pilot_symbols.detach().cpu().numpy(), cond, self.assume)
+            host = lmmse_seq_estimate_host if self.tables.multi_slot else lmmse_estimate_host
+            est = host(self.tables, pilot_symbols.detach().cpu().numpy(), cond, self.assume)
             return torch.from_numpy(est.astype(np.complex64))
         if B == 0:
             return torch.empty((0, *self.ofdm_size), dtype=torch.complex64, device=dev)
@@ -300,4 +464,4 @@ class LmmseEstimator(nn.Module):
 
     def get_model_info(self) -> dict:
         return {"model_name": self.__class__.__name__, "ofdm_size": self.ofdm_size, "pilot_size": self.pilot_size,
-                "assume": dict(self.assume), "device": str(self.table_image.device), "total_parameters": 0, "trainable_parameters": 0}
+                "assume": dict(self.assume), "window": self.window, "horizon": self.horizon, "device": str(self.table_image.device), "total_parameters": 0, "trainable_parameters": 0}

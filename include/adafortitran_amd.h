@@ -392,6 +392,35 @@ size_t aft_lmmse_table_floats(const aft_lmmse *plan);
 int aft_lmmse_f32(const aft_lmmse *plan, const float *tables, const float *pilots, const float *snr, const float *ds,
                   const float *dop, float *est, int batch, void *stream);
 
+/* The multi-slot form (lmmse.py "smoothing and prediction over slot sequences"): the batch is whole sequences of the simulator's,
+ * `slots` = K slots of `group` = G frames each, slot-major (aft_channel_sim_seq_f32's order): frame (seq, k, a) is (seq K + k) G + a.
+ * Target frame (seq, k, a) is estimated from the pilots of member a in the w = min(window, k - horizon + 1) slots that end at slot
+ * k - horizon, oldest first, side by side along time: P is [Ps, w Pt], and with it
+ *   R_t^(w) = r_t(q - q') = U_t^(w) diag(lt^(w)) U_t^(w)T over the window's w Pt pilot symbols q = (i - (w - 1) - horizon) L + sym_j
+ *             (relative to the target slot's symbol 0; L the symbols from one slot's start to the next),  T'^(w) = r_t(t - q) U_t^(w),
+ *   est = F' [ D o (U_f^H P U_t^(w)) ] T'^(w)T,    D[k][l] = 1 / (lf[k] lt^(w)[l] + noise_var).
+ * With k < horizon there is nothing to look at: est is +0 in every component and nothing is read for that frame.  The design point is
+ * the TARGET frame's (its own entries of snr / ds / dop).  L and horizon's effect on q live in the tables only.  The image: the n_ds
+ * blocks of aft_lmmse_f32's image, then per Doppler i the `window` sub-blocks for w = 1 .. window, adjacent, sub-block w holding
+ *     U_t^(w)  real  [w Pt(j)][w Pt(l)],    T'^(w)  real  [w Pt(l)][T],    lt^(w)  real  [w Pt]
+ * (w Pt (w Pt + T + 1) floats); aft_lmmse_seq_table_floats gives the image's length.  With window = 1 and horizon = 0 image and
+ * output are aft_lmmse_f32's, bit for bit: every product stage is the same chain of fused multiply-adds in increasing index from +0,
+ * over w Pt terms where that has Pt.  A frame's bits depend on its window's pilots and its conditions only: not on batch, not on the
+ * sequence's place in it, and on k only through w. */
+#define AFT_LMMSE_MAX_WINDOW_PILOTS 32
+
+/* Floats in the multi-slot image of `plan` for `window` (0 where aft_lmmse_seq_f32 would refuse plan or window with AFT_ERR_SHAPE). */
+size_t aft_lmmse_seq_table_floats(const aft_lmmse *plan, int window);
+
+/* One launch, one workgroup per target frame; everything else as aft_lmmse_f32 (the memory each pointer may name, the stores, no
+ * atomics, nothing synchronised, every output element written).  40 KB of static LDS; 24 KB when window * pilot_symbols <= 16 (the same
+ * body on narrower tiles: the bits do not depend on it).
+ * Nothing is launched on AFT_ERR_ARG (aft_lmmse_f32's; batch not a multiple of slots * group) and AFT_ERR_SHAPE (aft_lmmse_f32's;
+ * group outside 1 .. AFT_CHANSIM_MAX_GROUP, slots outside 1 .. AFT_CHANSIM_MAX_SLOTS, window below 1 or above slots,
+ * window * pilot_symbols above AFT_LMMSE_MAX_WINDOW_PILOTS, horizon outside 0 .. slots - 1). */
+int aft_lmmse_seq_f32(const aft_lmmse *plan, int group, int slots, int window, int horizon, const float *tables, const float *pilots,
+                      const float *snr, const float *ds, const float *dop, float *est, int batch, void *stream);
+
 /* ---- link-level bit errors (adafortitran_amd/linksim.py holds the definition) ----
  *
  * What a channel estimate is for: data symbols go through the TRUE channel H plus noise, a one-tap equaliser uses the ESTIMATE E, a hard
