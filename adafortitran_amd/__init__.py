@@ -9,11 +9,12 @@ Package contents (only what the hot path needs):
   config         YAML/pydantic config surface
   synth          deterministic synthetic weights + inputs
   metrics        channel-MSE metric (device reduction + RCCL all-gather)
-  lmmse          the LMMSE (Wiener) baseline of the channel simulator, one slot or a window of slots: definition, closed-form MSE, nn.Module
+  lmmse          the LMMSE (Wiener) baseline of the channel simulator, one slot or a window of slots: definition, closed-form MSE, nn.Module;
+                 its design point chosen from the pilots (ConditionEstimator, EstimatedConditions)
 """
 from .config import ModelConfig, SystemConfig, load_config  # noqa: F401
 from .estimators import (AdaFortiTranEstimator, BaseFortiTranEstimator, FortiTranEstimator,  # noqa: F401
                          LinearEstimator)
-from .lmmse import LmmseEstimator  # noqa: F401
+from .lmmse import ConditionEstimator, EstimatedConditions, LmmseEstimator, lmmse_classify_host  # noqa: F401
 
 __version__ = "0.1.0"

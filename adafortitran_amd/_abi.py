@@ -225,6 +225,8 @@ SIGNATURES = {
     "aft_lmmse_f32": (C.c_int, [C.POINTER(AftLmmse), vp, vp, vp, vp, vp, vp, C.c_int, vp]),
     "aft_lmmse_seq_table_floats": (C.c_size_t, [C.POINTER(AftLmmse), C.c_int]),
     "aft_lmmse_seq_f32": (C.c_int, [C.POINTER(AftLmmse)] + [C.c_int] * 4 + [vp, vp, vp, vp, vp, vp, C.c_int, vp]),
+    "aft_lmmse_classify_table_floats": (C.c_size_t, [C.POINTER(AftLmmse), C.c_int]),
+    "aft_lmmse_classify_f32": (C.c_int, [C.POINTER(AftLmmse)] + [C.c_int] * 5 + [vp] * 8 + [C.c_int, vp]),
     "aft_link_errors_f32": (C.c_int, [C.POINTER(AftLink), vp, vp, vp, vp, vp, C.c_int, vp]),
     "aft_link_soft_f32": (C.c_int, [C.POINTER(AftLink), vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp]),
     "aft_link_decode_f32": (C.c_int, [C.POINTER(AftLink), vp, vp, C.c_int, C.c_int, C.c_ulonglong, C.c_ulonglong, C.c_float, vp, vp,

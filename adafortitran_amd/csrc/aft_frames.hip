@@ -57,9 +57,9 @@ int check_lmmse(const aft_lmmse *p) {
     return AFT_OK;
 }
 
-// what the multi-slot form adds to the plan's checks; 0 = fine.  group = 1, slots = window = 1, horizon = 0 always pass
-int check_lmmse_seq(const aft_lmmse *p, int group, int slots, int window, int horizon) {
-    const char *who = "lmmse seq";
+// what the multi-slot form adds to the plan's checks, in the name of the entry point that asks; 0 = fine.  group = 1,
+// slots = window = 1, horizon = 0 always pass
+int check_lmmse_seq(const aft_lmmse *p, int group, int slots, int window, int horizon, const char *who = "lmmse seq") {
     if (!within(who, "group", group, 1, AFT_CHANSIM_MAX_GROUP) || !within(who, "slots", slots, 1, AFT_CHANSIM_MAX_SLOTS) ||
         !within(who, "window", window, 1, slots) ||
         !within(who, "window * pilot_symbols", window * p->pilot_symbols, 1, AFT_LMMSE_MAX_WINDOW_PILOTS) ||
@@ -334,6 +334,31 @@ int aft_lmmse_seq_f32(const aft_lmmse *plan, int group, int slots, int window, i
     hipError_t e = launch_lmmse_seq(*plan, group, slots, window, horizon, tables, pilots, snr, ds, dop, est, batch,
                                     static_cast<hipStream_t>(stream));
     return e == hipSuccess ? AFT_OK : hip_fail("lmmse_seq", e);
+}
+
+size_t aft_lmmse_classify_table_floats(const aft_lmmse *plan, int window) {
+    if (plan == nullptr || check_lmmse(plan) != AFT_OK ||
+        check_lmmse_seq(plan, 1, AFT_CHANSIM_MAX_SLOTS, window, 0, "lmmse classify") != AFT_OK)
+        return 0;
+    return lmmse_classify_table_floats(*plan, window);
+}
+
+int aft_lmmse_classify_f32(const aft_lmmse *plan, int group, int slots, int window, int horizon, int pool, const float *tables,
+                           const float *logdet, const float *pilots, int32_t *idx, float *snr, float *ds, float *dop, float *scores,
+                           int batch, void *stream) {
+    AFT_REQUIRE(plan && tables && logdet && pilots && idx && snr && ds && dop, "lmmse classify: NULL pointer argument (only scores may be NULL)");
+    AFT_REQUIRE(aligned(8, tables, pilots), "lmmse classify: tables and pilots must be 8-byte aligned");
+    AFT_REQUIRE(aligned(4, logdet, snr, ds, dop, scores) && aligned(4, idx), "lmmse classify: logdet, idx, snr, ds, dop and scores must be 4-byte aligned");
+    AFT_REQUIRE(batch >= 1, "lmmse classify: batch must be at least 1 (got %d)", batch);
+    AFT_REQUIRE(pool == 0 || pool == 1, "lmmse classify: pool must be 0 (a frame decides alone) or 1 (a group decides together), got %d", pool);
+    int rc = check_lmmse(plan);
+    if (rc == AFT_OK) rc = check_lmmse_seq(plan, group, slots, window, horizon, "lmmse classify");
+    if (rc != AFT_OK) return rc;
+    AFT_REQUIRE(batch % (slots * group) == 0, "lmmse classify: batch = %d is not a multiple of slots * group = %d * %d: whole sequences only",
+                batch, slots, group);
+    hipError_t e = launch_lmmse_classify(*plan, group, slots, window, horizon, pool, tables, logdet, pilots, idx, snr, ds, dop, scores,
+                                         batch, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? AFT_OK : hip_fail("lmmse_classify", e);
 }
 
 int aft_link_errors_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys,

@@ -388,6 +388,11 @@ size_t lmmse_seq_tblock_floats(const aft_lmmse &plan, int window);
 hipError_t launch_lmmse_seq(const aft_lmmse &plan, int group, int slots, int window, int horizon, const float *tables,
                             const float *pilots, const float *snr, const float *ds, const float *dop, float *est, int batch,
                             hipStream_t st);
+// the design point from the pilots (k_lmmse_classify.hip): everything has passed aft_lmmse_classify_f32's checks; scores may be NULL
+size_t lmmse_classify_table_floats(const aft_lmmse &plan, int window);
+hipError_t launch_lmmse_classify(const aft_lmmse &plan, int group, int slots, int window, int horizon, int pool, const float *tables,
+                                 const float *logdet, const float *pilots, int32_t *idx, float *snr, float *ds, float *dop, float *scores,
+                                 int batch, hipStream_t st);
 // the link-level error count (k_link.hip): `link` has passed aft_link_errors_f32's checks
 hipError_t launch_link_errors(const aft_link &link, const float *ideal, const float *est, const unsigned long long *keys,
                               const float *sigma, int32_t *counts, int batch, hipStream_t st);

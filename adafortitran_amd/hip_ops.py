@@ -547,6 +547,58 @@ class LmmseSeqPlan(LmmsePlan):
                                      *conds, est, batch, _lib.current_stream_ptr(self.device))
 
 
+class LmmseClassifyPlan:
+    """The design point from the pilots (``lmmse.lmmse_classify_host`` is the definition) planned ONCE: the ``aft_lmmse`` struct, the
+    estimator's own float32 image (``seq_image()`` with a window, ``image()`` without) and the log-determinant table
+    (``LmmseTables.classify_image()``) on the device.  ``plan(pilots, scores=False)`` -> ``(idx int32 [batch,3], snr, ds, dop float32
+    [batch][, scores float32 [units, n_snr n_ds n_dop]])`` on the plan's device: one ``torch.empty`` per output, one ``ctypes`` call, one
+    launch (``aft_lmmse_classify_f32``) on the current stream of that device, no synchronisation.  ``pilots`` complex64
+    ``[batch,Ps,Pt]`` live on the plan's device or in pinned host memory; ``batch`` is whole sequences (with single-slot tables: whole
+    groups when pooling, anything otherwise).  ``pool``: a group of frames decides together (units = batch / group), else every frame
+    alone.  ``image`` / ``logdet``: the tables when the caller already holds them on the device.  ``snr``, ``ds`` and ``dop`` are what
+    ``LmmseSeqPlan`` / ``LmmsePlan`` of the same tables take as conditions.  The plan trusts its caller in one thing only: its device
+    is the current one."""
+
+    def __init__(self, cfg, device: torch.device, assume=None, pool: bool = True, image: Optional[torch.Tensor] = None,
+                 logdet: Optional[torch.Tensor] = None) -> None:
+        from .lmmse import LmmseTables
+        self.device = _hip_device(device, "LmmseClassifyPlan", "lmmse.lmmse_classify_host")
+        self.tables = tb = cfg if isinstance(cfg, LmmseTables) else LmmseTables(cfg)
+        self.plan = tb.to_struct(assume)
+        self.fixed = (self.plan.fixed_snr, self.plan.fixed_ds, self.plan.fixed_dop)
+        self.pilot, self.pool = tuple(tb.cfg.pilot), bool(pool)
+        self.window, self.horizon = tb.window, tb.horizon
+        self.slots = tb.cfg.slots if tb.multi_slot else 1                       # single-slot tables look at no other slot ...
+        self.group = tb.cfg.group if (tb.multi_slot or self.pool) else 1        # ... and a frame that decides alone at no other member
+        self.candidates = self.plan.n_snr * self.plan.n_ds * self.plan.n_dop
+        lib = _lib.load()
+        if image is None:
+            image = torch.from_numpy(tb.seq_image() if tb.multi_slot else tb.image()).to(self.device)
+        if logdet is None:
+            logdet = torch.from_numpy(tb.classify_image()).to(self.device)
+        for name, t, floats in (("table image", image, lib.aft_lmmse_seq_table_floats(C.byref(self.plan), self.window)),
+                                ("log-determinant table", logdet, lib.aft_lmmse_classify_table_floats(C.byref(self.plan), self.window))):
+            if t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous() or t.numel() != floats:
+                raise ValueError(f"the {name} must be {floats} contiguous float32 values on {self.device} (got {t.numel()} {t.dtype} on "
+                                 f"{t.device})")
+        self.image, self.logdet = image, logdet
+
+    def __call__(self, pilots: torch.Tensor, scores: bool = False, lib=None):
+        lib = lib or _lib.load()
+        if pilots.dim() != 3 or tuple(pilots.shape[1:]) != self.pilot or pilots.shape[0] < 1:
+            raise ValueError(f"Expected pilot shape (B >= 1, {self.pilot[0]}, {self.pilot[1]}), got {tuple(pilots.shape)}")
+        batch = pilots.shape[0]
+        pil = _in_place("pilots", pilots, torch.complex64, self.device)
+        idx = torch.empty((batch, 3), dtype=torch.int32, device=self.device)    # the kernel writes every element of all of them
+        snr, ds, dop = (torch.empty((batch,), dtype=torch.float32, device=self.device) for _ in range(3))
+        units = batch // self.group if self.pool else batch
+        sc = torch.empty((units, self.candidates), dtype=torch.float32, device=self.device) if scores else None
+        _lib.check(lib.aft_lmmse_classify_f32(C.byref(self.plan), self.group, self.slots, self.window, self.horizon, int(self.pool),
+                                              self.image.data_ptr(), self.logdet.data_ptr(), pil.data_ptr(), idx.data_ptr(), snr.data_ptr(),
+                                              ds.data_ptr(), dop.data_ptr(), _ptr(sc), batch, _lib.current_stream_ptr(self.device)), lib)
+        return (idx, snr, ds, dop, sc) if scores else (idx, snr, ds, dop)
+
+
 class LinkPlan:
     """A link configuration (``linksim.LinkConfig``) turned into the ``aft_link`` struct ONCE.  ``plan(ideal, est, keys, sigma)`` ->
     ``counts int32 [batch, 2]`` = (bit errors, symbol errors) per frame on the plan's device: one ``torch.empty``, one ``ctypes`` call,

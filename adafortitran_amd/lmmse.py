@@ -38,6 +38,28 @@ batch, ``LmmseEstimator(cfg, window=W, horizon=h)`` the module.  ``W = 1, h = 0`
 Which design point a frame uses: per condition the index of the NEAREST table value (``|v - value[i]|`` in float64, ties to the lower
 index, NaN to index 0) -- a total function, no error path; ``assume=dict(snr_db=.., delay_spread_ns=.., doppler_hz=..)`` pins any of the
 three for every frame, whatever its meta says (the mismatched, or robust, receiver); a pinned value is chosen by nearest value too.
+
+Choosing the design point from the pilots.  A receiver has no meta: it has the pilots.  In the eigenbasis above the Gaussian likelihood
+of a window's pilots under a design point ``c = (s, d, e) = (i_snr, i_ds, i_dop)`` is diagonal, so the maximum-likelihood design point
+is a classification over the ``n_snr n_ds n_dop`` candidates in which no matrix is inverted.  Target frame ``(seq, k, a)`` looks at
+exactly what its estimator looks at -- ``w = min(W, k - h + 1)`` slots ending at slot ``k - h``, ``P_a [Ps, w Pt]``, the same tables::
+
+    Z_a = U_f[d]^H P_a U_t^(w)[e]        E_kl = sum_a |Z_a,kl|^2        V_kl = lf[d]_k lt^(w)[e]_l + sigma2[s]
+    score(c) = -( m sum_kl log V_kl + sum_kl E_kl / V_kl )
+
+With ``pool=True`` the sum over ``a`` runs over the ``m = G`` members of the frame's group in member order (the simulator defines a
+group's conditions as shared) and the group is the UNIT that decides; with ``pool=False`` a frame is its own unit (``m = 1``).  This is
+the log-likelihood of the window under a circular Gaussian channel with the simulator's second-order statistics (up to a constant); a
+quasi-likelihood here, because a tap is a sum of 8 rays.  The candidate with the highest score wins; ties go to the lowest flat index
+``(s n_ds + d) n_dop + e``; a NaN score never wins, and where every score is NaN the choice is index 0 per free condition -- a total
+function, like ``nearest_index``.  ``assume`` pins a condition (by nearest value, as above): only candidates with that index compete
+(the others' scores read -inf), and with all three pinned nothing is computed.  With ``w = 0`` (``k < h``) there is nothing to look
+at: the choice is the pinned index or 0 and the competing scores are 0.  ``lmmse_classify_host`` is the float64 twin,
+``aft_lmmse_classify_f32`` (csrc/k_lmmse_classify.hip, through ``hip_ops.LmmseClassifyPlan``) the device's one launch per batch; it
+reads the estimator's own image and ONE more table, ``LmmseTables.classify_image()``: float32 ``sum_kl log V_kl`` per ``(d, e, w, s)``
+(the device takes no logarithm).  ``ConditionEstimator`` is the module, ``LmmseEstimator(conditions="estimated")`` the blind baseline
+(classify, then estimate: two launches, the conditions never leave the device), ``EstimatedConditions`` wraps any estimator with the
+``forward(pilot_symbols, meta_data)`` signature and hands it estimated conditions in place of the loader's.
 """
 from __future__ import annotations
 
@@ -242,6 +264,18 @@ class LmmseTables:
                 parts += [u.reshape(-1), t.T.reshape(-1), lam]
         return np.concatenate(parts).astype(np.float32)
 
+    def logdet(self, i_ds: int, i_dop: int, w: int) -> np.ndarray:
+        """``sum_kl log(lf[k] lt^(w)[l] + sigma2[s])`` for every SNR of the table (float64 ``[n_snr]``)."""
+        lam = self.lam_f[i_ds][:, None] * self.time(i_dop, w)[0][None, :]
+        return np.log(lam[None] + self.sigma2[:, None, None]).sum(axis=(1, 2))
+
+    def classify_image(self) -> np.ndarray:
+        """The float32 table ``aft_lmmse_classify_f32`` reads beside ``seq_image()`` / ``image()``: ``logdet`` as
+        ``[n_ds][n_dop][window][n_snr]`` (entry ``w - 1`` for a window of ``w`` slots)."""
+        out = [self.logdet(d, e, w) for d in range(len(self.delay_turns)) for e in range(len(self.doppler_turns))
+               for w in range(1, self.window + 1)]
+        return np.concatenate(out).astype(np.float32)
+
     def to_struct(self, assume=None) -> "_abi.AftLmmse":
         p = _abi.AftLmmse()
         p.num_scs, p.num_symbols = self.cfg.ofdm
@@ -331,6 +365,83 @@ def lmmse_seq_estimate_host(tables: Union[ChannelSimConfig, LmmseTables], pilots
     return out
 
 
+def _classify_units(tb: LmmseTables, n: int, pool: bool) -> Tuple[int, int, int]:
+    """(K, G, m) a classification of ``n`` frames works with: slots per sequence and frames per slot as far as they matter (single-slot
+    tables look at no other slot, a frame that decides alone at no other member), members per unit; or the refusal that names the fix."""
+    K = tb.cfg.slots if tb.multi_slot else 1
+    G = tb.cfg.group if (tb.multi_slot or pool) else 1
+    if n % (K * G):
+        if K > 1:
+            raise ValueError(f"{n} frames are not whole sequences: pass a multiple of slots * group = {K} * {G} = {K * G} frames, in "
+                             f"sequence order")
+        raise ValueError(f"{n} frames are not whole groups: pass a multiple of group = {G} frames, in group order, or pool=False to "
+                         f"let every frame decide alone")
+    return K, G, (G if pool else 1)
+
+
+def lmmse_classify_host(tables: Union[ChannelSimConfig, LmmseTables], pilots, assume=None, pool: bool = True, return_scores: bool = False):
+    """The design point from the pilots, in float64 (module docstring, "choosing the design point from the pilots"): pilots
+    ``[n, Ps, Pt]`` of whole sequences in order -> ``(idx int64 [n, 3], values float32 [n, 3])``, the chosen ``(i_snr, i_ds, i_dop)`` and
+    the table values ``(snr_db, delay_spread_ns, doppler_hz)`` in the form ``meta`` has; with ``return_scores`` also the scores, float64
+    ``[units, n_snr n_ds n_dop]`` in flat index order, a unit being a group (``pool=True``) or a frame.  Window and horizon are the tables'
+    (a bare config or single-slot tables: 1 and 0, and then any number of whole groups -- of frames with ``pool=False`` -- will do).
+    Needs no library."""
+    tb = _tables(tables)
+    cfg = tb.cfg
+    pilots = np.asarray(pilots).astype(np.complex128)
+    if pilots.ndim != 3 or pilots.shape[1:] != tuple(cfg.pilot):
+        raise ValueError(f"Expected pilot shape (n, {cfg.pilot[0]}, {cfg.pilot[1]}), got {pilots.shape}")
+    if not isinstance(pool, (bool, np.bool_)):
+        raise ValueError(f"pool must be True (a group decides together) or False (every frame alone); got {pool!r}")
+    n = len(pilots)
+    K, G, m = _classify_units(tb, n, bool(pool))
+    Ps, Pt = cfg.pilot
+    fixed = tb.fixed(assume)
+    sizes = tuple(len(tb.values[name]) for name in CONDITIONS)
+    n_snr, n_ds, n_dop = sizes
+    compete = np.ones(sizes, dtype=bool)
+    for axis, f in enumerate(fixed):
+        if f >= 0:
+            keep = np.zeros(sizes[axis], dtype=bool)
+            keep[f] = True
+            compete &= keep.reshape([-1 if a == axis else 1 for a in range(3)])
+    lowest = int(np.flatnonzero(compete.reshape(-1))[0])                                       # the pinned index or 0 per condition
+    units = n // m
+    head = np.arange(units) * m                                                                # a unit's first frame
+    ws = tb.slot_window(head // G % K)
+    scores = np.where(compete.reshape(-1), 0.0, -np.inf)[None, :].repeat(units, axis=0)
+    if min(fixed) < 0:                                                                         # all three pinned: nothing is computed
+        for w in np.unique(ws[ws > 0]):
+            w = int(w)
+            sel = np.nonzero(ws == w)[0]
+            frames = head[sel][:, None] + np.arange(m)[None, :]                                # [u, m]
+            src = frames[:, :, None] - (tb.horizon + w - 1 - np.arange(w))[None, None, :] * G  # [u, m, w], oldest first
+            p = pilots[src].transpose(0, 1, 3, 2, 4).reshape(len(sel), m, Ps, w * Pt)
+            for d in range(n_ds):
+                if fixed[1] >= 0 and d != fixed[1]:
+                    continue
+                y1 = np.einsum("ik,umij->umkj", tb.u_f[d].conj(), p)
+                for e in range(n_dop):
+                    if fixed[2] >= 0 and e != fixed[2]:
+                        continue
+                    lam_t, u_t, _ = tb.time(e, w)
+                    energy = (np.abs(np.einsum("umkj,jl->umkl", y1, u_t)) ** 2).sum(axis=1)   # E [u, Ps, w Pt]: over members first
+                    v = (tb.lam_f[d][:, None] * lam_t[None, :])[None] + tb.sigma2[:, None, None]
+                    with np.errstate(invalid="ignore", over="ignore"):
+                        q = np.einsum("ukl,skl->us", energy, 1.0 / v)
+                        sc = -(m * tb.logdet(d, e, w)[None, :] + q)                           # [u, n_snr]
+                    for s in range(n_snr):
+                        if fixed[0] < 0 or s == fixed[0]:
+                            scores[sel, (s * n_ds + d) * n_dop + e] = sc[:, s]
+    ranked = np.where(np.isnan(scores), -np.inf, scores)
+    pick = ranked.argmax(axis=1)                                                               # the first of the highest: the lowest index
+    pick = np.where(np.isneginf(ranked.max(axis=1)), lowest, pick)
+    idx_u = np.stack([pick // (n_ds * n_dop), pick // n_dop % n_ds, pick % n_dop], axis=1).astype(np.int64)
+    idx = np.repeat(idx_u, m, axis=0)
+    values = np.stack([tb.values[name][idx[:, k]] for k, name in enumerate(CONDITIONS)], axis=1).astype(np.float32)
+    return (idx, values, scores) if return_scores else (idx, values)
+
+
 def lmmse_predicted_mse(cfg: Union[ChannelSimConfig, LmmseTables], snr_db: float, delay_spread_ns: float, doppler_hz: float,
                         assume=None, window: Optional[int] = None, horizon: Optional[int] = None, slot: Optional[int] = None) -> float:
     """The closed-form MSE per grid element of the estimator on frames drawn at the given condition (its nearest table values).
@@ -379,24 +490,41 @@ class LmmseEstimator(nn.Module):
     estimator, launch for launch): slot k of every sequence is estimated from the pilots of the last W slots up to slot k - h.  A batch
     must then hold WHOLE sequences in order (``B`` a multiple of ``slots * group``), as ``SynthLoader``, ``make_pack`` and an unshuffled
     ``ResidentLoader`` deliver them; the forward is one launch of ``aft_lmmse_seq_f32`` through the same pinned ring, and on the CPU
-    ``lmmse_seq_estimate_host``."""
+    ``lmmse_seq_estimate_host``.
 
-    def __init__(self, cfg: ChannelSimConfig, assume=None, window: int = 1, horizon: int = 0) -> None:
+    ``conditions="estimated"`` is the BLIND baseline (module docstring, "choosing the design point from the pilots"; the default
+    ``"meta"`` is the module above, launch for launch): the three condition entries of ``meta_data`` are ignored (it may be None) and the
+    design point is the maximum-likelihood one of the frame's own window, pooled over its group with ``pool=True``.  On a HIP device that
+    is two launches, ``aft_lmmse_classify_f32`` then the estimator, and the conditions never leave the device; ``assume`` pins conditions
+    for both.  A batch then holds whole groups (whole sequences with a window), as the classification needs them."""
+
+    def __init__(self, cfg: ChannelSimConfig, assume=None, window: int = 1, horizon: int = 0, conditions: str = "meta",
+                 pool: bool = True) -> None:
         super().__init__()
-        self.tables = LmmseTables(cfg, window, horizon)
+        if conditions not in ("meta", "estimated"):
+            raise ValueError(f'conditions = {conditions!r}: choose "meta" (the loader\'s conditions) or "estimated" (chosen from the pilots)')
+        self.conditions = conditions
+        self.chooser = ConditionEstimator(cfg, window, horizon, assume, pool) if conditions == "estimated" else None
+        self.tables = LmmseTables(cfg, window, horizon) if self.chooser is None else self.chooser.tables
         self.window, self.horizon = self.tables.window, self.tables.horizon
         self.cfg = cfg
         self.assume = _check_assume(assume)
         self.fixed = self.tables.fixed(self.assume)
         self.ofdm_size, self.pilot_size = tuple(cfg.ofdm), tuple(cfg.pilot)
-        image = self.tables.seq_image() if self.tables.multi_slot else self.tables.image()
-        self.register_buffer("table_image", torch.from_numpy(image), persistent=False)
+        if self.chooser is None:
+            image = torch.from_numpy(self.tables.seq_image() if self.tables.multi_slot else self.tables.image())
+        else:
+            image = self.chooser.table_image                         # the same image: ONE tensor serves both launches
+        self.register_buffer("table_image", image, persistent=False)
         self._plan = None
         self._stager = None
 
     def _apply(self, fn, *args, **kwargs):          # .to() / .cuda() re-allocate the buffer
         self._plan = None
-        return super()._apply(fn, *args, **kwargs)
+        out = super()._apply(fn, *args, **kwargs)
+        if self.chooser is not None:                # ... each module its own: keep the chooser's, drop the copy
+            self._buffers["table_image"] = self.chooser.table_image
+        return out
 
     def _hip_plan(self):
         img = self.table_image
@@ -425,7 +553,10 @@ class LmmseEstimator(nn.Module):
             raise ValueError(f"window = {self.window}, horizon = {self.horizon} need whole sequences in order: the batch of {B} frames "
                              f"is not a multiple of slots * group = {self.cfg.slots} * {self.cfg.group} = {unit}")
         conds = None
-        if meta_data is not None:
+        estimated = self.chooser is not None
+        if estimated:
+            _classify_units(self.tables, B, self.chooser.pool)
+        elif meta_data is not None:
             _, snr, ds, dop, _, _ = meta_data
             conds = [snr, ds, dop]
             if any(c.numel() != B for c in conds):
@@ -435,6 +566,8 @@ class LmmseEstimator(nn.Module):
         dev = self.table_image.device
         if dev.type != "cuda":
             cond = None if conds is None else np.stack([c.detach().cpu().reshape(-1).double().numpy() for c in conds], axis=1)
+            if estimated:
+                cond = lmmse_classify_host(self.tables, pilot_symbols.detach().cpu().numpy(), self.assume, self.chooser.pool)[1]
             host = lmmse_seq_estimate_host if self.tables.multi_slot else lmmse_estimate_host
             est = host(self.tables, pilot_symbols.detach().cpu().numpy(), cond, self.assume)
             return torch.from_numpy(est.astype(np.complex64))
@@ -459,9 +592,124 @@ class LmmseEstimator(nn.Module):
     def _launch(self, plan, pilots, conds):
         if torch.cuda.current_device() != plan.device.index:       # the launch belongs to the estimator's device, whichever is current
             with torch.cuda.device(plan.device):
-                return plan(pilots, *(conds or (None, None, None)))
+                return self._launch(plan, pilots, conds)
+        if self.chooser is not None and min(self.fixed) < 0:        # classify, then estimate: the same pilots, where they are
+            conds = self.chooser.hip_plan()(pilots)[1:4]
         return plan(pilots, *(conds or (None, None, None)))
 
     def get_model_info(self) -> dict:
         return {"model_name": self.__class__.__name__, "ofdm_size": self.ofdm_size, "pilot_size": self.pilot_size,
-                "assume": dict(self.assume), "window": self.window, "horizon": self.horizon, "device": str(self.table_image.device), "total_parameters": 0, "trainable_parameters": 0}
+                "assume": dict(self.assume), "window": self.window, "horizon": self.horizon, "conditions": self.conditions, "device": str(self.table_image.device), "total_parameters": 0, "trainable_parameters": 0}
+
+
+class ConditionEstimator(nn.Module):
+    """The design point from the pilots as a module (module docstring, "choosing the design point from the pilots"):
+    ``forward(pilot_symbols)`` with complex64 ``[B, Ps, Pt]`` -> ``(snr, ds, dop)``, float32 ``[B]`` each, the table values of the
+    maximum-likelihood candidate of every frame's window (``window`` / ``horizon`` as ``LmmseEstimator``'s; ``pool``: a group decides
+    together); ``classify(pilot_symbols, scores=False)`` also returns the indices, ``(idx [B, 3], snr, ds, dop[, scores])``.  No
+    parameters; the two float32 tables are non-persistent buffers.  On a HIP device a forward is ONE launch of
+    ``aft_lmmse_classify_f32`` on the current stream (``hip_ops.LmmseClassifyPlan``), CPU pilots going through the pinned ring of
+    ``LmmseEstimator``: nothing is copied, read back or synchronised, and idx is int32.  On the CPU it is ``lmmse_classify_host``
+    (idx int64).  A batch holds whole groups when pooling, whole sequences with a window."""
+
+    def __init__(self, cfg: ChannelSimConfig, window: int = 1, horizon: int = 0, assume=None, pool: bool = True) -> None:
+        super().__init__()
+        if not isinstance(pool, (bool, np.bool_)):
+            raise ValueError(f"pool must be True (a group decides together) or False (every frame alone); got {pool!r}")
+        self.tables = LmmseTables(cfg, window, horizon)
+        self.cfg, self.window, self.horizon, self.pool = cfg, self.tables.window, self.tables.horizon, bool(pool)
+        self.assume = _check_assume(assume)
+        self.fixed = self.tables.fixed(self.assume)
+        self.pilot_size = tuple(cfg.pilot)
+        image = self.tables.seq_image() if self.tables.multi_slot else self.tables.image()
+        self.register_buffer("table_image", torch.from_numpy(image), persistent=False)
+        self.register_buffer("logdet_image", torch.from_numpy(self.tables.classify_image()), persistent=False)
+        self._plan = None
+        self._stager = None
+
+    def _apply(self, fn, *args, **kwargs):          # .to() / .cuda() re-allocate the buffers
+        self._plan = None
+        return super()._apply(fn, *args, **kwargs)
+
+    def hip_plan(self):
+        img, ld = self.table_image, self.logdet_image
+        if img.dtype != torch.float32 or ld.dtype != torch.float32:
+            raise ValueError(f"the classification tables must stay float32 on the HIP device (they are {img.dtype}, {ld.dtype})")
+        if self._plan is None or self._plan.image.data_ptr() != img.data_ptr() or self._plan.logdet.data_ptr() != ld.data_ptr():
+            from .hip_ops import LmmseClassifyPlan       # loads the extension: a missing .so raises here, loudly
+            self._plan = LmmseClassifyPlan(self.tables, img.device, assume=self.assume, pool=self.pool, image=img, logdet=ld)
+        return self._plan
+
+    def classify(self, pilot_symbols: torch.Tensor, scores: bool = False):
+        if pilot_symbols.dim() != 3 or tuple(pilot_symbols.shape[1:]) != self.pilot_size:
+            raise ValueError(f"Expected pilot shape (B, {self.pilot_size[0]}, {self.pilot_size[1]}), got {tuple(pilot_symbols.shape)}")
+        if pilot_symbols.dtype != torch.complex64:
+            raise ValueError(f"pilot_symbols must be complex64, got {pilot_symbols.dtype}")
+        B = pilot_symbols.shape[0]
+        _, _, m = _classify_units(self.tables, B, self.pool)
+        dev = self.table_image.device
+        if dev.type != "cuda":
+            out = lmmse_classify_host(self.tables, pilot_symbols.detach().cpu().numpy(), self.assume, self.pool, return_scores=scores)
+            res = (torch.from_numpy(out[0]), *(torch.from_numpy(np.ascontiguousarray(out[1][:, k])) for k in range(3)))
+            return res + (torch.from_numpy(out[2]),) if scores else res
+        if B == 0:
+            res = (torch.empty((0, 3), dtype=torch.int32, device=dev), *(torch.empty(0, dtype=torch.float32, device=dev) for _ in range(3)))
+            return res + (torch.empty((0, self.logdet_image.numel() // self.window), dtype=torch.float32, device=dev),) if scores else res
+        plan = self.hip_plan()
+        if pilot_symbols.device.type != "cpu":
+            return self._launch(plan, pilot_symbols.to(dev), scores)
+        from .estimators import _InputStager
+        if self._stager is None or self._stager.device != dev:
+            self._stager = _InputStager(dev)
+        slot, _, pil_h, _ = self._stager.fill(pilot_symbols, None)
+        try:
+            return self._launch(plan, pil_h, scores)
+        finally:
+            self._stager.release(slot)
+
+    def _launch(self, plan, pilots, scores):
+        if torch.cuda.current_device() != plan.device.index:       # the launch belongs to the module's device, whichever is current
+            with torch.cuda.device(plan.device):
+                return plan(pilots, scores=scores)
+        return plan(pilots, scores=scores)
+
+    def forward(self, pilot_symbols: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        return tuple(self.classify(pilot_symbols)[1:4])
+
+    def get_model_info(self) -> dict:
+        return {"model_name": self.__class__.__name__, "pilot_size": self.pilot_size, "assume": dict(self.assume), "window": self.window,
+                "horizon": self.horizon, "pool": self.pool, "device": str(self.table_image.device), "total_parameters": 0,
+                "trainable_parameters": 0}
+
+
+class EstimatedConditions(nn.Module):
+    """Any estimator with the reference's ``forward(pilot_symbols, meta_data)`` signature (``estimators.AdaFortiTranEstimator``,
+    ``LmmseEstimator``), fed ESTIMATED conditions: the ``snr / ds / dop`` entries of the six-tuple ``(file_no, snr, ds, dop, n, types)``
+    are replaced by ``ConditionEstimator(cfg, window, horizon, assume, pool)``'s, in the shape of the entries they replace (``[B, 1]``
+    where ``meta_data`` is None, and the other four entries are then None); everything else passes through.  The estimated
+    conditions stay on the chooser's device: on a HIP device nothing is read back.  ``evaluation.get_test_stats`` measures the wrapper
+    like any estimator, which is how a blind AdaFortiTran is compared with a genie-aided one."""
+
+    def __init__(self, model: nn.Module, cfg: ChannelSimConfig, window: int = 1, horizon: int = 0, assume=None, pool: bool = True) -> None:
+        super().__init__()
+        if not isinstance(model, nn.Module):
+            raise ValueError(f"EstimatedConditions wraps an nn.Module with forward(pilot_symbols, meta_data); got {type(model).__name__}")
+        self.model = model
+        self.chooser = ConditionEstimator(cfg, window, horizon, assume, pool)
+
+    def substitute(self, pilot_symbols: torch.Tensor, meta_data: Optional[tuple]) -> tuple:
+        """The six-tuple the wrapped model sees."""
+        est = self.chooser(pilot_symbols)
+        if meta_data is None:
+            return (None, *(c.reshape(-1, 1) for c in est), None, None)
+        file_no, snr, ds, dop, n, types = meta_data
+        shaped = [c.reshape(old.shape) if torch.is_tensor(old) and old.numel() == c.numel() else c.reshape(-1, 1)
+                  for c, old in zip(est, (snr, ds, dop))]
+        return (file_no, *shaped, n, types)
+
+    def forward(self, pilot_symbols: torch.Tensor, meta_data: Optional[tuple] = None) -> torch.Tensor:
+        return self.model(pilot_symbols, self.substitute(pilot_symbols, meta_data))
+
+    def get_model_info(self) -> dict:
+        inner = self.model.get_model_info() if hasattr(self.model, "get_model_info") else {"model_name": type(self.model).__name__}
+        return {**inner, "model_name": f"EstimatedConditions({inner.get('model_name')})", "conditions": self.chooser.get_model_info()}

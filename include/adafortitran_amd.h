@@ -421,6 +421,33 @@ size_t aft_lmmse_seq_table_floats(const aft_lmmse *plan, int window);
 int aft_lmmse_seq_f32(const aft_lmmse *plan, int group, int slots, int window, int horizon, const float *tables, const float *pilots,
                       const float *snr, const float *ds, const float *dop, float *est, int batch, void *stream);
 
+/* Choosing the design point from the pilots (lmmse.py "choosing the design point from the pilots"): a maximum-likelihood classification
+ * of a window's pilots over the table's candidates c = (s, d, e) = (i_snr, i_ds, i_dop), in the estimator's own eigenbasis.  The batch is
+ * whole sequences as for aft_lmmse_seq_f32, and target frame (seq, k, a) looks at exactly the window that call estimates it from:
+ * w = min(window, k - horizon + 1) slots ending at slot k - horizon, P_a [Ps, w Pt].  A UNIT is the `group` frames of one slot when
+ * pool = 1 (the simulator defines a group's conditions as shared; m = group members), one frame when pool = 0 (m = 1):
+ *   Z_a = U_f[d]^H P_a U_t^(w)[e],   E_kl = sum over the unit's members of |Z_a,kl|^2,   V_kl = lf[d]_k lt^(w)[e]_l + noise_var[s],
+ *   score(c) = -( m logdet[d][e][w][s] + sum_kl E_kl / V_kl ),
+ * the Gaussian log-likelihood of the window under candidate c.  `tables` is aft_lmmse_seq_f32's image for `window` (with slots = 1,
+ * window = 1 that is aft_lmmse_f32's image); `logdet` is float32 [n_ds][n_dop][window][n_snr] = sum_kl log V_kl, computed by the host
+ * in double (the device takes no logarithm); aft_lmmse_classify_table_floats gives its length.  The highest score wins, ties go to the
+ * lowest flat index (s n_ds + d) n_dop + e, a NaN score never wins, and with every score NaN the choice is index 0: a total function.
+ * fixed_* >= 0 pins a condition: only candidates with that index compete, the others' scores are -inf; with all three pinned, or with
+ * no slot to look at (k < horizon), nothing is read, the choice is the pinned index or 0 and the competing scores are +0.
+ * Outputs, per FRAME (every member of a unit gets the unit's choice): idx int32 [batch, 3] and the table values snr / ds / dop
+ * float32 [batch], the form aft_lmmse_seq_f32 takes them in; scores, when not NULL, float32 [units, n_snr n_ds n_dop] in flat index order,
+ * units = batch / group when pool = 1, batch otherwise.  A unit's bits depend on its window's pilots only. */
+size_t aft_lmmse_classify_table_floats(const aft_lmmse *plan, int window);
+
+/* One launch, one workgroup per unit, no atomics, nothing synchronised, every output element written.  pilots may be any
+ * device-addressable memory, pinned host memory included; tables, logdet and the outputs are device memory.  Static LDS: 40 KB,
+ * 24 KB when window * pilot_symbols <= 16 (the same body: the bits do not depend on it).
+ * Nothing is launched on AFT_ERR_ARG (a NULL plan / tables / logdet / pilots / idx / snr / ds / dop; tables or pilots not 8-byte, another
+ * array not 4-byte aligned; batch < 1 or not a multiple of slots * group; pool not 0 or 1) and AFT_ERR_SHAPE (aft_lmmse_seq_f32's). */
+int aft_lmmse_classify_f32(const aft_lmmse *plan, int group, int slots, int window, int horizon, int pool, const float *tables,
+                           const float *logdet, const float *pilots, int32_t *idx, float *snr, float *ds, float *dop, float *scores,
+                           int batch, void *stream);
+
 /* ---- link-level bit errors (adafortitran_amd/linksim.py holds the definition) ----
  *
  * What a channel estimate is for: data symbols go through the TRUE channel H plus noise, a one-tap equaliser uses the ESTIMATE E, a hard
