@@ -11,10 +11,14 @@ Package contents (only what the hot path needs):
   metrics        channel-MSE metric (device reduction + RCCL all-gather)
   lmmse          the LMMSE (Wiener) baseline of the channel simulator, one slot or a window of slots: definition, closed-form MSE, nn.Module;
                  its design point chosen from the pilots (ConditionEstimator, EstimatedConditions)
+                 and the full-grid smoother a decision-directed receiver re-estimates with (lmmse_grid_host)
+  linksim        the link the estimates are measured on (bit errors, rates, coded blocks) and DataAidedRefiner, the receiver loop that
+                 refines an estimate from its own decisions
 """
 from .config import ModelConfig, SystemConfig, load_config  # noqa: F401
 from .estimators import (AdaFortiTranEstimator, BaseFortiTranEstimator, FortiTranEstimator,  # noqa: F401
                          LinearEstimator)
-from .lmmse import ConditionEstimator, EstimatedConditions, LmmseEstimator, lmmse_classify_host  # noqa: F401
+from .linksim import DataAidedRefiner  # noqa: F401
+from .lmmse import ConditionEstimator, EstimatedConditions, LmmseEstimator, lmmse_classify_host, lmmse_grid_host  # noqa: F401
 
 __version__ = "0.1.0"

@@ -68,6 +68,7 @@ AFT_LINK_MAX_BRANCHES = 8
 AFT_LINK_MAX_STREAMS = 2
 AFT_LINK_PAIR_TIME, AFT_LINK_PAIR_FREQUENCY = 0, 1
 AFT_LINK_MAX_SUBBANDS = 1024
+AFT_LINK_OBSERVE_DECIDED, AFT_LINK_OBSERVE_SENT = 0, 1
 AFT_LINK_HARQ_MAX_ROUNDS, AFT_LINK_HARQ_COUNTS = 4, 7
 
 
@@ -225,6 +226,7 @@ SIGNATURES = {
     "aft_lmmse_f32": (C.c_int, [C.POINTER(AftLmmse), vp, vp, vp, vp, vp, vp, C.c_int, vp]),
     "aft_lmmse_seq_table_floats": (C.c_size_t, [C.POINTER(AftLmmse), C.c_int]),
     "aft_lmmse_seq_f32": (C.c_int, [C.POINTER(AftLmmse)] + [C.c_int] * 4 + [vp, vp, vp, vp, vp, vp, C.c_int, vp]),
+    "aft_lmmse_grid_f32": (C.c_int, [C.POINTER(AftLmmse), C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp]),
     "aft_lmmse_classify_table_floats": (C.c_size_t, [C.POINTER(AftLmmse), C.c_int]),
     "aft_lmmse_classify_f32": (C.c_int, [C.POINTER(AftLmmse)] + [C.c_int] * 5 + [vp] * 8 + [C.c_int, vp]),
     "aft_link_errors_f32": (C.c_int, [C.POINTER(AftLink), vp, vp, vp, vp, vp, C.c_int, vp]),
@@ -247,6 +249,7 @@ SIGNATURES = {
                                       C.c_int, vp]),
     "aft_link_ldpc_masked_f32": (C.c_int, [C.POINTER(AftLink), vp, vp, C.c_int, C.c_int, vp, C.c_ulonglong, C.c_ulonglong, C.c_float, C.c_int,
                                            C.c_int, vp, C.c_int, vp, vp, C.c_int, vp]),
+    "aft_link_observe_f32": (C.c_int, [C.POINTER(AftLink), vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]),
     # training path
     "aft_encoder_tape_bytes": (C.c_size_t, [cfgp, C.c_int]),
     "aft_encoder_train_scratch_bytes": (C.c_size_t, [cfgp, C.c_int]),

@@ -16,7 +16,7 @@ from concurrent.futures import ThreadPoolExecutor
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 SOURCES = ("aft_api.hip", "aft_frames.hip", "aft_train.hip", "aft_stamps.hip", "k_chain.hip", "k_attn.hip", "k_layer.hip", "k_conv.hip", "k_conv_stream.hip", "k_conv_rows.hip", "k_misc.hip", "k_gemm.hip",
            "k_attn_train.hip", "k_train.hip", "k_conv_train.hip", "k_chain_bwd.hip", "k_ends_train.hip", "k_chansim.hip", "k_lmmse.hip", "k_lmmse_classify.hip", "k_link.hip","k_linkcode.hip", "k_linkldpc.hip", "k_linkharq.hip", "k_linksm.hip",
-           "k_linkalamouti.hip", "k_linkprecode.hip")
+           "k_linkalamouti.hip", "k_linkprecode.hip", "k_linkobserve.hip")
 LIB = os.path.join(CSRC, "libaft_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]

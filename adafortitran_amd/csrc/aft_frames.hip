@@ -336,6 +336,28 @@ int aft_lmmse_seq_f32(const aft_lmmse *plan, int group, int slots, int window, i
     return e == hipSuccess ? AFT_OK : hip_fail("lmmse_seq", e);
 }
 
+int aft_lmmse_grid_f32(const aft_lmmse *plan, int kf, const float *tables, const float *z, const float *snr, const float *ds,
+                       const float *dop, float *est, int batch, void *stream) {
+    const char *who = "lmmse grid";
+    AFT_REQUIRE(plan && tables && z && est, "lmmse grid: NULL pointer argument");
+    AFT_REQUIRE(aligned(8, tables, z, est), "lmmse grid: tables, z and est must be 8-byte aligned");
+    AFT_REQUIRE(aligned(4, snr, ds, dop), "lmmse grid: the condition arrays must be 4-byte aligned");
+    AFT_REQUIRE(batch >= 1, "lmmse grid: batch must be at least 1 (got %d)", batch);
+    const int rc = check_lmmse(plan);
+    if (rc != AFT_OK) return rc;
+    if (plan->num_symbols > AFT_LMMSE_MAX_WINDOW_PILOTS) {
+        set_error("lmmse grid: num_symbols = %d: the full-grid smoother filters all T symbols of a frame at once and holds at most "
+                  "AFT_LMMSE_MAX_WINDOW_PILOTS = %d of them", plan->num_symbols, AFT_LMMSE_MAX_WINDOW_PILOTS);
+        return AFT_ERR_SHAPE;
+    }
+    if (!within(who, "kf", kf, 1, plan->num_scs < AFT_CHANSIM_MAX_TAPS ? plan->num_scs : AFT_CHANSIM_MAX_TAPS)) return AFT_ERR_SHAPE;
+    AFT_REQUIRE((snr || plan->fixed_snr >= 0) && (ds || plan->fixed_ds >= 0) && (dop || plan->fixed_dop >= 0),
+                "lmmse grid: NULL condition array whose fixed_* index is -1 (snr %p / %d, ds %p / %d, dop %p / %d)", (const void *)snr,
+                plan->fixed_snr, (const void *)ds, plan->fixed_ds, (const void *)dop, plan->fixed_dop);
+    hipError_t e = launch_lmmse_grid(*plan, kf, tables, z, snr, ds, dop, est, batch, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? AFT_OK : hip_fail("lmmse_grid", e);
+}
+
 size_t aft_lmmse_classify_table_floats(const aft_lmmse *plan, int window) {
     if (plan == nullptr || check_lmmse(plan) != AFT_OK ||
         check_lmmse_seq(plan, 1, AFT_CHANSIM_MAX_SLOTS, window, 0, "lmmse classify") != AFT_OK)
@@ -461,6 +483,21 @@ int aft_link_mrc_f32(const aft_link *link, const float *ideal, const float *est,
     hipError_t e = launch_link_mrc(*link, ideal, est, keys, sigma, rho, scale, factors, n_factors, branches, counts, loss, llr, batch,
                                    static_cast<hipStream_t>(stream));
     return e == hipSuccess ? AFT_OK : hip_fail("link_mrc", e);
+}
+
+int aft_link_observe_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys,
+                         const float *sigma, const float *rho, const float *pilots, int source, int branches, float *z,
+                         unsigned char *decisions, int32_t *symbol_errors, int batch, void *stream) {
+    const int rc = check_front("link observe", link, ideal, est, keys, {sigma, rho, symbol_errors}, "sigma, rho and symbol_errors", nullptr,
+                               batch, 1, branches);
+    if (rc != AFT_OK) return rc;
+    AFT_REQUIRE(pilots && z && decisions, "link observe: NULL pointer argument");
+    AFT_REQUIRE(aligned(8, pilots, z), "link observe: pilots and z must be 8-byte aligned");
+    AFT_REQUIRE(source == AFT_LINK_OBSERVE_DECIDED || source == AFT_LINK_OBSERVE_SENT,
+                "link observe: source = %d is neither AFT_LINK_OBSERVE_DECIDED nor AFT_LINK_OBSERVE_SENT", source);
+    hipError_t e = launch_link_observe(*link, ideal, est, keys, sigma, rho, pilots, source, branches, z, decisions, symbol_errors, batch,
+                                       static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? AFT_OK : hip_fail("link_observe", e);
 }
 
 int aft_link_harq_f32(const aft_link *link, const float *llr, const unsigned long long *keys, int base_rows, int base_cols,

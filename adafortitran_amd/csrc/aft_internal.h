@@ -388,6 +388,12 @@ size_t lmmse_seq_tblock_floats(const aft_lmmse &plan, int window);
 hipError_t launch_lmmse_seq(const aft_lmmse &plan, int group, int slots, int window, int horizon, const float *tables,
                             const float *pilots, const float *snr, const float *ds, const float *dop, float *est, int batch,
                             hipStream_t st);
+// ... and the full-grid smoother (k_lmmse.hip): everything has passed aft_lmmse_grid_f32's checks; the two sizes are the
+// per-delay-spread and per-Doppler blocks of the grid image for `kf` eigen-directions along frequency
+size_t lmmse_grid_gblock_floats(const aft_lmmse &plan, int kf);
+size_t lmmse_grid_tblock_floats(const aft_lmmse &plan);
+hipError_t launch_lmmse_grid(const aft_lmmse &plan, int kf, const float *tables, const float *z, const float *snr, const float *ds,
+                             const float *dop, float *est, int batch, hipStream_t st);
 // the design point from the pilots (k_lmmse_classify.hip): everything has passed aft_lmmse_classify_f32's checks; scores may be NULL
 size_t lmmse_classify_table_floats(const aft_lmmse &plan, int window);
 hipError_t launch_lmmse_classify(const aft_lmmse &plan, int group, int slots, int window, int horizon, int pool, const float *tables,
@@ -405,6 +411,11 @@ hipError_t launch_link_soft(const aft_link &link, const float *ideal, const floa
 hipError_t launch_link_mrc(const aft_link &link, const float *ideal, const float *est, const unsigned long long *keys,
                            const float *sigma, const float *rho, const float *scale, const float *factors, int n_factors, int branches,
                            int32_t *counts, float *loss, float *llr, int batch, hipStream_t st);
+// the decision-directed observation on the same link (k_linkobserve.hip): everything has passed aft_link_observe_f32's checks; one
+// workgroup per group of `branches` frames, batch a multiple of it
+hipError_t launch_link_observe(const aft_link &link, const float *ideal, const float *est, const unsigned long long *keys,
+                               const float *sigma, const float *rho, const float *pilots, int source, int branches, float *z,
+                               unsigned char *decisions, int32_t *symbol_errors, int batch, hipStream_t st);
 // the coded link's Viterbi decoder (k_linkcode.hip): everything has passed aft_link_decode_f32's checks; coded_bits = n and blocks = B
 // of the definition; bits may be NULL.  link_code_waves: the code blocks a workgroup decodes at once (its survivor words fill LDS)
 int link_code_waves(unsigned steps, unsigned blocks);

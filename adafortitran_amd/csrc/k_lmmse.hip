@@ -21,6 +21,10 @@
 // step 4 over zero terms: +0 everywhere through the same stores, nothing read.  LDS: two [64][32] complex tiles and the time tile,
 // 40 KB, static; a second instantiation with [64][16] tiles (24 KB, this file's other kernel's) takes the windows that fit it.
 //
+// The full-grid smoother (lmmse_grid_kernel, aft_lmmse_grid_f32) is the same estimator with every grid position an observation: its own
+// first product, S-deep, is described where it stands below; from Y1 on it runs lmmse_tail, the code of steps 3 and 4 of the two
+// kernels above, with (Ps, Pt) = (Kf, T).
+//
 // No atomics, every output element written exactly once.  The rounding behind tests/test_lmmse_gpu.py's bound: every product stage is a
 // chain of fused multiply-adds in sequence, the table entries are float32 roundings of the host's double tables.
 #include "frame_device.h"
@@ -66,7 +70,65 @@ __device__ __forceinline__ int nearest(const float *value, int n, float v) {
     return best;
 }
 
-// The body of both kernels.  pc: the pilots, then C = D o Y; y1: U_f^H P (both [Ps][Pw], Pw <= Args::kMaxPw); v: C T'^T, one time tile.
+// Steps 3 (from Y1 on) and 4, shared by every kernel of this file: y1 is [K][Pt] in LDS and the caller has synchronised after writing
+// it; C = D o (Y1 U_t) goes to pc, then per time tile V = C T'^T to v and est = F' V to the frame's plane at `est`.  K eigen-directions
+// along frequency (lf [K], fp [K][S] k-major), Pt along time (ut [Pt][Pt], tp [Pt][T] l-major, lt [Pt]); Pk = K, or 0 for a frame with
+// nothing to look at (the last product then runs over zero terms).
+__device__ __forceinline__ void lmmse_tail(int tid, int S, int T, int K, int Pt, int Pk, const float *ut, const float *tp, const float *lt,
+                                           const float *lf, const float2 *fp, float sigma2, float2 *pc, const float2 *y1,
+                                           float2 (*v)[kFrameTile], float2 *est, int wide) {
+    for (int i = tid; i < K * Pt; i += kFrameThreads) {                             // C[k][l] = D[k][l] sum_j y1[k][j] U_t[j][l]
+        const int k = i / Pt, l = i - k * Pt;
+        float re = 0.f, im = 0.f;
+        for (int j = 0; j < Pt; ++j) {
+            AFT_DEV_ASSERT(k * Pt + j < K * Pt && j * Pt + l < Pt * Pt);
+            const float2 y = y1[k * Pt + j];
+            const float u = ut[j * Pt + l];
+            re = fmaf(y.x, u, re);
+            im = fmaf(y.y, u, im);
+        }
+        const float d = 1.f / fmaf(lf[k], lt[l], sigma2);
+        pc[i] = make_float2(d * re, d * im);
+    }
+    __syncthreads();
+
+    for (int t0 = 0; t0 < T; t0 += kFrameTile) {
+        if (t0 != 0) __syncthreads();                                   // the previous tile's readers are done with `v`
+        for (int i = tid; i < K * kFrameTile; i += kFrameThreads) {     // v[k][tt] = sum_l C[k][l] T'[t0 + tt][l]
+            const int k = i / kFrameTile, tt = i - k * kFrameTile, t = t0 + tt;
+            float re = 0.f, im = 0.f;
+            if (t < T)
+                for (int l = 0; l < Pt; ++l) {
+                    AFT_DEV_ASSERT(k < K && (size_t)l * T + t < (size_t)Pt * T);
+                    const float2 z = pc[k * Pt + l];
+                    const float w = tp[(size_t)l * T + t];
+                    re = fmaf(z.x, w, re);
+                    im = fmaf(z.y, w, im);
+                }
+            v[k][tt] = make_float2(re, im);
+        }
+        __syncthreads();
+
+        const int groups = (min(T - t0, kFrameTile) + kFrameCols - 1) / kFrameCols;
+        for (int i = tid; i < S * groups; i += kFrameThreads) {
+            const int hg = i / S, s = i - hg * S, col = kFrameCols * hg;
+            float2 acc[kFrameCols];
+#pragma unroll
+            for (int j = 0; j < kFrameCols; ++j) acc[j] = make_float2(0.f, 0.f);
+            for (int k = 0; k < Pk; ++k) {
+                AFT_DEV_ASSERT(s < S && col + kFrameCols <= kFrameTile);
+                const float2 f = fp[(size_t)k * S + s];
+#pragma unroll
+                for (int j = 0; j < kFrameCols; ++j) cfma(acc[j], f, v[k][col + j]);
+            }
+            const int n = min(kFrameCols, T - t0 - col);                // valid columns; even when T is
+            AFT_DEV_ASSERT(s < S && t0 + col + n <= T);
+            store_row_piece(est + (size_t)s * (size_t)T + t0 + col, acc, n, wide);
+        }
+    }
+}
+
+// The body of both pilot kernels.  pc: the pilots, then C = D o Y; y1: U_f^H P (both [Ps][Pw], Pw <= Args::kMaxPw); v: C T'^T, one time tile.
 template <class Args>
 __device__ __forceinline__ void lmmse_body(const Args &a, float2 *pc, float2 *y1, float2 (*v)[kFrameTile]) {
     const aft_lmmse &c = a.c;
@@ -123,55 +185,7 @@ __device__ __forceinline__ void lmmse_body(const Args &a, float2 *pc, float2 *y1
         y1[i] = make_float2(re, im);
     }
     __syncthreads();                                                                // the pilots have been read: pc is free for C
-    for (int i = tid; i < Ps * Pt; i += kFrameThreads) {                            // C[k][l] = D[k][l] sum_j y1[k][j] U_t[j][l]
-        const int k = i / Pt, l = i - k * Pt;
-        float re = 0.f, im = 0.f;
-        for (int j = 0; j < Pt; ++j) {
-            AFT_DEV_ASSERT(k * Pt + j < Ps * Pt && j * Pt + l < Pt * Pt);
-            const float2 y = y1[k * Pt + j];
-            const float u = ut[j * Pt + l];
-            re = fmaf(y.x, u, re);
-            im = fmaf(y.y, u, im);
-        }
-        const float d = 1.f / fmaf(lf[k], lt[l], sigma2);
-        pc[i] = make_float2(d * re, d * im);
-    }
-    __syncthreads();
-
-    for (int t0 = 0; t0 < T; t0 += kFrameTile) {
-        if (t0 != 0) __syncthreads();                                   // the previous tile's readers are done with `v`
-        for (int i = tid; i < Ps * kFrameTile; i += kFrameThreads) {    // v[k][tt] = sum_l C[k][l] T'[t0 + tt][l]
-            const int k = i / kFrameTile, tt = i - k * kFrameTile, t = t0 + tt;
-            float re = 0.f, im = 0.f;
-            if (t < T)
-                for (int l = 0; l < Pt; ++l) {
-                    AFT_DEV_ASSERT(k < Ps && (size_t)l * T + t < (size_t)Pt * T);
-                    const float2 z = pc[k * Pt + l];
-                    const float w = tp[(size_t)l * T + t];
-                    re = fmaf(z.x, w, re);
-                    im = fmaf(z.y, w, im);
-                }
-            v[k][tt] = make_float2(re, im);
-        }
-        __syncthreads();
-
-        const int groups = (min(T - t0, kFrameTile) + kFrameCols - 1) / kFrameCols;
-        for (int i = tid; i < S * groups; i += kFrameThreads) {
-            const int hg = i / S, s = i - hg * S, col = kFrameCols * hg;
-            float2 acc[kFrameCols];
-#pragma unroll
-            for (int j = 0; j < kFrameCols; ++j) acc[j] = make_float2(0.f, 0.f);
-            for (int k = 0; k < Pk; ++k) {
-                AFT_DEV_ASSERT(s < S && col + kFrameCols <= kFrameTile);
-                const float2 f = fp[(size_t)k * S + s];
-#pragma unroll
-                for (int j = 0; j < kFrameCols; ++j) cfma(acc[j], f, v[k][col + j]);
-            }
-            const int n = min(kFrameCols, T - t0 - col);                // valid columns; even when T is
-            AFT_DEV_ASSERT(s < S && t0 + col + n <= T);
-            store_row_piece(a.est + (b * S + s) * (size_t)T + t0 + col, acc, n, a.wide);
-        }
-    }
+    lmmse_tail(tid, S, T, Ps, Pt, Pk, ut, tp, lt, lf, fp, sigma2, pc, y1, v, a.est + b * (size_t)S * (size_t)T, a.wide);
 }
 
 __global__ __launch_bounds__(kFrameThreads) void lmmse_kernel(const LmmseArgs a) {
@@ -191,7 +205,115 @@ __global__ __launch_bounds__(kFrameThreads) void lmmse_seq_kernel(const LmmseSeq
     lmmse_body(a, pc, y1, v);
 }
 
+// ---- the full-grid smoother (aft_lmmse_grid_f32; lmmse.py "the full-grid smoother"): every grid position is an observation ----
+//
+// est = F_g [ D o (U_g^H Z U_tg) ] T_g^T with Z the frame's [S, T] observations.  The new work is the first product, Y1 = U_g^H Z,
+// [Kf, T] from an S-deep sum; from Y1 on it is lmmse_tail with (K, Pt) = (Kf, T), Kf <= 32 and T <= 32.
+//   * Z is read once, straight through: rows s0 .. s0 + 32 of the row-major plane are ONE contiguous run of 32 T values, so a chunk goes
+//     to LDS by consecutive lanes on consecutive 8-byte addresses (whole cache lines, whatever T is); the time tiles of frame_device.h
+//     would cut every row into 128-byte pieces instead, and are kept for the stores, whose rows a thread owns.
+//   * U_g^H is stored s-major, [S(s)][Kf(k)], so the same 32 rows of it are one contiguous run too and stage the same way; every
+//     frame of a delay spread reads the same table, which therefore stays in L2 while Z streams from memory.
+//   * a thread owns up to four of the Kf T <= 1024 outputs (i = tid + 256 n, k = i / T, j = i % T) and keeps them in registers over the
+//     chunks: per term one LDS read of U_g^H[s][k] (the lanes of a wave share k for T lanes in a row: a broadcast) and one of Z[s][j]
+//     (consecutive lanes, consecutive addresses), four fused multiply-adds, in increasing s from +0 -- the chain of lmmse_body's Y1.
+// Any S: LDS holds one chunk.  28 KB of static LDS.  No atomics, every output element written exactly once.
+constexpr int kGridMaxK = AFT_CHANSIM_MAX_TAPS, kGridMaxT = kLmMaxPw, kGridRows = 32, kGridOut = kGridMaxK * kGridMaxT / kFrameThreads;
+static_assert(kGridMaxK <= kLmMaxPs && kGridRows * kGridMaxT <= kGridMaxK * kGridMaxT, "a chunk of Z fits the tile that later holds C");
+
+struct LmmseGridArgs {
+    aft_lmmse c;
+    const float *tables;
+    const float2 *z;
+    const float *snr, *ds, *dop;
+    float2 *est;
+    unsigned long long gblock, tblock;      // floats per delay-spread block / per Doppler block of the grid image
+    int kf;                                 // eigen-directions kept along frequency
+    int wide;                               // 1: 16-byte stores into est
+};
+
+__global__ __launch_bounds__(kFrameThreads) void lmmse_grid_kernel(const LmmseGridArgs a) {
+    __shared__ float2 pc[kGridMaxK * kGridMaxT];                // a chunk of Z, [rows][T]; then C
+    __shared__ float2 y1[kGridMaxK * kGridMaxT];
+    __shared__ float2 uc[kGridRows * kGridMaxK];                // the chunk's rows of U_g^H, [rows][Kf]
+    __shared__ float2 v[kGridMaxK][kFrameTile];
+    const aft_lmmse &c = a.c;
+    const int tid = threadIdx.x;
+    const size_t b = blockIdx.x;
+    const int S = c.num_scs, T = c.num_symbols, Kf = a.kf;
+    AFT_DEV_ASSERT(Kf >= 1 && Kf <= kGridMaxK && Kf <= S && T >= 1 && T <= kGridMaxT);
+    const int i_snr = c.fixed_snr >= 0 ? c.fixed_snr : nearest(c.snr_db, c.n_snr, a.snr[b]);
+    const int i_ds = c.fixed_ds >= 0 ? c.fixed_ds : nearest(c.delay_spread_ns, c.n_ds, a.ds[b]);
+    const int i_dop = c.fixed_dop >= 0 ? c.fixed_dop : nearest(c.doppler_hz, c.n_dop, a.dop[b]);
+    AFT_DEV_ASSERT(i_snr >= 0 && i_snr < c.n_snr && i_ds >= 0 && i_ds < c.n_ds && i_dop >= 0 && i_dop < c.n_dop);
+    const float sigma2 = c.noise_var[i_snr];
+    const float *gb = a.tables + (size_t)i_ds * a.gblock, *tb = a.tables + (size_t)c.n_ds * a.gblock + (size_t)i_dop * a.tblock;
+    const float2 *ugh = reinterpret_cast<const float2 *>(gb);                       // [S(s)][Kf(k)]
+    const float2 *fp = ugh + (size_t)S * Kf;                                         // [Kf(k)][S]
+    const float *lf = gb + 4 * (size_t)S * Kf;                                       // [Kf]
+    const float *ut = tb, *tp = tb + T * T, *lt = tp + T * T;                        // [T(j)][T(l)], [T(l)][T], [T]
+    const float2 *zf = a.z + b * (size_t)S * (size_t)T;
+
+    const int outs = Kf * T;
+    int ko[kGridOut], jo[kGridOut];
+    float re[kGridOut], im[kGridOut];
+#pragma unroll
+    for (int n = 0; n < kGridOut; ++n) {
+        const int i = min(tid + n * kFrameThreads, outs - 1);                       // a thread without an n-th output repeats the last one
+        ko[n] = i / T;
+        jo[n] = i - ko[n] * T;
+        re[n] = im[n] = 0.f;
+    }
+    for (int s0 = 0; s0 < S; s0 += kGridRows) {
+        const int rows = min(kGridRows, S - s0);
+        if (s0 != 0) __syncthreads();                                               // the previous chunk's readers are done
+        for (int i = tid; i < rows * T; i += kFrameThreads) pc[i] = zf[(size_t)s0 * T + i];
+        for (int i = tid; i < rows * Kf; i += kFrameThreads) uc[i] = ugh[(size_t)s0 * Kf + i];
+        __syncthreads();
+#pragma unroll
+        for (int n = 0; n < kGridOut; ++n) {
+            if (tid + n * kFrameThreads >= outs) continue;
+            for (int q = 0; q < rows; ++q) {                                        // y1[k][j] += conj(U_g[s][k]) Z[s][j]
+                AFT_DEV_ASSERT(q * Kf + ko[n] < kGridRows * kGridMaxK && q * T + jo[n] < kGridMaxK * kGridMaxT);
+                const float2 u = uc[q * Kf + ko[n]], p = pc[q * T + jo[n]];
+                re[n] = fmaf(u.x, p.x, fmaf(-u.y, p.y, re[n]));
+                im[n] = fmaf(u.x, p.y, fmaf(u.y, p.x, im[n]));
+            }
+        }
+    }
+#pragma unroll
+    for (int n = 0; n < kGridOut; ++n)
+        if (tid + n * kFrameThreads < outs) y1[tid + n * kFrameThreads] = make_float2(re[n], im[n]);
+    __syncthreads();                                                                // the last chunk has been read: pc is free for C
+    lmmse_tail(tid, S, T, Kf, T, Kf, ut, tp, lt, lf, fp, sigma2, pc, y1, v, a.est + b * (size_t)S * (size_t)T, a.wide);
+}
+
 }  // namespace
+
+size_t lmmse_grid_gblock_floats(const aft_lmmse &p, int kf) {
+    return 4 * (size_t)p.num_scs * (size_t)kf + (size_t)kf + (size_t)(kf & 1);
+}
+
+size_t lmmse_grid_tblock_floats(const aft_lmmse &p) {
+    const size_t T = (size_t)p.num_symbols;
+    return 2 * T * T + T;
+}
+
+hipError_t launch_lmmse_grid(const aft_lmmse &plan, int kf, const float *tables, const float *z, const float *snr, const float *ds,
+                             const float *dop, float *est, int batch, hipStream_t st) {
+    LmmseGridArgs a{};
+    a.c = plan;
+    a.tables = tables;
+    a.z = reinterpret_cast<const float2 *>(z);
+    a.snr = snr; a.ds = ds; a.dop = dop;
+    a.est = reinterpret_cast<float2 *>(est);
+    a.gblock = lmmse_grid_gblock_floats(plan, kf);
+    a.tblock = lmmse_grid_tblock_floats(plan);
+    a.kf = kf;
+    a.wide = wide_ok(plan.num_symbols, est);
+    hipLaunchKernelGGL(lmmse_grid_kernel, dim3((unsigned)batch), dim3(kFrameThreads), 0, st, a);
+    return hipGetLastError();
+}
 
 size_t lmmse_fblock_floats(const aft_lmmse &p) {
     const size_t Ps = (size_t)p.pilot_scs;

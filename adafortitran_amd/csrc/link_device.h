@@ -7,7 +7,8 @@
 // of the successive-cancellation detector and the joint max-log demapper; and what transmit
 // diversity (k_linkalamouti.hip) adds: a line's k-th data element, the Alamouti combiner's step and the store of one element's LLRs;
 // and what closed-loop precoding (k_linkprecode.hip) adds: the exact product with a codebook entry, a subband's selection sum and its
-// decision, and the combiner's step on the effective estimate.
+// decision, and the combiner's step on the effective estimate; and what the decision-directed observation (k_linkobserve.hip) adds:
+// the received sample on its own (link_received, which link_branch is built on), one plane's pair load and a pilot's place in its list.
 // adafortitran_amd/linksim.py holds the definitions.
 #pragma once
 
@@ -64,6 +65,26 @@ __device__ __forceinline__ void link_load_pairs(const float2 *hq, const float2 *
     }
 }
 
+// the elements (q, q + 1) of ONE plane, by link_load_pairs' rules
+__device__ __forceinline__ LinkPair link_load_pair(const float2 *hq, int wide, bool two) {
+    if (wide) {
+        const f32x4 hv = *reinterpret_cast<const f32x4 *>(hq);
+        return LinkPair{make_float2(hv[0], hv[1]), make_float2(hv[2], hv[3])};
+    }
+    return LinkPair{hq[0], two ? hq[1] : make_float2(0.f, 0.f)};
+}
+
+// the index of v in sorted[0 .. n), or -1: link_listed's search, for a caller that needs the place as well
+__device__ __forceinline__ int link_position(const int *sorted, int n, int v) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (sorted[mid] < v) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < n && sorted[lo] == v ? lo : -1;
+}
+
 // level index of a Gray code of at most four bits: k ^ (k >> 1) = g
 __device__ __forceinline__ unsigned gray_level(unsigned g) {
     g ^= g >> 1;
@@ -100,13 +121,26 @@ struct LinkBranch {
     float cr, ci, p;
 };
 
-__device__ __forceinline__ LinkBranch link_branch(unsigned long long kf, float sigma, unsigned q, float xr, float xi, float2 h, float2 e) {
+// the branch's received sample alone, y = H x + noise: link_branch's own first step, for a caller that also needs y (k_linkobserve.hip)
+struct LinkReceived {
+    float yr, yi;
+};
+
+__device__ __forceinline__ LinkReceived link_received(unsigned long long kf, float sigma, unsigned q, float xr, float xi, float2 h) {
     const FrameNoise nz = frame_noise(kf, kStreamDataNoiseRadius, kStreamDataNoiseAngle, q, sigma);
-    const float yr = fmaf(nz.r, nz.c, fmaf(h.x, xr, -(h.y * xi)));
-    const float yi = fmaf(nz.r, nz.s, fmaf(h.x, xi, h.y * xr));
+    return LinkReceived{fmaf(nz.r, nz.c, fmaf(h.x, xr, -(h.y * xi))), fmaf(nz.r, nz.s, fmaf(h.x, xi, h.y * xr))};
+}
+
+// ... and the branch from a sample already formed: c = y conj(E), p = |E|^2, link_branch's second step
+__device__ __forceinline__ LinkBranch link_branch_of(const LinkReceived &y, float2 e) {
+    const float yr = y.yr, yi = y.yi;
     const float cr = fmaf(yr, e.x, yi * e.y);                   // y conj(E)
     const float ci = fmaf(yi, e.x, -(yr * e.y));
     return LinkBranch{cr, ci, fmaf(e.x, e.x, e.y * e.y)};
+}
+
+__device__ __forceinline__ LinkBranch link_branch(unsigned long long kf, float sigma, unsigned q, float xr, float xi, float2 h, float2 e) {
+    return link_branch_of(link_received(kf, sigma, q, xr, xi, h), e);
 }
 
 // The combiner's step: c += rho c_r, p += rho p_r, one fused multiply-add each, the product exact inside it

@@ -547,6 +547,54 @@ class LmmseSeqPlan(LmmsePlan):
                                      *conds, est, batch, _lib.current_stream_ptr(self.device))
 
 
+class LmmseGridPlan:
+    """The full-grid smoother (``lmmse.lmmse_grid_host`` is the definition) planned ONCE: the ``aft_lmmse`` struct with
+    ``noise_var = float32(noise_scale * sigma2)`` and the float32 grid image (``LmmseTables.grid().image()``) on the device.
+    ``plan(z, snr, ds, dop)`` -> ``est complex64 [batch,S,T]`` on the plan's device from the observations ``z complex64 [batch,S,T]``
+    (device memory): one ``torch.empty``, one ``ctypes`` call, one launch (``aft_lmmse_grid_f32``) on the current stream, no
+    synchronisation.  The three float32 conditions as ``LmmsePlan``'s.  A grid with more than 32 symbols is refused here, as by the
+    entry point.  The plan trusts its caller in one thing only: its device is the current one."""
+
+    def __init__(self, cfg, device: torch.device, assume=None, noise_scale: float = 1.0, image: Optional[torch.Tensor] = None) -> None:
+        from .lmmse import LmmseTables
+        self.device = _hip_device(device, "LmmseGridPlan", "lmmse.lmmse_grid_host")
+        self.tables = cfg if isinstance(cfg, LmmseTables) else LmmseTables(cfg)
+        grid = self.tables.grid()                               # refuses T > 32 with the message that says so
+        self.kf, self.noise_scale = grid.kf, float(noise_scale)
+        self.plan = grid.to_struct(assume, noise_scale)
+        self.fixed = (self.plan.fixed_snr, self.plan.fixed_ds, self.plan.fixed_dop)
+        self.grid = tuple(self.tables.cfg.ofdm)
+        S, T = self.grid
+        floats = self.plan.n_ds * (4 * S * self.kf + self.kf + (self.kf & 1)) + self.plan.n_dop * (2 * T * T + T)
+        if image is None:
+            image = torch.from_numpy(grid.image()).to(self.device)
+        if image.dtype != torch.float32 or image.device != self.device or not image.is_contiguous() or image.numel() != floats:
+            raise ValueError(f"the grid image must be {floats} contiguous float32 values on {self.device} (got {image.numel()} "
+                             f"{image.dtype} on {image.device})")
+        self.image = image
+
+    def __call__(self, z: torch.Tensor, snr=None, ds=None, dop=None, lib=None) -> torch.Tensor:
+        lib = lib or _lib.load()
+        if z.dim() != 3 or tuple(z.shape[1:]) != self.grid or z.shape[0] < 1:
+            raise ValueError(f"Expected observations of shape (B >= 1, {self.grid[0]}, {self.grid[1]}), got {tuple(z.shape)}")
+        if z.dtype != torch.complex64 or z.device != self.device:
+            raise ValueError(f"z must be complex64 on {self.device}, got {z.dtype} on {z.device}")
+        batch = z.shape[0]
+        z = z.contiguous()
+        conds = []
+        for name, c, fixed in zip(("snr", "ds", "dop"), (snr, ds, dop), self.fixed):
+            if c is None:
+                if fixed < 0:
+                    raise ValueError(f"{name} is required: assume does not pin it")
+                conds.append(None)
+                continue
+            conds.append(_in_place(name, c, torch.float32, self.device, batch))
+        est = torch.empty((batch, *self.grid), dtype=torch.complex64, device=self.device)   # the kernel writes every element
+        _lib.check(lib.aft_lmmse_grid_f32(C.byref(self.plan), self.kf, self.image.data_ptr(), z.data_ptr(), *[_ptr(c) for c in conds],
+                                          est.data_ptr(), batch, _lib.current_stream_ptr(self.device)), lib)
+        return est
+
+
 class LmmseClassifyPlan:
     """The design point from the pilots (``lmmse.lmmse_classify_host`` is the definition) planned ONCE: the ``aft_lmmse`` struct, the
     estimator's own float32 image (``seq_image()`` with a window, ``image()`` without) and the log-determinant table
@@ -729,6 +777,41 @@ class LinkMrcPlan(LinkPlan):
     def __call__(self, ideal: torch.Tensor, est: torch.Tensor, keys: torch.Tensor, sigma: torch.Tensor, rho: torch.Tensor,
                  scale: torch.Tensor, factors: torch.Tensor, want_llr: bool = False, lib=None):
         return self._grouped("aft_link_mrc_f32", ideal, est, keys, sigma, rho, [("scale", scale)], factors, want_llr, lib)
+
+
+class LinkObservePlan(LinkMrcPlan):
+    """The decision-directed observation on ``LinkMrcPlan``'s groups (``linksim.link_observe_host`` is the definition).
+    ``plan(ideal, est, keys, sigma, rho, pilots)`` -> ``(z complex64 [batch, S, T], decisions uint8 [G, S, T], symbol_errors int32
+    [G])`` on the plan's device: three ``torch.empty``, one ``ctypes`` call, one launch (``aft_link_observe_f32``) on the current
+    stream, no synchronisation.  ``pilots`` complex64 ``[batch, Ps, Pt]`` live on the plan's device; ``source``: ``"decided"`` or
+    ``"sent"``.  Everything else as ``LinkMrcPlan``."""
+    cpu_path = "linksim.link_observe_host"
+
+    def __init__(self, cfg, device: torch.device, branches: int = 1, source: str = "decided") -> None:
+        from .linksim import _source
+        super().__init__(cfg, device, branches)
+        self.source = _source(source)
+        self.pilot = tuple(cfg.sim.pilot)
+
+    def __call__(self, ideal: torch.Tensor, est: torch.Tensor, keys: torch.Tensor, sigma: torch.Tensor, rho: torch.Tensor,
+                 pilots: torch.Tensor, lib=None):
+        lib = lib or _lib.load()
+        batch, ideal, est, keys, sigma = self._checked(ideal, est, keys, sigma)
+        if batch % self.branches:
+            raise ValueError(f"a batch of {batch} frames is not a multiple of branches = {self.branches}")
+        groups = batch // self.branches
+        rho = _in_place("rho", rho, torch.float32, self.device, batch)
+        if tuple(pilots.shape) != (batch, *self.pilot) or pilots.dtype != torch.complex64 or pilots.device != self.device:
+            raise ValueError(f"pilots must be complex64 ({batch}, {self.pilot[0]}, {self.pilot[1]}) on {self.device}, got {pilots.dtype} "
+                             f"{tuple(pilots.shape)} on {pilots.device}")
+        pilots = pilots.contiguous()
+        z = torch.empty((batch, *self.grid), dtype=torch.complex64, device=self.device)          # the kernel writes every element
+        decisions = torch.empty((groups, *self.grid), dtype=torch.uint8, device=self.device)
+        errors = torch.empty((groups,), dtype=torch.int32, device=self.device)
+        _lib.check(lib.aft_link_observe_f32(C.byref(self.link), ideal.data_ptr(), est.data_ptr(), keys.data_ptr(), sigma.data_ptr(),
+                                            rho.data_ptr(), pilots.data_ptr(), self.source, self.branches, z.data_ptr(),
+                                            decisions.data_ptr(), errors.data_ptr(), batch, _lib.current_stream_ptr(self.device)), lib)
+        return z, decisions, errors
 
 
 class LinkSmPlan(LinkPlan):

@@ -454,6 +454,22 @@ and ``evaluation.get_link_harq`` are that surface::
 
 With Q = 1, C = nb, s_0 = 0 and the same stride this is the LDPC-coded link: column 0 is B less its block errors, columns 4, 5 and 6
 its bit errors, block errors and iterations, and the bits are equal bit for bit.
+
+The decision-directed observation.  Every estimator sees the pilots only; a receiver that has demodulated a frame can re-estimate the
+channel from its own decisions.  On the diversity link's groups (R frames, one transmission, the leader's key), with that link's y_r,
+c and p::
+
+    decision      (ki, kq), per axis the number of inner boundaries beta_b p at or below the component of c: the diversity link's own
+    x^            d (2 ki - (L - 1)) + j d (2 kq - (L - 1)); with source="sent" the sent x (the genie bound)
+    z_r[s, t]     y_r conj(x^) / |x^|^2 = H_r + (H_r (x - x^) + noise_r) conj(x^) / |x^|^2 at a data element: the channel plus noise of
+                  variance sigma_r^2 / |x^|^2 where the decision is right; frame r's own noisy pilot at a pilot position
+    decisions     uint8 [G, S, T], ki | kq << 4, and 255 at the pilots
+    symbol_errors int64 [G], the data elements whose (ki, kq) differ from the sent level indices
+
+``link_observe_host`` is the float64 twin, ``aft_link_observe_f32`` (csrc/k_linkobserve.hip, ``hip_ops.LinkObservePlan``) the device's
+one launch per batch.  ``data_noise_scale(m)``, the constellation's mean of 1 / |a|^2, is the factor the full-grid smoother
+(``lmmse.lmmse_grid_host``) puts on the noise variance; ``DataAidedRefiner`` is observe-then-smooth, iterated, and the ``refine=``
+keyword of the sweeps in ``evaluation`` runs it between the estimator and the accumulator.
 """
 from __future__ import annotations
 
@@ -771,6 +787,84 @@ def link_mrc_host(cfg: LinkConfig, keys, ideal, est, sigma, rho, scale, branches
     hard = _hard(cfg, gi, gq, c, p, reach, tau)
     soft = _soft(cfg, gi, gq, c, p, reach, scale, factors, e_lambda)
     return ((hard,) if tau is None else hard[:1]) + soft[:2] + (() if tau is None else hard[1:]) + soft[2:]
+
+
+# ---- the decision-directed observation (module docstring, "the decision-directed observation"), mirrored by csrc/k_linkobserve.hip ----
+
+OBSERVE_SOURCES = {"decided": _abi.AFT_LINK_OBSERVE_DECIDED, "sent": _abi.AFT_LINK_OBSERVE_SENT}
+# What the decision map reads at a pilot position.  At 8 bits per symbol ki = kq = 15 is a legal decision with the same byte: the
+# encoding is the interface's (ki | kq << 4, 255 at the pilots), so at m = 8 a reader tells the two apart by the pilot positions, as
+# link_observe_host(decisions=) does with the data mask.
+PILOT_DECISION = 255
+
+
+def data_noise_scale(m: int) -> float:
+    """The mean of ``1 / |a|^2`` over the unit-energy constellation of ``m`` bits per symbol: the factor by which dividing a received
+    sample by its symbol raises the noise variance, on average.  1 for QPSK, 17/9 for 16-QAM."""
+    return float(np.mean(1.0 / np.abs(constellation(m)) ** 2))
+
+
+def _source(source) -> int:
+    if not isinstance(source, str) or source not in OBSERVE_SOURCES:
+        raise ValueError(f'source = {source!r}: "decided" (the receiver\'s own hard decisions) or "sent" (the sent symbols: the genie bound)')
+    return OBSERVE_SOURCES[source]
+
+
+def link_observe_host(cfg: LinkConfig, keys, ideal, est, sigma, rho, pilots, branches: int = 1, source: str = "decided", decisions=None,
+                      tau: Optional[float] = None):
+    """The decision-directed observation (module docstring) in float64: ``keys`` / ``ideal`` / ``est`` / ``sigma`` / ``rho`` as
+    ``link_mrc_host``'s for the ``n`` frames, ``pilots`` complex ``[n, Ps, Pt]`` the frames' noisy pilots -> ``(z complex128 [n, S, T],
+    decisions uint8 [G, S, T], symbol_errors int64 [G])``, ``G = n / branches``.  The decision is the diversity link's own, on ``c = sum
+    rho_r y_r conj(E_r)`` and ``p = sum rho_r |E_r|^2``; the map holds ``ki | kq << 4`` and 255 at the pilots (at ``m = 8`` the byte 255 is also the legal decision ``ki = kq = 15``: the pilot
+    positions, not the byte, say which it is); ``symbol_errors`` counts the
+    data elements whose level indices differ from the sent ones.  ``z_r = y_r conj(x^) / |x^|^2`` at a data element with ``x^`` the
+    decided symbol -- the sent one with ``source="sent"`` (the map and the count stay the decided ones) -- and frame ``r``'s own pilot
+    at a pilot position.  ``decisions=`` takes a given map in the map's own encoding instead of deciding (what a decoder that
+    re-modulates would pass, and what a test passes to compare ``z`` on the device's own decisions); the map and the count returned
+    are then the given one's.  With ``tau`` the flags ``[G, S, T, 2]`` of ``link_mrc_host`` on the same ``c``, ``p`` and reach follow.
+    Needs no library."""
+    R = _branches(branches)
+    sent_source = _source(source) == OBSERVE_SOURCES["sent"]
+    keys, H, E, sigma = _checked(cfg, keys, ideal, est, sigma)
+    n, (S, T), (Ps, Pt) = len(keys), cfg.sim.ofdm, cfg.sim.pilot
+    G = _grouped(n, R)
+    rho = np.asarray(rho, dtype=np.float32).astype(np.float64).reshape(-1)
+    if rho.shape != (n,):
+        raise ValueError(f"rho must hold one value per frame ({n}), got {rho.size}")
+    pilots = np.asarray(pilots).astype(np.complex128)
+    if pilots.shape != (n, Ps, Pt):
+        raise ValueError(f"Expected pilots of shape ({n}, {Ps}, {Pt}), got {pilots.shape}")
+    L, d, mask = cfg.levels, cfg.d, cfg.data_mask
+    gi, gq, x = _sent(cfg, keys[::R])                                             # one transmission per group: the leader's key
+    y = np.empty((n, S, T), dtype=np.complex128)
+    c = p = reach = 0.0
+    for r in range(R):                                                           # in increasing r, starting from 0
+        noise = _noise(cfg, keys[r::R], sigma[r::R])
+        y[r::R] = H[r::R] * x + noise
+        E_r, w = E[r::R], rho[r::R, None, None]
+        c = c + w * (y[r::R] * E_r.conj())
+        p = p + w * (E_r.real ** 2 + E_r.imag ** 2)
+        reach = reach + w * ((np.abs(H[r::R]) * np.abs(x) + np.abs(noise)) * np.abs(E_r))
+    if decisions is None:
+        ki, kq = _levels(cfg, c.real, p), _levels(cfg, c.imag, p)
+    else:
+        given = np.asarray(decisions)
+        if given.shape != (G, S, T) or given.dtype != np.uint8:
+            raise ValueError(f"decisions must be uint8 [{G}, {S}, {T}] (ki | kq << 4, {PILOT_DECISION} at the pilots), got {given.dtype} "
+                             f"{given.shape}")
+        ki, kq = (given & 15).astype(np.int64), (given >> 4).astype(np.int64)
+        if (np.maximum(ki, kq)[:, mask] >= L).any():
+            raise ValueError(f"decisions holds a level index beyond the {L} levels of an axis at a data element")
+    out = np.where(mask[None], ki | (kq << 4), PILOT_DECISION).astype(np.uint8)
+    errors = (((ki != gray_level(gi)) | (kq != gray_level(gq))) & mask[None]).sum(axis=(1, 2)).astype(np.int64)
+    xh = x if sent_source else d * ((2 * ki - (L - 1)) + 1j * (2 * kq - (L - 1)))
+    xh = np.where(mask[None], xh, 1.0)                                            # a pilot position is not divided
+    z = y * np.repeat((xh.conj() / np.abs(xh) ** 2), R, axis=0)
+    sc, sym = np.asarray(cfg.sim.pilot_scs), np.asarray(cfg.sim.pilot_symbols)
+    z[:, sc[:, None], sym[None, :]] = pilots
+    if tau is None:
+        return z, out, errors
+    return z, out, errors, _hard(cfg, gi, gq, c, p, reach, tau)[2]
 
 
 MAX_STREAMS = _abi.AFT_LINK_MAX_STREAMS
@@ -1817,6 +1911,146 @@ class RateAccumulator(_FrameSweep):
     def result_gmi(self, group=None) -> float:
         """The best rate of the factor grid: the GMI's supremum over the LLR scale, taken on the grid."""
         return max(self.result(group))
+
+
+_REFINE_LINKS = ("refine= runs on the single-stream link -- one transmit antenna, branches=R receive antennas (get_link_stats, "
+                 "get_link_rates, get_link_bler and get_link_harq with branches=) --")
+
+
+class DataAidedRefiner(_FrameSweep):
+    """Decision-directed refinement of a channel estimate (module docstring, "the decision-directed observation"; ``lmmse``: "the
+    full-grid smoother"): a receiver that demodulates with ``est``, divides every received data sample by its own hard decision, and
+    re-estimates the channel from ALL grid positions.  ``refine(est, pilots, ideal, meta)`` -> ``est'`` complex64 like ``est``; each of
+    the ``iterations`` passes is observe (``link_observe_host`` / ``aft_link_observe_f32``) then smooth (``lmmse_grid_host`` /
+    ``aft_lmmse_grid_f32`` with ``noise_scale = data_noise_scale(m)``), and pass ``i + 1`` decides with pass ``i``'s estimate.  The
+    frames' keys and noise scales are the ones ``LinkAccumulator(link_cfg, device, seed, branches)`` forms from the same ``meta`` /
+    ``frame_ids`` / ``snr_db``, so the refiner sees the very received samples the accumulator then measures ``est'`` on; the design
+    point of the smoother is each frame's own ``meta`` (``assume`` pins conditions, as ``LmmseEstimator``'s).  ``branches=R``: the R
+    frames of a group are decided together, with the combiner weights ``branch_weights(snr_db, err_var, R)`` -- give the ``err_var`` of
+    the accumulator that measures the result (the coded ones take one), or the two combine with different weights --, and each is
+    re-estimated from its own samples.  ``source="sent"`` divides by the sent
+    symbols instead: the genie bound.  ``iterations=0`` returns ``est`` itself.  On a HIP device a pass is two launches on the current
+    stream and nothing synchronises (the group weights are formed once per batch by torch ops); on a CPU device the float64 twins
+    run.  ``symbol_error_rate()`` reads, once, the rate of wrong decisions of the LAST pass over everything refined so far."""
+
+    def __init__(self, link_cfg: LinkConfig, device, seed: int = 0, branches: int = 1, iterations: int = 1, source: str = "decided",
+                 assume=None, err_var: float = 0.0) -> None:
+        from .lmmse import LmmseTables, _check_assume
+        if not isinstance(link_cfg, LinkConfig):
+            raise ValueError(f"DataAidedRefiner needs a LinkConfig (got {type(link_cfg).__name__})")
+        if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or iterations < 0:
+            raise ValueError(f"iterations = {iterations!r}: an integer, at least 0")
+        self.cfg, self.seed, self.branches, self.iterations = link_cfg, int(seed), _branches(branches), int(iterations)
+        self.source = source
+        _source(source)
+        self.assume = _check_assume(assume)
+        self.tables = LmmseTables(link_cfg.sim)
+        self.tables.grid()                                      # refuses a grid the smoother does not cover, here and not mid-sweep
+        self.noise_scale = data_noise_scale(link_cfg.bits_per_symbol)
+        self.device = torch.device(device)
+        self._plan = self._smooth = None
+        if self.device.type == "cuda":
+            from . import hip_ops                               # loads the extension: a missing .so raises here, loudly
+            self._plan = hip_ops.LinkObservePlan(link_cfg, self.device, self.branches, source)
+            self.device = self._plan.device
+            self._smooth = hip_ops.LmmseGridPlan(self.tables, self.device, assume=self.assume, noise_scale=self.noise_scale)
+        self.err_var = float(err_var)
+        if not self.err_var >= 0.0:
+            raise ValueError(f"err_var = {err_var!r}: a variance, at least 0")
+        self._of_snr = (_SIGMA_OF_SNR, _SCALE_OF_SNR(self.err_var))
+        self.errors = torch.zeros((), dtype=torch.int64, device=self.device)     # wrong decisions of the last pass, summed on the device
+        self.groups = 0
+
+    def _conditions(self, meta, snr_db, b):
+        """The smoother's per-frame conditions: None where ``assume`` pins, else ``meta``'s (``snr_db=`` overrides the SNR)."""
+        fixed = self.tables.fixed(self.assume)
+        given = [snr_db if snr_db is not None else (None if meta is None else meta[1])] + \
+                [None if meta is None else meta[k] for k in (2, 3)]
+        out = []
+        for name, v, f in zip(("snr_db", "delay_spread_ns", "doppler_hz"), given, fixed):
+            if f >= 0:
+                out.append(None)
+                continue
+            if v is None:
+                raise ValueError(f"the smoother needs each frame's {name}: meta, or assume= to pin it")
+            v = v if torch.is_tensor(v) else torch.as_tensor(np.asarray(v, dtype=np.float32))
+            v = v.reshape(-1).to(torch.float32)
+            if v.numel() == 1:
+                v = v.expand(b)
+            if v.numel() != b:
+                raise ValueError(f"one {name} per frame ({b}), got {v.numel()}")
+            out.append(v.contiguous())
+        return out
+
+    def refine(self, est: torch.Tensor, pilots: torch.Tensor, ideal: torch.Tensor, meta: Optional[tuple] = None, *, frame_ids=None,
+               snr_db=None) -> torch.Tensor:
+        if est is None:
+            raise ValueError("refine needs an estimate to start from: est=None is perfect channel knowledge, which nothing refines")
+        Ps, Pt = self.cfg.sim.pilot
+        if pilots.dim() != 3 or tuple(pilots.shape[1:]) != (Ps, Pt) or pilots.shape[0] != ideal.shape[0] or pilots.dtype != torch.complex64:
+            raise ValueError(f"pilots must be complex64 [{ideal.shape[0]}, {Ps}, {Pt}], got {pilots.dtype} {tuple(pilots.shape)}")
+        if self.iterations == 0:
+            return est
+        ops = self._operands(est, ideal, meta, frame_ids, snr_db, self._of_snr)
+        if ops is None:
+            return est
+        b, H, E, keys, (sigma, scale) = ops
+        G = _grouped(b, self.branches)
+        conds = self._conditions(meta, snr_db, b)
+        if self._plan is None:
+            from .lmmse import lmmse_grid_host                  # lmmse imports nothing from this module at load time
+            rho = _weights(scale, self.branches)[0]
+            cond = np.zeros((b, 3))
+            for k, c in enumerate(conds):
+                if c is not None:
+                    cond[:, k] = c.detach().cpu().double().numpy()
+            P = pilots.detach().cpu().numpy()
+            for _ in range(self.iterations):
+                z, _, errors = link_observe_host(self.cfg, keys, H, E, sigma, rho, P, self.branches, self.source)
+                E = lmmse_grid_host(self.tables, z, cond, self.assume, self.noise_scale).astype(np.complex64)
+            self.errors += int(errors.sum())
+            self.groups += G
+            return torch.from_numpy(E)
+        rho = self._device_weights(scale, self.branches)[0]
+        P = pilots.to(self.device).contiguous()
+        conds = [None if c is None else (c.pin_memory() if c.device.type == "cpu" else c).to(self.device, non_blocking=True) for c in conds]
+        for _ in range(self.iterations):
+            z, _, errors = self._launch(H, E, keys, sigma, rho, P)
+            E = self._launch(z, *conds, plan=self._smooth)
+        self.errors += errors.sum(dtype=torch.int64)
+        self.groups += G
+        return E
+
+    def symbol_error_rate(self, group=None) -> float:
+        """The share of data elements the LAST pass decided wrongly, over everything refined so far and all ranks; one read."""
+        sent = torch.tensor(float(self.groups * self.cfg.data_elements), dtype=torch.float64, device=self.device)
+        errors, sent = self._all_ranks(torch.stack([self.errors.to(torch.float64), sent]), group)
+        return errors / sent if sent > 0 else 0.0
+
+
+def as_refiner(refine, link_cfg: LinkConfig, device, seed: int = 0, branches: int = 1, streams: int = 1,
+               tx_diversity: Optional[str] = None, precoding_subband: Optional[int] = None,
+               err_var: float = 0.0) -> Optional[DataAidedRefiner]:
+    """What the sweeps' ``refine=`` means: None -> None; an iteration count -> ``DataAidedRefiner(link_cfg, device, seed, branches,
+    iterations, err_var=err_var)``; a ``DataAidedRefiner`` -> itself, provided it was built for this link, seed, branches and -- with
+    several branches, where it sets the combiner's weights -- ``err_var``.  Two streams, transmit
+    diversity and precoding are refused: their received samples mix two channels, which this observation does not separate."""
+    if refine is None:
+        return None
+    if streams != 1 or tx_diversity is not None or precoding_subband is not None:
+        raise ValueError(f"{_REFINE_LINKS} not with streams = {streams!r}, tx_diversity = {tx_diversity!r}, precoding_subband = "
+                         f"{precoding_subband!r}: a received sample there mixes two channels")
+    if isinstance(refine, DataAidedRefiner):
+        if refine.cfg != link_cfg or refine.seed != int(seed) or refine.branches != branches or \
+                (branches > 1 and refine.err_var != float(err_var)):
+            raise ValueError("the refiner was built for another link, seed, number of branches or err_var than the sweep it is given to: it "
+                             "would refine on other received samples, or combine them with other weights, than the sweep measures")
+        return refine
+    if isinstance(refine, bool) or not isinstance(refine, (int, np.integer)) or refine < 0:
+        raise ValueError(f"refine = {refine!r}: None, an iteration count (0, 1, 2, ...) or a DataAidedRefiner")
+    if device is None:                                          # asked for the checks alone
+        return None
+    return DataAidedRefiner(link_cfg, device, seed, branches, int(refine), err_var=err_var)
 
 
 # ---- the coded link (module docstring, "the coded link"): integer NumPy, mirrored by csrc/k_linkcode.hip ----

@@ -60,6 +60,21 @@ reads the estimator's own image and ONE more table, ``LmmseTables.classify_image
 (the device takes no logarithm).  ``ConditionEstimator`` is the module, ``LmmseEstimator(conditions="estimated")`` the blind baseline
 (classify, then estimate: two launches, the conditions never leave the device), ``EstimatedConditions`` wraps any estimator with the
 ``forward(pilot_symbols, meta_data)`` signature and hands it estimated conditions in place of the loader's.
+
+The full-grid smoother.  A receiver that has demodulated a frame holds an observation of the channel at EVERY grid position
+(``linksim.link_observe_host``: the received sample divided by the decided symbol at a data element, the noisy pilot at a pilot).  The
+best linear estimate from all of them is the form above with "every grid position is a pilot"::
+
+    R_f = r_f(s - s') = U_g diag(lam_g) U_g^H   over all S subcarriers; the Kf = min(S, taps) largest eigenpairs, descending
+    R_t = r_t(t - t') = U_tg diag(lam_tg) U_tg^T over all T symbols
+    est = F_g [ D o (U_g^H Z U_tg) ] T_g^T,   F_g = U_g diag(lam_g),  T_g = U_tg diag(lam_tg),  D = 1 / (lam_g lam_tg + beta sigma2)
+
+``R_f`` is a sum of one rank-one term per tap, so with ``Kf = min(S, taps)`` nothing is dropped (the largest dropped eigenvalue is
+1e-14).  ``beta sigma2`` is ONE noise variance for the whole grid -- the simplification that keeps the estimator Kronecker-separable.
+``LmmseTables.grid()`` builds the tables when first asked (``image()``, ``seq_image()`` and ``classify_image()`` do not change),
+``lmmse_grid_host`` is the float64 twin, ``lmmse_grid_predicted_mse`` the exact MSE with the sent symbols known,
+``aft_lmmse_grid_f32`` (csrc/k_lmmse.hip, through ``hip_ops.LmmseGridPlan``) the device's one launch per batch, and
+``linksim.DataAidedRefiner`` the receiver loop that uses it.  ``T`` is at most 32 here.
 """
 from __future__ import annotations
 
@@ -189,9 +204,18 @@ class LmmseTables:
                 self.u_t_w.append(us)
                 self.t_w.append(ts)
 
+        self._grid = None                                        # the full-grid tables, built when first asked for
+
     @property
     def multi_slot(self) -> bool:
         return self.window > 1 or self.horizon > 0
+
+    def grid(self) -> "GridTables":
+        """The full-grid smoother's tables (module docstring, "the full-grid smoother"), built on first use and kept: ``image()``,
+        ``seq_image()`` and ``classify_image()`` do not see them."""
+        if self._grid is None:
+            self._grid = GridTables(self)
+        return self._grid
 
     def window_symbols(self, w: int) -> np.ndarray:
         """The ``w Pt`` pilot symbols of a window of ``w`` slots that ends ``horizon`` slots before the target slot, relative to the
@@ -292,6 +316,116 @@ class LmmseTables:
 
 def _tables(cfg: Union[ChannelSimConfig, LmmseTables]) -> LmmseTables:
     return cfg if isinstance(cfg, LmmseTables) else LmmseTables(cfg)
+
+
+MAX_GRID_SYMBOLS = _abi.AFT_LMMSE_MAX_WINDOW_PILOTS              # symbols the full-grid smoother filters at once
+
+
+class GridTables:
+    """The full-grid smoother's tables for the config of ``tables`` (module docstring, "the full-grid smoother"; ``LmmseTables.grid()``
+    builds them once): float64, per delay spread ``lam_g [Kf]`` (descending, clamped at 0) and ``u_g [S, Kf]``, the ``Kf = min(S, taps)``
+    largest eigenpairs of ``r_f`` over all ``S`` subcarriers; per Doppler ``lam_tg [T]`` and ``u_tg [T, T]`` of ``r_t`` over all ``T``
+    symbols.  ``image()`` is the float32 array ``aft_lmmse_grid_f32`` reads (include/adafortitran_amd.h documents its layout)."""
+
+    def __init__(self, tables: LmmseTables) -> None:
+        S, T = tables.cfg.ofdm
+        if T > MAX_GRID_SYMBOLS:
+            raise ValueError(f"ofdm grid {S} x {T}: the full-grid smoother filters all T symbols of a frame at once and holds at most "
+                             f"{MAX_GRID_SYMBOLS} of them (T > {MAX_GRID_SYMBOLS} is out of its scope); the pilot estimator "
+                             f"LmmseEstimator takes any T")
+        self.tables = tables
+        self.kf = Kf = min(S, len(tables.pw))
+        s, t = np.arange(S), np.arange(T)
+        self.lam_g, self.u_g = [], []
+        for i in range(len(tables.delay_turns)):
+            lam, u = np.linalg.eigh(tables.r_f(s[:, None] - s[None, :], i))
+            self.lam_g.append(np.maximum(lam[::-1][:Kf], 0.0))
+            self.u_g.append(np.ascontiguousarray(u[:, ::-1][:, :Kf]))
+        self.lam_tg, self.u_tg = [], []
+        for i in range(len(tables.doppler_turns)):
+            lam, u = np.linalg.eigh(tables.r_t(t[:, None] - t[None, :], i))
+            self.lam_tg.append(np.maximum(lam, 0.0))
+            self.u_tg.append(u)
+
+    def noise(self, noise_scale: float = 1.0) -> np.ndarray:
+        """``noise_scale * sigma2`` per SNR value, float64 ``[n_snr]``."""
+        beta = float(noise_scale)
+        if not (np.isfinite(beta) and beta > 0.0):
+            raise ValueError(f"noise_scale = {noise_scale!r}: a finite positive factor on the noise variance")
+        return beta * self.tables.sigma2
+
+    def gain(self, i_snr: int, i_ds: int, i_dop: int, noise_scale: float = 1.0) -> np.ndarray:
+        """D [Kf, T] of a design point."""
+        return 1.0 / (self.lam_g[i_ds][:, None] * self.lam_tg[i_dop][None, :] + self.noise(noise_scale)[i_snr])
+
+    def image(self) -> np.ndarray:
+        pairs = lambda z: np.stack([z.real, z.imag], axis=-1).reshape(-1)  # noqa: E731
+        parts = []
+        for lam, u in zip(self.lam_g, self.u_g):
+            parts += [pairs(u.conj()), pairs((u * lam[None, :]).T), lam, np.zeros(self.kf & 1)]
+        for lam, u in zip(self.lam_tg, self.u_tg):
+            parts += [u.reshape(-1), (u * lam[None, :]).T.reshape(-1), lam]
+        return np.concatenate(parts).astype(np.float32)
+
+    def to_struct(self, assume=None, noise_scale: float = 1.0) -> "_abi.AftLmmse":
+        """The estimator's struct with ``noise_var[i] = float32(noise_scale * sigma2[i])``: formed in double, rounded once."""
+        p = self.tables.to_struct(assume)
+        for i, v in enumerate(self.noise(noise_scale).astype(np.float32)):
+            p.noise_var[i] = float(v)
+        return p
+
+
+def lmmse_grid_host(tables: Union[ChannelSimConfig, LmmseTables], z, conditions, assume=None, noise_scale: float = 1.0) -> np.ndarray:
+    """The full-grid smoother in float64 (module docstring, "the full-grid smoother"): observations ``z [n, S, T]`` of every grid
+    position and conditions ``[n, 3]`` -> complex128 ``[n, S, T]``, ``est = F_g [ D o (U_g^H Z U_tg) ] T_g^T`` with ``D = 1 / (lam_g
+    lam_tg + noise_scale sigma2[i_snr])``.  THE SIMPLIFICATION: one noise variance ``noise_scale * sigma2`` for the whole grid,
+    although a decision-directed observation carries ``sigma2`` at a pilot and ``sigma2 / |x|^2`` at a data element
+    (``linksim.data_noise_scale(m)`` is the data elements' average factor); the estimator stays linear and Kronecker-separable, and
+    ``lmmse_grid_predicted_mse`` says what that costs.  The design point is ``indices()``'s, as everywhere.  Needs no library."""
+    tb = _tables(tables)
+    g = tb.grid()
+    z = np.asarray(z).astype(np.complex128)
+    if z.ndim != 3 or z.shape[1:] != tuple(tb.cfg.ofdm):
+        raise ValueError(f"Expected observations of shape (n, {tb.cfg.ofdm[0]}, {tb.cfg.ofdm[1]}), got {z.shape}")
+    if conditions is None:
+        if min(tb.fixed(assume)) < 0:
+            raise ValueError("conditions are required unless assume pins all three")
+        conditions = np.zeros((len(z), 3))
+    i_snr, i_ds, i_dop = tb.indices(conditions, assume)
+    if len(i_snr) != len(z):
+        raise ValueError(f"{len(z)} frames but {len(i_snr)} rows of conditions")
+    out = np.empty(z.shape, dtype=np.complex128)
+    key = i_snr * 1024 + i_ds * 32 + i_dop
+    for k in np.unique(key):
+        sel = np.nonzero(key == k)[0]
+        a, d, e = int(i_snr[sel[0]]), int(i_ds[sel[0]]), int(i_dop[sel[0]])
+        y = np.einsum("sk,nst,tl->nkl", g.u_g[d].conj(), z[sel], g.u_tg[e]) * g.gain(a, d, e, noise_scale)[None]
+        out[sel] = np.einsum("sk,nkl,tl->nst", g.u_g[d] * g.lam_g[d][None, :], y, g.u_tg[e] * g.lam_tg[e][None, :])
+    return out
+
+
+def lmmse_grid_predicted_mse(tables: Union[ChannelSimConfig, LmmseTables], snr_db: float, delay_spread_ns: float, doppler_hz: float,
+                             m: int) -> float:
+    """The exact MSE per grid element of ``lmmse_grid_host(noise_scale=data_noise_scale(m))`` on the observations of
+    ``linksim.link_observe_host(source="sent")`` with ``m`` bits per symbol, at the given condition (its nearest table values).  The
+    estimator is ``W = Q diag(g) Q^H`` with ``Q = U_g (x) U_tg`` and ``g_kl = lam_kl / (lam_kl + beta sigma2)``; the channel's
+    covariance is ``Q diag(lam) Q^H`` and the noise is independent with a DIAGONAL covariance, ``n_i = sigma2`` at a pilot and
+    ``beta sigma2`` on average at a data element (``beta = data_noise_scale(m)``, the mean of ``1 / |x|^2``), so
+    ``MSE = (1 / ST) [ sum_kl lam_kl (1 - g_kl)^2 + sum_i n_i |W[:, i]|^2 ]`` and the noise term separates over the Kronecker factors:
+    ``sum_i n_i |W[:, i]|^2 = beta sigma2 sum_kl g_kl^2 - (beta - 1) sigma2 sum_kl g_kl^2 A_k B_l`` with ``A_k = sum_{s in sc}
+    |U_g[s, k]|^2`` and ``B_l = sum_{t in sym} U_tg[t, l]^2`` the eigenvectors' mass at the pilot rows and columns."""
+    from .linksim import data_noise_scale
+    tb = _tables(tables)
+    g = tb.grid()
+    a, d, e = (int(v[0]) for v in tb.indices([[snr_db, delay_spread_ns, doppler_hz]]))
+    beta, s2 = data_noise_scale(m), float(tb.sigma2[a])
+    S, T = tb.cfg.ofdm
+    lam = g.lam_g[d][:, None] * g.lam_tg[e][None, :]
+    gain = lam / (lam + beta * s2)
+    at_sc = (np.abs(g.u_g[d][tb.sc]) ** 2).sum(axis=0)
+    at_sym = (g.u_tg[e][tb.sym] ** 2).sum(axis=0)
+    noise = beta * s2 * (gain ** 2).sum() - (beta - 1.0) * s2 * float(at_sc @ (gain ** 2) @ at_sym)
+    return float(((lam * (1.0 - gain) ** 2).sum() + noise) / (S * T))
 
 
 def lmmse_estimate_host(cfg: Union[ChannelSimConfig, LmmseTables], pilots, conditions, assume=None) -> np.ndarray:

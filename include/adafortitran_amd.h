@@ -421,6 +421,32 @@ size_t aft_lmmse_seq_table_floats(const aft_lmmse *plan, int window);
 int aft_lmmse_seq_f32(const aft_lmmse *plan, int group, int slots, int window, int horizon, const float *tables, const float *pilots,
                       const float *snr, const float *ds, const float *dop, float *est, int batch, void *stream);
 
+/* The full-grid smoother (lmmse.py "the full-grid smoother"): the same estimator with EVERY grid position an observation -- what a
+ * receiver that re-estimates the channel from its own decisions runs on aft_link_observe_f32's z.  With r_f over all S subcarriers and
+ * r_t over all T symbols,
+ *   R_f = U_g diag(lg) U_g^H, of which the kf = min(S, taps) largest eigenpairs are kept, descending (R_f has rank at most the number
+ *         of taps: nothing is lost),   F_g = U_g diag(lg)  [S, kf]
+ *   R_t = U_tg diag(ltg) U_tg^T  [T, T],   T_g = U_tg diag(ltg)
+ *   est = F_g [ D o (U_g^H Z U_tg) ] T_g^T,    D[k][l] = 1 / (lg[k] ltg[l] + noise_var),    Z the frame's [S, T] observations,
+ * one noise variance for the whole grid: the caller puts beta 10^(-snr_db[i] / 10) into noise_var[i], beta its average over pilot and
+ * data positions (formed in double, rounded once).  The image, float32:
+ *   per delay spread i (n_ds blocks of 4 S kf + kf + (kf & 1) floats):
+ *     U_g^H  complex [S(s)][kf(k)]    (s-major: entry (s, k) = conj(U_g[s][k]); the rows a workgroup streams are one contiguous run)
+ *     F_g    complex [kf(k)][S]       (k-major, as F')
+ *     lg     real    [kf]             (one float of padding when kf is odd)
+ *   then per Doppler i (n_dop blocks of 2 T T + T floats):
+ *     U_tg   real    [T(j)][T(l)],    T_g^T  real  [T(l)][T],    ltg  real  [T]
+ * The design point is chosen as aft_lmmse_f32 chooses it; pilot_scs / pilot_symbols of `plan` are checked and otherwise unused.
+ * One launch, one workgroup per frame: est complex64 [batch, S, T] from z complex64 [batch, S, T] (both device memory; z is read
+ * once, in chunks of 32 rows) and the float32 [batch] conditions (any device-addressable memory; NULL where fixed_* pins).  The first
+ * product is an S-deep chain of fused multiply-adds in increasing s from +0; from there on the arithmetic is aft_lmmse_f32's own code
+ * with (Ps, Pt) = (kf, T).  Every output element is written; no atomics, no workspace; nothing is synchronised; a frame's bits do not
+ * depend on batch or on its position in it; stores as aft_lmmse_f32's.  28 KB of static LDS, any S.
+ * Nothing is launched on AFT_ERR_ARG (aft_lmmse_f32's, with z for pilots) and AFT_ERR_SHAPE (aft_lmmse_f32's; num_symbols above
+ * AFT_LMMSE_MAX_WINDOW_PILOTS: all T symbols are filtered at once; kf outside 1 .. min(S, AFT_CHANSIM_MAX_TAPS)). */
+int aft_lmmse_grid_f32(const aft_lmmse *plan, int kf, const float *tables, const float *z, const float *snr, const float *ds,
+                       const float *dop, float *est, int batch, void *stream);
+
 /* Choosing the design point from the pilots (lmmse.py "choosing the design point from the pilots"): a maximum-likelihood classification
  * of a window's pilots over the table's candidates c = (s, d, e) = (i_snr, i_ds, i_dop), in the estimator's own eigenbasis.  The batch is
  * whole sequences as for aft_lmmse_seq_f32, and target frame (seq, k, a) looks at exactly the window that call estimates it from:
@@ -897,6 +923,32 @@ int aft_link_ldpc_masked_f32(const aft_link *link, const float *llr /* [batch,S,
                              unsigned long long stride, unsigned long long stride_inverse, float qgain, int offset, int max_iters,
                              const int32_t *mask /* [(batch - 1) * mask_stride + 1] */, int mask_stride,
                              int32_t *counts /* [batch][3] */, unsigned char *bits /* [batch,B,K] or NULL */, int batch, void *stream);
+
+/* ---- decision-directed observation: what the receiver's own decisions say about the channel (adafortitran_amd/linksim.py "the
+ * decision-directed observation") ----
+ *
+ * The diversity link's groups, keys, received samples and combiner, unchanged: y_r, c and p as aft_link_mrc_f32's, so the hard decision
+ * k_i, k_q (per axis the number of inner boundaries beta_b p at or below the component of c) is that entry point's, bit for bit.
+ *   x^          = d (2 k_i - (L - 1)) + j d (2 k_q - (L - 1)), the decided symbol; with source = AFT_LINK_OBSERVE_SENT the sent x
+ *                 (the genie bound: what a decoder that got every bit right would re-modulate)
+ *   z_r         = y_r conj(x^) / |x^|^2 at a data element, for each of the group's R frames: |x^|^2 = fma(ar, ar, ai ai), each
+ *                 component one product, one fused multiply-add and one correctly rounded division;
+ *                 frame r's own pilot, bit for bit, at pilot position (sc_i, sym_j)
+ *   decisions   uint8 [batch / branches, S, T]: k_i | k_q << 4 at a data element (the DECIDED indices, whatever `source`), 255 at a pilot
+ *   symbol_errors int32 [batch / branches]: the data elements whose decided (k_i, k_q) is not the sent one
+ * One launch, one workgroup per group: z complex64 [batch, S, T] from ideal and est complex64 [batch, S, T] and pilots complex64
+ * [batch, Ps, Pt] (device memory), keys uint64 [batch], sigma and rho float32 [batch] (any device-addressable memory).  Every element
+ * of the three outputs is written exactly once; no atomics, no workspace; nothing is synchronised; a group's outputs depend neither on
+ * batch, nor on its position in it, nor on the run, nor on the load and store forms (16 bytes per pair when T is even and the plane's
+ * base is 16-byte aligned, 8 bytes per element otherwise).
+ * Nothing is launched on AFT_ERR_ARG (a NULL pointer; ideal, est, keys, pilots or z not 8-byte, sigma, rho or symbol_errors not 4-byte
+ * aligned; batch < 1 or not a multiple of branches; source neither constant) and AFT_ERR_SHAPE (what aft_link_mrc_f32 refuses). */
+#define AFT_LINK_OBSERVE_DECIDED 0
+#define AFT_LINK_OBSERVE_SENT 1
+int aft_link_observe_f32(const aft_link *link, const float *ideal, const float *est, const unsigned long long *keys,
+                         const float *sigma, const float *rho, const float *pilots /* [batch,Ps,Pt] */, int source, int branches,
+                         float *z /* [batch,S,T] */, unsigned char *decisions /* [groups,S,T] */, int32_t *symbol_errors /* [groups] */,
+                         int batch, void *stream);
 
 /* ---- training path of the encoder ---- */
 
